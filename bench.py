@@ -4,17 +4,27 @@
 One "step" = one pass of the hot path (query preparation + SBQ quantisation, streaming beam search with Hamming
 scoring, f32 rerank, rescore window) over one batch of `--nq` synthetic queries that already sit in HBM.
 
-  python bench.py                       # 1 GPU, default workload: 50M x 768, L2, SBQ 2 bit + rerank (the configuration the
-                                        # metric of BASELINE.json is quoted on; 177 GB index on ONE GPU; ~7 min, 6 of them
-                                        # the on-device index build)
-  python bench.py --n 10000000 --distance cosine   # configs[2] (~1.5 min);   --n 1000000: configs[1] (~20 s)
+  python bench.py                       # 1 GPU, the headline value only, on a 4M x 768 index (L2, SBQ 2 bit + rerank) that is
+                                        # built on the device in seconds: set-up, warm-up, timed steps, the line
+  python bench.py --full                # 50M x 768 (the configuration the metric of BASELINE.json is quoted on; 177 GB index
+                                        # on ONE GPU; ~8 min, 3 of them the on-device index build) with everything else the
+                                        # script measures: CPU baseline, flat-scan roofline, PCIe leg, extras
+  python bench.py --n 50000000          # the headline value alone at 50M
+  python bench.py --full --n 10000000 --distance cosine   # configs[2] (~1.5 min);   --n 1000000: configs[1] (~20 s)
   python bench.py --n 20000000 --dim 1536 --distance cosine --labels 32   # configs[4]: label-filtered scans
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W   # index replicated per GPU, queries sharded, RCCL all_gather of top-k
 
 Prints ONE JSON line (rank 0).  Setup (corpus generation, SBQ training, quantisation, graph build, ground truth,
-recall sweep) is outside the timed region; the CPU baseline runs the oracle (a port of the reference path) on a
-bounded sample of the same queries on the host cores.
+recall sweep) is outside the timed region.
+
+A plain run does what the headline value needs and nothing else: set-up, warm-up, the timed steps, the recall check of
+the rows the last timed step produced, the line.  Everything else the script can measure — the CPU baseline (the oracle,
+a port of the reference path, on a bounded sample of the same queries on the host cores) with its closing row-identity
+check, the flat SBQ scan roofline, the PCIe-inclusive leg and the extras (default GUCs, cursor pools, latency, the
+harder corpus) — runs only with --full.  The 50M index takes three minutes to build, so it is the default corpus of a
+--full run only; a plain run defaults to 4M vectors of the same generator (`config.n` in the line says which).
+--dump-outputs DIR writes the rows of the last timed step as .npy files.
 """
 import argparse
 import ctypes as C
@@ -76,6 +86,14 @@ def graph_cache_path(args, n, dim, seed, bits, R):
     except OSError:
         return None
     return path
+
+
+def sample_rows(np, rows, row_bytes, budget):
+    """row numbers to dump: all of them when they fit `budget` bytes, else a fixed (seed 0) sorted sample that does"""
+    keep = max(1, budget // max(row_bytes, 1))
+    if rows <= keep:
+        return np.arange(rows)
+    return np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
 
 
 def kernel_source_hash():
@@ -248,15 +266,25 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--n", "--corpus", dest="n", type=int, default=50_000_000,
-                    help="corpus size (BASELINE configs: 1M / 10M / 50M); the default is the configuration BASELINE.json quotes "
+    ap.add_argument("--n", "--corpus", dest="n", type=int, default=None,
+                    help="corpus size (BASELINE configs: 1M / 10M / 50M).  Default with --full: the configuration BASELINE.json quotes "
                          "its metric on (50M x 768, L2): the whole index (177 GB) fits one MI355X; the on-device build takes "
-                         "about 6 minutes of the run.  --n 10000000 --distance cosine is configs[2], --n 1000000 configs[1]")
+                         "about 3 minutes of the run.  Default of a plain run: 4M, built in seconds.  --n 10000000 --distance cosine "
+                         "is configs[2], --n 1000000 configs[1]")
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--nq", type=int, default=262144, help="queries per step per GPU (scans of one launch; a launch ends with a tail of "
                     "its last scans on a half-empty chip, which large batches amortise: 168.3 ms per 262144 scans against 2 x 88.2 ms per "
                     "131072 at 50M, profiles/r03/ab_nq262144_50m.txt)")
-    ap.add_argument("--scan-nq", type=int, default=64, help="queries of the flat SBQ scan (K5) roofline measurement, 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything that is not needed for the headline value: the CPU baseline with its row-identity check "
+                         "(unless --skip-cpu), the flat SBQ scan roofline (--scan-nq), the PCIe-inclusive leg (--pcie-steps) and the extras "
+                         "(--extras), on the 50M corpus unless --n says otherwise.  Off by default: a plain run sets up, warms up, times "
+                         "the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned (rank 0's rows) to DIR/ids.npy (float64, [rows][k] "
+                         "node ids) and DIR/distances.npy (float32, [rows][k]); at most 64 MB in all — of a larger block a fixed seeded "
+                         "sample of the rows, their numbers in DIR/rows.npy (float64)")
+    ap.add_argument("--scan-nq", type=int, default=64, help="with --full: queries of the flat SBQ scan (K5) roofline measurement, 0 = skip")
     ap.add_argument("--distance", default="l2", choices=["l2", "cosine", "ip"])
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--recall-target", type=float, default=0.99)
@@ -266,7 +294,7 @@ def main():
                          "point is accepted only when the LOWER 95 %% confidence bound of recall@k on it reaches the target")
     ap.add_argument("--build-l", type=int, default=100)
     ap.add_argument("--fixed", default=None, help="L,rescore to use instead of the recall sweep")
-    ap.add_argument("--skip-cpu", action="store_true")
+    ap.add_argument("--skip-cpu", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--pipeline", type=int, default=1, choices=[1, 2],
                     help="batches in flight: 2 = the steps alternate between two views of the index (two streams), so the rerank of "
                          "a step runs under the search of the next one; the kernel times of the roofline then come from the "
@@ -299,7 +327,7 @@ def main():
     ap.add_argument("--noise-pct", type=int, default=-1, help="override the isotropic noise share (0..100)")
     ap.add_argument("--intra-pct", type=int, default=-1, help="override the within-cluster spread (0..100)")
     ap.add_argument("--pcie-steps", type=int, default=2,
-                    help="steps of the PCIe-inclusive leg (queries start in pageable host memory, rows end there: vs_search_batch); "
+                    help="with --full: steps of the PCIe-inclusive leg (queries start in pageable host memory, rows end there: vs_search_batch); "
                          "reported next to the value, never as the value; 0 = skip")
     ap.add_argument("--autotune", default="off", choices=["on", "off"],
                     help="off (default): the library's default launch variant — the one the committed rocprofv3 / PMC summaries under profiles/ "
@@ -309,7 +337,7 @@ def main():
                          "a child-process probe of the variants on a small index under a timeout (pgvectorscale_amd/tune_probe.py); the "
                          "line reports every candidate's time under `autotune`")
     ap.add_argument("--extras", default="auto", choices=["auto", "on", "off"],
-                    help="three more objects in the JSON line, outside the headline value (N = 1 only): `cursor_pool` — 32 backend processes streaming "
+                    help="with --full: three more objects in the JSON line, outside the headline value (N = 1 only): `cursor_pool` — 32 backend processes streaming "
                          "320 rows each through the shared-memory server, a cursor per scan against scan pools; `default_gucs` — the same index at the "
                          "reference's default GUCs (diskann.query_search_list_size = 100, diskann.query_rescore = 50, AM/guc.rs:3-4): QPS, "
                          "recall@k with its lower 95 %% bound, kernel fraction — and `harder_corpus` — a child run of this script on 10M vectors "
@@ -323,6 +351,8 @@ def main():
                          "--offload-arch=gfx950), before anything is loaded; the line's `library` object says how long it took and "
                          "with which hipcc.  Off by default: the library travels prebuilt and the full build takes minutes of host time")
     args = ap.parse_args()
+    if args.n is None:
+        args.n = 50_000_000 if args.full else 4_000_000
 
     rebuilt = None
     if args.rebuild and int(os.environ.get("RANK", "0")) == 0 and not EMU:
@@ -830,6 +860,15 @@ def main():
         sweep_log.append(("retimed", L, S, round(val["recall"], 4), round(val["lower95"], 4)))
     qps = world * nq * K / elapsed
     recall_heldout = None if hs is None else hs["recall"]
+    if args.dump_outputs and rank == 0:  # what a caller of the timed path received from its last step
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        ids_h = last_ids.cpu().numpy().view(np.uint32)
+        dist_h = last_dist.cpu().numpy()
+        keep = sample_rows(np, ids_h.shape[0], k * (8 + 4) + 8, 64 * 1000 * 1000)
+        np.save(os.path.join(args.dump_outputs, "ids.npy"), ids_h[keep].astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "distances.npy"), dist_h[keep].astype(np.float32))
+        if keep.size < ids_h.shape[0]:
+            np.save(os.path.join(args.dump_outputs, "rows.npy"), keep.astype(np.float64))
 
     # ---- roofline of the dominant kernel (k_search_fast): algorithmic bytes = visits*4R + d_quantized*8W of the scans
     # it completed (the few scans handed to the general kernel are accounted to "search_fallback") -------------------
@@ -895,7 +934,7 @@ def main():
     # tile, so GB/s and queries/s pull in opposite directions — all three are reported, "fastest_per_query" names the tile a
     # caller should use, and the roofline entry of the metric ("SBQ-scan achieved HBM GB/s") is the one with the best GB/s.
     scan_roofline = None
-    if args.scan_nq > 0 and rank == 0:
+    if args.full and args.scan_nq > 0 and rank == 0:
         try:
             qh_s = ctx.download(qbuf[0], np.empty((nq, dim), np.float32))[:args.scan_nq]
             if dt == P.VS_COSINE:
@@ -938,7 +977,7 @@ def main():
     # ---- PCIe-inclusive leg (never the value): the same step through the host-pointer entry point (vs_search_batch: queries
     # from pageable host memory through the pinned staging ring, rows back to the host)
     pcie = None
-    if args.pcie_steps > 0 and rank == 0 and not NL:
+    if args.full and args.pcie_steps > 0 and rank == 0 and not NL:
         try:
             qh_p = ctx.download(qbuf[args.warmup], np.empty((nq, dim), np.float32))
             # one untimed step of the full size first, as the device-resident path gets its warm-up steps: the chunk pipeline's own
@@ -958,7 +997,7 @@ def main():
             pcie = {"error": repr(e)}
 
     # ---- extras (never the value): the same index at the reference's DEFAULT GUCs (AM/guc.rs:3-4: search_list_size 100, rescore 50)
-    extras_on = world == 1 and (args.extras == "on" or (args.extras == "auto" and n == 50_000_000 and args.corpus == "lowrank" and not NL
+    extras_on = args.full and world == 1 and (args.extras == "on" or (args.extras == "auto" and n == 50_000_000 and args.corpus == "lowrank" and not NL
                                                          and dim == 768 and not args.fixed))
     default_gucs = None
     if extras_on and ix.desc.storage_type == _lib.VS_STORAGE_SBQ:
@@ -1150,7 +1189,7 @@ def main():
     }
 
     # ---- CPU baseline: the oracle (port of the reference path on flat arrays) on the host cores --------------------
-    if rank == 0 and world == 1 and not args.skip_cpu:
+    if args.full and rank == 0 and world == 1 and not args.skip_cpu:
         try:
             from oracle import oracle_py as O
             O.build()
@@ -1261,7 +1300,7 @@ def main():
     if extras_on and rank == 0:
         import subprocess
         t0 = time.time()
-        cmd = [sys.executable, os.path.abspath(__file__), "--n", "500" if EMU else "20000000", "--corpus-kind", "mid", "--extras", "off", "--steps", "3",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--n", "500" if EMU else "20000000", "--corpus-kind", "mid", "--extras", "off", "--steps", "3",
                "--warmup", "1", "--cpu-seconds", "4", "--pcie-steps", "0", "--scan-nq", "0", "--graph-cache", "none", "--distance", args.distance]
         if EMU:
             cmd += ["--nq", "16", "--dim", str(dim), "--recall-queries", "16", "--validate-queries", "16", "--heldout-queries", "16", "--build-l", "20"]

@@ -20,7 +20,7 @@ for step in "$@"; do
            PH=load; [ -f /tmp/diag_graph ] || PH=build
            timeout 900 python scripts/diag_state.py --n $N --phase $PH --graph /tmp/diag_graph --placement ${PLACE_TRIALS:-24} 2>&1 | grep -Ev "$NOBANNER" | sed 's/ *GPU\[0\].*//' | uniq | tee $O/placement_$N.txt ;;
     pmap)  timeout 1200 python scripts/placement_map.py --n ${arg:-50000000} $PMAP_ARGS 2>&1 | grep -Ev "$NOBANNER" | tee $O/placement_map.txt ;;
-    bench) timeout 2400 python bench.py $arg > $O/bench_$(echo "$arg" | tr -c 'A-Za-z0-9\n' '_').json 2> $O/bench.err; tail -3 $O/bench.err; tail -c 1500 $O/bench_*.json ;;
+    bench) timeout 2400 python bench.py --full $arg > $O/bench_$(echo "$arg" | tr -c 'A-Za-z0-9\n' '_').json 2> $O/bench.err; tail -3 $O/bench.err; tail -c 1500 $O/bench_*.json ;;
     ab)    N=${arg%%:*}; CFG=${arg#*:}
            timeout 1500 python scripts/perf_search.py --n $N --nq 262144 --L 3 --rescore 195 --reps 4 --graph-cache /tmp/g --configs "$CFG" 2>&1 | grep -Ev "$NOBANNER" | tee $O/ab_$N.txt ;;
     pmcissue) bash scripts/pmc_issue.sh ${arg:-10000000} 262144 3 195 2>&1 | grep -Ev "$NOBANNER" | tee $O/pmc_issue.txt ;;
@@ -29,7 +29,7 @@ for step in "$@"; do
     fuzzv) timeout $(( ${arg:-40} * 8 + 120 )) python scripts/fuzz_variants.py --gpu --cases ${arg:-40} --seed $RANDOM 2>&1 | tail -4 | tee $O/fuzz_variants_gpu.txt ;;
     final) # the evidence set of the frozen tree: the driver's bench command (builds, writes the graph cache), the same under rocprofv3
            # --kernel-trace --stats, two --pmc passes at the bench's operating point, the bench once more WITH roofline.traffic
-           timeout 2400 python bench.py --steps 20 --warmup 5 --graph-cache /tmp/g $FINAL_BENCH_ARGS > $O/bench_50m.json 2> $O/bench_50m.err; tail -3 $O/bench_50m.err
+           timeout 2400 python bench.py --full --steps 20 --warmup 5 --graph-cache /tmp/g $FINAL_BENCH_ARGS > $O/bench_50m.json 2> $O/bench_50m.err; tail -3 $O/bench_50m.err
            LS=$(python - <<PY
 import json
 j = json.loads(open("$O/bench_50m.json").read().strip().splitlines()[-1])
@@ -37,14 +37,14 @@ print(j["config"]["search_list_size"], j["config"]["rescore"], j["config"]["quer
 PY
 )
            set -- $LS; L=$1; S=$2; NQ=$3; echo "operating point L=$L rescore=$S nq=$NQ"
-           rm -rf gpurun_out/prof_final
-           timeout 1500 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_final -o bench -- python bench.py --steps 20 --warmup 5 --skip-cpu --extras off --graph-cache /tmp/g > $O/bench_50m_under_rocprof.json 2> $O/bench_50m_under_rocprof.err
-           python scripts/summarize_rocprof.py gpurun_out/prof_final/bench_kernel_stats.csv $O/kernel_stats_50m.csv "rocprofv3 --kernel-trace --stats -- python bench.py --steps 20 --warmup 5 --skip-cpu --extras off --graph-cache ... (50M x 768 l2, $NQ scans per launch, L=$L rescore=$S; index loaded from the cache the plain bench run wrote)"
+           rm -rf $O/prof_final
+           timeout 1500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_final -o bench -- python bench.py --n 50000000 --steps 20 --warmup 5 --graph-cache /tmp/g > $O/bench_50m_under_rocprof.json 2> $O/bench_50m_under_rocprof.err
+           python scripts/summarize_rocprof.py $O/prof_final/bench_kernel_stats.csv $O/kernel_stats_50m.csv "rocprofv3 --kernel-trace --stats -- python bench.py --n 50000000 --steps 20 --warmup 5 --graph-cache ... (50M x 768 l2, $NQ scans per launch, L=$L rescore=$S; index loaded from the cache the plain bench run wrote)"
            head -8 $O/kernel_stats_50m.csv
            timeout 1500 bash scripts/pmc_traffic.sh 50000000 $NQ $L $S /tmp/g 2>&1 | tail -40 > $O/pmc_traffic.log
            cp gpurun_out/pmc_search_traffic.json $O/pmc_search_traffic_50m.json
            mkdir -p profiles/${PROFROUND:-r06} && cp $O/pmc_search_traffic_50m.json profiles/${PROFROUND:-r06}/pmc_search_traffic_50m.json
-           timeout 900 python bench.py --steps 20 --warmup 5 --skip-cpu --extras off --graph-cache /tmp/g > $O/bench_50m_with_traffic.json 2> $O/bench_50m_with_traffic.err
+           timeout 900 python bench.py --n 50000000 --steps 20 --warmup 5 --graph-cache /tmp/g > $O/bench_50m_with_traffic.json 2> $O/bench_50m_with_traffic.err
            python - <<PY | tee $O/summary.txt
 import json
 for f in ("bench_50m", "bench_50m_under_rocprof", "bench_50m_with_traffic"):

@@ -18,7 +18,7 @@ def test_bench_dry_run_on_the_interpreter():
     r = subprocess.run(["make", "-C", os.path.join(ROOT, "tests", "emu"), "-j8", "-s"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     env = dict(os.environ, VS_EMU="1", VS_F_LDS_MAX_INS="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--n", "6000", "--dim", "64", "--nq", "128", "--steps", "1", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--n", "6000", "--dim", "64", "--nq", "128", "--steps", "1", "--warmup", "1",
            "--recall-queries", "16", "--scan-nq", "8", "--cpu-seconds", "1", "--graph-cache", "none"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, cwd=ROOT, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -57,7 +57,7 @@ def test_bench_dry_run_two_ranks():
 @pytest.mark.skipif(not os.environ.get("VS_EMU_FULL"), reason="slow (about 2 minutes); set VS_EMU_FULL=1")
 def test_bench_dry_run_two_batches_in_flight():
     env = dict(os.environ, VS_EMU="1", VS_F_LDS_MAX_INS="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--n", "6000", "--dim", "64", "--nq", "128", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--n", "6000", "--dim", "64", "--nq", "128", "--steps", "3", "--warmup", "1",
            "--recall-queries", "16", "--scan-nq", "8", "--cpu-seconds", "1", "--graph-cache", "none", "--pipeline", "2"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, cwd=ROOT, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -96,7 +96,7 @@ def test_bench_extras_small():
     r = subprocess.run(["make", "-C", os.path.join(ROOT, "tests", "emu"), "-j8", "-s"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     env = dict(os.environ, VS_EMU="1", VS_F_LDS_MAX_INS="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--n", "2000", "--dim", "64", "--nq", "32", "--steps", "1", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--n", "2000", "--dim", "64", "--nq", "32", "--steps", "1", "--warmup", "1",
            "--recall-queries", "16", "--validate-queries", "16", "--heldout-queries", "16", "--scan-nq", "0", "--cpu-seconds", "1",
            "--graph-cache", "none", "--pcie-steps", "0", "--extras", "on", "--fixed", "20,10"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, cwd=ROOT, timeout=1500)
