@@ -109,7 +109,9 @@ const char* vs_last_error(void);
  * variable of the same name; the environment itself is only SNAPSHOT — at the first lookup and again when the process's VS_* variables
  * change — never searched on the launch path.  No reference counterpart: these are the knobs of this implementation (the reference's
  * own GUCs, diskann.query_search_list_size and diskann.query_rescore, are arguments of vs_rescan / vs_search_batch).  Thread safe.
- * vs_get_option: 1 = set (copied to out, truncated to cap), 0 = set nowhere (out = ""). */
+ * vs_get_option: 1 = set (copied to out, truncated to cap), 0 = set nowhere (out = "").
+ * VS_RERANK_FUSED: how a batch reranks and runs the rescore window — "1" (default) one fused launch, "2" fused with the serial heap
+ * replay for every scan, "0" the separate rerank and window kernels; the rows are the same under all three. */
 int vs_set_option(const char* name, const char* value);
 int vs_get_option(const char* name, char* out, size_t cap);
 const char* vs_version(void);

@@ -165,6 +165,17 @@ static int run_post_search(vs_index* ix, const BatchPlan& bp, uint32_t* d_out_id
     if (bp.stream_only) return VS_OK;
     if (bp.rescore > 0) {
         VS_REQUIRE(ix->vecs, "diskann.query_rescore > 0 needs the heap vector column on the device");
+        // VS_RERANK_FUSED (default 1): rerank and rescore window in one launch, distances and heap in LDS (k_rerank_window); 2 = the
+        // same with the serial heap replay forced for every scan; 0 = the k_rerank + k_resort pair, which also takes the windows
+        // that do not fit the fused kernel's LDS budget (rerank_window_fits)
+        const uint32_t fused = env_u32("VS_RERANK_FUSED", 1);
+        if (fused && rerank_window_fits(ix, M, bp.rescore, bp.k)) {
+            hipEvent_t ev = prof_begin(c);
+            VS_TRY(launch_rerank_window(ix, (const float*)w.q_full.p, (const uint32_t*)w.stream_ids.p, (const uint32_t*)w.stream_cnt.p, M,
+                                        bp.rescore, bp.k, nq, d_out_ids, d_out_tids, d_out_dist, fused == 2 ? 2u : 1u));
+            prof_end(c, PK_RERANK, ev);
+            return VS_OK;
+        }
         VS_TRY(devbuf_reserve(c, w.rr_dist, (size_t)nq * M * 4));
         VS_TRY(devbuf_reserve(c, w.resort_heap, (size_t)nq * bp.rescore * 8));
         hipEvent_t ev = prof_begin(c);
@@ -177,6 +188,22 @@ static int run_post_search(vs_index* ix, const BatchPlan& bp, uint32_t* d_out_id
                          bp.rescore ? (const float*)w.rr_dist.p : nullptr, (uint64_t*)w.resort_heap.p, d_out_ids,
                          d_out_tids, d_out_dist));
     prof_end(c, PK_RESORT, ev);
+    return VS_OK;
+}
+
+// Sums the per-scan arrays of the launch in the workspace (status words, work counters, fallback marks, stream lengths) on the device
+// and sends the RED_N words to the handle's pinned block, behind the launch on its stream: what a finish reads after one
+// synchronisation instead of copying the arrays (10 MB per 262 144 scans, to pageable memory, summed by one host thread).
+static int enqueue_reduce(vs_index* ix, const BatchPlan& bp) {
+    vs_ctx* c = ix->ctx;
+    SearchWorkspace& w = ix->ws;
+    VS_TRY(devbuf_reserve(c, w.red, RED_N * 8));
+    if (!w.red_host) VS_HIP(hipHostMalloc((void**)&w.red_host, RED_N * 8, hipHostMallocDefault));
+    VS_HIP(hipMemsetAsync(w.red.p, 0, RED_N * 8, c->stream));
+    VS_TRY(launch_reduce_stats(ix, (const uint32_t*)w.stats.p, w.fb_valid ? (const uint32_t*)w.fb_flag.p : nullptr,
+                               (const uint32_t*)w.stream_cnt.p, (const uint32_t*)w.status.p, bp.nq, bp.M, bp.rescore,
+                               !bp.stream_only && bp.rescore > 0, ix->last_ins_limit, (uint64_t*)w.red.p));
+    VS_HIP(hipMemcpyAsync(w.red_host, w.red.p, RED_N * 8, hipMemcpyDeviceToHost, c->stream));
     return VS_OK;
 }
 
@@ -567,7 +594,44 @@ static int run_search_chunk(vs_index* ix, const BatchPlan& bp, const float* d_ra
         break;
     }
     if (check_now) VS_TRY(retry_failed_scans(ix, bp, d_qlabels, d_qlabel_off, caps, st));
-    return run_post_search(ix, bp, d_out_ids, d_out_tids, d_out_dist);
+    VS_TRY(run_post_search(ix, bp, d_out_ids, d_out_tids, d_out_dist));
+    // (unconditional, also for callers without stats and after a synchronous retry: finish_launch decides from RED_STATUS whether any
+    // scan still has to be re-run, and that word only exists once this has run — 0.09 ms per 262 144 scans)
+    return enqueue_reduce(ix, bp);
+}
+
+// the counters of a finished launch from the sums of enqueue_reduce (the stream has been synchronised since)
+static int collect_stats_reduced(vs_index* ix, uint32_t nq, uint32_t M, uint32_t rescore, bool stream_only, vs_stats* st, uint32_t obs_L) {
+    if (!st) return VS_OK;
+    const SearchWorkspace& w = ix->ws;
+    const uint64_t* r = w.red_host;
+    if (w.fb_valid && ix->last_ins_limit && r[RED_INS_FAST]) {  // what this batch needed: sizes the next launch with the same (L, M)
+        const double sum = (double)r[RED_INS_SUM], mx = (double)r[RED_INS_MAX];
+        ScanObs& o = ix->obs;
+        const bool same = o.valid && o.L == obs_L && o.M == M;
+        const double a = same ? 0.5 : 1.0;  // exponential average over batches
+        o.ins_mean = (1 - a) * o.ins_mean + a * (sum / (uint32_t)r[RED_INS_FAST]);
+        o.ins_max = same ? std::max(o.ins_max, mx) : mx;
+        o.ov_frac = (1 - a) * (same ? o.ov_frac : 0.0) + a * ((double)(uint32_t)r[RED_INS_OV] / nq);
+        o.L = obs_L;
+        o.M = M;
+        o.valid = true;
+    }
+    st->queries += nq;
+    st->visited_nodes += r[RED_VISITS];
+    st->candidate_nodes += r[RED_CAND];
+    if (ix->d.storage_type == VS_STORAGE_PLAIN) st->full_distance_comparisons += r[RED_DQ];
+    else st->quantized_distance_comparisons += r[RED_DQ];
+    st->node_reads += r[RED_READS];
+    st->next_calls += r[RED_NEXT];
+    st->fallback_scans += r[RED_FB_SCANS];
+    st->fallback_visited_nodes += r[RED_FB_VISITS];
+    st->fallback_quantized_distance_comparisons += r[RED_FB_DQ];
+    if (!stream_only && rescore > 0) {  // every row handed to the rescore window was fetched from the heap (see collect_stats)
+        st->full_distance_comparisons += r[RED_HEAP_ROWS];
+        st->node_heap_reads += r[RED_HEAP_ROWS];
+    }
+    return VS_OK;
 }
 
 static int collect_stats(vs_index* ix, uint32_t nq, uint32_t M, uint32_t rescore, bool stream_only, vs_stats* st,
@@ -597,7 +661,7 @@ static int collect_stats(vs_index* ix, uint32_t nq, uint32_t M, uint32_t rescore
         double sum = 0, mx = 0;
         uint32_t cnt_fast = 0, ov = 0;
         for (uint32_t q = 0; q < nq; ++q) {
-            const double v = hs[(size_t)q * ST_N + 7];
+            const double v = hs[(size_t)q * ST_N + ST_INS];
             if (fb[q]) {  // (finished by a second attempt: its insert count still tells how big a table the batch needs)
                 ov++;
                 mx = std::max(mx, v);
@@ -651,6 +715,24 @@ static int collect_stats(vs_index* ix, uint32_t nq, uint32_t M, uint32_t rescore
         }
     }
     return VS_OK;
+}
+
+// The end of a launch: waits for it, re-runs the scans that outgrew every pool (synchronously, growing capacities) and redoes the
+// window for them, then adds the launch's counters to *st.  VS_PHASE (diagnostics) reads the per-scan arrays themselves.
+static int finish_launch(vs_index* ix, const BatchPlan& bp, const int16_t* d_qlabels, const uint32_t* d_qlabel_off, Caps& caps,
+                         uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, vs_stats* st) {
+    vs_ctx* c = ix->ctx;
+    SearchWorkspace& w = ix->ws;
+    VS_REQUIRE(w.red_host, "finish: no launch to finish");
+    VS_HIP(hipStreamSynchronize(c->stream));
+    if (w.red_host[RED_STATUS]) {
+        VS_TRY(retry_failed_scans(ix, bp, d_qlabels, d_qlabel_off, caps, st));
+        VS_TRY(run_post_search(ix, bp, d_out_ids, d_out_tids, d_out_dist));
+        VS_TRY(enqueue_reduce(ix, bp));
+        VS_HIP(hipStreamSynchronize(c->stream));  // (stage_out does not wait for the compute stream)
+    }
+    if (env_u32("VS_PHASE", 0)) return collect_stats(ix, bp.nq, bp.M, bp.rescore, bp.stream_only, st, bp.L);
+    return collect_stats_reduced(ix, bp.nq, bp.M, bp.rescore, bp.stream_only, st, bp.L);
 }
 
 static uint32_t stream_len(uint32_t rescore, uint32_t k) { return rescore > 0 ? rescore + k - 1 : k; }
@@ -771,17 +853,8 @@ static int search_host(vs_index* ix, const float* queries, const int16_t* qlabel
     // the scans of a launch that outgrew every pool are re-run (synchronously, growing capacities) and the window is redone
     auto finish = [&](uint32_t ci, const BatchPlan& bp) -> int {
         const uint32_t q0 = ci * chunk;
-        std::vector<uint32_t> status(bp.nq);
-        VS_HIP(hipMemcpyAsync(status.data(), w.status.p, (size_t)bp.nq * 4, hipMemcpyDeviceToHost, c->stream));
-        VS_HIP(hipStreamSynchronize(c->stream));
-        uint32_t ovf = 0;
-        for (uint32_t v : status) ovf |= v;
-        if (ovf) {
-            VS_TRY(retry_failed_scans(ix, bp, d_labels_all, d_off_all ? d_off_all + q0 : nullptr, caps, stats));
-            VS_TRY(run_post_search(ix, bp, (uint32_t*)oids[ci & 1]->p, (uint64_t*)otids[ci & 1]->p, (float*)odist[ci & 1]->p));
-            VS_HIP(hipStreamSynchronize(c->stream));  // (stage_out does not wait for the compute stream)
-        }
-        return collect_stats(ix, bp.nq, M, rescore, stream_only, stats, L);
+        return finish_launch(ix, bp, d_labels_all, d_off_all ? d_off_all + q0 : nullptr, caps, (uint32_t*)oids[ci & 1]->p,
+                             (uint64_t*)otids[ci & 1]->p, (float*)odist[ci & 1]->p, stats);
     };
     // a stream-only chunk hands back the workspace's own stream arrays: they go out before the next launch overwrites them
     auto stage_out = [&](uint32_t ci) -> int {
@@ -893,24 +966,12 @@ int vs_search_batch_dev_finish_impl(vs_index* ix, vs_stats* stats) {
         return VS_ERR_STATE;
     }
     w.pending = false;
-    const uint32_t nq = w.pend_nq, M = w.pend_m;
     VS_REQUIRE(w.pend_blob, "vs_search_batch_dev_finish: no batch descriptor");
     PendingBatch pb;
     memcpy(&pb, w.pend_blob, sizeof(pb));
-    std::vector<uint32_t> status(nq);
-    VS_HIP(hipMemcpyAsync(status.data(), w.status.p, (size_t)nq * 4, hipMemcpyDeviceToHost, ix->ctx->stream));
-    VS_HIP(hipStreamSynchronize(ix->ctx->stream));
-    uint32_t ovf = 0;
-    for (uint32_t v : status) ovf |= v;
     vs_stats st{};
-    if (ovf) {
-        // some scans outgrew even the fallback pools of the asynchronous launch: re-run exactly those (synchronously,
-        // with growing capacities), then redo the rerank / rescore window so the outputs are complete
-        VS_TRY(retry_failed_scans(ix, pb.bp, pb.d_qlabels, pb.d_qlabel_off, pb.caps, &st));
-        VS_TRY(run_post_search(ix, pb.bp, pb.d_out_ids, pb.d_out_tids, pb.d_out_dist));
-        VS_HIP(hipStreamSynchronize(ix->ctx->stream));
-    }
-    VS_TRY(collect_stats(ix, nq, M, pb.bp.rescore, false, &st, w.pend_L));
+    // (scans that outgrew even the fallback pools of the asynchronous launch are re-run there, and the window redone)
+    VS_TRY(finish_launch(ix, pb.bp, pb.d_qlabels, pb.d_qlabel_off, pb.caps, pb.d_out_ids, pb.d_out_tids, pb.d_out_dist, &st));
     ix->last_stats = st;
     if (stats) *stats = st;
     return VS_OK;

@@ -121,7 +121,9 @@ struct WsSlab {
 struct SearchWorkspace {
     DevBuf q_full, qcodes, qlabels, qlabel_off, hash, heap_g, heap_g4, ghash4, heap_g4b, ghash4b, pool_ctr, fb_flag, phase, timeline, stream_ids, stream_ham, stream_cnt, stats, status,
         rr_dist, out_ids, out_tids, out_dist, resort_heap, raw_q, misc, q_index,
-        raw_q2, out_ids2, out_tids2, out_dist2;  // second set of a pipelined host batch (search_host)
+        raw_q2, out_ids2, out_tids2, out_dist2,  // second set of a pipelined host batch (search_host)
+        red;                                      // RED_N u64 sums of the last launch's per-scan arrays (k_reduce_stats)
+    uint64_t* red_host = nullptr;  // pinned; the sums land here (this handle's own: two handles of one context may each have a batch in flight)
     // pending async call (vs_search_batch_dev)
     bool fb_valid = false;  // fb_flag holds the fallback marks of the last chunk
     bool pending = false;
@@ -335,7 +337,7 @@ enum {
 size_t fast_lds_bytes(const vs_index* idx, const FastLaunch& s);
 int launch_search_fast(vs_index* idx, const FastLaunch& s);
 int fast_resident_scans(vs_index* idx, const FastLaunch& s, uint32_t* out);  // size of a persistent grid for this instantiation
-enum { ST_VISITS = 0, ST_CAND = 1, ST_DQ = 2, ST_READS = 3, ST_NEXT = 4, ST_GSPILL = 5, ST_INVIS = 6, ST_N = 8 };
+enum { ST_VISITS = 0, ST_CAND = 1, ST_DQ = 2, ST_READS = 3, ST_NEXT = 4, ST_GSPILL = 5, ST_INVIS = 6, ST_INS = 7 /* ids the fast kernel inserted */, ST_N = 8 };
 enum { OVF_HEAP = 1, OVF_VISITED = 2, OVF_HASH = 4, OVF_POOL = 8,
        OVF_KEY = 16 };  // (fast kernel only) the scan key has more labels than its LDS slot holds: the general kernel runs the scan
 size_t search_lds_bytes(const vs_index* idx, const SearchLaunch& s);
@@ -351,6 +353,16 @@ int launch_search(vs_index* idx, const SearchLaunch& s, bool build_mode = false)
 int launch_resort(vs_index* idx, uint32_t nq, uint32_t M, uint32_t rescore, uint32_t k, const uint32_t* d_stream_ids,
                   const uint32_t* d_cnt, const float* d_dist, uint64_t* d_heap_ws, uint32_t* d_out_ids,
                   uint64_t* d_out_tids, float* d_out_dist);
+// rerank + rescore window of a batch in one launch (rescore > 0; mode 2: the serial heap replay for every scan)
+bool rerank_window_fits(const vs_index* idx, uint32_t M, uint32_t rescore, uint32_t k);
+int launch_rerank_window(vs_index* idx, const float* d_q_full, const uint32_t* d_stream_ids, const uint32_t* d_cnt, uint32_t M,
+                         uint32_t rescore, uint32_t k, uint32_t nq, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist,
+                         uint32_t mode);
+// the per-scan arrays a batch's finish reads, summed on the device (k_reduce_stats)
+enum { RED_STATUS = 0, RED_VISITS, RED_CAND, RED_DQ, RED_READS, RED_NEXT, RED_FB_SCANS, RED_FB_VISITS, RED_FB_DQ, RED_HEAP_ROWS,
+       RED_INS_SUM, RED_INS_MAX, RED_INS_FAST, RED_INS_OV, RED_N = 16 };
+int launch_reduce_stats(vs_index* idx, const uint32_t* d_stats, const uint32_t* d_fb, const uint32_t* d_cnt, const uint32_t* d_status,
+                        uint32_t nq, uint32_t M, uint32_t rescore, bool windowed, uint32_t ins_limit, uint64_t* d_red);
 int launch_resort_cursor(vs_index* idx, uint32_t n, bool exhausted, uint32_t rescore, uint32_t k, const uint32_t* d_stream,
                          const float* d_dist, const uint32_t* d_keys, uint64_t* d_heap, uint32_t* d_cur, uint32_t* d_out_ids,
                          uint64_t* d_out_tids, float* d_out_dist);

@@ -17,12 +17,13 @@
 #include "vs_device.h"
 
 // ---------------------------------------------------------------------------------------------------------------
-// preprocess_cosine on a vector held in LDS (AM/distance/mod.rs:225-253): sequential f32 sum of squares (lane 0),
-// then every lane divides.  Returns nothing; buf is normalised in place.
+// preprocess_cosine on a vector held in LDS (AM/distance/mod.rs:225-253): sequential f32 sum of squares (the owner's lane 0),
+// then the owner's lanes divide (lane, lane + stride, ...).  buf is normalised in place.  The barriers are workgroup wide: every
+// thread of the workgroup calls this, `active` = this thread's wave owns a vector (one wave per workgroup: always).
 // ---------------------------------------------------------------------------------------------------------------
-__device__ void lds_preprocess_cosine(float* buf, uint32_t n, int lane, float* bcast /* LDS scratch [1] */) {
+__device__ void lds_preprocess_cosine(float* buf, uint32_t n, int lane, uint32_t stride, float* bcast /* LDS scratch [1] */, bool active = true) {
     __syncthreads();
-    if (lane == 0) {
+    if (active && lane == 0) {
         float norm = 0.0f;
         for (uint32_t i = 0; i < n; ++i) {
             float p = buf[i] * buf[i];
@@ -35,9 +36,10 @@ __device__ void lds_preprocess_cosine(float* buf, uint32_t n, int lane, float* b
         *bcast = s;
     }
     __syncthreads();
-    float s = *bcast;
-    if (s != 0.0f) {
-        for (uint32_t i = lane; i < n; i += blockDim.x) buf[i] = buf[i] / s;
+    if (active) {
+        float s = *bcast;
+        if (s != 0.0f)
+            for (uint32_t i = lane; i < n; i += stride) buf[i] = buf[i] / s;
     }
     __syncthreads();
 }
@@ -84,35 +86,113 @@ __device__ void wave_quantize(const float* v, uint32_t dims, uint32_t bits, cons
 
 // ---------------------------------------------------------------------------------------------------------------
 // K4a: query preparation = PgVector::from_datum(index=true, full=true) (AM/pg_vector.rs:162-199) +
-//      SbqSearchDistanceMeasure::new (AM/sbq/mod.rs:145-148).  One wave per query.
+//      SbqSearchDistanceMeasure::new (AM/sbq/mod.rs:145-148).
+// A workgroup of NW waves prepares NW queries per round (one per wave, each in its own LDS slice) for `rounds` rounds.  What belongs
+// to the index and not to the query is staged once per workgroup: the means and the per-dimension standard deviations
+// sqrtf(m2 / count) — the expression of SbqQuantizer::quantize, so every bit stays — instead of a square root and a division per
+// output BIT of every query.  Per query the number of one-bits of a dimension is computed once per dimension (lane = dimension), the
+// words are then packed with ballots (lane = bit) and stored 64 at a time by all lanes; q_full goes out as float4.
+// Barriers are workgroup wide and every wave passes the same ones (a wave without a query idles through them).
+// (The deviations are not cached per index: mean / m2 are written through vs_index_set_quantizer, training, broadcasts, clones AND the
+// device pointers vs_index_array hands out, so a derived array could go stale unseen; 16 queries per workgroup amortise them instead.
+// q_full is still written for every distance type: the second attempts, the general kernel on plain storage and a finish that
+// redoes the window read w.q_full after the call has returned, when the caller's query buffer is no longer the library's to read.)
+// LDS: [dim_index] mean | [dim_index] std (bits > 1) | per wave: [r4(dim_full)] full | [r4(dim_index)] index slice (if different) |
+//      [r4(dim_index)] u32 ones (bits > 1) | [4] scratch.
 // ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(WAVE) void k_prepare_queries(const float* __restrict__ raw, uint32_t nq,
-                                                          uint32_t dim_full, uint32_t dim_index, uint32_t vec_stride,
-                                                          uint32_t distance_type, uint32_t bits,
-                                                          const float* __restrict__ mean, const float* __restrict__ m2,
-                                                          float count_f, uint32_t words, uint32_t code_stride,
-                                                          float* __restrict__ q_full, uint64_t* __restrict__ qcodes) {
+__global__ __launch_bounds__(256) void k_prepare_queries(const float* __restrict__ raw, uint32_t nq,
+                                                         uint32_t dim_full, uint32_t dim_index, uint32_t vec_stride,
+                                                         uint32_t distance_type, uint32_t bits,
+                                                         const float* __restrict__ mean, const float* __restrict__ m2,
+                                                         float count_f, uint32_t words, uint32_t code_stride, uint32_t rounds,
+                                                         uint32_t vec4, float* __restrict__ q_full, uint64_t* __restrict__ qcodes) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float* full = reinterpret_cast<float*>(smem);
-    float* idxv = full + round_up_u32(dim_full, 4);
-    float* bc = idxv + round_up_u32(dim_index, 4);
-    const int lane = threadIdx.x;
-    const uint32_t q = blockIdx.x;
-    if (q >= nq) return;
-    const float* src = raw + (size_t)q * dim_full;
-    for (uint32_t i = lane; i < dim_full; i += WAVE) full[i] = src[i];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t nw = blockDim.x >> 6;
     const bool same = dim_full == dim_index;
-    if (!same)
-        for (uint32_t i = lane; i < dim_index; i += WAVE) idxv[i] = src[i];
-    __syncthreads();
-    if (distance_type == VS_COSINE) {
-        lds_preprocess_cosine(full, dim_full, lane, bc);
-        if (!same) lds_preprocess_cosine(idxv, dim_index, lane, bc);
+    const bool quant = words != 0, multi = quant && bits != 1;
+    const uint32_t rf = round_up_u32(dim_full, 4), ri = round_up_u32(dim_index, 4);
+    float* mu = reinterpret_cast<float*>(smem);
+    float* sdv = mu + (quant ? ri : 0u);
+    float* wbase = sdv + (multi ? ri : 0u);
+    const uint32_t per_wave = rf + (same ? 0u : ri) + (multi ? ri : 0u) + 4u;
+    float* full = wbase + (size_t)wave * per_wave;
+    float* idxv = same ? full : full + rf;
+    uint32_t* ones = reinterpret_cast<uint32_t*>((same ? full : idxv) + (same ? rf : ri));
+    float* bc = reinterpret_cast<float*>(ones + (multi ? ri : 0u));
+    if (quant)
+        for (uint32_t i = threadIdx.x; i < dim_index; i += blockDim.x) {
+            mu[i] = mean[i];
+            if (multi) {
+                float variance = m2[i] / count_f;
+                sdv[i] = sqrtf(variance);
+            }
+        }
+    for (uint32_t r = 0; r < rounds; ++r) {
+        const uint32_t q = (blockIdx.x * rounds + r) * nw + (uint32_t)wave;
+        const bool active = q < nq;
+        __syncthreads();  // (the staged statistics; the slices of the round before)
+        if (active) {
+            const float* src = raw + (size_t)q * dim_full;
+            if (vec4) {
+                for (uint32_t i = lane; i < dim_full / 4; i += WAVE)
+                    reinterpret_cast<float4*>(full)[i] = reinterpret_cast<const float4*>(src)[i];
+            } else {
+                for (uint32_t i = lane; i < rf; i += WAVE) full[i] = i < dim_full ? src[i] : 0.0f;
+            }
+            if (!same)
+                for (uint32_t i = lane; i < dim_index; i += WAVE) idxv[i] = src[i];
+        }
+        if (distance_type == VS_COSINE) {
+            lds_preprocess_cosine(full, dim_full, lane, WAVE, bc, active);
+            if (!same) lds_preprocess_cosine(idxv, dim_index, lane, WAVE, bc, active);
+        } else {
+            __syncthreads();
+        }
+        if (active) {
+            float* qf = q_full + (size_t)q * vec_stride;  // (vec_stride = r4(dim_full); rows are 16-byte aligned)
+            for (uint32_t i = lane; i < vec_stride / 4; i += WAVE) reinterpret_cast<float4*>(qf)[i] = reinterpret_cast<const float4*>(full)[i];
+            if (multi) {
+                const float ranges = (float)(bits + 1);
+                for (uint32_t dim = lane; dim < dim_index; dim += WAVE) {
+                    float x = idxv[dim];
+                    float z = (x - mu[dim]) / sdv[dim];
+                    float index = (z + 2.0f) / (4.0f / ranges);
+                    uint32_t o = 0;
+                    if (!(index < 1.0f)) {  // NaN falls through like Rust's `if index < 1.0 {} else {..}`
+                        float fl = floorf(index);
+                        // `fl as usize` saturating, NaN -> 0; then min(bits)
+                        if (fl != fl) o = 0;
+                        else if (fl >= (float)bits) o = bits;
+                        else if (fl <= 0.0f) o = 0;
+                        else o = (uint32_t)fl;
+                    }
+                    ones[dim] = o;
+                }
+            }
+        }
+        __syncthreads();
+        if (active) {
+            uint64_t* out = qcodes + (size_t)q * code_stride;
+            uint64_t mine = 0;
+            for (uint32_t w = 0; w < code_stride; ++w) {
+                uint64_t word = 0;
+                if (w < words) {
+                    const uint32_t g = w * 64u + (uint32_t)lane;  // global bit index
+                    const uint32_t dim = g / bits;
+                    const uint32_t j = g - dim * bits;
+                    bool bit = false;
+                    if (dim < dim_index) bit = multi ? j < ones[dim] : idxv[dim] > mu[dim];
+                    word = __ballot(bit);
+                }
+                if ((uint32_t)lane == (w & 63u)) mine = word;
+                if ((w & 63u) == 63u || w + 1 == code_stride) {
+                    const uint32_t w0 = w & ~63u;
+                    if (w0 + (uint32_t)lane <= w) out[w0 + lane] = mine;
+                }
+            }
+        }
     }
-    float* qf = q_full + (size_t)q * vec_stride;
-    for (uint32_t i = lane; i < vec_stride; i += WAVE) qf[i] = i < dim_full ? full[i] : 0.0f;
-    wave_quantize(same ? full : idxv, dim_index, bits, mean, m2, count_f, qcodes + (size_t)q * code_stride, words,
-                  code_stride, lane);
 }
 
 // plain storage with num_dimensions_to_index < num_dimensions: the graph search compares the INDEX slice of the query,
@@ -128,7 +208,7 @@ __global__ __launch_bounds__(WAVE) void k_prepare_index_slice(const float* __res
     if (q >= nq) return;
     for (uint32_t i = lane; i < dim_index; i += WAVE) idxv[i] = raw[(size_t)q * dim_full + i];
     __syncthreads();
-    if (distance_type == VS_COSINE) lds_preprocess_cosine(idxv, dim_index, lane, bc);
+    if (distance_type == VS_COSINE) lds_preprocess_cosine(idxv, dim_index, lane, blockDim.x, bc);
     for (uint32_t i = lane; i < vec_stride; i += WAVE) q_index[(size_t)q * vec_stride + i] = i < dim_index ? idxv[i] : 0.0f;
 }
 
@@ -178,6 +258,75 @@ __global__ __launch_bounds__(WAVE) void k_hamming_gather(const uint64_t* __restr
 // ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float shfl_f(float v, int src) { return __shfl(v, src, WAVE); }
 
+// distance of one candidate row to the query in LDS, computed by the 8 lanes of a group (all 64 lanes call it; !valid groups idle).
+// The result is returned on the group's lane l8 == 0 (other lanes: unspecified).  s = the row's cosine divisor (0: leave alone).
+__device__ __forceinline__ float rerank_row_dist(const float* __restrict__ row, const float* qv, float s, uint32_t distance_type,
+                                                 uint32_t steps, uint32_t dim_full, int lane, int l8, bool valid) {
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    if (valid) {
+        if (distance_type == VS_L2) {
+            for (uint32_t t = 0; t < steps; ++t) {
+                float4 x = *reinterpret_cast<const float4*>(row + 32 * t + 4 * l8);
+                float4 y = *reinterpret_cast<const float4*>(qv + 32 * t + 4 * l8);
+                float d0 = x.x - y.x, d1 = x.y - y.y, d2 = x.z - y.z, d3 = x.w - y.w;
+                float p0 = d0 * d0, p1 = d1 * d1, p2 = d2 * d2, p3 = d3 * d3;
+                a0 = a0 + p0;
+                a1 = a1 + p1;
+                a2 = a2 + p2;
+                a3 = a3 + p3;
+            }
+        } else {
+            for (uint32_t t = 0; t < steps; ++t) {
+                float4 x = *reinterpret_cast<const float4*>(row + 32 * t + 4 * l8);
+                float4 y = *reinterpret_cast<const float4*>(qv + 32 * t + 4 * l8);
+                if (s != 0.0f) {
+                    x.x = x.x / s;
+                    x.y = x.y / s;
+                    x.z = x.z / s;
+                    x.w = x.w / s;
+                }
+                a0 = __builtin_fmaf(x.x, y.x, a0);
+                a1 = __builtin_fmaf(x.y, y.y, a1);
+                a2 = __builtin_fmaf(x.z, y.z, a2);
+                a3 = __builtin_fmaf(x.w, y.w, a3);
+            }
+        }
+    }
+    // horizontal_add_ps of accumulator j lives on lanes (2j, 2j+1) of the 8-lane group:
+    // s_c = a_c + a_{c+4}; h = (s0+s1)+(s2+s3)
+    float s0 = a0 + shfl_f(a0, lane ^ 1);
+    float s1 = a1 + shfl_f(a1, lane ^ 1);
+    float s2 = a2 + shfl_f(a2, lane ^ 1);
+    float s3 = a3 + shfl_f(a3, lane ^ 1);
+    float t0 = s0 + s1;
+    float t1 = s2 + s3;
+    float h = t0 + t1;
+    const int g0 = lane & ~7;
+    float h0 = shfl_f(h, g0 + 0), h1 = shfl_f(h, g0 + 2), h2 = shfl_f(h, g0 + 4), h3 = shfl_f(h, g0 + 6);
+    float dist = h0 + h1;
+    dist = dist + h2;
+    dist = dist + h3;
+    float r = dist;
+    if (valid && l8 == 0) {
+        for (uint32_t i = steps * 32; i < dim_full; ++i) {  // scalar tail, in element order
+            float x = row[i];
+            if (distance_type == VS_L2) {
+                float diff = x - qv[i];
+                float p = diff * diff;
+                dist = dist + p;
+            } else {
+                if (s != 0.0f) x = x / s;
+                float p = x * qv[i];
+                dist = dist + p;
+            }
+        }
+        if (distance_type == VS_L2) r = dist;
+        else if (distance_type == VS_IP) r = -dist;
+        else r = fmaxf(1.0f - dist, 0.0f);
+    }
+    return r;
+}
+
 __global__ __launch_bounds__(256) void k_rerank(const float* __restrict__ vecs, uint32_t vec_stride, uint32_t dim_full,
                                                 const float* __restrict__ vnorm, uint32_t distance_type,
                                                 const float* __restrict__ q_full, const uint32_t* __restrict__ ids,
@@ -209,69 +358,10 @@ __global__ __launch_bounds__(256) void k_rerank(const float* __restrict__ vecs, 
         const float* row = vecs + (size_t)(valid ? id : 0) * vec_stride;
         float s = 0.0f;
         if (valid && distance_type == VS_COSINE) s = vnorm[id];
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-        if (valid) {
-            if (distance_type == VS_L2) {
-                for (uint32_t t = 0; t < steps; ++t) {
-                    float4 x = *reinterpret_cast<const float4*>(row + 32 * t + 4 * l8);
-                    float4 y = *reinterpret_cast<const float4*>(qv + 32 * t + 4 * l8);
-                    float d0 = x.x - y.x, d1 = x.y - y.y, d2 = x.z - y.z, d3 = x.w - y.w;
-                    float p0 = d0 * d0, p1 = d1 * d1, p2 = d2 * d2, p3 = d3 * d3;
-                    a0 = a0 + p0;
-                    a1 = a1 + p1;
-                    a2 = a2 + p2;
-                    a3 = a3 + p3;
-                }
-            } else {
-                for (uint32_t t = 0; t < steps; ++t) {
-                    float4 x = *reinterpret_cast<const float4*>(row + 32 * t + 4 * l8);
-                    float4 y = *reinterpret_cast<const float4*>(qv + 32 * t + 4 * l8);
-                    if (s != 0.0f) {
-                        x.x = x.x / s;
-                        x.y = x.y / s;
-                        x.z = x.z / s;
-                        x.w = x.w / s;
-                    }
-                    a0 = __builtin_fmaf(x.x, y.x, a0);
-                    a1 = __builtin_fmaf(x.y, y.y, a1);
-                    a2 = __builtin_fmaf(x.z, y.z, a2);
-                    a3 = __builtin_fmaf(x.w, y.w, a3);
-                }
-            }
-        }
-        // horizontal_add_ps of accumulator j lives on lanes (2j, 2j+1) of the 8-lane group:
-        // s_c = a_c + a_{c+4}; h = (s0+s1)+(s2+s3)
-        float s0 = a0 + shfl_f(a0, lane ^ 1);
-        float s1 = a1 + shfl_f(a1, lane ^ 1);
-        float s2 = a2 + shfl_f(a2, lane ^ 1);
-        float s3 = a3 + shfl_f(a3, lane ^ 1);
-        float t0 = s0 + s1;
-        float t1 = s2 + s3;
-        float h = t0 + t1;
-        const int g0 = lane & ~7;
-        float h0 = shfl_f(h, g0 + 0), h1 = shfl_f(h, g0 + 2), h2 = shfl_f(h, g0 + 4), h3 = shfl_f(h, g0 + 6);
-        float dist = h0 + h1;
-        dist = dist + h2;
-        dist = dist + h3;
-        if (valid && l8 == 0) {
-            for (uint32_t i = steps * 32; i < dim_full; ++i) {  // scalar tail, in element order
-                float x = row[i];
-                if (distance_type == VS_L2) {
-                    float diff = x - qv[i];
-                    float p = diff * diff;
-                    dist = dist + p;
-                } else {
-                    if (s != 0.0f) x = x / s;
-                    float p = x * qv[i];
-                    dist = dist + p;
-                }
-            }
-            float r;
-            if (distance_type == VS_L2) r = dist;
-            else if (distance_type == VS_IP) r = -dist;
-            else r = fmaxf(1.0f - dist, 0.0f);
-            out[j] = r;
-        }
+        const float r = rerank_row_dist(row, qv, s, distance_type, steps, dim_full, lane, l8, valid);
+        // (a row without a node is skipped, as ever: its slot of `out` keeps what it held.  The search kernels never emit one inside
+        // cnt[q]; k_rerank_window gives such a row NaN, which no window of real rows would tell apart)
+        if (valid && l8 == 0) out[j] = r;
     }
 }
 
@@ -337,6 +427,58 @@ __device__ __forceinline__ int32_t total_key(float f) {
     return b;
 }
 
+// The window as the reference runs it: pushes while the heap holds fewer than `rescore` entries and the stream has rows, then one pop
+// per output row.  h: room for `rescore` entries; sd: the n reranked distances in stream order; emit(sp) takes the stream position of
+// every row popped.  Returns the number of rows popped (<= k).  Serial: one thread.
+template <class Emit>
+__device__ __forceinline__ uint32_t window_replay(uint64_t* h, const float* sd, uint32_t n, uint32_t rescore, uint32_t k, Emit emit) {
+    uint32_t produced = 0, len = 0, pos = 0;
+    // le(a,b) (Rust a <= b for ResortData) == key(b) <= key(a)
+    auto kof = [](uint64_t e) { return (int32_t)(uint32_t)(e >> 32); };
+    auto sift_up = [&](uint32_t p, uint64_t elem) {
+        while (p > 0) {
+            uint32_t parent = (p - 1) >> 1;
+            uint64_t pe = h[parent];
+            if (kof(pe) <= kof(elem)) break;  // elem <= parent
+            h[p] = pe;
+            p = parent;
+        }
+        h[p] = elem;
+    };
+    while (produced < k) {
+        while (len < rescore && pos < n) {
+            uint64_t e = ((uint64_t)(uint32_t)total_key(sd[pos]) << 32) | pos;
+            uint32_t p = len++;
+            sift_up(p, e);
+            ++pos;
+        }
+        if (len == 0) break;
+        uint64_t item = h[--len];
+        uint64_t top = item;
+        if (len > 0) {
+            top = h[0];
+            uint32_t end = len, p = 0, child = 1;
+            uint32_t lim = end >= 2 ? end - 2 : 0;
+            while (child <= lim) {
+                uint64_t le = h[child], ri = h[child + 1];
+                uint32_t pick = (kof(ri) <= kof(le)) ? 1u : 0u;  // data[child] <= data[child+1]
+                child += pick;
+                h[p] = pick ? ri : le;
+                p = child;
+                child = 2 * p + 1;
+            }
+            if (child == end - 1) {
+                h[p] = h[child];
+                p = child;
+            }
+            sift_up(p, item);
+        }
+        emit((uint32_t)top);
+        ++produced;
+    }
+    return produced;
+}
+
 __global__ void k_resort(uint32_t nq, uint32_t M, uint32_t rescore, uint32_t k, const uint32_t* __restrict__ stream,
                          const uint32_t* __restrict__ cnt, const float* __restrict__ dist, const uint64_t* __restrict__ tids,
                          uint64_t* __restrict__ heap_ws, uint32_t* __restrict__ out_ids, uint64_t* __restrict__ out_tids,
@@ -363,60 +505,195 @@ __global__ void k_resort(uint32_t nq, uint32_t M, uint32_t rescore, uint32_t k, 
             }
         }
     } else {
-        uint64_t* h = heap_ws + (size_t)q * rescore;
-        uint32_t len = 0, pos = 0;
-        // le(a,b) (Rust a <= b for ResortData) == key(b) <= key(a)
-        auto kof = [](uint64_t e) { return (int32_t)(uint32_t)(e >> 32); };
-        auto sift_up = [&](uint32_t p, uint64_t elem) {
-            while (p > 0) {
-                uint32_t parent = (p - 1) >> 1;
-                uint64_t pe = h[parent];
-                if (kof(pe) <= kof(elem)) break;  // elem <= parent
-                h[p] = pe;
-                p = parent;
-            }
-            h[p] = elem;
-        };
-        while (produced < k) {
-            while (len < rescore && pos < n) {
-                uint64_t e = ((uint64_t)(uint32_t)total_key(sd[pos]) << 32) | pos;
-                uint32_t p = len++;
-                sift_up(p, e);
-                ++pos;
-            }
-            if (len == 0) break;
-            uint64_t item = h[--len];
-            uint64_t top = item;
-            if (len > 0) {
-                top = h[0];
-                uint32_t end = len, p = 0, child = 1;
-                uint32_t lim = end >= 2 ? end - 2 : 0;
-                while (child <= lim) {
-                    uint64_t le = h[child], ri = h[child + 1];
-                    uint32_t pick = (kof(ri) <= kof(le)) ? 1u : 0u;  // data[child] <= data[child+1]
-                    child += pick;
-                    h[p] = pick ? ri : le;
-                    p = child;
-                    child = 2 * p + 1;
-                }
-                if (child == end - 1) {
-                    h[p] = h[child];
-                    p = child;
-                }
-                sift_up(p, item);
-            }
-            uint32_t sp = (uint32_t)top;
+        uint32_t row = 0;
+        produced = window_replay(heap_ws + (size_t)q * rescore, sd, n, rescore, k, [&](uint32_t sp) {
             uint32_t id = sid[sp];
-            out_ids[(size_t)q * k + produced] = id;
-            if (out_tids) out_tids[(size_t)q * k + produced] = tids[id];
-            if (out_dist) out_dist[(size_t)q * k + produced] = sd[sp];
-            ++produced;
-        }
+            out_ids[(size_t)q * k + row] = id;
+            if (out_tids) out_tids[(size_t)q * k + row] = tids[id];
+            if (out_dist) out_dist[(size_t)q * k + row] = sd[sp];
+            ++row;
+        });
     }
     for (; produced < k; ++produced) {
         out_ids[(size_t)q * k + produced] = VS_INVALID_NODE;
         if (out_tids) out_tids[(size_t)q * k + produced] = 0;
         if (out_dist) out_dist[(size_t)q * k + produced] = __int_as_float(0x7fc00000);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// K2 + window in one launch (the batch path, rescore > 0): k_rerank's shape and row-distance code, but the distances of the scan's
+// n <= M stream rows stay in LDS and wave 0 runs the rescore window over them after a barrier, while the other workgroups of the CU
+// keep the memory system busy.  No rr_dist round trip, no heap in global memory, no second launch.
+//
+// The window is selected wave-parallel: pop i of the reference happens when stream positions < min(rescore + i, n) have been
+// pushed, and returns an entry with the smallest key among those not popped yet.  While that smallest key is held by ONE live
+// entry, every BinaryHeap layout must return that entry (a heap's pop returns a greatest element of the order, and here there is
+// only one), so the set of live entries after the pop does not depend on the layout either; by induction over the pops the
+// selection equals the replay as long as every pop so far found its minimum unique.  Equal keys that are not the minimum of a pop
+// decide nothing at that pop — they are seen when (if) they become the minimum of a later one.  The first pop whose minimum is
+// held by more than one live entry is where the layout starts to matter: the scan is then replayed serially from the start
+// (window_replay on an LDS heap), which is k_resort's own sequence.  mode 2 forces the replay for every scan (A/B, tests).
+// LDS: [vec_stride] f32 query | [rescore] u64 heap | [M] f32 distances | [k + 1] u32 stream positions of the rows, row count.
+// ---------------------------------------------------------------------------------------------------------------
+__host__ __device__ static inline size_t rerank_window_lds(uint32_t vec_stride, uint32_t M, uint32_t rescore, uint32_t k) {
+    return (size_t)vec_stride * 4 + (size_t)rescore * 8 + (size_t)M * 4 + ((size_t)k + 1) * 4;
+}
+
+__global__ __launch_bounds__(256, 6) void k_rerank_window(const float* __restrict__ vecs, uint32_t vec_stride, uint32_t dim_full,
+                                                       const float* __restrict__ vnorm, uint32_t distance_type,
+                                                       const float* __restrict__ q_full, const uint32_t* __restrict__ stream,
+                                                       const uint32_t* __restrict__ cnt, uint32_t M, uint32_t rescore, uint32_t k,
+                                                       uint32_t nq, const uint64_t* __restrict__ tids, uint32_t* __restrict__ out_ids,
+                                                       uint64_t* __restrict__ out_tids, float* __restrict__ out_dist, uint32_t mode) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float* qv = reinterpret_cast<float*>(smem);
+    uint64_t* hh = reinterpret_cast<uint64_t*>(qv + vec_stride);  // (vec_stride is a multiple of 4 floats)
+    float* sd = reinterpret_cast<float*>(hh + rescore);
+    uint32_t* sps = reinterpret_cast<uint32_t*>(sd + M);
+    const uint32_t q = blockIdx.x;
+    if (q >= nq) return;
+    for (uint32_t i = threadIdx.x; i < vec_stride; i += blockDim.x) qv[i] = q_full[(size_t)q * vec_stride + i];
+    const uint32_t n = min(cnt[q], M);
+    const uint32_t* sid = stream + (size_t)q * M;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int l8 = lane & 7, grp = lane >> 3;
+    const uint32_t steps = dim_full / 32;
+    for (uint32_t base = 0; base < n; base += 32) {
+        const uint32_t j = base + (uint32_t)(wave * 8 + grp);
+        bool valid = j < n;
+        const uint32_t id = valid ? sid[j] : VS_INVALID_NODE;
+        if (id == VS_INVALID_NODE) valid = false;
+        const float* row = vecs + (size_t)(valid ? id : 0) * vec_stride;
+        float s = 0.0f;
+        if (valid && distance_type == VS_COSINE) s = vnorm[id];
+        const float r = rerank_row_dist(row, qv, s, distance_type, steps, dim_full, lane, l8, valid);
+        if (j < n && l8 == 0) sd[j] = valid ? r : __int_as_float(0x7fc00000);
+    }
+    __syncthreads();
+    if (wave == 0) {
+        bool replay = mode == 2;
+        uint32_t produced = 0;
+        if (!replay) {
+            uint64_t taken = 0;  // bit j: this lane's position lane + 64 j has been popped (M <= 4096)
+            for (uint32_t i = 0; i < k; ++i) {
+                const uint32_t limit = min(rescore + i, n);
+                if (limit <= i) break;  // the heap is empty
+                const int64_t none = 0x7fffffffffffffffll;
+                int64_t best = none;
+                uint32_t bj = 0, c = 0;
+                for (uint32_t j = 0, p = (uint32_t)lane; p < limit; ++j, p += 64) {
+                    if ((taken >> j) & 1ull) continue;
+                    const int64_t key = total_key(sd[p]);
+                    if (key < best) {
+                        best = key;
+                        bj = j;
+                        c = 1;
+                    } else if (key == best) {
+                        ++c;
+                    }
+                }
+                int64_t wbest = best;
+                for (int m = 1; m < WAVE; m <<= 1) {
+                    const int64_t o = __shfl_xor(wbest, m, WAVE);
+                    wbest = o < wbest ? o : wbest;
+                }
+                const bool mine = best == wbest && best != none;
+                const uint64_t holders = __ballot(mine);
+                if (__popcll(holders) != 1 || __ballot(mine && c > 1) != 0) {
+                    replay = true;
+                    break;
+                }
+                if (mine) {
+                    taken |= 1ull << bj;
+                    sps[i] = (uint32_t)lane + 64u * bj;
+                }
+                ++produced;
+            }
+        }
+        if (replay && lane == 0) {  // (from the start: rows selected before the tie are produced again)
+            uint32_t row = 0;
+            produced = window_replay(hh, sd, n, rescore, k, [&](uint32_t sp) { sps[row++] = sp; });
+        }
+        if (lane == 0) sps[k] = produced;
+    }
+    __syncthreads();
+    if (wave == 0) {
+        const uint32_t produced = sps[k];
+        for (uint32_t j = (uint32_t)lane; j < k; j += WAVE) {
+            uint32_t id = VS_INVALID_NODE;
+            uint64_t tid = 0;
+            float d = __int_as_float(0x7fc00000);
+            if (j < produced) {
+                const uint32_t sp = sps[j];
+                id = sid[sp];
+                if (out_tids) tid = tids[id];
+                d = sd[sp];
+            }
+            out_ids[(size_t)q * k + j] = id;
+            if (out_tids) out_tids[(size_t)q * k + j] = tid;
+            if (out_dist) out_dist[(size_t)q * k + j] = d;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// What a batch's finish needs of the per-scan arrays (work counters [nq][ST_N], fallback marks, stream lengths, status words), summed
+// on the device into RED_N u64 words: a few hundred bytes go to the host instead of nq x 44 B.  All integer: sums of u32 counters are
+// exact in u64, so the doubles the host derives (mean / maximum of the inserted ids) are the ones it used to compute from the copies.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_reduce_stats(const uint32_t* __restrict__ stats, const uint32_t* __restrict__ fb,
+                                                      const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ status, uint32_t nq,
+                                                      uint32_t M, uint32_t rescore, uint32_t windowed, uint32_t has_visible,
+                                                      uint32_t ins_limit, unsigned long long* __restrict__ red) {
+    unsigned long long v[RED_N];
+    for (int i = 0; i < RED_N; ++i) v[i] = 0;
+    for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += gridDim.x * blockDim.x) {
+        const uint4 lo = *reinterpret_cast<const uint4*>(stats + (size_t)q * ST_N);
+        const uint4 hi = *reinterpret_cast<const uint4*>(stats + (size_t)q * ST_N + 4);
+        static_assert(ST_N == 8 && ST_VISITS == 0 && ST_CAND == 1 && ST_DQ == 2 && ST_READS == 3 && ST_NEXT == 4 && ST_INVIS == 6 && ST_INS == 7,
+                      "k_reduce_stats reads a scan's counters as two uint4");
+        const uint32_t visits = lo.x, cand = lo.y, dq = lo.z, reads = lo.w, next = hi.x, invis = hi.z, ins = hi.w;
+        const uint32_t f = fb ? fb[q] : 0u, cq = cnt[q];
+        v[RED_STATUS] |= status[q];
+        v[RED_VISITS] += visits;
+        v[RED_CAND] += cand;
+        v[RED_DQ] += dq;
+        v[RED_READS] += reads;
+        unsigned long long next_calls = next;
+        if (windowed && cq < M && next > 0) {
+            // an exhausted stream under next_with_resort: see collect_stats
+            const long long C = cq, S = rescore, kk = (long long)M - rescore + 1;
+            const long long J = kk < C + 1 ? kk : C + 1, j0 = C - S + 2 > 1 ? C - S + 2 : 1;
+            const long long extra = J - j0 + 1 > 1 ? J - j0 + 1 : 1;
+            next_calls = next_calls - 1 + (unsigned long long)extra;
+        }
+        v[RED_NEXT] += next_calls;
+        if (f) {
+            v[RED_FB_SCANS] += 1;
+            v[RED_FB_VISITS] += visits;
+            v[RED_FB_DQ] += dq;
+            v[RED_INS_OV] += 1;
+        } else {
+            v[RED_INS_SUM] += ins;
+            v[RED_INS_FAST] += 1;
+            v[RED_INS_OV] += ins > ins_limit ? 1u : 0u;
+        }
+        v[RED_INS_MAX] = v[RED_INS_MAX] > ins ? v[RED_INS_MAX] : ins;
+        if (windowed) v[RED_HEAP_ROWS] += min(cq, M) + (has_visible ? invis : 0u);
+    }
+    for (int i = 0; i < RED_N; ++i) {
+        unsigned long long x = v[i];
+        for (int m = 1; m < WAVE; m <<= 1) {
+            const unsigned long long o = __shfl_xor(x, m, WAVE);
+            x = i == RED_STATUS ? (x | o) : i == RED_INS_MAX ? (x > o ? x : o) : x + o;
+        }
+        if ((threadIdx.x & 63) == 0 && x) {
+            if (i == RED_STATUS) atomicOr(&red[i], x);
+            else if (i == RED_INS_MAX) atomicMax(&red[i], x);
+            else atomicAdd(&red[i], x);
+        }
     }
 }
 
@@ -624,12 +901,30 @@ static float count_as_f32(uint64_t c) { return (float)c; }
 int launch_prepare_queries(vs_index* idx, const float* d_raw, uint32_t nq, float* d_q_full, uint64_t* d_qcodes) {
     if (nq == 0) return VS_OK;
     const vs_index_desc& d = idx->d;
-    size_t lds = (round_up_u32(d.dim_full, 4) + round_up_u32(d.dim_index, 4) + 4) * sizeof(float);
+    const uint32_t words = d.storage_type == VS_STORAGE_PLAIN ? 0u : d.words;  // plain: no SBQ code
+    const bool same = d.dim_full == d.dim_index, multi = words && d.bits != 1;
+    const uint32_t rf = round_up_u32(d.dim_full, 4), ri = round_up_u32(d.dim_index, 4);
+    const size_t shared = ((words ? ri : 0u) + (multi ? ri : 0u)) * sizeof(float);
+    const size_t per_wave = ((size_t)rf + (same ? 0u : ri) + (multi ? ri : 0u) + 4u) * sizeof(float);
+    // four queries in flight per workgroup while their slices fit the 64 KB a launch gets without opting in
+    uint32_t nw = nq >= 4 ? 4 : nq >= 2 ? 2 : 1;
+    while (nw > 1 && shared + nw * per_wave > 64 * 1024) nw >>= 1;
+    const size_t lds = shared + nw * per_wave;
     VS_REQUIRE(lds <= 160 * 1024, "query too large for LDS staging (%u dims)", d.dim_full);
-    hipLaunchKernelGGL(k_prepare_queries, dim3(nq), dim3(WAVE), lds, idx->ctx->stream, d_raw, nq, d.dim_full,
+    if (lds > 64 * 1024) {  // (one very wide query per workgroup: beyond what a launch gets without opting in)
+        static DeviceOnce attr_set;
+        if (attr_set.pending(idx->ctx->device)) {
+            VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_prepare_queries), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            attr_set.done(idx->ctx->device);
+        }
+    }
+    // rounds: the per-workgroup staging is shared by nw x rounds queries, the grid still covers the device several times over
+    const uint32_t rounds = nq >= 65536 ? 4 : nq >= 8192 ? 2 : 1;
+    const uint32_t grid = (nq + nw * rounds - 1) / (nw * rounds);
+    const uint32_t vec4 = (d.dim_full % 4 == 0 && ((uintptr_t)d_raw & 15) == 0) ? 1u : 0u;
+    hipLaunchKernelGGL(k_prepare_queries, dim3(grid), dim3(nw * WAVE), lds, idx->ctx->stream, d_raw, nq, d.dim_full,
                        d.dim_index, idx->vec_stride, d.distance_type, d.bits, idx->mean, idx->m2,
-                       count_as_f32(idx->count), d.storage_type == VS_STORAGE_PLAIN ? 0u : d.words /* plain: no SBQ code */,
-                       idx->code_stride, d_q_full, d_qcodes);
+                       count_as_f32(idx->count), words, idx->code_stride, rounds, vec4, d_q_full, d_qcodes);
     VS_HIP(hipGetLastError());
     return VS_OK;
 }
@@ -686,6 +981,41 @@ int launch_resort(vs_index* idx, uint32_t nq, uint32_t M, uint32_t rescore, uint
                                      ? (const uint32_t*)idx->ws.stream_ham.p : nullptr;
     hipLaunchKernelGGL(k_resort, dim3((nq + 63) / 64), dim3(64), 0, idx->ctx->stream, nq, M, rescore, k, d_stream_ids,
                        d_cnt, d_dist, idx->tids, d_heap_ws, d_out_ids, d_out_tids, d_out_dist, plain_keys);
+    VS_HIP(hipGetLastError());
+    return VS_OK;
+}
+
+// The fused kernel keeps one query, one window heap and M distances in LDS.  Registers, not waves, limit both kernels: k_rerank takes
+// 80 VGPRs = 6 waves per SIMD = 6 workgroups of 256 threads per CU, and k_rerank_window is held to the same 80 (launch bounds: 6 waves
+// per SIMD; no scratch — left alone the compiler takes 92 and one workgroup fewer).  Six workgroups share the CU's 160 KB of LDS while
+// each stays under 160 / 6 = 26.6 KB; the fused kernel is taken up to 24 KB (room for the allocation granule): 12 M + 3 KB at 768
+// dimensions, M <= ~1 790 — every rescore the GUC allows (<= 1000) with k up to several hundred.  Beyond that (and past 4096
+// rows, the width of the per-lane pop masks) the pair runs.
+bool rerank_window_fits(const vs_index* idx, uint32_t M, uint32_t rescore, uint32_t k) {
+    return M <= 4096 && rerank_window_lds(idx->vec_stride, M, rescore, k) <= 24 * 1024;
+}
+
+int launch_rerank_window(vs_index* idx, const float* d_q_full, const uint32_t* d_stream_ids, const uint32_t* d_cnt, uint32_t M,
+                         uint32_t rescore, uint32_t k, uint32_t nq, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist,
+                         uint32_t mode) {
+    if (nq == 0) return VS_OK;
+    VS_REQUIRE(idx->vecs != nullptr, "index has no vector column: rerank impossible");
+    VS_REQUIRE(rescore > 0 && rerank_window_fits(idx, M, rescore, k), "fused rerank: window of %u rows does not fit", M);
+    const size_t lds = rerank_window_lds(idx->vec_stride, M, rescore, k);
+    hipLaunchKernelGGL(k_rerank_window, dim3(nq), dim3(256), lds, idx->ctx->stream, idx->vecs, idx->vec_stride, idx->d.dim_full,
+                       idx->vnorm, idx->d.distance_type, d_q_full, d_stream_ids, d_cnt, M, rescore, k, nq, idx->tids, d_out_ids,
+                       d_out_tids, d_out_dist, mode);
+    VS_HIP(hipGetLastError());
+    return VS_OK;
+}
+
+// d_red: RED_N u64 words, zeroed by the caller on the same stream
+int launch_reduce_stats(vs_index* idx, const uint32_t* d_stats, const uint32_t* d_fb, const uint32_t* d_cnt, const uint32_t* d_status,
+                        uint32_t nq, uint32_t M, uint32_t rescore, bool windowed, uint32_t ins_limit, uint64_t* d_red) {
+    if (nq == 0) return VS_OK;
+    const uint32_t blocks = (nq + 255) / 256 < 256 ? (nq + 255) / 256 : 256;
+    hipLaunchKernelGGL(k_reduce_stats, dim3(blocks), dim3(256), 0, idx->ctx->stream, d_stats, d_fb, d_cnt, d_status, nq, M, rescore,
+                       windowed ? 1u : 0u, idx->visible ? 1u : 0u, ins_limit, (unsigned long long*)d_red);
     VS_HIP(hipGetLastError());
     return VS_OK;
 }
