@@ -111,7 +111,11 @@ const char* vs_last_error(void);
  * own GUCs, diskann.query_search_list_size and diskann.query_rescore, are arguments of vs_rescan / vs_search_batch).  Thread safe.
  * vs_get_option: 1 = set (copied to out, truncated to cap), 0 = set nowhere (out = "").
  * VS_RERANK_FUSED: how a batch reranks and runs the rescore window — "1" (default) one fused launch, "2" fused with the serial heap
- * replay for every scan, "0" the separate rerank and window kernels; the rows are the same under all three. */
+ * replay for every scan, "0" the separate rerank and window kernels; the rows are the same under all three.
+ * VS_RERANK_ORDER: the order in which a batch's rerank takes its scans — "1" (default) grouped by corpus neighbourhood when the batch
+ * re-reads rows (nq x rows per scan >= 2 n and nq >= 16384), "2" always, "0" never (the scans' own order).  VS_RERANK_SEEDS (default
+ * 1024, up to 4096) corpus rows define the neighbourhoods; VS_RERANK_DEAL "0" keeps the order but not the per-XCD split.  The rows
+ * returned are the same, bit for bit, under every setting. */
 int vs_set_option(const char* name, const char* value);
 int vs_get_option(const char* name, char* out, size_t cap);
 const char* vs_version(void);
@@ -180,6 +184,9 @@ enum vs_array { VS_ARR_CODES = 0, VS_ARR_NBRS = 1, VS_ARR_TIDS = 2, VS_ARR_VECS 
                 VS_ARR_VNORM = 6, VS_ARR_LABEL_OFF = 7, VS_ARR_LABEL_VAL = 8 };
 /* device pointer + row stride (in elements) of one of the index arrays */
 int vs_index_array(const vs_index* idx, int which, void** dev_ptr, uint32_t* row_stride);
+/* diagnostics: the rerank order of the handle's last batch (VS_RERANK_ORDER) — place -> scan number, *out_n entries (0: that batch
+ * took the scans' own order), at most cap of them copied to out_perm.  Synchronises the stream. */
+int vs_index_rerank_order(vs_index* idx, uint32_t* out_perm, uint32_t cap, uint32_t* out_n);
 int vs_index_set_quantizer(vs_index* idx, const float* mean, const float* m2, uint64_t count);
 int vs_index_set_start_nodes(vs_index* idx, uint32_t default_start, const int16_t* labels, const uint32_t* nodes, uint32_t n);
 int vs_index_set_labels(vs_index* idx, const uint32_t* label_off, const int16_t* label_val);

@@ -151,6 +151,7 @@ SYMBOLS = {
     "vs_index_prepare_workspace": (_i, [_vp]),
     "vs_index_get_desc": (_i, [_vp, C.POINTER(IndexDesc)]),
     "vs_index_array": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_u32)]),
+    "vs_index_rerank_order": (_i, [_vp, _vp, _u32, C.POINTER(_u32)]),
     "vs_index_set_quantizer": (_i, [_vp, _vp, _vp, _u64]),
     "vs_index_set_start_nodes": (_i, [_vp, _u32, _vp, _vp, _u32]),
     "vs_index_set_labels": (_i, [_vp, _vp, _vp]),

@@ -465,7 +465,7 @@ extern "C" void vs_index_free(vs_index* ix) {
     SearchWorkspace& w = ix->ws;
     DevBuf* bufs[] = {&w.q_full, &w.qcodes, &w.qlabels, &w.qlabel_off, &w.hash, &w.heap_g, &w.heap_g4, &w.ghash4, &w.heap_g4b, &w.ghash4b, &w.pool_ctr, &w.fb_flag, &w.phase, &w.timeline, &w.raw_q2, &w.out_ids2, &w.out_tids2, &w.out_dist2, &w.stream_ids,
                       &w.stream_ham, &w.stream_cnt, &w.stats, &w.status, &w.rr_dist, &w.out_ids, &w.out_tids,
-                      &w.out_dist, &w.resort_heap, &w.raw_q, &w.misc, &w.q_index, &w.red};
+                      &w.out_dist, &w.resort_heap, &w.raw_q, &w.misc, &w.q_index, &w.red, &w.order_work, &w.order_perm};
     for (DevBuf* b : bufs) devbuf_free(*b);
     if (w.red_host) (void)hipHostFree(w.red_host);
     w.red_host = nullptr;

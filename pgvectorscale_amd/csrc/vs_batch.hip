@@ -158,6 +158,31 @@ struct PendingBatch {
     float* d_out_dist;
 };
 
+// VS_RERANK_ORDER: whether this batch's rerank takes its scans in the order of their corpus neighbourhood (k_scan_regions), and with
+// how many seed rows (0 = no: the launch is the plain one, nothing else runs).  0 = never, 2 = whenever the kernel can tile the
+// index's codes, 1 (default) = by rule: the ordering pays when rows are fetched several times per batch (expected fetches per corpus
+// row nq * M / n >= ORDER_MIN_REUSE) and the batch fills the device many times over (nq >= ORDER_MIN_NQ); below that the keys and the
+// sort cost more than the cache hits can return.  Measured at 4M (6.7 fetches per row, 262 144 scans: profiles/r08); the thresholds
+// themselves are reasoned, not yet measured at their edge.
+static const double ORDER_MIN_REUSE = 2.0;
+static const uint32_t ORDER_MIN_NQ = 16384;
+static uint32_t rerank_order_seeds(const vs_index* ix, uint32_t nq, uint32_t M) {
+    const uint32_t mode = env_u32("VS_RERANK_ORDER", 1);
+    if (mode == 0 || !scan_order_fits(ix)) return 0;
+    if (mode == 1 && (nq < ORDER_MIN_NQ || (double)nq * M < ORDER_MIN_REUSE * (double)ix->d.n)) return 0;
+    const uint32_t S = std::min<uint32_t>(std::max<uint32_t>(env_u32("VS_RERANK_SEEDS", 1024), 1), 4096);
+    return std::min<uint32_t>(S, ix->d.n);
+}
+
+extern "C" int vs_index_rerank_order(vs_index* ix, uint32_t* out_perm, uint32_t cap, uint32_t* out_n) {
+    VS_REQUIRE(ix && out_n && (cap == 0 || out_perm), "vs_index_rerank_order: bad args");
+    VS_HIP(hipStreamSynchronize(ix->ctx->stream));
+    *out_n = ix->ws.order_nq;
+    const uint32_t m = std::min(cap, ix->ws.order_nq);
+    if (m) VS_HIP(hipMemcpy(out_perm, ix->ws.order_perm.p, (size_t)m * 4, hipMemcpyDeviceToHost));
+    return VS_OK;
+}
+
 static int run_post_search(vs_index* ix, const BatchPlan& bp, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist) {
     vs_ctx* c = ix->ctx;
     SearchWorkspace& w = ix->ws;
@@ -165,6 +190,19 @@ static int run_post_search(vs_index* ix, const BatchPlan& bp, uint32_t* d_out_id
     if (bp.stream_only) return VS_OK;
     if (bp.rescore > 0) {
         VS_REQUIRE(ix->vecs, "diskann.query_rescore > 0 needs the heap vector column on the device");
+        const uint32_t* perm = nullptr;
+        bool deal = false;
+        w.order_nq = 0;
+        if (const uint32_t S = rerank_order_seeds(ix, nq, M)) {
+            VS_TRY(devbuf_reserve(c, w.order_work, scan_order_work_bytes(nq, S)));
+            VS_TRY(devbuf_reserve(c, w.order_perm, (size_t)nq * 4));
+            hipEvent_t ev = prof_begin(c);
+            VS_TRY(launch_scan_order(ix, (const uint64_t*)w.qcodes.p, nq, S, (uint32_t*)w.order_work.p, (uint32_t*)w.order_perm.p));
+            prof_end(c, PK_ORDER, ev);
+            perm = (const uint32_t*)w.order_perm.p;
+            w.order_nq = nq;
+            deal = env_u32("VS_RERANK_DEAL", 1) != 0;  // (0: the order without the per-XCD eighths, for A/B)
+        }
         // VS_RERANK_FUSED (default 1): rerank and rescore window in one launch, distances and heap in LDS (k_rerank_window); 2 = the
         // same with the serial heap replay forced for every scan; 0 = the k_rerank + k_resort pair, which also takes the windows
         // that do not fit the fused kernel's LDS budget (rerank_window_fits)
@@ -172,7 +210,7 @@ static int run_post_search(vs_index* ix, const BatchPlan& bp, uint32_t* d_out_id
         if (fused && rerank_window_fits(ix, M, bp.rescore, bp.k)) {
             hipEvent_t ev = prof_begin(c);
             VS_TRY(launch_rerank_window(ix, (const float*)w.q_full.p, (const uint32_t*)w.stream_ids.p, (const uint32_t*)w.stream_cnt.p, M,
-                                        bp.rescore, bp.k, nq, d_out_ids, d_out_tids, d_out_dist, fused == 2 ? 2u : 1u));
+                                        bp.rescore, bp.k, nq, d_out_ids, d_out_tids, d_out_dist, fused == 2 ? 2u : 1u, perm, deal));
             prof_end(c, PK_RERANK, ev);
             return VS_OK;
         }
@@ -180,7 +218,7 @@ static int run_post_search(vs_index* ix, const BatchPlan& bp, uint32_t* d_out_id
         VS_TRY(devbuf_reserve(c, w.resort_heap, (size_t)nq * bp.rescore * 8));
         hipEvent_t ev = prof_begin(c);
         VS_TRY(launch_rerank(ix, (const float*)w.q_full.p, (const uint32_t*)w.stream_ids.p, nullptr,
-                             (const uint32_t*)w.stream_cnt.p, M, nq, (float*)w.rr_dist.p));
+                             (const uint32_t*)w.stream_cnt.p, M, nq, (float*)w.rr_dist.p, 0, perm, deal));
         prof_end(c, PK_RERANK, ev);
     }
     hipEvent_t ev = prof_begin(c);

@@ -88,7 +88,7 @@ struct vs_ctx {
     double prof_ms[8] = {0};
     uint64_t prof_launches[8] = {0};
 };
-enum { PK_PREPARE = 0, PK_SEARCH = 1, PK_RERANK = 2, PK_RESORT = 3, PK_SEARCH_FB = 4, PK_SCAN = 5 };
+enum { PK_PREPARE = 0, PK_SEARCH = 1, PK_RERANK = 2, PK_RESORT = 3, PK_SEARCH_FB = 4, PK_SCAN = 5, PK_ORDER = 6 };
 hipEvent_t prof_begin(vs_ctx* c);
 void prof_end(vs_ctx* c, int kind, hipEvent_t a);
 
@@ -122,7 +122,9 @@ struct SearchWorkspace {
     DevBuf q_full, qcodes, qlabels, qlabel_off, hash, heap_g, heap_g4, ghash4, heap_g4b, ghash4b, pool_ctr, fb_flag, phase, timeline, stream_ids, stream_ham, stream_cnt, stats, status,
         rr_dist, out_ids, out_tids, out_dist, resort_heap, raw_q, misc, q_index,
         raw_q2, out_ids2, out_tids2, out_dist2,  // second set of a pipelined host batch (search_host)
-        red;                                      // RED_N u64 sums of the last launch's per-scan arrays (k_reduce_stats)
+        red,                                      // RED_N u64 sums of the last launch's per-scan arrays (k_reduce_stats)
+        order_work, order_perm;                   // VS_RERANK_ORDER: keys + counting-sort tables, and the batch's rerank order
+    uint32_t order_nq = 0;         // scans of the last batch's rerank order in order_perm (0: it took the scans' own order)
     uint64_t* red_host = nullptr;  // pinned; the sums land here (this handle's own: two handles of one context may each have a batch in flight)
     // pending async call (vs_search_batch_dev)
     bool fb_valid = false;  // fb_flag holds the fallback marks of the last chunk
@@ -348,7 +350,8 @@ int launch_quantize_rows(vs_index* idx, const float* d_rows, uint32_t row_stride
 int launch_hamming_gather(vs_index* idx, const uint64_t* d_qcodes, const uint32_t* d_ids, const uint32_t* d_off,
                           uint32_t nq, uint32_t* d_out);
 int launch_rerank(vs_index* idx, const float* d_q_full, const uint32_t* d_ids, const uint32_t* d_off,
-                  const uint32_t* d_cnt, uint32_t fixed_m, uint32_t nq, float* d_out, uint32_t row_base = 0);
+                  const uint32_t* d_cnt, uint32_t fixed_m, uint32_t nq, float* d_out, uint32_t row_base = 0,
+                  const uint32_t* d_perm = nullptr, bool deal = false);  // d_perm / deal: as launch_rerank_window
 int launch_search(vs_index* idx, const SearchLaunch& s, bool build_mode = false);
 int launch_resort(vs_index* idx, uint32_t nq, uint32_t M, uint32_t rescore, uint32_t k, const uint32_t* d_stream_ids,
                   const uint32_t* d_cnt, const float* d_dist, uint64_t* d_heap_ws, uint32_t* d_out_ids,
@@ -357,7 +360,12 @@ int launch_resort(vs_index* idx, uint32_t nq, uint32_t M, uint32_t rescore, uint
 bool rerank_window_fits(const vs_index* idx, uint32_t M, uint32_t rescore, uint32_t k);
 int launch_rerank_window(vs_index* idx, const float* d_q_full, const uint32_t* d_stream_ids, const uint32_t* d_cnt, uint32_t M,
                          uint32_t rescore, uint32_t k, uint32_t nq, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist,
-                         uint32_t mode);
+                         uint32_t mode, const uint32_t* d_perm = nullptr, bool deal = false);
+// VS_RERANK_ORDER: the order in which a batch's rerank workgroups take the scans.  d_perm (null = the scans' own order): place ->
+// scan number; deal: workgroup b takes place (b % 8) * ceil(nq / 8) + b / 8, a contiguous eighth of the order per XCD
+bool scan_order_fits(const vs_index* idx);  // the index has codes k_scan_regions can tile (code rows of up to 38 words)
+size_t scan_order_work_bytes(uint32_t nq, uint32_t S);
+int launch_scan_order(vs_index* idx, const uint64_t* d_qcodes, uint32_t nq, uint32_t S, uint32_t* d_work, uint32_t* d_perm);
 // the per-scan arrays a batch's finish reads, summed on the device (k_reduce_stats)
 enum { RED_STATUS = 0, RED_VISITS, RED_CAND, RED_DQ, RED_READS, RED_NEXT, RED_FB_SCANS, RED_FB_VISITS, RED_FB_DQ, RED_HEAP_ROWS,
        RED_INS_SUM, RED_INS_MAX, RED_INS_FAST, RED_INS_OV, RED_N = 16 };

@@ -327,15 +327,29 @@ __device__ __forceinline__ float rerank_row_dist(const float* __restrict__ row, 
     return r;
 }
 
+// Which place of a batch's rerank order workgroup b takes (VS_RERANK_ORDER, k_scan_regions below).  deal == 0: place b.  deal != 0:
+// the hardware hands consecutive workgroups to the 8 XCDs in turn, so workgroup b takes place (b % 8) * ceil(nq / 8) + b / 8 — each
+// XCD walks its own contiguous eighth of the order and scans that share rows meet in one L2.  The grid is 8 * ceil(nq / 8) then; places
+// >= nq do not exist.
+__device__ static inline uint32_t rerank_slot(uint32_t b, uint32_t nq, uint32_t deal) {
+    if (!deal) return b;
+    const uint32_t per = (nq + 7) / 8;
+    return (b & 7u) * per + (b >> 3);
+}
+
+static inline uint32_t rerank_grid(uint32_t nq, bool deal) { return deal ? (nq + 7) / 8 * 8 : nq; }
+
 __global__ __launch_bounds__(256) void k_rerank(const float* __restrict__ vecs, uint32_t vec_stride, uint32_t dim_full,
                                                 const float* __restrict__ vnorm, uint32_t distance_type,
                                                 const float* __restrict__ q_full, const uint32_t* __restrict__ ids,
                                                 const uint32_t* __restrict__ off, const uint32_t* __restrict__ cnt,
-                                                uint32_t fixed_m, uint32_t nq, float* __restrict__ out, uint32_t row_base) {
+                                                uint32_t fixed_m, uint32_t nq, float* __restrict__ out, uint32_t row_base,
+                                                const uint32_t* __restrict__ perm, uint32_t deal) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* qv = reinterpret_cast<float*>(smem);
-    const uint32_t q = blockIdx.x;
-    if (q >= nq) return;
+    const uint32_t slot = rerank_slot(blockIdx.x, nq, deal);
+    if (slot >= nq) return;
+    const uint32_t q = perm ? perm[slot] : slot;
     for (uint32_t i = threadIdx.x; i < vec_stride; i += blockDim.x) qv[i] = q_full[(size_t)q * vec_stride + i];
     __syncthreads();
     uint32_t b, e;
@@ -545,14 +559,16 @@ __global__ __launch_bounds__(256, 6) void k_rerank_window(const float* __restric
                                                        const float* __restrict__ q_full, const uint32_t* __restrict__ stream,
                                                        const uint32_t* __restrict__ cnt, uint32_t M, uint32_t rescore, uint32_t k,
                                                        uint32_t nq, const uint64_t* __restrict__ tids, uint32_t* __restrict__ out_ids,
-                                                       uint64_t* __restrict__ out_tids, float* __restrict__ out_dist, uint32_t mode) {
+                                                       uint64_t* __restrict__ out_tids, float* __restrict__ out_dist, uint32_t mode,
+                                                       const uint32_t* __restrict__ perm, uint32_t deal) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* qv = reinterpret_cast<float*>(smem);
     uint64_t* hh = reinterpret_cast<uint64_t*>(qv + vec_stride);  // (vec_stride is a multiple of 4 floats)
     float* sd = reinterpret_cast<float*>(hh + rescore);
     uint32_t* sps = reinterpret_cast<uint32_t*>(sd + M);
-    const uint32_t q = blockIdx.x;
-    if (q >= nq) return;
+    const uint32_t slot = rerank_slot(blockIdx.x, nq, deal);
+    if (slot >= nq) return;
+    const uint32_t q = perm ? perm[slot] : slot;
     for (uint32_t i = threadIdx.x; i < vec_stride; i += blockDim.x) qv[i] = q_full[(size_t)q * vec_stride + i];
     const uint32_t n = min(cnt[q], M);
     const uint32_t* sid = stream + (size_t)q * M;
@@ -635,6 +651,143 @@ __global__ __launch_bounds__(256, 6) void k_rerank_window(const float* __restric
             if (out_tids) out_tids[(size_t)q * k + j] = tid;
             if (out_dist) out_dist[(size_t)q * k + j] = d;
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The order in which a batch's rerank workgroups take the scans (VS_RERANK_ORDER).  A batch whose scans fetch more rows than the
+// corpus has (nq * M > n) reads every row several times; the repeats only hit cache when the scans that share a row run at the same
+// time.  So the scans are grouped by where in the corpus they look: S seed rows (the SBQ codes of corpus rows i * (n / S), read in place
+// — the key is a pure function of the codes as they stand, nothing is cached, nothing can go stale), key(q) = the seed whose code is
+// nearest to q's code by Hamming distance (the lowest seed index among equals), perm = the scan numbers stably sorted by key.  Only
+// the order of the workgroups changes: every output stays indexed by the scan's own number, and no result depends on a key.
+//
+// k_scan_regions is tiled like a small GEMM: a workgroup keeps the codes of REG_T scans in LDS, streams the seed codes past them in
+// tiles of REG_T and each thread scores 4 x 4 (scan, seed) pairs per code word (xor + popcount: about 4 VALU operations per pair and
+// word).  LDS: 2 tiles of [code_stride][REG_P] u64 (rows padded to REG_P so the transposing stores spread over the banks) + REG_T u32.
+// ---------------------------------------------------------------------------------------------------------------
+enum { REG_T = 64, REG_P = 66, ORD_CHUNK = 1024 };
+__host__ __device__ static inline size_t scan_regions_lds(uint32_t code_stride) { return (size_t)2 * code_stride * REG_P * 8 + REG_T * 4; }
+
+__global__ __launch_bounds__(256) void k_scan_regions(const uint64_t* __restrict__ codes, uint32_t code_stride, uint32_t seed_step, uint32_t S,
+                                                      const uint64_t* __restrict__ qcodes, uint32_t nq, uint32_t* __restrict__ keys) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint64_t* qs = reinterpret_cast<uint64_t*>(smem);           // [code_stride][REG_P]: word w of the tile's scan i at w * REG_P + i
+    uint64_t* ss = qs + (size_t)code_stride * REG_P;            // the same for the seed tile
+    uint32_t* bestq = reinterpret_cast<uint32_t*>(ss + (size_t)code_stride * REG_P);
+    const uint32_t tid = threadIdx.x, q0 = blockIdx.x * REG_T;
+    // (a tile is loaded 8 rows at a time, 32 lanes along a row: coalesced, no division)
+    for (uint32_t r = tid >> 5; r < REG_T; r += 8)
+        for (uint32_t w = tid & 31u; w < code_stride; w += 32) qs[w * REG_P + r] = q0 + r < nq ? qcodes[(size_t)(q0 + r) * code_stride + w] : 0ull;
+    if (tid < REG_T) bestq[tid] = 0xFFFFFFFFu;
+    const uint32_t tq = (tid & 15u) * 4, ts = (tid >> 4) * 4;
+    uint32_t best[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};  // (Hamming distance << 16) | seed, smallest so far
+    for (uint32_t s0 = 0; s0 < S; s0 += REG_T) {
+        __syncthreads();  // (the previous tile has been read; first pass: the scan tile is written)
+        for (uint32_t r = tid >> 5; r < REG_T; r += 8) {
+            const uint32_t s = s0 + r;
+            for (uint32_t w = tid & 31u; w < code_stride; w += 32) ss[w * REG_P + r] = s < S ? codes[(size_t)s * seed_step * code_stride + w] : 0ull;
+        }
+        __syncthreads();
+        uint32_t acc[4][4];
+        for (int a = 0; a < 4; ++a)
+            for (int b = 0; b < 4; ++b) acc[a][b] = 0;
+        for (uint32_t w = 0; w < code_stride; ++w) {
+            const uint64_t* qp = qs + w * REG_P + tq;
+            const uint64_t* sp = ss + w * REG_P + ts;
+            const uint64_t qa[4] = {qp[0], qp[1], qp[2], qp[3]}, sa[4] = {sp[0], sp[1], sp[2], sp[3]};
+            for (int a = 0; a < 4; ++a)
+                for (int b = 0; b < 4; ++b) acc[a][b] += (uint32_t)__popcll(qa[a] ^ sa[b]);
+        }
+        for (int b = 0; b < 4; ++b) {
+            const uint32_t s = s0 + ts + (uint32_t)b;
+            if (s >= S) break;
+            for (int a = 0; a < 4; ++a) best[a] = min(best[a], (acc[a][b] << 16) | s);
+        }
+    }
+    for (int a = 0; a < 4; ++a) atomicMin(&bestq[tq + a], best[a]);
+    __syncthreads();
+    if (tid < REG_T && q0 + tid < nq) keys[q0 + tid] = bestq[tid] & 0xFFFFu;
+}
+
+// perm = the scan numbers sorted by (key, scan number), a counting sort in three small launches over chunks of ORD_CHUNK scans:
+// k_order_count: cnt[key][chunk] = scans of the chunk with that key; k_order_scan: every key's row of cnt becomes its exclusive prefix
+// over the chunks, total[key] its sum; k_order_scatter: place = (scans with a smaller key) + (same key, earlier chunk) + (same key,
+// earlier in the chunk).  No place is handed out by an atomic, so perm is the same in every run.
+__global__ __launch_bounds__(256) void k_order_count(const uint32_t* __restrict__ keys, uint32_t nq, uint32_t S, uint32_t nchunks,
+                                                     uint32_t* __restrict__ cnt) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t* hist = reinterpret_cast<uint32_t*>(smem);  // [S]
+    const uint32_t c = blockIdx.x;
+    for (uint32_t s = threadIdx.x; s < S; s += 256) hist[s] = 0;
+    __syncthreads();
+    for (uint32_t e = threadIdx.x; e < ORD_CHUNK; e += 256) {
+        const uint32_t q = c * ORD_CHUNK + e;
+        if (q < nq) atomicAdd(&hist[keys[q]], 1u);
+    }
+    __syncthreads();
+    for (uint32_t s = threadIdx.x; s < S; s += 256) cnt[(size_t)s * nchunks + c] = hist[s];
+}
+
+// exclusive prefix sum of x over the wave's lanes
+__device__ static inline uint32_t wave_exclusive_sum(uint32_t x, int lane) {
+    uint32_t incl = x;
+    for (int d = 1; d < WAVE; d <<= 1) {
+        const uint32_t o = __shfl(incl, lane >= d ? lane - d : lane, WAVE);
+        if (lane >= d) incl += o;
+    }
+    return incl - x;
+}
+
+__global__ __launch_bounds__(WAVE) void k_order_scan(uint32_t* __restrict__ cnt, uint32_t nchunks, uint32_t* __restrict__ total) {
+    const int lane = threadIdx.x;
+    uint32_t* row = cnt + (size_t)blockIdx.x * nchunks;
+    const uint32_t per = (nchunks + WAVE - 1) / WAVE, b = min((uint32_t)lane * per, nchunks), e = min(b + per, nchunks);
+    uint32_t sum = 0;
+    for (uint32_t i = b; i < e; ++i) sum += row[i];
+    uint32_t run = wave_exclusive_sum(sum, lane);
+    for (uint32_t i = b; i < e; ++i) {
+        const uint32_t v = row[i];
+        row[i] = run;
+        run += v;
+    }
+    if (lane == WAVE - 1) total[blockIdx.x] = run;  // (the last lane's run ends at the row's sum, whether or not it owns entries)
+}
+
+__global__ __launch_bounds__(256) void k_order_scatter(const uint32_t* __restrict__ keys, uint32_t nq, uint32_t S, uint32_t nchunks,
+                                                       const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ total,
+                                                       uint32_t* __restrict__ perm) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t* kk = reinterpret_cast<uint32_t*>(smem);  // [ORD_CHUNK] the chunk's keys
+    uint32_t* base = kk + ORD_CHUNK;                    // [S] first place of (key, this chunk)
+    const uint32_t c = blockIdx.x, tid = threadIdx.x;
+    for (uint32_t e = tid; e < ORD_CHUNK; e += 256) {
+        const uint32_t q = c * ORD_CHUNK + e;
+        kk[e] = q < nq ? keys[q] : 0xFFFFFFFFu;
+    }
+    if (tid < WAVE) {  // wave 0: exclusive prefix of total[] over the keys
+        const uint32_t per = (S + WAVE - 1) / WAVE, b = min(tid * per, S), e = min(b + per, S);
+        uint32_t sum = 0;
+        for (uint32_t s = b; s < e; ++s) sum += total[s];
+        uint32_t run = wave_exclusive_sum(sum, (int)tid);
+        for (uint32_t s = b; s < e; ++s) {
+            base[s] = run + cnt[(size_t)s * nchunks + c];
+            run += total[s];
+        }
+    }
+    __syncthreads();
+    const uint4* kk4 = reinterpret_cast<const uint4*>(kk);
+    for (uint32_t e = tid; e < ORD_CHUNK; e += 256) {
+        const uint32_t q = c * ORD_CHUNK + e;
+        if (q >= nq) break;
+        const uint32_t key = kk[e];
+        uint32_t rank = 0;  // scans of this chunk before e with the same key
+        for (uint32_t i = 0; i < e / 4; ++i) {
+            const uint4 v = kk4[i];
+            rank += (v.x == key) + (v.y == key) + (v.z == key) + (v.w == key);
+        }
+        for (uint32_t i = e & ~3u; i < e; ++i) rank += kk[i] == key;
+        perm[base[key] + rank] = q;
     }
 }
 
@@ -961,13 +1114,14 @@ int launch_hamming_gather(vs_index* idx, const uint64_t* d_qcodes, const uint32_
 }
 
 int launch_rerank(vs_index* idx, const float* d_q_full, const uint32_t* d_ids, const uint32_t* d_off,
-                  const uint32_t* d_cnt, uint32_t fixed_m, uint32_t nq, float* d_out, uint32_t row_base) {
+                  const uint32_t* d_cnt, uint32_t fixed_m, uint32_t nq, float* d_out, uint32_t row_base, const uint32_t* d_perm,
+                  bool deal) {
     if (nq == 0) return VS_OK;
     VS_REQUIRE(idx->vecs != nullptr, "index has no vector column: rerank impossible");
     size_t lds = (size_t)idx->vec_stride * 4;
-    hipLaunchKernelGGL(k_rerank, dim3(nq), dim3(256), lds, idx->ctx->stream, idx->vecs, idx->vec_stride,
+    hipLaunchKernelGGL(k_rerank, dim3(rerank_grid(nq, deal)), dim3(256), lds, idx->ctx->stream, idx->vecs, idx->vec_stride,
                        idx->d.dim_full, idx->vnorm, idx->d.distance_type, d_q_full, d_ids, d_off, d_cnt, fixed_m, nq,
-                       d_out, row_base);
+                       d_out, row_base, d_perm, deal ? 1u : 0u);
     VS_HIP(hipGetLastError());
     return VS_OK;
 }
@@ -997,14 +1151,38 @@ bool rerank_window_fits(const vs_index* idx, uint32_t M, uint32_t rescore, uint3
 
 int launch_rerank_window(vs_index* idx, const float* d_q_full, const uint32_t* d_stream_ids, const uint32_t* d_cnt, uint32_t M,
                          uint32_t rescore, uint32_t k, uint32_t nq, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist,
-                         uint32_t mode) {
+                         uint32_t mode, const uint32_t* d_perm, bool deal) {
     if (nq == 0) return VS_OK;
     VS_REQUIRE(idx->vecs != nullptr, "index has no vector column: rerank impossible");
     VS_REQUIRE(rescore > 0 && rerank_window_fits(idx, M, rescore, k), "fused rerank: window of %u rows does not fit", M);
     const size_t lds = rerank_window_lds(idx->vec_stride, M, rescore, k);
-    hipLaunchKernelGGL(k_rerank_window, dim3(nq), dim3(256), lds, idx->ctx->stream, idx->vecs, idx->vec_stride, idx->d.dim_full,
-                       idx->vnorm, idx->d.distance_type, d_q_full, d_stream_ids, d_cnt, M, rescore, k, nq, idx->tids, d_out_ids,
-                       d_out_tids, d_out_dist, mode);
+    hipLaunchKernelGGL(k_rerank_window, dim3(rerank_grid(nq, deal)), dim3(256), lds, idx->ctx->stream, idx->vecs, idx->vec_stride,
+                       idx->d.dim_full, idx->vnorm, idx->d.distance_type, d_q_full, d_stream_ids, d_cnt, M, rescore, k, nq, idx->tids,
+                       d_out_ids, d_out_tids, d_out_dist, mode, d_perm, deal ? 1u : 0u);
+    VS_HIP(hipGetLastError());
+    return VS_OK;
+}
+
+// The rerank order of a batch (k_scan_regions + the counting sort): d_perm[nq] = the scan numbers by (nearest of S seed rows, scan
+// number).  d_work: scan_order_work_bytes(nq, S) bytes.  S <= min(n, 4096) (a key and a Hamming distance share a 32-bit word).
+bool scan_order_fits(const vs_index* idx) { return idx->codes != nullptr && idx->d.n > 0 && scan_regions_lds(idx->code_stride) <= 40 * 1024; }
+size_t scan_order_work_bytes(uint32_t nq, uint32_t S) {
+    const size_t nchunks = (nq + ORD_CHUNK - 1) / ORD_CHUNK;
+    return ((size_t)nq + S + (size_t)S * nchunks) * 4;
+}
+int launch_scan_order(vs_index* idx, const uint64_t* d_qcodes, uint32_t nq, uint32_t S, uint32_t* d_work, uint32_t* d_perm) {
+    if (nq == 0) return VS_OK;
+    VS_REQUIRE(scan_order_fits(idx) && S >= 1 && S <= 4096 && S <= idx->d.n, "rerank order: %u seeds of %u-word codes not supported", S,
+               idx->code_stride);
+    const uint32_t nchunks = (nq + ORD_CHUNK - 1) / ORD_CHUNK;
+    uint32_t *d_keys = d_work, *d_total = d_keys + nq, *d_cnt = d_total + S;
+    hipStream_t st = idx->ctx->stream;
+    hipLaunchKernelGGL(k_scan_regions, dim3((nq + REG_T - 1) / REG_T), dim3(256), scan_regions_lds(idx->code_stride), st, idx->codes,
+                       idx->code_stride, idx->d.n / S, S, d_qcodes, nq, d_keys);
+    hipLaunchKernelGGL(k_order_count, dim3(nchunks), dim3(256), (size_t)S * 4, st, d_keys, nq, S, nchunks, d_cnt);
+    hipLaunchKernelGGL(k_order_scan, dim3(S), dim3(WAVE), 0, st, d_cnt, nchunks, d_total);
+    hipLaunchKernelGGL(k_order_scatter, dim3(nchunks), dim3(256), (size_t)(ORD_CHUNK + S) * 4, st, d_keys, nq, S, nchunks, d_cnt, d_total,
+                       d_perm);
     VS_HIP(hipGetLastError());
     return VS_OK;
 }

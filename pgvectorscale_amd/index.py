@@ -72,7 +72,7 @@ class Context:
         """{kernel: (total_ms, launches)} from HIP events recorded on the ctx stream."""
         p = _lib.Profile()
         check(self._L.vs_profile_read(self.h, C.byref(p), int(reset)))
-        names = ["prepare_queries", "search", "rerank", "resort", "search_fallback", "scan"]
+        names = ["prepare_queries", "search", "rerank", "resort", "search_fallback", "scan", "rerank_order"]
         return {n: (float(p.ms[k]), int(p.launches[k])) for k, n in enumerate(names)}
 
     def ws_probe(self, d_mem, nbytes, iters=600):
@@ -221,6 +221,15 @@ class DiskAnnIndex:
 
     def _refresh(self):
         check(self._L.vs_index_get_desc(self.h, C.byref(self.desc)))
+
+    def rerank_order(self):
+        """the rerank order of the last batch (VS_RERANK_ORDER): place -> scan number; empty when it took the scans' own order"""
+        n = C.c_uint32()
+        check(self._L.vs_index_rerank_order(self.h, None, 0, C.byref(n)))
+        out = np.empty(int(n.value), np.uint32)
+        if out.size:
+            check(self._L.vs_index_rerank_order(self.h, out.ctypes.data_as(C.c_void_p), out.size, C.byref(n)))
+        return out
 
     def array(self, which):
         p, s = C.c_void_p(), C.c_uint32()
