@@ -134,7 +134,7 @@ int vs_ctx_mem_info(vs_ctx* ctx, uint64_t* free_bytes, uint64_t* total_bytes);
 /* per-kernel timing with HIP events recorded on the ctx stream around every launch of the batched-scan pipeline
  * (what bench.py's roofline figure is computed from).  kind: 0 prepare_queries, 1 search (the LDS-resident fast
  * kernel; the general kernel when the fast path is off), 2 rerank, 3 resort, 4 search fallback (general kernel re-running
- * the scans the fast kernel handed over), 5 flat SBQ scan (vs_scan_topk). */
+ * the scans the fast kernel handed over), 5 flat SBQ scan (vs_scan_topk), 6 rerank order, 7 page encode (vs_pages_out_*). */
 typedef struct vs_profile {
     double ms[8];        /* accumulated kernel time per kind */
     uint64_t launches[8];
@@ -392,6 +392,48 @@ int vs_pages_dev_meta(vs_pages_dev* d, const vs_meta_layout* layout, vs_meta_pag
  * extras: vecs / mean / m2 / count / label_start_labels / label_start_nodes (node ids); frees the raw pages */
 int vs_pages_dev_build(vs_pages_dev* d, const vs_index_desc* desc, const vs_index_host* extras, vs_pages_info* info, vs_index** out);
 void vs_pages_dev_close(vs_pages_dev* d);
+
+/* ---- the way back: a device-resident index written out as the pages of a `diskann` index relation (vs_pages.cpp,
+ * vs_pages_dev.hip) — the layout the reference's ambuild leaves behind: block 0 = Meta chain (MetaPageHeader item 1, MetaPage
+ * item 2; MetaPage::store, AM/meta_page.rs:344-365), the chained SbqMeans item (AM/sbq/mod.rs:123-137), then the SbqNode items
+ * in node order on PageType::SbqNode pages filled by the Tape rule (a new page when aligned free space < item size,
+ * util/tape.rs:53-76); a MetaPage that has outgrown block 0 (hundreds of labeled start nodes) chains onto fresh pages after
+ * the last node page.  Every node item carries num_neighbors ItemPointers, (InvalidBlockNumber, 0) from the list's end on;
+ * deleted tuples keep heap offset 0; no all-zero block is emitted.  memory_optimized (SBQ) indexes, classic and labeled nodes.
+ * The node pages are composed ON the device (k_pages_encode: a workgroup per page, neighbor ids become ItemPointers there)
+ * and leave through the pinned ring, the encode of one chunk under the copy of the previous one; the few metadata pages are
+ * encoded on the host.  Classic nodes all have one size, so node -> (block, offset) is arithmetic; label sets make the item
+ * size vary, so vs_pages_out_open computes the page breaks in one sequential host pass over the label offsets (4 bytes per
+ * node down, 6 bytes per node up and kept on the device until vs_pages_out_close).  The field order inside the archived
+ * structs stays a parameter (vs_node_layout / vs_meta_layout), as for the readers. */
+typedef struct vs_pages_out vs_pages_out;
+typedef struct vs_pages_out_params {
+    uint32_t page_size;                 /* VS_BLCKSZ (the only size the writer lays out)                                  */
+    const vs_node_layout* node_layout;  /* NULL = vs_node_layout_default(has_labels); for classic nodes off_labels, when it
+                                         * names a slot, is where the always-empty _neighbor_vectors field goes             */
+    const vs_meta_layout* meta_layout;  /* NULL = vs_meta_layout_default                                                   */
+    const char* extension_version;      /* MetaPage.extension_version_when_built (NULL = "", at most 63 bytes)             */
+    uint32_t search_list_size;          /* build-time MetaPage fields the index handle does not keep                       */
+    double max_alpha;
+} vs_pages_out_params;
+/* fixes the whole layout: info->n_blocks is the relation's size, the other fields are what a reader of the result reports.
+ * The index's arrays, start nodes and quantizer must not change until vs_pages_out_close.  VS_ERR_INVALID for an index of
+ * another storage type or without codes / neighbors. */
+int vs_pages_out_open(vs_index* idx, const vs_pages_out_params* p, vs_pages_out** out, vs_pages_info* info);
+/* blocks first_block .. first_block + n_blocks - 1 into the host buffer `pages`: any range, in any order, any number of
+ * times, always the same bytes (stream to a file or to smgrextend in chunks of the caller's choosing) */
+int vs_pages_out_read(vs_pages_out* w, uint32_t first_block, uint32_t n_blocks, void* pages);
+/* the same into DEVICE memory (vs_dev_alloc): the node pages are composed in place by one launch, nothing crosses PCIe but
+ * the metadata pages */
+int vs_pages_out_read_dev(vs_pages_out* w, uint32_t first_block, uint32_t n_blocks, void* d_pages);
+int vs_pages_out_item_pointer_of(const vs_pages_out* w, uint32_t node, uint32_t* block, uint32_t* offset);
+void vs_pages_out_close(vs_pages_out* w);
+/* rkyv::to_bytes::<MetaPage> (host-only; the counterpart of vs_meta_page_decode): the labeled start nodes in key order,
+ * written as the archived B-tree when meta->has_start_nodes; meta->n_labeled_start_nodes is ignored in favour of n_starts.
+ * *len = bytes needed; buf may be NULL to query it; a buf of cap < *len is an error and nothing is written. */
+int vs_meta_page_encode(const vs_meta_page* meta, const int16_t* start_labels, const uint32_t* start_blocks,
+                        const uint32_t* start_offsets, uint32_t n_starts, const vs_meta_layout* layout, void* buf, size_t cap,
+                        size_t* len);
 
 /* ---- K4: SBQ quantisation of queries (SbqQuantizer::quantize, AM/sbq/quantize.rs:52-102) --------------------- */
 /* q: host [nq][dim_index], already cosine-normalised by the caller if applicable; out: host [nq][words] */

@@ -97,6 +97,11 @@ class PagesInfo(C.Structure):
                 ("meta_version", C.c_uint32)]
 
 
+class PagesOutParams(C.Structure):
+    _fields_ = [("page_size", C.c_uint32), ("node_layout", C.POINTER(NodeLayout)), ("meta_layout", C.POINTER(MetaLayout)),
+                ("extension_version", C.c_char_p), ("search_list_size", C.c_uint32), ("max_alpha", C.c_double)]
+
+
 class BrokerConfig(C.Structure):
     _fields_ = [("max_batch", C.c_uint32), ("max_wait_us", C.c_uint32), ("cursor_lanes", C.c_uint32), ("cursor_pool", C.c_uint32)]
 
@@ -190,6 +195,12 @@ SYMBOLS = {
     "vs_pages_dev_sbq_means": (_i, [_vp, _u32, _u32, _vp, _vp, _u32, C.POINTER(_u32), C.POINTER(_u64)]),
     "vs_pages_dev_build": (_i, [_vp, C.POINTER(IndexDesc), C.POINTER(IndexHost), C.POINTER(PagesInfo), C.POINTER(_vp)]),
     "vs_pages_dev_close": (None, [_vp]),
+    "vs_pages_out_open": (_i, [_vp, C.POINTER(PagesOutParams), C.POINTER(_vp), C.POINTER(PagesInfo)]),
+    "vs_pages_out_read": (_i, [_vp, _u32, _u32, _vp]),
+    "vs_pages_out_read_dev": (_i, [_vp, _u32, _u32, _vp]),
+    "vs_pages_out_item_pointer_of": (_i, [_vp, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
+    "vs_pages_out_close": (None, [_vp]),
+    "vs_meta_page_encode": (_i, [C.POINTER(MetaPage), _vp, _vp, _vp, _u32, C.POINTER(MetaLayout), _vp, _sz, C.POINTER(_sz)]),
     "vs_quantize": (_i, [_vp, _vp, _u32, _vp]),
     "vs_hamming_gather": (_i, [_vp, _vp, _vp, _vp, _u32, _vp]),
     "vs_rerank": (_i, [_vp, _vp, _vp, _vp, _u32, _vp]),

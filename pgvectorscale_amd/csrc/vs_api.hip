@@ -193,7 +193,7 @@ static unsigned stage_threads() {
     }();
     return nt_cfg;
 }
-static void stage_copy(void* dst, const void* src, size_t n) {
+void stage_copy(void* dst, const void* src, size_t n) {
     const unsigned nt_cfg = stage_threads();
     if (n < (8u << 20) || nt_cfg == 1) {
         memcpy(dst, src, n);

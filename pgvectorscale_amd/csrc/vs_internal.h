@@ -88,7 +88,7 @@ struct vs_ctx {
     double prof_ms[8] = {0};
     uint64_t prof_launches[8] = {0};
 };
-enum { PK_PREPARE = 0, PK_SEARCH = 1, PK_RERANK = 2, PK_RESORT = 3, PK_SEARCH_FB = 4, PK_SCAN = 5, PK_ORDER = 6 };
+enum { PK_PREPARE = 0, PK_SEARCH = 1, PK_RERANK = 2, PK_RESORT = 3, PK_SEARCH_FB = 4, PK_SCAN = 5, PK_ORDER = 6, PK_PAGES = 7 };
 hipEvent_t prof_begin(vs_ctx* c);
 void prof_end(vs_ctx* c, int kind, hipEvent_t a);
 
@@ -237,6 +237,7 @@ size_t slab_bytes_wanted(const vs_index* ix);                      // vs_slab.hi
 void slab_select(vs_index* ix, WsSlab* s, size_t slab_bytes);     // vs_slab.hip: probes the candidates (caller holds s->mu)
 hipEvent_t pool_event(vs_ctx* c);                                  // vs_api.hip: an event from the context's pool
 int download_async_rows(vs_ctx* c, void* dst, const void* src, size_t bytes);  // vs_api.hip: rows back through the pinned ring
+void stage_copy(void* dst, const void* src, size_t n);                         // vs_api.hip: pageable <-> pinned, split over VS_STAGE_THREADS
 int vs_search_batch_dev_impl(vs_index* ix, const float* d_queries, const int16_t* d_qlabels, const uint32_t* d_qlabel_off, uint32_t nq,
                              uint32_t L, uint32_t rescore, uint32_t k, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist);  // vs_batch.hip
 int vs_search_batch_dev_finish_impl(vs_index* ix, vs_stats* stats);  // vs_batch.hip

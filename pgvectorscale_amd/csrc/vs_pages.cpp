@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/vsgpu.h"
+#include "vs_pages_out.h"
 
 void vs_set_error(const char* fmt, ...);
 
@@ -930,3 +931,439 @@ int vs_pages_item_pointer_of(const vs_pages* p, uint32_t node, uint32_t* block, 
 }
 
 }  // extern "C"
+
+// ---- the way back: an index written out as relation pages (host half; the node pages are composed by k_pages_encode) ----------
+// What is restated here is the reference's writer: PageInit / PageAddItemExtended as WritablePage drives them (UT/page.rs:107-215),
+// ChainTapeWriter::write (UT/chain.rs:72-131), Tape::write (UT/tape.rs:53-76) and rkyv 0.7 to_bytes of MetaPage / SbqMeans
+// (out-of-line data in field order, the root object at the end).
+namespace {
+
+inline void wr16(uint8_t* p, uint32_t v) { const uint16_t x = (uint16_t)v; memcpy(p, &x, 2); }
+inline void wr32(uint8_t* p, uint32_t v) { memcpy(p, &v, 4); }
+inline uint32_t maxalign(uint32_t x) { return (x + 7u) & ~7u; }
+
+struct Archive {  // rkyv's AlignedSerializer
+    std::vector<uint8_t> b;
+    size_t align(size_t a) {
+        while (b.size() % a) b.push_back(0);
+        return b.size();
+    }
+    size_t put(const void* p, size_t n) {
+        const size_t pos = b.size();
+        const uint8_t* q = static_cast<const uint8_t*>(p);
+        b.insert(b.end(), q, q + n);
+        return pos;
+    }
+    void put16(uint32_t v) { uint8_t t[2]; wr16(t, v); put(t, 2); }
+    void put32(uint32_t v) { uint8_t t[4]; wr32(t, v); put(t, 4); }
+};
+
+struct StartEntry {
+    int16_t key;
+    uint32_t block, offset;
+};
+constexpr size_t kBtMaxNode = 4096;  // rkyv's btree_map MIN_ENTRIES_PER_*_NODE come from a 4096-byte node target
+
+// ArchivedBTreeMap::serialize_from_reverse_iter: the nodes are built from the keys in REVERSE order, a node is closed once it has
+// reached 4096 bytes, so the leaf with the largest keys is written first and the root last; returns the root's position
+size_t btree_nodes(Archive& s, const std::vector<StartEntry>& entries) {
+    struct Ref { int16_t key; size_t pos; };
+    std::vector<Ref> level;  // (first key, node position), back to front
+    const size_t n = entries.size();
+    size_t i = 0;  // index into the reversed sequence: rev[i] = entries[n - 1 - i]
+    bool have_next = false;
+    size_t next_leaf = 0;
+    while (i < n) {
+        size_t g0 = i, g = 1;
+        i++;
+        while (kBtHeader + g * kBtLeafEntry < kBtMaxNode && i < n) {
+            g++;
+            i++;
+        }
+        const size_t pos = s.align(4);
+        const uint32_t size = (uint32_t)(kBtHeader + g * kBtLeafEntry);
+        const int32_t ptr = have_next ? (int32_t)((int64_t)next_leaf - (int64_t)(pos + 8)) : 0;
+        s.put16((uint32_t)g);
+        s.put16(0);
+        s.put32(size);
+        s.put32((uint32_t)ptr);
+        for (size_t e = 0; e < g; ++e) {  // entries are stored in key order
+            const StartEntry& x = entries[n - 1 - (g0 + g - 1 - e)];
+            s.put16((uint16_t)x.key);
+            s.put16(0);
+            s.put32(x.block);
+            s.put16(x.offset);
+            s.put16(0);
+        }
+        next_leaf = pos;
+        have_next = true;
+        level.push_back({entries[n - 1 - (g0 + g - 1)].key, pos});
+    }
+    while (level.size() > 1) {
+        std::vector<Ref> nxt;
+        size_t j = 0;
+        while (j < level.size()) {  // `level` is still in reverse key order
+            std::vector<Ref> grp{level[j]};
+            j++;
+            for (;;) {
+                const size_t est = kBtHeader + grp.size() * kBtInnerEntry;
+                if (est >= kBtMaxNode && grp.size() >= 2) break;
+                if (j < level.size()) grp.push_back(level[j++]);
+                else break;
+            }
+            std::reverse(grp.begin(), grp.end());  // the smallest child hangs off the header, the others are (ptr, key) entries
+            if (grp.size() == 1 && j >= level.size() && nxt.empty()) {  // a lone child: it is the root itself
+                nxt.push_back(grp[0]);
+                continue;
+            }
+            const size_t pos = s.align(4);
+            const size_t rest = grp.size() - 1;
+            s.put16(0x8000u | (uint32_t)rest);
+            s.put16(0);
+            s.put32((uint32_t)(kBtHeader + rest * kBtInnerEntry));
+            s.put32((uint32_t)(int32_t)((int64_t)grp[0].pos - (int64_t)(pos + 8)));
+            for (size_t e = 0; e < rest; ++e) {
+                const size_t epos = pos + kBtHeader + e * kBtInnerEntry;
+                s.put32((uint32_t)(int32_t)((int64_t)grp[1 + e].pos - (int64_t)epos));
+                s.put16((uint16_t)grp[1 + e].key);
+                s.put16(0);
+            }
+            nxt.push_back({grp[0].key, pos});
+        }
+        level.swap(nxt);
+    }
+    return level[0].pos;
+}
+
+int check_meta_layout(const vs_meta_layout& L) {
+    const uint32_t offs[] = {L.off_magic_number + 4, L.off_version + 4, L.off_extension_version_when_built + 8, L.off_distance_type + 2,
+                             L.off_num_dimensions + 4, L.off_num_dimensions_to_index + 4, L.off_bq_num_bits_per_dimension + 1,
+                             L.off_storage_type + 1, L.off_num_neighbors + 4, L.off_search_list_size + 4, L.off_max_alpha + 8,
+                             L.off_start_nodes + 20, L.off_quantizer_metadata + 8, L.off_has_labels + 1};
+    if (L.root_size > 4096 || (L.root_size & 7)) return fail("vs_meta_layout: a root object of %u bytes", L.root_size);
+    for (uint32_t e : offs)
+        if (e > L.root_size) return fail("vs_meta_layout: a field ends at byte %u of a %u-byte root object", e, L.root_size);
+    return VS_OK;
+}
+
+int meta_page_bytes(const vs_meta_page& m, const std::vector<StartEntry>& starts, const vs_meta_layout& L, std::vector<uint8_t>& out) {
+    int rc = check_meta_layout(L);
+    if (rc != VS_OK) return rc;
+    for (size_t i = 1; i < starts.size(); ++i)
+        if (starts[i - 1].key >= starts[i].key) return fail("vs_meta_page_encode: start-node labels must be strictly increasing (entry %zu)", i);
+    Archive s;
+    const size_t vlen = strnlen(m.extension_version_when_built, sizeof m.extension_version_when_built);
+    size_t p_ver = 0;
+    if (vlen > 7) p_ver = s.put(m.extension_version_when_built, vlen);  // ArchivedString: longer than 7 bytes = out of line
+    size_t root_pos = 0;
+    const bool tree = m.has_start_nodes && !starts.empty();
+    if (tree) root_pos = btree_nodes(s, starts);
+    const size_t root = s.align(8);
+    s.b.resize(root + L.root_size, 0);
+    uint8_t* b = s.b.data() + root;
+    wr32(b + L.off_magic_number, m.magic_number);
+    wr32(b + L.off_version, m.version);
+    {
+        uint8_t* f = b + L.off_extension_version_when_built;
+        if (vlen <= 7) {
+            memcpy(f, m.extension_version_when_built, vlen);
+            f[7] = (uint8_t)vlen;
+        } else {
+            wr32(f, (uint32_t)vlen);
+            wr32(f + 4, (uint32_t)(int32_t)((int64_t)p_ver - (int64_t)(root + L.off_extension_version_when_built)));
+        }
+    }
+    wr16(b + L.off_distance_type, m.distance_type);
+    wr32(b + L.off_num_dimensions, m.num_dimensions);
+    wr32(b + L.off_num_dimensions_to_index, m.num_dimensions_to_index);
+    b[L.off_bq_num_bits_per_dimension] = (uint8_t)m.bq_num_bits_per_dimension;
+    b[L.off_storage_type] = (uint8_t)m.storage_type;
+    wr32(b + L.off_num_neighbors, m.num_neighbors);
+    wr32(b + L.off_search_list_size, m.search_list_size);
+    memcpy(b + L.off_max_alpha, &m.max_alpha, 8);
+    if (m.has_start_nodes) {  // ArchivedOption<ArchivedStartNodes>: tag, default_node, {len, root} of the B-tree
+        uint8_t* sn = b + L.off_start_nodes;
+        sn[0] = 1;
+        wr32(sn + 4, m.default_start_block);
+        wr16(sn + 8, m.default_start_offset);
+        wr32(sn + 12, (uint32_t)starts.size());
+        const int64_t root_field = (int64_t)root + L.off_start_nodes + 16;
+        wr32(sn + 16, tree ? (uint32_t)(int32_t)((int64_t)root_pos - root_field) : 0u);
+    }
+    wr32(b + L.off_quantizer_metadata, m.quantizer_block);
+    wr16(b + L.off_quantizer_metadata + 4, m.quantizer_offset);
+    b[L.off_has_labels] = m.has_labels ? 1 : 0;
+    out.swap(s.b);
+    return VS_OK;
+}
+
+// the metadata pages of the relation being written: (block number, bytes), a page at a time
+struct HostRel {
+    uint32_t ps;
+    uint32_t next_block = 0;
+    std::vector<std::pair<uint32_t, std::vector<uint8_t>>> pages;
+    uint32_t by_type[9] = {0};
+
+    void init(std::vector<uint8_t>& p, int type) const {  // WritablePage::new: PageInit with a 4-byte special area
+        p.assign(ps, 0);
+        const uint32_t special = ps - maxalign(4);
+        wr16(&p[12], kPageHeaderSize);
+        wr16(&p[14], special);
+        wr16(&p[16], special);
+        wr16(&p[18], ps | 4u);  // pd_pagesize_version: PG_PAGE_LAYOUT_VERSION 4
+        p[special] = (uint8_t)type;
+        wr16(&p[special + 2], kTsvPageId);
+    }
+    size_t new_page(int type) {
+        pages.emplace_back(next_block++, std::vector<uint8_t>());
+        init(pages.back().second, type);
+        by_type[type]++;
+        return pages.size() - 1;
+    }
+    uint32_t aligned_free(size_t i) const {  // WritablePage::get_aligned_free_space over PageGetFreeSpace
+        const uint8_t* p = pages[i].second.data();
+        const uint32_t space = rd16(p + 14) - rd16(p + 12);
+        const uint32_t fs = space < 4 ? 0 : space - 4;
+        return fs - fs % 8;
+    }
+    // PageAddItemExtended of a chain item: the 8-byte ArchivedChainItemHeader (ItemPointer of the next piece), then the payload
+    uint32_t add_item(size_t i, const uint8_t* hdr8, const uint8_t* data, size_t len) {
+        uint8_t* p = pages[i].second.data();
+        const uint32_t lower = rd16(p + 12), upper = rd16(p + 14);
+        const uint32_t size = (uint32_t)len + kChainHeader;
+        const uint32_t off = (lower - kPageHeaderSize) / 4 + 1;
+        const uint32_t new_upper = upper - maxalign(size);
+        memcpy(p + new_upper, hdr8, kChainHeader);
+        memcpy(p + new_upper + kChainHeader, data, len);
+        wr32(p + kPageHeaderSize + 4 * (off - 1), new_upper | (1u << 15) | (size << 17));
+        wr16(p + 12, lower + 4);
+        wr16(p + 14, new_upper);
+        return off;
+    }
+    // ChainTapeWriter::write, starting on page `cur`; -> ItemPointer of the chain's first item
+    void chain_write(int type, size_t cur, const std::vector<uint8_t>& payload, uint32_t& blk, uint32_t& off) {
+        const uint8_t* data = payload.data();
+        size_t len = payload.size();
+        if (aligned_free(cur) < kChainHeader + 1) cur = new_page(type);
+        bool first = true;
+        uint8_t hdr[8];
+        auto note = [&](uint32_t o) {
+            if (first) {
+                blk = pages[cur].first;
+                off = o;
+                first = false;
+            }
+        };
+        while (kChainHeader + len > aligned_free(cur)) {
+            const size_t nxt = new_page(type);
+            const size_t part = aligned_free(cur) - kChainHeader;
+            memset(hdr, 0, 8);
+            wr32(hdr, pages[nxt].first);
+            wr16(hdr + 4, 1);
+            note(add_item(cur, hdr, data, part));
+            cur = nxt;
+            data += part;
+            len -= part;
+        }
+        memset(hdr, 0, 8);
+        wr32(hdr, kInvalidBlock);
+        note(add_item(cur, hdr, data, len));
+    }
+};
+
+}  // namespace
+
+extern "C" int vs_meta_page_encode(const vs_meta_page* meta, const int16_t* start_labels, const uint32_t* start_blocks,
+                                   const uint32_t* start_offsets, uint32_t n_starts, const vs_meta_layout* layout, void* buf, size_t cap,
+                                   size_t* len) {
+    if (!meta || !len) return fail("vs_meta_page_encode: null argument");
+    if (n_starts && (!start_labels || !start_blocks || !start_offsets)) return fail("vs_meta_page_encode: %u start nodes but no arrays", n_starts);
+    if (n_starts > 65536) return fail("vs_meta_page_encode: %u labeled start nodes (labels are smallints)", n_starts);
+    vs_meta_layout L;
+    if (layout) L = *layout;
+    else vs_meta_layout_default(&L);
+    try {
+        std::vector<StartEntry> starts(n_starts);
+        for (uint32_t i = 0; i < n_starts; ++i) starts[i] = {start_labels[i], start_blocks[i], start_offsets[i]};
+        std::vector<uint8_t> bytes;
+        const int rc = meta_page_bytes(*meta, starts, L, bytes);
+        if (rc != VS_OK) return rc;
+        *len = bytes.size();
+        if (!buf) return VS_OK;
+        if (bytes.size() > cap) return fail("vs_meta_page_encode: %zu bytes needed, buffer holds %zu", bytes.size(), cap);
+        memcpy(buf, bytes.data(), bytes.size());
+    } catch (const std::bad_alloc&) {
+        vs_set_error("vs_meta_page_encode: out of host memory");
+        return VS_ERR_OOM;
+    }
+    return VS_OK;
+}
+
+int vs_pages_out_plan_item_pointer(const PagesOutPlan& plan, uint32_t node, uint32_t* block, uint32_t* offset) {
+    if (!block || !offset) return fail("vs_pages_out_item_pointer_of: null argument");
+    if (node >= plan.n) return fail("node %u of %u", node, plan.n);
+    if (!plan.has_labels) {  // every classic item has one size: K per page
+        *block = plan.first_node_block + node / plan.K;
+        *offset = node % plan.K + 1;
+        return VS_OK;
+    }
+    // the last node page whose first node is <= node (page_first is strictly increasing but for its last entry, n)
+    const size_t pg = (size_t)(std::upper_bound(plan.page_first.begin(), plan.page_first.begin() + plan.n_node_pages, node) - plan.page_first.begin()) - 1;
+    *block = plan.first_node_block + (uint32_t)pg;
+    *offset = node - plan.page_first[pg] + 1;
+    return VS_OK;
+}
+
+int vs_pages_out_plan(const vs_index_desc& d, const vs_pages_out_params& p, const float* mean, const float* m2, uint64_t count,
+                      const uint32_t* label_off, const int16_t* ls_labels, const uint32_t* ls_nodes, PagesOutPlan& plan) {
+    if (p.page_size != VS_BLCKSZ) return fail("vs_pages_out_open: page_size %u (the writer lays out %u-byte pages)", p.page_size, VS_BLCKSZ);
+    if (d.words == 0 || d.num_neighbors == 0) return fail("vs_pages_out_open: an index of %u code words and %u neighbor slots", d.words, d.num_neighbors);
+    if (d.has_labels && !label_off) return fail("vs_pages_out_open: the index says has_labels but holds no label sets");
+    const char* ver = p.extension_version ? p.extension_version : "";
+    if (strlen(ver) >= sizeof(vs_meta_page().extension_version_when_built))
+        return fail("vs_pages_out_open: extension_version of %zu bytes (at most 63)", strlen(ver));
+    try {
+        const uint32_t ps = p.page_size, n = d.n, W = d.words, R = d.num_neighbors;
+        plan = PagesOutPlan();
+        plan.page_size = ps;
+        plan.n = n;
+        plan.W = W;
+        plan.R = R;
+        plan.has_labels = d.has_labels != 0;
+        // node layout: three named fields and the slot of the fourth (labels, or the classic node's empty _neighbor_vectors)
+        vs_node_layout lay;
+        if (p.node_layout) lay = *p.node_layout;
+        else vs_node_layout_default(plan.has_labels, &lay);
+        const uint32_t named[3] = {lay.off_heap_item_pointer, lay.off_bq_vector, lay.off_neighbor_index_pointers};
+        auto fits = [&](uint32_t o) { return o <= lay.root_size && lay.root_size - o >= 8 && (o & 3) == 0; };
+        if (lay.root_size > 4096 || (lay.root_size & 3)) return fail("vs_pages_out_open: a %u-byte archived node", lay.root_size);
+        for (uint32_t o : named)
+            if (!fits(o)) return fail("vs_pages_out_open: field offset %u does not fit a %u-byte archived node", o, lay.root_size);
+        if (!fits(lay.off_labels)) {
+            if (plan.has_labels) return fail("vs_pages_out_open: the node layout has no labels field");
+            lay.off_labels = 0xFFFFFFFFu;
+            for (uint32_t o = 0; o + 8 <= lay.root_size && lay.off_labels == 0xFFFFFFFFu; o += 8)
+                if (o != named[0] && o != named[1] && o != named[2]) lay.off_labels = o;
+            if (lay.off_labels == 0xFFFFFFFFu) return fail("vs_pages_out_open: no room for the fourth field in a %u-byte archived node", lay.root_size);
+        }
+        const uint32_t four[4] = {named[0], named[1], named[2], lay.off_labels};
+        for (int a = 0; a < 4; a++)
+            for (int b2 = a + 1; b2 < 4; b2++)
+                if (four[a] < four[b2] + 8 && four[b2] < four[a] + 8) return fail("vs_pages_out_open: fields at +%u and +%u of the archived node overlap", four[a], four[b2]);
+        plan.lay = lay;
+        vs_meta_layout ML;
+        if (p.meta_layout) ML = *p.meta_layout;
+        else vs_meta_layout_default(&ML);
+
+        HostRel rel;
+        rel.ps = ps;
+        const uint32_t special = ps - 8, fresh_free = ((special - kPageHeaderSize - 4) / 8) * 8;
+        // block 0: the Meta chain (MetaPage::create stores the header and a first MetaPage here; both are rewritten below)
+        const size_t meta0 = rel.new_page(VS_PAGE_META);
+        // the SbqMeans chain: to_bytes(SbqMeans {count, means, m2})
+        std::vector<uint8_t> means((size_t)8 * d.dim_index + 24, 0);
+        memcpy(means.data(), mean, (size_t)4 * d.dim_index);
+        if (m2) memcpy(means.data() + (size_t)4 * d.dim_index, m2, (size_t)4 * d.dim_index);
+        {
+            uint8_t* r = means.data() + (size_t)8 * d.dim_index;
+            memcpy(r, &count, 8);
+            wr32(r + 8, (uint32_t)(int32_t)(-(int64_t)((size_t)8 * d.dim_index + 8)));
+            wr32(r + 12, d.dim_index);
+            wr32(r + 16, (uint32_t)(int32_t)((int64_t)4 * d.dim_index - (int64_t)((size_t)8 * d.dim_index + 16)));
+            wr32(r + 20, d.dim_index);
+        }
+        uint32_t q_blk = 0, q_off = 0;
+        rel.chain_write(VS_PAGE_SBQ_MEANS, rel.new_page(VS_PAGE_SBQ_MEANS), means, q_blk, q_off);
+        // the SbqNode pages: Tape::new takes a page at once, Tape::write a new one when aligned free space < item size
+        plan.first_node_block = rel.next_block;
+        const uint32_t body0 = 8 * W + 8 * R;
+        if (!plan.has_labels) {
+            plan.item_size = ((body0 + 3) & ~3u) + lay.root_size;
+            if (plan.item_size > fresh_free) return fail("vs_pages_out_open: a node item of %u bytes does not fit a page", plan.item_size);
+            uint32_t lower = kPageHeaderSize, upper = special, k = 0;
+            for (;;) {
+                const uint32_t space = upper - lower, fs = space < 4 ? 0 : space - 4;
+                if (fs - fs % 8 < plan.item_size) break;
+                upper -= maxalign(plan.item_size);
+                lower += 4;
+                k++;
+            }
+            plan.K = k;
+            plan.n_node_pages = n ? (n + k - 1) / k : 1;
+        } else {
+            plan.page_first.push_back(0);
+            plan.node_block.resize(n);
+            plan.node_lpoff.resize(n);
+            uint32_t lower = kPageHeaderSize, upper = special, page = 0;
+            for (uint32_t i = 0; i < n; ++i) {
+                if (label_off[i + 1] < label_off[i]) return fail("vs_pages_out_open: label offsets decrease at node %u", i);
+                const uint64_t body = (uint64_t)body0 + 2ull * (label_off[i + 1] - label_off[i]);
+                if (body + lay.root_size + 3 > fresh_free) return fail("vs_pages_out_open: the item of node %u does not fit a page", i);
+                const uint32_t size = (((uint32_t)body + 3) & ~3u) + lay.root_size;
+                const uint32_t space = upper - lower, fs = space < 4 ? 0 : space - 4;
+                if (fs - fs % 8 < size) {
+                    plan.page_first.push_back(i);
+                    page++;
+                    lower = kPageHeaderSize;
+                    upper = special;
+                }
+                upper -= maxalign(size);
+                lower += 4;
+                plan.node_block[i] = plan.first_node_block + page;
+                plan.node_lpoff[i] = (uint16_t)upper;
+            }
+            plan.n_node_pages = page + 1;
+            plan.page_first.push_back(n);
+            plan.n_label_vals = label_off[n];
+        }
+        if ((uint64_t)plan.first_node_block + plan.n_node_pages + 64 >= kInvalidBlock) return fail("vs_pages_out_open: block number overflow");
+        rel.next_block = plan.first_node_block + plan.n_node_pages;
+        rel.by_type[VS_PAGE_SBQ_NODE] = plan.n_node_pages;
+        // MetaPage::store on the re-initialised block 0, start nodes and quantizer pointer now known
+        vs_meta_page m;
+        memset(&m, 0, sizeof m);
+        m.magic_number = kTsvMagic;
+        m.version = 3;  // TSV_VERSION (AM/meta_page.rs:23)
+        memcpy(m.extension_version_when_built, ver, strlen(ver));
+        m.distance_type = d.distance_type;
+        m.num_dimensions = d.dim_full;
+        m.num_dimensions_to_index = d.dim_index;
+        m.bq_num_bits_per_dimension = d.bits;
+        m.storage_type = 2;  // StorageType::SbqCompression
+        m.num_neighbors = R;
+        m.search_list_size = p.search_list_size;
+        m.max_alpha = p.max_alpha;
+        m.quantizer_block = q_blk;
+        m.quantizer_offset = q_off;
+        m.has_labels = plan.has_labels;
+        std::vector<StartEntry> starts;
+        if (d.default_start != VS_INVALID_NODE) {
+            m.has_start_nodes = 1;
+            int rc = vs_pages_out_plan_item_pointer(plan, d.default_start, &m.default_start_block, &m.default_start_offset);
+            if (rc != VS_OK) return rc;
+            starts.resize(d.n_label_starts);
+            for (uint32_t i = 0; i < d.n_label_starts; ++i) {
+                starts[i].key = ls_labels[i];
+                rc = vs_pages_out_plan_item_pointer(plan, ls_nodes[i], &starts[i].block, &starts[i].offset);
+                if (rc != VS_OK) return rc;
+            }
+        }
+        std::vector<uint8_t> body;
+        int rc = meta_page_bytes(m, starts, ML, body);
+        if (rc != VS_OK) return rc;
+        const uint8_t header[8] = {(uint8_t)(kTsvMagic & 0xFF), (uint8_t)((kTsvMagic >> 8) & 0xFF), (uint8_t)((kTsvMagic >> 16) & 0xFF),
+                                   (uint8_t)(kTsvMagic >> 24), 3, 0, 0, 0};  // to_bytes(MetaPageHeader {magic_number, version})
+        uint32_t b_, o_;
+        rel.chain_write(VS_PAGE_META, meta0, std::vector<uint8_t>(header, header + 8), b_, o_);
+        rel.chain_write(VS_PAGE_META, meta0, body, b_, o_);
+        if (b_ != 0 || o_ != 2) return fail("vs_pages_out_open: the MetaPage landed at (%u,%u)", b_, o_);
+        plan.n_blocks = rel.next_block;
+        for (int t = 0; t < 9; t++) plan.pages_by_type[t] = rel.by_type[t];
+        plan.host_pages.swap(rel.pages);
+        std::sort(plan.host_pages.begin(), plan.host_pages.end(), [](const auto& a, const auto& b2) { return a.first < b2.first; });
+    } catch (const std::bad_alloc&) {
+        vs_set_error("vs_pages_out_open: out of host memory");
+        return VS_ERR_OOM;
+    }
+    return VS_OK;
+}

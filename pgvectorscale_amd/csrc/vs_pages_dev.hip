@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "vs_device.h"
+#include "vs_pages_out.h"
 
 struct vs_pages_dev {
     vs_ctx* ctx = nullptr;
@@ -357,4 +358,433 @@ extern "C" int vs_pages_dev_build(vs_pages_dev* d, const vs_index_desc* desc, co
     }
     *out = ix;
     return VS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The way back (vs_pages_out_*): the index arrays composed into SbqNode pages ON the device.
+//
+// k_pages_encode: one workgroup (four waves) per node page.  The page is put together in 8 KB of LDS — zeroed, then the
+// PageHeaderData, the TsvPageOpaqueData special area, one line pointer per item and the items themselves: a wave per item, its
+// lanes over the 16-byte pieces of the code row and of the neighbor row (four neighbor ids become four ArchivedItemPointers: block and
+// offset of a classic node are arithmetic, those of a labeled node are gathered from node_block / page_first), then the label set
+// and the four 8-byte fields of the archived root — and leaves for global memory as 512 full-lane 16-byte stores.  Items are
+// MAXALIGNed (8 bytes) from pd_special = page_size - 8 downwards, so an item starts on an 8-byte, not a 16-byte boundary: the
+// LDS side of the copy is 8 bytes per store.  What the page must look like is restated in vs_pages.cpp (PageAddItemExtended,
+// Tape::write, rkyv to_bytes of ClassicSbqNode / LabeledSbqNode: code words, neighbor pointers, labels, root at the end).
+// ---------------------------------------------------------------------------------------------------------------
+struct PagesEncodeArgs {
+    const uint64_t* codes;
+    const uint32_t* nbrs;
+    const uint64_t* tids;
+    const uint32_t* label_off;   // labeled nodes only
+    const int16_t* label_val;
+    const uint32_t* page_first;  // labeled: first node of every node page (+ n at the end)
+    const uint32_t* node_block;  // labeled: block of every node's item
+    const uint16_t* node_lpoff;  // labeled: lp_off of every node's item
+    uint32_t code_stride, nbr_stride;
+    uint32_t n, W, R;
+    uint32_t K, item_size;       // classic: items per page, bytes per item
+    uint32_t first_node_block;
+    uint32_t root_size, o_heap, o_code, o_nbr, o_last;
+    uint32_t has_labels;
+};
+enum { PO_OK = 0, PO_NEIGHBOR = 1, PO_LAYOUT = 2 };
+constexpr uint32_t kOutPage = VS_BLCKSZ, kOutSpecial = VS_BLCKSZ - 8, kOutThreads = 256;
+
+typedef uint64_t __attribute__((may_alias)) po_u64;
+typedef uint32_t __attribute__((may_alias)) po_u32;
+typedef uint16_t __attribute__((may_alias)) po_u16;
+
+// ArchivedItemPointer {u32 block_number, u16 offset, 2 B pad} as one little-endian word
+__device__ __forceinline__ uint64_t item_pointer_word(uint32_t block, uint32_t offset) { return (uint64_t)block | ((uint64_t)offset << 32); }
+
+__global__ __launch_bounds__(kOutThreads) void k_pages_encode(PagesEncodeArgs a, uint32_t page0, uint4* __restrict__ out, uint32_t* __restrict__ err) {
+    __shared__ uint4 pg4[kOutPage / 16];
+    uint8_t* pg = reinterpret_cast<uint8_t*>(pg4);
+    const uint32_t tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    const uint32_t p = page0 + blockIdx.x;  // node page number: block first_node_block + p
+    pg4[tid] = make_uint4(0, 0, 0, 0);
+    pg4[tid + kOutThreads] = make_uint4(0, 0, 0, 0);
+    uint32_t first, cnt;
+    if (a.has_labels) {
+        first = a.page_first[p];
+        cnt = a.page_first[p + 1] - first;
+    } else {
+        first = p * a.K;
+        cnt = first < a.n ? min(a.K, a.n - first) : 0u;
+    }
+    __syncthreads();
+    const uint32_t body0 = 8 * a.W + 8 * a.R;
+    const uint32_t classic_step = (a.item_size + 7u) & ~7u;
+    if (tid == 0) {
+        // PageInit + cnt x PageAddItemExtended: pd_lsn, pd_checksum, pd_flags, pd_prune_xid stay zero
+        uint32_t upper = kOutSpecial;
+        if (cnt) upper = a.has_labels ? (uint32_t)a.node_lpoff[first + cnt - 1] : kOutSpecial - cnt * classic_step;
+        *reinterpret_cast<po_u32*>(pg + 12) = (24 + 4 * cnt) | (upper << 16);        // pd_lower, pd_upper
+        *reinterpret_cast<po_u32*>(pg + 16) = kOutSpecial | ((kOutPage | 4u) << 16);  // pd_special, pd_pagesize_version
+        *reinterpret_cast<po_u32*>(pg + kOutSpecial) = (uint32_t)VS_PAGE_SBQ_NODE | (0xAE24u << 16);  // TsvPageOpaqueData
+    }
+    for (uint32_t k = wave; k < cnt; k += kOutThreads / WAVE) {
+        const uint32_t node = first + k;
+        uint32_t L = 0, lo = 0, lp_off;
+        if (a.has_labels) {
+            lo = a.label_off[node];
+            L = a.label_off[node + 1] - lo;
+            lp_off = a.node_lpoff[node];
+        } else {
+            lp_off = kOutSpecial - (k + 1) * classic_step;
+        }
+        const uint32_t root = (body0 + 2 * L + 3u) & ~3u;
+        const uint32_t size = root + a.root_size;
+        // the layout was fixed at open from the label sets as they were then: an item that no longer fits where it was planned
+        // (or would run into the line pointers) is left out and reported, never written
+        const uint32_t above = k == 0 ? kOutSpecial : (a.has_labels ? (uint32_t)a.node_lpoff[node - 1] : lp_off + classic_step);
+        if (L > 0x8000u || lp_off + ((size + 7u) & ~7u) != above || lp_off < 24 + 4 * cnt || lp_off > kOutSpecial) {
+            if (lane == 0) page_error(err, PO_LAYOUT, a.first_node_block + p, k + 1, node);
+            continue;
+        }
+        uint8_t* item = pg + lp_off;
+        if (lane == 0) *reinterpret_cast<po_u32*>(pg + 24 + 4 * k) = lp_off | (1u << 15) | (size << 17);  // LP_NORMAL
+        // bq_vector: code rows are code_stride (even) words, 16-byte aligned
+        const uint64_t* crow = a.codes + (size_t)node * a.code_stride;
+        for (uint32_t w = 2 * lane; w < a.W; w += 2 * WAVE) {
+            const ulonglong2 v = *reinterpret_cast<const ulonglong2*>(crow + w);
+            *reinterpret_cast<po_u64*>(item + 8 * w) = v.x;
+            if (w + 1 < a.W) *reinterpret_cast<po_u64*>(item + 8 * w + 8) = v.y;
+        }
+        // neighbor_index_pointers: R slots, the list ends at the first VS_INVALID_NODE, (InvalidBlockNumber, 0) from there on
+        const uint32_t* nrow = a.nbrs + (size_t)node * a.nbr_stride;  // nbr_stride is a multiple of 16: 64-byte aligned rows
+        uint8_t* nb = item + 8 * a.W;
+        bool ended = false;
+        for (uint32_t j0 = 0; j0 < a.R; j0 += 4 * WAVE) {
+            const uint32_t j = j0 + 4 * lane;
+            uint4 v = make_uint4(VS_INVALID_NODE, VS_INVALID_NODE, VS_INVALID_NODE, VS_INVALID_NODE);
+            if (j < a.R) v = *reinterpret_cast<const uint4*>(nrow + j);
+            const uint32_t ids[4] = {v.x, v.y, v.z, v.w};
+            uint32_t fi = 4;  // first slot of this lane's four that ends the list (or lies past R)
+            for (int t = 3; t >= 0; --t)
+                if (j + t >= a.R || ids[t] == VS_INVALID_NODE) fi = (uint32_t)t;
+            const uint64_t enders = __ballot(fi < 4);
+            const uint32_t fl = enders ? (uint32_t)__builtin_ctzll(enders) : WAVE;
+            const uint32_t nvalid = ended ? 0u : (lane < fl ? 4u : (lane == fl ? fi : 0u));
+            // an id the index does not have is written as an invalid pointer; the item's lowest such slot is the one reported
+            uint32_t bad = 4;
+            for (int t = 3; t >= 0; --t)
+                if ((uint32_t)t < nvalid && ids[t] >= a.n) bad = (uint32_t)t;
+            const uint64_t bads = __ballot(bad < 4);
+            if (bads && lane == (uint32_t)__builtin_ctzll(bads)) page_error(err, PO_NEIGHBOR, a.first_node_block + p, k + 1, j + bad);
+            for (uint32_t t = 0; t < 4; ++t) {
+                if (j + t >= a.R) break;
+                uint64_t word = item_pointer_word(0xFFFFFFFFu, 0);
+                if (t < nvalid && ids[t] < a.n) {
+                    const uint32_t u = ids[t];
+                    if (a.has_labels) {
+                        const uint32_t blk = a.node_block[u];
+                        word = item_pointer_word(blk, u - a.page_first[blk - a.first_node_block] + 1);
+                    } else {
+                        word = item_pointer_word(a.first_node_block + u / a.K, u % a.K + 1);
+                    }
+                }
+                *reinterpret_cast<po_u64*>(nb + 8 * (j + t)) = word;
+            }
+            if (enders) ended = true;
+        }
+        // labels (ArchivedLabelSet = ArchivedVec<i16>)
+        for (uint32_t j = lane; j < L; j += WAVE) *reinterpret_cast<po_u16*>(item + body0 + 2 * j) = (uint16_t)a.label_val[lo + j];
+        // the archived root: heap_item_pointer and three ArchivedVec {i32 offset relative to the field, u32 len}
+        if (lane < 4) {
+            uint32_t fld, w0, w1;
+            if (lane == 0) {
+                const uint64_t tid64 = a.tids[node];
+                fld = a.o_heap;
+                w0 = (uint32_t)(tid64 >> 16);
+                w1 = (uint32_t)(tid64 & 0xFFFFu);
+            } else if (lane == 1) {
+                fld = a.o_code;
+                w0 = 0u - (root + fld);
+                w1 = a.W;
+            } else if (lane == 2) {
+                fld = a.o_nbr;
+                w0 = 8 * a.W - (root + fld);
+                w1 = a.R;
+            } else {
+                fld = a.o_last;
+                w0 = body0 - (root + fld);
+                w1 = L;
+            }
+            *reinterpret_cast<po_u32*>(item + root + fld) = w0;
+            *reinterpret_cast<po_u32*>(item + root + fld + 4) = w1;
+        }
+    }
+    __syncthreads();
+    uint4* dst = out + (size_t)blockIdx.x * (kOutPage / 16);
+    dst[tid] = pg4[tid];
+    dst[tid + kOutThreads] = pg4[tid + kOutThreads];
+}
+
+// nodes whose heap_item_pointer.offset is InvalidOffsetNumber
+__global__ __launch_bounds__(256) void k_pages_count_deleted(const uint64_t* __restrict__ tids, uint32_t n, uint32_t* __restrict__ out) {
+    uint32_t c = 0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) c += (tids[i] & 0xFFFFu) == 0;
+    if (c) atomicAdd(out, c);
+}
+
+struct vs_pages_out {
+    vs_index* ix = nullptr;
+    vs_ctx* ctx = nullptr;
+    PagesOutPlan plan;
+    PagesEncodeArgs args{};
+    uint32_t* d_page_first = nullptr;
+    uint32_t* d_node_block = nullptr;
+    uint16_t* d_node_lpoff = nullptr;
+    uint8_t* d_stage[2] = {nullptr, nullptr};  // one chunk of node pages each, as large as a pinned staging buffer
+    uint32_t* d_err = nullptr;
+    hipEvent_t ev_done[2] = {nullptr, nullptr};  // the encode of the chunk in d_stage[i] has finished
+    uint32_t chunk_pages = 0;
+};
+
+extern "C" void vs_pages_out_close(vs_pages_out* w) {
+    if (!w) return;
+    if (w->ctx) (void)hipSetDevice(w->ctx->device);
+    if (w->d_page_first) (void)hipFree(w->d_page_first);
+    if (w->d_node_block) (void)hipFree(w->d_node_block);
+    if (w->d_node_lpoff) (void)hipFree(w->d_node_lpoff);
+    for (int i = 0; i < 2; ++i) {
+        if (w->d_stage[i]) (void)hipFree(w->d_stage[i]);
+        if (w->ev_done[i]) (void)hipEventDestroy(w->ev_done[i]);
+    }
+    if (w->d_err) (void)hipFree(w->d_err);
+    delete w;
+}
+
+static int pages_out_open_impl(vs_index* ix, const vs_pages_out_params* p, vs_pages_out* w, vs_pages_info* info) {
+    vs_ctx* c = ix->ctx;
+    const vs_index_desc& d = ix->d;
+    VS_HIP(hipSetDevice(c->device));
+    VS_REQUIRE(c->pinned_bytes >= p->page_size, "vs_pages_out_open: the context's staging buffers (%zu bytes) do not hold one page", c->pinned_bytes);
+    // what the host half needs: quantizer, label offsets (labeled nodes), the labeled start nodes
+    std::vector<float> mean(d.dim_index), m2(d.dim_index);
+    uint64_t count = 0;
+    VS_TRY(vs_index_get_quantizer(ix, mean.data(), m2.data(), &count));
+    std::vector<uint32_t> label_off;
+    if (d.has_labels) {
+        VS_REQUIRE(ix->label_off && ix->label_val, "vs_pages_out_open: the index says has_labels but holds no label sets");
+        label_off.resize((size_t)d.n + 1);
+        VS_TRY(vs_dev_download(c, label_off.data(), ix->label_off, ((size_t)d.n + 1) * 4));
+    }
+    std::vector<int16_t> ls_labels(d.n_label_starts);
+    std::vector<uint32_t> ls_nodes(d.n_label_starts);
+    if (d.n_label_starts) {
+        VS_TRY(vs_dev_download(c, ls_labels.data(), ix->ls_labels, (size_t)d.n_label_starts * 2));
+        VS_TRY(vs_dev_download(c, ls_nodes.data(), ix->ls_nodes, (size_t)d.n_label_starts * 4));
+    }
+    VS_TRY(vs_pages_out_plan(d, *p, mean.data(), m2.data(), count, d.has_labels ? label_off.data() : nullptr, ls_labels.data(), ls_nodes.data(),
+                             w->plan));
+    PagesOutPlan& plan = w->plan;
+    if (plan.has_labels) {
+        VS_HIP(hipMalloc(&w->d_page_first, plan.page_first.size() * 4));
+        VS_HIP(hipMalloc(&w->d_node_block, std::max<size_t>(plan.node_block.size(), 1) * 4));
+        VS_HIP(hipMalloc(&w->d_node_lpoff, std::max<size_t>(plan.node_lpoff.size(), 1) * 2));
+        VS_TRY(vs_dev_upload(c, w->d_page_first, plan.page_first.data(), plan.page_first.size() * 4));
+        VS_TRY(vs_dev_upload(c, w->d_node_block, plan.node_block.data(), plan.node_block.size() * 4));
+        VS_TRY(vs_dev_upload(c, w->d_node_lpoff, plan.node_lpoff.data(), plan.node_lpoff.size() * 2));
+        std::vector<uint32_t>().swap(plan.node_block);  // the host keeps page_first only (vs_pages_out_item_pointer_of)
+        std::vector<uint16_t>().swap(plan.node_lpoff);
+    }
+    w->chunk_pages = (uint32_t)std::min<size_t>(c->pinned_bytes / plan.page_size, std::max<uint32_t>(plan.n_node_pages, 1));
+    for (int i = 0; i < 2; ++i) {
+        VS_HIP(hipMalloc(&w->d_stage[i], (size_t)w->chunk_pages * plan.page_size));
+        VS_HIP(hipEventCreateWithFlags(&w->ev_done[i], hipEventDisableTiming));
+    }
+    VS_HIP(hipMalloc(&w->d_err, 32));
+    VS_HIP(hipMemsetAsync(w->d_err, 0, 32, c->stream));
+    PagesEncodeArgs& a = w->args;
+    a.codes = ix->codes;
+    a.nbrs = ix->nbrs;
+    a.tids = ix->tids;
+    a.label_off = plan.has_labels ? ix->label_off : nullptr;
+    a.label_val = plan.has_labels ? ix->label_val : nullptr;
+    a.page_first = w->d_page_first;
+    a.node_block = w->d_node_block;
+    a.node_lpoff = w->d_node_lpoff;
+    a.code_stride = ix->code_stride;
+    a.nbr_stride = ix->nbr_stride;
+    a.n = d.n;
+    a.W = d.words;
+    a.R = d.num_neighbors;
+    a.K = plan.K;
+    a.item_size = plan.item_size;
+    a.first_node_block = plan.first_node_block;
+    a.root_size = plan.lay.root_size;
+    a.o_heap = plan.lay.off_heap_item_pointer;
+    a.o_code = plan.lay.off_bq_vector;
+    a.o_nbr = plan.lay.off_neighbor_index_pointers;
+    a.o_last = plan.lay.off_labels;
+    a.has_labels = plan.has_labels ? 1u : 0u;
+    // n_deleted, as a reader of the result counts it
+    uint32_t n_deleted = 0;
+    if (d.n) {
+        hipLaunchKernelGGL(k_pages_count_deleted, dim3(std::min<uint32_t>((d.n + 255) / 256, 1024)), dim3(256), 0, c->stream, (const uint64_t*)ix->tids,
+                           d.n, w->d_err + 4);
+        VS_HIP(hipGetLastError());
+        VS_HIP(hipMemcpyAsync(&n_deleted, w->d_err + 4, 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    VS_HIP(hipStreamSynchronize(c->stream));
+    if (info) {
+        memset(info, 0, sizeof *info);
+        info->n_blocks = plan.n_blocks;
+        info->n_nodes = d.n;
+        info->words = d.words;
+        info->num_neighbors = d.num_neighbors;
+        info->has_labels = plan.has_labels;
+        info->n_deleted = n_deleted;
+        info->n_label_vals = plan.n_label_vals;
+        for (int t = 0; t < 9; ++t) info->pages_by_type[t] = plan.pages_by_type[t];
+        info->meta_magic = 768756476u;  // TSV_MAGIC_NUMBER (AM/meta_page.rs:22)
+        info->meta_version = 3;
+    }
+    return VS_OK;
+}
+
+extern "C" int vs_pages_out_open(vs_index* ix, const vs_pages_out_params* p, vs_pages_out** out, vs_pages_info* info) {
+    VS_REQUIRE(ix && p && out, "vs_pages_out_open: bad args");
+    *out = nullptr;
+    VS_REQUIRE(ix->d.storage_type == VS_STORAGE_SBQ, "vs_pages_out_open: memory_optimized (SBQ) indexes only; writing `plain` storage is not supported");
+    VS_REQUIRE(ix->codes && ix->nbrs && ix->tids, "vs_pages_out_open: the index holds no codes / neighbors");
+    return vs_guard("vs_pages_out_open", [&] {
+        vs_pages_out* w = new vs_pages_out();
+        w->ix = ix;
+        w->ctx = ix->ctx;
+        const int r = pages_out_open_impl(ix, p, w, info);
+        if (r != VS_OK) {
+            vs_pages_out_close(w);
+            return r;
+        }
+        *out = w;
+        return (int)VS_OK;
+    });
+}
+
+extern "C" int vs_pages_out_item_pointer_of(const vs_pages_out* w, uint32_t node, uint32_t* block, uint32_t* offset) {
+    VS_REQUIRE(w, "vs_pages_out_item_pointer_of: null writer");
+    return vs_pages_out_plan_item_pointer(w->plan, node, block, offset);
+}
+
+// node pages [p0, p0 + np) into d_out, on the compute stream
+static int launch_pages_encode(vs_pages_out* w, uint32_t p0, uint32_t np, void* d_out) {
+    vs_ctx* c = w->ctx;
+    hipEvent_t ev = prof_begin(c);
+    hipLaunchKernelGGL(k_pages_encode, dim3(np), dim3(kOutThreads), 0, c->stream, w->args, p0, reinterpret_cast<uint4*>(d_out), w->d_err);
+    VS_HIP(hipGetLastError());
+    prof_end(c, PK_PAGES, ev);
+    return VS_OK;
+}
+
+// after the stream has been synchronised: what the kernels reported
+static int pages_out_check(vs_pages_out* w) {
+    uint32_t herr[4] = {0, 0, 0, 0};
+    VS_HIP(hipMemcpy(herr, w->d_err, 16, hipMemcpyDeviceToHost));
+    if (herr[0] == PO_OK) return VS_OK;
+    VS_HIP(hipMemset(w->d_err, 0, 16));
+    if (herr[0] == PO_NEIGHBOR) vs_set_error("block %u item %u: neighbor slot %u names a node the index does not have", herr[1], herr[2], herr[3]);
+    else vs_set_error("block %u item %u (node %u): the label sets changed after vs_pages_out_open fixed the layout", herr[1], herr[2], herr[3]);
+    return VS_ERR_INVALID;
+}
+
+// the metadata pages inside [first_block, first_block + n_blocks): fn(block, bytes)
+template <class F>
+static int pages_out_host_pages(const vs_pages_out* w, uint32_t first_block, uint32_t n_blocks, F&& fn) {
+    for (const auto& hp : w->plan.host_pages)
+        if (hp.first >= first_block && hp.first - first_block < n_blocks) VS_TRY(fn(hp.first, hp.second.data()));
+    return VS_OK;
+}
+
+static int pages_out_range(const vs_pages_out* w, const char* what, uint32_t first_block, uint32_t n_blocks, const void* pages, uint32_t* p0,
+                           uint32_t* np) {
+    VS_REQUIRE(w && (pages || !n_blocks), "%s: bad args", what);
+    VS_REQUIRE((uint64_t)first_block + n_blocks <= w->plan.n_blocks, "%s: blocks %u .. %llu of a relation of %u blocks", what, first_block,
+               (unsigned long long)first_block + n_blocks, w->plan.n_blocks);
+    const uint32_t fnb = w->plan.first_node_block, end = first_block + n_blocks;
+    const uint32_t lo = std::max(first_block, fnb), hi = std::min(end, fnb + w->plan.n_node_pages);
+    *p0 = lo < hi ? lo - fnb : 0;
+    *np = lo < hi ? hi - lo : 0;
+    return VS_OK;
+}
+
+static int pages_out_read_impl(vs_pages_out* w, uint32_t first_block, uint32_t n_blocks, void* pages) {
+    uint32_t p0 = 0, np = 0;
+    VS_TRY(pages_out_range(w, "vs_pages_out_read", first_block, n_blocks, pages, &p0, &np));
+    vs_ctx* c = w->ctx;
+    const size_t ps = w->plan.page_size;
+    uint8_t* dst = static_cast<uint8_t*>(pages);
+    VS_HIP(hipSetDevice(c->device));
+    VS_TRY(pages_out_host_pages(w, first_block, n_blocks, [&](uint32_t blk, const uint8_t* bytes) {
+        memcpy(dst + (size_t)(blk - first_block) * ps, bytes, ps);
+        return (int)VS_OK;
+    }));
+    if (np == 0) return VS_OK;
+    // chunk i is encoded into d_stage[i & 1] on the compute stream, copied to pinned[i & 1] on the copy stream once its kernel has
+    // finished, and drained to the caller's buffer when its slot comes round again: the kernel of chunk i + 1 runs under the copy of
+    // chunk i, the host's copy out of one pinned buffer under the transfer into the other (as vs_dev_download).  The kernel of
+    // chunk i is queued BEFORE the host drains chunk i - 2 out of pinned[i & 1]: it waits on the device for that chunk's transfer
+    // (d_stage[i & 1] is free then), not for the host's memcpy; only the transfer into pinned[i & 1] comes after the drain.
+    uint8_t* node_dst = dst + (size_t)(w->plan.first_node_block + p0 - first_block) * ps;
+    const uint32_t nchunks = (np + w->chunk_pages - 1) / w->chunk_pages;
+    size_t pend_off[2] = {0, 0}, pend_n[2] = {0, 0};
+    auto pump = [&]() -> int {
+        for (uint32_t i = 0; i < nchunks + 2; ++i) {
+            const int slot = (int)(i & 1);
+            const uint32_t q0 = i * w->chunk_pages, qn = i < nchunks ? std::min(w->chunk_pages, np - q0) : 0;
+            if (qn) {
+                if (pend_n[slot]) VS_HIP(hipStreamWaitEvent(c->stream, c->pinned_ev[slot], 0));
+                VS_TRY(launch_pages_encode(w, p0 + q0, qn, w->d_stage[slot]));
+                VS_HIP(hipEventRecord(w->ev_done[slot], c->stream));
+            }
+            if (pend_n[slot]) {
+                VS_HIP(hipEventSynchronize(c->pinned_ev[slot]));
+                stage_copy(node_dst + pend_off[slot], c->pinned[slot], pend_n[slot]);
+                pend_n[slot] = 0;
+            }
+            if (qn) {
+                VS_HIP(hipStreamWaitEvent(c->copy_stream, w->ev_done[slot], 0));
+                VS_HIP(hipMemcpyAsync(c->pinned[slot], w->d_stage[slot], (size_t)qn * ps, hipMemcpyDeviceToHost, c->copy_stream));
+                VS_HIP(hipEventRecord(c->pinned_ev[slot], c->copy_stream));
+                pend_off[slot] = (size_t)q0 * ps;
+                pend_n[slot] = (size_t)qn * ps;
+            }
+        }
+        return VS_OK;
+    };
+    const int rc = pump();
+    if (rc != VS_OK) {  // nothing may still be on its way into the context's pinned buffers when the call returns
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipStreamSynchronize(c->copy_stream);
+        return rc;
+    }
+    VS_HIP(hipStreamSynchronize(c->stream));
+    return pages_out_check(w);
+}
+
+extern "C" int vs_pages_out_read(vs_pages_out* w, uint32_t first_block, uint32_t n_blocks, void* pages) {
+    return vs_guard("vs_pages_out_read", [&] { return pages_out_read_impl(w, first_block, n_blocks, pages); });
+}
+
+static int pages_out_read_dev_impl(vs_pages_out* w, uint32_t first_block, uint32_t n_blocks, void* d_pages) {
+    uint32_t p0 = 0, np = 0;
+    VS_TRY(pages_out_range(w, "vs_pages_out_read_dev", first_block, n_blocks, d_pages, &p0, &np));
+    vs_ctx* c = w->ctx;
+    const size_t ps = w->plan.page_size;
+    uint8_t* dst = static_cast<uint8_t*>(d_pages);
+    VS_REQUIRE(((uintptr_t)dst & 15) == 0, "vs_pages_out_read_dev: the device buffer must be 16-byte aligned");
+    VS_HIP(hipSetDevice(c->device));
+    if (np) VS_TRY(launch_pages_encode(w, p0, np, dst + (size_t)(w->plan.first_node_block + p0 - first_block) * ps));
+    VS_TRY(pages_out_host_pages(w, first_block, n_blocks, [&](uint32_t blk, const uint8_t* bytes) {
+        return vs_dev_upload(c, dst + (size_t)(blk - first_block) * ps, bytes, ps);
+    }));
+    VS_HIP(hipStreamSynchronize(c->stream));
+    return pages_out_check(w);
+}
+
+extern "C" int vs_pages_out_read_dev(vs_pages_out* w, uint32_t first_block, uint32_t n_blocks, void* d_pages) {
+    return vs_guard("vs_pages_out_read_dev", [&] { return pages_out_read_dev_impl(w, first_block, n_blocks, d_pages); });
 }

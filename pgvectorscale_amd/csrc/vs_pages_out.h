@@ -1,0 +1,34 @@
+// vs_pages_out.h — the host half of the page writer (vs_pages.cpp), shared with its device half (vs_pages_dev.hip).
+// Plain C++: no HIP in here.
+#pragma once
+#include <cstdint>
+#include <utility>
+#include <vector>
+
+#include "../../include/vsgpu.h"
+
+// The whole layout of the relation a vs_pages_out writes, fixed at open.
+struct PagesOutPlan {
+    uint32_t page_size = VS_BLCKSZ;
+    uint32_t n = 0, W = 0, R = 0;
+    bool has_labels = false;
+    vs_node_layout lay{};        // off_labels = where the last 8-byte field goes (labels, or the empty _neighbor_vectors)
+    uint32_t first_node_block = 0, n_node_pages = 0, n_blocks = 0;
+    // classic nodes: every item has item_size bytes, K of them fill a page
+    uint32_t item_size = 0, K = 0;
+    // labeled nodes: first node of every node page (n_node_pages + 1 entries, the last one = n) and, until the device half has
+    // taken them over, block and lp_off of every node's item
+    std::vector<uint32_t> page_first;
+    std::vector<uint32_t> node_block;
+    std::vector<uint16_t> node_lpoff;
+    // Meta chain and SbqMeans chain, by block number (ascending)
+    std::vector<std::pair<uint32_t, std::vector<uint8_t>>> host_pages;
+    uint32_t pages_by_type[9] = {0};
+    uint64_t n_label_vals = 0;
+};
+
+// label_off: host copy of the index's label offsets (n + 1 entries) for labeled nodes, else null; ls_labels / ls_nodes: the
+// labeled start nodes (d.n_label_starts entries, node ids)
+int vs_pages_out_plan(const vs_index_desc& d, const vs_pages_out_params& p, const float* mean, const float* m2, uint64_t count,
+                      const uint32_t* label_off, const int16_t* ls_labels, const uint32_t* ls_nodes, PagesOutPlan& plan);
+int vs_pages_out_plan_item_pointer(const PagesOutPlan& plan, uint32_t node, uint32_t* block, uint32_t* offset);

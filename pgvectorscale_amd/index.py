@@ -72,7 +72,7 @@ class Context:
         """{kernel: (total_ms, launches)} from HIP events recorded on the ctx stream."""
         p = _lib.Profile()
         check(self._L.vs_profile_read(self.h, C.byref(p), int(reset)))
-        names = ["prepare_queries", "search", "rerank", "resort", "search_fallback", "scan", "rerank_order"]
+        names = ["prepare_queries", "search", "rerank", "resort", "search_fallback", "scan", "rerank_order", "pages_encode"]
         return {n: (float(p.ms[k]), int(p.launches[k])) for k, n in enumerate(names)}
 
     def ws_probe(self, d_mem, nbytes, iters=600):
@@ -304,6 +304,15 @@ class DiskAnnIndex:
     def build_unreachable(self):
         """nodes the last build_graph left unreachable from the default start node (0 on well-formed input)"""
         return int(self._L.vs_index_build_unreachable(self.h))
+
+    def write_pages(self, **kw):
+        """the index as the bytes of a `diskann` index relation (pages.PagesOut in one call; keyword arguments as PagesOut's)"""
+        from .pages import PagesOut
+        w = PagesOut(self, **kw)
+        try:
+            return w.read().tobytes()
+        finally:
+            w.close()
 
     # -- single kernels ------------------------------------------------------------------------------------------------
     def save_graph(self, path):

@@ -6,13 +6,16 @@ arrays of `vs_index_host`, and `upload()` streams them to the device through the
 read from the pages is what the reference itself keeps elsewhere or only the Rust side can decode: the heap's vector
 column (`vecs`, needed for rerank).  The MetaPage body (geometry, start nodes, the SbqMeans pointer) is decoded by
 `meta()` / `upload_from_meta()` (vs_pages_meta), or passed by hand to `upload()`.
+
+The way back is `PagesOut` (vs_pages_out_*): a device-resident index written out as the same relation, block range by block
+range, and `encode_meta_page` next to `decode_meta_page`.
 """
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
-from ._lib import HeapAttr, HeapInfo, IndexDesc, IndexHost, MetaLayout, MetaPage, NodeLayout, PagesInfo, check
+from ._lib import HeapAttr, HeapInfo, IndexDesc, IndexHost, MetaLayout, MetaPage, NodeLayout, PagesInfo, PagesOutParams, check
 
 BLCKSZ = 8192
 PAGE_SBQ_MEANS, PAGE_META = 7, 8
@@ -42,6 +45,27 @@ def decode_meta_page(data, layout=None):
     check(L.vs_meta_page_decode(buf.ctypes.data_as(C.c_void_p), buf.size, None if lay is None else C.byref(lay), C.byref(m),
                                 lab.ctypes.data_as(C.c_void_p), blk.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p), n))
     return m.as_dict(), {int(l): (int(b), int(o)) for l, b, o in zip(lab, blk, off)}
+
+
+def encode_meta_page(fields, labeled_starts=None, layout=None):
+    """rkyv::to_bytes::<MetaPage>: `fields` as decode_meta_page returns them (missing keys are zero; has_start_nodes selects
+    Some(StartNodes)), labeled_starts {label: (block, offset)} -> the bytes of the chain payload at (0, 2)"""
+    L = _lib.load()
+    m = MetaPage()
+    for k, v in fields.items():
+        setattr(m, k, v.encode() if isinstance(v, str) else v)
+    ls = sorted((labeled_starts or {}).items())
+    lab = np.array([k for k, _ in ls], np.int16)
+    blk = np.array([v[0] for _, v in ls], np.uint32)
+    off = np.array([v[1] for _, v in ls], np.uint32)
+    lay = _meta_layout(layout)
+    args = (C.byref(m), lab.ctypes.data_as(C.c_void_p), blk.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p), len(ls),
+            None if lay is None else C.byref(lay))
+    n = C.c_size_t()
+    check(L.vs_meta_page_encode(*args, None, 0, C.byref(n)))
+    buf = np.empty(int(n.value), np.uint8)
+    check(L.vs_meta_page_encode(*args, buf.ctypes.data_as(C.c_void_p), buf.size, C.byref(n)))
+    return buf.tobytes()
 
 
 def _meta_of(fn, handle, layout):
@@ -377,3 +401,66 @@ class DevicePages:
         if self.h:
             self._L.vs_pages_dev_close(self.h)
             self.h = None
+
+
+class PagesOut:
+    """A device-resident memory_optimized index written out as the pages of a `diskann` index relation (vs_pages_out_*): the
+    layout is fixed here, `read` hands out any block range any number of times.  layout: a vs_node_layout 5-tuple (root size, heap
+    pointer, code, neighbors, labels / fourth field), meta_layout: a dict as oracle/pages_py.meta_layout() gives."""
+
+    def __init__(self, index, extension_version="0.8.0", search_list_size=100, max_alpha=1.2, layout=None, meta_layout=None,
+                 page_size=BLCKSZ):
+        self._L = index._L
+        self.index = index
+        self.page_size = page_size
+        self._lay = None if layout is None else NodeLayout(*layout)
+        self._mlay = _meta_layout(meta_layout)
+        p = PagesOutParams()
+        p.page_size = page_size
+        p.node_layout = None if self._lay is None else C.pointer(self._lay)
+        p.meta_layout = None if self._mlay is None else C.pointer(self._mlay)
+        p.extension_version = extension_version.encode()
+        p.search_list_size, p.max_alpha = search_list_size, max_alpha
+        h, info = C.c_void_p(), PagesInfo()
+        check(self._L.vs_pages_out_open(index.h, C.byref(p), C.byref(h), C.byref(info)))
+        self.h = h
+        self.info = info
+        self.n_blocks = int(info.n_blocks)
+
+    def read(self, first_block=0, n_blocks=None, out=None):
+        """blocks first_block .. first_block + n_blocks - 1 as a uint8 array (into `out` when given)"""
+        nb = self.n_blocks - first_block if n_blocks is None else n_blocks
+        if out is None:
+            out = np.empty(max(nb, 0) * self.page_size, np.uint8)
+        assert out.flags["C_CONTIGUOUS"] and out.nbytes >= nb * self.page_size
+        check(self._L.vs_pages_out_read(self.h, first_block, nb, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def read_dev(self, dev_ptr, first_block=0, n_blocks=None):
+        """the same into device memory (Context.alloc): the node pages never cross PCIe"""
+        nb = self.n_blocks - first_block if n_blocks is None else n_blocks
+        check(self._L.vs_pages_out_read_dev(self.h, first_block, nb, dev_ptr))
+
+    def item_pointer_of(self, node):
+        b, o = C.c_uint32(), C.c_uint32()
+        check(self._L.vs_pages_out_item_pointer_of(self.h, node, C.byref(b), C.byref(o)))
+        return int(b.value), int(o.value)
+
+    def write_file(self, path, chunk_blocks=16384):
+        """the relation's main fork as one file, streamed chunk by chunk"""
+        buf = np.empty(min(chunk_blocks, max(self.n_blocks, 1)) * self.page_size, np.uint8)
+        with open(path, "wb") as f:
+            for b0 in range(0, self.n_blocks, chunk_blocks):
+                nb = min(chunk_blocks, self.n_blocks - b0)
+                f.write(self.read(b0, nb, out=buf)[:nb * self.page_size].data)
+
+    def close(self):
+        if self.h:
+            self._L.vs_pages_out_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
