@@ -469,8 +469,6 @@ extern "C" void vs_index_free(vs_index* ix) {
     for (DevBuf* b : bufs) devbuf_free(*b);
     if (w.red_host) (void)hipHostFree(w.red_host);
     w.red_host = nullptr;
-    free(w.pend_blob);
-    w.pend_blob = nullptr;
     vs_slab_release(ix->slab);  // (after the stream synchronisation above; the last handle frees the allocation)
     delete ix;
 }

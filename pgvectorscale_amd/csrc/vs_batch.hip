@@ -17,14 +17,6 @@
 // ---------------------------------------------------------------------------------------------------------------
 // batched scans
 // ---------------------------------------------------------------------------------------------------------------
-struct Caps {
-    uint32_t hl, hcap, vcap, lh, hashcap, g0;  // general kernel (vs_search.hip)
-    // fast kernel (vs_search_fast.hip); f_lh == 0: no LDS dedup table (every id in the global table)
-    bool f_on;
-    uint32_t f_hl, f_hcap, f_gstride, f_lh, f_gcap, f_sb, f_vr, f_vcap;
-    double f_pool_frac;  // share of the scans expected to need a global dedup-overflow table
-};
-
 // a launch knob: the environment variable when set, else the index's tuned variant (vs_index_autotune), else the default
 static uint32_t knob_u32(const char* name, int tuned, uint32_t dflt) {
     const char* v = vs_opt_get(name);
@@ -140,24 +132,6 @@ static bool grow_caps(Caps& c, uint32_t ovf) {
     return grew;
 }
 
-// runs prepare -> search (-> rerank -> resort) for nq queries already on the device.  Outputs land in the workspace
-// (or the caller's device buffers).  Synchronous w.r.t. overflow retries when `allow_sync` is set.
-struct BatchPlan {
-    uint32_t nq, L, rescore, k, M;
-    bool stream_only;  // vs_stream_batch: no rerank
-};
-
-// rerank + rescore window over the streams the search kernels left in the workspace
-struct PendingBatch {
-    BatchPlan bp;
-    Caps caps;
-    const int16_t* d_qlabels;
-    const uint32_t* d_qlabel_off;
-    uint32_t* d_out_ids;
-    uint64_t* d_out_tids;
-    float* d_out_dist;
-};
-
 // VS_RERANK_ORDER: whether this batch's rerank takes its scans in the order of their corpus neighbourhood (k_scan_regions), and with
 // how many seed rows (0 = no: the launch is the plain one, nothing else runs).  0 = never, 2 = whenever the kernel can tile the
 // index's codes, 1 (default) = by rule: the ordering pays when rows are fetched several times per batch (expected fetches per corpus
@@ -183,6 +157,7 @@ extern "C" int vs_index_rerank_order(vs_index* ix, uint32_t* out_perm, uint32_t 
     return VS_OK;
 }
 
+// rerank + rescore window over the streams the search kernels left in the workspace
 static int run_post_search(vs_index* ix, const BatchPlan& bp, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist) {
     vs_ctx* c = ix->ctx;
     SearchWorkspace& w = ix->ws;
@@ -245,12 +220,51 @@ static int enqueue_reduce(vs_index* ix, const BatchPlan& bp) {
     return VS_OK;
 }
 
+// the general kernel's launch over the workspace of this chunk (w.hash / w.heap_g reserved by the caller); what differs between its
+// callers — only_failed, fb_flag, the region pool — is theirs to set
+static SearchLaunch general_launch(const vs_index* ix, const BatchPlan& bp, const Caps& caps, const int16_t* d_qlabels,
+                                   const uint32_t* d_qlabel_off) {
+    const SearchWorkspace& w = ix->ws;
+    SearchLaunch s;
+    s.nq = bp.nq;
+    s.L = bp.L;
+    s.M = bp.M;
+    s.hl = caps.hl;
+    s.hcap = caps.hcap;
+    s.vcap = caps.vcap;
+    s.lh = caps.lh;
+    s.hashcap = caps.hashcap;
+    s.g0 = caps.g0;
+    s.qcodes = (const uint64_t*)w.qcodes.p;
+    s.qlabels = d_qlabels;
+    s.qlabel_off = d_qlabel_off;
+    s.heap_g = (uint64_t*)w.heap_g.p;
+    s.hash = (uint32_t*)w.hash.p;
+    s.out_ids = (uint32_t*)w.stream_ids.p;
+    s.out_ham = (uint32_t*)w.stream_ham.p;
+    s.out_cnt = (uint32_t*)w.stream_cnt.p;
+    s.stats = (uint32_t*)w.stats.p;
+    s.status = (uint32_t*)w.status.p;
+    s.visible = (!bp.stream_only && bp.rescore > 0) ? ix->visible : nullptr;
+    return s;
+}
+
+// the general kernel's per-scan regions (dedup ladder, heap spill array) for `gslots` scans
+static int reserve_general_regions(vs_index* ix, const Caps& caps, uint32_t gslots) {
+    vs_ctx* c = ix->ctx;
+    SearchWorkspace& w = ix->ws;
+    const size_t hg = caps.hcap > caps.hl ? caps.hcap - caps.hl : 0;
+    VS_TRY(devbuf_reserve(c, w.hash, (size_t)gslots * caps.hashcap * 4));
+    VS_TRY(devbuf_reserve(c, w.heap_g, std::max<size_t>((size_t)gslots * hg * 8, 16)));
+    return devbuf_reserve(c, w.pool_ctr, 64);
+}
+
 // (re)runs the general kernel over the scans whose status is non-zero until none is left; synchronises the stream
 static int retry_failed_scans(vs_index* ix, const BatchPlan& bp, const int16_t* d_qlabels, const uint32_t* d_qlabel_off,
                               Caps& caps, vs_stats* st) {
     vs_ctx* c = ix->ctx;
     SearchWorkspace& w = ix->ws;
-    const uint32_t nq = bp.nq, M = bp.M;
+    const uint32_t nq = bp.nq;
     std::vector<uint32_t> status(nq);
     for (int attempt = 0;; ++attempt) {
         VS_HIP(hipMemcpyAsync(status.data(), w.status.p, (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
@@ -267,46 +281,372 @@ static int retry_failed_scans(vs_index* ix, const BatchPlan& bp, const int16_t* 
                          ovf, caps.hcap, caps.vcap, caps.hashcap);
             return VS_ERR_CAPACITY;
         }
-        const size_t hg = caps.hcap > caps.hl ? caps.hcap - caps.hl : 0;
         const uint32_t gslots = std::min<uint32_t>(nq, std::max<uint32_t>(general_pool_slots(nq), nbad));
-        VS_TRY(devbuf_reserve(c, w.hash, (size_t)gslots * caps.hashcap * 4));
-        VS_TRY(devbuf_reserve(c, w.heap_g, std::max<size_t>((size_t)gslots * hg * 8, 16)));
-        VS_TRY(devbuf_reserve(c, w.pool_ctr, 64));
+        VS_TRY(reserve_general_regions(ix, caps, gslots));
         VS_HIP(hipMemsetAsync((char*)w.pool_ctr.p + 32, 0, 4, c->stream));
-        SearchLaunch s;
-        s.nq = nq;
-        s.L = bp.L;
-        s.M = M;
-        s.hl = caps.hl;
-        s.hcap = caps.hcap;
-        s.vcap = caps.vcap;
-        s.lh = caps.lh;
-        s.hashcap = caps.hashcap;
-        s.g0 = caps.g0;
-        s.qcodes = (const uint64_t*)w.qcodes.p;
-        s.qlabels = d_qlabels;
-        s.qlabel_off = d_qlabel_off;
-        s.heap_g = (uint64_t*)w.heap_g.p;
-        s.hash = (uint32_t*)w.hash.p;
-        s.out_ids = (uint32_t*)w.stream_ids.p;
-        s.out_ham = (uint32_t*)w.stream_ham.p;
-        s.out_cnt = (uint32_t*)w.stream_cnt.p;
-        s.stats = (uint32_t*)w.stats.p;
-        s.status = (uint32_t*)w.status.p;
+        SearchLaunch s = general_launch(ix, bp, caps, d_qlabels, d_qlabel_off);
         s.only_failed = 1;
         s.fb_flag = w.fb_valid ? (uint32_t*)w.fb_flag.p : nullptr;
         s.pool_counter = (uint32_t*)((char*)w.pool_ctr.p + 32);
         s.pool_slots = gslots;
-        s.visible = (!bp.stream_only && bp.rescore > 0) ? ix->visible : nullptr;
         hipEvent_t ev = prof_begin(c);
         VS_TRY(launch_search(ix, s));
         prof_end(c, PK_SEARCH_FB, ev);
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// the first attempt of k_search_fast: which instantiation, with which capacities, on how large a grid.  plan_fast_launch decides
+// (one measured rule per function below, in the order they were found and must run); run_fast_attempts binds buffers and launches.
+// ---------------------------------------------------------------------------------------------------------------
+struct FastPlan {
+    FastLaunch f;      // every field that is not a buffer (the pointers that select an instantiation are fast_select() or null)
+    uint32_t gregion;  // u32 words of one region of the dedup table array
+    uint32_t fslots;   // regions of the dedup table array (and, on a persistent grid, of the heap spill array)
+};
+// stands for "there will be label keys / a visibility mask / a phase buffer" while a launch is planned: fast_resident_scans picks the
+// instantiation from which of these pointers are set and dereferences none; bind_fast_buffers puts the real ones in their place
+template <class T>
+static T* fast_select() {
+    return (T*)16;
+}
+
+static bool opt_is_set(const char* name) {
+    const char* v = vs_opt_get(name);
+    return v && *v;
+}
+static uint32_t visited_want(uint32_t L) { return (uint32_t)std::min<uint64_t>((uint64_t)L + L / 2 + 32, 1u << 20); }
+
+// One question of a rule: does `cand` keep enough of the resident scans of `base` — num * res_cand >= den * res_base?  With names
+// given, VS_WS_DEBUG prints both counts.
+static int candidate_holds(vs_index* ix, const FastLaunch& base, const FastLaunch& cand, uint64_t num, uint64_t den, bool* holds,
+                           const char* base_name = nullptr, const char* cand_name = nullptr, const char* tail = "") {
+    uint32_t res_base = 0, res_cand = 0;
+    VS_TRY(fast_resident_scans(ix, base, &res_base));
+    VS_TRY(fast_resident_scans(ix, cand, &res_cand));
+    if (base_name && env_u32("VS_WS_DEBUG", 0))
+        fprintf(stderr, "[VS_WS_DEBUG] resident scans: %s %u, %s %u%s\n", base_name, res_base, cand_name, res_cand, tail);
+    *holds = num * res_cand >= den * res_base;
+    return VS_OK;
+}
+
+// table form, 4-byte entries: *slot_eligible = one occupancy bit per slot is possible for this table (whether or not the 4-byte slot
+// bitmap is taken)
+static int choose_table_bitmap(vs_index* ix, FastLaunch& f, uint32_t vmode, bool phase, bool* slot_eligible) {
+    // written-bucket bitmap (VS_F_VIRGIN=1, table-less regime): 128 slots of the table per LDS word; tables of more than
+    // 64 Ki slots keep the clear (the bitmap would cost occupancy)
+    // ... or (VS_F_VIRGIN=2) one bit per SLOT: linear probing at slot granularity with the occupancy known on chip, so most new
+    // ids are stored without a load of the table; 32 slots per LDS word — taken only while it costs no scans per CU (else the
+    // bucket bitmap runs)
+    // Default since round 4's third GPU session: the slot bitmap — 161.1 ms per 262 144 scans at 50M against 167.9 with the bucket
+    // bitmap and 171.2 with cleared tables, 125.8 / 129.7 / 130.1 at 10M (profiles/r04/s3_ab_slotmap_*.txt); 639 device fuzz cases.
+    // Default since round 5: the 16-bit tables below (VS_F_VIRGIN=3) — 139.7 ms per 262 144 scans at 50M against 153.5 with the 4-byte
+    // slot-bitmap tables, same session, same slab (profiles/r05/s10_ab_q16_50m.txt); 300 device fuzz runs, regimes green on hardware.
+    *slot_eligible = false;
+    if (f.lh != 0 || f.vr || !vmode || phase || f.gcap > (1u << 16)) return VS_OK;
+    f.vwords = (f.gcap + 127) / 128;
+    if (vmode < 2 || f.rc || f.gcap % 32 != 0) return VS_OK;
+    *slot_eligible = true;
+    FastLaunch g = f;
+    g.vwords = f.gcap / 32;
+    g.vslot = 1;
+    bool holds = false;
+    VS_TRY(candidate_holds(ix, f, g, 1, 1, &holds));
+    if (holds || env_u32("VS_F_SLOTMAP_FORCE", 0)) f = g;
+    return VS_OK;
+}
+
+// table form, 16-bit entries; *gregion follows the form taken
+static int choose_tables16(vs_index* ix, FastLaunch& f, uint32_t vmode, bool slot_eligible, bool keyed, uint32_t* gregion) {
+    // ... or (VS_F_VIRGIN=3) 16-BIT entries: buckets of eight slots (one 16-byte load), the entry is the remainder of a bijective
+    // hash of the node id given its bucket (quotienting), a small overflow table of whole ids behind the buckets.  Half the bytes
+    // per slot: the tables of the scans in flight are the largest part of the kernel's hot private state (fast_scan, VG == 3).
+    // Needs a power-of-two number of buckets and ceil(log2 n) - log2(buckets) <= 16 remainder bits.
+    // Round 6 (profiles/r06/s20-s22): the rule used to be "only while it costs no scans per CU", against the 4-byte slot bitmap, which
+    // itself had to cost none against the bucket bitmap — and at search_list_size 100 (a visited ring of 3 KB per scan) it does:
+    // 19 resident scans per CU against 23.  So the reference's default GUCs, the label-filtered configuration and every other long
+    // list ran round 3's bucket-bitmap tables and none of the round-5 / round-6 kernel work (rocprofv3 names the instantiation:
+    // k_search_fast<3,0,false,6,false,*,1,0>).  Measured at 10M, 100 / 50: 100.8 ms per 262 144 scans (bucket bitmap, 23 per CU)
+    // against 90.4 (16-bit tables, 19 per CU) and 86.2 (16-bit tables with the heap top below, 22 per CU); label keys at 100 / 90:
+    // 119.1 / 115.5 / 110.6.  The 16-bit tables are now taken while they keep at least four fifths of the resident scans of whatever
+    // the rules above chose — two thirds for label-filtered scans (s24, 10M x 1536, 100 / 90: 110.2 ms at 15 scans per CU against 119.0
+    // at 22).  Not below that for unfiltered scans: the `mid` corpus at 100 / 592 (tables of 32 Ki slots, 15 against 21 per CU, the
+    // heap spill arrays carrying most of the traffic) runs 436.6 ms with them against 382.2 without (s24).
+    if (vmode != 3 || !f.vwords || !slot_eligible || f.lh != 0) return VS_OK;
+    FastLaunch g = f;
+    g.gcap = std::max<uint32_t>(next_pow2_u32(f.gcap), 1024);
+    if (!fast_tables16_geometry(ix, g)) return VS_OK;
+    g.glimit = (uint32_t)((uint64_t)g.gcap * gload_pct() / 100) - 64u;
+    char tail[48];
+    snprintf(tail, sizeof tail, "; gcap %u -> %u", f.gcap, g.gcap);
+    // (label-filtered scans mark ~50 ids per ~9 scored rows, AM/sbq/storage.rs:148-172: the table is most of what they touch)
+    bool holds = false;
+    VS_TRY(candidate_holds(ix, f, g, keyed ? 3 : 5, keyed ? 2 : 4, &holds, "4-byte tables", "16-bit tables", tail));
+    if (holds || env_u32("VS_F_SLOTMAP_FORCE", 0)) {
+        f = g;
+        *gregion = g.gregion;
+    }
+    return VS_OK;
+}
+
+static int choose_heap_top(vs_index* ix, FastLaunch& f, Caps& caps, bool phase) {
+    // LDS-bound launches: where the LDS per scan — not the register cap of the instantiation — limits the resident scans, a heap top
+    // of 255 entries instead of 511 (1 KB less) is taken when it buys at least a tenth more of them (s22: 90.4 -> 86.2 ms at 100 / 50,
+    // 115.5 -> 110.6 with label keys, 22 instead of 19 per CU; where the registers are the limit — search_list_size 3, 24 per CU —
+    // nothing changes: there a smaller heap top only costs).  An explicit VS_F_HL stands.
+    if (f.lh != 0 || f.vr || f.hl != 511 || f.hcap <= 511 || phase || opt_is_set("VS_F_HL")) return VS_OK;
+    FastLaunch h = f;
+    h.hl = 255;
+    h.gstride = round_up_u32(h.hcap - h.hl + 2, 2);
+    bool holds = false;
+    VS_TRY(candidate_holds(ix, f, h, 10, 11, &holds, "heap top 511", "255"));
+    if (holds) {
+        f = h;
+        caps.f_hl = h.hl;  // (the batch's later chunks and its finish see the smaller heap top: the rule runs once per batch)
+        caps.f_gstride = h.gstride;
+    }
+    return VS_OK;
+}
+
+static int choose_visited_ring(vs_index* ix, FastLaunch& f, uint32_t L, bool phase) {
+    // ... and likewise the visited ring: room for 1.4 instead of 2 times the list's expected length (1 KB less at search_list_size 100)
+    // where that buys at least a tenth more resident scans.  The scans that outgrow the smaller ring are finished by the second
+    // attempt below, a few milliseconds on the critical path — worth it for label-filtered scans (s21 / s22, 10M x 1536, 100 / 90: 98 of
+    // 262 144 scans, 3.5 ms, for a first attempt of 101.5 instead of 110.6 ms: 17 -> 19 scans per CU), a wash for unfiltered ones at
+    // 100 / 50 (83.5 + 1.8 against 86.2 ms; 22 -> 24 per CU is under the threshold).  An explicit VS_F_VCAP stands.
+    if (f.lh != 0 || f.vr || f.minw == 7 || phase) return VS_OK;
+    const uint32_t want_v = visited_want(L);
+    const uint32_t lean_v = round_up_u32(std::max<uint32_t>(want_v + 2 * want_v / 5, 64), 64);
+    if (opt_is_set("VS_F_VCAP") || lean_v >= f.vcap) return VS_OK;
+    FastLaunch v = f;
+    v.vcap = lean_v;
+    char wide_name[40], lean_name[24];
+    snprintf(wide_name, sizeof wide_name, "visited ring %u entries", f.vcap);
+    snprintf(lean_name, sizeof lean_name, "%u entries", v.vcap);
+    bool holds = false;
+    VS_TRY(candidate_holds(ix, f, v, 10, 11, &holds, wide_name, lean_name));
+    if (holds) f = v;
+    return VS_OK;
+}
+
+static void choose_ring_step7(FastLaunch& f, uint32_t L) {
+    // (VS_F_MINW=7 with the 16-bit tables: 28 scans per CU when a scan's LDS fits 5 632 B — the visited ring is then sized in steps
+    // of 16 entries instead of 64)
+    if (f.minw == 7 && f.vslot == 2 && !f.vr && !env_u32("VS_F_VCAP", 0)) f.vcap = round_up_u32(std::max<uint32_t>(2 * visited_want(L), 64), 16);
+}
+
+static int choose_persistent_grid(vs_index* ix, FastLaunch& f, uint32_t* fslots) {
+    // Persistent grid (VS_F_PERSIST, default on): as many single-wave workgroups as the device holds at once, each taking scan
+    // after scan from a counter and reusing ITS region of the heap spill array and of the dedup tables — the workspace is
+    // (resident scans) x (region) instead of nq x (region): 0.6 GB instead of 26 GB for 262 144 scans of the 50M index
+    if (!knob_u32("VS_F_PERSIST", ix->tune.persist, 1)) return VS_OK;
+    uint32_t res = 0;
+    VS_TRY(fast_resident_scans(ix, f, &res));
+    f.persist = std::max<uint32_t>(1, (uint32_t)((uint64_t)res * env_u32("VS_F_PERSIST_PCT", 100) / 100));
+    *fslots = std::min(f.persist, f.nq);
+    return VS_OK;
+}
+
+// What the first attempt of this chunk will be.  Enqueues nothing and touches no buffer; its only device-facing calls are the
+// occupancy queries of the rules.  `caps` is in-out (choose_heap_top).
+static int plan_fast_launch(vs_index* ix, const BatchPlan& bp, Caps& caps, bool keyed, bool masked, FastPlan* out) {
+    const bool phase = env_u32("VS_PHASE", 0) != 0;  // (diagnostics: its instantiation has none of the table forms and keeps the capacities)
+    FastPlan p{};
+    FastLaunch& f = p.f;
+    f.nq = bp.nq;
+    f.L = bp.L;
+    f.M = bp.M;
+    f.hl = caps.f_hl;
+    f.hcap = caps.f_hcap;
+    f.gstride = caps.f_gstride;
+    f.vr = caps.f_vr;
+    f.gcap = caps.f_gcap;
+    f.glimit = (uint32_t)((uint64_t)caps.f_gcap * gload_pct() / 100) - 64u;
+    f.lh = caps.f_lh;
+    f.minw = knob_u32("VS_F_MINW", (caps.f_lh == 0 && !caps.f_vr) ? ix->tune.minw : -1, caps.f_lh == 0 ? (caps.f_vr ? 4 : 6) : 1);
+    f.flags = env_u32("VS_F_FLAGS", 0);
+    f.sb = caps.f_sb;
+    f.vcap = caps.f_vcap;
+    f.qlabel_off = keyed ? fast_select<const uint32_t>() : nullptr;
+    f.visible = masked ? fast_select<const uint8_t>() : nullptr;
+    f.rc = caps.f_lh == 0 ? env_u32("VS_F_RC", 0) : 0;  // (measurement: LDS id cache in front of the dedup table in HBM)
+    if (f.rc) f.rc = next_pow2_u32(f.rc);
+    p.gregion = f.gcap;
+    p.fslots = fast_pool_slots(bp.nq, caps.f_pool_frac);
+    const uint32_t vmode = knob_u32("VS_F_VIRGIN", ix->tune.virgin, 3);
+    bool slot_eligible = false;
+    VS_TRY(choose_table_bitmap(ix, f, vmode, phase, &slot_eligible));
+    VS_TRY(choose_tables16(ix, f, vmode, slot_eligible, keyed, &p.gregion));
+    VS_TRY(choose_heap_top(ix, f, caps, phase));
+    VS_TRY(choose_visited_ring(ix, f, bp.L, phase));
+    choose_ring_step7(f, bp.L);
+    if (phase) f.phase = fast_select<uint64_t>();
+    VS_TRY(choose_persistent_grid(ix, f, &p.fslots));
+    *out = p;
+    return VS_OK;
+}
+
+// The second attempt of the scans that outgrew the first's capacities (a handful per launch at the tail of the distribution):
+// the same kernel with a four times larger dedup table, twice the heap and visited-list room, regions from a small
+// pool.  Scans finished above return at once; what still does not fit goes to the general kernel below.
+// Returns whether such a launch exists; its heap_g / ghash are the caller's to reserve and set.
+static bool second_attempt_of(const vs_index* ix, const FastLaunch& first, uint32_t nq, FastLaunch* out) {
+    const SearchWorkspace& w = ix->ws;
+    FastLaunch r = first;
+    r.vwords = 0;  // (its own, smaller table array: cleared by the few scans that run)
+    r.vslot = 0;
+    r.persist = 0;  // (one workgroup per scan: nearly all of them return at once; regions from the pool)
+    r.timeline = nullptr;
+    r.only_failed = 1;
+    r.fb_flag = (uint32_t*)w.fb_flag.p;
+    r.phase = nullptr;
+    r.gcap = (uint32_t)std::min<uint64_t>(4ull * first.gcap, 1u << 22);
+    r.glimit = 0;  // (75 % of the larger table)
+    r.hcap = (uint32_t)std::min<uint64_t>(2ull * first.hcap, 1u << 22);
+    r.gstride = round_up_u32(r.hcap - r.hl + 2, 2);
+    if (!r.vr) r.vcap = 2 * first.vcap;
+    r.sb = 0;
+    while ((1ull << r.sb) < (uint64_t)r.lh + r.gcap) r.sb++;
+    r.pool_slots = general_pool_slots(nq);
+    r.pool_counter = (uint32_t*)((char*)w.pool_ctr.p + 16);
+    *out = r;
+    const uint64_t nbits = (uint64_t)ix->d.dim_index * ix->d.bits;
+    return nbits < (1ull << (32 - r.sb)) && fast_lds_bytes(ix, r) <= 64 * 1024;
+}
+
+// reserves the regions the plan asks for, clears the counters and the fallback marks, and puts the workspace's pointers into p.f
+static int bind_fast_buffers(vs_index* ix, FastPlan& p, const int16_t* d_qlabels, const uint32_t* d_qlabel_off, const uint8_t* visible) {
+    vs_ctx* c = ix->ctx;
+    SearchWorkspace& w = ix->ws;
+    FastLaunch& f = p.f;
+    const size_t table_bytes = (size_t)p.fslots * p.gregion * 4;
+    // (persistent grid: the two randomly accessed arrays live in the index's slab, dedup tables first)
+    if (f.persist) {
+        const size_t heap_bytes = std::max<size_t>((size_t)p.fslots * f.gstride * 4, 16);
+        const uint32_t what = env_u32("VS_WS_SLAB_WHAT", 3);  // (measurement: 1 = only the dedup tables, 2 = only the heap spill arrays)
+        if (what & 1) VS_TRY(devbuf_reserve_hot(ix, w.ghash4, table_bytes, 0));
+        else VS_TRY(devbuf_reserve(c, w.ghash4, table_bytes));
+        if (what & 2) VS_TRY(devbuf_reserve_hot(ix, w.heap_g4, heap_bytes, 1));
+        else VS_TRY(devbuf_reserve(c, w.heap_g4, heap_bytes));
+    } else {
+        VS_TRY(devbuf_reserve(c, w.heap_g4, std::max<size_t>((size_t)f.nq * f.gstride * 4, 16)));
+        VS_TRY(devbuf_reserve(c, w.ghash4, table_bytes));
+    }
+    if (env_u32("VS_WS_DEBUG", 0))  // diagnostics: where the hot arrays live (scripts/diag_state.py --placement)
+        fprintf(stderr, "[VS_WS_DEBUG] ghash4 %p (%zu B%s) heap_g4 %p (%zu B%s) region bytes: table %zu heap %zu x %u regions; stream_ids %p qcodes %p\n", w.ghash4.p,
+                w.ghash4.bytes, w.ghash4.in_slab ? ", slab" : "", w.heap_g4.p, w.heap_g4.bytes, w.heap_g4.in_slab ? ", slab" : "",
+                (size_t)p.gregion * 4, (size_t)f.gstride * 4, p.fslots, w.stream_ids.p, w.qcodes.p);
+    VS_TRY(devbuf_reserve(c, w.pool_ctr, 64));
+    VS_HIP(hipMemsetAsync(w.pool_ctr.p, 0, 64, c->stream));
+    VS_TRY(devbuf_reserve(c, w.fb_flag, (size_t)f.nq * 4));
+    VS_HIP(hipMemsetAsync(w.fb_flag.p, 0, (size_t)f.nq * 4, c->stream));
+    f.qlabels = d_qlabels;
+    f.qlabel_off = d_qlabel_off;
+    f.visible = visible;
+    f.heap_g = (uint32_t*)w.heap_g4.p;
+    f.ghash = (uint32_t*)w.ghash4.p;
+    f.pool_counter = (uint32_t*)w.pool_ctr.p;
+    f.scan_counter = (uint32_t*)w.pool_ctr.p + 2;
+    f.pool_slots = p.fslots;
+    f.phase = nullptr;
+    f.qcodes = (const uint64_t*)w.qcodes.p;
+    f.out_ids = (uint32_t*)w.stream_ids.p;
+    f.out_ham = (uint32_t*)w.stream_ham.p;
+    f.out_cnt = (uint32_t*)w.stream_cnt.p;
+    f.stats = (uint32_t*)w.stats.p;
+    f.status = (uint32_t*)w.status.p;
+    return VS_OK;
+}
+
+// ---- diagnostics of the fast launch (each synchronises or costs a buffer: none runs unless its option is set) ----
+// VS_PHASE: the per-scan buffer of shader-clock sums (printed by collect_stats)
+static int bind_phase_buffer(vs_index* ix, FastLaunch& f) {
+    if (!env_u32("VS_PHASE", 0)) return VS_OK;
+    SearchWorkspace& w = ix->ws;
+    VS_TRY(devbuf_reserve(ix->ctx, w.phase, (size_t)f.nq * 64));
+    VS_HIP(hipMemsetAsync(w.phase.p, 0, (size_t)f.nq * 64, ix->ctx->stream));
+    f.phase = (uint64_t*)w.phase.p;
+    return VS_OK;
+}
+
+// VS_TIMELINE: start / end of every scan of this launch, dumped to a file
+static int bind_timeline_buffer(vs_index* ix, FastLaunch& f, std::string* path) {
+    const char* const tl_opt = vs_opt_get("VS_TIMELINE");
+    *path = tl_opt ? tl_opt : "";  // (the option's pointer lives until this thread's next lookup)
+    if (path->empty()) return VS_OK;
+    SearchWorkspace& w = ix->ws;
+    VS_TRY(devbuf_reserve(ix->ctx, w.timeline, (size_t)f.nq * 16));
+    VS_HIP(hipMemsetAsync(w.timeline.p, 0, (size_t)f.nq * 16, ix->ctx->stream));
+    f.timeline = (uint64_t*)w.timeline.p;
+    return VS_OK;
+}
+static int dump_timeline(vs_index* ix, uint32_t nq, const std::string& path) {
+    std::vector<uint64_t> tl((size_t)nq * 2);
+    VS_HIP(hipMemcpyAsync(tl.data(), ix->ws.timeline.p, tl.size() * 8, hipMemcpyDeviceToHost, ix->ctx->stream));
+    VS_HIP(hipStreamSynchronize(ix->ctx->stream));
+    if (FILE* fp = fopen(path.c_str(), "wb")) {
+        fwrite(tl.data(), 8, tl.size(), fp);
+        fclose(fp);
+    }
+    return VS_OK;
+}
+
+// VS_DEBUG_STATUS: which flags did the fast kernel leave behind?
+static int dump_fast_status(vs_index* ix, const FastLaunch& f, double pool_frac) {
+    vs_ctx* c = ix->ctx;
+    SearchWorkspace& w = ix->ws;
+    std::vector<uint32_t> stv(f.nq);
+    VS_HIP(hipMemcpyAsync(stv.data(), w.status.p, (size_t)f.nq * 4, hipMemcpyDeviceToHost, c->stream));
+    uint32_t ctr[2] = {0, 0};
+    VS_HIP(hipMemcpyAsync(ctr, w.pool_ctr.p, 4, hipMemcpyDeviceToHost, c->stream));
+    VS_HIP(hipStreamSynchronize(c->stream));
+    uint32_t hist[16] = {0};
+    for (uint32_t v : stv) hist[v & 15]++;
+    fprintf(stderr, "[VS_DEBUG_STATUS] fast kernel: lh=%u gcap=%u vr=%u minw=%u bitmap_words=%u (per %s); pool claims=%u of %u;",
+            f.lh, f.gcap, f.vr, f.minw, f.vwords, f.vslot == 2 ? "slot, 16-bit entries" : f.vslot ? "slot" : "bucket", ctr[0], fast_pool_slots(f.nq, pool_frac));
+    for (int i = 0; i < 16; ++i)
+        if (hist[i]) fprintf(stderr, " status[%d]=%u", i, hist[i]);
+    fprintf(stderr, "\n");
+    return VS_OK;
+}
+
+// k_search_fast over the chunk: the planned first attempt, then the second attempt of the scans that outgrew it
+static int run_fast_attempts(vs_index* ix, const BatchPlan& bp, Caps& caps, const int16_t* d_qlabels, const uint32_t* d_qlabel_off) {
+    vs_ctx* c = ix->ctx;
+    SearchWorkspace& w = ix->ws;
+    const uint8_t* const visible = (!bp.stream_only && bp.rescore > 0) ? ix->visible : nullptr;  // the heap is only fetched for the rescore window
+    ix->last_ins_limit = caps.f_lh ? caps.f_lh - caps.f_lh / 8 - 64 : 0xFFFFFFFFu;
+    FastPlan p;
+    VS_TRY(plan_fast_launch(ix, bp, caps, d_qlabel_off != nullptr, visible != nullptr, &p));
+    FastLaunch& f = p.f;
+    VS_TRY(bind_fast_buffers(ix, p, d_qlabels, d_qlabel_off, visible));
+    VS_TRY(bind_phase_buffer(ix, f));
+    std::string tl_path;
+    VS_TRY(bind_timeline_buffer(ix, f, &tl_path));
+    hipEvent_t ev = prof_begin(c);
+    VS_TRY(launch_search_fast(ix, f));
+    prof_end(c, PK_SEARCH, ev);
+    if (f.timeline) VS_TRY(dump_timeline(ix, bp.nq, tl_path));
+    ix->last_fast = FastSig{f.vwords, f.minw, f.gcap, f.lh, f.vr, 1u};
+    FastLaunch r;
+    if (env_u32("VS_F_RETRY", 1) && second_attempt_of(ix, f, bp.nq, &r)) {
+        VS_TRY(devbuf_reserve(c, w.heap_g4b, (size_t)r.pool_slots * r.gstride * 4));
+        VS_TRY(devbuf_reserve(c, w.ghash4b, (size_t)r.pool_slots * r.gcap * 4));
+        r.heap_g = (uint32_t*)w.heap_g4b.p;
+        r.ghash = (uint32_t*)w.ghash4b.p;
+        hipEvent_t ev2 = prof_begin(c);
+        VS_TRY(launch_search_fast(ix, r));
+        prof_end(c, PK_SEARCH_FB, ev2);
+    }
+    if (env_u32("VS_DEBUG_STATUS", 0)) VS_TRY(dump_fast_status(ix, f, caps.f_pool_frac));
+    return VS_OK;
+}
+
+// runs prepare -> search (-> rerank -> resort) for nq queries already on the device.  Outputs land in the workspace
+// (or the caller's device buffers).  Nothing here waits for the device: the scans that outgrew every pool are found and re-run by
+// finish_launch.
 static int run_search_chunk(vs_index* ix, const BatchPlan& bp, const float* d_raw_q, const int16_t* d_qlabels,
-                            const uint32_t* d_qlabel_off, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist,
-                            Caps& caps, bool check_now, vs_stats* st) {
+                            const uint32_t* d_qlabel_off, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, Caps& caps) {
     vs_ctx* c = ix->ctx;
     SearchWorkspace& w = ix->ws;
     const uint32_t nq = bp.nq, M = bp.M;
@@ -326,316 +666,43 @@ static int run_search_chunk(vs_index* ix, const BatchPlan& bp, const float* d_ra
         }
         prof_end(c, PK_PREPARE, ev);
     }
-    bool fast_done = false;
     ix->last_fast = FastSig{};
-    if (caps.f_on) {
-        uint32_t fslots = fast_pool_slots(nq, caps.f_pool_frac);
-        ix->last_ins_limit = caps.f_lh ? caps.f_lh - caps.f_lh / 8 - 64 : 0xFFFFFFFFu;
-        // Persistent grid (VS_F_PERSIST, default on): as many single-wave workgroups as the device holds at once, each taking scan
-        // after scan from a counter and reusing ITS region of the heap spill array and of the dedup tables — the workspace is
-        // (resident scans) x (region) instead of nq x (region): 0.6 GB instead of 26 GB for 262 144 scans of the 50M index
-        FastLaunch f;
-        f.nq = nq;
-        f.L = bp.L;
-        f.M = M;
-        f.hl = caps.f_hl;
-        f.hcap = caps.f_hcap;
-        f.gstride = caps.f_gstride;
-        f.vr = caps.f_vr;
-        f.gcap = caps.f_gcap;
-        f.glimit = (uint32_t)((uint64_t)caps.f_gcap * gload_pct() / 100) - 64u;
-        f.lh = caps.f_lh;
-        f.minw = knob_u32("VS_F_MINW", (caps.f_lh == 0 && !caps.f_vr) ? ix->tune.minw : -1, caps.f_lh == 0 ? (caps.f_vr ? 4 : 6) : 1);
-        f.flags = env_u32("VS_F_FLAGS", 0);
-        f.sb = caps.f_sb;
-        f.vcap = caps.f_vcap;
-        f.qlabels = d_qlabels;
-        f.qlabel_off = d_qlabel_off;
-        f.visible = (!bp.stream_only && bp.rescore > 0) ? ix->visible : nullptr;  // the heap is only fetched for the rescore window
-        f.rc = caps.f_lh == 0 ? env_u32("VS_F_RC", 0) : 0;  // (measurement: LDS id cache in front of the dedup table in HBM)
-        if (f.rc) f.rc = next_pow2_u32(f.rc);
-        // written-bucket bitmap (VS_F_VIRGIN=1, table-less regime): 128 slots of the table per LDS word; tables of more than
-        // 64 Ki slots keep the clear (the bitmap would cost occupancy)
-        // ... or (VS_F_VIRGIN=2) one bit per SLOT: linear probing at slot granularity with the occupancy known on chip, so most new
-        // ids are stored without a load of the table; 32 slots per LDS word — taken only while it costs no scans per CU (else the
-        // bucket bitmap runs)
-        // Default since round 4's third GPU session: the slot bitmap — 161.1 ms per 262 144 scans at 50M against 167.9 with the bucket
-        // bitmap and 171.2 with cleared tables, 125.8 / 129.7 / 130.1 at 10M (profiles/r04/s3_ab_slotmap_*.txt); 639 device fuzz cases.
-        // Default since round 5: the 16-bit tables below (VS_F_VIRGIN=3) — 139.7 ms per 262 144 scans at 50M against 153.5 with the 4-byte
-        // slot-bitmap tables, same session, same slab (profiles/r05/s10_ab_q16_50m.txt); 300 device fuzz runs, regimes green on hardware.
-        const uint32_t vmode = knob_u32("VS_F_VIRGIN", ix->tune.virgin, 3);
-        bool slot_eligible = false;  // one occupancy bit per slot is possible for this table (whether or not the 4-byte slot bitmap is taken)
-        if (caps.f_lh == 0 && !f.vr && vmode && !env_u32("VS_PHASE", 0) && f.gcap <= (1u << 16)) {
-            f.vwords = (f.gcap + 127) / 128;
-            if (vmode >= 2 && !f.rc && f.gcap % 32 == 0) {
-                slot_eligible = true;
-                FastLaunch g = f;
-                g.vwords = f.gcap / 32;
-                g.vslot = 1;
-                uint32_t res_b = 0, res_s = 0;
-                VS_TRY(fast_resident_scans(ix, f, &res_b));
-                VS_TRY(fast_resident_scans(ix, g, &res_s));
-                if (res_s >= res_b || env_u32("VS_F_SLOTMAP_FORCE", 0)) {
-                    f.vwords = g.vwords;
-                    f.vslot = 1;
-                }
-            }
-        }
-        // ... or (VS_F_VIRGIN=3) 16-BIT entries: buckets of eight slots (one 16-byte load), the entry is the remainder of a bijective
-        // hash of the node id given its bucket (quotienting), a small overflow table of whole ids behind the buckets.  Half the bytes
-        // per slot: the tables of the scans in flight are the largest part of the kernel's hot private state (fast_scan, VG == 3).
-        // Needs a power-of-two number of buckets and ceil(log2 n) - log2(buckets) <= 16 remainder bits.
-        // Round 6 (profiles/r06/s20-s22): the rule used to be "only while it costs no scans per CU", against the 4-byte slot bitmap, which
-        // itself had to cost none against the bucket bitmap — and at search_list_size 100 (a visited ring of 3 KB per scan) it does:
-        // 19 resident scans per CU against 23.  So the reference's default GUCs, the label-filtered configuration and every other long
-        // list ran round 3's bucket-bitmap tables and none of the round-5 / round-6 kernel work (rocprofv3 names the instantiation:
-        // k_search_fast<3,0,false,6,false,*,1,0>).  Measured at 10M, 100 / 50: 100.8 ms per 262 144 scans (bucket bitmap, 23 per CU)
-        // against 90.4 (16-bit tables, 19 per CU) and 86.2 (16-bit tables with the heap top below, 22 per CU); label keys at 100 / 90:
-        // 119.1 / 115.5 / 110.6.  The 16-bit tables are now taken while they keep at least four fifths of the resident scans of whatever
-        // the rules above chose — two thirds for label-filtered scans (s24, 10M x 1536, 100 / 90: 110.2 ms at 15 scans per CU against 119.0
-        // at 22).  Not below that for unfiltered scans: the `mid` corpus at 100 / 592 (tables of 32 Ki slots, 15 against 21 per CU, the
-        // heap spill arrays carrying most of the traffic) runs 436.6 ms with them against 382.2 without (s24).
-        uint32_t gregion = f.gcap;
-        if (vmode == 3 && f.vwords && slot_eligible && caps.f_lh == 0) {
-            uint32_t qd = 1;
-            while ((1ull << qd) < (uint64_t)std::max<uint32_t>(ix->d.n, 2)) qd++;
-            const uint32_t gcap16 = std::max<uint32_t>(next_pow2_u32(f.gcap), 1024);
-            uint32_t lb = 0;
-            while ((1u << lb) < (gcap16 >> 3)) lb++;
-            if (qd < lb + 3) qd = lb + 3;  // (a small index: more hash bits than id bits — the bijection works on any width)
-            const uint32_t qk = qd - lb;
-            FastLaunch g = f;
-            g.gcap = gcap16;
-            g.ocap = std::max<uint32_t>(round_up_u32(gcap16 / 16, 32), 256);
-            g.vwords = (g.gcap + g.ocap) / 32;
-            g.vslot = 2;
-            g.sb = 0;
-            while ((1ull << g.sb) < (uint64_t)g.gcap + g.ocap) g.sb++;
-            const uint64_t nbits = (uint64_t)ix->d.dim_index * ix->d.bits;
-            uint32_t res_s = 0, res_q = 0;
-            if (qk <= 16 && qd <= 32 && nbits < (1ull << (32 - g.sb))) {
-                g.qd = qd;
-                g.qk = qk;
-                g.gregion = (g.gcap >> 1) + g.ocap;
-                g.glimit = (uint32_t)((uint64_t)g.gcap * gload_pct() / 100) - 64u;
-                VS_TRY(fast_resident_scans(ix, f, &res_s));
-                VS_TRY(fast_resident_scans(ix, g, &res_q));
-                if (env_u32("VS_WS_DEBUG", 0))
-                    fprintf(stderr, "[VS_WS_DEBUG] resident scans: 4-byte tables %u, 16-bit tables %u; gcap %u -> %u\n", res_s, res_q, f.gcap, g.gcap);
-                // (label-filtered scans mark ~50 ids per ~9 scored rows, AM/sbq/storage.rs:148-172: the table is most of what they touch)
-                const bool keyed = f.qlabel_off != nullptr;
-                if ((keyed ? 3ull * res_q >= 2ull * res_s : 5ull * res_q >= 4ull * res_s) || env_u32("VS_F_SLOTMAP_FORCE", 0)) {
-                    f = g;
-                    gregion = g.gregion;
-                }
-            }
-        }
-        // LDS-bound launches: where the LDS per scan — not the register cap of the instantiation — limits the resident scans, a heap top
-        // of 255 entries instead of 511 (1 KB less) is taken when it buys at least a tenth more of them (s22: 90.4 -> 86.2 ms at 100 / 50,
-        // 115.5 -> 110.6 with label keys, 22 instead of 19 per CU; where the registers are the limit — search_list_size 3, 24 per CU —
-        // nothing changes: there a smaller heap top only costs).  An explicit VS_F_HL stands.
-        if (caps.f_lh == 0 && !f.vr && f.hl == 511 && f.hcap > 511 && !env_u32("VS_PHASE", 0)) {
-            const char* const hl_opt = vs_opt_get("VS_F_HL");
-            if (!(hl_opt && *hl_opt)) {
-                FastLaunch h = f;
-                h.hl = 255;
-                h.gstride = round_up_u32(h.hcap - h.hl + 2, 2);
-                uint32_t res_511 = 0, res_255 = 0;
-                VS_TRY(fast_resident_scans(ix, f, &res_511));
-                VS_TRY(fast_resident_scans(ix, h, &res_255));
-                if (env_u32("VS_WS_DEBUG", 0)) fprintf(stderr, "[VS_WS_DEBUG] resident scans: heap top 511 %u, 255 %u\n", res_511, res_255);
-                if (10ull * res_255 >= 11ull * res_511) {
-                    f = h;
-                    caps.f_hl = h.hl;
-                    caps.f_gstride = h.gstride;
-                }
-            }
-        }
-        // ... and likewise the visited ring: room for 1.4 instead of 2 times the list's expected length (1 KB less at search_list_size 100)
-        // where that buys at least a tenth more resident scans.  The scans that outgrow the smaller ring are finished by the second
-        // attempt below, a few milliseconds on the critical path — worth it for label-filtered scans (s21 / s22, 10M x 1536, 100 / 90: 98 of
-        // 262 144 scans, 3.5 ms, for a first attempt of 101.5 instead of 110.6 ms: 17 -> 19 scans per CU), a wash for unfiltered ones at
-        // 100 / 50 (83.5 + 1.8 against 86.2 ms; 22 -> 24 per CU is under the threshold).  An explicit VS_F_VCAP stands.
-        if (caps.f_lh == 0 && !f.vr && f.minw != 7 && !env_u32("VS_PHASE", 0)) {
-            const char* const vc_opt = vs_opt_get("VS_F_VCAP");
-            const uint32_t want_v = (uint32_t)std::min<uint64_t>((uint64_t)bp.L + bp.L / 2 + 32, 1u << 20);
-            const uint32_t lean_v = round_up_u32(std::max<uint32_t>(want_v + 2 * want_v / 5, 64), 64);
-            if (!(vc_opt && *vc_opt) && lean_v < f.vcap) {
-                FastLaunch v = f;
-                v.vcap = lean_v;
-                uint32_t res_wide = 0, res_lean = 0;
-                VS_TRY(fast_resident_scans(ix, f, &res_wide));
-                VS_TRY(fast_resident_scans(ix, v, &res_lean));
-                if (env_u32("VS_WS_DEBUG", 0))
-                    fprintf(stderr, "[VS_WS_DEBUG] resident scans: visited ring %u entries %u, %u entries %u\n", f.vcap, res_wide, v.vcap, res_lean);
-                if (10ull * res_lean >= 11ull * res_wide) f = v;
-            }
-        }
-        // (VS_F_MINW=7 with the 16-bit tables: 28 scans per CU when a scan's LDS fits 5 632 B — the visited ring is then sized in steps
-        // of 16 entries instead of 64)
-        if (f.minw == 7 && f.vslot == 2 && !f.vr && !env_u32("VS_F_VCAP", 0)) {
-            const uint32_t want_v = (uint32_t)std::min<uint64_t>((uint64_t)bp.L + bp.L / 2 + 32, 1u << 20);
-            f.vcap = round_up_u32(std::max<uint32_t>(2 * want_v, 64), 16);
-        }
-        if (env_u32("VS_PHASE", 0)) f.phase = (uint64_t*)16;  // (selects the instantiation; the buffer is set below)
-        if (knob_u32("VS_F_PERSIST", ix->tune.persist, 1)) {
-            uint32_t res = 0;
-            VS_TRY(fast_resident_scans(ix, f, &res));
-            f.persist = std::max<uint32_t>(1, (uint32_t)((uint64_t)res * env_u32("VS_F_PERSIST_PCT", 100) / 100));
-            fslots = std::min(f.persist, nq);
-        }
-        // (persistent grid: the two randomly accessed arrays live in the index's slab, dedup tables first)
-        if (f.persist) {
-            const uint32_t what = env_u32("VS_WS_SLAB_WHAT", 3);  // (measurement: 1 = only the dedup tables, 2 = only the heap spill arrays)
-            if (what & 1) VS_TRY(devbuf_reserve_hot(ix, w.ghash4, (size_t)fslots * gregion * 4, 0));
-            else VS_TRY(devbuf_reserve(c, w.ghash4, (size_t)fslots * gregion * 4));
-            if (what & 2) VS_TRY(devbuf_reserve_hot(ix, w.heap_g4, std::max<size_t>((size_t)fslots * caps.f_gstride * 4, 16), 1));
-            else VS_TRY(devbuf_reserve(c, w.heap_g4, std::max<size_t>((size_t)fslots * caps.f_gstride * 4, 16)));
-        } else {
-            VS_TRY(devbuf_reserve(c, w.heap_g4, std::max<size_t>((size_t)nq * caps.f_gstride * 4, 16)));
-            VS_TRY(devbuf_reserve(c, w.ghash4, (size_t)fslots * gregion * 4));
-        }
-        if (env_u32("VS_WS_DEBUG", 0))  // diagnostics: where the hot arrays live (scripts/diag_state.py --placement)
-            fprintf(stderr, "[VS_WS_DEBUG] ghash4 %p (%zu B%s) heap_g4 %p (%zu B%s) region bytes: table %zu heap %zu x %u regions; stream_ids %p qcodes %p\n", w.ghash4.p,
-                    w.ghash4.bytes, w.ghash4.in_slab ? ", slab" : "", w.heap_g4.p, w.heap_g4.bytes, w.heap_g4.in_slab ? ", slab" : "",
-                    (size_t)gregion * 4, (size_t)caps.f_gstride * 4, fslots, w.stream_ids.p, w.qcodes.p);
-        VS_TRY(devbuf_reserve(c, w.pool_ctr, 64));
-        VS_HIP(hipMemsetAsync(w.pool_ctr.p, 0, 64, c->stream));
-        VS_TRY(devbuf_reserve(c, w.fb_flag, (size_t)nq * 4));
-        VS_HIP(hipMemsetAsync(w.fb_flag.p, 0, (size_t)nq * 4, c->stream));
-        f.heap_g = (uint32_t*)w.heap_g4.p;
-        f.ghash = (uint32_t*)w.ghash4.p;
-        f.pool_counter = (uint32_t*)w.pool_ctr.p;
-        f.scan_counter = (uint32_t*)w.pool_ctr.p + 2;
-        f.pool_slots = fslots;
-        f.phase = nullptr;
-        f.qcodes = (const uint64_t*)w.qcodes.p;
-        f.out_ids = (uint32_t*)w.stream_ids.p;
-        f.out_ham = (uint32_t*)w.stream_ham.p;
-        f.out_cnt = (uint32_t*)w.stream_cnt.p;
-        f.stats = (uint32_t*)w.stats.p;
-        f.status = (uint32_t*)w.status.p;
-        if (env_u32("VS_PHASE", 0)) {
-            VS_TRY(devbuf_reserve(c, w.phase, (size_t)nq * 64));
-            VS_HIP(hipMemsetAsync(w.phase.p, 0, (size_t)nq * 64, c->stream));
-            f.phase = (uint64_t*)w.phase.p;
-        }
-        const char* const tl_opt = vs_opt_get("VS_TIMELINE");  // diagnostics: start / end of every scan of this launch, dumped to a file
-        const std::string tl_s = tl_opt ? tl_opt : "";  // (the option's pointer lives until this thread's next lookup)
-        const char* const tl_path = tl_s.c_str();
-        if (*tl_path) {
-            VS_TRY(devbuf_reserve(c, w.timeline, (size_t)nq * 16));
-            VS_HIP(hipMemsetAsync(w.timeline.p, 0, (size_t)nq * 16, c->stream));
-            f.timeline = (uint64_t*)w.timeline.p;
-        }
-        hipEvent_t ev = prof_begin(c);
-        VS_TRY(launch_search_fast(ix, f));
-        prof_end(c, PK_SEARCH, ev);
-        fast_done = true;
-        if (f.timeline) {
-            std::vector<uint64_t> tl((size_t)nq * 2);
-            VS_HIP(hipMemcpyAsync(tl.data(), w.timeline.p, tl.size() * 8, hipMemcpyDeviceToHost, c->stream));
-            VS_HIP(hipStreamSynchronize(c->stream));
-            if (FILE* fp = fopen(tl_path, "wb")) {
-                fwrite(tl.data(), 8, tl.size(), fp);
-                fclose(fp);
-            }
-        }
-        ix->last_fast = FastSig{f.vwords, f.minw, f.gcap, f.lh, f.vr, 1u};
-        // second attempt of the scans that outgrew these capacities (a handful per launch at the tail of the distribution):
-        // the same kernel with a four times larger dedup table, twice the heap and visited-list room, regions from a small
-        // pool.  Scans finished above return at once; what still does not fit goes to the general kernel below.
-        if (env_u32("VS_F_RETRY", 1)) {
-            FastLaunch r = f;
-            r.vwords = 0;  // (its own, smaller table array: cleared by the few scans that run)
-            r.vslot = 0;
-            r.persist = 0;  // (one workgroup per scan: nearly all of them return at once; regions from the pool)
-            r.timeline = nullptr;
-            r.only_failed = 1;
-            r.fb_flag = (uint32_t*)w.fb_flag.p;
-            r.phase = nullptr;
-            r.gcap = (uint32_t)std::min<uint64_t>(4ull * f.gcap, 1u << 22);
-            r.glimit = 0;  // (75 % of the larger table)
-            r.hcap = (uint32_t)std::min<uint64_t>(2ull * f.hcap, 1u << 22);
-            r.gstride = round_up_u32(r.hcap - r.hl + 2, 2);
-            if (!r.vr) r.vcap = 2 * f.vcap;
-            r.sb = 0;
-            while ((1ull << r.sb) < (uint64_t)r.lh + r.gcap) r.sb++;
-            r.pool_slots = general_pool_slots(nq);
-            r.pool_counter = (uint32_t*)((char*)w.pool_ctr.p + 16);
-            const uint64_t nbits = (uint64_t)ix->d.dim_index * ix->d.bits;
-            if (nbits < (1ull << (32 - r.sb)) && fast_lds_bytes(ix, r) <= 64 * 1024) {
-                VS_TRY(devbuf_reserve(c, w.heap_g4b, (size_t)r.pool_slots * r.gstride * 4));
-                VS_TRY(devbuf_reserve(c, w.ghash4b, (size_t)r.pool_slots * r.gcap * 4));
-                r.heap_g = (uint32_t*)w.heap_g4b.p;
-                r.ghash = (uint32_t*)w.ghash4b.p;
-                hipEvent_t ev2 = prof_begin(c);
-                VS_TRY(launch_search_fast(ix, r));
-                prof_end(c, PK_SEARCH_FB, ev2);
-            }
-        }
-        if (env_u32("VS_DEBUG_STATUS", 0)) {  // diagnostics: which flags did the fast kernel leave behind?
-            std::vector<uint32_t> stv(nq);
-            VS_HIP(hipMemcpyAsync(stv.data(), w.status.p, (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
-            uint32_t ctr[2] = {0, 0};
-            VS_HIP(hipMemcpyAsync(ctr, w.pool_ctr.p, 4, hipMemcpyDeviceToHost, c->stream));
-            VS_HIP(hipStreamSynchronize(c->stream));
-            uint32_t hist[16] = {0};
-            for (uint32_t v : stv) hist[v & 15]++;
-            fprintf(stderr, "[VS_DEBUG_STATUS] fast kernel: lh=%u gcap=%u vr=%u minw=%u bitmap_words=%u (per %s); pool claims=%u of %u;",
-                    f.lh, f.gcap, f.vr, f.minw, f.vwords, f.vslot == 2 ? "slot, 16-bit entries" : f.vslot ? "slot" : "bucket", ctr[0], fast_pool_slots(nq, caps.f_pool_frac));
-            for (int i = 0; i < 16; ++i)
-                if (hist[i]) fprintf(stderr, " status[%d]=%u", i, hist[i]);
-            fprintf(stderr, "\n");
-        }
-    }
+    const bool fast_done = caps.f_on;
+    if (fast_done) VS_TRY(run_fast_attempts(ix, bp, caps, d_qlabels, d_qlabel_off));
     w.fb_valid = fast_done;
-    for (int attempt = 0;; ++attempt) {
-        const size_t hg = caps.hcap > caps.hl ? caps.hcap - caps.hl : 0;
+    {
         // after the fast kernel only a few scans are left: they claim their regions from a small pool
         const uint32_t gslots = fast_done ? general_pool_slots(nq) : nq;
-        VS_TRY(devbuf_reserve(c, w.hash, (size_t)gslots * caps.hashcap * 4));
-        VS_TRY(devbuf_reserve(c, w.heap_g, std::max<size_t>((size_t)gslots * hg * 8, 16)));
-        VS_TRY(devbuf_reserve(c, w.pool_ctr, 64));
+        VS_TRY(reserve_general_regions(ix, caps, gslots));
         if (fast_done) VS_HIP(hipMemsetAsync((char*)w.pool_ctr.p + 32, 0, 4, c->stream));
-        SearchLaunch s;
-        s.nq = nq;
-        s.L = bp.L;
-        s.M = M;
-        s.hl = caps.hl;
-        s.hcap = caps.hcap;
-        s.vcap = caps.vcap;
-        s.lh = caps.lh;
-        s.hashcap = caps.hashcap;
-        s.g0 = caps.g0;
-        s.qcodes = (const uint64_t*)w.qcodes.p;
-        s.qlabels = d_qlabels;
-        s.qlabel_off = d_qlabel_off;
-        s.heap_g = (uint64_t*)w.heap_g.p;
-        s.hash = (uint32_t*)w.hash.p;
-        s.out_ids = (uint32_t*)w.stream_ids.p;
-        s.out_ham = (uint32_t*)w.stream_ham.p;
-        s.out_cnt = (uint32_t*)w.stream_cnt.p;
-        s.stats = (uint32_t*)w.stats.p;
-        s.status = (uint32_t*)w.status.p;
-        // after the fast kernel (or a failed attempt) only the scans whose status is non-zero are (re)run
-        s.only_failed = (fast_done || attempt > 0) ? 1u : 0u;
+        SearchLaunch s = general_launch(ix, bp, caps, d_qlabels, d_qlabel_off);
+        // after the fast kernel only the scans whose status is non-zero are (re)run
+        s.only_failed = fast_done ? 1u : 0u;
         s.fb_flag = fast_done ? (uint32_t*)w.fb_flag.p : nullptr;
         s.pool_counter = fast_done ? (uint32_t*)((char*)w.pool_ctr.p + 32) : nullptr;
         s.pool_slots = gslots;
-        s.visible = (!bp.stream_only && bp.rescore > 0) ? ix->visible : nullptr;
-        {
-            hipEvent_t ev = prof_begin(c);
-            VS_TRY(launch_search(ix, s));
-            prof_end(c, fast_done ? PK_SEARCH_FB : PK_SEARCH, ev);
-        }
-        break;
+        hipEvent_t ev = prof_begin(c);
+        VS_TRY(launch_search(ix, s));
+        prof_end(c, fast_done ? PK_SEARCH_FB : PK_SEARCH, ev);
     }
-    if (check_now) VS_TRY(retry_failed_scans(ix, bp, d_qlabels, d_qlabel_off, caps, st));
     VS_TRY(run_post_search(ix, bp, d_out_ids, d_out_tids, d_out_dist));
     // (unconditional, also for callers without stats and after a synchronous retry: finish_launch decides from RED_STATUS whether any
     // scan still has to be re-run, and that word only exists once this has run — 0.09 ms per 262 144 scans)
     return enqueue_reduce(ix, bp);
+}
+
+// what this batch needed: sizes the next launch with the same (L, M).  sum / max: ids inserted by the n_fast scans the first attempt
+// finished; n_over: the scans (of nq) that outgrew the LDS table or took a second attempt
+static void update_scan_obs(vs_index* ix, double sum, double max, uint32_t n_fast, uint32_t n_over, uint32_t nq, uint32_t L, uint32_t M) {
+    ScanObs& o = ix->obs;
+    const bool same = o.valid && o.L == L && o.M == M;
+    const double a = same ? 0.5 : 1.0;  // exponential average over batches
+    o.ins_mean = (1 - a) * o.ins_mean + a * (sum / n_fast);
+    o.ins_max = same ? std::max(o.ins_max, max) : max;
+    o.ov_frac = (1 - a) * (same ? o.ov_frac : 0.0) + a * ((double)n_over / nq);
+    o.L = L;
+    o.M = M;
+    o.valid = true;
 }
 
 // the counters of a finished launch from the sums of enqueue_reduce (the stream has been synchronised since)
@@ -643,18 +710,8 @@ static int collect_stats_reduced(vs_index* ix, uint32_t nq, uint32_t M, uint32_t
     if (!st) return VS_OK;
     const SearchWorkspace& w = ix->ws;
     const uint64_t* r = w.red_host;
-    if (w.fb_valid && ix->last_ins_limit && r[RED_INS_FAST]) {  // what this batch needed: sizes the next launch with the same (L, M)
-        const double sum = (double)r[RED_INS_SUM], mx = (double)r[RED_INS_MAX];
-        ScanObs& o = ix->obs;
-        const bool same = o.valid && o.L == obs_L && o.M == M;
-        const double a = same ? 0.5 : 1.0;  // exponential average over batches
-        o.ins_mean = (1 - a) * o.ins_mean + a * (sum / (uint32_t)r[RED_INS_FAST]);
-        o.ins_max = same ? std::max(o.ins_max, mx) : mx;
-        o.ov_frac = (1 - a) * (same ? o.ov_frac : 0.0) + a * ((double)(uint32_t)r[RED_INS_OV] / nq);
-        o.L = obs_L;
-        o.M = M;
-        o.valid = true;
-    }
+    if (w.fb_valid && ix->last_ins_limit && r[RED_INS_FAST])
+        update_scan_obs(ix, (double)r[RED_INS_SUM], (double)r[RED_INS_MAX], (uint32_t)r[RED_INS_FAST], (uint32_t)r[RED_INS_OV], nq, obs_L, M);
     st->queries += nq;
     st->visited_nodes += r[RED_VISITS];
     st->candidate_nodes += r[RED_CAND];
@@ -672,6 +729,24 @@ static int collect_stats_reduced(vs_index* ix, uint32_t nq, uint32_t M, uint32_t
     return VS_OK;
 }
 
+// VS_PHASE: where the scans of the last fast launch spent their shader clocks (hs: the per-scan work counters, on the host)
+static int dump_phase_clocks(vs_index* ix, uint32_t nq, const std::vector<uint32_t>& hs) {
+    std::vector<uint64_t> ph((size_t)nq * 8);
+    VS_HIP(hipMemcpy(ph.data(), ix->ws.phase.p, ph.size() * 8, hipMemcpyDeviceToHost));
+    double sum[8] = {0};
+    uint64_t visits = 0;
+    for (uint32_t q = 0; q < nq; ++q) {
+        for (int k = 0; k < 8; ++k) sum[k] += (double)ph[(size_t)q * 8 + k];
+        visits += hs[(size_t)q * ST_N + ST_VISITS];
+    }
+    const char* names[8] = {"pop", "row_wait", "visited", "dedup", "gather", "push", "other", "-"};
+    fprintf(stderr, "[VS_PHASE] shader clocks per visit:");
+    for (int k = 0; k < 7; ++k) fprintf(stderr, " %s=%.0f", names[k], sum[k] / (double)std::max<uint64_t>(visits, 1));
+    fprintf(stderr, "\n");
+    return VS_OK;
+}
+
+// the same counters from the per-scan arrays themselves (VS_PHASE: diagnostics)
 static int collect_stats(vs_index* ix, uint32_t nq, uint32_t M, uint32_t rescore, bool stream_only, vs_stats* st,
                          uint32_t obs_L = 0) {
     if (!st) return VS_OK;
@@ -681,21 +756,8 @@ static int collect_stats(vs_index* ix, uint32_t nq, uint32_t M, uint32_t rescore
     if (w.fb_valid) VS_HIP(hipMemcpyAsync(fb.data(), w.fb_flag.p, fb.size() * 4, hipMemcpyDeviceToHost, ix->ctx->stream));
     VS_HIP(hipMemcpyAsync(cnt.data(), w.stream_cnt.p, cnt.size() * 4, hipMemcpyDeviceToHost, ix->ctx->stream));
     VS_HIP(hipStreamSynchronize(ix->ctx->stream));
-    if (env_u32("VS_PHASE", 0) && w.phase.p && w.fb_valid) {
-        std::vector<uint64_t> ph((size_t)nq * 8);
-        VS_HIP(hipMemcpy(ph.data(), w.phase.p, ph.size() * 8, hipMemcpyDeviceToHost));
-        double sum[8] = {0};
-        uint64_t visits = 0;
-        for (uint32_t q = 0; q < nq; ++q) {
-            for (int k = 0; k < 8; ++k) sum[k] += (double)ph[(size_t)q * 8 + k];
-            visits += hs[(size_t)q * ST_N + ST_VISITS];
-        }
-        const char* names[8] = {"pop", "row_wait", "visited", "dedup", "gather", "push", "other", "-"};
-        fprintf(stderr, "[VS_PHASE] shader clocks per visit:");
-        for (int k = 0; k < 7; ++k) fprintf(stderr, " %s=%.0f", names[k], sum[k] / (double)std::max<uint64_t>(visits, 1));
-        fprintf(stderr, "\n");
-    }
-    if (w.fb_valid && ix->last_ins_limit) {  // what this batch needed: sizes the next launch with the same (L, M)
+    if (env_u32("VS_PHASE", 0) && w.phase.p && w.fb_valid) VS_TRY(dump_phase_clocks(ix, nq, hs));
+    if (w.fb_valid && ix->last_ins_limit) {
         double sum = 0, mx = 0;
         uint32_t cnt_fast = 0, ov = 0;
         for (uint32_t q = 0; q < nq; ++q) {
@@ -710,17 +772,7 @@ static int collect_stats(vs_index* ix, uint32_t nq, uint32_t M, uint32_t rescore
             cnt_fast++;
             ov += v > ix->last_ins_limit;
         }
-        if (cnt_fast) {
-            ScanObs& o = ix->obs;
-            const bool same = o.valid && o.L == obs_L && o.M == M;
-            const double a = same ? 0.5 : 1.0;  // exponential average over batches
-            o.ins_mean = (1 - a) * o.ins_mean + a * (sum / cnt_fast);
-            o.ins_max = same ? std::max(o.ins_max, mx) : mx;
-            o.ov_frac = (1 - a) * (same ? o.ov_frac : 0.0) + a * ((double)ov / nq);
-            o.L = obs_L;
-            o.M = M;
-            o.valid = true;
-        }
+        if (cnt_fast) update_scan_obs(ix, sum, mx, cnt_fast, ov, nq, obs_L, M);
     }
     for (uint32_t q = 0; q < nq; ++q) {
         st->queries++;
@@ -886,7 +938,7 @@ static int search_host(vs_index* ix, const float* queries, const int16_t* qlabel
         bp = BatchPlan{cq, L, rescore, k, M, stream_only};
         // label CSR offsets are absolute into d_labels_all, so a chunk just offsets the off pointer
         return run_search_chunk(ix, bp, (const float*)rawq[ci & 1]->p, d_labels_all, d_off_all ? d_off_all + q0 : nullptr,
-                                (uint32_t*)oids[ci & 1]->p, (uint64_t*)otids[ci & 1]->p, (float*)odist[ci & 1]->p, caps, false, stats);
+                                (uint32_t*)oids[ci & 1]->p, (uint64_t*)otids[ci & 1]->p, (float*)odist[ci & 1]->p, caps);
     };
     // the scans of a launch that outgrew every pool are re-run (synchronously, growing capacities) and the window is redone
     auto finish = [&](uint32_t ci, const BatchPlan& bp) -> int {
@@ -973,19 +1025,9 @@ int vs_search_batch_dev_impl(vs_index* ix, const float* d_queries, const int16_t
     Caps caps = initial_caps(ix, L, M);
     VS_REQUIRE(chunk_queries(ix, caps, M, nq) == nq, "vs_search_batch_dev: batch of %u queries exceeds the workspace budget", nq);
     BatchPlan bp{nq, L, rescore, k, M, false};
-    VS_TRY(run_search_chunk(ix, bp, d_queries, d_qlabels, d_qlabel_off, d_out_ids, d_out_tids, d_out_dist, caps, false,
-                            nullptr));
+    VS_TRY(run_search_chunk(ix, bp, d_queries, d_qlabels, d_qlabel_off, d_out_ids, d_out_tids, d_out_dist, caps));
     w.pending = true;
-    w.pend_nq = nq;
-    w.pend_m = M;
-    w.pend_L = L;
-    {
-        const PendingBatch pbv{bp, caps, d_qlabels, d_qlabel_off, d_out_ids, d_out_tids, d_out_dist};
-        free(w.pend_blob);  // trivially copyable record
-        w.pend_blob = malloc(sizeof(PendingBatch));
-        VS_REQUIRE(w.pend_blob, "out of host memory");
-        memcpy(w.pend_blob, &pbv, sizeof(pbv));
-    }
+    w.pend = PendingBatch{bp, caps, d_qlabels, d_qlabel_off, d_out_ids, d_out_tids, d_out_dist};
     ix->last_stats = vs_stats{};
     return VS_OK;
 }
@@ -1004,9 +1046,7 @@ int vs_search_batch_dev_finish_impl(vs_index* ix, vs_stats* stats) {
         return VS_ERR_STATE;
     }
     w.pending = false;
-    VS_REQUIRE(w.pend_blob, "vs_search_batch_dev_finish: no batch descriptor");
-    PendingBatch pb;
-    memcpy(&pb, w.pend_blob, sizeof(pb));
+    PendingBatch pb = w.pend;  // (a copy: a synchronous retry grows its capacities)
     vs_stats st{};
     // (scans that outgrew even the fallback pools of the asynchronous launch are re-run there, and the window redone)
     VS_TRY(finish_launch(ix, pb.bp, pb.d_qlabels, pb.d_qlabel_off, pb.caps, pb.d_out_ids, pb.d_out_tids, pb.d_out_dist, &st));

@@ -118,6 +118,31 @@ struct WsSlab {
     bool external = false;  // the caller's memory (vs_index_set_slab): used whatever VS_WS_SLAB_MB / the size rule say
 };
 
+// ---- a batch of scans (vs_batch.hip) ----------------------------------------------------------------------------
+// capacities of a batch's launches
+struct Caps {
+    uint32_t hl, hcap, vcap, lh, hashcap, g0;  // general kernel (vs_search.hip)
+    // fast kernel (vs_search_fast.hip); f_lh == 0: no LDS dedup table (every id in the global table)
+    bool f_on;
+    uint32_t f_hl, f_hcap, f_gstride, f_lh, f_gcap, f_sb, f_vr, f_vcap;
+    double f_pool_frac;  // share of the scans expected to need a global dedup-overflow table
+};
+// one launch (a chunk of the batch): nq scans of search list L that each leave a stream of M rows
+struct BatchPlan {
+    uint32_t nq, L, rescore, k, M;
+    bool stream_only;  // vs_stream_batch: no rerank
+};
+// plan + capacities + the caller's device pointers of the batch in flight between vs_search_batch_dev and its finish
+struct PendingBatch {
+    BatchPlan bp;
+    Caps caps;
+    const int16_t* d_qlabels;
+    const uint32_t* d_qlabel_off;
+    uint32_t* d_out_ids;
+    uint64_t* d_out_tids;
+    float* d_out_dist;
+};
+
 struct SearchWorkspace {
     DevBuf q_full, qcodes, qlabels, qlabel_off, hash, heap_g, heap_g4, ghash4, heap_g4b, ghash4b, pool_ctr, fb_flag, phase, timeline, stream_ids, stream_ham, stream_cnt, stats, status,
         rr_dist, out_ids, out_tids, out_dist, resort_heap, raw_q, misc, q_index,
@@ -126,13 +151,10 @@ struct SearchWorkspace {
         order_work, order_perm;                   // VS_RERANK_ORDER: keys + counting-sort tables, and the batch's rerank order
     uint32_t order_nq = 0;         // scans of the last batch's rerank order in order_perm (0: it took the scans' own order)
     uint64_t* red_host = nullptr;  // pinned; the sums land here (this handle's own: two handles of one context may each have a batch in flight)
-    // pending async call (vs_search_batch_dev)
     bool fb_valid = false;  // fb_flag holds the fallback marks of the last chunk
+    // pending async call (vs_search_batch_dev)
     bool pending = false;
-    uint32_t pend_nq = 0;
-    uint32_t pend_m = 0;
-    uint32_t pend_L = 0;
-    void* pend_blob = nullptr;  // PendingBatch of vs_api.hip (plan + capacities + output pointers of the batch in flight)
+    PendingBatch pend{};
 };
 
 // what the last batches needed (per search_list_size / stream length): sizes the LDS dedup table of the next launch
@@ -338,6 +360,26 @@ enum {
     FAST_FULL_VARIANT = 8,     // run the instantiation that handles label keys and a visibility mask even when the batch has neither
 };
 size_t fast_lds_bytes(const vs_index* idx, const FastLaunch& s);
+// The 16-bit table form (vslot == 2) of a launch whose gcap is set (a power of two >= 1024): fills ocap, vwords, vslot, sb, qd, qk
+// and gregion as fast_scan (VG == 3) lays the tables out.  false: the form cannot be represented for this index — more than 16
+// remainder bits, more than 32 hashed bits, or no room for the Hamming key beside a slot handle in a heap entry.
+static inline bool fast_tables16_geometry(const vs_index* idx, FastLaunch& f) {
+    uint32_t qd = 1, lb = 0;
+    while ((1ull << qd) < (uint64_t)(idx->d.n > 2 ? idx->d.n : 2)) qd++;
+    while ((1u << lb) < (f.gcap >> 3)) lb++;
+    if (qd < lb + 3) qd = lb + 3;  // (a small index: more hash bits than id bits — the bijection works on any width)
+    f.qd = qd;
+    f.qk = qd - lb;
+    const uint32_t o = round_up_u32(f.gcap / 16, 32);
+    f.ocap = o > 256 ? o : 256;
+    f.vwords = (f.gcap + f.ocap) / 32;
+    f.vslot = 2;
+    f.gregion = (f.gcap >> 1) + f.ocap;
+    f.sb = 0;
+    while ((1ull << f.sb) < (uint64_t)f.gcap + f.ocap) f.sb++;
+    const uint64_t nbits = (uint64_t)idx->d.dim_index * idx->d.bits;
+    return f.qk <= 16 && f.qd <= 32 && nbits < (1ull << (32 - f.sb));
+}
 int launch_search_fast(vs_index* idx, const FastLaunch& s);
 int fast_resident_scans(vs_index* idx, const FastLaunch& s, uint32_t* out);  // size of a persistent grid for this instantiation
 enum { ST_VISITS = 0, ST_CAND = 1, ST_DQ = 2, ST_READS = 3, ST_NEXT = 4, ST_GSPILL = 5, ST_INVIS = 6, ST_INS = 7 /* ids the fast kernel inserted */, ST_N = 8 };

@@ -133,21 +133,9 @@ static int scanpool_create_impl(vs_index* ix, uint32_t capacity, uint32_t L, uin
         f.vcap = round_up_u32(std::max<uint32_t>(2u * (uint32_t)std::min<uint64_t>((uint64_t)L + L / 2 + 32, 1u << 16), 64), 64);
         f.minw = 1;
         f.gcap = std::max<uint32_t>(next_pow2_u32(std::min<uint64_t>(pushes * 4 / 3 + 256, 1u << 22)), 1024);
-        f.ocap = std::max<uint32_t>(round_up_u32(f.gcap / 16, 32), 256);
-        f.vwords = (f.gcap + f.ocap) / 32;
-        f.vslot = 2;
-        while ((1ull << f.sb) < (uint64_t)f.gcap + f.ocap) f.sb++;
-        uint32_t qd = 1, lb = 0;
-        while ((1ull << qd) < (uint64_t)std::max<uint32_t>(ix->d.n, 2)) qd++;
-        while ((1u << lb) < (f.gcap >> 3)) lb++;
-        if (qd < lb + 3) qd = lb + 3;
-        f.qd = qd;
-        f.qk = qd - lb;
-        f.gregion = (f.gcap >> 1) + f.ocap;
         f.glimit = (uint32_t)((uint64_t)f.gcap * 3 / 4) - 64u;
-        const uint64_t nbits = (uint64_t)ix->d.dim_index * ix->d.bits;
         const uint32_t nch = (ix->code_stride + 7) / 8;
-        if (f.qk <= 16 && f.qd <= 32 && nbits < (1ull << (32 - f.sb)) && nch <= 6 && fast_lds_bytes(ix, f) <= 96 * 1024) {
+        if (fast_tables16_geometry(ix, f) && nch <= 6 && fast_lds_bytes(ix, f) <= 96 * 1024) {
             p->fast = true;
             p->fl = f;
             p->rw = (uint32_t)fast_resume_words(f);
