@@ -733,6 +733,73 @@ int vs_build_graph(vs_index* idx, uint32_t search_list_size, double max_alpha, u
  * The reference's build gives no reachability guarantee either (AM/graph/mod.rs:700-715 only warns about orphans). */
 uint32_t vs_index_build_unreachable(const vs_index* idx);
 
+/* ---- rows that arrive after the index is resident: aminsert (AM/build.rs:464-558) ------------------------------------------
+ * The reference's aminsert loads the trained quantizer without touching it (SbqSpeedupStorage::load_for_insert), writes the node
+ * (create_node) and links it with Graph::insert (AM/graph/mod.rs:637-735).  vs_index_insert does the same for a batch of rows on
+ * the device: the rows become nodes n .. n + n_new - 1 in input order, their cosine divisors and SBQ codes are computed with the
+ * quantizer as it stands (mean / m2 / count never change), label sets are appended, a label first carried by an inserted node gets
+ * it as its start node and an empty index gets node 0 as the default start (update_start_nodes, AM/graph/mod.rs:490-531).  The
+ * rows are then linked in batches of at most batch_max with the machinery of vs_build_graph (build-mode search over the graph
+ * as it stands, prune_neighbors, update_back_pointer per target; labeled sets: the filtered pass, then the unfiltered one) and
+ * three steps a whole-graph build replaces by its repair sweep, which an insert into 50M nodes cannot afford:
+ *   - the batch sees itself: the VS_INSERT_MATES (vs_set_option; default 16, 0 = off, at most 64) nearest nodes of the same
+ *     batch by (Hamming, id) join every node's candidates before pruning;
+ *   - no new row may be unfindable: a new node is ANCHORED when the row of a node older than its batch names it, or the row of an
+ *     anchored node of its batch does — two new nodes that only name each other are not.  A node that is not anchored is given a slot
+ *     in the list of its closest old-or-anchored out-neighbor (a free one, else that of the list's last entry when that entry keeps
+ *     another such in-edge); what cannot be placed is counted in orphans_left, never hidden.
+ * memory_optimized (SBQ) indexes with the vector column on the device; VS_ERR_INVALID for plain storage.  VS_ERR_STATE: the
+ * quantizer is untrained (count == 0), a view of the index is alive, a batch is in flight, or a caller-owned device visibility
+ * mask (vs_index_set_visibility_dev) is in force — the library cannot grow it; clear or replace it first.  New rows are visible
+ * (1) in the library's own mask and invisible (0) in every stored snapshot mask: a snapshot taken before the insert cannot see the
+ * tuple.  An insert changes n and may MOVE every array: open vs_scans, scan pools (vs_scanpool_*, whose prefetched round must have
+ * been settled — no pool call in flight) and brokers of the index must be ended or rescanned afterwards, pointers taken with
+ * vs_index_array asked for again, and a writer opened with vs_pages_out_open closed first; vs_pages_out_* afterwards writes the
+ * grown relation.  Not thread safe against any other call on the index.
+ * The refusals above (and a growth that fails) leave the index exactly as it was.  An error AFTER the rows were staged — device
+ * memory running out for the batch buffers, VS_ERR_CAPACITY from a batch's searches, a HIP error — cannot be undone, because
+ * older rows may already name the new nodes: the index then has its n + n_new nodes, label sets and start nodes, with the rows
+ * of the unfinished batches unlinked (empty lists: scans do not find them, nothing dangles).  Run the insert's remaining work
+ * again by rebuilding (vs_build_graph), or accept the unlinked rows and call vs_index_repair.
+ *
+ * vs_index_reserve makes room for `capacity` nodes in every per-node array (codes, neighbor lists, heap tids, vectors, cosine
+ * divisors, label offsets, the library's visibility masks): allocate, copy device to device on the context's stream, free; a
+ * failed growth leaves the index as it was.  vs_index_alloc / vs_index_upload allocate exactly n (capacity == n); an insert that
+ * does not fit grows by half, at least to fit. */
+int vs_index_reserve(vs_index* idx, uint32_t capacity);
+uint32_t vs_index_capacity(const vs_index* idx);
+typedef struct vs_insert_stats {
+    uint32_t first_node, inserted;         /* the new rows are nodes first_node .. first_node + inserted - 1, in input order */
+    uint32_t batches, retries;             /* insert batches run; capacity-overflow relaunches of their searches              */
+    uint32_t mate_edges;                   /* out-edges of new nodes that point at a node of the same batch                   */
+    uint32_t orphans_placed, orphans_left; /* new nodes the anchoring rule had to place / could not place                     */
+    uint32_t grew;                         /* 1 if the arrays were reallocated by this call                                   */
+} vs_insert_stats;
+/* vectors: host [n_new][dim_full] raw f32; heap_tids [n_new]; label_off [n_new + 1] / label_val: CSR of the rows' sorted,
+ * de-duplicated label sets (at most 64 labels per row) for a labeled index, NULL otherwise; batch_max 0 = as vs_build_graph;
+ * out may be NULL */
+int vs_index_insert(vs_index* idx, const float* vectors, const uint64_t* heap_tids, const uint32_t* label_off, const int16_t* label_val,
+                    uint32_t n_new, uint32_t search_list_size, double max_alpha, uint32_t batch_max, vs_insert_stats* out);
+/* the same with the vectors already in device memory (d_vectors [n_new][dim_full]; every other argument stays a host pointer) */
+int vs_index_insert_dev(vs_index* idx, const float* d_vectors, const uint64_t* heap_tids, const uint32_t* label_off,
+                        const int16_t* label_val, uint32_t n_new, uint32_t search_list_size, double max_alpha, uint32_t batch_max,
+                        vs_insert_stats* out);
+/* HIP-event milliseconds the three insert kernels took on this index since the last reset, collected while vs_profile_enable is on:
+ * ms[0] the batch's mates, ms[1] their merge into the candidate lists, ms[2] the anchoring rounds */
+int vs_index_insert_kernel_ms(vs_index* idx, double* ms, int reset);
+/* the batch-mates kernel on its own (as vs_hamming_gather / vs_rerank expose theirs): for each of n code rows (host [n][words]) the c
+ * (1..64) nearest OTHER rows by (Hamming, row number), ties to the lower row; out_ids / out_ham [n][c], padded with VS_INVALID_NODE
+ * (out_ham may be NULL) */
+int vs_batch_mates(vs_index* idx, const uint64_t* codes, uint32_t n, uint32_t c, uint32_t* out_ids, uint32_t* out_ham);
+/* the form the filtered pass of a labeled insert runs (as vs_scan_topk_filtered is to vs_scan_topk): only rows whose label sets
+ * overlap are mates (LabelSetView::overlaps, AM/labels/mod.rs:124-142); label_off [n + 1] / label_val: CSR of the rows' sorted,
+ * de-duplicated label sets, at most 64 labels per row; a row without labels has no mates */
+int vs_batch_mates_filtered(vs_index* idx, const uint64_t* codes, const uint32_t* label_off, const int16_t* label_val, uint32_t n,
+                            uint32_t c, uint32_t* out_ids, uint32_t* out_ham);
+/* the repair pass of vs_build_graph on its own (after many inserts, at the caller's choice): every node the default start node does
+ * not reach is given an in-edge where that strands nobody else; *unreachable (may be NULL) = what vs_index_build_unreachable reports */
+int vs_index_repair(vs_index* idx, uint32_t* unreachable);
+
 /* ---- synthetic corpora generated in HBM (bench / tests; bit-reproducible on the CPU, see pgvectorscale_amd/datagen.py) */
 typedef struct vs_datagen_params {
     uint64_t seed;

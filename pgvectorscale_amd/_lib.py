@@ -114,6 +114,14 @@ class Profile(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_uint64 * 8)]
 
 
+class InsertStats(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("first_node", "inserted", "batches", "retries", "mate_edges", "orphans_placed",
+                                          "orphans_left", "grew")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class DatagenParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("dim", C.c_uint32), ("latent_dim", C.c_uint32), ("n_clusters", C.c_uint32),
                 ("intra_pct", C.c_uint32), ("noise_pct", C.c_uint32), ("normalize", C.c_uint32)]
@@ -269,6 +277,14 @@ SYMBOLS = {
     "vs_sbq_quantize_corpus": (_i, [_vp]),
     "vs_build_graph": (_i, [_vp, _u32, C.c_double, _u32, _u64]),
     "vs_index_build_unreachable": (_u32, [_vp]),
+    "vs_index_reserve": (_i, [_vp, _u32]),
+    "vs_index_capacity": (_u32, [_vp]),
+    "vs_index_insert": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, C.c_double, _u32, C.POINTER(InsertStats)]),
+    "vs_index_insert_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, C.c_double, _u32, C.POINTER(InsertStats)]),
+    "vs_index_insert_kernel_ms": (_i, [_vp, C.POINTER(C.c_double), _i]),
+    "vs_batch_mates": (_i, [_vp, _vp, _u32, _u32, _vp, _vp]),
+    "vs_batch_mates_filtered": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp]),
+    "vs_index_repair": (_i, [_vp, C.POINTER(_u32)]),
     "vs_datagen_fill": (_i, [_vp, C.POINTER(DatagenParams), _u64, _u64, _vp]),
     "vs_bruteforce_topk": (_i, [_vp, _vp, _u32, _u32, _vp, _vp]),
 }

@@ -387,6 +387,7 @@ static int index_alloc_common(vs_ctx* c, const vs_index_desc* desc, bool with_ve
     ix->owner_id = vs_new_owner_id();
     ix->slab = vs_slab_new(c->device);
     ix->d = *desc;
+    ix->capacity = desc->n;  // (vs_index_reserve / vs_index_insert make room for more)
     // (VS_WS_SLAB_EARLY=1: the slab is the index's FIRST device allocation instead of being made by the first search that needs it)
     if (env_u32("VS_WS_SLAB_EARLY", 0) && slab_bytes_wanted(ix)) {
         std::lock_guard<std::mutex> lk(ix->slab->mu);
@@ -419,24 +420,6 @@ int vs_index_live_views(vs_index* ix) {
     const auto it = vs_view_count.find(ix->owner_id);
     return it == vs_view_count.end() ? 0 : it->second;
 }
-#define VS_REQUIRE_OWNER(ix, what)                                                                                                     \
-    do {                                                                                                                                \
-        if ((ix)->is_view) {                                                                                                            \
-            vs_set_error("%s: this handle is a view; the arrays belong to the index it was made from", what);                         \
-            return VS_ERR_STATE;                                                                                                        \
-        }                                                                                                                               \
-    } while (0)
-#define VS_REQUIRE_NO_VIEWS(ix, what)                                                                                                  \
-    do {                                                                                                                                \
-        const int _nv = vs_index_live_views(ix);                                                                                        \
-        if (_nv > 0) {                                                                                                                  \
-            vs_set_error("%s: %d view(s) of this index are alive (cursor lanes, a second stream, a vs_multi shard) and hold its device " \
-                         "pointers; free them first",                                                                                  \
-                         what, _nv);                                                                                                    \
-            return VS_ERR_STATE;                                                                                                        \
-        }                                                                                                                               \
-    } while (0)
-
 extern "C" void vs_index_free(vs_index* ix) {
     if (!ix) return;
     {
@@ -584,7 +567,7 @@ static int vs_index_set_labels_impl(vs_index* ix, const uint32_t* label_off, con
     if (ix->label_off) VS_HIP(hipFree(ix->label_off));
     if (ix->label_val) VS_HIP(hipFree(ix->label_val));
     ix->n_label_vals = label_off[n];
-    VS_HIP(hipMalloc(&ix->label_off, ((size_t)n + 1) * 4));
+    VS_HIP(hipMalloc(&ix->label_off, ((size_t)std::max(n, ix->capacity) + 1) * 4));
     VS_HIP(hipMalloc(&ix->label_val, std::max<uint64_t>(ix->n_label_vals, 1) * 2));
     VS_TRY(vs_dev_upload(ix->ctx, ix->label_off, label_off, ((size_t)n + 1) * 4));
     if (ix->n_label_vals) VS_TRY(vs_dev_upload(ix->ctx, ix->label_val, label_val, ix->n_label_vals * 2));
@@ -595,6 +578,79 @@ extern "C" int vs_index_set_labels(vs_index* ix, const uint32_t* label_off, cons
     return vs_guard("vs_index_set_labels", [&] { return vs_index_set_labels_impl(ix, label_off, label_val); });
 }
 
+
+// ---- capacity: room for rows an insert will add (vs_index_reserve, vs_index_insert) -----------------------------------------
+// Every per-node array the handle owns is reallocated at `capacity` rows, the d.n live rows are copied device to device on the
+// context's stream, and only when every allocation and copy has succeeded do the pointers change hands: a failed growth leaves
+// the index as it was.  label_mask is sized by d.n and re-derived by vs_refresh_label_masks; nbr_mask is dropped by the insert.
+int vs_index_reserve_impl(vs_index* ix, uint32_t capacity, const char* what) {
+    VS_REQUIRE(ix, "%s: index is NULL", what);
+    VS_REQUIRE_OWNER(ix, what);
+    VS_REQUIRE_NO_VIEWS(ix, what);
+    VS_REQUIRE(capacity < VS_INVALID_NODE, "%s: a capacity of %u nodes reaches the end-of-list sentinel", what, capacity);
+    if (ix->ws.pending) {
+        vs_set_error("%s: a batch of this handle is in flight (vs_search_batch_dev_finish first)", what);
+        return VS_ERR_STATE;
+    }
+    if (capacity <= ix->capacity) return VS_OK;
+    vs_ctx* c = ix->ctx;
+    VS_HIP(hipSetDevice(c->device));
+    struct Item {
+        void** slot;
+        size_t row_bytes, extra_rows;  // extra_rows: label_off holds one entry more than there are rows
+        int fill;                      // byte the rows past d.n are set to
+        void* fresh;
+    };
+    std::vector<Item> items;
+    auto add = [&](void* slot, size_t row_bytes, int fill, size_t extra = 0) {
+        void** s = reinterpret_cast<void**>(slot);
+        if (*s) items.push_back(Item{s, row_bytes, extra, fill, nullptr});
+    };
+    add(&ix->codes, ix->code_stride * 8ull, 0);
+    add(&ix->nbrs, ix->nbr_stride * 4ull, 0xFF);
+    add(&ix->tids, 8, 0);
+    add(&ix->vecs, ix->vec_stride * 4ull, 0);
+    add(&ix->vnorm, 4, 0);
+    add(&ix->vnorm_idx, 4, 0);
+    add(&ix->label_off, 4, 0, 1);
+    add(&ix->visible_own, 1, 1);
+    for (int sn = 1; sn < VS_MAX_SNAPSHOTS; ++sn) add(&ix->snap[sn], 1, 0);
+    const size_t live = ix->d.n;
+    int r = VS_OK;
+    for (Item& it : items) {
+        const size_t total = ((size_t)capacity + it.extra_rows) * it.row_bytes, keep = (live + it.extra_rows) * it.row_bytes;
+        hipError_t e = hipMalloc(&it.fresh, total);
+        if (e == hipSuccess && keep) e = hipMemcpyAsync(it.fresh, *it.slot, keep, hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(static_cast<char*>(it.fresh) + keep, it.fill, total - keep, c->stream);
+        if (e != hipSuccess) {
+            vs_set_error("%s: growing to %u nodes failed: %s", what, capacity, hipGetErrorString(e));
+            r = e == hipErrorOutOfMemory ? VS_ERR_OOM : VS_ERR_HIP;
+            break;
+        }
+    }
+    if (r == VS_OK && hipStreamSynchronize(c->stream) != hipSuccess) {
+        vs_set_error("%s: growing to %u nodes failed in the copy", what, capacity);
+        r = VS_ERR_HIP;
+    }
+    if (r != VS_OK) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(c->stream);
+        for (Item& it : items)
+            if (it.fresh) (void)hipFree(it.fresh);
+        return r;
+    }
+    for (Item& it : items) {
+        if (ix->visible && ix->visible == *it.slot) ix->visible = static_cast<const uint8_t*>(it.fresh);  // (the mask in force moved too)
+        (void)hipFree(*it.slot);
+        *it.slot = it.fresh;
+    }
+    ix->capacity = capacity;
+    return VS_OK;
+}
+extern "C" int vs_index_reserve(vs_index* ix, uint32_t capacity) {
+    return vs_guard("vs_index_reserve", [&] { return vs_index_reserve_impl(ix, capacity, "vs_index_reserve"); });
+}
+extern "C" uint32_t vs_index_capacity(const vs_index* ix) { return ix ? ix->capacity : 0; }
 
 extern "C" uint32_t vs_index_build_unreachable(const vs_index* ix) { return ix ? ix->build_unreachable : 0xFFFFFFFFu; }
 
@@ -610,7 +666,7 @@ extern "C" int vs_index_set_visibility(vs_index* ix, const uint8_t* visible) {
         ix->visible = nullptr;
         return VS_OK;
     }
-    if (!ix->visible_own) VS_HIP(hipMalloc(&ix->visible_own, std::max<size_t>(ix->d.n, 1)));
+    if (!ix->visible_own) VS_HIP(hipMalloc(&ix->visible_own, std::max<size_t>(std::max(ix->d.n, ix->capacity), 1)));
     if (ix->d.n) VS_TRY(vs_dev_upload(ix->ctx, ix->visible_own, visible, ix->d.n));
     ix->visible = ix->visible_own;
     return VS_OK;
@@ -628,7 +684,7 @@ extern "C" int vs_index_snapshot_put(vs_index* ix, uint32_t snapshot, const uint
         }
         return VS_OK;
     }
-    if (!ix->snap[snapshot]) VS_HIP(hipMalloc(&ix->snap[snapshot], std::max<size_t>(ix->d.n, 1)));
+    if (!ix->snap[snapshot]) VS_HIP(hipMalloc(&ix->snap[snapshot], std::max<size_t>(std::max(ix->d.n, ix->capacity), 1)));
     else VS_HIP(hipStreamSynchronize(ix->ctx->stream));  // (replacing a mask a launch may still be reading)
     if (ix->d.n) VS_TRY(vs_dev_upload(ix->ctx, ix->snap[snapshot], visible, ix->d.n));
     return VS_OK;

@@ -482,6 +482,204 @@ __global__ void k_count_reached_sources(const uint32_t* __restrict__ nbrs, uint3
     if (v != VS_INVALID_NODE && reached[v] > ls) atomicAdd(&indeg[v], 1u);
 }
 
+// ---- insert: the batch sees itself ----------------------------------------------------------------------------------
+// vs_build_graph can let the nodes of one batch ignore each other because a sweep over the whole graph follows it; an insert
+// into a 50M-node index cannot afford that sweep, so the nodes of an insert batch are made candidates of one another first.
+// k_batch_mates: for every row i of `n` code rows, the c nearest OTHER rows by (Hamming, row number), ties to the lower row.
+// A tiled all-pairs xor + popcount: one wave owns 64 rows and walks the column tiles of 64 rows; the two tiles of a chunk of
+// KW code words sit in LDS, a lane accumulates an 8 x 8 block of pairs in registers, the finished 64 x 64 distances go
+// through LDS to the per-row top-c lists (sorted keys (hamming << 32) | row, kept in LDS across the column tiles).  A tile
+// only touches a row's list when one of its 64 candidates beats the list's last entry.  Rows are `stride` words (zero
+// padded), any W; rows past n read as absent.  c <= 64.
+#define MATES_KW 8
+// label_off != nullptr (the filtered pass of a labeled set): row r is node label_base + r, and only rows whose label sets overlap
+// are mates — what the label filter of the pass's search admits.
+__global__ __launch_bounds__(WAVE) void k_batch_mates(const uint64_t* __restrict__ codes, uint32_t stride, uint32_t n, uint32_t c,
+                                                      uint32_t* __restrict__ out_ids, uint32_t* __restrict__ out_ham,
+                                                      const uint32_t* __restrict__ label_off, const int16_t* __restrict__ label_val,
+                                                      uint32_t label_base) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint64_t* ta = reinterpret_cast<uint64_t*>(smem);          // [64][MATES_KW + 1]
+    uint64_t* tb = ta + 64 * (MATES_KW + 1);                   // [64][MATES_KW + 1]
+    uint64_t* scratch = tb + 64 * (MATES_KW + 1);              // [128]
+    uint64_t* best = scratch + 128;                            // [64][c]
+    uint32_t* dist = reinterpret_cast<uint32_t*>(best + 64 * c);  // [64][65]
+    const int lane = threadIdx.x;
+    const uint32_t i0 = blockIdx.x * 64u;
+    if (i0 >= n) return;
+    const uint32_t ty = (uint32_t)lane >> 3, tx = (uint32_t)lane & 7u;
+    for (uint32_t t = lane; t < 64 * c; t += WAVE) best[t] = ~0ull;
+    __syncthreads();
+    for (uint32_t j0 = 0; j0 < n; j0 += 64) {
+        uint32_t acc[8][8];
+#pragma unroll
+        for (int a = 0; a < 8; ++a)
+#pragma unroll
+            for (int b = 0; b < 8; ++b) acc[a][b] = 0;
+        for (uint32_t w0 = 0; w0 < stride; w0 += MATES_KW) {
+            for (uint32_t t = lane; t < 64 * MATES_KW; t += WAVE) {
+                const uint32_t r = t / MATES_KW, w = t % MATES_KW;
+                const bool wok = w0 + w < stride;
+                ta[r * (MATES_KW + 1) + w] = (wok && i0 + r < n) ? codes[(size_t)(i0 + r) * stride + w0 + w] : 0ull;
+                tb[r * (MATES_KW + 1) + w] = (wok && j0 + r < n) ? codes[(size_t)(j0 + r) * stride + w0 + w] : 0ull;
+            }
+            __syncthreads();
+            for (uint32_t w = 0; w < MATES_KW; ++w) {
+                uint64_t xa[8], xb[8];
+#pragma unroll
+                for (int a = 0; a < 8; ++a) xa[a] = ta[(ty * 8 + a) * (MATES_KW + 1) + w];
+#pragma unroll
+                for (int b = 0; b < 8; ++b) xb[b] = tb[(tx * 8 + b) * (MATES_KW + 1) + w];
+#pragma unroll
+                for (int a = 0; a < 8; ++a)
+#pragma unroll
+                    for (int b = 0; b < 8; ++b) acc[a][b] += (uint32_t)__popcll(xa[a] ^ xb[b]);
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int a = 0; a < 8; ++a)
+#pragma unroll
+            for (int b = 0; b < 8; ++b) dist[(ty * 8 + a) * 65 + tx * 8 + b] = acc[a][b];
+        __syncthreads();
+        for (uint32_t r = 0; r < 64 && i0 + r < n; ++r) {  // (uniform: the block is one wave)
+            const uint32_t j = j0 + (uint32_t)lane;
+            uint64_t key = (j < n && j != i0 + r) ? ((uint64_t)dist[r * 65 + lane] << 32) | j : ~0ull;
+            const uint64_t last = best[r * c + c - 1];
+            if (label_off && key < last && label_pmask(label_off, label_val, label_base + i0 + r, label_base + j) == 0) key = ~0ull;
+            if (!__ballot(key < last)) continue;
+            const uint64_t mine = (uint32_t)lane < c ? best[r * c + lane] : ~0ull;
+            scratch[lane] = mine;
+            scratch[64 + lane] = key;
+            __syncthreads();
+            uint32_t rk_m = 0, rk_k = 0;  // keys are distinct (a row number occurs once); absent entries rank nowhere
+            for (uint32_t t = 0; t < 128; ++t) {
+                const uint64_t o = scratch[t];
+                rk_m += o < mine;
+                rk_k += o < key;
+            }
+            __syncthreads();
+            if (mine != ~0ull && rk_m < c) best[r * c + rk_m] = mine;
+            if (key != ~0ull && rk_k < c) best[r * c + rk_k] = key;
+            __syncthreads();
+        }
+        __syncthreads();
+    }
+    for (uint32_t t = lane; t < 64 * c; t += WAVE) {
+        const uint32_t r = t / c;
+        if (i0 + r >= n) continue;
+        const uint64_t k = best[t];
+        out_ids[(size_t)(i0 + r) * c + (t - r * c)] = k == ~0ull ? VS_INVALID_NODE : (uint32_t)k;
+        out_ham[(size_t)(i0 + r) * c + (t - r * c)] = k == ~0ull ? 0xFFFFFFFFu : (uint32_t)(k >> 32);
+    }
+}
+static size_t mates_lds_bytes(uint32_t c) { return (size_t)(2 * 64 * (MATES_KW + 1) + 128 + 64 * c) * 8 + 64 * 65 * 4; }
+
+// k_insert_merge_mates: the mates of new node b0 + b (row numbers inside the batch, sorted by (Hamming, row)) join its sorted
+// candidate list (vis_ids / vis_d of the build-mode search, ascending by (distance, id)) before pruning: every id once, never the
+// node itself, the closest vmax kept.  One wave per node; both lists are staged in LDS and every entry computes its own place in
+// the merged order (its index + the entries of the other list that sort before it).
+__global__ __launch_bounds__(WAVE) void k_insert_merge_mates(uint32_t b0, uint32_t bn, uint32_t* __restrict__ vis_ids,
+                                                             uint32_t* __restrict__ vis_d, uint32_t* __restrict__ vis_cnt, uint32_t vmax,
+                                                             const uint32_t* __restrict__ mate_ids, const uint32_t* __restrict__ mate_ham,
+                                                             uint32_t c) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint64_t* vk = reinterpret_cast<uint64_t*>(smem);  // [vmax]
+    uint64_t* mk = vk + vmax;                           // [64]
+    const int lane = threadIdx.x;
+    const uint32_t b = blockIdx.x;
+    if (b >= bn) return;
+    const uint32_t p = b0 + b;
+    const uint32_t C0 = min(vis_cnt[b], vmax);
+    for (uint32_t t = lane; t < C0; t += WAVE) vk[t] = ((uint64_t)vis_d[(size_t)b * vmax + t] << 32) | vis_ids[(size_t)b * vmax + t];
+    __syncthreads();
+    // the mates that are new to the list, packed in their order
+    uint64_t key = ~0ull;
+    if ((uint32_t)lane < c) {
+        const uint32_t m = mate_ids[(size_t)b * c + lane];
+        if (m != VS_INVALID_NODE && b0 + m != p) {
+            key = ((uint64_t)mate_ham[(size_t)b * c + lane] << 32) | (b0 + m);
+            for (uint32_t t = 0; t < C0; ++t)
+                if ((uint32_t)vk[t] == b0 + m) key = ~0ull;
+        }
+    }
+    const uint64_t okm = __ballot(key != ~0ull);
+    const uint32_t nm = (uint32_t)__popcll(okm);
+    if (nm == 0) return;  // (uniform)
+    const uint32_t mpos = (uint32_t)__popcll(okm & ((1ull << lane) - 1ull));
+    if (key != ~0ull) mk[mpos] = key;
+    __syncthreads();
+    const uint32_t T = min(C0 + nm, vmax);
+    for (uint32_t t = lane; t < C0; t += WAVE) {
+        const uint64_t k = vk[t];
+        uint32_t before = 0;
+        for (uint32_t u = 0; u < nm; ++u) before += mk[u] < k;
+        const uint32_t pos = t + before;
+        if (pos < T) {
+            vis_ids[(size_t)b * vmax + pos] = (uint32_t)k;
+            vis_d[(size_t)b * vmax + pos] = (uint32_t)(k >> 32);
+        }
+    }
+    if ((uint32_t)lane < nm) {
+        const uint64_t k = mk[lane];
+        uint32_t lo = 0, hi = C0;  // entries of the sorted list that sort before k
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (vk[mid] < k) lo = mid + 1;
+            else hi = mid;
+        }
+        const uint32_t pos = (uint32_t)lane + lo;
+        if (pos < T) {
+            vis_ids[(size_t)b * vmax + pos] = (uint32_t)k;
+            vis_d[(size_t)b * vmax + pos] = (uint32_t)(k >> 32);
+        }
+    }
+    if (lane == 0) vis_cnt[b] = T;
+}
+
+// k_insert_anchor: one round of the anchoring rule over the new nodes b0 .. b0 + bn - 1.  A new node is ANCHORED when the row of
+// an old node (id < b0) names it, or the row of an already anchored node of the range does; of the rows that could, the ones
+// looked at are those of the node's own out-neighbors (a back-edge is only ever asked of those): R rows, one ballot per 64
+// entries.  Two new nodes that only name each other never become anchored.  The host repeats the launch until a round changes
+// nothing (flags only go 0 -> 1, so the fixed point does not depend on the order the waves run in).  mate_cnt (may be null):
+// += the out-edges of the range that point into the range.
+__global__ __launch_bounds__(WAVE) void k_insert_anchor(const uint32_t* __restrict__ nbrs, uint32_t nbr_stride, uint32_t R, uint32_t b0,
+                                                        uint32_t bn, uint32_t* __restrict__ anch, uint32_t* __restrict__ changed,
+                                                        uint32_t* __restrict__ mate_cnt) {
+    const int lane = threadIdx.x;
+    const uint32_t b = blockIdx.x;
+    if (b >= bn) return;
+    const uint32_t x = b0 + b;
+    const uint32_t* rowx = nbrs + (size_t)x * nbr_stride;
+    if (mate_cnt) {
+        uint32_t m = 0;
+        for (uint32_t c0 = 0; c0 < R; c0 += WAVE) {
+            const uint32_t v = c0 + lane < R ? rowx[c0 + lane] : VS_INVALID_NODE;
+            m += (uint32_t)__popcll(__ballot(v != VS_INVALID_NODE && v >= b0 && v - b0 < bn));
+        }
+        if (lane == 0 && m) atomicAdd(mate_cnt, m);
+    }
+    if (anch[b]) return;
+    for (uint32_t t = 0; t < R; ++t) {
+        const uint32_t y = rowx[t];  // (uniform)
+        if (y == VS_INVALID_NODE) break;
+        if (y >= b0 && (y - b0 >= bn || !anch[y - b0])) continue;
+        const uint32_t* rowy = nbrs + (size_t)y * nbr_stride;
+        bool found = false;
+        for (uint32_t c0 = 0; c0 < R && !found; c0 += WAVE) {
+            const uint32_t v = c0 + lane < R ? rowy[c0 + lane] : VS_INVALID_NODE;
+            found = __ballot(v == x) != 0;
+        }
+        if (found) {
+            if (lane == 0) {
+                anch[b] = 1;
+                *changed = 1;
+            }
+            return;
+        }
+    }
+}
+
 struct BuildBufs {
     uint32_t *vis_ids = nullptr, *vis_d = nullptr, *vis_cnt = nullptr, *stats = nullptr, *status = nullptr;
     uint32_t* hash = nullptr;
@@ -493,120 +691,133 @@ struct BuildBufs {
     size_t cub_bytes = 0;
     uint32_t *f_ghash = nullptr, *f_heap = nullptr, *f_pool = nullptr;  // fast-kernel overflow table / heap spill / pool counter
     uint8_t* mark = nullptr;                                             // repair pass: node is reachable from the start node
+    uint32_t *mate_ids = nullptr, *mate_ham = nullptr;                   // insert: [batch][c] mates of the batch's nodes
+    uint32_t* anch = nullptr;                                            // insert: [rows of the call] anchored flags, then `changed`, then the mate-edge count
     void free_all() {
         void* ps[] = {vis_ids, vis_d, vis_cnt, stats, status, hash, heap_g, edge_q, edge_q_sorted, seg_start, nseg,
-                      edge_pd, edge_pd_sorted, cub_tmp, f_ghash, f_heap, f_pool, mark};
+                      edge_pd, edge_pd_sorted, cub_tmp, f_ghash, f_heap, f_pool, mark, mate_ids, mate_ham, anch};
         for (void* p : ps)
             if (p) (void)hipFree(p);
     }
 };
 
-static int build_graph_impl(vs_index* ix, uint32_t L, double max_alpha_d, uint32_t batch_max, BuildBufs& B) {
-    vs_ctx* c = ix->ctx;
-    hipStream_t st = c->stream;
-    const uint32_t n = ix->d.n, R = ix->d.num_neighbors, stride = ix->code_stride;
-    const float max_alpha = (float)max_alpha_d;
-    VS_HIP(hipMemsetAsync(ix->nbrs, 0xFF, (size_t)std::max(n, 1u) * ix->nbr_stride * 4, st));
-    if (n == 0) {
-        ix->d.default_start = VS_INVALID_NODE;
+// The batch machinery shared by vs_build_graph and vs_index_insert: capacities and buffers of the build-mode search (init), and one
+// batch (run): searches for the new nodes b0 .. b0 + bn - 1 over the graph as it stands, their out-edges, the back-edges.
+struct BatchRunner {
+    vs_index* ix = nullptr;
+    BuildBufs* Bp = nullptr;
+    hipStream_t st = nullptr;
+    uint32_t R = 0, stride = 0, L = 0, batch_max = 0;
+    float max_alpha = 1.0f;
+    bool labeled = false;
+    uint32_t vmax = 0, hl = 512, lh = 0, hcap = 0, hashcap = 0, cmax = 1, mcap = 0;
+    uint32_t use_lds_new = 0, use_lds_back = 0, use_lds_merge = 0;
+    size_t lds_new = 0, lds_back = 0, lds_merge = 0, hash_alloc = 0, ids_alloc = 0;
+    FastLaunch f{};
+    bool use_fast = true;
+    uint32_t retries = 0;
+    // insert only: mates per node (0: the nodes of a batch do not see each other, as in vs_build_graph) and HIP-event time of the
+    // three insert kernels (ms[0] k_batch_mates, [1] k_insert_merge_mates, [2] k_insert_anchor)
+    uint32_t mates = 0;
+    double ms[3] = {0, 0, 0};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+
+    // n: the nodes the graph will have when the last batch is in (sizes the default batch and picks the dedup regime)
+    int init(vs_index* ix_, BuildBufs& B, uint32_t L_, float max_alpha_, uint32_t batch_max_, uint32_t n) {
+        ix = ix_;
+        Bp = &B;
+        vs_ctx* c = ix->ctx;
+        st = c->stream;
+        R = ix->d.num_neighbors;
+        stride = ix->code_stride;
+        L = L_;
+        max_alpha = max_alpha_;
+        labeled = ix->label_off != nullptr;
+        batch_max = batch_max_;
+        if (batch_max == 0) batch_max = std::min<uint32_t>(65536, std::max<uint32_t>(1024, n / 64));
+        // capacities of the build-mode search
+        vmax = std::max<uint32_t>(round_up_u32(3 * L + 64, 64), 128);      // visited list cap (candidates of prune)
+        hcap = (2 * L + 64) * R;                                // heap capacity (global spill beyond hl)
+        hashcap = std::max<uint32_t>(next_pow2_u32(2ull * hcap), 256);
+        while (cmax < R + 128) cmax <<= 1;  // back-edge candidate cap (pow2, >= R + new sources kept)
+        const size_t code_bytes = (size_t)stride * 8;
+        use_lds_new = (vmax * code_bytes + vmax * 12 + R * 4 + 64 <= 150 * 1024) ? 1 : 0;
+        use_lds_back = (cmax * code_bytes + cmax * 28 + R * 4 + 64 <= 150 * 1024) ? 1 : 0;
+        lds_new = (size_t)vmax * 12 + round_up_u32(R, 4) * 4 + (use_lds_new ? vmax * code_bytes : 0) + 64;
+        lds_back = (size_t)cmax * 28 + round_up_u32(R, 4) * 4 + (use_lds_back ? cmax * code_bytes : 0) + 64;
+        mcap = next_pow2_u32((uint64_t)vmax + R);  // candidates of k_build_prune_merge
+        use_lds_merge = (mcap * code_bytes + mcap * 28 + R * 4 + 64 <= 150 * 1024) ? 1 : 0;
+        lds_merge = (size_t)mcap * 28 + round_up_u32(R, 4) * 4 + (use_lds_merge ? mcap * code_bytes : 0) + 64;
+        VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_build_prune_new),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_build_backedges),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_build_prune_merge),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+
+        const size_t bm = batch_max;
+        VS_HIP(hipMalloc(&B.vis_ids, bm * vmax * 4));
+        VS_HIP(hipMalloc(&B.vis_d, bm * vmax * 4));
+        VS_HIP(hipMalloc(&B.vis_cnt, bm * 4));
+        VS_HIP(hipMalloc(&B.stats, bm * ST_N * 4));
+        VS_HIP(hipMalloc(&B.status, bm * 4));
+        VS_HIP(hipMalloc(&B.edge_q, bm * R * 8));
+        VS_HIP(hipMalloc(&B.edge_q_sorted, bm * R * 8));
+        VS_HIP(hipMalloc(&B.edge_pd, bm * R * 8));
+        VS_HIP(hipMalloc(&B.edge_pd_sorted, bm * R * 8));
+        VS_HIP(hipMalloc(&B.seg_start, bm * R * 4));
+        VS_HIP(hipMalloc(&B.nseg, 4));
+        VS_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, B.cub_bytes, B.edge_q, B.edge_q_sorted, B.edge_pd,
+                                                  B.edge_pd_sorted, (int)(bm * R), 0, 64, st));
+        VS_HIP(hipMalloc(&B.cub_tmp, B.cub_bytes + 16));
+
+        // The searches of a batch run on the LDS-resident kernel (vs_search_fast.hip, BUILD variant); the general kernel only
+        // re-runs the scans that outgrow it.  Same operating-point rule as for queries: dedup table in LDS for small graphs,
+        // table-less (global table, high occupancy) once a search inserts more ids than an LDS table should hold.
+        use_fast = vs_opt_get("VS_BUILD_FAST") ? atoi(vs_opt_get("VS_BUILD_FAST")) != 0 : true;
+        {
+            const uint64_t nbits = (uint64_t)ix->d.dim_index * ix->d.bits;
+            const uint32_t typ_ins = (L + L / 4 + 16) * std::min<uint32_t>(R, 16);
+            const bool lds_table = n <= 4000000u && typ_ins <= 3072;
+            f.L = L;
+            f.M = vmax;
+            f.hl = 1023;
+            f.hcap = std::max(hcap, f.hl);  // small L * R: the whole heap fits the LDS part (the launcher wants hcap >= hl)
+            f.gstride = round_up_u32(f.hcap - f.hl + 2, 2);
+            f.lh = lds_table ? std::max<uint32_t>(round_up_u32(typ_ins, 64), 256) : 0;
+            f.gcap = next_pow2_u32(std::max<uint32_t>(4 * typ_ins, 1024));
+            f.sb = 0;
+            while ((1ull << f.sb) < (uint64_t)f.lh + f.gcap) f.sb++;
+            f.vr = 0;
+            f.vcap = vmax + 64;
+            f.minw = 1;
+            f.build = 1;
+            if (nbits >= (1ull << (32 - f.sb)) || fast_lds_bytes(ix, f) > 64 * 1024) use_fast = false;
+            if (use_fast) {
+                VS_HIP(hipMalloc(&B.f_ghash, bm * f.gcap * 4));
+                VS_HIP(hipMalloc(&B.f_heap, bm * f.gstride * 4));
+                VS_HIP(hipMalloc(&B.f_pool, 64));
+            }
+        }
         return VS_OK;
     }
-    ix->d.default_start = 0;
-    const bool labeled = ix->label_off != nullptr;
-    if (labeled) {
-        // update_start_nodes (AM/graph/mod.rs:490-531): a node is the start node of every label it is the first to carry;
-        // nodes arrive in id order, so that is the smallest id per label
-        std::vector<uint32_t> off((size_t)n + 1);
-        VS_HIP(hipMemcpy(off.data(), ix->label_off, off.size() * 4, hipMemcpyDeviceToHost));
-        std::vector<int16_t> val(std::max<size_t>(off[n], 1));
-        if (off[n]) VS_HIP(hipMemcpy(val.data(), ix->label_val, (size_t)off[n] * 2, hipMemcpyDeviceToHost));
-        std::map<int16_t, uint32_t> first;
-        for (uint32_t i = 0; i < n; ++i) {
-            VS_REQUIRE(off[i + 1] - off[i] <= 64, "vs_build_graph: node %u carries more than 64 labels", i);
-            for (uint32_t j = off[i]; j < off[i + 1]; ++j) first.emplace(val[j], i);
-        }
-        std::vector<int16_t> sl;
-        std::vector<uint32_t> sn;
-        for (const auto& kv : first) {
-            sl.push_back(kv.first);
-            sn.push_back(kv.second);
-        }
-        VS_TRY(vs_index_set_start_nodes(ix, 0, sl.data(), sn.data(), (uint32_t)sl.size()));
+
+    void tick() {
+        if (ev[0]) (void)hipEventRecord(ev[0], st);
     }
-    if (batch_max == 0) batch_max = std::min<uint32_t>(65536, std::max<uint32_t>(1024, n / 64));
-    // capacities of the build-mode search
-    uint32_t vmax = std::max<uint32_t>(round_up_u32(3 * L + 64, 64), 128);      // visited list cap (candidates of prune)
-    uint32_t hl = 512, lh = 0;                                       // LDS-resident parts of the search state
-    uint32_t hcap = (2 * L + 64) * R;                                // heap capacity (global spill beyond hl)
-    uint32_t hashcap = std::max<uint32_t>(next_pow2_u32(2ull * hcap), 256);
-    uint32_t cmax = 1;
-    while (cmax < R + 128) cmax <<= 1;  // back-edge candidate cap (pow2, >= R + new sources kept)
-    const size_t code_bytes = (size_t)stride * 8;
-    const uint32_t use_lds_new = (vmax * code_bytes + vmax * 12 + R * 4 + 64 <= 150 * 1024) ? 1 : 0;
-    const uint32_t use_lds_back = (cmax * code_bytes + cmax * 28 + R * 4 + 64 <= 150 * 1024) ? 1 : 0;
-    const size_t lds_new = (size_t)vmax * 12 + round_up_u32(R, 4) * 4 + (use_lds_new ? vmax * code_bytes : 0) + 64;
-    const size_t lds_back = (size_t)cmax * 28 + round_up_u32(R, 4) * 4 + (use_lds_back ? cmax * code_bytes : 0) + 64;
-    const uint32_t mcap = next_pow2_u32((uint64_t)vmax + R);  // candidates of k_build_prune_merge
-    const uint32_t use_lds_merge = (mcap * code_bytes + mcap * 28 + R * 4 + 64 <= 150 * 1024) ? 1 : 0;
-    const size_t lds_merge = (size_t)mcap * 28 + round_up_u32(R, 4) * 4 + (use_lds_merge ? mcap * code_bytes : 0) + 64;
-    VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_build_prune_new),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_build_backedges),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_build_prune_merge),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-
-    const size_t bm = batch_max;
-    VS_HIP(hipMalloc(&B.vis_ids, bm * vmax * 4));
-    VS_HIP(hipMalloc(&B.vis_d, bm * vmax * 4));
-    VS_HIP(hipMalloc(&B.vis_cnt, bm * 4));
-    VS_HIP(hipMalloc(&B.stats, bm * ST_N * 4));
-    VS_HIP(hipMalloc(&B.status, bm * 4));
-    VS_HIP(hipMalloc(&B.edge_q, bm * R * 8));
-    VS_HIP(hipMalloc(&B.edge_q_sorted, bm * R * 8));
-    VS_HIP(hipMalloc(&B.edge_pd, bm * R * 8));
-    VS_HIP(hipMalloc(&B.edge_pd_sorted, bm * R * 8));
-    VS_HIP(hipMalloc(&B.seg_start, bm * R * 4));
-    VS_HIP(hipMalloc(&B.nseg, 4));
-    VS_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, B.cub_bytes, B.edge_q, B.edge_q_sorted, B.edge_pd,
-                                              B.edge_pd_sorted, (int)(bm * R), 0, 64, st));
-    VS_HIP(hipMalloc(&B.cub_tmp, B.cub_bytes + 16));
-    size_t hash_alloc = 0, ids_alloc = 0;
-
-    // The searches of a batch run on the LDS-resident kernel (vs_search_fast.hip, BUILD variant); the general kernel only
-    // re-runs the scans that outgrow it.  Same operating-point rule as for queries: dedup table in LDS for small graphs,
-    // table-less (global table, high occupancy) once a search inserts more ids than an LDS table should hold.
-    FastLaunch f{};
-    bool use_fast = vs_opt_get("VS_BUILD_FAST") ? atoi(vs_opt_get("VS_BUILD_FAST")) != 0 : true;
-    {
-        const uint64_t nbits = (uint64_t)ix->d.dim_index * ix->d.bits;
-        const uint32_t typ_ins = (L + L / 4 + 16) * std::min<uint32_t>(R, 16);
-        const bool lds_table = n <= 4000000u && typ_ins <= 3072;
-        f.L = L;
-        f.M = vmax;
-        f.hl = 1023;
-        f.hcap = std::max(hcap, f.hl);  // small L * R: the whole heap fits the LDS part (the launcher wants hcap >= hl)
-        f.gstride = round_up_u32(f.hcap - f.hl + 2, 2);
-        f.lh = lds_table ? std::max<uint32_t>(round_up_u32(typ_ins, 64), 256) : 0;
-        f.gcap = next_pow2_u32(std::max<uint32_t>(4 * typ_ins, 1024));
-        f.sb = 0;
-        while ((1ull << f.sb) < (uint64_t)f.lh + f.gcap) f.sb++;
-        f.vr = 0;
-        f.vcap = vmax + 64;
-        f.minw = 1;
-        f.build = 1;
-        if (nbits >= (1ull << (32 - f.sb)) || fast_lds_bytes(ix, f) > 64 * 1024) use_fast = false;
-        if (use_fast) {
-            VS_HIP(hipMalloc(&B.f_ghash, bm * f.gcap * 4));
-            VS_HIP(hipMalloc(&B.f_heap, bm * f.gstride * 4));
-            VS_HIP(hipMalloc(&B.f_pool, 64));
-        }
+    void tock(int which) {
+        if (!ev[0]) return;
+        float t = 0.f;
+        if (hipEventRecord(ev[1], st) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
+            hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess)
+            ms[which] += t;
     }
 
-    // one batch: searches for the new nodes b0 .. b0 + bn - 1, their out-edges, the back-edges
     // filtered: the pass from the label start nodes with the label filter (labeled sets only); otherwise from the default
-    // start node.  A labeled set's unfiltered pass merges into the rows the filtered pass wrote.
-    auto insert_batch = [&](uint32_t b0, uint32_t bn, bool filtered) -> int {
+    // start node.  A labeled set's unfiltered pass merges into the rows the filtered pass wrote.  with_mates (insert): the c
+    // nearest nodes of the same batch join every node's candidates before pruning.
+    int run(uint32_t b0, uint32_t bn, bool filtered, bool with_mates = false) {
+        BuildBufs& B = *Bp;
         const uint64_t* qcodes = ix->codes + (size_t)b0 * stride;
         // label keys of the searches = the new nodes' own label sets (CSR offsets are absolute into label_val)
         const int16_t* ql = filtered ? ix->label_val : nullptr;
@@ -671,7 +882,10 @@ static int build_graph_impl(vs_index* ix, uint32_t L, double max_alpha_d, uint32
             VS_HIP(hipStreamSynchronize(st));
             uint32_t ovf = 0;
             for (uint32_t v : status) ovf |= v;
-            if (!ovf) break;
+            if (!ovf) {
+                retries += (uint32_t)attempt;
+                break;
+            }
             if (attempt >= 5) {
                 vs_set_error("vs_build_graph: search structures overflowed (flags 0x%x)", ovf);
                 return VS_ERR_CAPACITY;
@@ -684,6 +898,20 @@ static int build_graph_impl(vs_index* ix, uint32_t L, double max_alpha_d, uint32
             }
             if (ovf & OVF_HEAP) hcap *= 2;
             if (ovf & OVF_HASH) hashcap *= 2;
+        }
+        if (with_mates && mates && bn > 1) {
+            const uint32_t c = mates;
+            tick();
+            hipLaunchKernelGGL(k_batch_mates, dim3((bn + 63) / 64), dim3(WAVE), mates_lds_bytes(c), st, ix->codes + (size_t)b0 * stride,
+                               stride, bn, c, B.mate_ids, B.mate_ham, filtered ? ix->label_off : nullptr,
+                               filtered ? ix->label_val : nullptr, b0);
+            VS_HIP(hipGetLastError());
+            tock(0);
+            tick();
+            hipLaunchKernelGGL(k_insert_merge_mates, dim3(bn), dim3(WAVE), ((size_t)vmax + 64) * 8, st, b0, bn, B.vis_ids, B.vis_d,
+                               B.vis_cnt, vmax, B.mate_ids, B.mate_ham, c);
+            VS_HIP(hipGetLastError());
+            tock(1);
         }
         // out-edges of the new nodes + back-edge requests
         if (labeled)
@@ -708,140 +936,182 @@ static int build_graph_impl(vs_index* ix, uint32_t L, double max_alpha_d, uint32
                            use_lds_back, labeled ? ix->label_off : nullptr, labeled ? ix->label_val : nullptr);
         VS_HIP(hipGetLastError());
         return VS_OK;
-    };
+    }
+};
+
+// repair pass (see k_reach_sweep): rounds of { reachable set, in-edges for the nodes outside it } until a sweep finds every
+// node (at most eight); what the last sweep still could not reach is reported by vs_index_build_unreachable()
+static int repair_graph(vs_index* ix, BuildBufs& B) {
+    hipStream_t st = ix->ctx->stream;
+    const uint32_t n = ix->d.n, R = ix->d.num_neighbors;
+    if (n <= 2) return VS_OK;  // (nothing a sweep could find)
+    ix->build_unreachable = 0;
+    VS_HIP(hipMalloc(&B.mark, (size_t)n + 8));  // n flags, then (4-byte aligned) the `changed` word
+    uint32_t* d_changed = reinterpret_cast<uint32_t*>(B.mark + (((size_t)n + 3) & ~(size_t)3));
+    std::vector<uint8_t> reached(n);
+    std::vector<uint32_t> lost, indeg, row0(R);
+    const size_t cells = (size_t)n * R;
+    const dim3 cgrid((unsigned)((cells + 255) / 256));
+    const uint32_t start = ix->d.default_start;
+    for (int round = 0; round < 8; ++round) {
+        VS_HIP(hipMemsetAsync(B.mark, 0, (size_t)n + 8, st));
+        const uint8_t one = 1;
+        VS_HIP(hipMemcpyAsync(B.mark + start, &one, 1, hipMemcpyHostToDevice, st));
+        bool converged = false;
+        for (uint32_t level = 1; level < 255 && !converged; ++level) {  // one BFS level per sweep
+            uint32_t changed = 0;
+            VS_HIP(hipMemsetAsync(d_changed, 0, 4, st));
+            hipLaunchKernelGGL(k_reach_sweep, cgrid, dim3(256), 0, st, ix->nbrs, ix->nbr_stride, R, n, B.mark, level, d_changed);
+            VS_HIP(hipGetLastError());
+            VS_HIP(hipMemcpyAsync(&changed, d_changed, 4, hipMemcpyDeviceToHost, st));
+            VS_HIP(hipStreamSynchronize(st));
+            converged = changed == 0;
+        }
+        if (!converged) {  // more than 254 levels deep: not a graph this pass can judge
+            ix->build_unreachable = 0xFFFFFFFFu;
+            break;
+        }
+        VS_HIP(hipMemcpyAsync(reached.data(), B.mark, n, hipMemcpyDeviceToHost, st));
+        VS_HIP(hipStreamSynchronize(st));
+        lost.clear();
+        for (uint32_t i = 0; i < n; ++i)
+            if (!reached[i]) lost.push_back(i);
+        ix->build_unreachable = (uint32_t)lost.size();  // (what the last completed sweep found; 0 when the loop ends here)
+        if (lost.empty() || round == 7) break;
+        // Each of them takes a slot in the list of its closest reachable out-neighbor — a free one, else that of the last
+        // entry that keeps an in-edge from a node of a strictly lower BFS level (indeg[] counts only those: a lower-level
+        // source is reached without passing through the entry, so the entry cannot be stranded by losing this edge —
+        // counting every reachable source would let two nodes that only reach each other vouch for one another).  Rare
+        // (none on the bench corpora), so this runs on the host, in node order; the sweep of the next round re-checks.
+        uint32_t* d_indeg = nullptr;
+        VS_HIP(hipMalloc(&d_indeg, (size_t)n * 4));
+        indeg.assign(n, 0);
+        int r = VS_OK;
+        auto hip_ok = [&](hipError_t e) {
+            if (r == VS_OK && e != hipSuccess) {
+                vs_set_error("vs_build_graph (repair): %s", hipGetErrorString(e));
+                r = VS_ERR_HIP;
+            }
+        };
+        hip_ok(hipMemsetAsync(d_indeg, 0, (size_t)n * 4, st));
+        hipLaunchKernelGGL(k_count_reached_sources, cgrid, dim3(256), 0, st, ix->nbrs, ix->nbr_stride, R, n, B.mark, d_indeg);
+        hip_ok(hipGetLastError());
+        hip_ok(hipMemcpyAsync(indeg.data(), d_indeg, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        hip_ok(hipStreamSynchronize(st));
+        (void)hipFree(d_indeg);
+        // the lists of the lost nodes, so that what becomes reachable through a node that was just given a way in is known
+        // without another sweep
+        std::vector<uint32_t> lrows(lost.size() * (size_t)R), lidx(n, 0xFFFFFFFFu), stack, level(n);
+        for (uint32_t i = 0; i < n; ++i) level[i] = reached[i];  // 1 + BFS level (0: not reached); grows past 255 on the host
+        for (size_t oi = 0; oi < lost.size() && r == VS_OK; ++oi) {
+            lidx[lost[oi]] = (uint32_t)oi;
+            hip_ok(hipMemcpy(&lrows[oi * R], ix->nbrs + (size_t)lost[oi] * ix->nbr_stride, (size_t)R * 4, hipMemcpyDeviceToHost));
+        }
+        for (bool progress = true; progress && r == VS_OK;) {
+            progress = false;
+            for (size_t oi = 0; oi < lost.size() && r == VS_OK; ++oi) {
+                const uint32_t x = lost[oi];
+                if (reached[x]) continue;
+                const uint32_t* rowx = &lrows[oi * R];
+                bool placed = false;
+                for (uint32_t c = 0; c < R && r == VS_OK && !placed && rowx[c] != VS_INVALID_NODE; ++c) {  // closest first
+                    const uint32_t n0 = rowx[c];
+                    if (!reached[n0]) continue;
+                    uint32_t* rown = lidx[n0] != 0xFFFFFFFFu ? &lrows[(size_t)lidx[n0] * R] : row0.data();
+                    if (rown == row0.data())
+                        hip_ok(hipMemcpy(row0.data(), ix->nbrs + (size_t)n0 * ix->nbr_stride, (size_t)R * 4, hipMemcpyDeviceToHost));
+                    if (r != VS_OK) break;
+                    int slot = -1;
+                    for (uint32_t t = 0; t < R && slot < 0; ++t)
+                        if (rown[t] == VS_INVALID_NODE) slot = (int)t;
+                    for (int t = (int)R - 1; t >= 0 && slot < 0; --t) {
+                        const uint32_t y = rown[t];
+                        const uint32_t mine = (reached[y] && level[n0] < level[y]) ? 1u : 0u;  // is n0 -> y one of the counted edges?
+                        if (indeg[y] >= mine + 1u) slot = t;
+                    }
+                    if (slot < 0) continue;
+                    if (rown[slot] != VS_INVALID_NODE && reached[rown[slot]] && level[n0] < level[rown[slot]]) indeg[rown[slot]]--;
+                    rown[slot] = x;
+                    level[x] = level[n0] + 1;
+                    indeg[x]++;
+                    placed = true;
+                    hip_ok(hipMemcpy(ix->nbrs + (size_t)n0 * ix->nbr_stride, rown, (size_t)R * 4, hipMemcpyHostToDevice));
+                }
+                if (!placed) continue;
+                progress = true;
+                reached[x] = 1;
+                stack.assign(1, x);
+                while (!stack.empty()) {  // everything x leads to is reachable now
+                    const uint32_t u = stack.back();
+                    stack.pop_back();
+                    const uint32_t* rowu = &lrows[(size_t)lidx[u] * R];
+                    for (uint32_t t = 0; t < R && rowu[t] != VS_INVALID_NODE; ++t) {
+                        const uint32_t v = rowu[t];
+                        if (!reached[v]) {
+                            reached[v] = 1;
+                            level[v] = level[u] + 1;
+                            indeg[v]++;
+                            stack.push_back(v);
+                        } else if (level[u] < level[v]) {
+                            indeg[v]++;
+                        }
+                    }
+                }
+            }
+        }
+        VS_TRY(r);
+    }
+    return VS_OK;
+}
+
+static int build_graph_impl(vs_index* ix, uint32_t L, double max_alpha_d, uint32_t batch_max, BuildBufs& B) {
+    vs_ctx* c = ix->ctx;
+    hipStream_t st = c->stream;
+    const uint32_t n = ix->d.n;
+    VS_HIP(hipMemsetAsync(ix->nbrs, 0xFF, (size_t)std::max(n, 1u) * ix->nbr_stride * 4, st));
+    if (n == 0) {
+        ix->d.default_start = VS_INVALID_NODE;
+        return VS_OK;
+    }
+    ix->d.default_start = 0;
+    const bool labeled = ix->label_off != nullptr;
+    if (labeled) {
+        // update_start_nodes (AM/graph/mod.rs:490-531): a node is the start node of every label it is the first to carry;
+        // nodes arrive in id order, so that is the smallest id per label
+        std::vector<uint32_t> off((size_t)n + 1);
+        VS_HIP(hipMemcpy(off.data(), ix->label_off, off.size() * 4, hipMemcpyDeviceToHost));
+        std::vector<int16_t> val(std::max<size_t>(off[n], 1));
+        if (off[n]) VS_HIP(hipMemcpy(val.data(), ix->label_val, (size_t)off[n] * 2, hipMemcpyDeviceToHost));
+        std::map<int16_t, uint32_t> first;
+        for (uint32_t i = 0; i < n; ++i) {
+            VS_REQUIRE(off[i + 1] - off[i] <= 64, "vs_build_graph: node %u carries more than 64 labels", i);
+            for (uint32_t j = off[i]; j < off[i + 1]; ++j) first.emplace(val[j], i);
+        }
+        std::vector<int16_t> sl;
+        std::vector<uint32_t> sn;
+        for (const auto& kv : first) {
+            sl.push_back(kv.first);
+            sn.push_back(kv.second);
+        }
+        VS_TRY(vs_index_set_start_nodes(ix, 0, sl.data(), sn.data(), (uint32_t)sl.size()));
+    }
+    BatchRunner br;
+    VS_TRY(br.init(ix, B, L, (float)max_alpha_d, batch_max, n));
+    batch_max = br.batch_max;
 
     uint32_t b0 = 1;  // node 0 is the start node and has no one to link to yet
     uint32_t bsz = 1;
     while (b0 < n) {
         const uint32_t bn = std::min<uint32_t>(std::min<uint32_t>(bsz, batch_max), n - b0);
-        if (labeled) VS_TRY(insert_batch(b0, bn, true));  // Graph::insert: first with the label filter ...
-        VS_TRY(insert_batch(b0, bn, false));              // ... then from the default start node without it
+        if (labeled) VS_TRY(br.run(b0, bn, true));  // Graph::insert: first with the label filter ...
+        VS_TRY(br.run(b0, bn, false));              // ... then from the default start node without it
         b0 += bn;
         if (bsz < batch_max) bsz = std::min<uint32_t>(batch_max, bsz * 2);
     }
     VS_HIP(hipStreamSynchronize(st));
 
-    // repair pass (see k_reach_sweep): rounds of { reachable set, in-edges for the nodes outside it } until a sweep finds every
-    // node (at most eight); what the last sweep still could not reach is reported by vs_index_build_unreachable()
     const char* rep_env = vs_opt_get("VS_BUILD_REPAIR");
-    if (n > 2 && !(rep_env && *rep_env == '0')) {
-        VS_HIP(hipMalloc(&B.mark, (size_t)n + 8));  // n flags, then (4-byte aligned) the `changed` word
-        uint32_t* d_changed = reinterpret_cast<uint32_t*>(B.mark + (((size_t)n + 3) & ~(size_t)3));
-        std::vector<uint8_t> reached(n);
-        std::vector<uint32_t> lost, indeg, row0(R);
-        const size_t cells = (size_t)n * R;
-        const dim3 cgrid((unsigned)((cells + 255) / 256));
-        const uint32_t start = ix->d.default_start;
-        ix->build_unreachable = 0;
-        for (int round = 0; round < 8; ++round) {
-            VS_HIP(hipMemsetAsync(B.mark, 0, (size_t)n + 8, st));
-            const uint8_t one = 1;
-            VS_HIP(hipMemcpyAsync(B.mark + start, &one, 1, hipMemcpyHostToDevice, st));
-            bool converged = false;
-            for (uint32_t level = 1; level < 255 && !converged; ++level) {  // one BFS level per sweep
-                uint32_t changed = 0;
-                VS_HIP(hipMemsetAsync(d_changed, 0, 4, st));
-                hipLaunchKernelGGL(k_reach_sweep, cgrid, dim3(256), 0, st, ix->nbrs, ix->nbr_stride, R, n, B.mark, level, d_changed);
-                VS_HIP(hipGetLastError());
-                VS_HIP(hipMemcpyAsync(&changed, d_changed, 4, hipMemcpyDeviceToHost, st));
-                VS_HIP(hipStreamSynchronize(st));
-                converged = changed == 0;
-            }
-            if (!converged) {  // more than 254 levels deep: not a graph this pass can judge
-                ix->build_unreachable = 0xFFFFFFFFu;
-                break;
-            }
-            VS_HIP(hipMemcpyAsync(reached.data(), B.mark, n, hipMemcpyDeviceToHost, st));
-            VS_HIP(hipStreamSynchronize(st));
-            lost.clear();
-            for (uint32_t i = 0; i < n; ++i)
-                if (!reached[i]) lost.push_back(i);
-            ix->build_unreachable = (uint32_t)lost.size();  // (what the last completed sweep found; 0 when the loop ends here)
-            if (lost.empty() || round == 7) break;
-            // Each of them takes a slot in the list of its closest reachable out-neighbor — a free one, else that of the last
-            // entry that keeps an in-edge from a node of a strictly lower BFS level (indeg[] counts only those: a lower-level
-            // source is reached without passing through the entry, so the entry cannot be stranded by losing this edge —
-            // counting every reachable source would let two nodes that only reach each other vouch for one another).  Rare
-            // (none on the bench corpora), so this runs on the host, in node order; the sweep of the next round re-checks.
-            uint32_t* d_indeg = nullptr;
-            VS_HIP(hipMalloc(&d_indeg, (size_t)n * 4));
-            indeg.assign(n, 0);
-            int r = VS_OK;
-            auto hip_ok = [&](hipError_t e) {
-                if (r == VS_OK && e != hipSuccess) {
-                    vs_set_error("vs_build_graph (repair): %s", hipGetErrorString(e));
-                    r = VS_ERR_HIP;
-                }
-            };
-            hip_ok(hipMemsetAsync(d_indeg, 0, (size_t)n * 4, st));
-            hipLaunchKernelGGL(k_count_reached_sources, cgrid, dim3(256), 0, st, ix->nbrs, ix->nbr_stride, R, n, B.mark, d_indeg);
-            hip_ok(hipGetLastError());
-            hip_ok(hipMemcpyAsync(indeg.data(), d_indeg, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-            hip_ok(hipStreamSynchronize(st));
-            (void)hipFree(d_indeg);
-            // the lists of the lost nodes, so that what becomes reachable through a node that was just given a way in is known
-            // without another sweep
-            std::vector<uint32_t> lrows(lost.size() * (size_t)R), lidx(n, 0xFFFFFFFFu), stack, level(n);
-            for (uint32_t i = 0; i < n; ++i) level[i] = reached[i];  // 1 + BFS level (0: not reached); grows past 255 on the host
-            for (size_t oi = 0; oi < lost.size() && r == VS_OK; ++oi) {
-                lidx[lost[oi]] = (uint32_t)oi;
-                hip_ok(hipMemcpy(&lrows[oi * R], ix->nbrs + (size_t)lost[oi] * ix->nbr_stride, (size_t)R * 4, hipMemcpyDeviceToHost));
-            }
-            for (bool progress = true; progress && r == VS_OK;) {
-                progress = false;
-                for (size_t oi = 0; oi < lost.size() && r == VS_OK; ++oi) {
-                    const uint32_t x = lost[oi];
-                    if (reached[x]) continue;
-                    const uint32_t* rowx = &lrows[oi * R];
-                    bool placed = false;
-                    for (uint32_t c = 0; c < R && r == VS_OK && !placed && rowx[c] != VS_INVALID_NODE; ++c) {  // closest first
-                        const uint32_t n0 = rowx[c];
-                        if (!reached[n0]) continue;
-                        uint32_t* rown = lidx[n0] != 0xFFFFFFFFu ? &lrows[(size_t)lidx[n0] * R] : row0.data();
-                        if (rown == row0.data())
-                            hip_ok(hipMemcpy(row0.data(), ix->nbrs + (size_t)n0 * ix->nbr_stride, (size_t)R * 4, hipMemcpyDeviceToHost));
-                        if (r != VS_OK) break;
-                        int slot = -1;
-                        for (uint32_t t = 0; t < R && slot < 0; ++t)
-                            if (rown[t] == VS_INVALID_NODE) slot = (int)t;
-                        for (int t = (int)R - 1; t >= 0 && slot < 0; --t) {
-                            const uint32_t y = rown[t];
-                            const uint32_t mine = (reached[y] && level[n0] < level[y]) ? 1u : 0u;  // is n0 -> y one of the counted edges?
-                            if (indeg[y] >= mine + 1u) slot = t;
-                        }
-                        if (slot < 0) continue;
-                        if (rown[slot] != VS_INVALID_NODE && reached[rown[slot]] && level[n0] < level[rown[slot]]) indeg[rown[slot]]--;
-                        rown[slot] = x;
-                        level[x] = level[n0] + 1;
-                        indeg[x]++;
-                        placed = true;
-                        hip_ok(hipMemcpy(ix->nbrs + (size_t)n0 * ix->nbr_stride, rown, (size_t)R * 4, hipMemcpyHostToDevice));
-                    }
-                    if (!placed) continue;
-                    progress = true;
-                    reached[x] = 1;
-                    stack.assign(1, x);
-                    while (!stack.empty()) {  // everything x leads to is reachable now
-                        const uint32_t u = stack.back();
-                        stack.pop_back();
-                        const uint32_t* rowu = &lrows[(size_t)lidx[u] * R];
-                        for (uint32_t t = 0; t < R && rowu[t] != VS_INVALID_NODE; ++t) {
-                            const uint32_t v = rowu[t];
-                            if (!reached[v]) {
-                                reached[v] = 1;
-                                level[v] = level[u] + 1;
-                                indeg[v]++;
-                                stack.push_back(v);
-                            } else if (level[u] < level[v]) {
-                                indeg[v]++;
-                            }
-                        }
-                    }
-                }
-            }
-            VS_TRY(r);
-        }
-    }
+    if (!(rep_env && *rep_env == '0')) VS_TRY(repair_graph(ix, B));
     return VS_OK;
 }
 
@@ -865,3 +1135,406 @@ extern "C" int vs_build_graph(vs_index* ix, uint32_t search_list_size, double ma
     return vs_guard("vs_build_graph", [&] { return vs_build_graph_impl(ix, search_list_size, max_alpha, batch_max, seed); });
 }
 
+// the repair pass on its own: after many inserts, at the caller's choice (an insert only anchors its own rows; what its re-prunes
+// cost older rows is what this sweep over the whole graph finds)
+static int vs_index_repair_impl(vs_index* ix, uint32_t* unreachable) {
+    VS_REQUIRE(ix, "vs_index_repair: index is NULL");
+    VS_REQUIRE_OWNER(ix, "vs_index_repair");
+    VS_REQUIRE_NO_VIEWS(ix, "vs_index_repair");
+    VS_REQUIRE(ix->nbrs, "vs_index_repair: the index has no neighbor lists");
+    VS_HIP(hipSetDevice(ix->ctx->device));
+    ix->build_unreachable = 0;
+    if (ix->d.default_start != VS_INVALID_NODE) {
+        BuildBufs B;
+        ix->nbr_mask_valid = false;
+        int r = repair_graph(ix, B);
+        (void)hipStreamSynchronize(ix->ctx->stream);
+        B.free_all();
+        VS_TRY(r);
+        VS_TRY(vs_validate_graph(ix));
+    }
+    if (unreachable) *unreachable = ix->build_unreachable;
+    return VS_OK;
+}
+extern "C" int vs_index_repair(vs_index* ix, uint32_t* unreachable) {
+    return vs_guard("vs_index_repair", [&] { return vs_index_repair_impl(ix, unreachable); });
+}
+
+// ---- vs_batch_mates: k_batch_mates on its own --------------------------------------------------------------------------
+static int vs_batch_mates_impl(vs_index* ix, const uint64_t* codes, const uint32_t* label_off, const int16_t* label_val, uint32_t n,
+                               uint32_t c, uint32_t* out_ids, uint32_t* out_ham) {
+    VS_REQUIRE(ix && (n == 0 || (codes && out_ids)), "vs_batch_mates: bad args");
+    VS_REQUIRE(c >= 1 && c <= 64, "vs_batch_mates: %u mates per row outside [1,64]", c);
+    if (n == 0) return VS_OK;
+    vs_ctx* ctx = ix->ctx;
+    VS_HIP(hipSetDevice(ctx->device));
+    const uint32_t stride = ix->code_stride;
+    uint64_t* d_codes = nullptr;
+    uint32_t *d_out = nullptr, *d_off = nullptr;  // ids, then Hamming distances; the rows' label sets (filtered form)
+    int16_t* d_val = nullptr;
+    int r = VS_OK;
+    if (label_off) {
+        VS_REQUIRE(label_off[0] == 0, "vs_batch_mates_filtered: label_off[0] must be 0");
+        for (uint32_t i = 0; i < n; ++i) {
+            VS_REQUIRE(label_off[i] <= label_off[i + 1], "vs_batch_mates_filtered: label_off must be non-decreasing");
+            VS_REQUIRE(label_off[i + 1] - label_off[i] <= 64, "vs_batch_mates_filtered: row %u carries more than 64 labels", i);
+            VS_REQUIRE(label_off[i + 1] == label_off[i] || label_val, "vs_batch_mates_filtered: label_val is NULL");
+            for (uint32_t j = label_off[i] + 1; j < label_off[i + 1]; ++j)
+                VS_REQUIRE(label_val[j - 1] < label_val[j], "vs_batch_mates_filtered: row %u: label set must be sorted and de-duplicated", i);
+        }
+    }
+    auto hip_ok = [&](hipError_t e) {
+        if (r == VS_OK && e != hipSuccess) {
+            vs_set_error("vs_batch_mates: %s", hipGetErrorString(e));
+            r = e == hipErrorOutOfMemory ? VS_ERR_OOM : VS_ERR_HIP;
+        }
+    };
+    hip_ok(hipMalloc(&d_codes, (size_t)n * stride * 8));
+    if (r == VS_OK) hip_ok(hipMalloc(&d_out, (size_t)n * c * 8));
+    if (r == VS_OK) r = vs_upload_rows(ctx, d_codes, stride * 8ull, codes, ix->d.words * 8ull, ix->d.words * 8ull, n);
+    if (r == VS_OK && label_off) {
+        hip_ok(hipMalloc(&d_off, ((size_t)n + 1) * 4));
+        if (r == VS_OK) hip_ok(hipMalloc(&d_val, std::max<size_t>(label_off[n], 1) * 2));
+        if (r == VS_OK) r = vs_dev_upload(ctx, d_off, label_off, ((size_t)n + 1) * 4);
+        if (r == VS_OK && label_off[n]) r = vs_dev_upload(ctx, d_val, label_val, (size_t)label_off[n] * 2);
+    }
+    if (r == VS_OK) {
+        hipLaunchKernelGGL(k_batch_mates, dim3((n + 63) / 64), dim3(WAVE), mates_lds_bytes(c), ctx->stream, d_codes, stride, n, c, d_out,
+                           d_out + (size_t)n * c, (const uint32_t*)d_off, (const int16_t*)d_val, 0u);
+        hip_ok(hipGetLastError());
+    }
+    if (r == VS_OK) r = vs_dev_download(ctx, out_ids, d_out, (size_t)n * c * 4);
+    if (r == VS_OK && out_ham) r = vs_dev_download(ctx, out_ham, d_out + (size_t)n * c, (size_t)n * c * 4);
+    if (d_codes) (void)hipFree(d_codes);
+    if (d_out) (void)hipFree(d_out);
+    if (d_off) (void)hipFree(d_off);
+    if (d_val) (void)hipFree(d_val);
+    return r;
+}
+extern "C" int vs_batch_mates(vs_index* ix, const uint64_t* codes, uint32_t n, uint32_t c, uint32_t* out_ids, uint32_t* out_ham) {
+    return vs_guard("vs_batch_mates", [&] { return vs_batch_mates_impl(ix, codes, nullptr, nullptr, n, c, out_ids, out_ham); });
+}
+extern "C" int vs_batch_mates_filtered(vs_index* ix, const uint64_t* codes, const uint32_t* label_off, const int16_t* label_val, uint32_t n,
+                                       uint32_t c, uint32_t* out_ids, uint32_t* out_ham) {
+    return vs_guard("vs_batch_mates_filtered", [&]() -> int {
+        VS_REQUIRE(label_off, "vs_batch_mates_filtered: label_off is NULL");
+        return vs_batch_mates_impl(ix, codes, label_off, label_val, n, c, out_ids, out_ham);
+    });
+}
+
+// ---- vs_index_insert: aminsert (AM/build.rs:464-558) for rows that arrive after the index is resident -----------------------
+// The anchoring rule over the new nodes r0 .. r0 + rn - 1 (k_insert_anchor to its fixed point), then, on the host and in node order
+// (placement is rare), a slot for every node that stayed unanchored in the list of its closest old-or-anchored out-neighbor: a free
+// one, else that of the list's last entry y — but only when y keeps another in-edge among the rows of y's own out-neighbors whose
+// source is old or anchored and is not the row being edited.  The flags are recomputed from nothing after every sweep of placements,
+// so that a node whose anchor was the evicted edge is seen.  *left = nodes still unanchored at the end (reported, never hidden).
+static int anchor_range(BatchRunner& br, uint32_t r0, uint32_t rn, bool count_mates, uint32_t* mate_edges, uint32_t* placed,
+                        uint32_t* left) {
+    vs_index* ix = br.ix;
+    BuildBufs& B = *br.Bp;
+    hipStream_t st = br.st;
+    const uint32_t R = br.R, ns = ix->nbr_stride;
+    uint32_t* d_changed = B.anch + rn;
+    uint32_t* d_mates = B.anch + rn + 1;
+    std::vector<uint32_t> anch(rn), rowx(R), rowy(R), rowz(R), roww(R);
+    auto get_row = [&](uint32_t node, std::vector<uint32_t>& row) -> int {
+        VS_HIP(hipMemcpy(row.data(), ix->nbrs + (size_t)node * ns, (size_t)R * 4, hipMemcpyDeviceToHost));
+        return VS_OK;
+    };
+    *left = 0;
+    for (int sweep = 0; sweep <= 8; ++sweep) {  // (the ninth pass only recomputes: *left is what the final graph shows)
+        VS_HIP(hipMemsetAsync(B.anch, 0, ((size_t)rn + 2) * 4, st));
+        br.tick();
+        for (uint32_t round = 0; round <= rn; ++round) {  // (a round that anchors nobody ends it; rn rounds is the longest chain)
+            uint32_t changed = 0;
+            VS_HIP(hipMemsetAsync(d_changed, 0, 4, st));
+            hipLaunchKernelGGL(k_insert_anchor, dim3(rn), dim3(WAVE), 0, st, ix->nbrs, ns, R, r0, rn, B.anch, d_changed,
+                               (count_mates && sweep == 0 && round == 0) ? d_mates : nullptr);
+            VS_HIP(hipGetLastError());
+            VS_HIP(hipMemcpyAsync(&changed, d_changed, 4, hipMemcpyDeviceToHost, st));
+            VS_HIP(hipStreamSynchronize(st));
+            if (!changed) break;
+        }
+        br.tock(2);
+        VS_HIP(hipMemcpy(anch.data(), B.anch, (size_t)rn * 4, hipMemcpyDeviceToHost));
+        if (count_mates && sweep == 0) {
+            uint32_t m = 0;
+            VS_HIP(hipMemcpy(&m, d_mates, 4, hipMemcpyDeviceToHost));
+            *mate_edges += m;
+        }
+        uint32_t un = 0;
+        for (uint32_t v : anch) un += v == 0;
+        *left = un;
+        if (un == 0 || sweep == 8) return VS_OK;
+        auto solid = [&](uint32_t v) { return v < r0 || (v - r0 < rn && anch[v - r0]); };  // old, or anchored
+        uint32_t done = 0;
+        for (uint32_t b = 0; b < rn; ++b) {
+            if (anch[b]) continue;
+            const uint32_t x = r0 + b;
+            VS_TRY(get_row(x, rowx));
+            bool ok = false;
+            for (uint32_t t = 0; t < R && !ok && rowx[t] != VS_INVALID_NODE; ++t) {  // closest first
+                const uint32_t y = rowx[t];
+                if (!solid(y)) continue;
+                VS_TRY(get_row(y, rowy));
+                int slot = -1;
+                bool named = false;
+                for (uint32_t u = 0; u < R; ++u) {
+                    named |= rowy[u] == x;
+                    if (rowy[u] == VS_INVALID_NODE && slot < 0) slot = (int)u;
+                }
+                if (named) {  // (a placement earlier in this sweep made y solid: x is anchored already)
+                    ok = true;
+                    break;
+                }
+                if (slot < 0) {
+                    const uint32_t z = rowy[R - 1];
+                    VS_TRY(get_row(z, rowz));
+                    bool kept = false;
+                    for (uint32_t u = 0; u < R && !kept && rowz[u] != VS_INVALID_NODE; ++u) {
+                        const uint32_t w = rowz[u];
+                        if (w == y || !solid(w)) continue;
+                        VS_TRY(get_row(w, roww));
+                        for (uint32_t q = 0; q < R && !kept; ++q) kept = roww[q] == z;
+                    }
+                    if (kept) slot = (int)R - 1;
+                }
+                if (slot < 0) continue;
+                rowy[slot] = x;
+                VS_HIP(hipMemcpy(ix->nbrs + (size_t)y * ns, rowy.data(), (size_t)R * 4, hipMemcpyHostToDevice));
+                ok = true;
+                ++*placed;
+                ++done;
+            }
+            if (ok) anch[b] = 1;
+        }
+        if (!done) return VS_OK;  // (nothing more can be placed: *left stands)
+    }
+    return VS_OK;
+}
+
+static int index_insert_impl(vs_index* ix, const float* vectors, bool vectors_on_device, const uint64_t* heap_tids,
+                             const uint32_t* label_off, const int16_t* label_val, uint32_t n_new, uint32_t L, double max_alpha,
+                             uint32_t batch_max, vs_insert_stats* out) {
+    const char* what = "vs_index_insert";
+    VS_REQUIRE(ix, "%s: index is NULL", what);
+    if (out) memset(out, 0, sizeof(*out));
+    VS_REQUIRE_OWNER(ix, what);
+    VS_REQUIRE_NO_VIEWS(ix, what);
+    VS_REQUIRE(ix->d.storage_type == VS_STORAGE_SBQ, "%s: plain storage is not supported (memory_optimized indexes only)", what);
+    VS_REQUIRE(ix->codes && ix->nbrs && ix->tids && ix->vecs, "%s: needs codes, neighbor lists, heap tids and the vector column on the device", what);
+    VS_REQUIRE(n_new == 0 || (vectors && heap_tids), "%s: vectors / heap_tids are NULL", what);
+    VS_REQUIRE(L >= 1 && L <= 1000, "%s: search_list_size outside [1,1000]", what);
+    VS_REQUIRE(max_alpha >= 1.0 && max_alpha <= 5.0, "%s: max_alpha outside [1,5]", what);
+    const uint32_t n_old = ix->d.n;
+    VS_REQUIRE((uint64_t)n_old + n_new < VS_INVALID_NODE, "%s: %u + %u nodes reach the end-of-list sentinel", what, n_old, n_new);
+    const bool labeled = ix->label_off != nullptr;
+    VS_REQUIRE(labeled == (label_off != nullptr), labeled ? "%s: the index is labeled, the rows carry no label sets" : "%s: label sets for an index without labels", what);
+    if (labeled && n_new) {
+        VS_REQUIRE(label_off[0] == 0, "%s: label_off[0] must be 0", what);
+        for (uint32_t i = 0; i < n_new; ++i) {
+            VS_REQUIRE(label_off[i] <= label_off[i + 1], "%s: label_off must be non-decreasing", what);
+            VS_REQUIRE(label_off[i + 1] - label_off[i] <= 64, "%s: row %u carries more than 64 labels", what, i);
+            VS_REQUIRE(label_off[i + 1] == label_off[i] || label_val, "%s: label_val is NULL", what);
+            for (uint32_t j = label_off[i] + 1; j < label_off[i + 1]; ++j)
+                VS_REQUIRE(label_val[j - 1] < label_val[j], "%s: row %u: label set must be sorted and de-duplicated", what, i);
+        }
+        VS_REQUIRE(ix->n_label_vals + label_off[n_new] < (1ull << 32), "%s: more than 2^32 label values", what);
+    }
+    auto state_error = [&](const char* msg) {
+        vs_set_error("%s: %s", what, msg);
+        return VS_ERR_STATE;
+    };
+    if (ix->count == 0) return state_error("the quantizer is untrained (vs_sbq_train / vs_index_set_quantizer first; an insert never trains)");
+    if (ix->ws.pending) return state_error("a batch of this handle is in flight (vs_search_batch_dev_finish first)");
+    if (ix->visible && ix->visible != ix->visible_own) {
+        bool ours = false;
+        for (const uint8_t* sp : ix->snap) ours |= sp == ix->visible;
+        if (!ours) return state_error("a caller-owned device visibility mask is in force and cannot be grown by the library (clear or replace it)");
+    }
+    if (n_new == 0) {
+        if (out) out->first_node = n_old;
+        return VS_OK;
+    }
+    vs_ctx* c = ix->ctx;
+    hipStream_t st = c->stream;
+    VS_HIP(hipSetDevice(c->device));
+    const uint32_t n = n_old + n_new;
+    uint32_t grew = 0;
+    if (n > ix->capacity) {  // geometric growth, at least to fit
+        const uint64_t want = std::max<uint64_t>(n, (uint64_t)ix->capacity + ix->capacity / 2);
+        VS_TRY(vs_index_reserve_impl(ix, (uint32_t)std::min<uint64_t>(want, VS_INVALID_NODE - 1), what));
+        grew = 1;
+    }
+    // the label CSR of the grown set (the only array that is not sized by rows): built aside, swapped in when everything else is staged
+    int16_t* new_val = nullptr;
+    const uint64_t old_vals = ix->n_label_vals, add_vals = labeled ? label_off[n_new] : 0;
+    if (labeled && add_vals) {
+        VS_HIP(hipMalloc(&new_val, (old_vals + add_vals) * 2));
+        int r = VS_OK;
+        if (old_vals && hipMemcpyAsync(new_val, ix->label_val, old_vals * 2, hipMemcpyDeviceToDevice, st) != hipSuccess) r = VS_ERR_HIP;
+        if (r == VS_OK && hipStreamSynchronize(st) != hipSuccess) r = VS_ERR_HIP;
+        if (r == VS_OK) r = vs_dev_upload(c, new_val + old_vals, label_val, add_vals * 2);
+        if (r != VS_OK) {
+            (void)hipFree(new_val);
+            if (r == VS_ERR_HIP) vs_set_error("%s: staging the label sets failed", what);
+            return r;
+        }
+    }
+    // stage the rows: vectors (device rows are vec_stride floats, zero padded), heap tids, empty neighbor lists, visibility
+    if (vectors_on_device) {
+        VS_HIP(hipMemsetAsync(ix->vecs + (size_t)n_old * ix->vec_stride, 0, (size_t)n_new * ix->vec_stride * 4, st));
+        VS_HIP(hipMemcpy2DAsync(ix->vecs + (size_t)n_old * ix->vec_stride, ix->vec_stride * 4ull, vectors, ix->d.dim_full * 4ull,
+                                ix->d.dim_full * 4ull, n_new, hipMemcpyDeviceToDevice, st));
+    } else {
+        VS_TRY(vs_upload_rows(c, ix->vecs + (size_t)n_old * ix->vec_stride, ix->vec_stride * 4ull, vectors, ix->d.dim_full * 4ull,
+                              ix->d.dim_full * 4ull, n_new));
+    }
+    VS_TRY(vs_dev_upload(c, ix->tids + n_old, heap_tids, (size_t)n_new * 8));
+    VS_HIP(hipMemsetAsync(ix->nbrs + (size_t)n_old * ix->nbr_stride, 0xFF, (size_t)n_new * ix->nbr_stride * 4, st));
+    // a new tuple is visible to the library's own mask and to no snapshot that was stored before it existed
+    if (ix->visible_own) VS_HIP(hipMemsetAsync(ix->visible_own + n_old, 1, n_new, st));
+    for (int sn = 1; sn < VS_MAX_SNAPSHOTS; ++sn)
+        if (ix->snap[sn]) VS_HIP(hipMemsetAsync(ix->snap[sn] + n_old, 0, n_new, st));
+    // norms and codes of the new rows only, with the quantizer as it stands (preprocess_cosine rule of vs_index_refresh_norms)
+    VS_TRY(launch_row_norms_range(ix, n_old, n_new));
+    VS_TRY(vs_quantize_row_range(ix, n_old, n_new));
+    if (labeled) {
+        std::vector<uint32_t> off(n_new);
+        for (uint32_t i = 0; i < n_new; ++i) off[i] = (uint32_t)(old_vals + label_off[i + 1]);
+        if (n_old == 0) {
+            const uint32_t zero = 0;
+            VS_HIP(hipMemcpy(ix->label_off, &zero, 4, hipMemcpyHostToDevice));
+        }
+        VS_TRY(vs_dev_upload(c, ix->label_off + n_old + 1, off.data(), (size_t)n_new * 4));
+        if (new_val) {
+            VS_HIP(hipStreamSynchronize(st));
+            if (ix->label_val) (void)hipFree(ix->label_val);
+            ix->label_val = new_val;
+            ix->n_label_vals = old_vals + add_vals;
+        }
+    }
+    ix->d.n = n;
+    // what was derived from the old row count is stale: the label masks (re-derived now), the neighbor masks (dropped, re-derived
+    // lazily at the new size), what the launch planner remembered of the last batches
+    if (ix->nbr_mask) {
+        VS_HIP(hipStreamSynchronize(st));
+        (void)hipFree(ix->nbr_mask);
+        ix->nbr_mask = nullptr;
+    }
+    ix->nbr_mask_valid = false;
+    ix->nbr_mask_tried = false;
+    ix->obs = ScanObs{};
+    ix->last_fast = FastSig{};
+    ix->last_ins_limit = 0;
+    if (labeled) VS_TRY(vs_refresh_label_masks(ix));
+    bool new_label = false;  // the call brings a label no older row carries
+    // start nodes (update_start_nodes, AM/graph/mod.rs:490-531): an empty index gets node 0 as the default start; a label that an
+    // inserted node is the first to carry gets that node
+    {
+        std::map<int16_t, uint32_t> starts;
+        const uint32_t ns0 = ix->d.n_label_starts;
+        if (ns0) {
+            std::vector<int16_t> sl(ns0);
+            std::vector<uint32_t> sn(ns0);
+            VS_HIP(hipMemcpy(sl.data(), ix->ls_labels, (size_t)ns0 * 2, hipMemcpyDeviceToHost));
+            VS_HIP(hipMemcpy(sn.data(), ix->ls_nodes, (size_t)ns0 * 4, hipMemcpyDeviceToHost));
+            for (uint32_t i = 0; i < ns0; ++i) starts.emplace(sl[i], sn[i]);
+        }
+        bool changed = ix->d.default_start == VS_INVALID_NODE;
+        const size_t labels_before = starts.size();
+        if (labeled)
+            for (uint32_t i = 0; i < n_new; ++i)
+                for (uint32_t j = label_off[i]; j < label_off[i + 1]; ++j) changed |= starts.emplace(label_val[j], n_old + i).second;
+        new_label = starts.size() != labels_before;
+        if (changed) {
+            std::vector<int16_t> sl;
+            std::vector<uint32_t> sn;
+            for (const auto& kv : starts) {
+                sl.push_back(kv.first);
+                sn.push_back(kv.second);
+            }
+            VS_TRY(vs_index_set_start_nodes(ix, ix->d.default_start == VS_INVALID_NODE ? 0u : ix->d.default_start, sl.data(), sn.data(),
+                                            (uint32_t)sl.size()));
+        }
+    }
+    vs_insert_stats s{};
+    s.first_node = n_old;
+    s.inserted = n_new;
+    s.grew = grew;
+    BuildBufs B;
+    BatchRunner br;
+    int r = VS_OK;
+    do {
+        // (the buffers are sized by the batch: a one-row call must not allocate what a 65 536-row batch needs)
+        if (batch_max == 0) batch_max = std::min<uint32_t>(65536, std::max<uint32_t>(1024, n / 64));
+        batch_max = std::max(1u, std::min(std::min<uint32_t>(batch_max, 65536), n_new));
+        if ((r = br.init(ix, B, L, (float)max_alpha, batch_max, n))) break;
+        br.mates = std::min<uint32_t>(env_u32("VS_INSERT_MATES", 16), 64);
+        const uint32_t bm = std::min(br.batch_max, n_new);
+        hipError_t e = hipSuccess;
+        if (br.mates) e = hipMalloc(&B.mate_ids, (size_t)bm * br.mates * 4);
+        if (e == hipSuccess && br.mates) e = hipMalloc(&B.mate_ham, (size_t)bm * br.mates * 4);
+        if (e == hipSuccess) e = hipMalloc(&B.anch, ((size_t)n_new + 2) * 4);
+        if (e == hipSuccess && c->profiling) {
+            e = hipEventCreate(&br.ev[0]);
+            if (e == hipSuccess) e = hipEventCreate(&br.ev[1]);
+        }
+        if (e != hipSuccess) {
+            vs_set_error("%s: %s", what, hipGetErrorString(e));
+            r = e == hipErrorOutOfMemory ? VS_ERR_OOM : VS_ERR_HIP;
+            break;
+        }
+        // batches as in vs_build_graph: none is larger than the graph it searches (node 0 of an empty index has no one to link to)
+        // For a label the call is the first to bring, the graph under that label's filter IS empty: the batches then double from one
+        // row, as vs_build_graph's do, so that the label's carriers find the ones before them.
+        uint32_t b0 = std::max(n_old, 1u), bsz = new_label ? 1u : br.batch_max;
+        while (b0 < n && r == VS_OK) {
+            const uint32_t bn = std::min(std::min(std::min(br.batch_max, bsz), b0), n - b0);
+            if (bsz < br.batch_max) bsz = std::min(br.batch_max, bsz * 2);
+            if (labeled) r = br.run(b0, bn, true, true);  // Graph::insert: first with the label filter (mates: the batch's rows it admits) ...
+            if (r == VS_OK) r = br.run(b0, bn, false, true);  // ... then from the default start node, the batch's mates among the candidates
+            uint32_t left = 0;
+            if (r == VS_OK) r = anchor_range(br, b0, bn, true, &s.mate_edges, &s.orphans_placed, &left);
+            s.orphans_left = left;
+            s.batches++;
+            b0 += bn;
+        }
+        if (r != VS_OK) break;
+        // later batches re-prune rows that anchored the earlier ones: the rule once more over every row of the call, against the graph
+        // as it was before the call
+        // (node 0 of an index that was empty is the entry point itself)
+        if (s.batches > 1) r = anchor_range(br, std::max(n_old, 1u), n - std::max(n_old, 1u), false, &s.mate_edges, &s.orphans_placed, &s.orphans_left);
+    } while (0);
+    (void)hipStreamSynchronize(st);
+    s.retries = br.retries;
+    if (br.ev[0]) (void)hipEventDestroy(br.ev[0]);
+    if (br.ev[1]) (void)hipEventDestroy(br.ev[1]);
+    B.free_all();
+    if (r == VS_OK) r = vs_validate_graph(ix);
+    for (int k = 0; k < 3; ++k) ix->insert_ms[k] += br.ms[k];
+    if (out) *out = s;
+    return r;
+}
+extern "C" int vs_index_insert(vs_index* ix, const float* vectors, const uint64_t* heap_tids, const uint32_t* label_off,
+                               const int16_t* label_val, uint32_t n_new, uint32_t search_list_size, double max_alpha, uint32_t batch_max,
+                               vs_insert_stats* out) {
+    return vs_guard("vs_index_insert", [&] {
+        return index_insert_impl(ix, vectors, false, heap_tids, label_off, label_val, n_new, search_list_size, max_alpha, batch_max, out);
+    });
+}
+extern "C" int vs_index_insert_dev(vs_index* ix, const float* d_vectors, const uint64_t* heap_tids, const uint32_t* label_off,
+                                   const int16_t* label_val, uint32_t n_new, uint32_t search_list_size, double max_alpha,
+                                   uint32_t batch_max, vs_insert_stats* out) {
+    return vs_guard("vs_index_insert", [&] {
+        return index_insert_impl(ix, d_vectors, true, heap_tids, label_off, label_val, n_new, search_list_size, max_alpha, batch_max, out);
+    });
+}
+extern "C" int vs_index_insert_kernel_ms(vs_index* ix, double* ms /*[3]*/, int reset) {
+    VS_REQUIRE(ix && ms, "vs_index_insert_kernel_ms: bad args");
+    for (int k = 0; k < 3; ++k) {
+        ms[k] = ix->insert_ms[k];
+        if (reset) ix->insert_ms[k] = 0;
+    }
+    return VS_OK;
+}

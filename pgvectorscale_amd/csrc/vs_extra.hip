@@ -337,6 +337,34 @@ extern "C" int vs_sbq_quantize_corpus(vs_index* ix) {
     return VS_OK;
 }
 
+// the same for rows [row_begin, row_begin + rows) only, with the quantizer as it stands (vs_index_insert: the reference's aminsert
+// loads the trained quantizer and never updates it, SbqSpeedupStorage::load_for_insert).  The cosine divisors of the rows are
+// taken from vnorm (the caller refreshed that range) or, for an index slice, computed here.
+int vs_quantize_row_range(vs_index* ix, uint32_t row_begin, uint32_t rows) {
+    if (rows == 0) return VS_OK;
+    const float* vecs = ix->vecs + (size_t)row_begin * ix->vec_stride;
+    float* rn = nullptr;
+    bool owned = false;
+    if (ix->d.distance_type == VS_COSINE) {
+        if (ix->d.dim_index == ix->d.dim_full) {
+            rn = ix->vnorm + row_begin;
+        } else {
+            VS_HIP(hipMalloc(&rn, (size_t)rows * 4));
+            owned = true;
+            hipLaunchKernelGGL(k_slice_norms, dim3(std::min<uint32_t>((rows + 63) / 64, 8192)), dim3(WAVE), 0, ix->ctx->stream, vecs,
+                               ix->vec_stride, ix->d.dim_index, rows, rn);
+        }
+    }
+    hipLaunchKernelGGL(k_quantize_corpus, dim3(std::min<uint32_t>(rows, 1u << 20)), dim3(WAVE), 0, ix->ctx->stream, vecs, ix->vec_stride,
+                       rows, ix->d.dim_index, ix->d.bits, rn, ix->mean, ix->m2, (float)ix->count, ix->d.words, ix->code_stride,
+                       ix->codes + (size_t)row_begin * ix->code_stride);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(ix->ctx->stream);
+    if (owned) (void)hipFree(rn);
+    VS_HIP(e);
+    return VS_OK;
+}
+
 // ===============================================================================================================
 // K5 host entry: flat SBQ scan (kernels in vs_scan.hip)
 // ===============================================================================================================

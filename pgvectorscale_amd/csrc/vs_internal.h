@@ -190,12 +190,14 @@ struct vs_index {
     uint64_t owner_id = 0;        // key of the owner in the registry of live views (unique per vs_index_alloc / replica, never reused)
     WsSlab* slab = nullptr;       // shared by an index and its views (reference counted)
     vs_index_desc d{};
+    uint32_t capacity = 0;     // rows the per-node arrays have room for (>= d.n; vs_index_reserve / vs_index_insert grow it)
     uint32_t code_stride = 0;  // u64 words per code row (W rounded up to even, zero padded)
     uint32_t nbr_stride = 0;   // u32 per neighbor row (R rounded up to 16)
     uint32_t vec_stride = 0;   // floats per vector row (dim_full rounded up to 4)
     uint64_t* codes = nullptr;
     uint32_t* nbrs = nullptr;
     uint64_t* tids = nullptr;
+    double insert_ms[3] = {0, 0, 0};   // HIP-event time of k_batch_mates / k_insert_merge_mates / k_insert_anchor (vs_profile_enable; vs_index_insert_kernel_ms)
     uint32_t build_unreachable = 0;    // nodes the last vs_build_graph left unreachable from the start node (0xFFFFFFFF: not judged)
     const uint8_t* visible = nullptr;  // per node, 0 = the heap fetch finds nothing under the scan's snapshot (nullptr: all visible)
     uint8_t* visible_own = nullptr;    // the library's own copy (vs_index_set_visibility)
@@ -242,6 +244,25 @@ uint64_t vs_new_owner_id();
 WsSlab* vs_slab_new(int device);
 void vs_slab_release(WsSlab* s);
 int vs_index_live_views(vs_index* ix);  // views made of ix that have not been freed yet
+// the entry points that free or move the arrays of an index refuse view handles and owners with live views
+#define VS_REQUIRE_OWNER(ix, what)                                                                                                     \
+    do {                                                                                                                                \
+        if ((ix)->is_view) {                                                                                                            \
+            vs_set_error("%s: this handle is a view; the arrays belong to the index it was made from", what);                         \
+            return VS_ERR_STATE;                                                                                                        \
+        }                                                                                                                               \
+    } while (0)
+#define VS_REQUIRE_NO_VIEWS(ix, what)                                                                                                  \
+    do {                                                                                                                                \
+        const int _nv = vs_index_live_views(ix);                                                                                        \
+        if (_nv > 0) {                                                                                                                  \
+            vs_set_error("%s: %d view(s) of this index are alive (cursor lanes, a second stream, a vs_multi shard) and hold its device " \
+                         "pointers; free them first",                                                                                  \
+                         what, _nv);                                                                                                    \
+            return VS_ERR_STATE;                                                                                                        \
+        }                                                                                                                               \
+    } while (0)
+int vs_index_reserve_impl(vs_index* ix, uint32_t capacity, const char* what);  // vs_api.hip: arrays may move
 // row-wise staging through the pinned ring (device rows may be wider than host rows) / neighbor-list validation
 int vs_upload_rows(vs_ctx* c, void* dst, size_t dev_row_bytes, const void* src, size_t host_row_bytes, size_t copy_bytes, size_t rows);
 int vs_validate_graph(vs_index* ix);
@@ -423,6 +444,8 @@ int launch_resort_cursor_batch(vs_index* idx, uint32_t n, const uint32_t* d_list
 int launch_pool_append(vs_index* idx, uint32_t nq, const uint32_t* d_cnt, const uint32_t* d_off, const uint32_t* d_stage, uint32_t stage_kind_stride, uint32_t M,
                        uint32_t* d_all, uint32_t all_kind_stride, uint32_t rows_cap);
 int launch_row_norms(vs_index* idx);
+int launch_row_norms_range(vs_index* idx, uint32_t row_begin, uint32_t rows);  // the same for rows [row_begin, row_begin + rows)
+int vs_quantize_row_range(vs_index* ix, uint32_t row_begin, uint32_t rows);     // vs_extra.hip: vs_sbq_quantize_corpus over a row range
 int launch_slice_norms(vs_index* idx, float* d_out);  // divisor of the first dim_index dims of every heap vector
 int launch_prepare_index_slice(vs_index* idx, const float* d_raw, uint32_t nq, float* d_q_index);
 int launch_validate_nbrs(vs_index* idx, uint32_t* d_flag);

@@ -1257,6 +1257,15 @@ int launch_row_norms(vs_index* idx) {
     return VS_OK;
 }
 
+int launch_row_norms_range(vs_index* idx, uint32_t row_begin, uint32_t rows) {
+    if (!idx->vecs || rows == 0) return VS_OK;
+    const uint32_t blocks = (rows + 63) / 64 > 8192 ? 8192 : (rows + 63) / 64;
+    hipLaunchKernelGGL(k_row_norms, dim3(blocks), dim3(WAVE), 0, idx->ctx->stream, idx->vecs + (size_t)row_begin * idx->vec_stride,
+                       idx->vec_stride, idx->d.dim_full, rows, idx->vnorm + row_begin);
+    VS_HIP(hipGetLastError());
+    return VS_OK;
+}
+
 int launch_validate_nbrs(vs_index* idx, uint32_t* d_flag) {
     if (idx->d.n == 0) return VS_OK;
     hipLaunchKernelGGL(k_validate_nbrs, dim3((idx->d.n + 255) / 256), dim3(256), 0, idx->ctx->stream, idx->nbrs,

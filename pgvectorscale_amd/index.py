@@ -305,6 +305,66 @@ class DiskAnnIndex:
         """nodes the last build_graph left unreachable from the default start node (0 on well-formed input)"""
         return int(self._L.vs_index_build_unreachable(self.h))
 
+    # -- rows that arrive later (aminsert) -------------------------------------------------------------------------------
+    def reserve(self, capacity):
+        """room for `capacity` nodes in every per-node array (vs_index_reserve); the arrays may move"""
+        check(self._L.vs_index_reserve(self.h, capacity))
+
+    @property
+    def capacity(self):
+        return int(self._L.vs_index_capacity(self.h))
+
+    def insert(self, vectors, heap_tids, labels=None, search_list_size=100, max_alpha=1.2, batch_max=0):
+        """aminsert for a batch of rows (vs_index_insert): they become nodes n .. n + len - 1 in input order, quantised with the
+        quantizer as it stands and linked into the graph.  labels: one label list per row (a labeled index) or None.
+        -> dict of vs_insert_stats (first_node, inserted, batches, retries, mate_edges, orphans_placed, orphans_left, grew)"""
+        v = np.ascontiguousarray(vectors, np.float32).reshape(-1, self.desc.dim_full)
+        t = None if heap_tids is None else np.ascontiguousarray(heap_tids, np.uint64)
+        if t is not None and t.shape != (v.shape[0],):
+            raise ValueError(f"heap_tids must have shape ({v.shape[0]},), got {t.shape}")
+        lo = lv = None
+        if labels is not None:
+            if len(labels) != v.shape[0]:
+                raise ValueError("one label list per row")
+            lo = np.zeros(v.shape[0] + 1, np.uint32)
+            vals = []
+            for i, l in enumerate(labels):
+                vals.extend(int(x) for x in l)
+                lo[i + 1] = len(vals)
+            lv = np.array(vals, np.int16)
+        st = _lib.InsertStats()
+        try:
+            check(self._L.vs_index_insert(self.h, _p(v), _p(t), _p(lo), _p(lv), v.shape[0], search_list_size, max_alpha, batch_max,
+                                          C.byref(st)))
+        finally:
+            self._refresh()
+        return st.as_dict()
+
+    def insert_kernel_ms(self, reset=True):
+        """HIP-event milliseconds of the three insert kernels since the last reset (Context.profile_enable first)"""
+        ms = (C.c_double * 3)()
+        check(self._L.vs_index_insert_kernel_ms(self.h, ms, int(reset)))
+        return {"batch_mates": float(ms[0]), "merge_mates": float(ms[1]), "anchor": float(ms[2])}
+
+    def batch_mates(self, codes, c=16, labels=None):
+        """for every row of codes [n][words] the c nearest other rows by (Hamming, row): (ids, hamming), VS_INVALID_NODE padded.
+        labels (one sorted label list per row): only rows whose label sets overlap are mates (vs_batch_mates_filtered)"""
+        codes = np.ascontiguousarray(codes, np.uint64).reshape(-1, self.desc.words)
+        ids = np.empty((codes.shape[0], c), np.uint32)
+        ham = np.empty((codes.shape[0], c), np.uint32)
+        if labels is None:
+            check(self._L.vs_batch_mates(self.h, _p(codes), codes.shape[0], c, _p(ids), _p(ham)))
+            return ids, ham
+        lv, lo = self._label_keys(labels, codes.shape[0])
+        check(self._L.vs_batch_mates_filtered(self.h, _p(codes), _p(lo), _p(lv), codes.shape[0], c, _p(ids), _p(ham)))
+        return ids, ham
+
+    def repair(self):
+        """the repair pass of build_graph on its own (vs_index_repair) -> nodes still unreachable from the default start node"""
+        u = C.c_uint32(0)
+        check(self._L.vs_index_repair(self.h, C.byref(u)))
+        return int(u.value)
+
     def write_pages(self, **kw):
         """the index as the bytes of a `diskann` index relation (pages.PagesOut in one call; keyword arguments as PagesOut's)"""
         from .pages import PagesOut
