@@ -224,6 +224,25 @@ int vs_index_download(const vs_index* idx, uint64_t* codes, uint32_t* nbrs /*[n]
 int vs_index_refresh_norms(vs_index* idx);
 /* mark heap tuples deleted (what ambulkdelete does to heap_item_pointer, AM/vacuum.rs:24-78) */
 int vs_index_mark_deleted(vs_index* idx, const uint32_t* nodes, uint32_t n);
+/* ambulkdelete by heap TID (bulk_delete_for_storage, AM/vacuum.rs:80-136: every live node's heap_item_pointer is put to the
+ * callback, a dead one has its pointer invalidated and the page is committed only `if modified`).  dead_tids: host array of
+ * (block << 16) | offset, unsorted, duplicates allowed; an entry with offset 0 (InvalidOffsetNumber) is VS_ERR_INVALID and
+ * nothing is changed.  The library stages the array through the pinned ring and sorts it on the device; the _dev form takes a
+ * device array that is already sorted ascending and de-duplicated.  One kernel over the TID column on the context's stream:
+ * a node whose offset is 0 already is skipped (is_deleted(), :112), a binary search in the dead set decides for the others, a
+ * hit clears the low 16 bits — exactly what vs_index_mark_deleted writes.  The block number STAYS (the reference invalidates
+ * it too, ItemPointerSetInvalid; here the pages written by vs_pages_out_* keep it, and is_deleted() only looks at the offset).
+ * The call is ordered on the context's stream after whatever that stream has in flight and synchronises only to hand back the
+ * three counters; VS_ERR_STATE while a batch of this handle is in flight (vs_search_batch_dev_finish first).  SBQ and plain
+ * storage alike: only the heap tids are touched.  The library's visibility masks are left alone: the scans drop a deleted
+ * node by the rule of AM/scan.rs:231-234 already. */
+typedef struct vs_bulk_delete_stats { /* IndexBulkDeleteResult, AM/vacuum.rs:122-129 */
+    uint64_t tuples_removed;          /* live nodes whose heap TID was in the dead set: marked now    */
+    uint64_t num_index_tuples;        /* live nodes that stay                                          */
+    uint64_t already_deleted;         /* nodes skipped because is_deleted() (counted in neither, :112) */
+} vs_bulk_delete_stats;
+int vs_index_bulk_delete(vs_index* idx, const uint64_t* dead_tids, uint64_t n_dead, vs_bulk_delete_stats* out /* may be NULL */);
+int vs_index_bulk_delete_dev(vs_index* idx, const uint64_t* d_dead_tids_sorted, uint64_t n_dead, vs_bulk_delete_stats* out);
 
 /* ---- index relation pages -> vs_index_host (the exporter the arrays above come from) ------
  * The reference reaches a node through the buffer manager, one page pin per neighbor (ItemPointer::read_bytes,
@@ -428,6 +447,41 @@ int vs_pages_out_read(vs_pages_out* w, uint32_t first_block, uint32_t n_blocks, 
 int vs_pages_out_read_dev(vs_pages_out* w, uint32_t first_block, uint32_t n_blocks, void* d_pages);
 int vs_pages_out_item_pointer_of(const vs_pages_out* w, uint32_t node, uint32_t* block, uint32_t* offset);
 void vs_pages_out_close(vs_pages_out* w);
+/* ---- page by page: only the blocks an insert or a vacuum changed are written back.  The reference persists that way at every
+ * point: bulk_delete_for_storage commits a page only `if modified` (AM/vacuum.rs:80-136), aminsert dirties the pages of the new
+ * node and of the nodes whose neighbor lists it rewrote (AM/build.rs:464-558).  A BASELINE records what the relation looked like
+ * when it was last written: n_blocks, one 128-bit digest per node page (16 bytes per block, kept in device memory) and verbatim
+ * copies of the few pages the host encodes (Meta chain, SbqMeans chain).  The digest is taken over the BYTES OF THE FINISHED
+ * PAGE — the digest pass is k_pages_encode composing the page in LDS with the digest as its tail instead of the 8 KB of stores —
+ * so it cannot miss a way a page changes: neighbor ItemPointers that moved because other nodes did, page breaks that moved
+ * because an earlier label set grew, vs_index_insert's back-pointers, vs_index_repair, vs_index_set_labels, a rebuild.  It reads
+ * what an encode reads and writes 16 bytes per page.  The function is in DESIGN.md section 6; the odds that a changed page keeps
+ * its digest are 2^-128 per changed page for changes that were not made to collide (it is not a cryptographic hash).
+ * A baseline belongs to the device of the writer's context, not to the writer or the index: it survives vs_pages_out_close,
+ * vs_index_insert moving every array, vs_index_reserve and vs_index_free; vs_pages_base_free releases it.
+ * Out of scope: a baseline of pages something else wrote (the relation files an index was staged from carry pd_lsn, checksums
+ * and the reference's own page fill).  A baseline describes a relation THIS writer produced; a writer opened with other
+ * vs_pages_out_params simply finds every page changed, which is correct, not an error. */
+typedef struct vs_pages_base vs_pages_base;
+/* digests of the relation exactly as `w` would write it now: one digest-pass launch + copies of the host-encoded pages */
+int vs_pages_out_baseline(vs_pages_out* w, vs_pages_base** out);
+void vs_pages_base_free(vs_pages_base* b);
+uint32_t vs_pages_base_blocks(const vs_pages_base* b);
+/* the blocks of w's relation that are not, byte for byte, what `base` recorded: every block >= base's n_blocks, every block whose
+ * digest (node pages) or bytes (host-encoded pages) differ, every block whose kind changed (node page <-> host-encoded page).
+ * Ascending (the list is compacted on the device by a prefix scan, not by an atomic counter).  *n_dirty = how many; the list
+ * stays with the writer until the next delta call or vs_pages_out_close (vs_pages_out_delta_blocks copies it out; cap < *n_dirty
+ * is VS_ERR_INVALID).  new_base (may be NULL) receives the baseline of the relation as it is NOW — the pass has computed every
+ * digest anyway — so a caller advances without a second pass.  A relation that got shorter is legal: *n_blocks_now (may be NULL)
+ * tells the caller where to truncate. */
+int vs_pages_out_delta(vs_pages_out* w, const vs_pages_base* base, uint32_t* n_dirty, uint32_t* n_blocks_now, vs_pages_base** new_base);
+int vs_pages_out_delta_blocks(const vs_pages_out* w, uint32_t* blocks, uint32_t cap);
+/* the gathered form of vs_pages_out_read / _read_dev: pages[i] = block blocks[i]; any list, any order, repeats allowed.  The node
+ * pages go through the same double-buffered pinned ring, chunks cut from the list (k_pages_encode takes its pages from an indirect
+ * list); host-encoded pages are served from the layout.  A block >= n_blocks anywhere in the list is VS_ERR_INVALID and nothing is
+ * written. */
+int vs_pages_out_read_blocks(vs_pages_out* w, const uint32_t* blocks, uint32_t n, void* pages);
+int vs_pages_out_read_blocks_dev(vs_pages_out* w, const uint32_t* blocks, uint32_t n, void* d_pages);
 /* rkyv::to_bytes::<MetaPage> (host-only; the counterpart of vs_meta_page_decode): the labeled start nodes in key order,
  * written as the archived B-tree when meta->has_start_nodes; meta->n_labeled_start_nodes is ignored in favour of n_starts.
  * *len = bytes needed; buf may be NULL to query it; a buf of cap < *len is an error and nothing is written. */

@@ -122,6 +122,13 @@ class InsertStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class BulkDeleteStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("tuples_removed", "num_index_tuples", "already_deleted")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class DatagenParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("dim", C.c_uint32), ("latent_dim", C.c_uint32), ("n_clusters", C.c_uint32),
                 ("intra_pct", C.c_uint32), ("noise_pct", C.c_uint32), ("normalize", C.c_uint32)]
@@ -174,6 +181,8 @@ SYMBOLS = {
     "vs_index_download": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32]),
     "vs_index_refresh_norms": (_i, [_vp]),
     "vs_index_mark_deleted": (_i, [_vp, _vp, _u32]),
+    "vs_index_bulk_delete": (_i, [_vp, _vp, _u64, C.POINTER(BulkDeleteStats)]),
+    "vs_index_bulk_delete_dev": (_i, [_vp, _vp, _u64, C.POINTER(BulkDeleteStats)]),
     "vs_node_layout_default": (_i, [_i, C.POINTER(NodeLayout)]),
     "vs_pages_open": (_i, [_u32, _i, C.POINTER(NodeLayout), _u32, C.POINTER(_vp)]),
     "vs_pages_open_plain": (_i, [_u32, C.POINTER(NodeLayout), _u32, C.POINTER(_vp)]),
@@ -208,6 +217,13 @@ SYMBOLS = {
     "vs_pages_out_read_dev": (_i, [_vp, _u32, _u32, _vp]),
     "vs_pages_out_item_pointer_of": (_i, [_vp, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
     "vs_pages_out_close": (None, [_vp]),
+    "vs_pages_out_baseline": (_i, [_vp, C.POINTER(_vp)]),
+    "vs_pages_base_free": (None, [_vp]),
+    "vs_pages_base_blocks": (_u32, [_vp]),
+    "vs_pages_out_delta": (_i, [_vp, _vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_vp)]),
+    "vs_pages_out_delta_blocks": (_i, [_vp, _vp, _u32]),
+    "vs_pages_out_read_blocks": (_i, [_vp, _vp, _u32, _vp]),
+    "vs_pages_out_read_blocks_dev": (_i, [_vp, _vp, _u32, _vp]),
     "vs_meta_page_encode": (_i, [C.POINTER(MetaPage), _vp, _vp, _vp, _u32, C.POINTER(MetaLayout), _vp, _sz, C.POINTER(_sz)]),
     "vs_quantize": (_i, [_vp, _vp, _u32, _vp]),
     "vs_hamming_gather": (_i, [_vp, _vp, _vp, _vp, _u32, _vp]),

@@ -1538,3 +1538,116 @@ extern "C" int vs_index_insert_kernel_ms(vs_index* ix, double* ms /*[3]*/, int r
     }
     return VS_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// ambulkdelete by heap TID (AM/vacuum.rs:80-136): bulk_delete_for_storage walks the node pages and asks the callback about every
+// live node's heap_item_pointer; here the dead TIDs are one sorted array and every node looks itself up.  One kernel over the TID
+// column on the context's stream: a node whose offset is InvalidOffsetNumber already is skipped (is_deleted(), :112), a binary
+// search in the dead set decides for the others, a hit clears the offset — what vs_index_mark_deleted writes.  The three counters
+// of IndexBulkDeleteResult are ballots summed per wave and leave as one atomic per wave and counter.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_bulk_delete(uint64_t* __restrict__ tids, uint32_t n, const uint64_t* __restrict__ dead, uint64_t n_dead,
+                                                     unsigned long long* __restrict__ counters) {
+    const uint32_t lane = threadIdx.x & (WAVE - 1);
+    const uint64_t wave = ((uint64_t)blockIdx.x * 256 + threadIdx.x) / WAVE, n_waves = (uint64_t)gridDim.x * (256 / WAVE);
+    uint32_t removed = 0, stay = 0, already = 0;
+    for (uint64_t i0 = wave * WAVE; i0 < n; i0 += n_waves * WAVE) {  // (wave-uniform trip count: the ballots below see every lane)
+        const uint64_t i = i0 + lane;
+        bool hit = false, live = false, gone = false;
+        if (i < n) {
+            const uint64_t t = tids[i];
+            if ((t & 0xFFFFull) == 0) {
+                gone = true;
+            } else {
+                uint64_t lo = 0, hi = n_dead;
+                while (lo < hi) {
+                    const uint64_t mid = lo + ((hi - lo) >> 1);
+                    if (dead[mid] < t) lo = mid + 1;
+                    else hi = mid;
+                }
+                hit = lo < n_dead && dead[lo] == t;
+                live = !hit;
+                if (hit) tids[i] = t & ~0xFFFFull;  // heap_item_pointer.offset = InvalidOffsetNumber
+            }
+        }
+        removed += (uint32_t)__popcll(__ballot(hit));
+        stay += (uint32_t)__popcll(__ballot(live));
+        already += (uint32_t)__popcll(__ballot(gone));
+    }
+    if (lane == 0) {
+        if (removed) atomicAdd(&counters[0], (unsigned long long)removed);
+        if (stay) atomicAdd(&counters[1], (unsigned long long)stay);
+        if (already) atomicAdd(&counters[2], (unsigned long long)already);
+    }
+}
+
+static int bulk_delete_impl(vs_index* ix, const char* what, const uint64_t* dead, uint64_t n_dead, bool on_device, vs_bulk_delete_stats* out) {
+    VS_REQUIRE(ix, "%s: index is NULL", what);
+    if (out) memset(out, 0, sizeof(*out));
+    VS_REQUIRE(n_dead == 0 || dead, "%s: dead_tids is NULL", what);
+    VS_REQUIRE(n_dead <= 0x7FFFFFFFull, "%s: %llu dead tids in one call (at most 2^31 - 1)", what, (unsigned long long)n_dead);
+    VS_REQUIRE(ix->tids || ix->d.n == 0, "%s: the index holds no heap tids", what);
+    if (!on_device)
+        for (uint64_t i = 0; i < n_dead; ++i)
+            VS_REQUIRE((dead[i] & 0xFFFFull) != 0, "%s: dead_tids[%llu] has offset 0 (InvalidOffsetNumber)", what, (unsigned long long)i);
+    if (ix->ws.pending) {
+        vs_set_error("%s: a batch of this handle is in flight (vs_search_batch_dev_finish first)", what);
+        return VS_ERR_STATE;
+    }
+    vs_ctx* c = ix->ctx;
+    hipStream_t st = c->stream;
+    VS_HIP(hipSetDevice(c->device));
+    uint64_t *d_in = nullptr, *d_sorted = nullptr;
+    uint8_t* d_pay = nullptr;
+    void* d_tmp = nullptr;
+    unsigned long long* d_cnt = nullptr;
+    unsigned long long h_cnt[3] = {0, 0, 0};
+    auto run = [&]() -> int {
+        const uint64_t* d_dead = dead;
+        if (!on_device && n_dead) {
+            // staged through the pinned ring, sorted on the device (the radix sort the build already uses: pairs, here with one byte
+            // of payload nobody reads); duplicates stay, a binary search does not mind them
+            VS_HIP(hipMalloc(&d_in, n_dead * 8));
+            VS_HIP(hipMalloc(&d_sorted, n_dead * 8));
+            VS_HIP(hipMalloc(&d_pay, n_dead * 2));
+            VS_HIP(hipMemsetAsync(d_pay, 0, n_dead * 2, st));
+            VS_TRY(vs_dev_upload(c, d_in, dead, n_dead * 8));
+            size_t tmp_bytes = 0;
+            VS_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (const uint64_t*)d_in, d_sorted, (const uint8_t*)d_pay, d_pay + n_dead,
+                                                      (int)n_dead, 0, 64, st));
+            VS_HIP(hipMalloc(&d_tmp, tmp_bytes + 16));
+            VS_HIP(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, (const uint64_t*)d_in, d_sorted, (const uint8_t*)d_pay, d_pay + n_dead,
+                                                      (int)n_dead, 0, 64, st));
+            d_dead = d_sorted;
+        }
+        VS_HIP(hipMalloc(&d_cnt, sizeof h_cnt));
+        VS_HIP(hipMemsetAsync(d_cnt, 0, sizeof h_cnt, st));
+        if (ix->d.n) {
+            const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)ix->d.n + 255) / 256, 8192);
+            hipLaunchKernelGGL(k_bulk_delete, dim3(grid), dim3(256), 0, st, ix->tids, ix->d.n, d_dead, n_dead, d_cnt);
+            VS_HIP(hipGetLastError());
+        }
+        VS_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
+        VS_HIP(hipStreamSynchronize(st));  // (the only wait: the three counters)
+        return VS_OK;
+    };
+    const int rc = run();
+    if (rc != VS_OK) (void)hipStreamSynchronize(st);
+    if (d_in) (void)hipFree(d_in);
+    if (d_sorted) (void)hipFree(d_sorted);
+    if (d_pay) (void)hipFree(d_pay);
+    if (d_tmp) (void)hipFree(d_tmp);
+    if (d_cnt) (void)hipFree(d_cnt);
+    if (rc == VS_OK && out) {
+        out->tuples_removed = h_cnt[0];
+        out->num_index_tuples = h_cnt[1];
+        out->already_deleted = h_cnt[2];
+    }
+    return rc;
+}
+extern "C" int vs_index_bulk_delete(vs_index* ix, const uint64_t* dead_tids, uint64_t n_dead, vs_bulk_delete_stats* out) {
+    return vs_guard("vs_index_bulk_delete", [&] { return bulk_delete_impl(ix, "vs_index_bulk_delete", dead_tids, n_dead, false, out); });
+}
+extern "C" int vs_index_bulk_delete_dev(vs_index* ix, const uint64_t* d_dead_tids_sorted, uint64_t n_dead, vs_bulk_delete_stats* out) {
+    return vs_guard("vs_index_bulk_delete_dev", [&] { return bulk_delete_impl(ix, "vs_index_bulk_delete_dev", d_dead_tids_sorted, n_dead, true, out); });
+}

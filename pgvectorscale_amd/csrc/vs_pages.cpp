@@ -1214,6 +1214,25 @@ int vs_pages_out_plan_item_pointer(const PagesOutPlan& plan, uint32_t node, uint
     return VS_OK;
 }
 
+static const std::vector<uint8_t>* host_page_at(const std::vector<std::pair<uint32_t, std::vector<uint8_t>>>& pages, uint32_t block) {
+    auto it = std::lower_bound(pages.begin(), pages.end(), block, [](const auto& hp, uint32_t b) { return hp.first < b; });
+    return it != pages.end() && it->first == block ? &it->second : nullptr;
+}
+
+const uint8_t* vs_pages_out_plan_host_page(const PagesOutPlan& plan, uint32_t block) {
+    const std::vector<uint8_t>* p = host_page_at(plan.host_pages, block);
+    return p ? p->data() : nullptr;
+}
+
+// The byte rule for the pages the host encodes: a block past the baseline's end, a block the baseline held as a node page, a block
+// whose bytes differ.  (A block that WAS a host page and is a node page now is the digest pass's to report.)
+void vs_pages_out_host_delta(const PagesOutPlan& plan, const vs_pages_base& base, std::vector<uint32_t>& dirty) {
+    for (const auto& hp : plan.host_pages) {
+        const std::vector<uint8_t>* was = hp.first < base.n_blocks ? host_page_at(base.host_pages, hp.first) : nullptr;
+        if (!was || was->size() != hp.second.size() || memcmp(was->data(), hp.second.data(), was->size()) != 0) dirty.push_back(hp.first);
+    }
+}
+
 int vs_pages_out_plan(const vs_index_desc& d, const vs_pages_out_params& p, const float* mean, const float* m2, uint64_t count,
                       const uint32_t* label_off, const int16_t* ls_labels, const uint32_t* ls_nodes, PagesOutPlan& plan) {
     if (p.page_size != VS_BLCKSZ) return fail("vs_pages_out_open: page_size %u (the writer lays out %u-byte pages)", p.page_size, VS_BLCKSZ);

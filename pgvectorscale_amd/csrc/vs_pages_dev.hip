@@ -398,11 +398,48 @@ typedef uint16_t __attribute__((may_alias)) po_u16;
 // ArchivedItemPointer {u32 block_number, u16 offset, 2 B pad} as one little-endian word
 __device__ __forceinline__ uint64_t item_pointer_word(uint32_t block, uint32_t offset) { return (uint64_t)block | ((uint64_t)offset << 32); }
 
-__global__ __launch_bounds__(kOutThreads) void k_pages_encode(PagesEncodeArgs a, uint32_t page0, uint4* __restrict__ out, uint32_t* __restrict__ err) {
+// The digest of a finished page: the page is 512 pieces of 16 bytes (lo, hi: two little-endian u64); piece i
+// contributes, in each of two independently keyed lanes, a strong 64-bit finaliser of its bytes and its position,
+//     A_i = fmixA(fmixA(lo + KA + (i + 1) * GA) ^ hi),   B_i = fmixB(fmixB(lo + KB + (i + 1) * GB) ^ hi)
+// (fmixA: the splitmix64 finaliser, fmixB: MurmurHash3's fmix64), and the digest is (sum A_i, sum B_i) modulo 2^64: addition
+// commutes, so neither the order of the in-wave shuffles nor that of the cross-wave sum through LDS matters.
+__device__ __forceinline__ uint64_t digest_fmix_a(uint64_t x) {
+    x ^= x >> 30;
+    x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27;
+    x *= 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+__device__ __forceinline__ uint64_t digest_fmix_b(uint64_t x) {
+    x ^= x >> 33;
+    x *= 0xFF51AFD7ED558CCDull;
+    x ^= x >> 33;
+    x *= 0xC4CEB9FE1A85EC53ull;
+    return x ^ (x >> 33);
+}
+__device__ __forceinline__ void digest_piece(uint32_t i, uint64_t lo, uint64_t hi, uint64_t& sa, uint64_t& sb) {
+    sa += digest_fmix_a(digest_fmix_a(lo + 0x243F6A8885A308D3ull + (uint64_t)(i + 1) * 0x9E3779B97F4A7C15ull) ^ hi);
+    sb += digest_fmix_b(digest_fmix_b(lo + 0x13198A2E03707344ull + (uint64_t)(i + 1) * 0xC2B2AE3D27D4EB4Full) ^ hi);
+}
+
+// where the digest instantiation leaves its result, and what it is compared against
+struct PagesDigestArgs {
+    uint64_t* digest;             // [n_blocks][2] of the relation as it is now: node page p lands at block first_node_block + p
+    const uint64_t* base_digest;  // [base_n_blocks][2] of the baseline (null: nothing to compare with)
+    uint8_t* dirty;               // [n_node_pages] 1 = the block is not what the baseline recorded (null without a baseline)
+    uint32_t base_n_blocks, base_first_node_block, base_n_node_pages;
+};
+
+// DIGEST = false: the page leaves as 512 full-lane 16-byte stores (slot blockIdx.x of `out`); true: 16 bytes of digest leave instead.
+// page_list (may be null: pages page0, page0 + 1, ...): the node page of every workgroup; VS_INVALID_NODE = this slot is not a node page
+template <bool DIGEST>
+__global__ __launch_bounds__(kOutThreads) void k_pages_encode(PagesEncodeArgs a, uint32_t page0, const uint32_t* __restrict__ page_list,
+                                                              uint4* __restrict__ out, PagesDigestArgs dg, uint32_t* __restrict__ err) {
     __shared__ uint4 pg4[kOutPage / 16];
     uint8_t* pg = reinterpret_cast<uint8_t*>(pg4);
     const uint32_t tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    const uint32_t p = page0 + blockIdx.x;  // node page number: block first_node_block + p
+    const uint32_t p = page_list ? page_list[blockIdx.x] : page0 + blockIdx.x;  // node page number: block first_node_block + p
+    if (p == VS_INVALID_NODE) return;  // (the whole workgroup)
     pg4[tid] = make_uint4(0, 0, 0, 0);
     pg4[tid + kOutThreads] = make_uint4(0, 0, 0, 0);
     uint32_t first, cnt;
@@ -517,9 +554,84 @@ __global__ __launch_bounds__(kOutThreads) void k_pages_encode(PagesEncodeArgs a,
         }
     }
     __syncthreads();
-    uint4* dst = out + (size_t)blockIdx.x * (kOutPage / 16);
-    dst[tid] = pg4[tid];
-    dst[tid + kOutThreads] = pg4[tid + kOutThreads];
+    if (!DIGEST) {
+        uint4* dst = out + (size_t)blockIdx.x * (kOutPage / 16);
+        dst[tid] = pg4[tid];
+        dst[tid + kOutThreads] = pg4[tid + kOutThreads];
+        return;
+    }
+    __shared__ uint64_t red[2 * kOutThreads / WAVE];
+    uint64_t sa = 0, sb = 0;
+    for (uint32_t i = tid; i < kOutPage / 16; i += kOutThreads) {
+        const uint4 v = pg4[i];
+        digest_piece(i, (uint64_t)v.x | ((uint64_t)v.y << 32), (uint64_t)v.z | ((uint64_t)v.w << 32), sa, sb);
+    }
+    for (int m = 1; m < WAVE; m <<= 1) {
+        sa += __shfl_xor(sa, m);
+        sb += __shfl_xor(sb, m);
+    }
+    if (lane == 0) {
+        red[2 * wave] = sa;
+        red[2 * wave + 1] = sb;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        sa = sb = 0;
+        for (uint32_t w = 0; w < kOutThreads / WAVE; ++w) {
+            sa += red[2 * w];
+            sb += red[2 * w + 1];
+        }
+        const uint32_t b = a.first_node_block + p;
+        dg.digest[2 * (size_t)b] = sa;
+        dg.digest[2 * (size_t)b + 1] = sb;
+        if (dg.dirty) {
+            // the byte rule for a node page: past the baseline's end, not a node page then, or other bytes
+            bool same = b < dg.base_n_blocks && b >= dg.base_first_node_block && b - dg.base_first_node_block < dg.base_n_node_pages;
+            if (same) same = dg.base_digest[2 * (size_t)b] == sa && dg.base_digest[2 * (size_t)b + 1] == sb;
+            dg.dirty[p] = same ? 0 : 1;
+        }
+    }
+}
+
+// The dirty node pages as an ascending list of block numbers.  Three passes, so that the order is the pages' own and not that of an
+// atomic slot counter: dirty pages per wave of 64 pages (ballot), one exclusive scan over the waves' counts, then every dirty page
+// writes itself at its wave's offset + its rank among the wave's dirty lanes.
+__global__ __launch_bounds__(256) void k_pages_dirty_count(const uint8_t* __restrict__ dirty, uint32_t n, uint32_t* __restrict__ wave_cnt) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    const uint64_t m = __ballot(i < n && dirty[i] != 0);
+    if ((threadIdx.x & (WAVE - 1)) == 0) wave_cnt[i / WAVE] = (uint32_t)__popcll(m);
+}
+// one workgroup: v[0 .. m) becomes its exclusive prefix sums, v[m] the total
+__global__ __launch_bounds__(256) void k_pages_scan_counts(uint32_t* __restrict__ v, uint32_t m) {
+    __shared__ uint32_t part[256];
+    const uint32_t per = (m + 255) / 256, lo = min(threadIdx.x * per, m), hi = min(lo + per, m);
+    uint32_t s = 0;
+    for (uint32_t i = lo; i < hi; ++i) s += v[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t run = 0;
+        for (uint32_t t = 0; t < 256; ++t) {
+            const uint32_t c = part[t];
+            part[t] = run;
+            run += c;
+        }
+        v[m] = run;
+    }
+    __syncthreads();
+    uint32_t run = part[threadIdx.x];
+    for (uint32_t i = lo; i < hi; ++i) {
+        const uint32_t c = v[i];
+        v[i] = run;
+        run += c;
+    }
+}
+__global__ __launch_bounds__(256) void k_pages_dirty_scatter(const uint8_t* __restrict__ dirty, uint32_t n, const uint32_t* __restrict__ wave_off,
+                                                             uint32_t first_node_block, uint32_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & (WAVE - 1);
+    const bool d = i < n && dirty[i] != 0;
+    const uint64_t m = __ballot(d);
+    if (d) out[wave_off[i / WAVE] + (uint32_t)__popcll(m & ((1ull << lane) - 1))] = first_node_block + i;
 }
 
 // nodes whose heap_item_pointer.offset is InvalidOffsetNumber
@@ -541,6 +653,9 @@ struct vs_pages_out {
     uint32_t* d_err = nullptr;
     hipEvent_t ev_done[2] = {nullptr, nullptr};  // the encode of the chunk in d_stage[i] has finished
     uint32_t chunk_pages = 0;
+    uint32_t* d_list = nullptr;  // the node pages of a vs_pages_out_read_blocks call (grow-only)
+    size_t list_cap = 0;
+    std::vector<uint32_t> delta;  // the dirty blocks of the last vs_pages_out_delta (ascending)
 };
 
 extern "C" void vs_pages_out_close(vs_pages_out* w) {
@@ -554,6 +669,7 @@ extern "C" void vs_pages_out_close(vs_pages_out* w) {
         if (w->ev_done[i]) (void)hipEventDestroy(w->ev_done[i]);
     }
     if (w->d_err) (void)hipFree(w->d_err);
+    if (w->d_list) (void)hipFree(w->d_list);
     delete w;
 }
 
@@ -670,11 +786,12 @@ extern "C" int vs_pages_out_item_pointer_of(const vs_pages_out* w, uint32_t node
     return vs_pages_out_plan_item_pointer(w->plan, node, block, offset);
 }
 
-// node pages [p0, p0 + np) into d_out, on the compute stream
-static int launch_pages_encode(vs_pages_out* w, uint32_t p0, uint32_t np, void* d_out) {
+// node pages [p0, p0 + np) — or, with d_list, the np pages it names — into d_out, on the compute stream
+static int launch_pages_encode(vs_pages_out* w, uint32_t p0, const uint32_t* d_list, uint32_t np, void* d_out) {
     vs_ctx* c = w->ctx;
     hipEvent_t ev = prof_begin(c);
-    hipLaunchKernelGGL(k_pages_encode, dim3(np), dim3(kOutThreads), 0, c->stream, w->args, p0, reinterpret_cast<uint4*>(d_out), w->d_err);
+    hipLaunchKernelGGL((k_pages_encode<false>), dim3(np), dim3(kOutThreads), 0, c->stream, w->args, p0, d_list, reinterpret_cast<uint4*>(d_out),
+                       PagesDigestArgs{}, w->d_err);
     VS_HIP(hipGetLastError());
     prof_end(c, PK_PAGES, ev);
     return VS_OK;
@@ -711,46 +828,38 @@ static int pages_out_range(const vs_pages_out* w, const char* what, uint32_t fir
     return VS_OK;
 }
 
-static int pages_out_read_impl(vs_pages_out* w, uint32_t first_block, uint32_t n_blocks, void* pages) {
-    uint32_t p0 = 0, np = 0;
-    VS_TRY(pages_out_range(w, "vs_pages_out_read", first_block, n_blocks, pages, &p0, &np));
+// np node pages through the pinned ring.  Chunk i is encoded into d_stage[i & 1] on the compute stream (launch(q0, qn, d_stage)),
+// copied to pinned[i & 1] on the copy stream once its kernel has finished, and drained to the caller's buffer (drain(q0, qn, pinned))
+// when its slot comes round again: the kernel of chunk i + 1 runs under the copy of chunk i, the host's copy out of one pinned buffer
+// under the transfer into the other (as vs_dev_download).  The kernel of chunk i is queued BEFORE the host drains chunk i - 2 out of
+// pinned[i & 1]: it waits on the device for that chunk's transfer (d_stage[i & 1] is free then), not for the host's memcpy; only the
+// transfer into pinned[i & 1] comes after the drain.
+template <class Launch, class Drain>
+static int pages_out_pump(vs_pages_out* w, uint32_t np, Launch&& launch, Drain&& drain) {
     vs_ctx* c = w->ctx;
     const size_t ps = w->plan.page_size;
-    uint8_t* dst = static_cast<uint8_t*>(pages);
-    VS_HIP(hipSetDevice(c->device));
-    VS_TRY(pages_out_host_pages(w, first_block, n_blocks, [&](uint32_t blk, const uint8_t* bytes) {
-        memcpy(dst + (size_t)(blk - first_block) * ps, bytes, ps);
-        return (int)VS_OK;
-    }));
-    if (np == 0) return VS_OK;
-    // chunk i is encoded into d_stage[i & 1] on the compute stream, copied to pinned[i & 1] on the copy stream once its kernel has
-    // finished, and drained to the caller's buffer when its slot comes round again: the kernel of chunk i + 1 runs under the copy of
-    // chunk i, the host's copy out of one pinned buffer under the transfer into the other (as vs_dev_download).  The kernel of
-    // chunk i is queued BEFORE the host drains chunk i - 2 out of pinned[i & 1]: it waits on the device for that chunk's transfer
-    // (d_stage[i & 1] is free then), not for the host's memcpy; only the transfer into pinned[i & 1] comes after the drain.
-    uint8_t* node_dst = dst + (size_t)(w->plan.first_node_block + p0 - first_block) * ps;
     const uint32_t nchunks = (np + w->chunk_pages - 1) / w->chunk_pages;
-    size_t pend_off[2] = {0, 0}, pend_n[2] = {0, 0};
+    uint32_t pend_q0[2] = {0, 0}, pend_n[2] = {0, 0};
     auto pump = [&]() -> int {
         for (uint32_t i = 0; i < nchunks + 2; ++i) {
             const int slot = (int)(i & 1);
             const uint32_t q0 = i * w->chunk_pages, qn = i < nchunks ? std::min(w->chunk_pages, np - q0) : 0;
             if (qn) {
                 if (pend_n[slot]) VS_HIP(hipStreamWaitEvent(c->stream, c->pinned_ev[slot], 0));
-                VS_TRY(launch_pages_encode(w, p0 + q0, qn, w->d_stage[slot]));
+                VS_TRY(launch(q0, qn, w->d_stage[slot]));
                 VS_HIP(hipEventRecord(w->ev_done[slot], c->stream));
             }
             if (pend_n[slot]) {
                 VS_HIP(hipEventSynchronize(c->pinned_ev[slot]));
-                stage_copy(node_dst + pend_off[slot], c->pinned[slot], pend_n[slot]);
+                drain(pend_q0[slot], pend_n[slot], static_cast<const uint8_t*>(c->pinned[slot]));
                 pend_n[slot] = 0;
             }
             if (qn) {
                 VS_HIP(hipStreamWaitEvent(c->copy_stream, w->ev_done[slot], 0));
                 VS_HIP(hipMemcpyAsync(c->pinned[slot], w->d_stage[slot], (size_t)qn * ps, hipMemcpyDeviceToHost, c->copy_stream));
                 VS_HIP(hipEventRecord(c->pinned_ev[slot], c->copy_stream));
-                pend_off[slot] = (size_t)q0 * ps;
-                pend_n[slot] = (size_t)qn * ps;
+                pend_q0[slot] = q0;
+                pend_n[slot] = qn;
             }
         }
         return VS_OK;
@@ -765,6 +874,24 @@ static int pages_out_read_impl(vs_pages_out* w, uint32_t first_block, uint32_t n
     return pages_out_check(w);
 }
 
+static int pages_out_read_impl(vs_pages_out* w, uint32_t first_block, uint32_t n_blocks, void* pages) {
+    uint32_t p0 = 0, np = 0;
+    VS_TRY(pages_out_range(w, "vs_pages_out_read", first_block, n_blocks, pages, &p0, &np));
+    vs_ctx* c = w->ctx;
+    const size_t ps = w->plan.page_size;
+    uint8_t* dst = static_cast<uint8_t*>(pages);
+    VS_HIP(hipSetDevice(c->device));
+    VS_TRY(pages_out_host_pages(w, first_block, n_blocks, [&](uint32_t blk, const uint8_t* bytes) {
+        memcpy(dst + (size_t)(blk - first_block) * ps, bytes, ps);
+        return (int)VS_OK;
+    }));
+    if (np == 0) return VS_OK;
+    uint8_t* node_dst = dst + (size_t)(w->plan.first_node_block + p0 - first_block) * ps;
+    return pages_out_pump(
+        w, np, [&](uint32_t q0, uint32_t qn, uint8_t* d_stage) { return launch_pages_encode(w, p0 + q0, nullptr, qn, d_stage); },
+        [&](uint32_t q0, uint32_t qn, const uint8_t* pinned) { stage_copy(node_dst + (size_t)q0 * ps, pinned, (size_t)qn * ps); });
+}
+
 extern "C" int vs_pages_out_read(vs_pages_out* w, uint32_t first_block, uint32_t n_blocks, void* pages) {
     return vs_guard("vs_pages_out_read", [&] { return pages_out_read_impl(w, first_block, n_blocks, pages); });
 }
@@ -777,7 +904,7 @@ static int pages_out_read_dev_impl(vs_pages_out* w, uint32_t first_block, uint32
     uint8_t* dst = static_cast<uint8_t*>(d_pages);
     VS_REQUIRE(((uintptr_t)dst & 15) == 0, "vs_pages_out_read_dev: the device buffer must be 16-byte aligned");
     VS_HIP(hipSetDevice(c->device));
-    if (np) VS_TRY(launch_pages_encode(w, p0, np, dst + (size_t)(w->plan.first_node_block + p0 - first_block) * ps));
+    if (np) VS_TRY(launch_pages_encode(w, p0, nullptr, np, dst + (size_t)(w->plan.first_node_block + p0 - first_block) * ps));
     VS_TRY(pages_out_host_pages(w, first_block, n_blocks, [&](uint32_t blk, const uint8_t* bytes) {
         return vs_dev_upload(c, dst + (size_t)(blk - first_block) * ps, bytes, ps);
     }));
@@ -787,4 +914,235 @@ static int pages_out_read_dev_impl(vs_pages_out* w, uint32_t first_block, uint32
 
 extern "C" int vs_pages_out_read_dev(vs_pages_out* w, uint32_t first_block, uint32_t n_blocks, void* d_pages) {
     return vs_guard("vs_pages_out_read_dev", [&] { return pages_out_read_dev_impl(w, first_block, n_blocks, d_pages); });
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Page by page (vs_pages_out_baseline / _delta / _read_blocks): what bulk_delete_for_storage (AM/vacuum.rs:80-136, page.commit()
+// only `if modified`) and aminsert (AM/build.rs:464-558) do to the relation — only the pages a change touched are written.  A
+// baseline is one digest per block of the relation as this writer last produced it; the digest pass is k_pages_encode with the
+// digest as its tail instead of the 8 KB of stores, so whatever decides a page's bytes decides its digest.
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" void vs_pages_base_free(vs_pages_base* b) {
+    if (!b) return;
+    if (b->d_digest) {
+        (void)hipSetDevice(b->device);
+        (void)hipFree(b->d_digest);
+    }
+    delete b;
+}
+
+extern "C" uint32_t vs_pages_base_blocks(const vs_pages_base* b) { return b ? b->n_blocks : 0; }
+
+// One digest pass over every node page of w.  base (may be null): the dirty blocks land in w->delta; out (may be null): the
+// baseline of the relation as it is now.
+static int pages_out_digest_impl(vs_pages_out* w, const char* what, const vs_pages_base* base, vs_pages_base** out) {
+    vs_ctx* c = w->ctx;
+    const PagesOutPlan& plan = w->plan;
+    VS_HIP(hipSetDevice(c->device));
+    if (base) {
+        VS_REQUIRE(base->device == c->device, "%s: the baseline lives on device %d, the writer on device %d", what, base->device, c->device);
+        VS_REQUIRE(base->page_size == plan.page_size, "%s: the baseline is one of %u-byte pages", what, base->page_size);
+    }
+    const uint32_t np = plan.n_node_pages;
+    const uint32_t waves = (np + 255) / 256 * (256 / WAVE);
+    uint64_t* d_digest = nullptr;
+    uint8_t* d_dirty = nullptr;
+    uint32_t *d_wave = nullptr, *d_blocks = nullptr;
+    auto release = [&] {
+        if (d_digest) (void)hipFree(d_digest);
+        if (d_dirty) (void)hipFree(d_dirty);
+        if (d_wave) (void)hipFree(d_wave);
+        if (d_blocks) (void)hipFree(d_blocks);
+    };
+    std::vector<uint32_t> node_dirty;
+    auto run = [&]() -> int {
+        VS_HIP(hipMalloc(&d_digest, (size_t)std::max<uint32_t>(plan.n_blocks, 1) * 16));
+        VS_HIP(hipMemsetAsync(d_digest, 0, (size_t)std::max<uint32_t>(plan.n_blocks, 1) * 16, c->stream));
+        if (base && np) {
+            VS_HIP(hipMalloc(&d_dirty, np));
+            VS_HIP(hipMalloc(&d_wave, ((size_t)waves + 1) * 4));
+            VS_HIP(hipMalloc(&d_blocks, (size_t)np * 4));
+        }
+        uint32_t n_dirty = 0;
+        if (np) {
+            PagesDigestArgs dg{};
+            dg.digest = d_digest;
+            dg.base_digest = base ? base->d_digest : nullptr;
+            dg.dirty = d_dirty;
+            dg.base_n_blocks = base ? base->n_blocks : 0;
+            dg.base_first_node_block = base ? base->first_node_block : 0;
+            dg.base_n_node_pages = base ? base->n_node_pages : 0;
+            hipEvent_t ev = prof_begin(c);
+            hipLaunchKernelGGL((k_pages_encode<true>), dim3(np), dim3(kOutThreads), 0, c->stream, w->args, 0u, (const uint32_t*)nullptr,
+                               (uint4*)nullptr, dg, w->d_err);
+            VS_HIP(hipGetLastError());
+            prof_end(c, PK_PAGES, ev);
+            if (base) {
+                hipLaunchKernelGGL(k_pages_dirty_count, dim3((np + 255) / 256), dim3(256), 0, c->stream, (const uint8_t*)d_dirty, np, d_wave);
+                VS_HIP(hipGetLastError());
+                hipLaunchKernelGGL(k_pages_scan_counts, dim3(1), dim3(256), 0, c->stream, d_wave, waves);
+                VS_HIP(hipGetLastError());
+                hipLaunchKernelGGL(k_pages_dirty_scatter, dim3((np + 255) / 256), dim3(256), 0, c->stream, (const uint8_t*)d_dirty, np,
+                                   (const uint32_t*)d_wave, plan.first_node_block, d_blocks);
+                VS_HIP(hipGetLastError());
+                VS_HIP(hipMemcpyAsync(&n_dirty, d_wave + waves, 4, hipMemcpyDeviceToHost, c->stream));
+            }
+        }
+        VS_HIP(hipStreamSynchronize(c->stream));
+        VS_TRY(pages_out_check(w));
+        VS_REQUIRE(n_dirty <= np, "%s: the dirty list holds %u of %u node pages", what, n_dirty, np);
+        node_dirty.resize(n_dirty);
+        if (n_dirty) VS_TRY(vs_dev_download(c, node_dirty.data(), d_blocks, (size_t)n_dirty * 4));
+        return VS_OK;
+    };
+    const int rc = run();
+    if (rc != VS_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        release();
+        return rc;
+    }
+    if (base) {
+        std::vector<uint32_t> host_dirty;
+        vs_pages_out_host_delta(plan, *base, host_dirty);
+        w->delta.resize(node_dirty.size() + host_dirty.size());
+        std::merge(node_dirty.begin(), node_dirty.end(), host_dirty.begin(), host_dirty.end(), w->delta.begin());
+    }
+    if (out) {
+        vs_pages_base* nb = new vs_pages_base();
+        nb->device = c->device;
+        nb->page_size = plan.page_size;
+        nb->n_blocks = plan.n_blocks;
+        nb->first_node_block = plan.first_node_block;
+        nb->n_node_pages = np;
+        nb->host_pages = plan.host_pages;
+        nb->d_digest = d_digest;
+        d_digest = nullptr;
+        *out = nb;
+    }
+    release();
+    return VS_OK;
+}
+
+extern "C" int vs_pages_out_baseline(vs_pages_out* w, vs_pages_base** out) {
+    VS_REQUIRE(w && out, "vs_pages_out_baseline: bad args");
+    *out = nullptr;
+    return vs_guard("vs_pages_out_baseline", [&] { return pages_out_digest_impl(w, "vs_pages_out_baseline", nullptr, out); });
+}
+
+extern "C" int vs_pages_out_delta(vs_pages_out* w, const vs_pages_base* base, uint32_t* n_dirty, uint32_t* n_blocks_now,
+                                  vs_pages_base** new_base) {
+    VS_REQUIRE(w && base && n_dirty, "vs_pages_out_delta: bad args");
+    if (new_base) *new_base = nullptr;
+    *n_dirty = 0;
+    w->delta.clear();
+    const int rc = vs_guard("vs_pages_out_delta", [&] { return pages_out_digest_impl(w, "vs_pages_out_delta", base, new_base); });
+    if (rc != VS_OK) {
+        w->delta.clear();
+        return rc;
+    }
+    *n_dirty = (uint32_t)w->delta.size();
+    if (n_blocks_now) *n_blocks_now = w->plan.n_blocks;
+    return VS_OK;
+}
+
+extern "C" int vs_pages_out_delta_blocks(const vs_pages_out* w, uint32_t* blocks, uint32_t cap) {
+    VS_REQUIRE(w && (blocks || w->delta.empty()), "vs_pages_out_delta_blocks: bad args");
+    VS_REQUIRE(cap >= w->delta.size(), "vs_pages_out_delta_blocks: room for %u of %zu blocks", cap, w->delta.size());
+    if (!w->delta.empty()) memcpy(blocks, w->delta.data(), w->delta.size() * 4);
+    return VS_OK;
+}
+
+// what every block of the list is: the host-encoded page (host[i] != null) or node page list[i]; nothing has been written when
+// a block fails the check
+static int pages_out_classify(const vs_pages_out* w, const char* what, const uint32_t* blocks, uint32_t n, const void* pages,
+                              std::vector<uint32_t>& list, std::vector<const uint8_t*>& host) {
+    VS_REQUIRE(w && (n == 0 || (blocks && pages)), "%s: bad args", what);
+    const PagesOutPlan& plan = w->plan;
+    list.assign(n, VS_INVALID_NODE);
+    host.assign(n, nullptr);
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t b = blocks[i];
+        VS_REQUIRE(b < plan.n_blocks, "%s: blocks[%u] = %u of a relation of %u blocks", what, i, b, plan.n_blocks);
+        if (b >= plan.first_node_block && b - plan.first_node_block < plan.n_node_pages) {
+            list[i] = b - plan.first_node_block;
+        } else {
+            host[i] = vs_pages_out_plan_host_page(plan, b);
+            VS_REQUIRE(host[i], "%s: block %u is neither a node page nor a page the host encoded", what, b);
+        }
+    }
+    return VS_OK;
+}
+
+static int pages_out_list_reserve(vs_pages_out* w, size_t n) {
+    if (n <= w->list_cap) return VS_OK;
+    if (w->d_list) VS_HIP(hipFree(w->d_list));
+    w->d_list = nullptr;
+    w->list_cap = 0;
+    VS_HIP(hipMalloc(&w->d_list, n * 4));
+    w->list_cap = n;
+    return VS_OK;
+}
+
+static int pages_out_read_blocks_impl(vs_pages_out* w, const uint32_t* blocks, uint32_t n, void* pages) {
+    std::vector<uint32_t> list;
+    std::vector<const uint8_t*> host;
+    VS_TRY(pages_out_classify(w, "vs_pages_out_read_blocks", blocks, n, pages, list, host));
+    vs_ctx* c = w->ctx;
+    const size_t ps = w->plan.page_size;
+    uint8_t* dst = static_cast<uint8_t*>(pages);
+    VS_HIP(hipSetDevice(c->device));
+    // the node pages of the list, in list order, and the slot of the output each one goes to
+    std::vector<uint32_t> node_pages, slot;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (host[i]) {
+            memcpy(dst + (size_t)i * ps, host[i], ps);
+        } else {
+            node_pages.push_back(list[i]);
+            slot.push_back(i);
+        }
+    }
+    const uint32_t np = (uint32_t)node_pages.size();
+    if (np == 0) return VS_OK;
+    VS_TRY(pages_out_list_reserve(w, np));
+    VS_TRY(vs_dev_upload(c, w->d_list, node_pages.data(), (size_t)np * 4));
+    // chunks are cut from the list; a chunk's pages go to their slots run by run (neighbours in the list are neighbours in the output
+    // unless a host-encoded page sits between them)
+    return pages_out_pump(
+        w, np, [&](uint32_t q0, uint32_t qn, uint8_t* d_stage) { return launch_pages_encode(w, 0, w->d_list + q0, qn, d_stage); },
+        [&](uint32_t q0, uint32_t qn, const uint8_t* pinned) {
+            for (uint32_t j = 0; j < qn;) {
+                uint32_t e = j + 1;
+                while (e < qn && slot[q0 + e] == slot[q0 + e - 1] + 1) e++;
+                stage_copy(dst + (size_t)slot[q0 + j] * ps, pinned + (size_t)j * ps, (size_t)(e - j) * ps);
+                j = e;
+            }
+        });
+}
+
+extern "C" int vs_pages_out_read_blocks(vs_pages_out* w, const uint32_t* blocks, uint32_t n, void* pages) {
+    return vs_guard("vs_pages_out_read_blocks", [&] { return pages_out_read_blocks_impl(w, blocks, n, pages); });
+}
+
+static int pages_out_read_blocks_dev_impl(vs_pages_out* w, const uint32_t* blocks, uint32_t n, void* d_pages) {
+    std::vector<uint32_t> list;
+    std::vector<const uint8_t*> host;
+    VS_TRY(pages_out_classify(w, "vs_pages_out_read_blocks_dev", blocks, n, d_pages, list, host));
+    if (n == 0) return VS_OK;
+    vs_ctx* c = w->ctx;
+    const size_t ps = w->plan.page_size;
+    uint8_t* dst = static_cast<uint8_t*>(d_pages);
+    VS_REQUIRE(((uintptr_t)dst & 15) == 0, "vs_pages_out_read_blocks_dev: the device buffer must be 16-byte aligned");
+    VS_HIP(hipSetDevice(c->device));
+    // one launch over the whole list: workgroup i composes slot i in place, the slots of host-encoded pages are skipped by it
+    VS_TRY(pages_out_list_reserve(w, n));
+    VS_TRY(vs_dev_upload(c, w->d_list, list.data(), (size_t)n * 4));
+    VS_TRY(launch_pages_encode(w, 0, w->d_list, n, dst));
+    for (uint32_t i = 0; i < n; ++i)
+        if (host[i]) VS_TRY(vs_dev_upload(c, dst + (size_t)i * ps, host[i], ps));
+    VS_HIP(hipStreamSynchronize(c->stream));
+    return pages_out_check(w);
+}
+
+extern "C" int vs_pages_out_read_blocks_dev(vs_pages_out* w, const uint32_t* blocks, uint32_t n, void* d_pages) {
+    return vs_guard("vs_pages_out_read_blocks_dev", [&] { return pages_out_read_blocks_dev_impl(w, blocks, n, d_pages); });
 }

@@ -32,3 +32,18 @@ struct PagesOutPlan {
 int vs_pages_out_plan(const vs_index_desc& d, const vs_pages_out_params& p, const float* mean, const float* m2, uint64_t count,
                       const uint32_t* label_off, const int16_t* ls_labels, const uint32_t* ls_nodes, PagesOutPlan& plan);
 int vs_pages_out_plan_item_pointer(const PagesOutPlan& plan, uint32_t node, uint32_t* block, uint32_t* offset);
+
+// What a relation looked like when it was last written (vs_pages_out_baseline / vs_pages_out_delta): one 128-bit digest per block
+// in device memory (node pages; the entries of host-encoded blocks stay zero) and the host-encoded pages themselves.  Belongs to a
+// device, not to a writer or an index: it outlives both.
+struct vs_pages_base {
+    int device = 0;
+    uint32_t page_size = VS_BLCKSZ;
+    uint32_t n_blocks = 0, first_node_block = 0, n_node_pages = 0;
+    uint64_t* d_digest = nullptr;  // [n_blocks][2]
+    std::vector<std::pair<uint32_t, std::vector<uint8_t>>> host_pages;  // as PagesOutPlan::host_pages
+};
+// the host-encoded pages of `plan` that are not, byte for byte, what `base` recorded at the same block (ascending)
+void vs_pages_out_host_delta(const PagesOutPlan& plan, const vs_pages_base& base, std::vector<uint32_t>& dirty);
+// the host-encoded page at `block`, or nullptr when the block is a node page
+const uint8_t* vs_pages_out_plan_host_page(const PagesOutPlan& plan, uint32_t block);

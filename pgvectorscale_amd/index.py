@@ -287,6 +287,20 @@ class DiskAnnIndex:
         a = np.ascontiguousarray(nodes, np.uint32)
         check(self._L.vs_index_mark_deleted(self.h, _p(a), a.size))
 
+    def bulk_delete(self, dead_tids):
+        """ambulkdelete by heap TID (vs_index_bulk_delete): dead_tids = (block << 16) | offset, unsorted, duplicates allowed ->
+        {"tuples_removed", "num_index_tuples", "already_deleted"}"""
+        a = np.ascontiguousarray(dead_tids, np.uint64)
+        st = _lib.BulkDeleteStats()
+        check(self._L.vs_index_bulk_delete(self.h, _p(a), a.size, C.byref(st)))
+        return st.as_dict()
+
+    def bulk_delete_dev(self, d_dead_tids_sorted, n_dead):
+        """the same with the dead TIDs in device memory, sorted ascending and de-duplicated"""
+        st = _lib.BulkDeleteStats()
+        check(self._L.vs_index_bulk_delete_dev(self.h, d_dead_tids_sorted, n_dead, C.byref(st)))
+        return st.as_dict()
+
     def refresh_norms(self):
         check(self._L.vs_index_refresh_norms(self.h))
 

@@ -8,7 +8,8 @@ column (`vecs`, needed for rerank).  The MetaPage body (geometry, start nodes, t
 `meta()` / `upload_from_meta()` (vs_pages_meta), or passed by hand to `upload()`.
 
 The way back is `PagesOut` (vs_pages_out_*): a device-resident index written out as the same relation, block range by block
-range, and `encode_meta_page` next to `decode_meta_page`.
+range — or, against a `PagesBase`, only the blocks that changed since it was last written (`delta` / `read_blocks` /
+`patch_file`) — and `encode_meta_page` next to `decode_meta_page`.
 """
 import ctypes as C
 
@@ -403,6 +404,30 @@ class DevicePages:
             self.h = None
 
 
+class PagesBase:
+    """What a relation looked like when a PagesOut last wrote it (vs_pages_base): a digest per node page in device memory and
+    the host-encoded pages.  Outlives the writer and the index it was taken from."""
+
+    def __init__(self, L, h):
+        self._L = L
+        self.h = h
+
+    @property
+    def n_blocks(self):
+        return int(self._L.vs_pages_base_blocks(self.h))
+
+    def close(self):
+        if self.h:
+            self._L.vs_pages_base_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class PagesOut:
     """A device-resident memory_optimized index written out as the pages of a `diskann` index relation (vs_pages_out_*): the
     layout is fixed here, `read` hands out any block range any number of times.  layout: a vs_node_layout 5-tuple (root size, heap
@@ -445,6 +470,57 @@ class PagesOut:
         b, o = C.c_uint32(), C.c_uint32()
         check(self._L.vs_pages_out_item_pointer_of(self.h, node, C.byref(b), C.byref(o)))
         return int(b.value), int(o.value)
+
+    def baseline(self):
+        """the relation exactly as this writer would write it now, as a PagesBase"""
+        h = C.c_void_p()
+        check(self._L.vs_pages_out_baseline(self.h, C.byref(h)))
+        return PagesBase(self._L, h)
+
+    def delta(self, base):
+        """-> (blocks, n_blocks_now, new_base): the blocks (ascending uint32) that are not, byte for byte, what `base` recorded,
+        the relation's size now, and the baseline of the relation as it is now"""
+        nd, nb, h = C.c_uint32(), C.c_uint32(), C.c_void_p()
+        check(self._L.vs_pages_out_delta(self.h, base.h, C.byref(nd), C.byref(nb), C.byref(h)))
+        new_base = PagesBase(self._L, h)
+        blocks = np.empty(int(nd.value), np.uint32)
+        check(self._L.vs_pages_out_delta_blocks(self.h, blocks.ctypes.data_as(C.c_void_p), blocks.size))
+        return blocks, int(nb.value), new_base
+
+    def read_blocks(self, blocks, out=None):
+        """the gathered form of read: page i of the result is block blocks[i] (any order, repeats allowed)"""
+        b = np.ascontiguousarray(blocks, np.uint32)
+        if out is None:
+            out = np.empty(b.size * self.page_size, np.uint8)
+        assert out.flags["C_CONTIGUOUS"] and out.nbytes >= b.size * self.page_size
+        check(self._L.vs_pages_out_read_blocks(self.h, b.ctypes.data_as(C.c_void_p), b.size, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def read_blocks_dev(self, dev_ptr, blocks):
+        """the same into device memory (Context.alloc)"""
+        b = np.ascontiguousarray(blocks, np.uint32)
+        check(self._L.vs_pages_out_read_blocks_dev(self.h, b.ctypes.data_as(C.c_void_p), b.size, dev_ptr))
+
+    def patch_file(self, path, base, chunk_blocks=16384):
+        """bring the relation file at `path` (as `base` recorded it) up to date in place: the dirty blocks are written where they
+        belong, the file is extended or truncated to the relation's size now -> the new baseline"""
+        blocks, nb, new_base = self.delta(base)
+        ps = self.page_size
+        buf = np.empty(min(chunk_blocks, max(blocks.size, 1)) * ps, np.uint8)
+        with open(path, "r+b") as f:
+            f.truncate(nb * ps)
+            for i0 in range(0, blocks.size, chunk_blocks):
+                part = blocks[i0:i0 + chunk_blocks]
+                self.read_blocks(part, out=buf)
+                j = 0
+                while j < part.size:  # one write per run of adjacent blocks
+                    e = j + 1
+                    while e < part.size and part[e] == part[e - 1] + 1:
+                        e += 1
+                    f.seek(int(part[j]) * ps)
+                    f.write(buf[j * ps:e * ps].data)
+                    j = e
+        return new_base
 
     def write_file(self, path, chunk_blocks=16384):
         """the relation's main fork as one file, streamed chunk by chunk"""

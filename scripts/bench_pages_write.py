@@ -13,6 +13,16 @@ kernel time of pipeline fill.  Nothing here asserts a speed; the bytes of (b) ar
     python scripts/bench_pages_write.py --out profiles/r09/s1_pages_write_4m.txt
     python scripts/bench_pages_write.py --dim 1536 --labels 32 --cosine --append --out profiles/r09/s1_pages_write_4m.txt
 
+--delta adds the page-by-page leg on the same index, in the same session as the legs above: baseline -> bulk_delete of 40 000 TIDs
+drawn at random -> insert of 4 096 rows -> delta + read_blocks.  It records the digest pass against the full k_pages_encode pass
+(HIP events, alternated --reps times), bulk_delete (host clock), delta + read_blocks end to end against vs_pages_out_read of the whole
+relation (host clock, alternated), and the number of dirty blocks out of the total.  Two expectations are reported against, each
+with the session's own spread as the margin: the digest pass does not take longer than the encode pass; delta + read_blocks beats
+the full read by roughly the ratio of blocks moved.
+
+    python scripts/bench_pages_write.py --delta --out profiles/r10/s1_pages_delta_4m.txt
+    python scripts/bench_pages_write.py --delta --dim 1536 --labels 32 --cosine --append --out profiles/r10/s1_pages_delta_4m.txt
+
 --open-only times vs_pages_out_open alone on an index whose arrays are allocated but not built (the layout depends on n, W, R and
 the label sets only), so that the labeled open pass can be timed at a size whose build would take minutes:
 
@@ -65,6 +75,86 @@ def timed_open(P, PagesOut, ctx, ix, a, say):
     return out, t_open, node_pages
 
 
+def delta_leg(P, PagesOut, ctx, ix, out, dbuf, host, a, say):
+    """the page-by-page leg (module docstring); closes `out`, leaves the index mutated"""
+    from pgvectorscale_amd import _lib
+    from pgvectorscale_amd.datagen import DatagenParams, rows_numpy
+    nb0 = out.n_blocks
+    # the digest pass against the full encode pass, alternated
+    base = out.baseline()  # warm-up: code object load
+    base.close()
+    ctx.profile_enable(True)
+    ctx.profile_read(reset=True)
+    dig_ms, enc_ms = [], []
+    for rep in range(a.reps):
+        base = out.baseline()
+        dig_ms.append(ctx.profile_read(reset=True)["pages_encode"][0])
+        out.read_dev(dbuf)
+        enc_ms.append(ctx.profile_read(reset=True)["pages_encode"][0])
+        if rep < a.reps - 1:
+            base.close()
+    ctx.profile_enable(False)
+    spread = max(max(dig_ms) - min(dig_ms), max(enc_ms) - min(enc_ms))
+    say(f"(d) digest pass (k_pages_encode<DIGEST>, {nb0} blocks): {' '.join(f'{x:.3f}' for x in dig_ms)} ms; full encode pass: "
+        f"{' '.join(f'{x:.3f}' for x in enc_ms)} ms; expectation median(digest) <= median(encode) + spread ({spread:.3f} ms): "
+        f"{'met' if np.median(dig_ms) <= np.median(enc_ms) + spread else 'NOT met'}")
+    out.close()
+    # vacuum: 40 000 live TIDs drawn at random, unsorted
+    rng = np.random.default_rng(12)
+    tids = ix.download(codes=False, nbrs=False)["heap_tids"]
+    live = np.flatnonzero(tids & np.uint64(0xFFFF))
+    dead = tids[rng.choice(live, min(40000, live.size), replace=False)]
+    t0 = time.perf_counter()
+    st = ix.bulk_delete(dead)
+    t_bd = time.perf_counter() - t0
+    say(f"(e) vs_index_bulk_delete of {dead.size} TIDs over {a.n} nodes: {t_bd * 1e3:.2f} ms (host clock, staging and sort included); {st}")
+    # aminsert: 4 096 rows
+    n_new = 4096
+    new = rows_numpy(DatagenParams(seed=8, dim=a.dim), a.n, n_new)
+    new_tids = ((np.arange(a.n, a.n + n_new, dtype=np.uint64) + 1) << np.uint64(16)) | np.uint64(1)
+    labels = None
+    if a.labels:
+        from bench import zipf_labels
+        lo, lv = zipf_labels(np, n_new, a.labels, 109, 1, 3)
+        labels = [lv[lo[i]:lo[i + 1]].tolist() for i in range(n_new)]
+    t0 = time.perf_counter()
+    ist = ix.insert(new, new_tids, labels=labels, search_list_size=a.build_list)
+    say(f"(f) vs_index_insert of {n_new} rows: {(time.perf_counter() - t0) * 1e3:.1f} ms; {ist}")
+    out = PagesOut(ix, search_list_size=a.build_list)
+    nb1 = out.n_blocks
+    if nb1 * out.page_size > host.size:
+        host = np.zeros(nb1 * out.page_size, np.uint8)
+    blocks, nb_now, nbase = out.delta(base)  # warm-up
+    nbase.close()
+    out.read_blocks(blocks, out=host)
+    out.read(out=host)
+    td, tf = [], []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        blocks, nb_now, nbase = out.delta(base)
+        out.read_blocks(blocks, out=host)
+        td.append(time.perf_counter() - t0)
+        nbase.close()
+        t0 = time.perf_counter()
+        out.read(out=host)
+        tf.append(time.perf_counter() - t0)
+    # the patched blocks are the blocks of the full read
+    full = out.read(out=host).reshape(nb1, out.page_size)
+    same = bool((out.read_blocks(blocks).reshape(-1, out.page_size) == full[blocks]).all())
+    ratio = nb1 / max(blocks.size, 1)
+    speedup = np.median(tf) / np.median(td)
+    margin = (max(tf) - min(tf)) + (max(td) - min(td))
+    say(f"(g) dirty blocks: {blocks.size} of {nb1} ({100.0 * blocks.size / nb1:.2f} %; the relation grew from {nb0} blocks); delta + read_blocks: "
+        f"{' '.join(f'{x * 1e3:.1f}' for x in td)} ms; vs_pages_out_read of the whole relation: {' '.join(f'{x * 1e3:.1f}' for x in tf)} ms; "
+        f"medians {np.median(td) * 1e3:.1f} / {np.median(tf) * 1e3:.1f} ms = {speedup:.1f}x against {ratio:.1f}x fewer blocks moved "
+        f"(spread of the two legs {margin * 1e3:.1f} ms); bytes identical to the full read: {same}")
+    out.close()
+    base.close()
+    return dict(blocks_before=nb0, blocks_after=nb1, dirty=int(blocks.size), digest_ms=[round(x, 3) for x in dig_ms],
+                encode_ms=[round(x, 3) for x in enc_ms], bulk_delete_ms=round(t_bd * 1e3, 2), delta_read_ms=[round(x * 1e3, 1) for x in td],
+                full_read_ms=[round(x * 1e3, 1) for x in tf], bytes_identical=same)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=4_000_000)
@@ -77,6 +167,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None)
     ap.add_argument("--append", action="store_true")
+    ap.add_argument("--delta", action="store_true", help="add the baseline / bulk_delete / insert / delta + read_blocks leg")
     ap.add_argument("--open-only", action="store_true", help="time vs_pages_out_open on an allocated, unbuilt index and stop")
     a = ap.parse_args()
 
@@ -188,9 +279,13 @@ def main():
     res = dict(n=a.n, dim=a.dim, bits=int(d.bits), R=a.R, labels=a.labels, blocks=nb, node_pages=node_pages, open_ms=round(t_open * 1e3, 1),
                kernel_ms=[round(x, 3) for x in k_ms], read_ms=[round(x * 1e3, 1) for x in tb], download_ms=[round(x * 1e3, 1) for x in tc],
                bytes_identical=same)
+    if a.delta:
+        res["delta"] = delta_leg(P, PagesOut, ctx, ix, out, dbuf, host, a, say)
+        out = None
     say(json.dumps(res))
     ctx.free(dbuf)
-    out.close()
+    if out is not None:
+        out.close()
     ix.close()
     ctx.close()
     flush()
