@@ -243,6 +243,53 @@ typedef struct vs_bulk_delete_stats { /* IndexBulkDeleteResult, AM/vacuum.rs:122
 } vs_bulk_delete_stats;
 int vs_index_bulk_delete(vs_index* idx, const uint64_t* dead_tids, uint64_t n_dead, vs_bulk_delete_stats* out /* may be NULL */);
 int vs_index_bulk_delete_dev(vs_index* idx, const uint64_t* d_dead_tids_sorted, uint64_t n_dead, vs_bulk_delete_stats* out);
+/* ---- consolidation of deleted rows (what a PGRX shim calls from amvacuumcleanup, after ambulkdelete) -------------------------
+ * Neither the reference nor vs_index_bulk_delete cleans up after a delete: a tombstone (heap offset 0) keeps its neighbor list
+ * and every in-edge live rows hold to it, so scans still gather, score, visit and expand it (only `consume` drops it,
+ * AM/scan.rs:231-234) and an insert links new rows to it.  The reference's only cure is REINDEX.  This call is the consolidation
+ * pass of streaming DiskANN instead: every row that names a deleted neighbor takes over that neighbor's neighbors and is pruned
+ * again.  The rule, evaluated on the graph as it stands when the call starts:
+ *   K = every node whose heap offset is not 0, plus the default start node and every per-label start node even when deleted
+ *       (scans begin there whatever their state); D = every other node.
+ *   Rows of D are never written.  Rows of K that name no node of D stay byte-identical.
+ *   A row p of K that names a node of D gets the candidates { v in N(p), v in K } + { w in N(d), d in N(p) and D, w in K }, without
+ *   p, every id once — one level: a tombstone's tombstone neighbors are not followed — sorted ascending by (Hamming(code[p],
+ *   code[w]), id), cut to the first cand_max (0 = min(4 * num_neighbors, 256); VS_ERR_INVALID unless num_neighbors < cand_max <=
+ *   1024).  At most num_neighbors candidates: they are the row, in that order (add_neighbors, AM/graph/mod.rs:243-256).  More: the
+ *   row is what prune_neighbors selects, in selection order (alpha ladder 1.0, x 1.2f while <= max_alpha; contains_intersection
+ *   relative to p for a labeled index), exactly as vs_build_graph prunes.  The row is padded with VS_INVALID_NODE.
+ *   Then, unless VS_CONSOLIDATE_NO_REPAIR is set, the repair pass of vs_build_graph runs with one difference: a node of D is not
+ *   "lost" — it is meant to be unreachable and is never handed an in-edge again.  CALLING vs_index_repair AFTER A CONSOLIDATION
+ *   WOULD RE-LINK THE TOMBSTONES (it knows no D); use this call's own repair.
+ * What it does not do: it never reclaims a tombstone's node (n and the page layout stay, D rows keep their bytes, so their pages
+ * stay clean for vs_pages_out_delta); it does not re-elect a deleted start node (it stays in K with a clean list); it gives no
+ * guarantee for label-filtered reachability beyond what Graph::insert gives.
+ * Refusals leave every byte as it was: VS_ERR_INVALID for plain storage, an index without codes / neighbor lists / heap tids, a
+ * node with more than 64 labels, max_alpha outside [1,5], a bad cand_max or unknown flags; VS_ERR_STATE while a view of the index
+ * is alive, a batch of this handle is in flight, or a writer opened with vs_pages_out_open has not been closed.  n does not change
+ * and no array moves, but open vs_scans, scan pools and brokers of the index must be ended or rescanned afterwards: their device
+ * state names rows that changed.  Not thread safe against any other call on the index; ordered on the context's stream.
+ * An error after the first rewritten row (a HIP error, memory running out for the repair pass) leaves a usable graph: every row
+ * is rewritten whole by one wave from rows nobody writes, so each row is either its old list or its new one, both valid lists;
+ * calling again finishes the work (a rewritten row names no node of D and is skipped).  `out` then holds what was counted. */
+#define VS_CONSOLIDATE_NO_REPAIR 1u   /* flags: stop after the row rewrite (tests; callers that run the repair themselves) */
+typedef struct vs_consolidate_stats {
+    uint64_t tombstones;         /* nodes whose heap offset is 0 */
+    uint64_t tombstones_kept;    /* of those: default / per-label start nodes, which stay in the graph */
+    uint64_t rows_rewritten;     /* kept nodes whose list named >= 1 dropped tombstone */
+    uint64_t edges_dropped;      /* list entries that named a dropped tombstone */
+    uint64_t edges_added;        /* entries of the new lists that the old lists did not hold */
+    uint64_t rows_pruned;        /* rewritten rows whose candidates exceeded num_neighbors (went through prune) */
+    uint64_t rows_capped;        /* rewritten rows whose de-duplicated candidates exceeded cand_max */
+    uint64_t rows_emptied;       /* rewritten rows left without a neighbor */
+    uint32_t unreachable_live;   /* live nodes the default start node does not reach at return (0xFFFFFFFF: not judged, as
+                                  * vs_index_build_unreachable; also with VS_CONSOLIDATE_NO_REPAIR) */
+} vs_consolidate_stats;
+int vs_index_consolidate_deletes(vs_index* idx, double max_alpha, uint32_t cand_max /* 0 = default */, uint32_t flags,
+                                 vs_consolidate_stats* out /* may be NULL */);
+/* HIP-event milliseconds of the two passes on this index since the last reset, collected while vs_profile_enable is on:
+ * ms[0] the flag pass (node classes, flags, work list), ms[1] k_consolidate_rows */
+int vs_index_consolidate_kernel_ms(vs_index* idx, double* ms, int reset);
 
 /* ---- index relation pages -> vs_index_host (the exporter the arrays above come from) ------
  * The reference reaches a node through the buffer manager, one page pin per neighbor (ItemPointer::read_bytes,
@@ -851,7 +898,8 @@ int vs_batch_mates(vs_index* idx, const uint64_t* codes, uint32_t n, uint32_t c,
 int vs_batch_mates_filtered(vs_index* idx, const uint64_t* codes, const uint32_t* label_off, const int16_t* label_val, uint32_t n,
                             uint32_t c, uint32_t* out_ids, uint32_t* out_ham);
 /* the repair pass of vs_build_graph on its own (after many inserts, at the caller's choice): every node the default start node does
- * not reach is given an in-edge where that strands nobody else; *unreachable (may be NULL) = what vs_index_build_unreachable reports */
+ * not reach is given an in-edge where that strands nobody else; *unreachable (may be NULL) = what vs_index_build_unreachable reports.
+ * It treats a tombstone like any node: after vs_index_consolidate_deletes it would hand the dropped tombstones in-edges again. */
 int vs_index_repair(vs_index* idx, uint32_t* unreachable);
 
 /* ---- synthetic corpora generated in HBM (bench / tests; bit-reproducible on the CPU, see pgvectorscale_amd/datagen.py) */

@@ -420,10 +420,28 @@ int vs_index_live_views(vs_index* ix) {
     const auto it = vs_view_count.find(ix->owner_id);
     return it == vs_view_count.end() ? 0 : it->second;
 }
+// writers opened with vs_pages_out_open hold the array pointers and a page layout fixed at open: counted the same way, for the entry
+// points that rewrite rows in place and must not run under an open writer (vs_index_consolidate_deletes)
+static std::unordered_map<uint64_t, int> vs_writer_count;  // owner id -> open writers
+int vs_index_open_writers(const vs_index* ix) {
+    std::lock_guard<std::mutex> lk(vs_view_mu);
+    const auto it = vs_writer_count.find(ix->owner_id);
+    return it == vs_writer_count.end() ? 0 : it->second;
+}
+void vs_index_writer_opened(uint64_t owner_id) {
+    std::lock_guard<std::mutex> lk(vs_view_mu);
+    vs_writer_count[owner_id]++;
+}
+void vs_index_writer_closed(uint64_t owner_id) {
+    std::lock_guard<std::mutex> lk(vs_view_mu);
+    const auto it = vs_writer_count.find(owner_id);  // (gone when the index was freed first)
+    if (it != vs_writer_count.end() && --it->second <= 0) vs_writer_count.erase(it);
+}
 extern "C" void vs_index_free(vs_index* ix) {
     if (!ix) return;
     {
         std::lock_guard<std::mutex> lk(vs_view_mu);
+        if (!ix->is_view) vs_writer_count.erase(ix->owner_id);
         if (ix->is_view) {
             const auto it = vs_view_count.find(ix->owner_id);  // (gone when the owner was freed first)
             if (it != vs_view_count.end() && --it->second <= 0) vs_view_count.erase(it);

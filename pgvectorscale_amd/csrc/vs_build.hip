@@ -17,6 +17,7 @@
 // to carry (update_start_nodes, AM/graph/mod.rs:490-531), and prune_neighbors only lets an existing neighbor occlude a
 // candidate when it carries every label the candidate shares with the point (contains_intersection,
 // AM/labels/mod.rs:85-111, used at AM/graph/mod.rs:442-456).
+#include <algorithm>
 #include <cstdlib>
 #include <map>
 #include <vector>
@@ -941,7 +942,10 @@ struct BatchRunner {
 
 // repair pass (see k_reach_sweep): rounds of { reachable set, in-edges for the nodes outside it } until a sweep finds every
 // node (at most eight); what the last sweep still could not reach is reported by vs_index_build_unreachable()
-static int repair_graph(vs_index* ix, BuildBufs& B) {
+// cls (vs_index_consolidate_deletes only; nullptr: every node counts, as always): per node 0 = live, 1 = a tombstone the consolidation
+// dropped from the graph, 2 = a tombstone kept as a start node.  A dropped tombstone is not "lost": it is meant to be unreachable and
+// is never handed an in-edge; build_unreachable then counts the LIVE nodes the sweep did not reach.
+static int repair_graph(vs_index* ix, BuildBufs& B, const uint8_t* cls = nullptr) {
     hipStream_t st = ix->ctx->stream;
     const uint32_t n = ix->d.n, R = ix->d.num_neighbors;
     if (n <= 2) return VS_OK;  // (nothing a sweep could find)
@@ -974,9 +978,13 @@ static int repair_graph(vs_index* ix, BuildBufs& B) {
         VS_HIP(hipMemcpyAsync(reached.data(), B.mark, n, hipMemcpyDeviceToHost, st));
         VS_HIP(hipStreamSynchronize(st));
         lost.clear();
+        uint32_t lost_live = 0;
         for (uint32_t i = 0; i < n; ++i)
-            if (!reached[i]) lost.push_back(i);
-        ix->build_unreachable = (uint32_t)lost.size();  // (what the last completed sweep found; 0 when the loop ends here)
+            if (!reached[i] && !(cls && cls[i] == 1)) {
+                lost.push_back(i);
+                lost_live += !cls || cls[i] == 0;
+            }
+        ix->build_unreachable = cls ? lost_live : (uint32_t)lost.size();  // (what the last completed sweep found; 0 when the loop ends here)
         if (lost.empty() || round == 7) break;
         // Each of them takes a slot in the list of its closest reachable out-neighbor — a free one, else that of the last
         // entry that keeps an in-edge from a node of a strictly lower BFS level (indeg[] counts only those: a lower-level
@@ -1047,6 +1055,7 @@ static int repair_graph(vs_index* ix, BuildBufs& B) {
                     const uint32_t* rowu = &lrows[(size_t)lidx[u] * R];
                     for (uint32_t t = 0; t < R && rowu[t] != VS_INVALID_NODE; ++t) {
                         const uint32_t v = rowu[t];
+                        if (cls && cls[v] == 1) continue;  // (a stale edge to a dropped tombstone leads nowhere a scan should go)
                         if (!reached[v]) {
                             reached[v] = 1;
                             level[v] = level[u] + 1;
@@ -1650,4 +1659,448 @@ extern "C" int vs_index_bulk_delete(vs_index* ix, const uint64_t* dead_tids, uin
 }
 extern "C" int vs_index_bulk_delete_dev(vs_index* ix, const uint64_t* d_dead_tids_sorted, uint64_t n_dead, vs_bulk_delete_stats* out) {
     return vs_guard("vs_index_bulk_delete_dev", [&] { return bulk_delete_impl(ix, "vs_index_bulk_delete_dev", d_dead_tids_sorted, n_dead, true, out); });
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// vs_index_consolidate_deletes: the consolidation pass of streaming DiskANN over the tombstones ambulkdelete leaves behind
+// (DESIGN.md section 6d has the rule).  K = the nodes that stay in the graph (live, or a start node), D = the other tombstones.
+// Every row of K that names a node of D is rewritten from { its entries in K } + { the entries in K of the rows of its D
+// entries }, one level deep, sorted by (Hamming to the row's node, id), cut to cand_max and pruned like any other candidate
+// list.  Rows of D are never written and rows of K read only their own list and lists of D nodes: the pass runs in place.
+// ---------------------------------------------------------------------------------------------------------------
+enum { CN_TOMB = 0, CN_KEPT, CN_EDGES_DROPPED, CN_EDGES_ADDED, CN_PRUNED, CN_CAPPED, CN_EMPTIED, CN_WIDE_LABELS, CN_N = 8 };
+
+// node classes from the tid column: 0 live, 1 tombstone (k_cons_keep_starts turns the start nodes among them into 2)
+__global__ __launch_bounds__(256) void k_cons_classify(const uint64_t* __restrict__ tids, const uint32_t* __restrict__ label_off, uint32_t n,
+                                                       uint8_t* __restrict__ cls, unsigned long long* __restrict__ cnt) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    bool dead = false, wide = false;
+    if (i < n) {
+        dead = (tids[i] & 0xFFFFull) == 0;
+        cls[i] = dead ? 1 : 0;
+        if (label_off) wide = label_off[i + 1] - label_off[i] > 64;  // (label_pmask holds a point's labels in one 64-bit mask)
+    }
+    const uint64_t md = __ballot(dead), mw = __ballot(wide);
+    if ((threadIdx.x & (WAVE - 1)) == 0) {
+        if (md) atomicAdd(&cnt[CN_TOMB], (unsigned long long)__popcll(md));
+        if (mw) atomicAdd(&cnt[CN_WIDE_LABELS], (unsigned long long)__popcll(mw));
+    }
+}
+// starts: the default start node and the per-label start nodes, every node once (the host de-duplicates)
+__global__ void k_cons_keep_starts(const uint32_t* __restrict__ starts, uint32_t ns, uint8_t* __restrict__ cls,
+                                   unsigned long long* __restrict__ cnt) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ns) return;
+    const uint32_t s = starts[t];
+    if (cls[s] == 1) {
+        cls[s] = 2;
+        atomicAdd(&cnt[CN_KEPT], 1ull);
+    }
+}
+// the flag pass over the n x R neighbor cells: a kept row that names a dropped tombstone is work; the cells that do are edges_dropped
+__global__ __launch_bounds__(256) void k_cons_flag(const uint32_t* __restrict__ nbrs, uint32_t nbr_stride, uint32_t R, uint32_t n,
+                                                   const uint8_t* __restrict__ cls, uint8_t* __restrict__ flag,
+                                                   unsigned long long* __restrict__ cnt) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    bool hit = false;
+    if (i < (size_t)n * R) {
+        const size_t row = i / R;
+        if (cls[row] != 1) {
+            const uint32_t v = nbrs[row * nbr_stride + (i % R)];
+            hit = v < n && cls[v] == 1;
+            if (hit) flag[row] = 1;
+        }
+    }
+    const uint64_t m = __ballot(hit);
+    if ((threadIdx.x & (WAVE - 1)) == 0 && m) atomicAdd(&cnt[CN_EDGES_DROPPED], (unsigned long long)__popcll(m));
+}
+// The flagged rows as an ascending work list — flagged rows per wave of 64 rows (ballot), one exclusive scan over the waves' counts,
+// then every flagged row writes itself at its wave's offset + its rank among the wave's flagged lanes (the three passes
+// vs_pages_out_delta compacts its dirty pages with): the order is the rows' own, not that of an atomic slot counter.
+__global__ __launch_bounds__(256) void k_cons_work_count(const uint8_t* __restrict__ flag, uint32_t n, uint32_t* __restrict__ wave_cnt) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    const uint64_t m = __ballot(i < n && flag[i] != 0);
+    if ((threadIdx.x & (WAVE - 1)) == 0 && i < n) wave_cnt[i / WAVE] = (uint32_t)__popcll(m);
+}
+// one workgroup: v[0 .. m) becomes its exclusive prefix sums, v[m] the total
+__global__ __launch_bounds__(256) void k_cons_work_scan(uint32_t* __restrict__ v, uint32_t m) {
+    __shared__ uint32_t part[256];
+    const uint32_t per = (m + 255) / 256, lo = min(threadIdx.x * per, m), hi = min(lo + per, m);
+    uint32_t s = 0;
+    for (uint32_t i = lo; i < hi; ++i) s += v[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t run = 0;
+        for (uint32_t t = 0; t < 256; ++t) {
+            const uint32_t c = part[t];
+            part[t] = run;
+            run += c;
+        }
+        v[m] = run;
+    }
+    __syncthreads();
+    uint32_t run = part[threadIdx.x];
+    for (uint32_t i = lo; i < hi; ++i) {
+        const uint32_t c = v[i];
+        v[i] = run;
+        run += c;
+    }
+}
+__global__ __launch_bounds__(256) void k_cons_work_scatter(const uint8_t* __restrict__ flag, uint32_t n, const uint32_t* __restrict__ wave_off,
+                                                           uint32_t* __restrict__ work) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & (WAVE - 1);
+    const bool f = i < n && flag[i] != 0;
+    const uint64_t m = __ballot(f);
+    if (f) work[wave_off[i / WAVE] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = i;
+}
+
+// LDS of k_consolidate_rows (bytes): two key lists of cap entries (the merge writes one from the other), the keys of the rows being
+// gathered, the arrays wave_prune works on, and the code rows — of the <= R rows in flight while merging, of the surviving
+// candidates while pruning (the same area; cap > R)
+struct ConsLds {
+    uint32_t cap4, R4, code_rows;
+    size_t bytes;
+};
+static ConsLds cons_lds(uint32_t cap, uint32_t R, uint32_t stride, bool labeled, bool lds_codes, bool stage_rows) {
+    ConsLds l;
+    l.cap4 = round_up_u32(cap, 4);
+    l.R4 = round_up_u32(R, 4);
+    l.code_rows = lds_codes ? l.cap4 : (stage_rows ? l.R4 : 0);
+    l.bytes = (size_t)l.cap4 * (16 + (labeled ? 8 : 0) + 12) + (size_t)l.R4 * (8 + 16) + (size_t)l.code_rows * stride * 8;
+    return l;
+}
+
+// one wave per work-list entry p
+__global__ __launch_bounds__(WAVE) void k_consolidate_rows(const uint64_t* __restrict__ codes, uint32_t stride, uint32_t* nbrs,
+                                                           uint32_t nbr_stride, uint32_t R, uint32_t n, float max_alpha, uint32_t cap,
+                                                           const uint32_t* __restrict__ work, uint32_t nwork,
+                                                           const uint8_t* __restrict__ cls, uint32_t use_lds_codes, uint32_t stage_rows,
+                                                           const uint32_t* __restrict__ label_off, const int16_t* __restrict__ label_val,
+                                                           unsigned long long* __restrict__ cnt) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x;
+    const uint64_t below = (1ull << lane) - 1ull;
+    const uint32_t cap4 = round_up_u32(cap, 4), R4 = round_up_u32(R, 4);
+    uint64_t* ka = reinterpret_cast<uint64_t*>(smem);  // [cap4] sorted keys (distance << 32) | id ...
+    uint64_t* kb = ka + cap4;                           // [cap4] ... and the list the next merge writes
+    uint64_t* inc = kb + cap4;                          // [R4] keys of the rows being merged in
+    uint64_t* pm = inc + R4;                            // [cap4] label masks relative to p (labeled sets only)
+    uint32_t* cid = reinterpret_cast<uint32_t*>(pm + (label_off ? cap4 : 0));
+    uint32_t* cd = cid + cap4;
+    float* maxf = reinterpret_cast<float*>(cd + cap4);
+    uint32_t* sel = reinterpret_cast<uint32_t*>(maxf + cap4);  // [R4] (while merging: the duplicate marks of inc[])
+    uint32_t* oldrow = sel + R4;                                // [R4] p's list as it was
+    uint32_t* tomb = oldrow + R4;                               // [R4] its entries in D
+    uint32_t* gid = tomb + R4;                                  // [R4] ids of the rows being gathered
+    uint64_t* ccode = reinterpret_cast<uint64_t*>(gid + R4);
+    for (uint32_t wi = blockIdx.x; wi < nwork; wi += gridDim.x) {
+        const uint32_t p = work[wi];
+        uint32_t* row = nbrs + (size_t)p * nbr_stride;
+        const uint64_t* cp = codes + (size_t)p * stride;
+        ulonglong2 pc[12];  // p's code (768 x 2 bit / 1536 x 1 bit): every distance of this row is taken against it
+        if (stride == 24) {
+#pragma unroll
+            for (int t = 0; t < 12; ++t) pc[t] = *reinterpret_cast<const ulonglong2*>(cp + 2 * t);
+        }
+        auto dist_to_p = [&](const uint64_t* c) -> uint32_t {
+            if (stride != 24) return ham_words(c, cp, stride);
+            ulonglong2 x[12];
+#pragma unroll
+            for (int t = 0; t < 12; ++t) x[t] = *reinterpret_cast<const ulonglong2*>(c + 2 * t);
+            uint32_t acc = 0;
+#pragma unroll
+            for (int t = 0; t < 12; ++t) acc += (uint32_t)__popcll(x[t].x ^ pc[t].x) + (uint32_t)__popcll(x[t].y ^ pc[t].y);
+            return acc;
+        };
+        uint64_t* cur = ka;
+        uint64_t* nxt = kb;
+        uint32_t T = 0;
+        bool capped = false;
+        // gid[0 .. ng) -> keys, each new id once, merged into the sorted list cur[0 .. T), the closest `cap` kept
+        auto merge_gathered = [&](uint32_t ng) {
+            if (ng == 0) return;  // (uniform)
+            if (stage_rows) {  // the rows' codes in flight together, not one latency per candidate
+                stage_codes(ccode, codes, gid, ng, stride, lane);
+                __syncthreads();
+            }
+            for (uint32_t t = lane; t < ng; t += WAVE) {
+                const uint32_t id = gid[t];
+                inc[t] = ((uint64_t)dist_to_p(stage_rows ? ccode + (size_t)t * stride : codes + (size_t)id * stride) << 32) | id;
+            }
+            __syncthreads();
+            for (uint32_t t = lane; t < ng; t += WAVE) {  // an equal key is a duplicate (the distance is a function of the id)
+                const uint64_t k = inc[t];
+                uint32_t lo = 0, hi = T;
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if (cur[mid] < k) lo = mid + 1;
+                    else hi = mid;
+                }
+                bool dup = lo < T && cur[lo] == k;
+                for (uint32_t u = 0; u < t && !dup; ++u) dup = inc[u] == k;
+                sel[t] = dup ? 1u : 0u;
+            }
+            __syncthreads();
+            uint32_t m = 0;
+            for (uint32_t t0 = 0; t0 < ng; t0 += WAVE) {
+                const uint32_t t = t0 + lane;
+                const bool ok = t < ng && sel[t] == 0;
+                if (t < ng && !ok) inc[t] = ~0ull;
+                m += (uint32_t)__popcll(__ballot(ok));
+            }
+            __syncthreads();
+            if (m == 0) return;  // (uniform)
+            for (uint32_t i = lane; i < T; i += WAVE) {  // every entry's place in the merged order
+                const uint64_t a = cur[i];
+                uint32_t before = 0;
+                for (uint32_t u = 0; u < ng; ++u) before += inc[u] < a;
+                if (i + before < cap) nxt[i + before] = a;
+            }
+            for (uint32_t t = lane; t < ng; t += WAVE) {
+                const uint64_t k = inc[t];
+                if (k == ~0ull) continue;
+                uint32_t lo = 0, hi = T;
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if (cur[mid] < k) lo = mid + 1;
+                    else hi = mid;
+                }
+                uint32_t before = 0;
+                for (uint32_t u = 0; u < ng; ++u) before += inc[u] < k;
+                if (lo + before < cap) nxt[lo + before] = k;
+            }
+            __syncthreads();
+            capped |= T + m > cap;
+            T = min(T + m, cap);
+            uint64_t* sw = cur;
+            cur = nxt;
+            nxt = sw;
+        };
+        // p's own list: the entries in K are the first candidates, the entries in D the rows to take over
+        uint32_t nt = 0, ng = 0;
+        for (uint32_t c0 = 0; c0 < R; c0 += WAVE) {
+            const uint32_t t = c0 + lane;
+            const uint32_t v = t < R ? row[t] : VS_INVALID_NODE;
+            if (t < R) oldrow[t] = v;
+            const bool isd = v < n && cls[v] == 1;
+            const bool keep = v < n && !isd && v != p;
+            const uint64_t dm = __ballot(isd), km = __ballot(keep);
+            if (isd) tomb[nt + (uint32_t)__popcll(dm & below)] = v;
+            if (keep) gid[ng + (uint32_t)__popcll(km & below)] = v;
+            nt += (uint32_t)__popcll(dm);
+            ng += (uint32_t)__popcll(km);
+        }
+        __syncthreads();
+        merge_gathered(ng);
+        for (uint32_t ti = 0; ti < nt; ++ti) {  // one level only: a tombstone's tombstone neighbors are not followed
+            const uint32_t* drow = nbrs + (size_t)tomb[ti] * nbr_stride;
+            ng = 0;
+            for (uint32_t c0 = 0; c0 < R; c0 += WAVE) {
+                const uint32_t t = c0 + lane;
+                const uint32_t w = t < R ? drow[t] : VS_INVALID_NODE;
+                const bool keep = w < n && cls[w] != 1 && w != p;
+                const uint64_t km = __ballot(keep);
+                if (keep) gid[ng + (uint32_t)__popcll(km & below)] = w;
+                ng += (uint32_t)__popcll(km);
+            }
+            __syncthreads();
+            merge_gathered(ng);
+        }
+        for (uint32_t t = lane; t < T; t += WAVE) {
+            const uint64_t k = cur[t];
+            cid[t] = (uint32_t)k;
+            cd[t] = (uint32_t)(k >> 32);
+            if (label_off) pm[t] = label_pmask(label_off, label_val, p, (uint32_t)k);  // as k_build_backedges: relative to the row's node
+        }
+        __syncthreads();
+        uint32_t nres;
+        if (T <= R) {  // Graph::add_neighbors prunes only a candidate list longer than num_neighbors (AM/graph/mod.rs:243-256)
+            for (uint32_t t = lane; t < T; t += WAVE) sel[t] = t;
+            nres = T;
+            __syncthreads();
+        } else {
+            if (use_lds_codes) {
+                stage_codes(ccode, codes, cid, T, stride, lane);
+                __syncthreads();
+            }
+            nres = wave_prune(cid, cd, T, use_lds_codes ? ccode : nullptr, codes, stride, R, max_alpha, maxf, sel, lane,
+                              label_off ? pm : nullptr);
+        }
+        uint32_t added = 0;  // entries of the new list the old one did not hold
+        for (uint32_t t0 = 0; t0 < nres; t0 += WAVE) {
+            const uint32_t t = t0 + lane;
+            bool fresh = t < nres;
+            if (fresh) {
+                const uint32_t id = cid[sel[t]];
+                for (uint32_t u = 0; u < R && fresh; ++u) fresh = oldrow[u] != id;
+            }
+            added += (uint32_t)__popcll(__ballot(fresh));
+        }
+        for (uint32_t t = lane; t < nbr_stride; t += WAVE) row[t] = t < nres ? cid[sel[t]] : VS_INVALID_NODE;
+        if (lane == 0) {
+            if (added) atomicAdd(&cnt[CN_EDGES_ADDED], (unsigned long long)added);
+            if (T > R) atomicAdd(&cnt[CN_PRUNED], 1ull);
+            if (capped) atomicAdd(&cnt[CN_CAPPED], 1ull);
+            if (nres == 0) atomicAdd(&cnt[CN_EMPTIED], 1ull);
+        }
+        __syncthreads();
+    }
+}
+
+static int consolidate_impl(vs_index* ix, double max_alpha, uint32_t cand_max, uint32_t flags, vs_consolidate_stats* out) {
+    const char* what = "vs_index_consolidate_deletes";
+    VS_REQUIRE(ix, "%s: index is NULL", what);
+    if (out) memset(out, 0, sizeof(*out));
+    VS_REQUIRE_OWNER(ix, what);
+    VS_REQUIRE_NO_VIEWS(ix, what);
+    VS_REQUIRE(ix->d.storage_type == VS_STORAGE_SBQ, "%s: plain storage is not supported (memory_optimized indexes only)", what);
+    VS_REQUIRE(ix->codes && ix->nbrs && ix->tids, "%s: needs codes, neighbor lists and heap tids on the device", what);
+    VS_REQUIRE(max_alpha >= 1.0 && max_alpha <= 5.0, "%s: max_alpha outside [1,5]", what);
+    VS_REQUIRE((flags & ~(uint32_t)VS_CONSOLIDATE_NO_REPAIR) == 0, "%s: unknown flags 0x%x", what, flags);
+    const uint32_t n = ix->d.n, R = ix->d.num_neighbors, stride = ix->code_stride;
+    if (cand_max == 0) cand_max = std::min<uint32_t>(4 * R, 256);
+    VS_REQUIRE(cand_max > R && cand_max <= 1024, "%s: cand_max %u outside (num_neighbors = %u, 1024]", what, cand_max, R);
+    if (ix->ws.pending) {
+        vs_set_error("%s: a batch of this handle is in flight (vs_search_batch_dev_finish first)", what);
+        return VS_ERR_STATE;
+    }
+    if (vs_index_open_writers(ix) > 0) {
+        vs_set_error("%s: a vs_pages_out writer of this index is open (its pages would mix rows from before and after; vs_pages_out_close first)", what);
+        return VS_ERR_STATE;
+    }
+    vs_consolidate_stats s{};
+    s.unreachable_live = (flags & VS_CONSOLIDATE_NO_REPAIR) ? 0xFFFFFFFFu : 0u;
+    if (n == 0 || ix->d.default_start == VS_INVALID_NODE) {
+        if (out) *out = s;
+        return VS_OK;
+    }
+    vs_ctx* c = ix->ctx;
+    hipStream_t st = c->stream;
+    VS_HIP(hipSetDevice(c->device));
+    // K keeps the default start node and every per-label start node whatever their state: scans begin there
+    std::vector<uint32_t> starts(1, ix->d.default_start);
+    if (ix->d.n_label_starts) {
+        starts.resize(1 + (size_t)ix->d.n_label_starts);
+        VS_HIP(hipMemcpy(starts.data() + 1, ix->ls_nodes, (size_t)ix->d.n_label_starts * 4, hipMemcpyDeviceToHost));
+    }
+    std::sort(starts.begin(), starts.end());
+    starts.erase(std::unique(starts.begin(), starts.end()), starts.end());
+    VS_REQUIRE(starts.back() < n, "%s: start node %u of an index of %u nodes", what, starts.back(), n);
+    const bool labeled = ix->label_off != nullptr;
+    // the candidate codes sit in LDS while a row is pruned when they fit; failing that, at least the <= R rows a merge gathers
+    bool lds_codes = cons_lds(cand_max, R, stride, labeled, true, true).bytes <= 150 * 1024;
+    bool stage_rows = lds_codes || cons_lds(cand_max, R, stride, labeled, false, true).bytes <= 150 * 1024;
+    const ConsLds lds = cons_lds(cand_max, R, stride, labeled, lds_codes, stage_rows);
+    VS_REQUIRE(lds.bytes <= 160 * 1024, "%s: num_neighbors %u / cand_max %u need %zu bytes of LDS", what, R, cand_max, lds.bytes);
+    const uint32_t n_waves = (n + WAVE - 1) / WAVE;
+    uint8_t *d_cls = nullptr, *d_flag = nullptr;
+    uint32_t *d_wave = nullptr, *d_work = nullptr, *d_starts = nullptr;
+    unsigned long long* d_cnt = nullptr;
+    unsigned long long h_cnt[CN_N] = {0};
+    uint32_t nwork = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double ms[2] = {0, 0};
+    auto tick = [&] {
+        if (ev[0]) (void)hipEventRecord(ev[0], st);
+    };
+    auto tock = [&](int which) {
+        float t = 0.f;
+        if (ev[0] && hipEventRecord(ev[1], st) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
+            hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess)
+            ms[which] += t;
+    };
+    BuildBufs B;
+    auto run = [&]() -> int {
+        if (c->profiling) {
+            VS_HIP(hipEventCreate(&ev[0]));
+            VS_HIP(hipEventCreate(&ev[1]));
+        }
+        VS_HIP(hipMalloc(&d_cls, (size_t)n));
+        VS_HIP(hipMalloc(&d_flag, (size_t)n));
+        VS_HIP(hipMalloc(&d_wave, ((size_t)n_waves + 1) * 4));
+        VS_HIP(hipMalloc(&d_starts, starts.size() * 4));
+        VS_HIP(hipMalloc(&d_cnt, sizeof h_cnt));
+        VS_HIP(hipMemcpyAsync(d_starts, starts.data(), starts.size() * 4, hipMemcpyHostToDevice, st));
+        VS_HIP(hipMemsetAsync(d_cnt, 0, sizeof h_cnt, st));
+        VS_HIP(hipMemsetAsync(d_flag, 0, (size_t)n, st));
+        tick();
+        const dim3 ngrid((n + 255) / 256);
+        hipLaunchKernelGGL(k_cons_classify, ngrid, dim3(256), 0, st, (const uint64_t*)ix->tids, (const uint32_t*)ix->label_off, n, d_cls, d_cnt);
+        VS_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_cons_keep_starts, dim3(((uint32_t)starts.size() + 255) / 256), dim3(256), 0, st, (const uint32_t*)d_starts,
+                           (uint32_t)starts.size(), d_cls, d_cnt);
+        VS_HIP(hipGetLastError());
+        const size_t cells = (size_t)n * R;
+        hipLaunchKernelGGL(k_cons_flag, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, (const uint32_t*)ix->nbrs, ix->nbr_stride, R, n,
+                           (const uint8_t*)d_cls, d_flag, d_cnt);
+        VS_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_cons_work_count, ngrid, dim3(256), 0, st, (const uint8_t*)d_flag, n, d_wave);
+        VS_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_cons_work_scan, dim3(1), dim3(256), 0, st, d_wave, n_waves);
+        VS_HIP(hipGetLastError());
+        VS_HIP(hipMemcpyAsync(&nwork, d_wave + n_waves, 4, hipMemcpyDeviceToHost, st));
+        VS_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
+        VS_HIP(hipStreamSynchronize(st));
+        VS_REQUIRE(h_cnt[CN_WIDE_LABELS] == 0, "%s: %llu node(s) carry more than 64 labels", what, h_cnt[CN_WIDE_LABELS]);
+        if (nwork) {
+            VS_HIP(hipMalloc(&d_work, (size_t)nwork * 4));
+            hipLaunchKernelGGL(k_cons_work_scatter, ngrid, dim3(256), 0, st, (const uint8_t*)d_flag, n, (const uint32_t*)d_wave, d_work);
+            VS_HIP(hipGetLastError());
+        }
+        tock(0);
+        if (nwork) {
+            VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_consolidate_rows), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            ix->nbr_mask_valid = false;  // (the neighbor lists are about to change: what was derived from them is stale)
+            tick();
+            hipLaunchKernelGGL(k_consolidate_rows, dim3(std::min<uint32_t>(nwork, 1u << 20)), dim3(WAVE), lds.bytes, st, (const uint64_t*)ix->codes,
+                               stride, ix->nbrs, ix->nbr_stride, R, n, (float)max_alpha, cand_max, (const uint32_t*)d_work, nwork,
+                               (const uint8_t*)d_cls, lds_codes ? 1u : 0u, stage_rows ? 1u : 0u, (const uint32_t*)ix->label_off,
+                               (const int16_t*)ix->label_val, d_cnt);
+            VS_HIP(hipGetLastError());
+            tock(1);
+            VS_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
+            VS_HIP(hipStreamSynchronize(st));
+        }
+        if (!(flags & VS_CONSOLIDATE_NO_REPAIR)) {
+            std::vector<uint8_t> cls(n);
+            VS_HIP(hipMemcpy(cls.data(), d_cls, n, hipMemcpyDeviceToHost));
+            ix->nbr_mask_valid = false;
+            ix->build_unreachable = 0;
+            VS_TRY(repair_graph(ix, B, cls.data()));
+            s.unreachable_live = ix->build_unreachable;
+        }
+        return VS_OK;
+    };
+    int rc = run();
+    (void)hipStreamSynchronize(st);
+    B.free_all();
+    void* ps[] = {d_cls, d_flag, d_wave, d_work, d_starts, d_cnt};
+    for (void* p : ps)
+        if (p) (void)hipFree(p);
+    for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    for (int k = 0; k < 2; ++k) ix->consolidate_ms[k] += ms[k];
+    s.tombstones = h_cnt[CN_TOMB];
+    s.tombstones_kept = h_cnt[CN_KEPT];
+    s.rows_rewritten = nwork;
+    s.edges_dropped = h_cnt[CN_EDGES_DROPPED];
+    s.edges_added = h_cnt[CN_EDGES_ADDED];
+    s.rows_pruned = h_cnt[CN_PRUNED];
+    s.rows_capped = h_cnt[CN_CAPPED];
+    s.rows_emptied = h_cnt[CN_EMPTIED];
+    if (out) *out = s;
+    if (rc == VS_OK) rc = vs_validate_graph(ix);
+    return rc;
+}
+extern "C" int vs_index_consolidate_deletes(vs_index* ix, double max_alpha, uint32_t cand_max, uint32_t flags, vs_consolidate_stats* out) {
+    return vs_guard("vs_index_consolidate_deletes", [&] { return consolidate_impl(ix, max_alpha, cand_max, flags, out); });
+}
+extern "C" int vs_index_consolidate_kernel_ms(vs_index* ix, double* ms /*[2]*/, int reset) {
+    VS_REQUIRE(ix && ms, "vs_index_consolidate_kernel_ms: bad args");
+    for (int k = 0; k < 2; ++k) {
+        ms[k] = ix->consolidate_ms[k];
+        if (reset) ix->consolidate_ms[k] = 0;
+    }
+    return VS_OK;
 }

@@ -198,6 +198,7 @@ struct vs_index {
     uint32_t* nbrs = nullptr;
     uint64_t* tids = nullptr;
     double insert_ms[3] = {0, 0, 0};   // HIP-event time of k_batch_mates / k_insert_merge_mates / k_insert_anchor (vs_profile_enable; vs_index_insert_kernel_ms)
+    double consolidate_ms[2] = {0, 0}; // HIP-event time of the flag pass / k_consolidate_rows (vs_profile_enable; vs_index_consolidate_kernel_ms)
     uint32_t build_unreachable = 0;    // nodes the last vs_build_graph left unreachable from the start node (0xFFFFFFFF: not judged)
     const uint8_t* visible = nullptr;  // per node, 0 = the heap fetch finds nothing under the scan's snapshot (nullptr: all visible)
     uint8_t* visible_own = nullptr;    // the library's own copy (vs_index_set_visibility)
@@ -244,6 +245,9 @@ uint64_t vs_new_owner_id();
 WsSlab* vs_slab_new(int device);
 void vs_slab_release(WsSlab* s);
 int vs_index_live_views(vs_index* ix);  // views made of ix that have not been freed yet
+int vs_index_open_writers(const vs_index* ix);  // vs_pages_out writers opened on ix (or a view of it) that have not been closed yet
+void vs_index_writer_opened(uint64_t owner_id);
+void vs_index_writer_closed(uint64_t owner_id);
 // the entry points that free or move the arrays of an index refuse view handles and owners with live views
 #define VS_REQUIRE_OWNER(ix, what)                                                                                                     \
     do {                                                                                                                                \

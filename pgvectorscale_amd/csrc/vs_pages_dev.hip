@@ -656,10 +656,12 @@ struct vs_pages_out {
     uint32_t* d_list = nullptr;  // the node pages of a vs_pages_out_read_blocks call (grow-only)
     size_t list_cap = 0;
     std::vector<uint32_t> delta;  // the dirty blocks of the last vs_pages_out_delta (ascending)
+    uint64_t owner_id = 0;        // != 0: counted among the open writers of that index (vs_index_open_writers)
 };
 
 extern "C" void vs_pages_out_close(vs_pages_out* w) {
     if (!w) return;
+    if (w->owner_id) vs_index_writer_closed(w->owner_id);
     if (w->ctx) (void)hipSetDevice(w->ctx->device);
     if (w->d_page_first) (void)hipFree(w->d_page_first);
     if (w->d_node_block) (void)hipFree(w->d_node_block);
@@ -776,6 +778,8 @@ extern "C" int vs_pages_out_open(vs_index* ix, const vs_pages_out_params* p, vs_
             vs_pages_out_close(w);
             return r;
         }
+        w->owner_id = ix->owner_id;
+        vs_index_writer_opened(w->owner_id);
         *out = w;
         return (int)VS_OK;
     });

@@ -301,6 +301,25 @@ class DiskAnnIndex:
         check(self._L.vs_index_bulk_delete_dev(self.h, d_dead_tids_sorted, n_dead, C.byref(st)))
         return st.as_dict()
 
+    def consolidate_deletes(self, max_alpha=1.2, cand_max=0, repair=True):
+        """vs_index_consolidate_deletes (after bulk_delete): every kept row that names a deleted node takes over that node's
+        neighbors and is pruned again; the tombstones leave the graph (not the arrays).  cand_max 0 = min(4 * num_neighbors, 256).
+        repair=False stops after the row rewrite.  Open scans, pools and brokers of the index must be rescanned afterwards.
+        -> dict of vs_consolidate_stats"""
+        st = _lib.ConsolidateStats()
+        try:
+            check(self._L.vs_index_consolidate_deletes(self.h, max_alpha, cand_max, 0 if repair else _lib.VS_CONSOLIDATE_NO_REPAIR,
+                                                       C.byref(st)))
+        finally:
+            self._refresh()
+        return st.as_dict()
+
+    def consolidate_kernel_ms(self, reset=True):
+        """HIP-event milliseconds of the two consolidation passes since the last reset (Context.profile_enable first)"""
+        ms = (C.c_double * 2)()
+        check(self._L.vs_index_consolidate_kernel_ms(self.h, ms, int(reset)))
+        return {"flag_pass": float(ms[0]), "rows": float(ms[1])}
+
     def refresh_norms(self):
         check(self._L.vs_index_refresh_norms(self.h))
 
