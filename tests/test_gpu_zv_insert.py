@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from helpers import TestIndex, make_vectors
+from lifecycle_checks import fresh_index as _fresh, make_tids as _tids, oracle_of as _oracle_of, well_formed as _well_formed  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -15,49 +16,6 @@ INV = 0xFFFFFFFF
 
 
 # ---- helpers ---------------------------------------------------------------------------------------------------------------------
-def _fresh(gpu_ctx, X, *, distance, bits=None, dim_index=None, R=24, L=48, tids=None, build=True):
-    """an index over the rows of X manufactured on the device: norms, training, codes, graph"""
-    import pgvectorscale_amd as P
-    n, dim = X.shape
-    ix = P.DiskAnnIndex.alloc(gpu_ctx, n=n, dim_full=dim, dim_index=dim_index, bits=bits, num_neighbors=R, distance_type=distance)
-    vp, stride = ix.array(P._lib.ARR_VECS)
-    Xp = np.zeros((max(n, 1), stride), np.float32)
-    Xp[:n, :dim] = X
-    if n:
-        gpu_ctx.upload(vp, Xp[:n])
-        ix.refresh_norms()
-        ix.sbq_train()
-        ix.sbq_quantize_corpus()
-        if tids is not None:
-            gpu_ctx.upload(ix.array(P._lib.ARR_TIDS)[0], np.ascontiguousarray(tids, np.uint64))
-        if build:
-            ix.build_graph(search_list_size=L, max_alpha=1.2)
-    return ix
-
-
-def _tids(first, n):
-    return ((np.arange(first, first + n, dtype=np.uint64) + 11) << np.uint64(16)) | np.uint64(3)
-
-
-def _well_formed(nb, R):
-    n = nb.shape[0]
-    assert nb.shape[1] == R
-    live = nb != INV
-    deg = live.sum(1)
-    assert (live == (np.arange(R)[None, :] < deg[:, None])).all(), "lists must be prefix-packed"
-    assert (nb[live] < n).all()
-    assert not (nb == np.arange(n, dtype=np.uint32)[:, None]).any(), "self loop"
-    s = np.sort(nb, axis=1)
-    assert not ((s[:, 1:] == s[:, :-1]) & (s[:, 1:] != INV)).any(), "a list names a node twice"
-
-
-def _oracle_of(O, ix, host, distance, **kw):
-    mean, m2, cnt = ix.get_quantizer()
-    return O.OracleIndex(codes=host["codes"], nbrs=host["nbrs"], heap_tids=host["heap_tids"], vecs=host["vecs"], mean=mean, m2=m2,
-                         count=cnt, bits=ix.desc.bits, dim_index=ix.desc.dim_index, num_neighbors=ix.desc.num_neighbors,
-                         distance_type=distance, default_start=ix.desc.default_start, **kw)
-
-
 def _parity(O, ix, distance, q, qlabels=None, **kw):
     host = ix.download(vecs=True)
     oidx = _oracle_of(O, ix, host, distance, **kw)
