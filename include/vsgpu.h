@@ -551,6 +551,13 @@ int vs_hamming_gather(vs_index* idx, const uint64_t* qcodes, const uint32_t* ids
  * PgVector::from_datum does, AM/pg_vector.rs:153-155). */
 int vs_rerank(vs_index* idx, const float* q_full, const uint32_t* ids, const uint32_t* off, uint32_t nq, float* out);
 
+/* ---- K4a on its own: what a search prepares of each query before its first expansion (PgVector::from_datum +
+ * SbqSearchDistanceMeasure::new): the device rows as they lie, padding included.  queries: host [nq][dim_full] RAW queries.
+ * out_q_full [nq][vec_stride] floats, out_codes [nq][code_stride] words (NULL allowed; always NULL-tolerant on plain storage, whose
+ * rows carry no code), out_q_index [nq][vec_stride] floats, only for plain storage with dim_index < dim_full (NULL otherwise).  The
+ * strides are those vs_index_array reports for VS_ARR_VECS / VS_ARR_CODES. */
+int vs_prepare_queries(vs_index* idx, const float* queries, uint32_t nq, float* out_q_full, uint64_t* out_codes, float* out_q_index);
+
 /* ---- K5: flat scan — top-k of Hamming distance over ALL codes, order (hamming asc, node id asc) ------------- */
 int vs_scan_topk(vs_index* idx, const uint64_t* qcodes, uint32_t nq, uint32_t k, uint32_t* out_ids, uint32_t* out_ham);
 /* The same with the scan's predicate: only rows whose label set overlaps the query's key (qlabels / qlabel_off: CSR per query, an

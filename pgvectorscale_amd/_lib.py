@@ -241,6 +241,7 @@ SYMBOLS = {
     "vs_quantize": (_i, [_vp, _vp, _u32, _vp]),
     "vs_hamming_gather": (_i, [_vp, _vp, _vp, _vp, _u32, _vp]),
     "vs_rerank": (_i, [_vp, _vp, _vp, _vp, _u32, _vp]),
+    "vs_prepare_queries": (_i, [_vp, _vp, _u32, _vp, _vp, _vp]),
     "vs_scan_topk": (_i, [_vp, _vp, _u32, _u32, _vp, _vp]),
     "vs_scan_topk_filtered": (_i, [_vp, _vp, _vp, _vp, _i, _u32, _u32, _vp, _vp]),
     "vs_search_batch": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, C.POINTER(Stats)]),

@@ -990,3 +990,37 @@ extern "C" int vs_rerank(vs_index* ix, const float* q_full, const uint32_t* ids,
                          float* out) {
     return vs_guard("vs_rerank", [&] { return vs_rerank_impl(ix, q_full, ids, off, nq, out); });
 }
+
+
+// The launches of run_search_chunk's prepare step and nothing else.  The workspace rows are filled with 0xFF bytes first: the buffers
+// are reused from call to call and never cleared, so whatever a kernel leaves unwritten (the stride padding) must show in the copy.
+static int vs_prepare_queries_impl(vs_index* ix, const float* queries, uint32_t nq, float* out_q_full, uint64_t* out_codes,
+                                   float* out_q_index) {
+    VS_REQUIRE(ix && (nq == 0 || (queries && out_q_full)), "vs_prepare_queries: bad args");
+    if (nq == 0) return VS_OK;
+    const bool plain = ix->d.storage_type == VS_STORAGE_PLAIN, slice = plain && ix->d.dim_index < ix->d.dim_full;
+    VS_REQUIRE(!out_q_index || slice, "vs_prepare_queries: out_q_index is for plain storage with dim_index < dim_full");
+    vs_ctx* c = ix->ctx;
+    SearchWorkspace& w = ix->ws;
+    const size_t vec_bytes = (size_t)nq * ix->vec_stride * 4, code_bytes = (size_t)nq * ix->code_stride * 8;
+    VS_TRY(devbuf_reserve(c, w.raw_q, (size_t)nq * ix->d.dim_full * 4));
+    VS_TRY(devbuf_reserve(c, w.q_full, vec_bytes));
+    VS_TRY(devbuf_reserve(c, w.qcodes, code_bytes));
+    VS_TRY(vs_dev_upload(c, w.raw_q.p, queries, (size_t)nq * ix->d.dim_full * 4));
+    VS_HIP(hipMemsetAsync(w.q_full.p, 0xFF, vec_bytes, c->stream));
+    VS_HIP(hipMemsetAsync(w.qcodes.p, 0xFF, code_bytes, c->stream));
+    VS_TRY(launch_prepare_queries(ix, (const float*)w.raw_q.p, nq, (float*)w.q_full.p, (uint64_t*)w.qcodes.p));
+    if (slice) {
+        VS_TRY(devbuf_reserve(c, w.q_index, vec_bytes));
+        VS_HIP(hipMemsetAsync(w.q_index.p, 0xFF, vec_bytes, c->stream));
+        VS_TRY(launch_prepare_index_slice(ix, (const float*)w.raw_q.p, nq, (float*)w.q_index.p));
+    }
+    VS_TRY(vs_dev_download(c, out_q_full, w.q_full.p, vec_bytes));
+    if (out_codes) VS_TRY(vs_dev_download(c, out_codes, w.qcodes.p, code_bytes));
+    if (out_q_index) VS_TRY(vs_dev_download(c, out_q_index, w.q_index.p, vec_bytes));
+    return VS_OK;
+}
+extern "C" int vs_prepare_queries(vs_index* ix, const float* queries, uint32_t nq, float* out_q_full, uint64_t* out_codes,
+                                  float* out_q_index) {
+    return vs_guard("vs_prepare_queries", [&] { return vs_prepare_queries_impl(ix, queries, nq, out_q_full, out_codes, out_q_index); });
+}

@@ -452,6 +452,19 @@ class DiskAnnIndex:
         check(self._L.vs_rerank(self.h, _p(q), _p(ids), _p(off), q.shape[0], _p(out)))
         return [out[off[i]:off[i + 1]] for i in range(len(id_lists))]
 
+    def prepare_queries(self, queries):
+        """What a search prepares of each raw query (vs_prepare_queries): (q_full [nq][vec_stride], codes [nq][code_stride] or None on
+        plain storage, q_index [nq][vec_stride] on plain storage with dim_index < dim_full, else None) — the device rows, padding included."""
+        q = np.ascontiguousarray(queries, np.float32).reshape(-1, self.desc.dim_full)
+        nq = q.shape[0]
+        vec_stride, code_stride = self.array(_lib.ARR_VECS)[1], self.array(_lib.ARR_CODES)[1]
+        plain = self.desc.storage_type == _lib.VS_STORAGE_PLAIN
+        q_full = np.empty((nq, vec_stride), np.float32)
+        codes = None if plain else np.empty((nq, code_stride), np.uint64)
+        q_index = np.empty((nq, vec_stride), np.float32) if plain and self.desc.dim_index < self.desc.dim_full else None
+        check(self._L.vs_prepare_queries(self.h, _p(q), nq, _p(q_full), _p(codes), _p(q_index)))
+        return q_full, codes, q_index
+
     def scan_topk(self, qcodes, k, qlabels=None, live_only=False):
         """flat SBQ scan: exact top-k of the Hamming distance, order (hamming, node id); qlabels (one label list per query) /
         live_only restrict it to the rows a label-filtered scan may return"""

@@ -19,7 +19,7 @@ EMU_DIR = os.path.join(ROOT, "tests", "emu")
 
 SUBSET = ("test_hip_path_reproduces_golden or test_index_from_pages_searches_like_the_oracle or "
           "(test_every_regime_is_exact and labels_deleted) or (test_search_rows_match_oracle and (cosine_768 or tiny_L)) or "
-          "(test_sbq_stream_bit_exact and (three_bits or big_R)) or (test_rerank_matches_reference_order and 100) or "
+          "(test_sbq_stream_bit_exact and (three_bits or big_R)) or test_rerank_matches_reference_order or test_rerank_window_small_dims or "
           "test_scan_topk or test_train_and_quantize_corpus_bit_exact or test_deleted_label_null_and_exhaustive or "
           "test_concurrent_scans_are_batched_and_exact or test_client_processes_share_launches or test_pages_decoded_on_the_device or (test_plain_storage_rows_match_the_oracle and 100) or "
           "(test_rows_and_stats_one_row_at_a_time and (l2_window or labels_deleted)) or test_scan_that_outgrows_its_capacities or "
@@ -32,7 +32,9 @@ SUBSET = ("test_hip_path_reproduces_golden or test_index_from_pages_searches_lik
           "test_a_client_that_rewrites_its_request_after_posting_cannot_move_the_dispatcher or test_replica_on_a_second_context_outlives_its_source or (test_multi_search_batch_returns_the_single_device_rows and 33) or "
           "test_comm_world_of_one_gathers_and_replicates or test_entry_points_that_move_the_arrays_refuse_while_a_view_is_alive or "
           "test_placement_never_changes_a_row or test_pooled_scans_hand_out_the_oracles_rows_and_stats or test_a_round_carries_the_listed_scans_that_are_streamed_ahead or (test_every_regime_is_exact and tableless_q16_tight) or "
-          "test_handles_return_their_device_memory or test_deep_scans_stream_on_lanes or test_shm_server_with_lanes_gives_its_memory_back or test_staging_ring_round_trip or test_row_wise_staging_pads_and_copies_every_row")
+          "test_handles_return_their_device_memory or test_deep_scans_stream_on_lanes or test_shm_server_with_lanes_gives_its_memory_back or test_staging_ring_round_trip or test_row_wise_staging_pads_and_copies_every_row or "
+          "test_code_widths or test_wave_count_boundaries or test_fewer_queries_than_waves or test_refusal_past_the_lds_limit or test_rounds or "
+          "test_quantiser_edges or test_cosine_edges or test_plain_storage_index_slice or test_misaligned_device_queries or test_row_norms")
 
 
 @pytest.fixture(scope="module")

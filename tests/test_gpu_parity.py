@@ -67,8 +67,12 @@ def test_hamming_gather_bit_exact(gpu_ctx, oracle, words):
     ix.close()
 
 
+# below one 32-float step of rerank_row_dist (steps == 0: the scalar tail alone) and off the float4 grid
+SMALL_DIMS = [1, 2, 3, 5, 7, 31, 33, 35, 63, 65]
+
+
 @pytest.mark.parametrize("distance", ["L2", "COSINE", "IP"])
-@pytest.mark.parametrize("dims", [128, 768, 100, 36])
+@pytest.mark.parametrize("dims", [128, 768, 100, 36] + SMALL_DIMS)
 def test_rerank_matches_reference_order(gpu_ctx, oracle, distance, dims):
     O = oracle
     dt = getattr(O, distance)
@@ -103,6 +107,44 @@ def test_rerank_matches_reference_order(gpu_ctx, oracle, distance, dims):
     print(f"rerank {distance} d={dims}: {exact}/{total} bit-identical to the AVX2-order oracle")
     assert exact == total  # stronger than the bar: the kernel replays the accumulation order exactly
     ix.close()
+
+
+@pytest.mark.parametrize("distance", ["L2", "COSINE", "IP"])
+@pytest.mark.parametrize("dims", SMALL_DIMS)
+def test_rerank_window_small_dims(gpu_ctx, oracle, distance, dims):
+    """The same row distance inside k_rerank_window: a tiny complete graph, every row rescored (rescore = k = n), ids and distance
+    bits against the oracle.  The inputs are finite and their distances distinct, so the window's tie replay stays out of it (a
+    cosine distance of one dimension is 0 or 2: two rows)."""
+    import pgvectorscale_amd as P
+    O = oracle
+    dt = getattr(O, distance)
+    n = 40 if not (dt == O.COSINE and dims < 3) else (2 if dims == 1 else 12)
+    rng = np.random.default_rng(dims * 3 + dt)
+    X = (rng.standard_normal((n, dims)) * rng.uniform(0.5, 2, (n, 1))).astype(np.float32)
+    if dims == 1:
+        X[:2, 0] = [0.75, -1.5]
+    Q = rng.standard_normal((5, dims)).astype(np.float32)
+    rows = np.stack([O.preprocess_cosine(x)[0] for x in X]) if dt == O.COSINE else X
+    bits = O.default_bits(dims)
+    mean, m2, cnt = O.train(rows, bits)
+    codes = O.quantize(mean, m2, cnt, bits, rows)
+    R = n - 1
+    nbrs = np.array([[j for j in range(n) if j != i] for i in range(n)], np.uint32)
+    tids = ((np.arange(n, dtype=np.uint64) + 7) << np.uint64(16)) | np.uint64(1)
+    kw = dict(codes=codes, nbrs=nbrs, heap_tids=tids, vecs=X, mean=mean, m2=m2, count=cnt, bits=bits, dim_index=dims,
+              num_neighbors=R, distance_type=dt, default_start=0)
+    oi, od, _ = O.OracleIndex(**kw).search_batch(Q, L=n, rescore=n, k=n)
+    assert all(sorted(r.tolist()) == list(range(n)) for r in oi)                            # every row came back ...
+    assert all(len(set(r.tolist())) == n for r in od.view(np.uint32)), "tied distances"     # ... at a distance of its own
+    ix = P.DiskAnnIndex.upload(gpu_ctx, **kw)
+    try:
+        P.set_option("VS_RERANK_FUSED", 1)
+        gi, _, gd, _ = ix.search_batch(Q, search_list_size=n, rescore=n, k=n)
+    finally:
+        P.set_option("VS_RERANK_FUSED", None)
+        ix.close()
+    assert (gi == oi).all()
+    assert (gd.view(np.uint32) == od.view(np.uint32)).all()
 
 
 CONFIGS = {
