@@ -262,7 +262,7 @@ int vs_index_bulk_delete_dev(vs_index* idx, const uint64_t* d_dead_tids_sorted, 
  *   "lost" — it is meant to be unreachable and is never handed an in-edge again.  CALLING vs_index_repair AFTER A CONSOLIDATION
  *   WOULD RE-LINK THE TOMBSTONES (it knows no D); use this call's own repair.
  * What it does not do: it never reclaims a tombstone's node (n and the page layout stay, D rows keep their bytes, so their pages
- * stay clean for vs_pages_out_delta); it does not re-elect a deleted start node (it stays in K with a clean list); it gives no
+ * stay clean for vs_pages_out_delta; vs_index_compact below is the call that reclaims them); it does not re-elect a deleted start node (it stays in K with a clean list); it gives no
  * guarantee for label-filtered reachability beyond what Graph::insert gives.
  * Refusals leave every byte as it was: VS_ERR_INVALID for plain storage, an index without codes / neighbor lists / heap tids, a
  * node with more than 64 labels, max_alpha outside [1,5], a bad cand_max or unknown flags; VS_ERR_STATE while a view of the index
@@ -290,6 +290,63 @@ int vs_index_consolidate_deletes(vs_index* idx, double max_alpha, uint32_t cand_
 /* HIP-event milliseconds of the two passes on this index since the last reset, collected while vs_profile_enable is on:
  * ms[0] the flag pass (node classes, flags, work list), ms[1] k_consolidate_rows */
 int vs_index_consolidate_kernel_ms(vs_index* idx, double* ms, int reset);
+/* ---- compaction: the tombstones leave the arrays and the nodes are renumbered in place (after the consolidation above) --------
+ * The last step of delete -> consolidate -> compact -> insert into the freed room.  Node ids are internal: what leaves the boundary
+ * is the heap tid, and no search ordering depends on an id beyond the id-ordered tie-breaks, which a stable renumbering keeps.
+ * The rule, exact:
+ *   1. K = every node whose heap offset is not 0, plus the default start node and every per-label start node even when deleted —
+ *      the K of vs_index_consolidate_deletes.  D = the rest.
+ *   2. new_of[i] = the number of K nodes below i for i in K, VS_INVALID_NODE for i in D: the compaction is stable.
+ *   3. Every per-node column keeps exactly the rows of K, in order: codes, neighbor lists, heap tids, vectors, the cosine divisors
+ *      (both), the library's own visibility mask and every stored snapshot mask.  A column the index does not hold is skipped
+ *      (a plain index has no codes).
+ *   4. A neighbor row handles its entries in list order: an entry v becomes new_of[v]; an entry with v in D is removed and the list
+ *      closes up, order preserved; the row is padded to its stride with VS_INVALID_NODE.  CONSOLIDATE FIRST: after
+ *      vs_index_consolidate_deletes with its repair no K row names a D node, nothing is cut and every list is a pure rename.
+ *      Without it the cut is legal but the edges are simply lost — nothing takes over the dropped node's neighbors, rows may end
+ *      up empty (rows_emptied) and live rows unreachable.  With VS_COMPACT_KEEP_EDGES_CHECK a first read-only pass counts edges_cut
+ *      and the call returns VS_ERR_STATE with every byte as it was when it is not 0.
+ *   5. The label CSR keeps the sets of K (built aside, swapped in); the label masks are re-derived; the neighbors' label masks are
+ *      dropped as an insert drops them; default_start and the per-label start nodes are mapped through new_of (all of them in K).
+ *   6. n = n_after.  The capacity and the allocations STAY: the freed tail is room for the next vs_index_insert (give it back with
+ *      vs_index_shrink_to_fit).  What the launch planner remembered of the last batches is dropped; the workspace slab stays.
+ *   7. Nothing in D: nothing is written, rows_moved == 0, every array byte-identical.
+ * Rows move inside their own arrays through a staging buffer of at most stage_bytes (0 = 256 MiB): every column moves as many rows
+ * per chunk as fit; VS_ERR_INVALID if one row of the widest column does not fit.  Rows below the first dropped node are not touched
+ * (their neighbor lists are renamed).  out_new_of (host, [n_before], may be NULL) receives the map whenever the call gets as far as
+ * computing it.
+ * Refusals leave every byte as it was: VS_ERR_STATE for a view handle, live views, a batch in flight, an open vs_pages_out writer,
+ * a caller-owned device visibility mask in force, or the edge check above; VS_ERR_INVALID for unknown flags, an index without
+ * neighbor lists / heap tids, a stage_bytes below one row.  SBQ and plain storage alike.
+ * Open vs_scans, scan pools and brokers of the index must be ENDED before the call (their device state names old ids); a baseline
+ * of vs_pages_out taken before stays usable for vs_pages_out_delta — item pointers of the written relation change, so the delta
+ * names nearly every node page and the relation shrinks.  Not thread safe against any other call on the index; ordered on the
+ * context's stream.
+ * NOT ATOMIC.  Every allocation (maps, staging, the new label arrays) happens before the first byte moves, and an error up to
+ * there leaves the index as it was.  A HIP error after that point leaves the index UNDEFINED: only vs_index_free is safe. */
+#define VS_COMPACT_KEEP_EDGES_CHECK 1u  /* refuse (VS_ERR_STATE, nothing changed) if any kept row names a dropped node */
+typedef struct vs_compact_stats {
+    uint32_t n_before, n_after;
+    uint64_t tombstones;        /* heap offset 0 */
+    uint64_t tombstones_kept;   /* of those: default / per-label start nodes */
+    uint64_t rows_moved;        /* kept rows whose id changed */
+    uint64_t edges_cut;         /* entries of kept rows that named a dropped node */
+    uint64_t rows_emptied;      /* kept rows left without a neighbor by the cut */
+    uint32_t chunks;            /* staged chunks the row mover ran (the widest column) */
+} vs_compact_stats;
+int vs_index_compact(vs_index* idx, uint64_t stage_bytes /* 0 = default */, uint32_t flags,
+                     uint32_t* out_new_of /* host, [n_before], may be NULL */, vs_compact_stats* out /* may be NULL */);
+/* HIP-event milliseconds of the two passes on this index since the last reset, collected while vs_profile_enable is on:
+ * ms[0] the keep flags and the two maps, ms[1] the row mover (every column's gathers and staging copies) */
+int vs_index_compact_kernel_ms(vs_index* idx, double* ms, int reset);
+/* gives the room behind n back to the device: the per-node arrays one at a time at n rows — allocate, copy device to device, swap,
+ * free — narrowest row first and the vectors last, so the peak extra memory is one array and the largest one asks when everything
+ * else has been returned.  Afterwards capacity == n.  If an allocation fails the call reports VS_ERR_OOM and the index stays fully
+ * usable: the arrays already done stay smaller, the others keep their size, and capacity is n all the same (n rows is what every
+ * array is known to hold; the next insert that needs room reserves).  Refusals as vs_index_reserve: a view handle, live views, a
+ * batch in flight.  The arrays MOVE: pointers taken with vs_index_array must be asked for again, scans ended or rescanned.  A
+ * separate call because a caller who expects inserts wants the room kept. */
+int vs_index_shrink_to_fit(vs_index* idx);
 
 /* ---- index relation pages -> vs_index_host (the exporter the arrays above come from) ------
  * The reference reaches a node through the buffer manager, one page pin per neighbor (ItemPointer::read_bytes,

@@ -140,6 +140,17 @@ class ConsolidateStats(C.Structure):
 VS_CONSOLIDATE_NO_REPAIR = 1
 
 
+class CompactStats(C.Structure):
+    _fields_ = [("n_before", C.c_uint32), ("n_after", C.c_uint32)] + [(k, C.c_uint64) for k in (
+        "tombstones", "tombstones_kept", "rows_moved", "edges_cut", "rows_emptied")] + [("chunks", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+VS_COMPACT_KEEP_EDGES_CHECK = 1
+
+
 class DatagenParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("dim", C.c_uint32), ("latent_dim", C.c_uint32), ("n_clusters", C.c_uint32),
                 ("intra_pct", C.c_uint32), ("noise_pct", C.c_uint32), ("normalize", C.c_uint32)]
@@ -196,6 +207,9 @@ SYMBOLS = {
     "vs_index_bulk_delete_dev": (_i, [_vp, _vp, _u64, C.POINTER(BulkDeleteStats)]),
     "vs_index_consolidate_deletes": (_i, [_vp, C.c_double, _u32, _u32, C.POINTER(ConsolidateStats)]),
     "vs_index_consolidate_kernel_ms": (_i, [_vp, C.POINTER(C.c_double), _i]),
+    "vs_index_compact": (_i, [_vp, C.c_uint64, _u32, _vp, C.POINTER(CompactStats)]),
+    "vs_index_compact_kernel_ms": (_i, [_vp, C.POINTER(C.c_double), _i]),
+    "vs_index_shrink_to_fit": (_i, [_vp]),
     "vs_node_layout_default": (_i, [_i, C.POINTER(NodeLayout)]),
     "vs_pages_open": (_i, [_u32, _i, C.POINTER(NodeLayout), _u32, C.POINTER(_vp)]),
     "vs_pages_open_plain": (_i, [_u32, C.POINTER(NodeLayout), _u32, C.POINTER(_vp)]),

@@ -2104,3 +2104,471 @@ extern "C" int vs_index_consolidate_kernel_ms(vs_index* ix, double* ms /*[2]*/, 
     }
     return VS_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// vs_index_compact: the tombstones consolidation left behind leave the arrays (DESIGN.md section 6e has the rule).  K is the K of
+// the consolidation (k_cons_classify + k_cons_keep_starts), new_of[i] = the number of K nodes below i, and every per-node column
+// keeps exactly the rows of K in their order.  Rows move INSIDE their arrays, chunk by chunk through a bounded staging buffer:
+// for the kept rows with new ids [a, b) one launch gathers their source rows (old ids old_of[a .. b)) into staging, a device copy
+// puts staging at [a, b).  A destination slot j in [a, b) is the source only of a kept row with new id <= j (old_of[j'] >= j' and
+// old_of ascends): that row went with an earlier chunk or is in staging already.  The neighbor form renames while it gathers.
+// ---------------------------------------------------------------------------------------------------------------
+// extra counters of the pass, behind those of the classification (CN_*): kept nodes, the first dropped node, label values kept
+enum { CP_N_AFTER = CN_N, CP_FIRST, CP_LABEL_VALS, CP_N };
+
+// kept nodes (class != 1) per wave of 64 nodes, and the lowest dropped node (one atomic per wave that has one)
+__global__ __launch_bounds__(256) void k_compact_keep_count(const uint8_t* __restrict__ cls, uint32_t n, uint32_t* __restrict__ wave_cnt,
+                                                            unsigned long long* __restrict__ cnt) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    const bool in = i < n, keep = in && cls[i] != 1;
+    const uint64_t mk = __ballot(keep), md = __ballot(in && !keep);
+    if ((threadIdx.x & (WAVE - 1)) == 0 && in) {
+        wave_cnt[i / WAVE] = (uint32_t)__popcll(mk);
+        if (md) atomicMin(&cnt[CP_FIRST], (unsigned long long)(i + (uint32_t)__builtin_ctzll(md)));
+    }
+}
+// wave_off: the exclusive scan of the counts (k_cons_work_scan).  new_of[old] for every node, old_of[new] for every kept one.
+__global__ __launch_bounds__(256) void k_compact_maps(const uint8_t* __restrict__ cls, uint32_t n, const uint32_t* __restrict__ wave_off,
+                                                      uint32_t* __restrict__ new_of, uint32_t* __restrict__ old_of) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & (WAVE - 1);
+    const bool keep = i < n && cls[i] != 1;
+    const uint64_t m = __ballot(keep);
+    if (i >= n) return;
+    if (keep) {
+        const uint32_t j = wave_off[i / WAVE] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        new_of[i] = j;
+        old_of[j] = i;
+    } else {
+        new_of[i] = VS_INVALID_NODE;
+    }
+}
+
+// The row mover for the wide columns (codes, vectors): rows [a, b) of the compacted order are gathered through old_of into staging,
+// lanes over the 16-byte pieces of a row.  lpr_log2 < 6: 1 << lpr_log2 lanes per row (the power of two that holds its `pieces`),
+// 64 >> lpr_log2 rows per wave; lpr_log2 == 6: one row per wave, the lanes stride over its pieces.  The host chooses from the width.
+__global__ __launch_bounds__(256) void k_compact_rows(const uint4* __restrict__ src, uint32_t pieces, uint32_t lpr_log2,
+                                                      const uint32_t* __restrict__ old_of, uint32_t a, uint32_t b, uint4* __restrict__ stage) {
+    const uint32_t lane = threadIdx.x & (WAVE - 1);
+    const uint64_t wave = ((uint64_t)blockIdx.x * 256 + threadIdx.x) / WAVE, n_waves = (uint64_t)gridDim.x * (256 / WAVE);
+    const uint32_t rpw = WAVE >> lpr_log2, sub = lane >> lpr_log2, first = lane & ((1u << lpr_log2) - 1u), step = 1u << lpr_log2;
+    const uint64_t rows = b - a;
+    for (uint64_t r = wave * rpw + sub; r < rows; r += n_waves * rpw) {
+        const uint4* from = src + (size_t)old_of[a + r] * pieces;
+        uint4* to = stage + (size_t)r * pieces;
+        for (uint32_t p = first; p < pieces; p += step) to[p] = from[p];
+    }
+}
+// the narrow columns (heap tids 8 B, cosine divisors 4 B, the byte masks): a lane per row
+template <typename T>
+__global__ __launch_bounds__(256) void k_compact_narrow(const T* __restrict__ src, const uint32_t* __restrict__ old_of, uint32_t a, uint32_t b,
+                                                        T* __restrict__ stage) {
+    const uint64_t rows = b - a;
+    for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < rows; r += (uint64_t)gridDim.x * 256) stage[r] = src[old_of[a + r]];
+}
+// The neighbor form: a lane per entry, seg (16, 32 or 64, a divisor of 64) lanes per row — the whole row when nbr_stride == seg, else
+// one row per wave in rounds of 64 entries with the running length carried over.  An entry v becomes new_of[v]; one that names a
+// dropped node is cut and the list closes up in its order: a surviving entry's place is the count of survivors before it (ballot,
+// popcount below the lane, within the lane's segment).  The tail is VS_INVALID_NODE.  Counters: one atomic per wave and counter.
+__global__ __launch_bounds__(256) void k_compact_nbrs(const uint32_t* __restrict__ nbrs, uint32_t nbr_stride, uint32_t R, uint32_t seg, uint32_t n_before,
+                                                      const uint32_t* __restrict__ old_of, const uint32_t* __restrict__ new_of, uint32_t a,
+                                                      uint32_t b, uint32_t* __restrict__ stage, unsigned long long* __restrict__ cnt) {
+    const uint32_t lane = threadIdx.x & (WAVE - 1);
+    const uint64_t wave = ((uint64_t)blockIdx.x * 256 + threadIdx.x) / WAVE, n_waves = (uint64_t)gridDim.x * (256 / WAVE);
+    const uint32_t rpw = WAVE / seg, sub = lane / seg, e0 = lane % seg;
+    const uint64_t segmask = seg == WAVE ? ~0ull : ((1ull << seg) - 1ull) << (sub * seg);
+    const uint64_t below = segmask & ((1ull << lane) - 1ull);
+    const uint64_t rows = b - a;
+    uint32_t cut_total = 0, emptied = 0;
+    for (uint64_t r0 = wave * rpw; r0 < rows; r0 += n_waves * rpw) {  // (wave-uniform trip count: the ballots see every lane)
+        const uint64_t r = r0 + sub;
+        const bool row_in = r < rows;
+        const uint32_t* from = row_in ? nbrs + (size_t)old_of[a + r] * nbr_stride : nullptr;
+        uint32_t* to = stage + (size_t)r * nbr_stride;
+        uint32_t len = 0, cut_row = 0;
+        for (uint32_t c0 = 0; c0 < nbr_stride; c0 += seg) {
+            const uint32_t e = c0 + e0;
+            const uint32_t v = row_in && e < R ? from[e] : VS_INVALID_NODE;  // (only the first R entries of a row are its list)
+            const uint32_t w = v < n_before ? new_of[v] : VS_INVALID_NODE;
+            const bool stays = w != VS_INVALID_NODE, cut = v < n_before && !stays;
+            const uint64_t ms = __ballot(stays), mc = __ballot(cut);
+            if (stays) to[len + (uint32_t)__popcll(ms & below)] = w;
+            len += (uint32_t)__popcll(ms & segmask);
+            cut_row += (uint32_t)__popcll(mc & segmask);
+            cut_total += (uint32_t)__popcll(mc);  // (the wave's: a lane without a row cuts nothing)
+        }
+        if (row_in)
+            for (uint32_t e = len + e0; e < nbr_stride; e += seg) to[e] = VS_INVALID_NODE;
+        emptied += (uint32_t)__popcll(__ballot(row_in && e0 == 0 && cut_row != 0 && len == 0));
+    }
+    if (lane == 0) {
+        if (cut_total) atomicAdd(&cnt[CN_EDGES_DROPPED], (unsigned long long)cut_total);
+        if (emptied) atomicAdd(&cnt[CN_EMPTIED], (unsigned long long)emptied);
+    }
+}
+// The label CSR of K, out of place (its rows have variable length).  First the label values of the kept nodes per wave of 64 nodes ...
+__global__ __launch_bounds__(256) void k_compact_label_count(const uint8_t* __restrict__ cls, const uint32_t* __restrict__ label_off, uint32_t n,
+                                                             uint32_t* __restrict__ wave_cnt) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    uint32_t len = i < n && cls[i] != 1 ? label_off[i + 1] - label_off[i] : 0;
+    for (int k = 1; k < WAVE; k <<= 1) len += __shfl_xor(len, k);
+    if ((threadIdx.x & (WAVE - 1)) == 0 && i < n) wave_cnt[i / WAVE] = len;
+}
+// ... then, with their exclusive scan, every kept node writes its new offset and copies its set (a lane per node; sets are short)
+__global__ __launch_bounds__(256) void k_compact_labels(const uint8_t* __restrict__ cls, const uint32_t* __restrict__ label_off,
+                                                        const int16_t* __restrict__ label_val, uint32_t n, const uint32_t* __restrict__ wave_off,
+                                                        const uint32_t* __restrict__ new_of, uint32_t n_after, uint32_t* __restrict__ out_off,
+                                                        int16_t* __restrict__ out_val) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & (WAVE - 1);
+    const bool keep = i < n && cls[i] != 1;
+    const uint32_t lo = keep ? label_off[i] : 0, len = keep ? label_off[i + 1] - lo : 0;
+    uint32_t incl = len;
+    for (uint32_t k = 1; k < WAVE; k <<= 1) {  // inclusive prefix sum over the wave
+        const uint32_t t = __shfl(incl, (int)(lane >= k ? lane - k : lane));
+        if (lane >= k) incl += t;
+    }
+    if (!keep) return;
+    const uint32_t at = wave_off[i / WAVE] + incl - len, j = new_of[i];
+    out_off[j] = at;
+    if (j + 1 == n_after) out_off[n_after] = at + len;
+    for (uint32_t t = 0; t < len; ++t) out_val[at + t] = label_val[lo + t];
+}
+// the per-label start nodes under their new ids (every one of them is in K)
+__global__ void k_compact_map_ids(uint32_t* __restrict__ ids, uint32_t n_ids, const uint32_t* __restrict__ new_of) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n_ids) ids[t] = new_of[ids[t]];
+}
+
+#define VS_COMPACT_STAGE_DEFAULT (256ull << 20)
+
+static int compact_impl(vs_index* ix, uint64_t stage_bytes, uint32_t flags, uint32_t* out_new_of, vs_compact_stats* out) {
+    const char* what = "vs_index_compact";
+    VS_REQUIRE(ix, "%s: index is NULL", what);
+    if (out) memset(out, 0, sizeof(*out));
+    VS_REQUIRE_OWNER(ix, what);
+    VS_REQUIRE_NO_VIEWS(ix, what);
+    VS_REQUIRE((flags & ~(uint32_t)VS_COMPACT_KEEP_EDGES_CHECK) == 0, "%s: unknown flags 0x%x", what, flags);
+    VS_REQUIRE(ix->nbrs && ix->tids, "%s: needs neighbor lists and heap tids on the device", what);
+    auto state_error = [&](const char* msg) {
+        vs_set_error("%s: %s", what, msg);
+        return VS_ERR_STATE;
+    };
+    if (ix->ws.pending) return state_error("a batch of this handle is in flight (vs_search_batch_dev_finish first)");
+    if (vs_index_open_writers(ix) > 0)
+        return state_error("a vs_pages_out writer of this index is open (its pages would mix rows from before and after; vs_pages_out_close first)");
+    if (ix->visible && ix->visible != ix->visible_own) {
+        bool ours = false;
+        for (const uint8_t* sp : ix->snap) ours |= sp == ix->visible;
+        if (!ours) return state_error("a caller-owned device visibility mask is in force and cannot be compacted by the library (clear or replace it)");
+    }
+    const uint32_t n = ix->d.n;
+    if (stage_bytes == 0) stage_bytes = VS_COMPACT_STAGE_DEFAULT;
+    // the per-node columns (the list vs_index_reserve_impl copies, less the label CSR, which is rebuilt aside)
+    struct Col {
+        void* p;
+        size_t row_bytes;
+        int form;  // 0 wide (16-byte pieces), 2 the neighbor lists, 8 / 4 / 1 narrow (bytes of a row)
+    };
+    std::vector<Col> cols;
+    auto add = [&](void* p, size_t row_bytes, int form) {
+        if (p) cols.push_back(Col{p, row_bytes, form});
+    };
+    add(ix->nbrs, ix->nbr_stride * 4ull, 2);
+    add(ix->codes, ix->code_stride * 8ull, 0);
+    add(ix->tids, 8, 8);
+    add(ix->vecs, ix->vec_stride * 4ull, 0);
+    add(ix->vnorm, 4, 4);
+    add(ix->vnorm_idx, 4, 4);
+    add(ix->visible_own, 1, 1);
+    for (int sn = 1; sn < VS_MAX_SNAPSHOTS; ++sn) add(ix->snap[sn], 1, 1);
+    size_t widest = 0;
+    for (const Col& cl : cols) {
+        widest = std::max(widest, cl.row_bytes);
+        VS_REQUIRE(cl.form != 0 || cl.row_bytes % 16 == 0, "%s: a row of %zu bytes is no multiple of 16", what, cl.row_bytes);
+    }
+    VS_REQUIRE(stage_bytes >= widest, "%s: stage_bytes %llu holds no row of %zu bytes", what, (unsigned long long)stage_bytes, widest);
+    VS_REQUIRE(ix->nbr_stride % 16 == 0, "%s: neighbor rows of %u entries", what, ix->nbr_stride);
+    vs_compact_stats s{};
+    s.n_before = s.n_after = n;
+    if (n == 0 || ix->d.default_start == VS_INVALID_NODE) {
+        if (out) *out = s;
+        return VS_OK;
+    }
+    vs_ctx* c = ix->ctx;
+    hipStream_t st = c->stream;
+    VS_HIP(hipSetDevice(c->device));
+    std::vector<uint32_t> starts(1, ix->d.default_start);
+    if (ix->d.n_label_starts) {
+        starts.resize(1 + (size_t)ix->d.n_label_starts);
+        VS_HIP(hipMemcpy(starts.data() + 1, ix->ls_nodes, (size_t)ix->d.n_label_starts * 4, hipMemcpyDeviceToHost));
+    }
+    std::sort(starts.begin(), starts.end());
+    starts.erase(std::unique(starts.begin(), starts.end()), starts.end());
+    VS_REQUIRE(starts.back() < n, "%s: start node %u of an index of %u nodes", what, starts.back(), n);
+    const bool labeled = ix->label_off != nullptr;
+    const uint32_t n_waves = (n + WAVE - 1) / WAVE;
+    uint8_t *d_cls = nullptr, *d_flag = nullptr, *d_stage = nullptr;
+    uint32_t *d_wave = nullptr, *d_lwave = nullptr, *d_starts = nullptr, *d_new_of = nullptr, *d_old_of = nullptr, *new_off = nullptr;
+    int16_t* new_val = nullptr;
+    unsigned long long* d_cnt = nullptr;
+    unsigned long long h_cnt[CP_N] = {0};
+    uint32_t new_default = ix->d.default_start, chunks = 0;
+    bool moved = false;  // the first byte has moved: an error from here on leaves the index undefined
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double ms[2] = {0, 0};
+    auto tick = [&] {
+        if (ev[0]) (void)hipEventRecord(ev[0], st);
+    };
+    auto tock = [&](int which) {
+        float t = 0.f;
+        if (ev[0] && hipEventRecord(ev[1], st) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
+            hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess)
+            ms[which] += t;
+    };
+    auto run = [&]() -> int {
+        if (c->profiling) {
+            VS_HIP(hipEventCreate(&ev[0]));
+            VS_HIP(hipEventCreate(&ev[1]));
+        }
+        VS_HIP(hipMalloc(&d_cls, (size_t)n));
+        VS_HIP(hipMalloc(&d_wave, ((size_t)n_waves + 1) * 4));
+        VS_HIP(hipMalloc(&d_starts, starts.size() * 4));
+        VS_HIP(hipMalloc(&d_cnt, sizeof h_cnt));
+        VS_HIP(hipMalloc(&d_new_of, (size_t)n * 4));
+        VS_HIP(hipMalloc(&d_old_of, (size_t)n * 4));
+        if (labeled) VS_HIP(hipMalloc(&d_lwave, ((size_t)n_waves + 1) * 4));
+        if (flags & VS_COMPACT_KEEP_EDGES_CHECK) {
+            VS_HIP(hipMalloc(&d_flag, (size_t)n));
+            VS_HIP(hipMemsetAsync(d_flag, 0, (size_t)n, st));
+        }
+        VS_HIP(hipMemcpyAsync(d_starts, starts.data(), starts.size() * 4, hipMemcpyHostToDevice, st));
+        h_cnt[CP_FIRST] = n;
+        VS_HIP(hipMemsetAsync(d_cnt, 0, sizeof h_cnt, st));
+        VS_HIP(hipMemcpyAsync(&d_cnt[CP_FIRST], &h_cnt[CP_FIRST], 8, hipMemcpyHostToDevice, st));  // (the atomicMin starts from n)
+        VS_HIP(hipStreamSynchronize(st));
+        tick();
+        const dim3 ngrid((n + 255) / 256);
+        hipLaunchKernelGGL(k_cons_classify, ngrid, dim3(256), 0, st, (const uint64_t*)ix->tids, (const uint32_t*)ix->label_off, n, d_cls, d_cnt);
+        VS_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_cons_keep_starts, dim3(((uint32_t)starts.size() + 255) / 256), dim3(256), 0, st, (const uint32_t*)d_starts,
+                           (uint32_t)starts.size(), d_cls, d_cnt);
+        VS_HIP(hipGetLastError());
+        if (d_flag) {  // the read-only pass of VS_COMPACT_KEEP_EDGES_CHECK: the cells of kept rows that name a dropped node
+            const size_t cells = (size_t)n * ix->d.num_neighbors;
+            hipLaunchKernelGGL(k_cons_flag, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, (const uint32_t*)ix->nbrs, ix->nbr_stride,
+                               ix->d.num_neighbors, n, (const uint8_t*)d_cls, d_flag, d_cnt);
+            VS_HIP(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_compact_keep_count, ngrid, dim3(256), 0, st, (const uint8_t*)d_cls, n, d_wave, d_cnt);
+        VS_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_cons_work_scan, dim3(1), dim3(256), 0, st, d_wave, n_waves);
+        VS_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_compact_maps, ngrid, dim3(256), 0, st, (const uint8_t*)d_cls, n, (const uint32_t*)d_wave, d_new_of, d_old_of);
+        VS_HIP(hipGetLastError());
+        if (labeled) {
+            hipLaunchKernelGGL(k_compact_label_count, ngrid, dim3(256), 0, st, (const uint8_t*)d_cls, (const uint32_t*)ix->label_off, n, d_lwave);
+            VS_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_cons_work_scan, dim3(1), dim3(256), 0, st, d_lwave, n_waves);
+            VS_HIP(hipGetLastError());
+            VS_HIP(hipMemcpyAsync(&d_cnt[CP_LABEL_VALS], d_lwave + n_waves, 4, hipMemcpyDeviceToDevice, st));
+        }
+        // the totals join the counters (little endian: the low half of a zeroed u64), so that one copy brings everything back
+        VS_HIP(hipMemcpyAsync(&d_cnt[CP_N_AFTER], d_wave + n_waves, 4, hipMemcpyDeviceToDevice, st));
+        VS_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
+        VS_HIP(hipStreamSynchronize(st));
+        tock(0);
+        const uint32_t n_after = (uint32_t)h_cnt[CP_N_AFTER], first = (uint32_t)h_cnt[CP_FIRST];
+        s.n_after = n_after;
+        s.tombstones = h_cnt[CN_TOMB];
+        s.tombstones_kept = h_cnt[CN_KEPT];
+        s.edges_cut = h_cnt[CN_EDGES_DROPPED];
+        if (d_flag && s.edges_cut) {
+            s.n_after = n;
+            vs_set_error("%s: %llu entries of kept rows name a dropped node (VS_COMPACT_KEEP_EDGES_CHECK; vs_index_consolidate_deletes first)",
+                         what, (unsigned long long)s.edges_cut);
+            return VS_ERR_STATE;
+        }
+        VS_REQUIRE(n_after >= 1 && n_after <= n && (n_after == n) == (first == n), "%s: %u of %u nodes kept, first dropped %u", what, n_after, n, first);
+        if (out_new_of) VS_HIP(hipMemcpy(out_new_of, d_new_of, (size_t)n * 4, hipMemcpyDeviceToHost));
+        if (n_after == n) return VS_OK;  // nothing in D: nothing is written
+        // every allocation before the first byte moves: the staging buffer and the label arrays of K
+        size_t need = 0;
+        for (const Col& cl : cols) {
+            const size_t rows = cl.form == 2 ? n_after : n_after - first;
+            need = std::max(need, std::min<size_t>(rows, stage_bytes / cl.row_bytes) * cl.row_bytes);
+        }
+        VS_HIP(hipMalloc(&d_stage, std::max<size_t>(need, 16)));
+        const uint64_t vals_after = h_cnt[CP_LABEL_VALS];
+        if (labeled) {
+            VS_HIP(hipMalloc(&new_off, ((size_t)std::max(n, ix->capacity) + 1) * 4));
+            VS_HIP(hipMalloc(&new_val, std::max<uint64_t>(vals_after, 1) * 2));
+        }
+        if (labeled) {  // (reads the label CSR as it stands, writes the fresh arrays: nothing of the index has changed yet)
+            hipLaunchKernelGGL(k_compact_labels, ngrid, dim3(256), 0, st, (const uint8_t*)d_cls, (const uint32_t*)ix->label_off,
+                               (const int16_t*)ix->label_val, n, (const uint32_t*)d_lwave, (const uint32_t*)d_new_of, n_after, new_off, new_val);
+            VS_HIP(hipGetLastError());
+        }
+        VS_HIP(hipMemcpyAsync(&new_default, d_new_of + ix->d.default_start, 4, hipMemcpyDeviceToHost, st));
+        VS_HIP(hipStreamSynchronize(st));
+        moved = true;
+        ix->nbr_mask_valid = false;
+        tick();
+        for (const Col& cl : cols) {
+            const uint32_t from = cl.form == 2 ? 0 : first;  // (every neighbor row is renamed; the other columns start at the first hole)
+            const uint32_t per = (uint32_t)std::min<uint64_t>(stage_bytes / cl.row_bytes, n_after - from);
+            uint32_t col_chunks = 0;
+            for (uint32_t a = from; a < n_after; a += per, ++col_chunks) {
+                const uint32_t b = (uint32_t)std::min<uint64_t>((uint64_t)a + per, n_after), rows = b - a;
+                char* col = static_cast<char*>(cl.p);
+                if (cl.form == 2) {
+                    const uint32_t seg = ix->nbr_stride == 16 || ix->nbr_stride == 32 ? ix->nbr_stride : WAVE;
+                    const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)rows + 4 * (WAVE / seg) - 1) / (4 * (WAVE / seg)), 1u << 16);
+                    hipLaunchKernelGGL(k_compact_nbrs, dim3(grid), dim3(256), 0, st, (const uint32_t*)ix->nbrs, ix->nbr_stride, ix->d.num_neighbors, seg,
+                                       n, (const uint32_t*)d_old_of, (const uint32_t*)d_new_of, a, b, reinterpret_cast<uint32_t*>(d_stage), d_cnt);
+                } else if (cl.form == 0) {
+                    const uint32_t pieces = (uint32_t)(cl.row_bytes / 16);
+                    uint32_t lpr_log2 = 0;
+                    while (lpr_log2 < 6 && (1u << lpr_log2) < pieces) ++lpr_log2;
+                    const uint32_t rpb = 4 * (WAVE >> lpr_log2);  // rows a workgroup of four waves handles per round
+                    const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)rows + rpb - 1) / rpb, 1u << 16);
+                    hipLaunchKernelGGL(k_compact_rows, dim3(grid), dim3(256), 0, st, reinterpret_cast<const uint4*>(cl.p), pieces, lpr_log2,
+                                       (const uint32_t*)d_old_of, a, b, reinterpret_cast<uint4*>(d_stage));
+                } else {
+                    const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)rows + 255) / 256, 1u << 16);
+                    if (cl.form == 8)
+                        hipLaunchKernelGGL(k_compact_narrow<uint64_t>, dim3(grid), dim3(256), 0, st, (const uint64_t*)cl.p, (const uint32_t*)d_old_of, a,
+                                           b, reinterpret_cast<uint64_t*>(d_stage));
+                    else if (cl.form == 4)
+                        hipLaunchKernelGGL(k_compact_narrow<uint32_t>, dim3(grid), dim3(256), 0, st, (const uint32_t*)cl.p, (const uint32_t*)d_old_of, a,
+                                           b, reinterpret_cast<uint32_t*>(d_stage));
+                    else
+                        hipLaunchKernelGGL(k_compact_narrow<uint8_t>, dim3(grid), dim3(256), 0, st, (const uint8_t*)cl.p, (const uint32_t*)d_old_of, a,
+                                           b, d_stage);
+                }
+                VS_HIP(hipGetLastError());
+                VS_HIP(hipMemcpyAsync(col + (size_t)a * cl.row_bytes, d_stage, (size_t)rows * cl.row_bytes, hipMemcpyDeviceToDevice, st));
+            }
+            if (cl.row_bytes == widest) chunks = std::max(chunks, col_chunks);
+        }
+        if (ix->d.n_label_starts) {
+            hipLaunchKernelGGL(k_compact_map_ids, dim3((ix->d.n_label_starts + 255) / 256), dim3(256), 0, st, ix->ls_nodes, ix->d.n_label_starts,
+                               (const uint32_t*)d_new_of);
+            VS_HIP(hipGetLastError());
+        }
+        // (the counters of the first copy stand; the neighbor form has added edges_cut — unless the check pass counted them — and rows_emptied)
+        VS_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
+        VS_HIP(hipStreamSynchronize(st));
+        tock(1);
+        if (labeled) {
+            (void)hipFree(ix->label_off);
+            (void)hipFree(ix->label_val);
+            ix->label_off = new_off;
+            ix->label_val = new_val;
+            new_off = nullptr;
+            new_val = nullptr;
+            ix->n_label_vals = vals_after;
+        }
+        ix->d.default_start = new_default;
+        ix->d.n = n_after;
+        s.rows_moved = n_after - first;
+        s.edges_cut = h_cnt[CN_EDGES_DROPPED];
+        s.rows_emptied = h_cnt[CN_EMPTIED];
+        s.chunks = chunks;
+        // what was derived from the old numbering is stale, as after an insert: the neighbor masks go (re-derived lazily), the
+        // launch planner forgets the last batches, the label masks are re-derived now
+        if (ix->nbr_mask) {
+            (void)hipFree(ix->nbr_mask);
+            ix->nbr_mask = nullptr;
+        }
+        ix->nbr_mask_valid = false;
+        ix->nbr_mask_tried = false;
+        ix->obs = ScanObs{};
+        ix->last_fast = FastSig{};
+        ix->last_ins_limit = 0;
+        if (labeled) VS_TRY(vs_refresh_label_masks(ix));
+        return VS_OK;
+    };
+    int rc = run();
+    (void)hipStreamSynchronize(st);
+    void* ps[] = {d_cls, d_flag, d_stage, d_wave, d_lwave, d_starts, d_new_of, d_old_of, new_off, new_val, d_cnt};
+    for (void* p : ps)
+        if (p) (void)hipFree(p);
+    for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    for (int k = 0; k < 2; ++k) ix->compact_ms[k] += ms[k];
+    if (out) *out = s;
+    if (rc == VS_OK && moved) rc = vs_validate_graph(ix);
+    return rc;
+}
+extern "C" int vs_index_compact(vs_index* ix, uint64_t stage_bytes, uint32_t flags, uint32_t* out_new_of, vs_compact_stats* out) {
+    return vs_guard("vs_index_compact", [&] { return compact_impl(ix, stage_bytes, flags, out_new_of, out); });
+}
+extern "C" int vs_index_compact_kernel_ms(vs_index* ix, double* ms /*[2]*/, int reset) {
+    VS_REQUIRE(ix && ms, "vs_index_compact_kernel_ms: bad args");
+    for (int k = 0; k < 2; ++k) {
+        ms[k] = ix->compact_ms[k];
+        if (reset) ix->compact_ms[k] = 0;
+    }
+    return VS_OK;
+}
+
+// vs_index_shrink_to_fit: the arrays one at a time at d.n rows — allocate, copy device to device, swap, free the old one — so the
+// peak extra memory is one array.  Narrowest row first, the vectors last: what the smaller arrays gave back is free when the
+// largest one asks.
+static int shrink_impl(vs_index* ix) {
+    const char* what = "vs_index_shrink_to_fit";
+    VS_REQUIRE(ix, "%s: index is NULL", what);
+    VS_REQUIRE_OWNER(ix, what);
+    VS_REQUIRE_NO_VIEWS(ix, what);
+    if (ix->ws.pending) {
+        vs_set_error("%s: a batch of this handle is in flight (vs_search_batch_dev_finish first)", what);
+        return VS_ERR_STATE;
+    }
+    const uint32_t n = ix->d.n;
+    if (n == 0 || ix->capacity <= n) return VS_OK;
+    vs_ctx* c = ix->ctx;
+    VS_HIP(hipSetDevice(c->device));
+    VS_HIP(hipStreamSynchronize(c->stream));
+    struct Item {
+        void** slot;
+        size_t row_bytes, extra_rows;
+    };
+    std::vector<Item> items;
+    auto add = [&](void* slot, size_t row_bytes, size_t extra = 0) {
+        void** sl = reinterpret_cast<void**>(slot);
+        if (*sl) items.push_back(Item{sl, row_bytes, extra});
+    };
+    add(&ix->visible_own, 1);
+    for (int sn = 1; sn < VS_MAX_SNAPSHOTS; ++sn) add(&ix->snap[sn], 1);
+    add(&ix->vnorm, 4);
+    add(&ix->vnorm_idx, 4);
+    add(&ix->label_off, 4, 1);
+    add(&ix->tids, 8);
+    add(&ix->nbrs, ix->nbr_stride * 4ull);
+    add(&ix->codes, ix->code_stride * 8ull);
+    add(&ix->vecs, ix->vec_stride * 4ull);
+    std::stable_sort(items.begin(), items.end(), [](const Item& x, const Item& y) { return x.row_bytes < y.row_bytes; });
+    int r = VS_OK;
+    for (Item& it : items) {
+        const size_t bytes = ((size_t)n + it.extra_rows) * it.row_bytes;
+        void* fresh = nullptr;
+        hipError_t e = hipMalloc(&fresh, bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(fresh, *it.slot, bytes, hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            if (fresh) (void)hipFree(fresh);
+            vs_set_error("%s: shrinking to %u nodes failed: %s", what, n, hipGetErrorString(e));
+            r = e == hipErrorOutOfMemory ? VS_ERR_OOM : VS_ERR_HIP;
+            break;
+        }
+        if (ix->visible && ix->visible == *it.slot) ix->visible = static_cast<const uint8_t*>(fresh);  // (the mask in force moved too)
+        (void)hipFree(*it.slot);
+        *it.slot = fresh;
+        // from the first swapped array on, n rows is all that every array is known to hold: an insert must reserve before it writes
+        ix->capacity = n;
+    }
+    return r;
+}
+extern "C" int vs_index_shrink_to_fit(vs_index* ix) {
+    return vs_guard("vs_index_shrink_to_fit", [&] { return shrink_impl(ix); });
+}

@@ -320,6 +320,34 @@ class DiskAnnIndex:
         check(self._L.vs_index_consolidate_kernel_ms(self.h, ms, int(reset)))
         return {"flag_pass": float(ms[0]), "rows": float(ms[1])}
 
+    def compact(self, stage_bytes=0, check_edges=False, return_map=False):
+        """vs_index_compact (after consolidate_deletes): the dropped tombstones leave every per-node array, the kept nodes are
+        renumbered in place (stable), the capacity stays as room for the next insert.  stage_bytes bounds the staging buffer
+        (0 = the library's default); check_edges refuses (VS_ERR_STATE, nothing changed) when a kept row still names a dropped node.
+        Open scans, pools and brokers of the index must be ended before the call.
+        -> dict of vs_compact_stats, or (dict, new_of uint32 [n_before], VS_INVALID_NODE for a dropped node) with return_map"""
+        st = _lib.CompactStats()
+        new_of = np.empty(self.desc.n, np.uint32) if return_map else None
+        try:
+            check(self._L.vs_index_compact(self.h, stage_bytes, _lib.VS_COMPACT_KEEP_EDGES_CHECK if check_edges else 0, _p(new_of),
+                                           C.byref(st)))
+        finally:
+            self._refresh()
+        return (st.as_dict(), new_of) if return_map else st.as_dict()
+
+    def compact_kernel_ms(self, reset=True):
+        """HIP-event milliseconds of the two compaction passes since the last reset (Context.profile_enable first)"""
+        ms = (C.c_double * 2)()
+        check(self._L.vs_index_compact_kernel_ms(self.h, ms, int(reset)))
+        return {"maps": float(ms[0]), "rows": float(ms[1])}
+
+    def shrink_to_fit(self):
+        """vs_index_shrink_to_fit: every per-node array reallocated at n rows, one at a time; the arrays move, capacity becomes n"""
+        try:
+            check(self._L.vs_index_shrink_to_fit(self.h))
+        finally:
+            self._refresh()
+
     def refresh_norms(self):
         check(self._L.vs_index_refresh_norms(self.h))
 
