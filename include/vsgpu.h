@@ -263,7 +263,7 @@ int vs_index_bulk_delete_dev(vs_index* idx, const uint64_t* d_dead_tids_sorted, 
  *   WOULD RE-LINK THE TOMBSTONES (it knows no D); use this call's own repair.
  * What it does not do: it never reclaims a tombstone's node (n and the page layout stay, D rows keep their bytes, so their pages
  * stay clean for vs_pages_out_delta; vs_index_compact below is the call that reclaims them); it does not re-elect a deleted start node (it stays in K with a clean list); it gives no
- * guarantee for label-filtered reachability beyond what Graph::insert gives.
+ * guarantee for label-filtered reachability beyond what Graph::insert gives (vs_index_label_reach audits it, vs_index_repair_labels repairs it).
  * Refusals leave every byte as it was: VS_ERR_INVALID for plain storage, an index without codes / neighbor lists / heap tids, a
  * node with more than 64 labels, max_alpha outside [1,5], a bad cand_max or unknown flags; VS_ERR_STATE while a view of the index
  * is alive, a batch of this handle is in flight, or a writer opened with vs_pages_out_open has not been closed.  n does not change
@@ -965,6 +965,87 @@ int vs_batch_mates_filtered(vs_index* idx, const uint64_t* codes, const uint32_t
  * not reach is given an in-edge where that strands nobody else; *unreachable (may be NULL) = what vs_index_build_unreachable reports.
  * It treats a tombstone like any node: after vs_index_consolidate_deletes it would hand the dropped tombstones in-edges again. */
 int vs_index_repair(vs_index* idx, uint32_t* unreachable);
+
+/* ---- label-filtered reachability: the audit and the repair (what a PGRX shim calls after ambuild, and after amvacuumcleanup's
+ * consolidation) ----------------------------------------------------------------------------------------------------------------
+ * Build, insert, consolidation and compaction keep every live row reachable from the DEFAULT start node.  A label-filtered scan
+ * starts at the start node of each label of its key (StartNodes::get_for_node, AM/graph/start_nodes.rs:39-48) and never enqueues
+ * a neighbor whose label set misses the key (AM/sbq/storage.rs:148-172): a row that carries label l is returned under the key {l}
+ * only if a path leads to it from l's start node through rows that all carry l.  Single-label keys are the strictest case (a row
+ * reached under {l} is reached under every key that contains l).  Definitions, on the graph as it stands:
+ *   Node classes are those of vs_index_consolidate_deletes: live (heap offset not 0), kept tombstone (offset 0, but the default
+ *   or a per-label start node), dropped tombstone D (every other node with offset 0).
+ *   Labels judged: every distinct label of some node's set or of the start map, ascending, in GROUPS of 64.  A label that is
+ *   carried but has no start node is not judged (get_for_node gives its key no start at all): it is counted in
+ *   labels_without_start and has no bit in what follows.
+ *   mask[i]  = the judged labels of the group that node i carries.
+ *   reach[i] = the least fixed point of: reach[s_l] holds l for every judged label l of the group, s_l its start node, whether or
+ *              not s_l carries l; for every entry u -> v of a neighbor list, reach[v] holds reach[u] & mask[v].  Every node
+ *              propagates, dropped tombstones included: scans expand them as long as an edge leads there.
+ *   need[x]  = mask[x] & ~reach[x] for a live x, 0 otherwise.  A live x with need[x] != 0 is LOST.
+ * vs_index_label_reach is the audit: read-only, works on a view, touches no index array.  out_labels / out_carriers / out_lost
+ * (each may be NULL, `cap` entries) receive, per label in ascending order, the label, its live carriers and how many of them are
+ * lost (stats.labels of them exist; a label without a start node reports 0 lost); out_node_lost (host, [n], may be NULL): 1 = the
+ * node is lost under at least one label.  VS_ERR_INVALID for an index without label sets or neighbor lists, VS_ERR_STATE while a
+ * batch of the handle is in flight. */
+typedef struct vs_label_reach_stats {
+    uint64_t lost_pairs;            /* (row, label) pairs: a live row not reached under a label it carries */
+    uint32_t lost_nodes;            /* live rows lost under at least one label */
+    uint32_t labels;                /* distinct labels of the node sets and the start map */
+    uint32_t labels_without_start;  /* carried labels that have no start node: not judged */
+    uint32_t sweeps;                /* launches of the reach sweep */
+} vs_label_reach_stats;
+int vs_index_label_reach(vs_index* idx, vs_label_reach_stats* out /* may be NULL */, int16_t* out_labels, uint32_t* out_carriers,
+                         uint32_t* out_lost, uint32_t cap, uint8_t* out_node_lost);
+/* vs_index_repair_labels hands the lost rows in-edges, at the caller's choice (no other call runs it).  One ROUND takes the groups
+ * in ascending order, a later group sees what an earlier one wrote.  Per group:
+ *   1. reach and need as above; nothing lost: the group is done.
+ *   2. strong[y] = the entries q -> y with q not in D and mask[y] & ~reach[q] == 0: in-edges from rows that are themselves
+ *      reached under every label y carries in the group.
+ *   3. every lost x picks the source p with the least (Hamming(code[x], code[p]) << 32) | p among the nodes p != x, p not in D,
+ *      reach[p] & need[x] != 0: the nearest row already reached under a label x still needs (the start node of a needed label
+ *      always qualifies).
+ *   4. a source serves one node per group and round: of the nodes that picked p the smallest id wins, the others (contended) wait
+ *      for the next round.
+ *   5. p's row, edited by one writer that reads only p's row and the arrays of steps 1-2: nothing if it names x already; else x
+ *      goes into the first free slot (placed_free); else, scanning from the last entry backwards, over the first entry that names
+ *      a dropped tombstone (placed_over_dropped); else over the first entry y with strong[y] >= 1 + (mask[y] & ~reach[p] == 0 ? 1
+ *      : 0), which keeps another strong in-edge besides this one (placed_victim); else nothing (blocked).  The list keeps its
+ *      order otherwise.  Rows of D are never written and no node of D is given an in-edge.
+ * Rounds repeat until a round finds nothing lost in any group, or max_rounds (0 = 16, at most 64).  A victim can be stranded when
+ * the strong edges of one round vouched for each other; the next round's audit finds it.  Then the audit runs again
+ * (lost_*_after: what could not be fixed is reported, never hidden) and one unfiltered sweep from the default start node counts
+ * unreachable_live (0xFFFFFFFF: not judged, as elsewhere).
+ * Only the neighbor lists are written: n, codes, tids, label sets and start nodes stay; the neighbors' label masks are dropped as
+ * an insert drops them.  Open vs_scans, scan pools and brokers of the index must be ended or rescanned afterwards.  An error
+ * between rounds leaves a valid graph: every row is either its old or its new list.  No guarantee survives later inserts or
+ * deletes: run the audit again.
+ * Refusals leave every byte as it was: VS_ERR_INVALID for plain storage, an index without codes / neighbor lists / label sets,
+ * unknown flags (none are defined), max_rounds > 64; VS_ERR_STATE for a view handle, live views, a batch in flight or an open
+ * vs_pages_out writer. */
+typedef struct vs_label_repair_stats {
+    uint64_t lost_pairs_before, lost_pairs_after;
+    uint64_t placed_free, placed_over_dropped, placed_victim;  /* entries written, by the slot rule that chose them */
+    uint64_t blocked;       /* claimed sources whose row had no slot to give (summed over groups and rounds) */
+    uint64_t contended;     /* lost nodes that lost the claim on their source and waited a round (summed) */
+    uint64_t rows_changed;  /* distinct rows written */
+    uint64_t source_tiles;  /* tiles of lost nodes (8, or 4 when at most 4 are lost) the source kernel streamed every code row for */
+    uint32_t lost_nodes_before, lost_nodes_after;
+    uint32_t rounds;        /* rounds that found something lost */
+    uint32_t sweeps;        /* launches of the reach sweep, both audits included */
+    uint32_t labels_without_start;
+    uint32_t unreachable_live;
+} vs_label_repair_stats;
+int vs_index_repair_labels(vs_index* idx, uint32_t max_rounds /* 0 = 16 */, uint32_t flags /* 0 */, vs_label_repair_stats* out /* may be NULL */);
+/* HIP-event milliseconds on this index since the last reset, collected while vs_profile_enable is on: ms[0] the reach sweeps,
+ * ms[1] strong[], ms[2] the source kernel, ms[3] claim + apply */
+int vs_index_label_repair_kernel_ms(vs_index* idx, double* ms, int reset);
+/* the source kernel on its own (as vs_batch_mates / vs_scan_topk_filtered expose theirs); every argument is a host array.  For
+ * each query node nodes[q] the nearest OTHER row p by (Hamming between the two code rows, id) with node_bits[p] & want[q] != 0 and
+ * (skip == NULL or skip[p] == 0); out_ids[q] = VS_INVALID_NODE and out_ham[q] = 0xFFFFFFFF when there is none (out_ham may be
+ * NULL).  node_bits / skip have one entry per node.  Any code width. */
+int vs_nearest_masked(vs_index* idx, const uint32_t* nodes, const uint64_t* want, uint32_t nq, const uint64_t* node_bits,
+                      const uint8_t* skip, uint32_t* out_ids, uint32_t* out_ham);
 
 /* ---- synthetic corpora generated in HBM (bench / tests; bit-reproducible on the CPU, see pgvectorscale_amd/datagen.py) */
 typedef struct vs_datagen_params {

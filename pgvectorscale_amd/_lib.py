@@ -151,6 +151,22 @@ class CompactStats(C.Structure):
 VS_COMPACT_KEEP_EDGES_CHECK = 1
 
 
+class LabelReachStats(C.Structure):
+    _fields_ = [("lost_pairs", C.c_uint64)] + [(k, C.c_uint32) for k in ("lost_nodes", "labels", "labels_without_start", "sweeps")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class LabelRepairStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("lost_pairs_before", "lost_pairs_after", "placed_free", "placed_over_dropped", "placed_victim",
+                                          "blocked", "contended", "rows_changed", "source_tiles")] + [(k, C.c_uint32) for k in (
+        "lost_nodes_before", "lost_nodes_after", "rounds", "sweeps", "labels_without_start", "unreachable_live")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class DatagenParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("dim", C.c_uint32), ("latent_dim", C.c_uint32), ("n_clusters", C.c_uint32),
                 ("intra_pct", C.c_uint32), ("noise_pct", C.c_uint32), ("normalize", C.c_uint32)]
@@ -329,6 +345,10 @@ SYMBOLS = {
     "vs_batch_mates": (_i, [_vp, _vp, _u32, _u32, _vp, _vp]),
     "vs_batch_mates_filtered": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp]),
     "vs_index_repair": (_i, [_vp, C.POINTER(_u32)]),
+    "vs_index_label_reach": (_i, [_vp, C.POINTER(LabelReachStats), _vp, _vp, _vp, _u32, _vp]),
+    "vs_index_repair_labels": (_i, [_vp, _u32, _u32, C.POINTER(LabelRepairStats)]),
+    "vs_index_label_repair_kernel_ms": (_i, [_vp, C.POINTER(C.c_double), _i]),
+    "vs_nearest_masked": (_i, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "vs_datagen_fill": (_i, [_vp, C.POINTER(DatagenParams), _u64, _u64, _vp]),
     "vs_bruteforce_topk": (_i, [_vp, _vp, _u32, _u32, _vp, _vp]),
 }

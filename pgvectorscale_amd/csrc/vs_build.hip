@@ -2572,3 +2572,840 @@ static int shrink_impl(vs_index* ix) {
 extern "C" int vs_index_shrink_to_fit(vs_index* ix) {
     return vs_guard("vs_index_shrink_to_fit", [&] { return shrink_impl(ix); });
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// vs_index_label_reach / vs_index_repair_labels: what a label-filtered scan can reach, and in-edges for what it cannot
+// (DESIGN.md section 6f has the rule).  A scan with key {l} starts at l's start node and only ever enqueues carriers of l, so a
+// row is returned under {l} only if a chain of carriers leads to it from there.  reach[i] = the labels under whose single-label
+// key node i is reached (64 labels per group, one bit each), need[x] = the labels a live x carries and is not reached under.
+// The repair hands every lost x one in-edge per group and round, from the nearest row that is already reached under a label x
+// still needs; a row serves one node per group and round, and the entry it gives up keeps another in-edge from a row that is
+// reached under everything the entry carries.
+// ---------------------------------------------------------------------------------------------------------------
+#include "vs_device.h"
+
+enum { LR_PLACED_FREE = 0, LR_PLACED_DROPPED, LR_PLACED_VICTIM, LR_BLOCKED, LR_CONTENDED, LR_ALREADY, LR_COUNT, LR_N = 8 };
+#define NEAR_WAVES 4   // waves per workgroup of k_nearest_masked
+#define NEAR_PASSES 4  // 16-row passes in flight per wave
+
+// per-group masks from the label CSR: table[label] = the label's bit in this group, 0xFF = not one of the group's labels
+__global__ __launch_bounds__(256) void k_lr_group_masks(const uint32_t* __restrict__ off, const int16_t* __restrict__ val, uint32_t n,
+                                                        const uint8_t* __restrict__ table, uint64_t* __restrict__ mask) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    uint64_t m = 0;
+    for (uint32_t j = off[i]; j < off[i + 1]; ++j) {
+        const uint32_t b = table[(uint16_t)val[j]];
+        if (b < 64) m |= 1ull << b;
+    }
+    mask[i] = m;
+}
+// a scan with key {l} starts at l's start node whether or not that node carries l (every node once: the host merges the bits)
+__global__ void k_lr_seed(const uint32_t* __restrict__ nodes, const uint64_t* __restrict__ bits, uint32_t ns, uint64_t* __restrict__ reach,
+                          uint64_t* __restrict__ fresh) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ns) return;
+    reach[nodes[t]] = bits[t];
+    fresh[nodes[t]] = bits[t];
+}
+// one lane per list cell u -> v: the bits u gained in the last sweep (fresh_in) that v carries and lacks go into reach[v]; what the
+// atomic really added is v's frontier for the next sweep.  The fixed point does not depend on the order of the atomics.
+__global__ __launch_bounds__(256) void k_lr_sweep(const uint32_t* __restrict__ nbrs, uint32_t nbr_stride, uint32_t R, uint32_t n,
+                                                  const uint64_t* __restrict__ mask, uint64_t jmask, uint64_t* reach,
+                                                  const uint64_t* __restrict__ fresh_in, uint64_t* fresh_out, uint32_t* __restrict__ changed) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)n * R) return;
+    const size_t u = i / R;
+    const uint64_t f = fresh_in[u];
+    if (!f) return;
+    const uint32_t v = nbrs[u * nbr_stride + (i % R)];
+    if (v >= n) return;
+    const uint64_t add = f & mask[v] & jmask & ~reach[v];
+    if (!add) return;
+    const uint64_t old = atomicOr(reinterpret_cast<unsigned long long*>(reach + v), (unsigned long long)add);
+    const uint64_t nw = add & ~old;
+    if (nw) {
+        atomicOr(reinterpret_cast<unsigned long long*>(fresh_out + v), (unsigned long long)nw);
+        *changed = 1;
+    }
+}
+// need[] and the per-bit counters (bitcnt[b] live carriers of bit b, bitcnt[64 + b] lost ones), through an LDS histogram per workgroup;
+// flag[] marks the lost nodes for the count / scan / scatter passes, any[] (may be null) collects them over the groups
+__global__ __launch_bounds__(256) void k_lr_need(const uint8_t* __restrict__ cls, const uint64_t* __restrict__ mask, uint64_t jmask,
+                                                 const uint64_t* __restrict__ reach, uint32_t n, uint64_t* __restrict__ need,
+                                                 uint8_t* __restrict__ flag, uint8_t* __restrict__ any, uint32_t* __restrict__ bitcnt) {
+    __shared__ uint32_t h[128];
+    if (threadIdx.x < 128) h[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) {
+        uint64_t nd = 0;
+        if (cls[i] == 0) {
+            uint64_t m = mask[i];
+            nd = m & jmask & ~reach[i];
+            for (; m; m &= m - 1) atomicAdd(&h[__builtin_ctzll(m)], 1u);
+            for (uint64_t t = nd; t; t &= t - 1) atomicAdd(&h[64 + __builtin_ctzll(t)], 1u);
+        }
+        need[i] = nd;
+        flag[i] = nd != 0;
+        if (nd && any) any[i] = 1;
+    }
+    __syncthreads();
+    if (threadIdx.x < 128 && h[threadIdx.x]) atomicAdd(&bitcnt[threadIdx.x], h[threadIdx.x]);
+}
+// nodes with flag[i] != 0 (and, with cls, class 0)
+__global__ __launch_bounds__(256) void k_lr_count(const uint8_t* __restrict__ flag, uint32_t want, const uint8_t* __restrict__ cls, uint32_t n,
+                                                  unsigned long long* __restrict__ out) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    const uint64_t m = __ballot(i < n && (flag[i] != 0) == (want != 0) && (!cls || cls[i] == 0));
+    if ((threadIdx.x & (WAVE - 1)) == 0 && m) atomicAdd(out, (unsigned long long)__popcll(m));
+}
+// strong[y]: in-edges q -> y from rows outside D that are reached under every label y carries in this group
+__global__ __launch_bounds__(256) void k_lr_strong(const uint32_t* __restrict__ nbrs, uint32_t nbr_stride, uint32_t R, uint32_t n,
+                                                   const uint8_t* __restrict__ cls, const uint64_t* __restrict__ mask, uint64_t jmask,
+                                                   const uint64_t* __restrict__ reach, uint32_t* __restrict__ strong) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)n * R) return;
+    const size_t q = i / R;
+    if (cls[q] == 1) return;
+    const uint32_t y = nbrs[q * nbr_stride + (i % R)];
+    if (y >= n) return;
+    if ((mask[y] & jmask & ~reach[q]) == 0) atomicAdd(&strong[y], 1u);
+}
+
+// k_nearest_masked: for each query node x the minimum of (Hamming(code[x], code[p]) << 32) | p over the rows p != x with
+// bits[p] & want != 0 and skip[p] != 1.  A flat pass over every code row per tile of Q queries, laid out as k_scan_topk (vs_scan.hip):
+// the tile's codes, want words and node ids sit in LDS, 4 lanes x 16 B cover a 64-B sector of a row, 16 rows per wave per pass,
+// NEAR_PASSES passes in flight, a contiguous row range per wave.  Top-1 needs no list: every lane keeps one running minimum per query
+// in registers, a wave folds them with shuffles at the end and publishes with one 64-bit atomicMin per query (the minimum does not
+// depend on the order).  Algorithmic traffic per tile: n x (code row + 8 B of bits + 1 B of skip).
+struct NearArgs {
+    const uint64_t* codes;
+    uint32_t code_stride, n;
+    const uint32_t* qnodes;  // [nq]
+    uint32_t nq;
+    const uint64_t* want;    // [nq], or per node with want_by_node
+    uint32_t want_by_node;
+    const uint64_t* bits;    // [n]
+    const uint8_t* skip;     // [n] or null; 1 = never a source
+    uint32_t rows_per_wave;  // multiple of 16 * NEAR_PASSES
+    unsigned long long* out_key;  // [nq], ~0 before the launch
+};
+__device__ __forceinline__ void near_stage_tile(const NearArgs& a, uint32_t q0, uint32_t Q, uint64_t* qc, uint64_t* qw, uint32_t* qn) {
+    const uint32_t nqt = min(Q, a.nq - q0);
+    for (uint32_t i = threadIdx.x; i < Q * a.code_stride; i += blockDim.x) {
+        const uint32_t qi = i / a.code_stride;
+        qc[i] = qi < nqt ? a.codes[(size_t)a.qnodes[q0 + qi] * a.code_stride + (i - qi * a.code_stride)] : 0ull;
+    }
+    if (threadIdx.x < Q) {
+        const uint32_t qi = threadIdx.x;
+        const uint32_t node = qi < nqt ? a.qnodes[q0 + qi] : VS_INVALID_NODE;
+        qn[qi] = node;
+        qw[qi] = qi < nqt ? (a.want_by_node ? a.want[node] : a.want[q0 + qi]) : 0ull;  // (a query past the tile's end wants nothing)
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ void near_publish(const NearArgs& a, uint32_t q, uint64_t best, int lane) {
+#pragma unroll
+    for (int sh = 1; sh < 64; sh <<= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)best, sh, WAVE);
+        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(best >> 32), sh, WAVE);
+        const uint64_t o = ((uint64_t)hi << 32) | lo;
+        best = o < best ? o : best;
+    }
+    if (lane == 0 && best != ~0ull && q < a.nq) atomicMin(a.out_key + q, (unsigned long long)best);
+}
+template <int NCH, int Q>
+__global__ __launch_bounds__(NEAR_WAVES* WAVE) void k_nearest_masked(NearArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint64_t* qc = reinterpret_cast<uint64_t*>(smem);          // [Q][code_stride]
+    uint64_t* qw = qc + (size_t)Q * a.code_stride;             // [Q]
+    uint32_t* qn = reinterpret_cast<uint32_t*>(qw + Q);        // [Q]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t q0 = blockIdx.x * Q;
+    near_stage_tile(a, q0, Q, qc, qw, qn);
+    const uint32_t gw = blockIdx.y * NEAR_WAVES + wave;
+    const uint32_t r_begin = (uint32_t)min<uint64_t>((uint64_t)gw * a.rows_per_wave, a.n);
+    const uint32_t r_end = (uint32_t)min<uint64_t>((uint64_t)r_begin + a.rows_per_wave, a.n);
+    const int l4 = lane & 3, grp = lane >> 2;
+    uint64_t best[Q];
+#pragma unroll
+    for (int qi = 0; qi < Q; ++qi) best[qi] = ~0ull;
+    for (uint32_t r0 = r_begin; r0 < r_end; r0 += 16 * NEAR_PASSES) {
+        ulonglong2 rows[NEAR_PASSES][NCH];
+        uint64_t rb[NEAR_PASSES];  // the row's bits, 0 for a row that is out of range or skipped
+#pragma unroll
+        for (int p = 0; p < NEAR_PASSES; ++p) {
+            const uint32_t row = r0 + (uint32_t)p * 16 + grp;
+            const bool ok = row < r_end;
+            const uint64_t* rp = a.codes + (size_t)(ok ? row : r_begin) * a.code_stride;
+#pragma unroll
+            for (int t = 0; t < NCH; ++t) {
+                const uint32_t w = 2u * (uint32_t)l4 + 8u * (uint32_t)t;
+                rows[p][t] = (ok && w < a.code_stride) ? *reinterpret_cast<const ulonglong2*>(rp + w) : make_ulonglong2(0, 0);
+            }
+            rb[p] = (ok && !(a.skip && a.skip[row] == 1)) ? a.bits[row] : 0ull;
+        }
+#pragma unroll
+        for (int qi = 0; qi < Q; ++qi) {
+            ulonglong2 qv[NCH];
+#pragma unroll
+            for (int t = 0; t < NCH; ++t) {
+                const uint32_t w = 2u * (uint32_t)l4 + 8u * (uint32_t)t;
+                qv[t] = w < a.code_stride ? *reinterpret_cast<const ulonglong2*>(qc + (size_t)qi * a.code_stride + w) : make_ulonglong2(0, 0);
+            }
+            const uint64_t want = qw[qi];
+            const uint32_t self = qn[qi];
+#pragma unroll
+            for (int p = 0; p < NEAR_PASSES; ++p) {
+                uint32_t acc = 0;
+#pragma unroll
+                for (int t = 0; t < NCH; ++t)
+                    acc += (uint32_t)__popcll(rows[p][t].x ^ qv[t].x) + (uint32_t)__popcll(rows[p][t].y ^ qv[t].y);
+                const uint32_t row = r0 + (uint32_t)p * 16 + grp;
+                const uint64_t key = ((uint64_t)quad_sum(acc) << 32) | row;
+                if ((rb[p] & want) != 0 && row != self && key < best[qi]) best[qi] = key;
+            }
+        }
+    }
+#pragma unroll
+    for (int qi = 0; qi < Q; ++qi) near_publish(a, q0 + (uint32_t)qi, best[qi], lane);
+}
+// code rows of more than 48 words: the same pass with the words of a row walked in a loop (ham_row4), one 16-row pass at a time
+template <int Q>
+__global__ __launch_bounds__(NEAR_WAVES* WAVE) void k_nearest_masked_wide(NearArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint64_t* qc = reinterpret_cast<uint64_t*>(smem);
+    uint64_t* qw = qc + (size_t)Q * a.code_stride;
+    uint32_t* qn = reinterpret_cast<uint32_t*>(qw + Q);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t q0 = blockIdx.x * Q;
+    near_stage_tile(a, q0, Q, qc, qw, qn);
+    const uint32_t gw = blockIdx.y * NEAR_WAVES + wave;
+    const uint32_t r_begin = (uint32_t)min<uint64_t>((uint64_t)gw * a.rows_per_wave, a.n);
+    const uint32_t r_end = (uint32_t)min<uint64_t>((uint64_t)r_begin + a.rows_per_wave, a.n);
+    const int l4 = lane & 3, grp = lane >> 2;
+    uint64_t best[Q];
+#pragma unroll
+    for (int qi = 0; qi < Q; ++qi) best[qi] = ~0ull;
+    for (uint32_t r0 = r_begin; r0 < r_end; r0 += 16) {
+        const uint32_t row = r0 + grp;
+        const bool ok = row < r_end;
+        const uint64_t* rp = a.codes + (size_t)(ok ? row : r_begin) * a.code_stride;
+        const uint64_t rb = (ok && !(a.skip && a.skip[row] == 1)) ? a.bits[row] : 0ull;
+#pragma unroll
+        for (int qi = 0; qi < Q; ++qi) {
+            const uint64_t key = ((uint64_t)ham_row4(rp, qc + (size_t)qi * a.code_stride, l4, a.code_stride, ok) << 32) | row;
+            if ((rb & qw[qi]) != 0 && row != qn[qi] && key < best[qi]) best[qi] = key;
+        }
+    }
+#pragma unroll
+    for (int qi = 0; qi < Q; ++qi) near_publish(a, q0 + (uint32_t)qi, best[qi], lane);
+}
+template <int NCH, int Q>
+static int launch_near_tq(vs_index* ix, const NearArgs& a, dim3 grid, size_t lds) {
+    if (NCH == 0) hipLaunchKernelGGL((k_nearest_masked_wide<Q>), grid, dim3(NEAR_WAVES * WAVE), lds, ix->ctx->stream, a);
+    else hipLaunchKernelGGL((k_nearest_masked<(NCH ? NCH : 1), Q>), grid, dim3(NEAR_WAVES * WAVE), lds, ix->ctx->stream, a);
+    VS_HIP(hipGetLastError());
+    return VS_OK;
+}
+template <int NCH>
+static int launch_near_t(vs_index* ix, const NearArgs& a, uint32_t Q, dim3 grid, size_t lds) {
+    return Q == 4 ? launch_near_tq<NCH, 4>(ix, a, grid, lds) : launch_near_tq<NCH, 8>(ix, a, grid, lds);
+}
+// d_keys [nq] is set to ~0 and receives the minimum keys; every pointer is a device pointer
+static int launch_nearest_masked(vs_index* ix, const uint32_t* d_qnodes, uint32_t nq, const uint64_t* d_want, bool want_by_node,
+                                 const uint64_t* d_bits, const uint8_t* d_skip, unsigned long long* d_keys, uint64_t* tiles = nullptr) {
+    if (nq == 0) return VS_OK;
+    vs_ctx* c = ix->ctx;
+    const uint32_t n = ix->d.n, stride = ix->code_stride;
+    VS_HIP(hipMemsetAsync(d_keys, 0xFF, (size_t)nq * 8, c->stream));
+    // queries per tile: the codes stream once per tile (the flat scan is issue bound from about 8 queries at 24-word codes)
+    const uint32_t Q = nq <= 4 ? 4u : 8u;
+    const uint32_t step = 16 * NEAR_PASSES;
+    uint32_t waves = (uint32_t)c->prop.multiProcessorCount * 8u;
+    uint32_t rows_per_wave = (uint32_t)(((uint64_t)n + waves - 1) / std::max(waves, 1u));
+    rows_per_wave = std::max(step, round_up_u32(rows_per_wave, step));
+    waves = (uint32_t)(((uint64_t)n + rows_per_wave - 1) / rows_per_wave);
+    NearArgs a;
+    a.codes = ix->codes;
+    a.code_stride = stride;
+    a.n = n;
+    a.qnodes = d_qnodes;
+    a.nq = nq;
+    a.want = d_want;
+    a.want_by_node = want_by_node ? 1u : 0u;
+    a.bits = d_bits;
+    a.skip = d_skip;
+    a.rows_per_wave = rows_per_wave;
+    a.out_key = d_keys;
+    const dim3 grid((nq + Q - 1) / Q, (waves + NEAR_WAVES - 1) / NEAR_WAVES);
+    if (tiles) *tiles += grid.x;
+    const size_t lds = (size_t)Q * stride * 8 + (size_t)Q * 12;
+    VS_REQUIRE(lds <= 48 * 1024, "vs_nearest_masked: code rows of %u words do not fit a tile in LDS", stride);
+    switch ((stride + 7) / 8) {
+        case 1: return launch_near_t<1>(ix, a, Q, grid, lds);
+        case 2: return launch_near_t<2>(ix, a, Q, grid, lds);
+        case 3: return launch_near_t<3>(ix, a, Q, grid, lds);
+        case 4: return launch_near_t<4>(ix, a, Q, grid, lds);
+        case 5:
+        case 6: return launch_near_t<6>(ix, a, Q, grid, lds);
+        default: return launch_near_t<0>(ix, a, Q, grid, lds);
+    }
+}
+
+// each source row serves one node per group and round: of the nodes that picked it, the smallest id
+__global__ __launch_bounds__(256) void k_lr_claim(const uint32_t* __restrict__ lost, uint32_t nlost, const unsigned long long* __restrict__ key,
+                                                  uint32_t* __restrict__ claim) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= nlost) return;
+    const unsigned long long k = key[t];
+    if (k != ~0ull) atomicMin(&claim[(uint32_t)k], lost[t]);
+}
+// one wave per lost node x; the wave whose x won the claim on its source p edits p's row: reads p's row, cls, mask, reach, strong,
+// writes one entry of p's row.  No two waves write the same row and nobody reads a row another wave writes.
+__global__ __launch_bounds__(WAVE) void k_lr_apply(const uint32_t* __restrict__ lost, uint32_t nlost, const unsigned long long* __restrict__ key,
+                                                   const uint32_t* __restrict__ claim, uint32_t* nbrs, uint32_t nbr_stride, uint32_t R,
+                                                   uint32_t n, const uint8_t* __restrict__ cls, const uint64_t* __restrict__ mask,
+                                                   uint64_t jmask, const uint64_t* __restrict__ reach, const uint32_t* __restrict__ strong,
+                                                   uint8_t* __restrict__ rowchg, unsigned long long* __restrict__ cnt) {
+    const uint32_t t = blockIdx.x;
+    if (t >= nlost) return;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t x = lost[t];
+    const unsigned long long k = key[t];
+    if (k == ~0ull) {  // (no admissible source: the start node of a needed label always is one, so this is a row of its own making)
+        if (lane == 0) atomicAdd(&cnt[LR_BLOCKED], 1ull);
+        return;
+    }
+    const uint32_t p = (uint32_t)k;
+    if (claim[p] != x) {
+        if (lane == 0) atomicAdd(&cnt[LR_CONTENDED], 1ull);
+        return;
+    }
+    uint32_t* row = nbrs + (size_t)p * nbr_stride;
+    uint32_t len = R;
+    uint64_t named = 0;
+    for (uint32_t c0 = 0; c0 < R && len == R; c0 += WAVE) {
+        const uint32_t j = c0 + lane;
+        const uint32_t e = j < R ? row[j] : VS_INVALID_NODE;
+        const uint64_t inv = __ballot(e == VS_INVALID_NODE);  // (lanes past R read as the sentinel)
+        const uint64_t below = inv ? ((1ull << __builtin_ctzll(inv)) - 1ull) : ~0ull;
+        named |= __ballot(e == x) & below;
+        if (inv) len = min(R, c0 + (uint32_t)__builtin_ctzll(inv));
+    }
+    if (named) {
+        if (lane == 0) atomicAdd(&cnt[LR_ALREADY], 1ull);
+        return;
+    }
+    uint32_t slot = VS_INVALID_NODE, kind = LR_PLACED_FREE;
+    if (len < R) {
+        slot = len;
+    } else {
+        const uint64_t rp = reach[p];
+        for (uint32_t pass = 0; pass < 2 && slot == VS_INVALID_NODE; ++pass) {  // from the last entry backwards
+            kind = pass == 0 ? LR_PLACED_DROPPED : LR_PLACED_VICTIM;
+            for (uint32_t c0 = (R - 1) / WAVE * WAVE; slot == VS_INVALID_NODE; c0 -= WAVE) {
+                const uint32_t j = c0 + lane;
+                const uint32_t y = j < R ? row[j] : VS_INVALID_NODE;
+                bool hit = false;
+                if (y < n) {
+                    if (pass == 0) hit = cls[y] == 1;
+                    else hit = strong[y] >= 1u + ((mask[y] & jmask & ~rp) == 0 ? 1u : 0u);
+                }
+                const uint64_t m = __ballot(hit);
+                if (m) slot = c0 + 63u - (uint32_t)__builtin_clzll(m);
+                if (c0 == 0) break;
+            }
+        }
+    }
+    if (lane == 0) {
+        if (slot == VS_INVALID_NODE) {
+            atomicAdd(&cnt[LR_BLOCKED], 1ull);
+        } else {
+            row[slot] = x;
+            rowchg[p] = 1;
+            atomicAdd(&cnt[kind], 1ull);
+        }
+    }
+}
+
+struct LrState {
+    vs_index* ix = nullptr;
+    const char* what = "";
+    hipStream_t st = nullptr;
+    uint32_t n = 0, R = 0, n_waves = 0;
+    // the labels judged, ascending; groups of 64 in that order
+    std::vector<int16_t> labels;
+    std::vector<uint32_t> lstart;   // the label's start node, VS_INVALID_NODE = none
+    std::vector<uint8_t> carried;   // the label is in some node's set
+    uint32_t without_start = 0, ngroups = 0;
+    bool own_masks = false;         // one group: the index's own label_mask / label_bit
+    std::vector<uint8_t> own_bit, table;
+    // the group in hand
+    const uint64_t* mask = nullptr;
+    uint64_t jmask = 0;             // bits of the group's labels that are carried and have a start node
+    uint8_t bit[64];
+    uint32_t sweeps = 0;
+    // device
+    uint8_t *cls = nullptr, *flag = nullptr, *any = nullptr, *rowchg = nullptr, *d_table = nullptr, *mark = nullptr;
+    uint64_t *mask_buf = nullptr, *reach = nullptr, *fresh[2] = {nullptr, nullptr}, *need = nullptr, *seed_bits = nullptr;
+    uint32_t *wave = nullptr, *strong = nullptr, *claim = nullptr, *lost = nullptr, *seed_nodes = nullptr, *bitcnt = nullptr, *changed = nullptr,
+             *d_starts = nullptr;
+    unsigned long long *cnt = nullptr, *keys = nullptr, *cons_cnt = nullptr;
+    size_t lost_cap = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double ms[4] = {0, 0, 0, 0};
+    void tick() {
+        if (ev[0]) (void)hipEventRecord(ev[0], st);
+    }
+    void tock(int which) {
+        float t = 0.f;
+        if (ev[0] && hipEventRecord(ev[1], st) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
+            hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess)
+            ms[which] += t;
+    }
+    void free_all() {
+        void* ps[] = {cls, flag, any, rowchg, d_table, mark, mask_buf, reach, fresh[0], fresh[1], need, seed_bits, wave, strong, claim, lost,
+                      seed_nodes, bitcnt, changed, d_starts, cnt, keys, cons_cnt};
+        for (void* p : ps)
+            if (p) (void)hipFree(p);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+// the labels, the node classes and the buffers every pass needs (repair: also those of steps 2-5)
+static int lr_init(LrState& S, vs_index* ix, const char* what, bool repair) {
+    S.ix = ix;
+    S.what = what;
+    S.st = ix->ctx->stream;
+    const uint32_t n = S.n = ix->d.n;
+    S.R = ix->d.num_neighbors;
+    S.n_waves = (n + WAVE - 1) / WAVE;
+    vs_ctx* c = ix->ctx;
+    // carried labels: from the index's own label -> bit table when it has one, else from the CSR's values
+    std::vector<uint8_t> present(65536, 0);
+    if (ix->label_mask && ix->label_bit) {
+        S.own_bit.resize(65536);
+        VS_TRY(vs_dev_download(c, S.own_bit.data(), ix->label_bit, 65536));
+        for (uint32_t v = 0; v < 65536; ++v) present[v] = S.own_bit[v] != 0xFF;
+    } else {
+        uint32_t nv = 0;
+        VS_TRY(vs_dev_download(c, &nv, ix->label_off + n, 4));
+        std::vector<int16_t> val(std::max<uint32_t>(nv, 1));
+        if (nv) VS_TRY(vs_dev_download(c, val.data(), ix->label_val, (size_t)nv * 2));
+        for (uint32_t j = 0; j < nv; ++j) present[(uint16_t)val[j]] = 1;
+    }
+    std::map<int16_t, uint32_t> start_of;
+    std::vector<uint32_t> starts(1, ix->d.default_start);
+    if (ix->d.n_label_starts) {
+        const uint32_t ns = ix->d.n_label_starts;
+        std::vector<int16_t> sl(ns);
+        std::vector<uint32_t> sn(ns);
+        VS_TRY(vs_dev_download(c, sl.data(), ix->ls_labels, (size_t)ns * 2));
+        VS_TRY(vs_dev_download(c, sn.data(), ix->ls_nodes, (size_t)ns * 4));
+        for (uint32_t t = 0; t < ns; ++t) {
+            VS_REQUIRE(sn[t] < n, "%s: start node %u of label %d in an index of %u nodes", what, sn[t], (int)sl[t], n);
+            start_of.emplace(sl[t], sn[t]);
+            starts.push_back(sn[t]);
+        }
+    }
+    VS_REQUIRE(starts[0] < n, "%s: default start node %u of an index of %u nodes", what, starts[0], n);
+    for (int v = -32768; v <= 32767; ++v) {
+        const bool car = present[(uint16_t)(int16_t)v] != 0;
+        const auto it = start_of.find((int16_t)v);
+        if (!car && it == start_of.end()) continue;
+        S.labels.push_back((int16_t)v);
+        S.carried.push_back(car);
+        S.lstart.push_back(it == start_of.end() ? VS_INVALID_NODE : it->second);
+        S.without_start += car && it == start_of.end();
+    }
+    S.ngroups = ((uint32_t)S.labels.size() + 63) / 64;
+    S.own_masks = S.ngroups <= 1 && !S.own_bit.empty();
+    std::sort(starts.begin(), starts.end());
+    starts.erase(std::unique(starts.begin(), starts.end()), starts.end());
+    if (c->profiling) {
+        VS_HIP(hipEventCreate(&S.ev[0]));
+        VS_HIP(hipEventCreate(&S.ev[1]));
+    }
+    VS_HIP(hipMalloc(&S.cls, n));
+    VS_HIP(hipMalloc(&S.flag, n));
+    VS_HIP(hipMalloc(&S.any, n));
+    VS_HIP(hipMalloc(&S.reach, (size_t)n * 8));
+    VS_HIP(hipMalloc(&S.fresh[0], (size_t)n * 8));
+    VS_HIP(hipMalloc(&S.fresh[1], (size_t)n * 8));
+    VS_HIP(hipMalloc(&S.need, (size_t)n * 8));
+    VS_HIP(hipMalloc(&S.wave, ((size_t)S.n_waves + 1) * 4));
+    VS_HIP(hipMalloc(&S.seed_nodes, 64 * 4));
+    VS_HIP(hipMalloc(&S.seed_bits, 64 * 8));
+    VS_HIP(hipMalloc(&S.bitcnt, 128 * 4));
+    VS_HIP(hipMalloc(&S.changed, 4));
+    VS_HIP(hipMalloc(&S.cnt, LR_N * 8));
+    VS_HIP(hipMalloc(&S.cons_cnt, CN_N * 8));
+    VS_HIP(hipMalloc(&S.d_starts, starts.size() * 4));
+    VS_HIP(hipMemsetAsync(S.cnt, 0, LR_N * 8, S.st));
+    VS_HIP(hipMemsetAsync(S.cons_cnt, 0, CN_N * 8, S.st));
+    if (!S.own_masks) {
+        VS_HIP(hipMalloc(&S.mask_buf, (size_t)n * 8));
+        VS_HIP(hipMalloc(&S.d_table, 65536));
+        S.table.resize(65536);
+    }
+    if (repair) {
+        VS_HIP(hipMalloc(&S.rowchg, n));
+        VS_HIP(hipMalloc(&S.strong, (size_t)n * 4));
+        VS_HIP(hipMalloc(&S.claim, (size_t)n * 4));
+        VS_HIP(hipMalloc(&S.mark, (size_t)n + 8));
+        VS_HIP(hipMemsetAsync(S.rowchg, 0, n, S.st));
+    }
+    // the node classes of section 6d
+    VS_HIP(hipMemcpyAsync(S.d_starts, starts.data(), starts.size() * 4, hipMemcpyHostToDevice, S.st));
+    hipLaunchKernelGGL(k_cons_classify, dim3((n + 255) / 256), dim3(256), 0, S.st, (const uint64_t*)ix->tids, (const uint32_t*)nullptr, n, S.cls,
+                       S.cons_cnt);
+    VS_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_cons_keep_starts, dim3(((uint32_t)starts.size() + 255) / 256), dim3(256), 0, S.st, (const uint32_t*)S.d_starts,
+                       (uint32_t)starts.size(), S.cls, S.cons_cnt);
+    VS_HIP(hipGetLastError());
+    VS_HIP(hipStreamSynchronize(S.st));  // (starts is a local)
+    return VS_OK;
+}
+
+// steps 1 of a group: masks, reach to its fixed point, need, the per-bit counters and the number of lost nodes (flag[] and the
+// scanned wave counts are left for the scatter)
+static int lr_group_reach(LrState& S, uint32_t g, bool collect_any, uint32_t* nlost, uint32_t* h_bitcnt /*[128]*/) {
+    vs_index* ix = S.ix;
+    const uint32_t n = S.n, R = S.R;
+    const uint32_t lo = g * 64, hi = std::min<uint32_t>(lo + 64, (uint32_t)S.labels.size());
+    std::map<uint32_t, uint64_t> seeds;
+    S.jmask = 0;
+    if (!S.own_masks) std::fill(S.table.begin(), S.table.end(), (uint8_t)0xFF);
+    for (uint32_t li = lo; li < hi; ++li) {
+        const uint8_t b = !S.carried[li] ? (uint8_t)0xFF : S.own_masks ? S.own_bit[(uint16_t)S.labels[li]] : (uint8_t)(li - lo);
+        S.bit[li - lo] = b;
+        if (b == 0xFF) continue;
+        if (!S.own_masks) S.table[(uint16_t)S.labels[li]] = b;
+        if (S.lstart[li] != VS_INVALID_NODE) {
+            S.jmask |= 1ull << b;
+            seeds[S.lstart[li]] |= 1ull << b;
+        }
+    }
+    if (S.own_masks) {
+        S.mask = ix->label_mask;
+    } else {
+        VS_HIP(hipMemcpyAsync(S.d_table, S.table.data(), 65536, hipMemcpyHostToDevice, S.st));
+        hipLaunchKernelGGL(k_lr_group_masks, dim3((n + 255) / 256), dim3(256), 0, S.st, (const uint32_t*)ix->label_off,
+                           (const int16_t*)ix->label_val, n, (const uint8_t*)S.d_table, S.mask_buf);
+        VS_HIP(hipGetLastError());
+        S.mask = S.mask_buf;
+    }
+    VS_HIP(hipMemsetAsync(S.reach, 0, (size_t)n * 8, S.st));
+    VS_HIP(hipMemsetAsync(S.fresh[0], 0, (size_t)n * 8, S.st));
+    VS_HIP(hipMemsetAsync(S.fresh[1], 0, (size_t)n * 8, S.st));
+    std::vector<uint32_t> sn;
+    std::vector<uint64_t> sb;
+    for (const auto& kv : seeds) {
+        sn.push_back(kv.first);
+        sb.push_back(kv.second);
+    }
+    if (!sn.empty()) {
+        VS_HIP(hipMemcpyAsync(S.seed_nodes, sn.data(), sn.size() * 4, hipMemcpyHostToDevice, S.st));
+        VS_HIP(hipMemcpyAsync(S.seed_bits, sb.data(), sb.size() * 8, hipMemcpyHostToDevice, S.st));
+        hipLaunchKernelGGL(k_lr_seed, dim3(1), dim3(64), 0, S.st, (const uint32_t*)S.seed_nodes, (const uint64_t*)S.seed_bits, (uint32_t)sn.size(),
+                           S.reach, S.fresh[0]);
+        VS_HIP(hipGetLastError());
+        VS_HIP(hipStreamSynchronize(S.st));  // (sn / sb are locals)
+        const size_t cells = (size_t)n * R;
+        S.tick();
+        int in = 0;
+        for (uint64_t it = 0;; ++it) {  // no level cap: a rare label's chain is deep
+            if (it > n) {  // (every sweep that changes something lengthens some label's chain, and a chain has at most n nodes)
+                vs_set_error("%s: the reach sweeps did not settle after %u sweeps", S.what, n);
+                return VS_ERR_CAPACITY;
+            }
+            uint32_t changed = 0;
+            VS_HIP(hipMemsetAsync(S.changed, 0, 4, S.st));
+            hipLaunchKernelGGL(k_lr_sweep, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, S.st, (const uint32_t*)ix->nbrs, ix->nbr_stride, R, n,
+                               S.mask, S.jmask, S.reach, (const uint64_t*)S.fresh[in], S.fresh[in ^ 1], S.changed);
+            VS_HIP(hipGetLastError());
+            VS_HIP(hipMemcpyAsync(&changed, S.changed, 4, hipMemcpyDeviceToHost, S.st));
+            VS_HIP(hipMemsetAsync(S.fresh[in], 0, (size_t)n * 8, S.st));
+            VS_HIP(hipStreamSynchronize(S.st));
+            S.sweeps++;
+            in ^= 1;
+            if (!changed) break;
+        }
+        S.tock(0);
+    }
+    VS_HIP(hipMemsetAsync(S.bitcnt, 0, 128 * 4, S.st));
+    const dim3 ngrid((n + 255) / 256);
+    hipLaunchKernelGGL(k_lr_need, ngrid, dim3(256), 0, S.st, (const uint8_t*)S.cls, S.mask, S.jmask, (const uint64_t*)S.reach, n, S.need, S.flag,
+                       collect_any ? S.any : (uint8_t*)nullptr, S.bitcnt);
+    VS_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_cons_work_count, ngrid, dim3(256), 0, S.st, (const uint8_t*)S.flag, n, S.wave);
+    VS_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_cons_work_scan, dim3(1), dim3(256), 0, S.st, S.wave, S.n_waves);
+    VS_HIP(hipGetLastError());
+    // the one small copy per group: how many lost, and the per-bit counters
+    VS_HIP(hipMemcpyAsync(nlost, S.wave + S.n_waves, 4, hipMemcpyDeviceToHost, S.st));
+    VS_HIP(hipMemcpyAsync(h_bitcnt, S.bitcnt, 128 * 4, hipMemcpyDeviceToHost, S.st));
+    VS_HIP(hipStreamSynchronize(S.st));
+    return VS_OK;
+}
+
+static int lr_count_flags(LrState& S, const uint8_t* flag, uint32_t want, const uint8_t* cls, uint32_t* out) {
+    unsigned long long v = 0;
+    VS_HIP(hipMemsetAsync(S.cnt + LR_COUNT, 0, 8, S.st));
+    hipLaunchKernelGGL(k_lr_count, dim3((S.n + 255) / 256), dim3(256), 0, S.st, flag, want, cls, S.n, S.cnt + LR_COUNT);
+    VS_HIP(hipGetLastError());
+    VS_HIP(hipMemcpyAsync(&v, S.cnt + LR_COUNT, 8, hipMemcpyDeviceToHost, S.st));
+    VS_HIP(hipStreamSynchronize(S.st));
+    *out = (uint32_t)v;
+    return VS_OK;
+}
+
+// the audit over all groups on the graph as it stands; carriers / lost: per label of S.labels, or null
+static int lr_audit(LrState& S, uint64_t* pairs, uint32_t* nodes, uint32_t* carriers, uint32_t* lost) {
+    *pairs = 0;
+    VS_HIP(hipMemsetAsync(S.any, 0, S.n, S.st));
+    for (uint32_t g = 0; g < S.ngroups; ++g) {
+        uint32_t nl = 0, bc[128];
+        VS_TRY(lr_group_reach(S, g, true, &nl, bc));
+        for (uint32_t li = g * 64; li < std::min<size_t>((size_t)g * 64 + 64, S.labels.size()); ++li) {
+            const uint8_t b = S.bit[li - g * 64];
+            if (carriers) carriers[li] = b == 0xFF ? 0u : bc[b];
+            if (lost) lost[li] = b == 0xFF ? 0u : bc[64 + b];
+            if (b != 0xFF) *pairs += bc[64 + b];
+        }
+    }
+    return lr_count_flags(S, S.any, 1, nullptr, nodes);
+}
+
+static int label_reach_impl(vs_index* ix, vs_label_reach_stats* out, int16_t* out_labels, uint32_t* out_carriers, uint32_t* out_lost,
+                            uint32_t cap, uint8_t* out_node_lost) {
+    const char* what = "vs_index_label_reach";
+    VS_REQUIRE(ix, "%s: index is NULL", what);
+    if (out) memset(out, 0, sizeof(*out));
+    VS_REQUIRE(ix->label_off && ix->label_val, "%s: the index has no label sets", what);
+    VS_REQUIRE(ix->nbrs && ix->tids, "%s: the index has no neighbor lists", what);
+    if (ix->ws.pending) {
+        vs_set_error("%s: a batch of this handle is in flight (vs_search_batch_dev_finish first)", what);
+        return VS_ERR_STATE;
+    }
+    vs_label_reach_stats s{};
+    if (ix->d.n == 0 || ix->d.default_start == VS_INVALID_NODE) {
+        if (out) *out = s;
+        return VS_OK;
+    }
+    VS_HIP(hipSetDevice(ix->ctx->device));
+    LrState S;
+    std::vector<uint32_t> carriers, lost;
+    auto run = [&]() -> int {
+        VS_TRY(lr_init(S, ix, what, false));
+        carriers.assign(S.labels.size(), 0);
+        lost.assign(S.labels.size(), 0);
+        VS_TRY(lr_audit(S, &s.lost_pairs, &s.lost_nodes, carriers.data(), lost.data()));
+        if (out_node_lost) VS_TRY(vs_dev_download(ix->ctx, out_node_lost, S.any, S.n));
+        return VS_OK;
+    };
+    const int rc = run();
+    (void)hipStreamSynchronize(S.st ? S.st : ix->ctx->stream);
+    S.free_all();
+    VS_TRY(rc);
+    s.labels = (uint32_t)S.labels.size();
+    s.labels_without_start = S.without_start;
+    s.sweeps = S.sweeps;
+    for (uint32_t li = 0; li < std::min<uint32_t>(cap, s.labels); ++li) {
+        if (out_labels) out_labels[li] = S.labels[li];
+        if (out_carriers) out_carriers[li] = carriers[li];
+        if (out_lost) out_lost[li] = lost[li];
+    }
+    if (out) *out = s;
+    return VS_OK;
+}
+extern "C" int vs_index_label_reach(vs_index* ix, vs_label_reach_stats* out, int16_t* out_labels, uint32_t* out_carriers, uint32_t* out_lost,
+                                    uint32_t cap, uint8_t* out_node_lost) {
+    return vs_guard("vs_index_label_reach", [&] { return label_reach_impl(ix, out, out_labels, out_carriers, out_lost, cap, out_node_lost); });
+}
+
+static int repair_labels_impl(vs_index* ix, uint32_t max_rounds, uint32_t flags, vs_label_repair_stats* out) {
+    const char* what = "vs_index_repair_labels";
+    VS_REQUIRE(ix, "%s: index is NULL", what);
+    if (out) memset(out, 0, sizeof(*out));
+    VS_REQUIRE_OWNER(ix, what);
+    VS_REQUIRE_NO_VIEWS(ix, what);
+    VS_REQUIRE(ix->d.storage_type == VS_STORAGE_SBQ, "%s: plain storage is not supported (memory_optimized indexes only)", what);
+    VS_REQUIRE(ix->codes && ix->nbrs && ix->tids, "%s: needs codes, neighbor lists and heap tids on the device", what);
+    VS_REQUIRE(ix->label_off && ix->label_val, "%s: the index has no label sets", what);
+    VS_REQUIRE(flags == 0, "%s: unknown flags 0x%x", what, flags);
+    VS_REQUIRE(max_rounds <= 64, "%s: max_rounds %u outside [0,64]", what, max_rounds);
+    if (max_rounds == 0) max_rounds = 16;
+    if (ix->ws.pending) {
+        vs_set_error("%s: a batch of this handle is in flight (vs_search_batch_dev_finish first)", what);
+        return VS_ERR_STATE;
+    }
+    if (vs_index_open_writers(ix) > 0) {
+        vs_set_error("%s: a vs_pages_out writer of this index is open (its pages would mix rows from before and after; vs_pages_out_close first)", what);
+        return VS_ERR_STATE;
+    }
+    vs_label_repair_stats s{};
+    if (ix->d.n == 0 || ix->d.default_start == VS_INVALID_NODE) {
+        if (out) *out = s;
+        return VS_OK;
+    }
+    VS_HIP(hipSetDevice(ix->ctx->device));
+    LrState S;
+    const uint32_t n = ix->d.n, R = ix->d.num_neighbors;
+    bool wrote = false;
+    auto run = [&]() -> int {
+        VS_TRY(lr_init(S, ix, what, true));
+        hipStream_t st = S.st;
+        VS_TRY(lr_audit(S, &s.lost_pairs_before, &s.lost_nodes_before, nullptr, nullptr));
+        s.lost_pairs_after = s.lost_pairs_before;
+        s.lost_nodes_after = s.lost_nodes_before;
+        const size_t cells = (size_t)n * R;
+        const dim3 cgrid((unsigned)((cells + 255) / 256)), ngrid((n + 255) / 256);
+        for (uint32_t round = 0; s.lost_pairs_before && round < max_rounds; ++round) {
+            bool any_lost = false;
+            for (uint32_t g = 0; g < S.ngroups; ++g) {  // a later group sees what an earlier one wrote
+                uint32_t nl = 0, bc[128];
+                VS_TRY(lr_group_reach(S, g, false, &nl, bc));
+                if (!nl) continue;
+                any_lost = true;
+                if (nl > S.lost_cap) {
+                    if (S.lost) VS_HIP(hipFree(S.lost));
+                    if (S.keys) VS_HIP(hipFree(S.keys));
+                    S.lost = nullptr;
+                    S.keys = nullptr;
+                    S.lost_cap = 0;
+                    VS_HIP(hipMalloc(&S.lost, (size_t)nl * 4));
+                    VS_HIP(hipMalloc(&S.keys, (size_t)nl * 8));
+                    S.lost_cap = nl;
+                }
+                hipLaunchKernelGGL(k_cons_work_scatter, ngrid, dim3(256), 0, st, (const uint8_t*)S.flag, n, (const uint32_t*)S.wave, S.lost);
+                VS_HIP(hipGetLastError());
+                S.tick();
+                VS_HIP(hipMemsetAsync(S.strong, 0, (size_t)n * 4, st));
+                hipLaunchKernelGGL(k_lr_strong, cgrid, dim3(256), 0, st, (const uint32_t*)ix->nbrs, ix->nbr_stride, R, n, (const uint8_t*)S.cls, S.mask,
+                                   S.jmask, (const uint64_t*)S.reach, S.strong);
+                VS_HIP(hipGetLastError());
+                S.tock(1);
+                S.tick();
+                VS_TRY(launch_nearest_masked(ix, S.lost, nl, S.need, true, S.reach, S.cls, S.keys, &s.source_tiles));
+                S.tock(2);
+                S.tick();
+                VS_HIP(hipMemsetAsync(S.claim, 0xFF, (size_t)n * 4, st));
+                hipLaunchKernelGGL(k_lr_claim, dim3((nl + 255) / 256), dim3(256), 0, st, (const uint32_t*)S.lost, nl,
+                                   (const unsigned long long*)S.keys, S.claim);
+                VS_HIP(hipGetLastError());
+                ix->nbr_mask_valid = false;  // (the neighbor lists are about to change: what was derived from them is stale)
+                wrote = true;
+                hipLaunchKernelGGL(k_lr_apply, dim3(nl), dim3(WAVE), 0, st, (const uint32_t*)S.lost, nl, (const unsigned long long*)S.keys,
+                                   (const uint32_t*)S.claim, ix->nbrs, ix->nbr_stride, R, n, (const uint8_t*)S.cls, S.mask, S.jmask,
+                                   (const uint64_t*)S.reach, (const uint32_t*)S.strong, S.rowchg, S.cnt);
+                VS_HIP(hipGetLastError());
+                S.tock(3);
+            }
+            if (!any_lost) break;
+            s.rounds++;
+        }
+        if (s.rounds) VS_TRY(lr_audit(S, &s.lost_pairs_after, &s.lost_nodes_after, nullptr, nullptr));
+        // one unfiltered sweep from the default start node: no live row may have lost its way in
+        VS_HIP(hipMemsetAsync(S.mark, 0, (size_t)n + 8, st));
+        uint32_t* d_changed = reinterpret_cast<uint32_t*>(S.mark + (((size_t)n + 3) & ~(size_t)3));
+        const uint8_t one = 1;
+        VS_HIP(hipMemcpyAsync(S.mark + ix->d.default_start, &one, 1, hipMemcpyHostToDevice, st));
+        bool converged = false;
+        for (uint32_t level = 1; level < 255 && !converged; ++level) {
+            uint32_t changed = 0;
+            VS_HIP(hipMemsetAsync(d_changed, 0, 4, st));
+            hipLaunchKernelGGL(k_reach_sweep, cgrid, dim3(256), 0, st, (const uint32_t*)ix->nbrs, ix->nbr_stride, R, n, S.mark, level, d_changed);
+            VS_HIP(hipGetLastError());
+            VS_HIP(hipMemcpyAsync(&changed, d_changed, 4, hipMemcpyDeviceToHost, st));
+            VS_HIP(hipStreamSynchronize(st));
+            converged = changed == 0;
+        }
+        s.unreachable_live = 0xFFFFFFFFu;
+        if (converged) VS_TRY(lr_count_flags(S, S.mark, 0, S.cls, &s.unreachable_live));
+        uint32_t rc_rows = 0;
+        VS_TRY(lr_count_flags(S, S.rowchg, 1, nullptr, &rc_rows));
+        s.rows_changed = rc_rows;
+        return VS_OK;
+    };
+    int rc = run();
+    (void)hipStreamSynchronize(S.st ? S.st : ix->ctx->stream);
+    unsigned long long h[LR_N] = {0};
+    if (S.cnt) (void)hipMemcpy(h, S.cnt, sizeof h, hipMemcpyDeviceToHost);
+    S.free_all();
+    for (int k = 0; k < 4; ++k) ix->label_repair_ms[k] += S.ms[k];
+    s.placed_free = h[LR_PLACED_FREE];
+    s.placed_over_dropped = h[LR_PLACED_DROPPED];
+    s.placed_victim = h[LR_PLACED_VICTIM];
+    s.blocked = h[LR_BLOCKED];
+    s.contended = h[LR_CONTENDED];
+    s.sweeps = S.sweeps;
+    s.labels_without_start = S.without_start;
+    if (out) *out = s;
+    if (rc == VS_OK && wrote) rc = vs_validate_graph(ix);
+    return rc;
+}
+extern "C" int vs_index_repair_labels(vs_index* ix, uint32_t max_rounds, uint32_t flags, vs_label_repair_stats* out) {
+    return vs_guard("vs_index_repair_labels", [&] { return repair_labels_impl(ix, max_rounds, flags, out); });
+}
+extern "C" int vs_index_label_repair_kernel_ms(vs_index* ix, double* ms /*[4]*/, int reset) {
+    VS_REQUIRE(ix && ms, "vs_index_label_repair_kernel_ms: bad args");
+    for (int k = 0; k < 4; ++k) {
+        ms[k] = ix->label_repair_ms[k];
+        if (reset) ix->label_repair_ms[k] = 0;
+    }
+    return VS_OK;
+}
+
+// ---- vs_nearest_masked: k_nearest_masked on its own -------------------------------------------------------------------------
+static int nearest_masked_impl(vs_index* ix, const uint32_t* nodes, const uint64_t* want, uint32_t nq, const uint64_t* node_bits,
+                               const uint8_t* skip, uint32_t* out_ids, uint32_t* out_ham) {
+    const char* what = "vs_nearest_masked";
+    VS_REQUIRE(ix && (nq == 0 || (nodes && want && node_bits && out_ids)), "%s: bad args", what);
+    VS_REQUIRE(ix->d.storage_type == VS_STORAGE_SBQ && ix->codes, "%s: needs SBQ codes on the device", what);
+    if (nq == 0) return VS_OK;
+    const uint32_t n = ix->d.n;
+    for (uint32_t q = 0; q < nq; ++q) VS_REQUIRE(nodes[q] < n, "%s: query %u names node %u of an index of %u nodes", what, q, nodes[q], n);
+    vs_ctx* c = ix->ctx;
+    VS_HIP(hipSetDevice(c->device));
+    uint32_t* d_nodes = nullptr;
+    uint64_t *d_want = nullptr, *d_bits = nullptr;
+    uint8_t* d_skip = nullptr;
+    unsigned long long* d_keys = nullptr;
+    std::vector<unsigned long long> keys(nq);
+    auto run = [&]() -> int {
+        VS_HIP(hipMalloc(&d_nodes, (size_t)nq * 4));
+        VS_HIP(hipMalloc(&d_want, (size_t)nq * 8));
+        VS_HIP(hipMalloc(&d_bits, (size_t)n * 8));
+        VS_HIP(hipMalloc(&d_keys, (size_t)nq * 8));
+        VS_TRY(vs_dev_upload(c, d_nodes, nodes, (size_t)nq * 4));
+        VS_TRY(vs_dev_upload(c, d_want, want, (size_t)nq * 8));
+        VS_TRY(vs_dev_upload(c, d_bits, node_bits, (size_t)n * 8));
+        if (skip) {
+            std::vector<uint8_t> sk(n);
+            for (uint32_t i = 0; i < n; ++i) sk[i] = skip[i] != 0;
+            VS_HIP(hipMalloc(&d_skip, n));
+            VS_TRY(vs_dev_upload(c, d_skip, sk.data(), n));
+        }
+        VS_TRY(launch_nearest_masked(ix, d_nodes, nq, d_want, false, d_bits, d_skip, d_keys));
+        return vs_dev_download(c, keys.data(), d_keys, (size_t)nq * 8);
+    };
+    const int rc = run();
+    (void)hipStreamSynchronize(c->stream);
+    void* ps[] = {d_nodes, d_want, d_bits, d_skip, d_keys};
+    for (void* p : ps)
+        if (p) (void)hipFree(p);
+    VS_TRY(rc);
+    for (uint32_t q = 0; q < nq; ++q) {
+        out_ids[q] = keys[q] == ~0ull ? VS_INVALID_NODE : (uint32_t)keys[q];
+        if (out_ham) out_ham[q] = keys[q] == ~0ull ? 0xFFFFFFFFu : (uint32_t)(keys[q] >> 32);
+    }
+    return VS_OK;
+}
+extern "C" int vs_nearest_masked(vs_index* ix, const uint32_t* nodes, const uint64_t* want, uint32_t nq, const uint64_t* node_bits,
+                                 const uint8_t* skip, uint32_t* out_ids, uint32_t* out_ham) {
+    return vs_guard("vs_nearest_masked", [&] { return nearest_masked_impl(ix, nodes, want, nq, node_bits, skip, out_ids, out_ham); });
+}

@@ -200,6 +200,7 @@ struct vs_index {
     double insert_ms[3] = {0, 0, 0};   // HIP-event time of k_batch_mates / k_insert_merge_mates / k_insert_anchor (vs_profile_enable; vs_index_insert_kernel_ms)
     double consolidate_ms[2] = {0, 0}; // HIP-event time of the flag pass / k_consolidate_rows (vs_profile_enable; vs_index_consolidate_kernel_ms)
     double compact_ms[2] = {0, 0};     // HIP-event time of the keep flags + maps / the row mover (vs_profile_enable; vs_index_compact_kernel_ms)
+    double label_repair_ms[4] = {0, 0, 0, 0};  // HIP-event time of the reach sweeps / strong[] / k_nearest_masked / claim + apply (vs_index_label_repair_kernel_ms)
     uint32_t build_unreachable = 0;    // nodes the last vs_build_graph left unreachable from the start node (0xFFFFFFFF: not judged)
     const uint8_t* visible = nullptr;  // per node, 0 = the heap fetch finds nothing under the scan's snapshot (nullptr: all visible)
     uint8_t* visible_own = nullptr;    // the library's own copy (vs_index_set_visibility)

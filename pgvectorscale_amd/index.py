@@ -426,6 +426,51 @@ class DiskAnnIndex:
         check(self._L.vs_index_repair(self.h, C.byref(u)))
         return int(u.value)
 
+    def label_reach(self, per_node=False):
+        """vs_index_label_reach, the read-only audit of what label-filtered scans can reach: a live row that carries label l is
+        lost under l when no chain of carriers of l leads to it from l's start node.
+        -> dict of vs_label_reach_stats + "per_label": {label: (live carriers, lost)} (+ "node_lost": uint8 [n] with per_node)"""
+        st = _lib.LabelReachStats()
+        cap = 65536
+        labels, car, lost = np.empty(cap, np.int16), np.empty(cap, np.uint32), np.empty(cap, np.uint32)
+        node = np.zeros(self.desc.n, np.uint8) if per_node else None
+        check(self._L.vs_index_label_reach(self.h, C.byref(st), _p(labels), _p(car), _p(lost), cap, _p(node)))
+        out = st.as_dict()
+        out["per_label"] = {int(labels[i]): (int(car[i]), int(lost[i])) for i in range(out["labels"])}
+        if per_node:
+            out["node_lost"] = node
+        return out
+
+    def repair_labels(self, max_rounds=0):
+        """vs_index_repair_labels: every row a single-label scan cannot reach gets an in-edge from the nearest row that is reached
+        under a label it still needs; only neighbor lists change.  max_rounds 0 = 16.  Open scans, pools and
+        brokers of the index must be rescanned afterwards.  -> dict of vs_label_repair_stats"""
+        st = _lib.LabelRepairStats()
+        try:
+            check(self._L.vs_index_repair_labels(self.h, max_rounds, 0, C.byref(st)))
+        finally:
+            self._refresh()
+        return st.as_dict()
+
+    def label_repair_kernel_ms(self, reset=True):
+        """HIP-event milliseconds of the label repair's kernels since the last reset (Context.profile_enable first)"""
+        ms = (C.c_double * 4)()
+        check(self._L.vs_index_label_repair_kernel_ms(self.h, ms, int(reset)))
+        return {"sweeps": float(ms[0]), "strong": float(ms[1]), "sources": float(ms[2]), "claim_apply": float(ms[3])}
+
+    def nearest_masked(self, nodes, want, node_bits, skip=None):
+        """the repair's source kernel on its own (vs_nearest_masked): for each query node the nearest other row p by (Hamming, id)
+        with node_bits[p] & want[q] != 0 and not skip[p] -> (ids, hamming); VS_INVALID_NODE / 0xFFFFFFFF where there is none"""
+        nodes = np.ascontiguousarray(nodes, np.uint32)
+        want = np.ascontiguousarray(want, np.uint64)
+        bits = np.ascontiguousarray(node_bits, np.uint64)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+        if want.shape != nodes.shape or bits.shape != (self.desc.n,) or (sk is not None and sk.shape != (self.desc.n,)):
+            raise ValueError("one want word per query node, one node_bits word (and skip byte) per node")
+        ids, ham = np.empty(nodes.size, np.uint32), np.empty(nodes.size, np.uint32)
+        check(self._L.vs_nearest_masked(self.h, _p(nodes), _p(want), nodes.size, _p(bits), _p(sk), _p(ids), _p(ham)))
+        return ids, ham
+
     def write_pages(self, **kw):
         """the index as the bytes of a `diskann` index relation (pages.PagesOut in one call; keyword arguments as PagesOut's)"""
         from .pages import PagesOut
