@@ -113,9 +113,12 @@ const char* vs_last_error(void);
  * VS_RERANK_FUSED: how a batch reranks and runs the rescore window — "1" (default) one fused launch, "2" fused with the serial heap
  * replay for every scan, "0" the separate rerank and window kernels; the rows are the same under all three.
  * VS_RERANK_ORDER: the order in which a batch's rerank takes its scans — "1" (default) grouped by corpus neighbourhood when the batch
- * re-reads rows (nq x rows per scan >= 2 n and nq >= 16384), "2" always, "0" never (the scans' own order).  VS_RERANK_SEEDS (default
- * 1024, up to 4096) corpus rows define the neighbourhoods; VS_RERANK_DEAL "0" keeps the order but not the per-XCD split.  The rows
- * returned are the same, bit for bit, under every setting. */
+ * re-reads rows (nq x rows per scan >= 2 n and nq >= 16384), "2" / "3" always, "0" never (the scans' own order).  The neighbourhood
+ * of a scan: under "1" and "3" the region label of the first row of its stream — a label per corpus row (its nearest seed row), built
+ * by the first batch that needs it and rebuilt when the codes or the row numbers have changed; under "2" (and on a view handle) the
+ * seed row nearest to the query's own code, computed per batch.  VS_RERANK_SEEDS corpus rows define the neighbourhoods (up to 4096;
+ * default 2048 for the labels, 1024 for the per-batch seed pass); VS_RERANK_DEAL "0" keeps the order but not the per-XCD split.  The
+ * rows returned are the same, bit for bit, under every setting. */
 int vs_set_option(const char* name, const char* value);
 int vs_get_option(const char* name, char* out, size_t cap);
 const char* vs_version(void);
@@ -182,7 +185,10 @@ int vs_index_prepare_workspace(vs_index* idx);
 int vs_index_get_desc(const vs_index* idx, vs_index_desc* out);
 enum vs_array { VS_ARR_CODES = 0, VS_ARR_NBRS = 1, VS_ARR_TIDS = 2, VS_ARR_VECS = 3, VS_ARR_MEAN = 4, VS_ARR_M2 = 5,
                 VS_ARR_VNORM = 6, VS_ARR_LABEL_OFF = 7, VS_ARR_LABEL_VAL = 8 };
-/* device pointer + row stride (in elements) of one of the index arrays */
+/* device pointer + row stride (in elements) of one of the index arrays.  The caller may write through the pointer, so a hand-out of
+ * VS_ARR_NBRS or VS_ARR_CODES marks what the library derived from that array as stale (the neighbors' label masks; the region labels
+ * of VS_RERANK_ORDER, rebuilt by the next batch that orders by them: milliseconds at 4M rows) — also when the call only wanted the
+ * stride.  It costs time, never a result; a caller on a hot path asks once and keeps the answer. */
 int vs_index_array(const vs_index* idx, int which, void** dev_ptr, uint32_t* row_stride);
 /* diagnostics: the rerank order of the handle's last batch (VS_RERANK_ORDER) — place -> scan number, *out_n entries (0: that batch
  * took the scans' own order), at most cap of them copied to out_perm.  Synchronises the stream. */

@@ -466,7 +466,7 @@ extern "C" void vs_index_free(vs_index* ix) {
     SearchWorkspace& w = ix->ws;
     DevBuf* bufs[] = {&w.q_full, &w.qcodes, &w.qlabels, &w.qlabel_off, &w.hash, &w.heap_g, &w.heap_g4, &w.ghash4, &w.heap_g4b, &w.ghash4b, &w.pool_ctr, &w.fb_flag, &w.phase, &w.timeline, &w.raw_q2, &w.out_ids2, &w.out_tids2, &w.out_dist2, &w.stream_ids,
                       &w.stream_ham, &w.stream_cnt, &w.stats, &w.status, &w.rr_dist, &w.out_ids, &w.out_tids,
-                      &w.out_dist, &w.resort_heap, &w.raw_q, &w.misc, &w.q_index, &w.red, &w.order_work, &w.order_perm};
+                      &w.out_dist, &w.resort_heap, &w.raw_q, &w.misc, &w.q_index, &w.red, &w.order_work, &w.order_perm, &w.order_labels};
     for (DevBuf* b : bufs) devbuf_free(*b);
     if (w.red_host) (void)hipHostFree(w.red_host);
     w.red_host = nullptr;
@@ -849,7 +849,11 @@ extern "C" int vs_index_array(const vs_index* ix, int which, void** p, uint32_t*
     VS_REQUIRE(ix && p, "vs_index_array: bad args");
     uint32_t s = 1;
     switch (which) {
-        case VS_ARR_CODES: *p = ix->codes; s = ix->code_stride; break;
+        case VS_ARR_CODES:  // (the caller may write through this pointer, as below: what was derived from the codes is stale)
+            const_cast<vs_index*>(ix)->codes_epoch++;
+            *p = ix->codes;
+            s = ix->code_stride;
+            break;
         case VS_ARR_NBRS:  // (the caller may write through this pointer: whatever was derived from the neighbor lists is stale;
             // a caller that keeps the pointer and writes again later must ask for it again before the next scan)
             const_cast<vs_index*>(ix)->nbr_mask_valid = false;

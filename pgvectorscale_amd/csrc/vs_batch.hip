@@ -132,20 +132,63 @@ static bool grow_caps(Caps& c, uint32_t ovf) {
     return grew;
 }
 
-// VS_RERANK_ORDER: whether this batch's rerank takes its scans in the order of their corpus neighbourhood (k_scan_regions), and with
-// how many seed rows (0 = no: the launch is the plain one, nothing else runs).  0 = never, 2 = whenever the kernel can tile the
-// index's codes, 1 (default) = by rule: the ordering pays when rows are fetched several times per batch (expected fetches per corpus
-// row nq * M / n >= ORDER_MIN_REUSE) and the batch fills the device many times over (nq >= ORDER_MIN_NQ); below that the keys and the
-// sort cost more than the cache hits can return.  Measured at 4M (6.7 fetches per row, 262 144 scans: profiles/r08); the thresholds
-// themselves are reasoned, not yet measured at their edge.
+// VS_RERANK_ORDER: whether this batch's rerank takes its scans in the order of their corpus neighbourhood, and with how many seed
+// rows (0 = no: the launch is the plain one, nothing else runs).  0 = never, 2 = whenever k_scan_regions can tile the index's codes,
+// keyed by the seed pass over the batch's query codes, 3 = the same keyed by the region labels kept per corpus row (below), 1 (default)
+// = by rule, with the labels: the ordering pays when rows are fetched several times per batch (expected fetches per corpus row
+// nq * M / n >= ORDER_MIN_REUSE) and the batch fills the device many times over (nq >= ORDER_MIN_NQ); below that the keys and the sort
+// cost more than the cache hits can return.  Measured at 4M (6.7 fetches per row, 262 144 scans: profiles/r08, profiles/r14); the
+// thresholds themselves are reasoned, not yet measured at their edge.  A view handle has no labels of its own
+// (it cannot see the owner's codes change) and keys modes 1 and 3 by the seed pass.
 static const double ORDER_MIN_REUSE = 2.0;
 static const uint32_t ORDER_MIN_NQ = 16384;
-static uint32_t rerank_order_seeds(const vs_index* ix, uint32_t nq, uint32_t M) {
+static const uint32_t ORDER_SEEDS = 1024;        // seed rows of the seed pass on the query codes (its cost grows with them)
+static const uint32_t ORDER_LABEL_SEEDS = 2048;  // ... of the region labels (profiles/r14: 8.22 ms of rerank per step against 8.93 at 1 024 and 8.38 at 4 096)
+static uint32_t rerank_order_seeds(const vs_index* ix, uint32_t nq, uint32_t M, bool* by_labels) {
     const uint32_t mode = env_u32("VS_RERANK_ORDER", 1);
+    *by_labels = mode != 2 && !ix->is_view;
     if (mode == 0 || !scan_order_fits(ix)) return 0;
     if (mode == 1 && (nq < ORDER_MIN_NQ || (double)nq * M < ORDER_MIN_REUSE * (double)ix->d.n)) return 0;
-    const uint32_t S = std::min<uint32_t>(std::max<uint32_t>(env_u32("VS_RERANK_SEEDS", 1024), 1), 4096);
+    const uint32_t S = std::min<uint32_t>(std::max<uint32_t>(env_u32("VS_RERANK_SEEDS", *by_labels ? ORDER_LABEL_SEEDS : ORDER_SEEDS), 1), 4096);
     return std::min<uint32_t>(S, ix->d.n);
+}
+
+// The region labels of the index for S seeds: label[i] = the seed row s * (n / S) whose code is nearest to row i's code (lowest s among
+// equals), a property of the codes, built by the first batch that orders by them and kept in the workspace.  Rebuilt when the codes
+// epoch has moved or the seed rows are other ones (S, or n / S after the corpus grew); rows appended since (vs_index_insert) are
+// labelled in place.  A stale label could only cost cache hits, never a result: the order decides when a scan is reranked, not how.
+// Both are paid inside the batch that finds them due; a corpus growing by inserts moves n / S once per S new rows, so it pays one
+// full pass (28 ms at 4M x 768 with 2 048 seeds) per S inserted rows that way.
+static int ensure_region_labels(vs_index* ix, uint32_t S) {
+    vs_ctx* c = ix->ctx;
+    SearchWorkspace& w = ix->ws;
+    const uint32_t n = ix->d.n, step = n / S;
+    const bool kept = w.lab_rows > 0 && w.lab_rows <= n && w.lab_epoch == ix->codes_epoch && w.lab_S == S && w.lab_step == step;
+    const uint32_t from = kept ? w.lab_rows : 0;
+    if (from == n) return VS_OK;
+    const bool debug = env_u32("VS_WS_DEBUG", 0) != 0;
+    if (debug) VS_HIP(hipStreamSynchronize(c->stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    if ((size_t)n * 2 > w.order_labels.bytes) {  // (half as much again: a corpus that grows by inserts moves the labels rarely)
+        DevBuf grown;
+        VS_TRY(devbuf_reserve(c, grown, std::max<size_t>((size_t)n * 2, w.order_labels.bytes + w.order_labels.bytes / 2)));
+        if (from) VS_HIP(hipMemcpyAsync(grown.p, w.order_labels.p, (size_t)from * 2, hipMemcpyDeviceToDevice, c->stream));
+        VS_HIP(hipStreamSynchronize(c->stream));
+        devbuf_free(w.order_labels);
+        w.order_labels = grown;
+    }
+    w.lab_rows = 0;
+    VS_TRY(launch_region_labels(ix, S, step, from, n - from, (uint16_t*)w.order_labels.p));
+    w.lab_rows = n;
+    w.lab_S = S;
+    w.lab_step = step;
+    w.lab_epoch = ix->codes_epoch;
+    if (debug) {
+        VS_HIP(hipStreamSynchronize(c->stream));
+        fprintf(stderr, "[VS_WS_DEBUG] region labels: rows %u .. %u, %u seeds %u rows apart, %.3f ms\n", from, n, S, step,
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    }
+    return VS_OK;
 }
 
 extern "C" int vs_index_rerank_order(vs_index* ix, uint32_t* out_perm, uint32_t cap, uint32_t* out_n) {
@@ -168,11 +211,17 @@ static int run_post_search(vs_index* ix, const BatchPlan& bp, uint32_t* d_out_id
         const uint32_t* perm = nullptr;
         bool deal = false;
         w.order_nq = 0;
-        if (const uint32_t S = rerank_order_seeds(ix, nq, M)) {
-            VS_TRY(devbuf_reserve(c, w.order_work, scan_order_work_bytes(nq, S)));
+        bool by_labels = false;
+        if (const uint32_t S = rerank_order_seeds(ix, nq, M, &by_labels)) {
+            VS_TRY(devbuf_reserve(c, w.order_work, scan_order_work_bytes(nq, S + 1)));
             VS_TRY(devbuf_reserve(c, w.order_perm, (size_t)nq * 4));
+            if (by_labels) VS_TRY(ensure_region_labels(ix, S));  // (outside the timed span: once per index, not per batch)
             hipEvent_t ev = prof_begin(c);
-            VS_TRY(launch_scan_order(ix, (const uint64_t*)w.qcodes.p, nq, S, (uint32_t*)w.order_work.p, (uint32_t*)w.order_perm.p));
+            if (by_labels)
+                VS_TRY(launch_label_order(ix, (const uint16_t*)w.order_labels.p, w.lab_rows, S, (const uint32_t*)w.stream_ids.p,
+                                          (const uint32_t*)w.stream_cnt.p, M, nq, (uint32_t*)w.order_work.p, (uint32_t*)w.order_perm.p));
+            else
+                VS_TRY(launch_scan_order(ix, (const uint64_t*)w.qcodes.p, nq, S, (uint32_t*)w.order_work.p, (uint32_t*)w.order_perm.p));
             prof_end(c, PK_ORDER, ev);
             perm = (const uint32_t*)w.order_perm.p;
             w.order_nq = nq;

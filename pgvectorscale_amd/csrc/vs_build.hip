@@ -2469,6 +2469,7 @@ static int compact_impl(vs_index* ix, uint64_t stage_bytes, uint32_t flags, uint
         }
         ix->d.default_start = new_default;
         ix->d.n = n_after;
+        ix->codes_epoch++;  // (rows have new numbers)
         s.rows_moved = n_after - first;
         s.edges_cut = h_cnt[CN_EDGES_DROPPED];
         s.rows_emptied = h_cnt[CN_EMPTIED];

@@ -264,6 +264,7 @@ extern "C" int vs_sbq_train(vs_index* ix) {
     if (owned) (void)hipFree(rn);
     VS_HIP(e);
     ix->count = ix->d.n;
+    ix->codes_epoch++;  // (the codes follow the quantizer: whoever trains is about to quantise)
     return VS_OK;
 }
 
@@ -322,6 +323,7 @@ extern "C" int vs_sbq_quantize_corpus(vs_index* ix) {
     VS_REQUIRE(ix && ix->vecs, "vs_sbq_quantize_corpus: needs the vector column on the device");
     VS_REQUIRE(ix->count > 0, "vs_sbq_quantize_corpus: quantizer not trained");
     VS_HIP(hipSetDevice(ix->ctx->device));
+    ix->codes_epoch++;
     float* rn = nullptr;
     bool owned = false;
     VS_TRY(index_slice_norms(ix, &rn, &owned));

@@ -148,8 +148,12 @@ struct SearchWorkspace {
         rr_dist, out_ids, out_tids, out_dist, resort_heap, raw_q, misc, q_index,
         raw_q2, out_ids2, out_tids2, out_dist2,  // second set of a pipelined host batch (search_host)
         red,                                      // RED_N u64 sums of the last launch's per-scan arrays (k_reduce_stats)
-        order_work, order_perm;                   // VS_RERANK_ORDER: keys + counting-sort tables, and the batch's rerank order
+        order_work, order_perm,                   // VS_RERANK_ORDER: keys + counting-sort tables, and the batch's rerank order
+        order_labels;                             // ... and the region label (u16: nearest seed row) of corpus rows [0, lab_rows)
     uint32_t order_nq = 0;         // scans of the last batch's rerank order in order_perm (0: it took the scans' own order)
+    // what order_labels was built from: the seed rows s * lab_step for s < lab_S of the codes at epoch lab_epoch (vs_index::codes_epoch)
+    uint32_t lab_rows = 0, lab_S = 0, lab_step = 0;
+    uint64_t lab_epoch = 0;
     uint64_t* red_host = nullptr;  // pinned; the sums land here (this handle's own: two handles of one context may each have a batch in flight)
     bool fb_valid = false;  // fb_flag holds the fallback marks of the last chunk
     // pending async call (vs_search_batch_dev)
@@ -195,6 +199,10 @@ struct vs_index {
     uint32_t nbr_stride = 0;   // u32 per neighbor row (R rounded up to 16)
     uint32_t vec_stride = 0;   // floats per vector row (dim_full rounded up to 4)
     uint64_t* codes = nullptr;
+    // moves whenever the codes of existing rows or the row numbers may have changed (training / quantising, a write hand-out of the
+    // array, page loads, broadcasts, compaction; not an insert, which only appends rows): what was derived from the codes and is kept
+    // between batches (SearchWorkspace::order_labels) is rebuilt when it finds its epoch gone
+    uint64_t codes_epoch = 0;
     uint32_t* nbrs = nullptr;
     uint64_t* tids = nullptr;
     double insert_ms[3] = {0, 0, 0};   // HIP-event time of k_batch_mates / k_insert_merge_mates / k_insert_anchor (vs_profile_enable; vs_index_insert_kernel_ms)
@@ -436,6 +444,12 @@ int launch_rerank_window(vs_index* idx, const float* d_q_full, const uint32_t* d
 bool scan_order_fits(const vs_index* idx);  // the index has codes k_scan_regions can tile (code rows of up to 38 words)
 size_t scan_order_work_bytes(uint32_t nq, uint32_t S);
 int launch_scan_order(vs_index* idx, const uint64_t* d_qcodes, uint32_t nq, uint32_t S, uint32_t* d_work, uint32_t* d_perm);
+// The same order from labels kept per corpus row: d_labels[i] = the seed row (of S, seed_step rows apart) nearest to row i's code.
+// launch_region_labels fills rows [row_begin, row_begin + rows); launch_label_order sorts the scans by (label of the first row of
+// their stream, scan number), scans without a row last (key S: d_work holds scan_order_work_bytes(nq, S + 1) bytes).
+int launch_region_labels(vs_index* idx, uint32_t S, uint32_t seed_step, uint32_t row_begin, uint32_t rows, uint16_t* d_labels);
+int launch_label_order(vs_index* idx, const uint16_t* d_labels, uint32_t lab_rows, uint32_t S, const uint32_t* d_stream_ids,
+                       const uint32_t* d_cnt, uint32_t M, uint32_t nq, uint32_t* d_work, uint32_t* d_perm);
 // the per-scan arrays a batch's finish reads, summed on the device (k_reduce_stats)
 enum { RED_STATUS = 0, RED_VISITS, RED_CAND, RED_DQ, RED_READS, RED_NEXT, RED_FB_SCANS, RED_FB_VISITS, RED_FB_DQ, RED_HEAP_ROWS,
        RED_INS_SUM, RED_INS_MAX, RED_INS_FAST, RED_INS_OV, RED_N = 16 };

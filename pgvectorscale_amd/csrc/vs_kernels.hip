@@ -658,7 +658,8 @@ __global__ __launch_bounds__(256, 6) void k_rerank_window(const float* __restric
 // The order in which a batch's rerank workgroups take the scans (VS_RERANK_ORDER).  A batch whose scans fetch more rows than the
 // corpus has (nq * M > n) reads every row several times; the repeats only hit cache when the scans that share a row run at the same
 // time.  So the scans are grouped by where in the corpus they look: S seed rows (the SBQ codes of corpus rows i * (n / S), read in place
-// — the key is a pure function of the codes as they stand, nothing is cached, nothing can go stale), key(q) = the seed whose code is
+// — the key of the seed pass is a pure function of the codes as they stand, nothing is cached, nothing can go stale; the labels the same
+// kernel writes per corpus row ARE kept, with the codes epoch they were built at: launch_region_labels, vs_batch.hip), key(q) = the seed whose code is
 // nearest to q's code by Hamming distance (the lowest seed index among equals), perm = the scan numbers stably sorted by key.  Only
 // the order of the workgroups changes: every output stays indexed by the scan's own number, and no result depends on a key.
 //
@@ -669,8 +670,10 @@ __global__ __launch_bounds__(256, 6) void k_rerank_window(const float* __restric
 enum { REG_T = 64, REG_P = 66, ORD_CHUNK = 1024 };
 __host__ __device__ static inline size_t scan_regions_lds(uint32_t code_stride) { return (size_t)2 * code_stride * REG_P * 8 + REG_T * 4; }
 
+// (K: uint32_t for the keys of a batch's scans, uint16_t for the labels kept per corpus row)
+template <class K>
 __global__ __launch_bounds__(256) void k_scan_regions(const uint64_t* __restrict__ codes, uint32_t code_stride, uint32_t seed_step, uint32_t S,
-                                                      const uint64_t* __restrict__ qcodes, uint32_t nq, uint32_t* __restrict__ keys) {
+                                                      const uint64_t* __restrict__ qcodes, uint32_t nq, K* __restrict__ keys) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint64_t* qs = reinterpret_cast<uint64_t*>(smem);           // [code_stride][REG_P]: word w of the tile's scan i at w * REG_P + i
     uint64_t* ss = qs + (size_t)code_stride * REG_P;            // the same for the seed tile
@@ -707,7 +710,22 @@ __global__ __launch_bounds__(256) void k_scan_regions(const uint64_t* __restrict
     }
     for (int a = 0; a < 4; ++a) atomicMin(&bestq[tq + a], best[a]);
     __syncthreads();
-    if (tid < REG_T && q0 + tid < nq) keys[q0 + tid] = bestq[tid] & 0xFFFFu;
+    if (tid < REG_T && q0 + tid < nq) keys[q0 + tid] = (K)(bestq[tid] & 0xFFFFu);
+}
+
+// The key of a scan from the labels kept per corpus row: the first row of its stream lies beside the query, so that row's nearest
+// seed stands for the scan's.  A scan without a row (and a row the labels do not cover) gets key S: last in the order.
+__global__ __launch_bounds__(256) void k_order_label_keys(const uint16_t* __restrict__ labels, uint32_t lab_rows, uint32_t S,
+                                                          const uint32_t* __restrict__ stream_ids, const uint32_t* __restrict__ cnt, uint32_t M,
+                                                          uint32_t nq, uint32_t* __restrict__ keys) {
+    const uint32_t q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= nq) return;
+    uint32_t key = S;
+    if (cnt[q] > 0) {
+        const uint32_t id = stream_ids[(size_t)q * M];
+        if (id < lab_rows) key = min((uint32_t)labels[id], S);
+    }
+    keys[q] = key;
 }
 
 // perm = the scan numbers sorted by (key, scan number), a counting sort in three small launches over chunks of ORD_CHUNK scans:
@@ -1170,19 +1188,48 @@ size_t scan_order_work_bytes(uint32_t nq, uint32_t S) {
     const size_t nchunks = (nq + ORD_CHUNK - 1) / ORD_CHUNK;
     return ((size_t)nq + S + (size_t)S * nchunks) * 4;
 }
+// counting sort of nq scans by (key < NK, scan number): d_work = keys[nq], then the sort's tables
+static void launch_order_sort(hipStream_t st, uint32_t* d_work, uint32_t nq, uint32_t NK, uint32_t* d_perm) {
+    const uint32_t nchunks = (nq + ORD_CHUNK - 1) / ORD_CHUNK;
+    uint32_t *d_keys = d_work, *d_total = d_keys + nq, *d_cnt = d_total + NK;
+    hipLaunchKernelGGL(k_order_count, dim3(nchunks), dim3(256), (size_t)NK * 4, st, d_keys, nq, NK, nchunks, d_cnt);
+    hipLaunchKernelGGL(k_order_scan, dim3(NK), dim3(WAVE), 0, st, d_cnt, nchunks, d_total);
+    hipLaunchKernelGGL(k_order_scatter, dim3(nchunks), dim3(256), (size_t)(ORD_CHUNK + NK) * 4, st, d_keys, nq, NK, nchunks, d_cnt, d_total,
+                       d_perm);
+}
 int launch_scan_order(vs_index* idx, const uint64_t* d_qcodes, uint32_t nq, uint32_t S, uint32_t* d_work, uint32_t* d_perm) {
     if (nq == 0) return VS_OK;
     VS_REQUIRE(scan_order_fits(idx) && S >= 1 && S <= 4096 && S <= idx->d.n, "rerank order: %u seeds of %u-word codes not supported", S,
                idx->code_stride);
-    const uint32_t nchunks = (nq + ORD_CHUNK - 1) / ORD_CHUNK;
-    uint32_t *d_keys = d_work, *d_total = d_keys + nq, *d_cnt = d_total + S;
     hipStream_t st = idx->ctx->stream;
-    hipLaunchKernelGGL(k_scan_regions, dim3((nq + REG_T - 1) / REG_T), dim3(256), scan_regions_lds(idx->code_stride), st, idx->codes,
-                       idx->code_stride, idx->d.n / S, S, d_qcodes, nq, d_keys);
-    hipLaunchKernelGGL(k_order_count, dim3(nchunks), dim3(256), (size_t)S * 4, st, d_keys, nq, S, nchunks, d_cnt);
-    hipLaunchKernelGGL(k_order_scan, dim3(S), dim3(WAVE), 0, st, d_cnt, nchunks, d_total);
-    hipLaunchKernelGGL(k_order_scatter, dim3(nchunks), dim3(256), (size_t)(ORD_CHUNK + S) * 4, st, d_keys, nq, S, nchunks, d_cnt, d_total,
-                       d_perm);
+    hipLaunchKernelGGL(k_scan_regions<uint32_t>, dim3((nq + REG_T - 1) / REG_T), dim3(256), scan_regions_lds(idx->code_stride), st, idx->codes,
+                       idx->code_stride, idx->d.n / S, S, d_qcodes, nq, d_work);
+    launch_order_sort(st, d_work, nq, S, d_perm);
+    VS_HIP(hipGetLastError());
+    return VS_OK;
+}
+// (in chunks of 2^20 rows: a launch of about the length of a search step's other kernels, whatever the corpus)
+int launch_region_labels(vs_index* idx, uint32_t S, uint32_t seed_step, uint32_t row_begin, uint32_t rows, uint16_t* d_labels) {
+    VS_REQUIRE(scan_order_fits(idx) && S >= 1 && S <= 4096 && seed_step >= 1 && (uint64_t)(S - 1) * seed_step < idx->d.n &&
+                   (uint64_t)row_begin + rows <= idx->d.n,
+               "region labels: %u seeds %u rows apart, rows %u + %u of %u not supported", S, seed_step, row_begin, rows, idx->d.n);
+    hipStream_t st = idx->ctx->stream;
+    for (uint32_t r0 = row_begin, end = row_begin + rows; r0 < end;) {
+        const uint32_t nr = std::min<uint32_t>(end - r0, 1u << 20);
+        hipLaunchKernelGGL(k_scan_regions<uint16_t>, dim3((nr + REG_T - 1) / REG_T), dim3(256), scan_regions_lds(idx->code_stride), st,
+                           idx->codes, idx->code_stride, seed_step, S, idx->codes + (size_t)r0 * idx->code_stride, nr, d_labels + r0);
+        r0 += nr;
+    }
+    VS_HIP(hipGetLastError());
+    return VS_OK;
+}
+int launch_label_order(vs_index* idx, const uint16_t* d_labels, uint32_t lab_rows, uint32_t S, const uint32_t* d_stream_ids,
+                       const uint32_t* d_cnt, uint32_t M, uint32_t nq, uint32_t* d_work, uint32_t* d_perm) {
+    if (nq == 0) return VS_OK;
+    VS_REQUIRE(d_labels && S >= 1 && S <= 4096 && M >= 1, "rerank order: no labels of %u seeds", S);
+    hipStream_t st = idx->ctx->stream;
+    hipLaunchKernelGGL(k_order_label_keys, dim3((nq + 255) / 256), dim3(256), 0, st, d_labels, lab_rows, S, d_stream_ids, d_cnt, M, nq, d_work);
+    launch_order_sort(st, d_work, nq, S + 1, d_perm);
     VS_HIP(hipGetLastError());
     return VS_OK;
 }

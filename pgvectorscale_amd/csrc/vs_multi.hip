@@ -649,6 +649,7 @@ static int vs_comm_replicate_index_impl(vs_comm* c, vs_index* ix, uint32_t root)
         ix->d.has_labels = hdr[15] ? (uint32_t)hdr[7] : 0;
         ix->d.n_label_starts = nls;
     }
+    if (!is_root) ix->codes_epoch++;
     VS_TRY(bcast_bytes(c, ix->codes, n * ix->code_stride * 8, root));
     VS_TRY(bcast_bytes(c, ix->nbrs, n * ix->nbr_stride * 4, root));
     VS_TRY(bcast_bytes(c, ix->tids, n * 8, root));

@@ -280,6 +280,7 @@ extern "C" int vs_pages_dev_build(vs_pages_dev* d, const vs_index_desc* desc, co
                                d->lay, dd.words, dd.num_neighbors, ix->codes, ix->code_stride, ix->nbrs, ix->nbr_stride, ix->tids,
                                d_err);
             hip_ok(hipGetLastError(), "k_pages_decode");
+            ix->codes_epoch++;
             hip_ok(hipMemcpyAsync(herr, d_err, 16, hipMemcpyDeviceToHost, c->stream), "error record");
             hip_ok(hipStreamSynchronize(c->stream), "k_pages_decode");
         }
