@@ -155,7 +155,9 @@ int vs_dev_download(vs_ctx* ctx, void* dst_host, const void* src_dev, size_t byt
 /* Stage host arrays chunk-wise through pinned buffers to HBM (hipMemcpyAsync, double-buffered) and validate them. */
 int vs_index_upload(vs_ctx* ctx, const vs_index_desc* desc, const vs_index_host* host, vs_index** out);
 /* Allocate an index whose arrays are produced on the device (vs_datagen_*, vs_sbq_train, vs_sbq_quantize_corpus,
- * vs_build_graph); contents are undefined until filled. */
+ * vs_build_graph); contents are undefined until filled.  desc->storage_type == VS_STORAGE_PLAIN allocates a `plain` index: it
+ * needs with_vecs and takes no labels (has_labels 0; vs_index_set_labels refuses it); its graph comes from vs_build_graph and
+ * vs_index_insert, which score with full-precision distances on the vector column. */
 int vs_index_alloc(vs_ctx* ctx, const vs_index_desc* desc, int with_vecs, vs_index** out);
 void vs_index_free(vs_index* idx);
 /* A second handle on the SAME device arrays with its own search workspace, bound to `ctx` (another HIP stream of the same device):
@@ -226,7 +228,8 @@ int vs_index_get_quantizer(const vs_index* idx, float* mean, float* m2, uint64_t
 int vs_index_download(const vs_index* idx, uint64_t* codes, uint32_t* nbrs /*[n][num_neighbors]*/, uint64_t* heap_tids,
                       float* vecs, uint32_t row_begin, uint32_t row_count);
 /* (re)compute the per-node cosine divisor cache from the vector column (exact preprocess_cosine semantics,
- * AM/distance/mod.rs:225-253); called by upload automatically */
+ * AM/distance/mod.rs:225-253), and on a plain cosine index with dim_index < dim_full the cache of the index slices' divisors too;
+ * called by upload automatically */
 int vs_index_refresh_norms(vs_index* idx);
 /* mark heap tuples deleted (what ambulkdelete does to heap_item_pointer, AM/vacuum.rs:24-78) */
 int vs_index_mark_deleted(vs_index* idx, const uint32_t* nodes, uint32_t n);
@@ -897,7 +900,18 @@ int vs_sbq_quantize_corpus(vs_index* idx);
  * the GPU counterpart of Graph::insert / prune_neighbors (AM/graph/mod.rs:392-488,637-717).  With label sets attached
  * (vs_index_set_labels before the call) the build is label-aware as Graph::insert is: a filtered pass from the label start
  * nodes, an unfiltered pass from the default start node, contains_intersection in the pruning rule, and a node becomes the
- * start node of every label it is the first to carry (at most 64 labels per node). */
+ * start node of every label it is the first to carry (at most 64 labels per node).
+ * On a `plain` index (VS_STORAGE_PLAIN, no codes) the same batched build scores with the full-precision pair distance of the
+ * reference's IndexFullDistanceMeasure: d(a -> b) is what a plain scan whose query is node a's raw row gives row b, over the first
+ * dim_index dimensions; keys are ordered like f32::total_cmp, every order is ascending (key, id).  The
+ * cosine divisors of the rows are recomputed from the vector column first.  Node 0 is the default start; the repair pass and the
+ * validation of the lists run as for SBQ.
+ * Every argument check and every refusal comes before the first byte of the neighbor lists is written: VS_ERR_INVALID for a
+ * search_list_size outside [1,1000], a max_alpha outside [1,5], a node with more than 64 labels, and on a plain index for the
+ * inner-product distance (DistanceWithTieBreak::new asserts distance >= 0, which -dot violates: the reference has no behaviour to
+ * mirror; IP search on an uploaded plain index is unaffected), label sets, or a missing vector column — the index is left byte
+ * for byte as it was.  Still refused for plain storage, unchanged: vs_index_consolidate_deletes, vs_index_repair_labels,
+ * vs_pages_out_open. */
 int vs_build_graph(vs_index* idx, uint32_t search_list_size, double max_alpha, uint32_t batch_max, uint64_t seed);
 /* nodes the last vs_build_graph could not make reachable from the default start node (its repair pass gives every such
  * node an in-edge where that strands nobody else; 0 on well-formed input, 0xFFFFFFFF = graph deeper than the pass can judge).
@@ -919,8 +933,15 @@ uint32_t vs_index_build_unreachable(const vs_index* idx);
  *     anchored node of its batch does — two new nodes that only name each other are not.  A node that is not anchored is given a slot
  *     in the list of its closest old-or-anchored out-neighbor (a free one, else that of the list's last entry when that entry keeps
  *     another such in-edge); what cannot be placed is counted in orphans_left, never hidden.
- * memory_optimized (SBQ) indexes with the vector column on the device; VS_ERR_INVALID for plain storage.  VS_ERR_STATE: the
- * quantizer is untrained (count == 0), a view of the index is alive, a batch is in flight, or a caller-owned device visibility
+ * Indexes with the vector column on the device.  A `plain` index (VS_STORAGE_PLAIN) takes the same path without the SBQ parts: the
+ * rows are staged behind n with their tids and cosine divisors (of the full row, and of the index slice when dim_index <
+ * dim_full), nothing touches the codes, there is no quantizer to be trained (count == 0 is no obstacle), label_off must be NULL,
+ * and searches, pruning, back-edges and the batch's mates score with the pair distance of vs_build_graph's plain form (mates by
+ * (key of d(row -> other), id)); vs_insert_stats is filled the same way.  VS_ERR_INVALID, the index left byte for byte as it was,
+ * for a plain index whose distance is the inner product (see vs_build_graph), that is handed label sets, or that came from
+ * vs_index_upload: such an index mirrors a relation, vs_pages_out_open cannot write plain storage back, and rows inserted on the
+ * device alone would never reach it — only plain indexes made with vs_index_alloc take rows (vs_build_graph takes both).  VS_ERR_STATE: the
+ * quantizer of an SBQ index is untrained (count == 0), a view of the index is alive, a batch is in flight, or a caller-owned device visibility
  * mask (vs_index_set_visibility_dev) is in force — the library cannot grow it; clear or replace it first.  New rows are visible
  * (1) in the library's own mask and invisible (0) in every stored snapshot mask: a snapshot taken before the insert cannot see the
  * tuple.  An insert changes n and may MOVE every array: open vs_scans, scan pools (vs_scanpool_*, whose prefetched round must have
@@ -956,8 +977,11 @@ int vs_index_insert_dev(vs_index* idx, const float* d_vectors, const uint64_t* h
                         const int16_t* label_val, uint32_t n_new, uint32_t search_list_size, double max_alpha, uint32_t batch_max,
                         vs_insert_stats* out);
 /* HIP-event milliseconds the three insert kernels took on this index since the last reset, collected while vs_profile_enable is on:
- * ms[0] the batch's mates, ms[1] their merge into the candidate lists, ms[2] the anchoring rounds */
+ * ms[0] the batch's mates (k_batch_mates, or the plain form on a plain index), ms[1] their merge into the candidate lists, ms[2] the anchoring rounds */
 int vs_index_insert_kernel_ms(vs_index* idx, double* ms, int reset);
+/* the same for the batch machinery vs_build_graph and vs_index_insert share (SBQ and plain alike): ms[0] the build-mode searches,
+ * ms[1] the prune of the new nodes' out-edges, ms[2] the back-edges (sort, segment heads, re-prune per target) */
+int vs_index_build_kernel_ms(vs_index* idx, double* ms, int reset);
 /* the batch-mates kernel on its own (as vs_hamming_gather / vs_rerank expose theirs): for each of n code rows (host [n][words]) the c
  * (1..64) nearest OTHER rows by (Hamming, row number), ties to the lower row; out_ids / out_ham [n][c], padded with VS_INVALID_NODE
  * (out_ham may be NULL) */
@@ -967,6 +991,18 @@ int vs_batch_mates(vs_index* idx, const uint64_t* codes, uint32_t n, uint32_t c,
  * de-duplicated label sets, at most 64 labels per row; a row without labels has no mates */
 int vs_batch_mates_filtered(vs_index* idx, const uint64_t* codes, const uint32_t* label_off, const int16_t* label_val, uint32_t n,
                             uint32_t c, uint32_t* out_ids, uint32_t* out_ham);
+/* The two kernels of the plain-storage build on their own, so that they can be pinned exactly; both only read the index (a plain
+ * index with its cosine divisors in place: uploaded, built or inserted into; VS_ERR_INVALID otherwise and for the inner product).
+ * vs_batch_mates_plain: for rows first_node .. first_node + n - 1 of the index the c (1..64) nearest OTHER rows of that range by
+ * (key of d(row -> other), row), ties to the lower row; out_ids [n][c] are row numbers inside the range, padded with
+ * VS_INVALID_NODE; out_dist [n][c] (may be NULL) the f32 pair distances, bits 0xFFFFFFFF in the padding.
+ * vs_prune_plain: for each of np points what add_neighbors + prune_neighbors make of its candidate set cand_ids[cand_off[i] ..
+ * cand_off[i + 1]) (any ids of the index, at most 4096 per point): every id once, never the point, sorted by (key of d(point ->
+ * id), id); all of them in that order when they fit num_neighbors, else the alpha ladder 1.0, x1.2 while <= max_alpha with
+ * get_factor on d(existing -> candidate).  out_rows [np][num_neighbors] padded with VS_INVALID_NODE, out_len [np]. */
+int vs_batch_mates_plain(vs_index* idx, uint32_t first_node, uint32_t n, uint32_t c, uint32_t* out_ids, float* out_dist);
+int vs_prune_plain(vs_index* idx, const uint32_t* points, const uint32_t* cand_off, const uint32_t* cand_ids, uint32_t np,
+                   double max_alpha, uint32_t* out_rows, uint32_t* out_len);
 /* the repair pass of vs_build_graph on its own (after many inserts, at the caller's choice): every node the default start node does
  * not reach is given an in-edge where that strands nobody else; *unreachable (may be NULL) = what vs_index_build_unreachable reports.
  * It treats a tombstone like any node: after vs_index_consolidate_deletes it would hand the dropped tombstones in-edges again. */

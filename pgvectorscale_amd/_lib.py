@@ -342,8 +342,11 @@ SYMBOLS = {
     "vs_index_insert": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, C.c_double, _u32, C.POINTER(InsertStats)]),
     "vs_index_insert_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, C.c_double, _u32, C.POINTER(InsertStats)]),
     "vs_index_insert_kernel_ms": (_i, [_vp, C.POINTER(C.c_double), _i]),
+    "vs_index_build_kernel_ms": (_i, [_vp, C.POINTER(C.c_double), _i]),
     "vs_batch_mates": (_i, [_vp, _vp, _u32, _u32, _vp, _vp]),
     "vs_batch_mates_filtered": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp]),
+    "vs_batch_mates_plain": (_i, [_vp, _u32, _u32, _u32, _vp, _vp]),
+    "vs_prune_plain": (_i, [_vp, _vp, _vp, _vp, _u32, C.c_double, _vp, _vp]),
     "vs_index_repair": (_i, [_vp, C.POINTER(_u32)]),
     "vs_index_label_reach": (_i, [_vp, C.POINTER(LabelReachStats), _vp, _vp, _vp, _u32, _vp]),
     "vs_index_repair_labels": (_i, [_vp, _u32, _u32, C.POINTER(LabelRepairStats)]),

@@ -515,8 +515,24 @@ static int index_alloc_fill(vs_ctx* c, const vs_index_desc* desc, vs_index* ix) 
 }
 
 extern "C" int vs_index_alloc(vs_ctx* c, const vs_index_desc* desc, int with_vecs, vs_index** out) {
+    VS_REQUIRE(desc, "vs_index_alloc: index desc is NULL");
+    const bool plain = desc->storage_type == VS_STORAGE_PLAIN;
+    VS_REQUIRE(desc->storage_type == VS_STORAGE_SBQ || plain, "vs_index_alloc: unknown storage_type %u", desc->storage_type);
+    if (plain) {  // PlainNode = vector + neighbor pointers + heap pointer (AM/plain/node.rs): built and grown on its vectors
+        VS_REQUIRE(with_vecs, "vs_index_alloc: plain storage needs the vector column (with_vecs)");
+        VS_REQUIRE(!desc->has_labels, "vs_index_alloc: Plain storage does not support label filters");
+    }
     VS_TRY(index_alloc_common(c, desc, with_vecs != 0, out));
-    const int r = index_alloc_fill(c, desc, *out);
+    int r = index_alloc_fill(c, desc, *out);
+    if (r == VS_OK && plain && desc->dim_index < desc->dim_full && desc->distance_type == VS_COSINE) {  // divisors of the index slices
+        vs_index* ix = *out;
+        const size_t nb = (size_t)std::max<uint32_t>(desc->n, 1) * 4;
+        if (hipMalloc(&ix->vnorm_idx, nb) != hipSuccess || hipMemsetAsync(ix->vnorm_idx, 0, nb, c->stream) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess) {
+            vs_set_error("vs_index_alloc: out of device memory");
+            r = VS_ERR_OOM;
+        }
+    }
     if (r != VS_OK) {
         vs_index_free(*out);
         *out = nullptr;
@@ -575,6 +591,7 @@ static int vs_index_set_labels_impl(vs_index* ix, const uint32_t* label_off, con
     VS_REQUIRE(ix && label_off, "vs_index_set_labels: bad args");
     VS_REQUIRE_OWNER(ix, "vs_index_set_labels");
     VS_REQUIRE_NO_VIEWS(ix, "vs_index_set_labels");
+    VS_REQUIRE(ix->d.storage_type != VS_STORAGE_PLAIN, "vs_index_set_labels: Plain storage does not support label filters");
     const uint32_t n = ix->d.n;
     VS_REQUIRE(label_off[0] == 0, "label_off[0] must be 0");
     for (uint32_t i = 0; i < n; ++i) {
@@ -729,6 +746,7 @@ extern "C" int vs_index_device(const vs_index* ix) { return ix ? ix->ctx->device
 extern "C" int vs_index_refresh_norms(vs_index* ix) {
     VS_REQUIRE(ix, "vs_index_refresh_norms: index is NULL");
     VS_TRY(launch_row_norms(ix));
+    VS_TRY(launch_slice_norms_range(ix, 0, ix->d.n));  // (a plain cosine index with dim_index < dim_full: its second cache)
     VS_HIP(hipStreamSynchronize(ix->ctx->stream));
     return VS_OK;
 }
@@ -780,6 +798,7 @@ static int vs_index_upload_impl(vs_ctx* c, const vs_index_desc* desc, const vs_i
     VS_REQUIRE(!desc->has_labels || (h->label_off && h->label_val), "has_labels set but no label arrays");
     vs_index* ix = nullptr;
     VS_TRY(index_alloc_common(c, desc, h->vecs != nullptr, &ix));
+    ix->uploaded = true;
     int r = VS_OK;
     const size_t n = desc->n;
     do {

@@ -17,6 +17,8 @@
 // to carry (update_start_nodes, AM/graph/mod.rs:490-531), and prune_neighbors only lets an existing neighbor occlude a
 // candidate when it carries every label the candidate shares with the point (contains_intersection,
 // AM/labels/mod.rs:85-111, used at AM/graph/mod.rs:442-456).
+// `plain` storage (no codes): the same batches, pruning and back-edges score with the full-precision pair distance of
+// IndexFullDistanceMeasure instead (PlainPair below; DESIGN.md section 6g has the rule).
 #include <algorithm>
 #include <cstdlib>
 #include <map>
@@ -24,9 +26,7 @@
 
 #include <hipcub/hipcub.hpp>
 
-#include "vs_internal.h"
-
-#define WAVE 64
+#include "vs_device.h"
 
 __device__ __forceinline__ uint32_t ham_words(const uint64_t* a, const uint64_t* b, uint32_t stride) {
     uint32_t acc = 0;
@@ -98,13 +98,125 @@ __device__ __forceinline__ uint64_t label_pmask(const uint32_t* __restrict__ lab
     return m;
 }
 
-// prune_neighbors for one node by one wave.  cand_id/cand_d: C candidates sorted ascending by (distance, id)
-// (LDS).  ccode: optional LDS copy of the candidate codes [C][stride] (nullptr => read codes from global).
-// Writes up to R selected candidate *positions* into sel[] (LDS) and returns their number.
-__device__ uint32_t wave_prune(const uint32_t* cand_id, const uint32_t* cand_d, uint32_t C, const uint64_t* ccode,
-                               const uint64_t* __restrict__ codes, uint32_t stride, uint32_t R, float max_alpha,
-                               float* maxf /*LDS [C]*/, uint32_t* sel /*LDS [R]*/, int lane,
+// ---- the pair distance of the build: what wave_prune, the back-edge kernel and the candidate keys score with ----------------
+// A policy names G, the lanes that score one candidate together (the tail of a selected candidate is walked 64 / G candidates per
+// pass), select(i) — candidate i was taken: its side of the pairs that follow — and factor(j, key of d(point -> j), act):
+// get_factor (AM/graph/neighbor_with_distance.rs:55-65) of candidate j against the selected one, a call every lane makes and
+// whose value counts on the first lane of j's group.
+// HamPair: SbqNodeDistanceMeasure (AM/sbq/mod.rs:161-190), xor + popcount of two code rows, one lane per candidate.
+struct PlainVecs {  // what a kernel needs of a plain index to score pairs (all zero for the SBQ forms)
+    const float* vecs;
+    const float* vdiv;  // cosine: the divisors of the index slices (vnorm, or vnorm_idx when dim_index < dim_full); else nullptr
+    uint32_t vec_stride, dim, distance_type;
+};
+struct HamPair {
+    static constexpr uint32_t G = 1;
+    const uint64_t* ccode;  // LDS copy of the candidate codes [C][stride], or nullptr: rows are read from global memory
+    const uint64_t* __restrict__ codes;
+    const uint32_t* cand_id;
+    uint32_t stride;
+    const uint64_t* ci;
+    __device__ __forceinline__ void select(uint32_t i, int) { ci = ccode ? ccode + (size_t)i * stride : codes + (size_t)cand_id[i] * stride; }
+    __device__ __forceinline__ float factor(uint32_t j, uint32_t dpc, bool act, int) const {
+        if (!act) return 0.0f;
+        const uint64_t* cj = ccode ? ccode + (size_t)j * stride : codes + (size_t)cand_id[j] * stride;
+        const uint32_t dij = ham_words(cj, ci, stride);
+        if (dij == 0) return dpc == 0 ? 1.0f : 3.0e38f;
+        return (float)dpc / (float)dij;
+    }
+};
+// PlainPair: IndexFullDistanceMeasure of `plain` storage.  d(a -> b) is what a plain scan whose query is
+// node a's raw row gives row b: the query side is a's index slice prepared as k_prepare_index_slice prepares a query (for cosine
+// divided by the divisor preprocess_cosine derives — the one k_row_norms cached for the row, same sum in the same order), held in
+// LDS as the qv of plain_dist8; the row side is b's raw row and its cached divisor.  Eight lanes score one candidate, so a pass
+// covers eight rows, each read from global memory in 16-byte pieces.  Keys are plain_key(d), distances come back with plain_unkey.
+struct PlainPair {
+    static constexpr uint32_t G = 8;
+    const float* __restrict__ vecs;
+    const float* __restrict__ vdiv;  // per-row cosine divisor of the index slice; nullptr for the other distance types
+    const uint32_t* cand_id;
+    float* qv;  // LDS [round_up(dim, 4)]
+    uint32_t vec_stride, dim, distance_type;
+    // node's prepared index slice becomes the query side (barriers on both ends: qv may still be read, and is read next)
+    __device__ __forceinline__ void stage(uint32_t node, int lane) const {
+        __syncthreads();
+        const float* row = vecs + (size_t)node * vec_stride;
+        const float s = vdiv ? vdiv[node] : 0.0f;
+        for (uint32_t i = 4u * (uint32_t)lane; i < dim; i += 4u * WAVE) {  // (rows are 16-byte aligned and padded to four floats)
+            float4 x = *reinterpret_cast<const float4*>(row + i);
+            if (s != 0.0f) {
+                x.x = x.x / s;
+                x.y = x.y / s;
+                x.z = x.z / s;
+                x.w = x.w / s;
+            }
+            *reinterpret_cast<float4*>(qv + i) = x;
+        }
+        __syncthreads();
+    }
+    // d(staged node -> node), valid on the first lane of each 8-lane group
+    __device__ __forceinline__ float dist(uint32_t node, bool act, int lane) const {
+        const float sdiv = (act && vdiv) ? vdiv[node] : 0.0f;
+        return plain_dist8(vecs + (size_t)(act ? node : 0u) * vec_stride, sdiv, qv, dim, distance_type, lane, act);
+    }
+    __device__ __forceinline__ void select(uint32_t i, int lane) const { stage(cand_id[i], lane); }
+    __device__ __forceinline__ float factor(uint32_t j, uint32_t dpc_key, bool act, int lane) const {
+        const float d_ec = dist(act ? cand_id[j] : 0u, act, lane);  // the existing neighbour is the query (AM/graph/mod.rs:434-465)
+        const float d_pc = plain_unkey(dpc_key);
+        const float eps = 1.1920929e-07f;  // f32::EPSILON
+        if (d_ec < eps) return d_pc < eps ? 1.0f : 3.0e38f;
+        return d_pc / d_ec;
+    }
+};
+
+// prune_neighbors for one node by one wave.  cand_id/cand_d: C candidates sorted ascending by (distance, id) (LDS); pd: the pair
+// distance (above).  Writes up to R selected candidate *positions* into sel[] (LDS) and returns their number.
+template <class P>
+__device__ uint32_t wave_prune(P& pd, const uint32_t* cand_d, uint32_t C, uint32_t R, float max_alpha, float* maxf /*LDS [C]*/,
+                               uint32_t* sel /*LDS [R]*/, int lane,
                                const uint64_t* pm = nullptr /*LDS [C] label masks (label_pmask) or nullptr*/) {
+    const float FMAX = 3.0e38f;
+    for (uint32_t j = lane; j < C; j += WAVE) maxf[j] = 0.0f;
+    __syncthreads();
+    uint32_t nres = 0;
+    float alpha = 1.0f;
+    while (alpha <= max_alpha && nres < R) {
+        for (uint32_t i = 0; i < C && nres < R; ++i) {
+            float mf = maxf[i];
+            if (mf > alpha) continue;
+            __syncthreads();
+            if (lane == 0) {
+                maxf[i] = FMAX;
+                sel[nres] = i;
+            }
+            nres++;
+            pd.select(i, lane);
+            for (uint32_t j0 = i + 1; j0 < C; j0 += WAVE / P::G) {  // (uniform trip count: factor() is a call of the whole wave)
+                const uint32_t j = j0 + (uint32_t)lane / P::G;
+                bool act = j < C;
+                float mj = 0.0f;
+                if (act) {
+                    mj = maxf[j];
+                    act = !(mj > max_alpha);
+                    if (act && pm && (pm[j] & ~pm[i]) != 0) act = false;  // "Does it contain essential labels?" (AM/graph/mod.rs:442-456)
+                }
+                const float factor = pd.factor(j, act ? cand_d[j] : 0u, act, lane);
+                if (act && ((uint32_t)lane & (P::G - 1)) == 0) maxf[j] = fmaxf(mj, factor);
+            }
+            __syncthreads();
+        }
+        alpha *= 1.2f;
+    }
+    __syncthreads();
+    return nres;
+}
+
+// the SBQ form: the register loop for 24-word codes, else wave_prune<HamPair>.  ccode: optional LDS copy of the candidate codes
+// [C][stride] (nullptr => read codes from global).
+__device__ uint32_t wave_prune_ham(const uint32_t* cand_id, const uint32_t* cand_d, uint32_t C, const uint64_t* ccode,
+                                   const uint64_t* __restrict__ codes, uint32_t stride, uint32_t R, float max_alpha,
+                                   float* maxf /*LDS [C]*/, uint32_t* sel /*LDS [R]*/, int lane,
+                                   const uint64_t* pm = nullptr /*LDS [C] label masks (label_pmask) or nullptr*/) {
     const float FMAX = 3.0e38f;
     if (ccode && stride == 24 && C <= WAVE) {
         // register form of the same loop (768 x 2 bit / 1536 x 1 bit codes, at most one candidate per lane): lane j keeps
@@ -148,42 +260,15 @@ __device__ uint32_t wave_prune(const uint32_t* cand_id, const uint32_t* cand_d, 
         __syncthreads();
         return nres;
     }
-    for (uint32_t j = lane; j < C; j += WAVE) maxf[j] = 0.0f;
-    __syncthreads();
-    uint32_t nres = 0;
-    float alpha = 1.0f;
-    while (alpha <= max_alpha && nres < R) {
-        for (uint32_t i = 0; i < C && nres < R; ++i) {
-            float mf = maxf[i];
-            if (mf > alpha) continue;
-            __syncthreads();
-            if (lane == 0) {
-                maxf[i] = FMAX;
-                sel[nres] = i;
-            }
-            nres++;
-            const uint64_t* ci = ccode ? ccode + (size_t)i * stride : codes + (size_t)cand_id[i] * stride;
-            for (uint32_t j = i + 1 + lane; j < C; j += WAVE) {
-                float mj = maxf[j];
-                if (mj > max_alpha) continue;
-                if (pm && (pm[j] & ~pm[i]) != 0) continue;  // "Does it contain essential labels?" (AM/graph/mod.rs:442-456)
-                const uint64_t* cj = ccode ? ccode + (size_t)j * stride : codes + (size_t)cand_id[j] * stride;
-                uint32_t dij = ham_words(cj, ci, stride);
-                float factor;
-                if (dij == 0) factor = cand_d[j] == 0 ? 1.0f : FMAX;
-                else factor = (float)cand_d[j] / (float)dij;
-                maxf[j] = fmaxf(mj, factor);
-            }
-            __syncthreads();
-        }
-        alpha *= 1.2f;
-    }
-    __syncthreads();
-    return nres;
+    HamPair pd{ccode, codes, cand_id, stride, nullptr};
+    return wave_prune(pd, cand_d, C, R, max_alpha, maxf, sel, lane, pm);
 }
 
 // ---- out-edges of the new nodes of one batch ------------------------------------------------------------------
 // one wave per new node p = b0 + blockIdx.x.  Input: its visited list (sorted) from k_search<BUILD>.
+// PLAIN: the candidates' keys are plain_key(d(p -> candidate)) and pruning scores with PlainPair; the area behind sel[] holds the
+// selected candidate's prepared vector instead of code rows.
+template <bool PLAIN>
 __global__ __launch_bounds__(WAVE) void k_build_prune_new(const uint64_t* __restrict__ codes, uint32_t stride,
                                                           uint32_t* __restrict__ nbrs, uint32_t nbr_stride, uint32_t R,
                                                           float max_alpha, uint32_t b0, uint32_t bn,
@@ -191,7 +276,7 @@ __global__ __launch_bounds__(WAVE) void k_build_prune_new(const uint64_t* __rest
                                                           const uint32_t* __restrict__ vis_d,
                                                           const uint32_t* __restrict__ vis_cnt, uint32_t vmax,
                                                           uint32_t use_lds_codes, uint64_t* __restrict__ edge_q,
-                                                          uint64_t* __restrict__ edge_pd) {
+                                                          uint64_t* __restrict__ edge_pd, PlainVecs pv) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
     const uint32_t b = blockIdx.x;
@@ -208,7 +293,7 @@ __global__ __launch_bounds__(WAVE) void k_build_prune_new(const uint64_t* __rest
         cd[j] = vis_d[(size_t)b * vmax + j];
     }
     __syncthreads();
-    if (use_lds_codes) {
+    if (!PLAIN && use_lds_codes) {
         stage_codes(ccode, codes, cid, C, stride, lane);
         __syncthreads();
     }
@@ -217,8 +302,11 @@ __global__ __launch_bounds__(WAVE) void k_build_prune_new(const uint64_t* __rest
         for (uint32_t t = lane; t < C; t += WAVE) sel[t] = t;
         nres = C;
         __syncthreads();
+    } else if constexpr (PLAIN) {
+        PlainPair pd{pv.vecs, pv.vdiv, cid, reinterpret_cast<float*>(ccode), pv.vec_stride, pv.dim, pv.distance_type};
+        nres = wave_prune(pd, cd, C, R, max_alpha, maxf, sel, lane);
     } else {
-        nres = wave_prune(cid, cd, C, use_lds_codes ? ccode : nullptr, codes, stride, R, max_alpha, maxf, sel, lane);
+        nres = wave_prune_ham(cid, cd, C, use_lds_codes ? ccode : nullptr, codes, stride, R, max_alpha, maxf, sel, lane);
     }
     uint32_t* row = nbrs + (size_t)p * nbr_stride;
     for (uint32_t t = lane; t < nbr_stride; t += WAVE) row[t] = t < nres ? cid[sel[t]] : VS_INVALID_NODE;
@@ -333,7 +421,7 @@ __global__ __launch_bounds__(WAVE) void k_build_prune_merge(const uint64_t* __re
         nres = T;
         __syncthreads();
     } else {
-        nres = wave_prune(cid, cd, T, use_lds_codes ? ccode : nullptr, codes, stride, R, max_alpha, maxf, sel, lane,
+        nres = wave_prune_ham(cid, cd, T, use_lds_codes ? ccode : nullptr, codes, stride, R, max_alpha, maxf, sel, lane,
                           label_off ? pm : nullptr);
     }
     for (uint32_t t = lane; t < nbr_stride; t += WAVE) row[t] = t < nres ? cid[sel[t]] : VS_INVALID_NODE;
@@ -350,6 +438,9 @@ __global__ __launch_bounds__(WAVE) void k_build_prune_merge(const uint64_t* __re
 }
 
 // ---- back-edges: one wave per target node q ---------------------------------------------------------------------
+// PLAIN: a request carries the forward key plain_key(d(p -> q)) (update_back_pointer reuses it), the target's existing
+// neighbours are scored d(q -> v) with q's prepared vector staged in LDS, eight of them per pass.
+template <bool PLAIN>
 __global__ __launch_bounds__(WAVE) void k_build_backedges(const uint64_t* __restrict__ codes, uint32_t stride,
                                                           uint32_t* __restrict__ nbrs, uint32_t nbr_stride, uint32_t R,
                                                           float max_alpha, const uint64_t* __restrict__ q_sorted,
@@ -357,7 +448,7 @@ __global__ __launch_bounds__(WAVE) void k_build_backedges(const uint64_t* __rest
                                                           const uint32_t* __restrict__ seg_start,
                                                           const uint32_t* __restrict__ nseg_p, uint32_t cmax,
                                                           uint32_t use_lds_codes, const uint32_t* __restrict__ label_off,
-                                                          const int16_t* __restrict__ label_val) {
+                                                          const int16_t* __restrict__ label_val, PlainVecs pv) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
     const uint32_t nseg = *nseg_p;
@@ -414,16 +505,27 @@ __global__ __launch_bounds__(WAVE) void k_build_backedges(const uint64_t* __rest
         uint32_t np2 = 1;
         while (np2 < T) np2 <<= 1;
         const uint64_t* cq = codes + (size_t)q * stride;
+        PlainPair ppd{pv.vecs, pv.vdiv, cid, reinterpret_cast<float*>(ccode), pv.vec_stride, pv.dim, pv.distance_type};
         for (uint32_t t = lane; t < np2; t += WAVE) {
             uint64_t key = ~0ull;
             if (t < deg) {
                 uint32_t id = row[t];
-                key = ((uint64_t)ham_words(codes + (size_t)id * stride, cq, stride) << 32) | id;
+                if (!PLAIN) key = ((uint64_t)ham_words(codes + (size_t)id * stride, cq, stride) << 32) | id;
             } else if (t < T) {
                 uint64_t pd = pd_sorted[e0 + (t - deg)];
                 if (!in_row((uint32_t)pd)) key = pd;  // (dist << 32) | p
             }
             keys[t] = key;
+        }
+        if constexpr (PLAIN) {
+            ppd.stage(q, lane);
+            for (uint32_t t0 = 0; t0 < deg; t0 += WAVE / 8) {
+                const uint32_t t = t0 + (uint32_t)lane / 8;
+                const bool act = t < deg;
+                const uint32_t id = act ? row[t] : 0u;
+                const float d = ppd.dist(id, act, lane);
+                if (act && (lane & 7) == 0) keys[t] = ((uint64_t)plain_key(d) << 32) | id;
+            }
         }
         __syncthreads();
         wave_bitonic_sort(keys, np2, lane);
@@ -435,7 +537,7 @@ __global__ __launch_bounds__(WAVE) void k_build_backedges(const uint64_t* __rest
             if (label_off) pm[t] = label_pmask(label_off, label_val, q, (uint32_t)keys[t]);  // add_neighbors(q, from_labels = q's)
         }
         __syncthreads();
-        if (use_lds_codes) {
+        if (!PLAIN && use_lds_codes) {
             stage_codes(ccode, codes, cid, Tv, stride, lane);
             __syncthreads();
         }
@@ -444,8 +546,10 @@ __global__ __launch_bounds__(WAVE) void k_build_backedges(const uint64_t* __rest
             for (uint32_t t = lane; t < Tv; t += WAVE) sel[t] = t;
             nres = Tv;
             __syncthreads();
+        } else if constexpr (PLAIN) {
+            nres = wave_prune(ppd, cd, Tv, R, max_alpha, maxf, sel, lane);
         } else {
-            nres = wave_prune(cid, cd, Tv, use_lds_codes ? ccode : nullptr, codes, stride, R, max_alpha, maxf, sel, lane,
+            nres = wave_prune_ham(cid, cd, Tv, use_lds_codes ? ccode : nullptr, codes, stride, R, max_alpha, maxf, sel, lane,
                               label_off ? pm : nullptr);
         }
         for (uint32_t t = lane; t < nbr_stride; t += WAVE) row[t] = t < nres ? cid[sel[t]] : VS_INVALID_NODE;
@@ -493,6 +597,23 @@ __global__ void k_count_reached_sources(const uint32_t* __restrict__ nbrs, uint3
 // only touches a row's list when one of its 64 candidates beats the list's last entry.  Rows are `stride` words (zero
 // padded), any W; rows past n read as absent.  c <= 64.
 #define MATES_KW 8
+// one row's sorted top-c list (LDS) takes in a tile's 64 keys, one per lane (~0: none): every entry ranks itself among the 128
+__device__ __forceinline__ void mates_merge(uint64_t* best_row /*LDS [c]*/, uint32_t c, uint64_t key, uint64_t* scratch /*LDS [128]*/, int lane) {
+    const uint64_t mine = (uint32_t)lane < c ? best_row[lane] : ~0ull;
+    scratch[lane] = mine;
+    scratch[64 + lane] = key;
+    __syncthreads();
+    uint32_t rk_m = 0, rk_k = 0;  // keys are distinct (a row number occurs once); absent entries rank nowhere
+    for (uint32_t t = 0; t < 128; ++t) {
+        const uint64_t o = scratch[t];
+        rk_m += o < mine;
+        rk_k += o < key;
+    }
+    __syncthreads();
+    if (mine != ~0ull && rk_m < c) best_row[rk_m] = mine;
+    if (key != ~0ull && rk_k < c) best_row[rk_k] = key;
+    __syncthreads();
+}
 // label_off != nullptr (the filtered pass of a labeled set): row r is node label_base + r, and only rows whose label sets overlap
 // are mates — what the label filter of the pass's search admits.
 __global__ __launch_bounds__(WAVE) void k_batch_mates(const uint64_t* __restrict__ codes, uint32_t stride, uint32_t n, uint32_t c,
@@ -549,20 +670,7 @@ __global__ __launch_bounds__(WAVE) void k_batch_mates(const uint64_t* __restrict
             const uint64_t last = best[r * c + c - 1];
             if (label_off && key < last && label_pmask(label_off, label_val, label_base + i0 + r, label_base + j) == 0) key = ~0ull;
             if (!__ballot(key < last)) continue;
-            const uint64_t mine = (uint32_t)lane < c ? best[r * c + lane] : ~0ull;
-            scratch[lane] = mine;
-            scratch[64 + lane] = key;
-            __syncthreads();
-            uint32_t rk_m = 0, rk_k = 0;  // keys are distinct (a row number occurs once); absent entries rank nowhere
-            for (uint32_t t = 0; t < 128; ++t) {
-                const uint64_t o = scratch[t];
-                rk_m += o < mine;
-                rk_k += o < key;
-            }
-            __syncthreads();
-            if (mine != ~0ull && rk_m < c) best[r * c + rk_m] = mine;
-            if (key != ~0ull && rk_k < c) best[r * c + rk_k] = key;
-            __syncthreads();
+            mates_merge(best + r * c, c, key, scratch, lane);
         }
         __syncthreads();
     }
@@ -575,6 +683,110 @@ __global__ __launch_bounds__(WAVE) void k_batch_mates(const uint64_t* __restrict
     }
 }
 static size_t mates_lds_bytes(uint32_t c) { return (size_t)(2 * 64 * (MATES_KW + 1) + 128 + 64 * c) * 8 + 64 * 65 * 4; }
+
+// k_batch_mates_plain: the same for rows first .. first + n - 1 of a plain index, by (plain_key(d(row -> other)), row).  The pair
+// distance has to come out of plain_dist8's accumulation order, so this is no tiled product: a wave owns MATESP_ROWS rows, stages
+// one of them at a time as the query side and walks all n rows eight per pass (8-lane groups, 16-byte loads); a tile of 64 keys
+// goes through LDS to the row's top-c list exactly as above.  out_key holds the keys (0xFFFFFFFF where there is no mate).
+#define MATESP_ROWS 16
+__global__ __launch_bounds__(WAVE) void k_batch_mates_plain(PlainVecs pv, uint32_t first, uint32_t n, uint32_t c,
+                                                            uint32_t* __restrict__ out_ids, uint32_t* __restrict__ out_key) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint64_t* scratch = reinterpret_cast<uint64_t*>(smem);            // [128]
+    uint64_t* best = scratch + 128;                                    // [MATESP_ROWS][c]
+    uint32_t* dist = reinterpret_cast<uint32_t*>(best + MATESP_ROWS * c);  // [64]
+    float* qv = reinterpret_cast<float*>(dist + 64);                   // [round_up(dim, 4)]
+    const int lane = threadIdx.x;
+    const uint32_t i0 = blockIdx.x * MATESP_ROWS;
+    if (i0 >= n) return;
+    for (uint32_t t = lane; t < MATESP_ROWS * c; t += WAVE) best[t] = ~0ull;
+    PlainPair pd{pv.vecs, pv.vdiv, nullptr, qv, pv.vec_stride, pv.dim, pv.distance_type};
+    for (uint32_t r = 0; r < MATESP_ROWS && i0 + r < n; ++r) {  // (uniform: the block is one wave)
+        pd.stage(first + i0 + r, lane);
+        for (uint32_t j0 = 0; j0 < n; j0 += 64) {
+            for (uint32_t p0 = 0; p0 < 64; p0 += WAVE / 8) {
+                const uint32_t jj = p0 + (uint32_t)lane / 8;
+                const bool act = j0 + jj < n;
+                const float d = pd.dist(act ? first + j0 + jj : 0u, act, lane);
+                if ((lane & 7) == 0) dist[jj] = act ? plain_key(d) : 0xFFFFFFFFu;
+            }
+            __syncthreads();
+            const uint32_t j = j0 + (uint32_t)lane;
+            const uint64_t key = (j < n && j != i0 + r) ? ((uint64_t)dist[lane] << 32) | j : ~0ull;
+            const uint64_t last = best[r * c + c - 1];
+            if (__ballot(key < last)) mates_merge(best + r * c, c, key, scratch, lane);
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    for (uint32_t t = lane; t < MATESP_ROWS * c; t += WAVE) {
+        const uint32_t r = t / c;
+        if (i0 + r >= n) continue;
+        const uint64_t k = best[t];
+        out_ids[(size_t)(i0 + r) * c + (t - r * c)] = k == ~0ull ? VS_INVALID_NODE : (uint32_t)k;
+        out_key[(size_t)(i0 + r) * c + (t - r * c)] = k == ~0ull ? 0xFFFFFFFFu : (uint32_t)(k >> 32);
+    }
+}
+static size_t mates_plain_lds_bytes(uint32_t c, uint32_t dim) { return (size_t)(128 + MATESP_ROWS * c) * 8 + 64 * 4 + (size_t)round_up_u32(dim, 4) * 4; }
+
+// k_prune_plain: what add_neighbors makes of a caller's candidate set for point p (vs_prune_plain): every id once, never p,
+// keyed plain_key(d(p -> id)), sorted by (key, id) — a repeated id repeats its key, so it sorts next to itself and is dropped
+// there — then all of them when they fit the list, else wave_prune.  One wave per point; cap (a power of two) bounds the set.
+__global__ __launch_bounds__(WAVE) void k_prune_plain(PlainVecs pv, uint32_t R, float max_alpha, const uint32_t* __restrict__ points,
+                                                      const uint32_t* __restrict__ cand_off, const uint32_t* __restrict__ cand_ids,
+                                                      uint32_t np, uint32_t cap, uint32_t* __restrict__ out_rows,
+                                                      uint32_t* __restrict__ out_len) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint64_t* keys = reinterpret_cast<uint64_t*>(smem);  // [cap]
+    uint32_t* cid = reinterpret_cast<uint32_t*>(keys + cap);
+    uint32_t* cd = cid + cap;
+    float* maxf = reinterpret_cast<float*>(cd + cap);
+    uint32_t* sel = reinterpret_cast<uint32_t*>(maxf + cap);
+    float* qv = reinterpret_cast<float*>(sel + round_up_u32(R, 4));
+    const int lane = threadIdx.x;
+    const uint32_t b = blockIdx.x;
+    if (b >= np) return;
+    const uint32_t p = points[b], c0 = cand_off[b], C0 = min(cand_off[b + 1] - c0, cap);
+    PlainPair pd{pv.vecs, pv.vdiv, cid, qv, pv.vec_stride, pv.dim, pv.distance_type};
+    for (uint32_t t = lane; t < cap; t += WAVE) keys[t] = ~0ull;
+    pd.stage(p, lane);
+    for (uint32_t t0 = 0; t0 < C0; t0 += WAVE / 8) {
+        const uint32_t t = t0 + (uint32_t)lane / 8;
+        const uint32_t id = t < C0 ? cand_ids[c0 + t] : p;
+        const bool act = id != p;  // "remove myself"
+        const float d = pd.dist(act ? id : 0u, act, lane);
+        if (act && (lane & 7) == 0) keys[t] = ((uint64_t)plain_key(d) << 32) | id;
+    }
+    __syncthreads();
+    wave_bitonic_sort(keys, cap, lane);
+    uint32_t T = 0;
+    for (uint32_t t0 = 0; t0 < cap; t0 += WAVE) {
+        const uint32_t t = t0 + (uint32_t)lane;
+        const uint64_t k = keys[t];
+        const bool ok = k != ~0ull && (t == 0 || keys[t - 1] != k);
+        const uint64_t okm = __ballot(ok);
+        if (ok) {
+            const uint32_t pos = T + (uint32_t)__popcll(okm & ((1ull << lane) - 1ull));
+            cid[pos] = (uint32_t)k;
+            cd[pos] = (uint32_t)(k >> 32);
+        }
+        T += (uint32_t)__popcll(okm);
+    }
+    __syncthreads();
+    uint32_t nres;
+    if (T <= R) {  // Graph::add_neighbors prunes only a candidate list longer than num_neighbors (AM/graph/mod.rs:243-256)
+        for (uint32_t t = lane; t < T; t += WAVE) sel[t] = t;
+        nres = T;
+        __syncthreads();
+    } else {
+        nres = wave_prune(pd, cd, T, R, max_alpha, maxf, sel, lane);
+    }
+    for (uint32_t t = lane; t < R; t += WAVE) out_rows[(size_t)b * R + t] = t < nres ? cid[sel[t]] : VS_INVALID_NODE;
+    if (lane == 0) out_len[b] = nres;
+}
+static size_t prune_plain_lds_bytes(uint32_t cap, uint32_t R, uint32_t dim) {
+    return (size_t)cap * 20 + (size_t)round_up_u32(R, 4) * 4 + (size_t)round_up_u32(dim, 4) * 4;
+}
 
 // k_insert_merge_mates: the mates of new node b0 + b (row numbers inside the batch, sorted by (Hamming, row)) join its sorted
 // candidate list (vis_ids / vis_d of the build-mode search, ascending by (distance, id)) before pruning: every id once, never the
@@ -681,6 +893,24 @@ __global__ __launch_bounds__(WAVE) void k_insert_anchor(const uint32_t* __restri
     }
 }
 
+// what the kernels need of a plain index to score pairs, or why this index cannot be scored
+static int plain_pair_args(vs_index* ix, const char* what, PlainVecs* pv) {
+    VS_REQUIRE(ix, "%s: index is NULL", what);
+    VS_REQUIRE(ix->d.storage_type == VS_STORAGE_PLAIN, "%s: plain storage indexes only", what);
+    VS_REQUIRE(ix->vecs && ix->vnorm, "%s: needs the vector column on the device", what);
+    // DistanceWithTieBreak::new asserts distance >= 0 (AM/graph/neighbor_with_distance.rs), which -dot violates: the reference has
+    // no build-time behaviour for the inner product on plain storage
+    VS_REQUIRE(ix->d.distance_type != VS_IP, "%s: plain storage has no build-time pair distance for the inner-product distance", what);
+    const bool truncated = ix->d.dim_index < ix->d.dim_full;
+    VS_REQUIRE(ix->d.distance_type != VS_COSINE || !truncated || ix->vnorm_idx, "%s: the index has no divisors for its index slices", what);
+    pv->vecs = ix->vecs;
+    pv->vdiv = ix->d.distance_type == VS_COSINE ? (truncated ? ix->vnorm_idx : ix->vnorm) : nullptr;
+    pv->vec_stride = ix->vec_stride;
+    pv->dim = ix->d.dim_index;
+    pv->distance_type = ix->d.distance_type;
+    return VS_OK;
+}
+
 struct BuildBufs {
     uint32_t *vis_ids = nullptr, *vis_d = nullptr, *vis_cnt = nullptr, *stats = nullptr, *status = nullptr;
     uint32_t* hash = nullptr;
@@ -711,6 +941,8 @@ struct BatchRunner {
     uint32_t R = 0, stride = 0, L = 0, batch_max = 0;
     float max_alpha = 1.0f;
     bool labeled = false;
+    bool plain = false;  // `plain` storage: full-precision pair distances (PlainPair), the general search kernel only
+    PlainVecs pv{nullptr, nullptr, 0, 0, 0};
     uint32_t vmax = 0, hl = 512, lh = 0, hcap = 0, hashcap = 0, cmax = 1, mcap = 0;
     uint32_t use_lds_new = 0, use_lds_back = 0, use_lds_merge = 0;
     size_t lds_new = 0, lds_back = 0, lds_merge = 0, hash_alloc = 0, ids_alloc = 0;
@@ -719,8 +951,10 @@ struct BatchRunner {
     uint32_t retries = 0;
     // insert only: mates per node (0: the nodes of a batch do not see each other, as in vs_build_graph) and HIP-event time of the
     // three insert kernels (ms[0] k_batch_mates, [1] k_insert_merge_mates, [2] k_insert_anchor)
+    // ms[3..5] (build and insert alike, while vs_profile_enable is on): the build-mode searches, the prune of the new nodes, the
+    // back-edges (sort, segment heads, k_build_backedges)
     uint32_t mates = 0;
-    double ms[3] = {0, 0, 0};
+    double ms[6] = {0, 0, 0, 0, 0, 0};
     hipEvent_t ev[2] = {nullptr, nullptr};
 
     // n: the nodes the graph will have when the last batch is in (sizes the default batch and picks the dedup regime)
@@ -734,6 +968,8 @@ struct BatchRunner {
         L = L_;
         max_alpha = max_alpha_;
         labeled = ix->label_off != nullptr;
+        plain = ix->d.storage_type == VS_STORAGE_PLAIN;
+        if (plain) VS_TRY(plain_pair_args(ix, "vs_build_graph", &pv));
         batch_max = batch_max_;
         if (batch_max == 0) batch_max = std::min<uint32_t>(65536, std::max<uint32_t>(1024, n / 64));
         // capacities of the build-mode search
@@ -749,9 +985,25 @@ struct BatchRunner {
         mcap = next_pow2_u32((uint64_t)vmax + R);  // candidates of k_build_prune_merge
         use_lds_merge = (mcap * code_bytes + mcap * 28 + R * 4 + 64 <= 150 * 1024) ? 1 : 0;
         lds_merge = (size_t)mcap * 28 + round_up_u32(R, 4) * 4 + (use_lds_merge ? mcap * code_bytes : 0) + 64;
-        VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_build_prune_new),
+        if (plain) {  // no code rows in LDS: the area behind sel[] holds one prepared vector
+            const size_t qv_bytes = (size_t)round_up_u32(pv.dim, 4) * 4;
+            use_lds_new = use_lds_back = 0;
+            lds_new = (size_t)vmax * 12 + round_up_u32(R, 4) * 4 + qv_bytes + 64;
+            lds_back = (size_t)cmax * 28 + round_up_u32(R, 4) * 4 + qv_bytes + 64;
+            VS_REQUIRE(lds_new <= 160 * 1024 && lds_back <= 160 * 1024, "vs_build_graph: %u dimensions do not fit the prune kernels' LDS", pv.dim);
+            VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_build_prune_new<true>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_build_backedges<true>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_batch_mates_plain),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            // the batch's own rows, prepared as queries, are what k_search<BUILD, PLAIN> reads from the workspace
+            VS_TRY(devbuf_reserve(c, ix->d.dim_index < ix->d.dim_full ? ix->ws.q_index : ix->ws.q_full,
+                                  (size_t)std::max<uint32_t>(batch_max, 1) * ix->vec_stride * 4));
+        }
+        VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_build_prune_new<false>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_build_backedges),
+        VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_build_backedges<false>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_build_prune_merge),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -776,7 +1028,8 @@ struct BatchRunner {
         // re-runs the scans that outgrow it.  Same operating-point rule as for queries: dedup table in LDS for small graphs,
         // table-less (global table, high occupancy) once a search inserts more ids than an LDS table should hold.
         use_fast = vs_opt_get("VS_BUILD_FAST") ? atoi(vs_opt_get("VS_BUILD_FAST")) != 0 : true;
-        {
+        if (plain) use_fast = false;  // (the LDS-resident kernel scores codes)
+        else {
             const uint64_t nbits = (uint64_t)ix->d.dim_index * ix->d.bits;
             const uint32_t typ_ins = (L + L / 4 + 16) * std::min<uint32_t>(R, 16);
             const bool lds_table = n <= 4000000u && typ_ins <= 3072;
@@ -823,6 +1076,10 @@ struct BatchRunner {
         // label keys of the searches = the new nodes' own label sets (CSR offsets are absolute into label_val)
         const int16_t* ql = filtered ? ix->label_val : nullptr;
         const uint32_t* qlo = filtered ? ix->label_off + b0 : nullptr;
+        if (plain) {  // the new rows as queries: their index slices, prepared as a scan's query is
+            DevBuf& qb = ix->d.dim_index < ix->d.dim_full ? ix->ws.q_index : ix->ws.q_full;
+            VS_TRY(launch_prepare_index_slice(ix, ix->vecs + (size_t)b0 * ix->vec_stride, bn, (float*)qb.p, ix->vec_stride));
+        }
         for (int attempt = 0;; ++attempt) {
             if ((size_t)bn * hashcap * 4 > hash_alloc || !B.hash) {
                 if (B.hash) VS_HIP(hipFree(B.hash));
@@ -857,6 +1114,7 @@ struct BatchRunner {
             s.out_cnt = B.vis_cnt;
             s.stats = B.stats;
             s.status = B.status;
+            tick();
             if (use_fast && attempt == 0) {
                 f.nq = bn;
                 f.hcap = std::max(std::min(hcap, f.hl + f.gstride - 2), f.hl);  // (the spill area was sized before the loop)
@@ -878,6 +1136,7 @@ struct BatchRunner {
             // after the fast kernel (or a failed attempt) only the scans whose status is non-zero are (re)run
             s.only_failed = (use_fast || attempt > 0) ? 1u : 0u;
             VS_TRY(launch_search(ix, s, true));
+            tock(3);
             std::vector<uint32_t> status(bn);
             VS_HIP(hipMemcpyAsync(status.data(), B.status, (size_t)bn * 4, hipMemcpyDeviceToHost, st));
             VS_HIP(hipStreamSynchronize(st));
@@ -903,9 +1162,13 @@ struct BatchRunner {
         if (with_mates && mates && bn > 1) {
             const uint32_t c = mates;
             tick();
-            hipLaunchKernelGGL(k_batch_mates, dim3((bn + 63) / 64), dim3(WAVE), mates_lds_bytes(c), st, ix->codes + (size_t)b0 * stride,
-                               stride, bn, c, B.mate_ids, B.mate_ham, filtered ? ix->label_off : nullptr,
-                               filtered ? ix->label_val : nullptr, b0);
+            if (plain)
+                hipLaunchKernelGGL(k_batch_mates_plain, dim3((bn + MATESP_ROWS - 1) / MATESP_ROWS), dim3(WAVE), mates_plain_lds_bytes(c, pv.dim), st,
+                                   pv, b0, bn, c, B.mate_ids, B.mate_ham);
+            else
+                hipLaunchKernelGGL(k_batch_mates, dim3((bn + 63) / 64), dim3(WAVE), mates_lds_bytes(c), st, ix->codes + (size_t)b0 * stride,
+                                   stride, bn, c, B.mate_ids, B.mate_ham, filtered ? ix->label_off : nullptr,
+                                   filtered ? ix->label_val : nullptr, b0);
             VS_HIP(hipGetLastError());
             tock(0);
             tick();
@@ -915,15 +1178,21 @@ struct BatchRunner {
             tock(1);
         }
         // out-edges of the new nodes + back-edge requests
+        tick();
         if (labeled)
             hipLaunchKernelGGL(k_build_prune_merge, dim3(bn), dim3(WAVE), lds_merge, st, ix->codes, stride, ix->nbrs,
                                ix->nbr_stride, R, max_alpha, b0, bn, B.vis_ids, B.vis_d, B.vis_cnt, vmax, mcap, use_lds_merge,
                                filtered ? 0u : 1u, ix->label_off, ix->label_val, B.edge_q, B.edge_pd);
+        else if (plain)
+            hipLaunchKernelGGL(k_build_prune_new<true>, dim3(bn), dim3(WAVE), lds_new, st, ix->codes, stride, ix->nbrs,
+                               ix->nbr_stride, R, max_alpha, b0, bn, B.vis_ids, B.vis_d, B.vis_cnt, vmax, 0u, B.edge_q, B.edge_pd, pv);
         else
-            hipLaunchKernelGGL(k_build_prune_new, dim3(bn), dim3(WAVE), lds_new, st, ix->codes, stride, ix->nbrs,
+            hipLaunchKernelGGL(k_build_prune_new<false>, dim3(bn), dim3(WAVE), lds_new, st, ix->codes, stride, ix->nbrs,
                                ix->nbr_stride, R, max_alpha, b0, bn, B.vis_ids, B.vis_d, B.vis_cnt, vmax, use_lds_new,
-                               B.edge_q, B.edge_pd);
+                               B.edge_q, B.edge_pd, pv);
         VS_HIP(hipGetLastError());
+        tock(4);
+        tick();
         const uint32_t ne = bn * R;
         size_t tmp_bytes = B.cub_bytes;
         VS_HIP(hipcub::DeviceRadixSort::SortPairs(B.cub_tmp, tmp_bytes, B.edge_q, B.edge_q_sorted, B.edge_pd,
@@ -932,10 +1201,16 @@ struct BatchRunner {
         hipLaunchKernelGGL(k_seg_heads, dim3((ne + 255) / 256), dim3(256), 0, st, B.edge_q_sorted, ne, B.seg_start, B.nseg);
         VS_HIP(hipGetLastError());
         uint32_t grid = std::min<uint32_t>(ne, 16384);
-        hipLaunchKernelGGL(k_build_backedges, dim3(grid), dim3(WAVE), lds_back, st, ix->codes, stride, ix->nbrs,
-                           ix->nbr_stride, R, max_alpha, B.edge_q_sorted, B.edge_pd_sorted, ne, B.seg_start, B.nseg, cmax,
-                           use_lds_back, labeled ? ix->label_off : nullptr, labeled ? ix->label_val : nullptr);
+        if (plain)
+            hipLaunchKernelGGL(k_build_backedges<true>, dim3(grid), dim3(WAVE), lds_back, st, ix->codes, stride, ix->nbrs,
+                               ix->nbr_stride, R, max_alpha, B.edge_q_sorted, B.edge_pd_sorted, ne, B.seg_start, B.nseg, cmax, 0u,
+                               (const uint32_t*)nullptr, (const int16_t*)nullptr, pv);
+        else
+            hipLaunchKernelGGL(k_build_backedges<false>, dim3(grid), dim3(WAVE), lds_back, st, ix->codes, stride, ix->nbrs,
+                               ix->nbr_stride, R, max_alpha, B.edge_q_sorted, B.edge_pd_sorted, ne, B.seg_start, B.nseg, cmax,
+                               use_lds_back, labeled ? ix->label_off : nullptr, labeled ? ix->label_val : nullptr, pv);
         VS_HIP(hipGetLastError());
+        tock(5);
         return VS_OK;
     }
 };
@@ -1077,12 +1352,12 @@ static int build_graph_impl(vs_index* ix, uint32_t L, double max_alpha_d, uint32
     vs_ctx* c = ix->ctx;
     hipStream_t st = c->stream;
     const uint32_t n = ix->d.n;
-    VS_HIP(hipMemsetAsync(ix->nbrs, 0xFF, (size_t)std::max(n, 1u) * ix->nbr_stride * 4, st));
+    // (every check and every allocation that can refuse the call comes before the first byte of nbrs is written)
     if (n == 0) {
+        VS_HIP(hipMemsetAsync(ix->nbrs, 0xFF, (size_t)ix->nbr_stride * 4, st));
         ix->d.default_start = VS_INVALID_NODE;
         return VS_OK;
     }
-    ix->d.default_start = 0;
     const bool labeled = ix->label_off != nullptr;
     if (labeled) {
         // update_start_nodes (AM/graph/mod.rs:490-531): a node is the start node of every label it is the first to carry;
@@ -1104,9 +1379,28 @@ static int build_graph_impl(vs_index* ix, uint32_t L, double max_alpha_d, uint32
         }
         VS_TRY(vs_index_set_start_nodes(ix, 0, sl.data(), sn.data(), (uint32_t)sl.size()));
     }
+    if (ix->d.storage_type == VS_STORAGE_PLAIN) {  // the divisors the pair distance divides by, from the rows as they stand
+        VS_TRY(launch_row_norms(ix));
+        VS_TRY(launch_slice_norms_range(ix, 0, n));
+    }
     BatchRunner br;
     VS_TRY(br.init(ix, B, L, (float)max_alpha_d, batch_max, n));
     batch_max = br.batch_max;
+    VS_HIP(hipMemsetAsync(ix->nbrs, 0xFF, (size_t)n * ix->nbr_stride * 4, st));
+    ix->d.default_start = 0;
+    struct Events {  // (vs_profile_enable: HIP-event time of the batch kernels, vs_index_build_kernel_ms)
+        BatchRunner& br;
+        vs_index* ix;
+        ~Events() {
+            for (int k = 0; k < 3; ++k) ix->build_ms[k] += br.ms[3 + k];
+            if (br.ev[0]) (void)hipEventDestroy(br.ev[0]);
+            if (br.ev[1]) (void)hipEventDestroy(br.ev[1]);
+        }
+    } events{br, ix};
+    if (c->profiling) {
+        VS_HIP(hipEventCreate(&br.ev[0]));
+        VS_HIP(hipEventCreate(&br.ev[1]));
+    }
 
     uint32_t b0 = 1;  // node 0 is the start node and has no one to link to yet
     uint32_t bsz = 1;
@@ -1129,6 +1423,16 @@ static int vs_build_graph_impl(vs_index* ix, uint32_t search_list_size, double m
     VS_REQUIRE(ix, "vs_build_graph: index is NULL");
     VS_REQUIRE(search_list_size >= 1 && search_list_size <= 1000, "vs_build_graph: search_list_size outside [1,1000]");
     VS_REQUIRE(max_alpha >= 1.0 && max_alpha <= 5.0, "vs_build_graph: max_alpha outside [1,5]");
+    VS_REQUIRE(ix->nbrs, "vs_build_graph: the index has no neighbor lists");
+    if (ix->d.storage_type == VS_STORAGE_PLAIN) {  // IndexFullDistanceMeasure: pair distances over the vector column
+        PlainVecs pv;
+        VS_TRY(plain_pair_args(ix, "vs_build_graph", &pv));
+        VS_REQUIRE(!ix->label_off, "vs_build_graph: Plain storage does not support label filters");
+        if (ix->ws.pending) {
+            vs_set_error("vs_build_graph: a batch of this handle is in flight (vs_search_batch_dev_finish first)");
+            return VS_ERR_STATE;
+        }
+    }
     VS_HIP(hipSetDevice(ix->ctx->device));
     BuildBufs B;
     ix->nbr_mask_valid = false;  // (the neighbor lists are about to change: what was derived from them is stale)
@@ -1231,6 +1535,99 @@ extern "C" int vs_batch_mates_filtered(vs_index* ix, const uint64_t* codes, cons
     });
 }
 
+// ---- vs_batch_mates_plain / vs_prune_plain: the two plain-storage build kernels on their own (read-only on the index) --------
+static int vs_batch_mates_plain_impl(vs_index* ix, uint32_t first_node, uint32_t n, uint32_t c, uint32_t* out_ids, float* out_dist) {
+    PlainVecs pv;
+    VS_TRY(plain_pair_args(ix, "vs_batch_mates_plain", &pv));
+    VS_REQUIRE(n == 0 || out_ids, "vs_batch_mates_plain: out_ids is NULL");
+    VS_REQUIRE(c >= 1 && c <= 64, "vs_batch_mates_plain: %u mates per row outside [1,64]", c);
+    VS_REQUIRE((uint64_t)first_node + n <= ix->d.n, "vs_batch_mates_plain: rows %u .. %llu are not all in the index (%u nodes)", first_node,
+               (unsigned long long)first_node + n, ix->d.n);
+    if (n == 0) return VS_OK;
+    vs_ctx* ctx = ix->ctx;
+    VS_HIP(hipSetDevice(ctx->device));
+    const size_t lds = mates_plain_lds_bytes(c, pv.dim);
+    VS_REQUIRE(lds <= 160 * 1024, "vs_batch_mates_plain: %u dimensions do not fit LDS", pv.dim);
+    VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_batch_mates_plain), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    uint32_t* d_out = nullptr;  // ids, then keys
+    VS_HIP(hipMalloc(&d_out, (size_t)n * c * 8));
+    int r = VS_OK;
+    hipLaunchKernelGGL(k_batch_mates_plain, dim3((n + MATESP_ROWS - 1) / MATESP_ROWS), dim3(WAVE), lds, ctx->stream, pv, first_node, n, c, d_out,
+                       d_out + (size_t)n * c);
+    if (hipGetLastError() != hipSuccess) {
+        vs_set_error("vs_batch_mates_plain: launch failed");
+        r = VS_ERR_HIP;
+    }
+    if (r == VS_OK) r = vs_dev_download(ctx, out_ids, d_out, (size_t)n * c * 4);
+    if (r == VS_OK && out_dist) {
+        r = vs_dev_download(ctx, out_dist, d_out + (size_t)n * c, (size_t)n * c * 4);
+        // keys -> the f32 distances, bit for bit (the total_cmp image undoes itself); the padding keeps 0xFFFFFFFF
+        uint32_t* k = reinterpret_cast<uint32_t*>(out_dist);
+        for (size_t i = 0; r == VS_OK && i < (size_t)n * c; ++i)
+            if (out_ids[i] != VS_INVALID_NODE) {
+                uint32_t b = k[i] ^ 0x80000000u;
+                b ^= (uint32_t)((int32_t)b >> 31) >> 1;
+                k[i] = b;
+            }
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d_out);
+    return r;
+}
+extern "C" int vs_batch_mates_plain(vs_index* ix, uint32_t first_node, uint32_t n, uint32_t c, uint32_t* out_ids, float* out_dist) {
+    return vs_guard("vs_batch_mates_plain", [&] { return vs_batch_mates_plain_impl(ix, first_node, n, c, out_ids, out_dist); });
+}
+
+static int vs_prune_plain_impl(vs_index* ix, const uint32_t* points, const uint32_t* cand_off, const uint32_t* cand_ids, uint32_t np,
+                               double max_alpha, uint32_t* out_rows, uint32_t* out_len) {
+    PlainVecs pv;
+    VS_TRY(plain_pair_args(ix, "vs_prune_plain", &pv));
+    VS_REQUIRE(np == 0 || (points && cand_off && out_rows && out_len), "vs_prune_plain: bad args");
+    VS_REQUIRE(max_alpha >= 1.0 && max_alpha <= 5.0, "vs_prune_plain: max_alpha outside [1,5]");
+    if (np == 0) return VS_OK;
+    VS_REQUIRE(cand_off[0] == 0, "vs_prune_plain: cand_off[0] must be 0");
+    uint32_t longest = 0;
+    for (uint32_t i = 0; i < np; ++i) {
+        VS_REQUIRE(points[i] < ix->d.n, "vs_prune_plain: point %u out of range", points[i]);
+        VS_REQUIRE(cand_off[i] <= cand_off[i + 1], "vs_prune_plain: cand_off must be non-decreasing");
+        longest = std::max(longest, cand_off[i + 1] - cand_off[i]);
+    }
+    const uint32_t total = cand_off[np];
+    VS_REQUIRE(total == 0 || cand_ids, "vs_prune_plain: cand_ids is NULL");
+    for (uint32_t i = 0; i < total; ++i) VS_REQUIRE(cand_ids[i] < ix->d.n, "vs_prune_plain: candidate id %u out of range", cand_ids[i]);
+    VS_REQUIRE(longest <= 4096, "vs_prune_plain: %u candidates for one point (at most 4096)", longest);
+    const uint32_t R = ix->d.num_neighbors, cap = std::max<uint32_t>(next_pow2_u32(longest), 64);
+    const size_t lds = prune_plain_lds_bytes(cap, R, pv.dim);
+    VS_REQUIRE(lds <= 160 * 1024, "vs_prune_plain: %u candidates of %u dimensions do not fit LDS", longest, pv.dim);
+    vs_ctx* ctx = ix->ctx;
+    VS_HIP(hipSetDevice(ctx->device));
+    VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_prune_plain), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    uint32_t* d_buf = nullptr;  // points | cand_off | cand_ids | out_len | out_rows
+    const size_t words = (size_t)np + (np + 1) + std::max<uint32_t>(total, 1) + np + (size_t)np * R;
+    VS_HIP(hipMalloc(&d_buf, words * 4));
+    uint32_t *d_points = d_buf, *d_off = d_points + np, *d_ids = d_off + np + 1, *d_len = d_ids + std::max<uint32_t>(total, 1), *d_rows = d_len + np;
+    int r = vs_dev_upload(ctx, d_points, points, (size_t)np * 4);
+    if (r == VS_OK) r = vs_dev_upload(ctx, d_off, cand_off, ((size_t)np + 1) * 4);
+    if (r == VS_OK && total) r = vs_dev_upload(ctx, d_ids, cand_ids, (size_t)total * 4);
+    if (r == VS_OK) {
+        hipLaunchKernelGGL(k_prune_plain, dim3(np), dim3(WAVE), lds, ctx->stream, pv, R, (float)max_alpha, d_points, d_off, d_ids, np, cap, d_rows,
+                           d_len);
+        if (hipGetLastError() != hipSuccess) {
+            vs_set_error("vs_prune_plain: launch failed");
+            r = VS_ERR_HIP;
+        }
+    }
+    if (r == VS_OK) r = vs_dev_download(ctx, out_len, d_len, (size_t)np * 4);
+    if (r == VS_OK) r = vs_dev_download(ctx, out_rows, d_rows, (size_t)np * R * 4);
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d_buf);
+    return r;
+}
+extern "C" int vs_prune_plain(vs_index* ix, const uint32_t* points, const uint32_t* cand_off, const uint32_t* cand_ids, uint32_t np,
+                              double max_alpha, uint32_t* out_rows, uint32_t* out_len) {
+    return vs_guard("vs_prune_plain", [&] { return vs_prune_plain_impl(ix, points, cand_off, cand_ids, np, max_alpha, out_rows, out_len); });
+}
+
 // ---- vs_index_insert: aminsert (AM/build.rs:464-558) for rows that arrive after the index is resident -----------------------
 // The anchoring rule over the new nodes r0 .. r0 + rn - 1 (k_insert_anchor to its fixed point), then, on the host and in node order
 // (placement is rare), a slot for every node that stayed unanchored in the list of its closest old-or-anchored out-neighbor: a free
@@ -1330,8 +1727,17 @@ static int index_insert_impl(vs_index* ix, const float* vectors, bool vectors_on
     if (out) memset(out, 0, sizeof(*out));
     VS_REQUIRE_OWNER(ix, what);
     VS_REQUIRE_NO_VIEWS(ix, what);
-    VS_REQUIRE(ix->d.storage_type == VS_STORAGE_SBQ, "%s: plain storage is not supported (memory_optimized indexes only)", what);
+    const bool plain = ix->d.storage_type == VS_STORAGE_PLAIN;
     VS_REQUIRE(ix->codes && ix->nbrs && ix->tids && ix->vecs, "%s: needs codes, neighbor lists, heap tids and the vector column on the device", what);
+    if (plain) {  // no quantizer, no labels; linked with full-precision pair distances
+        VS_REQUIRE(!label_off && !ix->label_off, "%s: Plain storage does not support label filters", what);
+        PlainVecs pv;
+        VS_TRY(plain_pair_args(ix, what, &pv));
+        // an uploaded plain index mirrors a relation that cannot be written back (vs_pages_out_open refuses plain storage): rows
+        // inserted here would exist on the device alone
+        VS_REQUIRE(!ix->uploaded, "%s: plain storage is not supported for an uploaded index (the page writer cannot write the rows back); "
+                   "plain indexes allocated on the device (vs_index_alloc) take rows", what);
+    }
     VS_REQUIRE(n_new == 0 || (vectors && heap_tids), "%s: vectors / heap_tids are NULL", what);
     VS_REQUIRE(L >= 1 && L <= 1000, "%s: search_list_size outside [1,1000]", what);
     VS_REQUIRE(max_alpha >= 1.0 && max_alpha <= 5.0, "%s: max_alpha outside [1,5]", what);
@@ -1354,7 +1760,7 @@ static int index_insert_impl(vs_index* ix, const float* vectors, bool vectors_on
         vs_set_error("%s: %s", what, msg);
         return VS_ERR_STATE;
     };
-    if (ix->count == 0) return state_error("the quantizer is untrained (vs_sbq_train / vs_index_set_quantizer first; an insert never trains)");
+    if (!plain && ix->count == 0) return state_error("the quantizer is untrained (vs_sbq_train / vs_index_set_quantizer first; an insert never trains)");
     if (ix->ws.pending) return state_error("a batch of this handle is in flight (vs_search_batch_dev_finish first)");
     if (ix->visible && ix->visible != ix->visible_own) {
         bool ours = false;
@@ -1407,7 +1813,8 @@ static int index_insert_impl(vs_index* ix, const float* vectors, bool vectors_on
         if (ix->snap[sn]) VS_HIP(hipMemsetAsync(ix->snap[sn] + n_old, 0, n_new, st));
     // norms and codes of the new rows only, with the quantizer as it stands (preprocess_cosine rule of vs_index_refresh_norms)
     VS_TRY(launch_row_norms_range(ix, n_old, n_new));
-    VS_TRY(vs_quantize_row_range(ix, n_old, n_new));
+    if (plain) VS_TRY(launch_slice_norms_range(ix, n_old, n_new));  // (nothing touches codes: the rows past n stay zero)
+    else VS_TRY(vs_quantize_row_range(ix, n_old, n_new));
     if (labeled) {
         std::vector<uint32_t> off(n_new);
         for (uint32_t i = 0; i < n_new; ++i) off[i] = (uint32_t)(old_vals + label_off[i + 1]);
@@ -1521,7 +1928,10 @@ static int index_insert_impl(vs_index* ix, const float* vectors, bool vectors_on
     if (br.ev[1]) (void)hipEventDestroy(br.ev[1]);
     B.free_all();
     if (r == VS_OK) r = vs_validate_graph(ix);
-    for (int k = 0; k < 3; ++k) ix->insert_ms[k] += br.ms[k];
+    for (int k = 0; k < 3; ++k) {
+        ix->insert_ms[k] += br.ms[k];
+        ix->build_ms[k] += br.ms[3 + k];
+    }
     if (out) *out = s;
     return r;
 }
@@ -1544,6 +1954,15 @@ extern "C" int vs_index_insert_kernel_ms(vs_index* ix, double* ms /*[3]*/, int r
     for (int k = 0; k < 3; ++k) {
         ms[k] = ix->insert_ms[k];
         if (reset) ix->insert_ms[k] = 0;
+    }
+    return VS_OK;
+}
+
+extern "C" int vs_index_build_kernel_ms(vs_index* ix, double* ms /*[3]*/, int reset) {
+    VS_REQUIRE(ix && ms, "vs_index_build_kernel_ms: bad args");
+    for (int k = 0; k < 3; ++k) {
+        ms[k] = ix->build_ms[k];
+        if (reset) ix->build_ms[k] = 0;
     }
     return VS_OK;
 }
@@ -1924,7 +2343,7 @@ __global__ __launch_bounds__(WAVE) void k_consolidate_rows(const uint64_t* __res
                 stage_codes(ccode, codes, cid, T, stride, lane);
                 __syncthreads();
             }
-            nres = wave_prune(cid, cd, T, use_lds_codes ? ccode : nullptr, codes, stride, R, max_alpha, maxf, sel, lane,
+            nres = wave_prune_ham(cid, cd, T, use_lds_codes ? ccode : nullptr, codes, stride, R, max_alpha, maxf, sel, lane,
                               label_off ? pm : nullptr);
         }
         uint32_t added = 0;  // entries of the new list the old one did not hold
@@ -2583,8 +3002,6 @@ extern "C" int vs_index_shrink_to_fit(vs_index* ix) {
 // still needs; a row serves one node per group and round, and the entry it gives up keeps another in-edge from a row that is
 // reached under everything the entry carries.
 // ---------------------------------------------------------------------------------------------------------------
-#include "vs_device.h"
-
 enum { LR_PLACED_FREE = 0, LR_PLACED_DROPPED, LR_PLACED_VICTIM, LR_BLOCKED, LR_CONTENDED, LR_ALREADY, LR_COUNT, LR_N = 8 };
 #define NEAR_WAVES 4   // waves per workgroup of k_nearest_masked
 #define NEAR_PASSES 4  // 16-row passes in flight per wave

@@ -190,6 +190,7 @@ struct FastSig {
 struct vs_index {
     vs_ctx* ctx = nullptr;
     bool is_view = false;  // vs_index_view: the device arrays belong to another handle
+    bool uploaded = false; // vs_index_upload staged it from host arrays (a relation's pages), vs_index_alloc did not
     vs_index* view_of = nullptr;  // ... that one (never dereferenced: the owner may be gone)
     uint64_t owner_id = 0;        // key of the owner in the registry of live views (unique per vs_index_alloc / replica, never reused)
     WsSlab* slab = nullptr;       // shared by an index and its views (reference counted)
@@ -206,6 +207,7 @@ struct vs_index {
     uint32_t* nbrs = nullptr;
     uint64_t* tids = nullptr;
     double insert_ms[3] = {0, 0, 0};   // HIP-event time of k_batch_mates / k_insert_merge_mates / k_insert_anchor (vs_profile_enable; vs_index_insert_kernel_ms)
+    double build_ms[3] = {0, 0, 0};    // HIP-event time of the batch machinery's searches / prune of new nodes / back-edges, vs_build_graph and vs_index_insert alike (vs_index_build_kernel_ms)
     double consolidate_ms[2] = {0, 0}; // HIP-event time of the flag pass / k_consolidate_rows (vs_profile_enable; vs_index_consolidate_kernel_ms)
     double compact_ms[2] = {0, 0};     // HIP-event time of the keep flags + maps / the row mover (vs_profile_enable; vs_index_compact_kernel_ms)
     double label_repair_ms[4] = {0, 0, 0, 0};  // HIP-event time of the reach sweeps / strong[] / k_nearest_masked / claim + apply (vs_index_label_repair_kernel_ms)
@@ -467,7 +469,9 @@ int launch_row_norms(vs_index* idx);
 int launch_row_norms_range(vs_index* idx, uint32_t row_begin, uint32_t rows);  // the same for rows [row_begin, row_begin + rows)
 int vs_quantize_row_range(vs_index* ix, uint32_t row_begin, uint32_t rows);     // vs_extra.hip: vs_sbq_quantize_corpus over a row range
 int launch_slice_norms(vs_index* idx, float* d_out);  // divisor of the first dim_index dims of every heap vector
-int launch_prepare_index_slice(vs_index* idx, const float* d_raw, uint32_t nq, float* d_q_index);
+// raw_stride: floats between two raw rows (0: dim_full, a caller's packed queries; vec_stride: rows of the index's own vector column)
+int launch_prepare_index_slice(vs_index* idx, const float* d_raw, uint32_t nq, float* d_q_index, uint32_t raw_stride = 0);
+int launch_slice_norms_range(vs_index* idx, uint32_t row_begin, uint32_t rows);  // vnorm_idx of rows [row_begin, row_begin + rows)
 int launch_validate_nbrs(vs_index* idx, uint32_t* d_flag);
 int launch_scan_topk(vs_index* idx, const uint64_t* d_qcodes, uint32_t nq, uint32_t k, uint32_t* d_out_ids,
                      uint32_t* d_out_ham, const int16_t* d_qlabels = nullptr, const uint32_t* d_qlabel_off = nullptr,

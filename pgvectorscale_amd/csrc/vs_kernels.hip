@@ -1100,11 +1100,13 @@ int launch_prepare_queries(vs_index* idx, const float* d_raw, uint32_t nq, float
     return VS_OK;
 }
 
-int launch_prepare_index_slice(vs_index* idx, const float* d_raw, uint32_t nq, float* d_q_index) {
+int launch_prepare_index_slice(vs_index* idx, const float* d_raw, uint32_t nq, float* d_q_index, uint32_t raw_stride) {
     if (nq == 0) return VS_OK;
     const vs_index_desc& d = idx->d;
     const size_t lds = (round_up_u32(d.dim_index, 4) + 4) * sizeof(float);
-    hipLaunchKernelGGL(k_prepare_index_slice, dim3(nq), dim3(WAVE), lds, idx->ctx->stream, d_raw, nq, d.dim_full, d.dim_index,
+    VS_REQUIRE(lds <= 64 * 1024, "index slice too large for LDS staging (%u dims)", d.dim_index);
+    // (the kernel only strides by its dim_full argument)
+    hipLaunchKernelGGL(k_prepare_index_slice, dim3(nq), dim3(WAVE), lds, idx->ctx->stream, d_raw, nq, raw_stride ? raw_stride : d.dim_full, d.dim_index,
                        idx->vec_stride, d.distance_type, d_q_index);
     VS_HIP(hipGetLastError());
     return VS_OK;
@@ -1309,6 +1311,15 @@ int launch_row_norms_range(vs_index* idx, uint32_t row_begin, uint32_t rows) {
     const uint32_t blocks = (rows + 63) / 64 > 8192 ? 8192 : (rows + 63) / 64;
     hipLaunchKernelGGL(k_row_norms, dim3(blocks), dim3(WAVE), 0, idx->ctx->stream, idx->vecs + (size_t)row_begin * idx->vec_stride,
                        idx->vec_stride, idx->d.dim_full, rows, idx->vnorm + row_begin);
+    VS_HIP(hipGetLastError());
+    return VS_OK;
+}
+
+int launch_slice_norms_range(vs_index* idx, uint32_t row_begin, uint32_t rows) {
+    if (!idx->vecs || !idx->vnorm_idx || rows == 0) return VS_OK;
+    const uint32_t blocks = (rows + 63) / 64 > 8192 ? 8192 : (rows + 63) / 64;
+    hipLaunchKernelGGL(k_row_norms, dim3(blocks), dim3(WAVE), 0, idx->ctx->stream, idx->vecs + (size_t)row_begin * idx->vec_stride,
+                       idx->vec_stride, idx->d.dim_index, rows, idx->vnorm_idx + row_begin);
     VS_HIP(hipGetLastError());
     return VS_OK;
 }

@@ -46,86 +46,6 @@ struct SearchArgs {
 
 #define MAX_QLABELS 64
 
-// monotone u32 image of f32::total_cmp (DistanceWithTieBreak compares distances with total_cmp,
-// AM/graph/neighbor_with_distance.rs:74-83): heap / visited keys of the plain-storage search
-__device__ __forceinline__ uint32_t plain_key(float f) {
-    int32_t b = __float_as_int(f);
-    b ^= (int32_t)(((uint32_t)(b >> 31)) >> 1);
-    return (uint32_t)b ^ 0x80000000u;
-}
-
-// PlainDistanceMeasure::calculate_distance (AM/plain/storage.rs:239-247,273-281): distance_fn(query index slice, node
-// vector) for the row each 8-lane group points at, in the reference's AVX2 accumulation order — the same arithmetic as
-// k_rerank (vs_kernels.hip): lane l8 owns elements 32t + 4 l8 .. +3, i.e. 4 of the 32 virtual AVX2 lanes; L2 is mul + add,
-// dot is FMA; horizontal_add_ps per accumulator, the four accumulators summed left to right, then the scalar tail.  The
-// stored vector is the cosine-normalised insert-time vector: the raw row divided by its cached norm.  Valid on l8 == 0.
-__device__ __forceinline__ float plain_dist8(const float* __restrict__ row, float sdiv, const float* qv, uint32_t dim,
-                                             uint32_t distance_type, int lane, bool valid) {
-    const int l8 = lane & 7;
-    const uint32_t steps = dim / 32;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    if (valid) {
-        if (distance_type == VS_L2) {
-            for (uint32_t t = 0; t < steps; ++t) {
-                const float4 x = *reinterpret_cast<const float4*>(row + 32 * t + 4 * l8);
-                const float4 y = *reinterpret_cast<const float4*>(qv + 32 * t + 4 * l8);
-                const float d0 = x.x - y.x, d1 = x.y - y.y, d2 = x.z - y.z, d3 = x.w - y.w;
-                const float p0 = d0 * d0, p1 = d1 * d1, p2 = d2 * d2, p3 = d3 * d3;
-                a0 = a0 + p0;
-                a1 = a1 + p1;
-                a2 = a2 + p2;
-                a3 = a3 + p3;
-            }
-        } else {
-            for (uint32_t t = 0; t < steps; ++t) {
-                float4 x = *reinterpret_cast<const float4*>(row + 32 * t + 4 * l8);
-                const float4 y = *reinterpret_cast<const float4*>(qv + 32 * t + 4 * l8);
-                if (sdiv != 0.0f) {
-                    x.x = x.x / sdiv;
-                    x.y = x.y / sdiv;
-                    x.z = x.z / sdiv;
-                    x.w = x.w / sdiv;
-                }
-                a0 = __builtin_fmaf(x.x, y.x, a0);
-                a1 = __builtin_fmaf(x.y, y.y, a1);
-                a2 = __builtin_fmaf(x.z, y.z, a2);
-                a3 = __builtin_fmaf(x.w, y.w, a3);
-            }
-        }
-    }
-    const float s0 = a0 + __shfl(a0, lane ^ 1, WAVE);
-    const float s1 = a1 + __shfl(a1, lane ^ 1, WAVE);
-    const float s2 = a2 + __shfl(a2, lane ^ 1, WAVE);
-    const float s3 = a3 + __shfl(a3, lane ^ 1, WAVE);
-    const float t0 = s0 + s1;
-    const float t1 = s2 + s3;
-    const float h = t0 + t1;
-    const int g0 = lane & ~7;
-    const float h0 = __shfl(h, g0 + 0, WAVE), h1 = __shfl(h, g0 + 2, WAVE), h2 = __shfl(h, g0 + 4, WAVE), h3 = __shfl(h, g0 + 6, WAVE);
-    float dist = h0 + h1;
-    dist = dist + h2;
-    dist = dist + h3;
-    float r = 0.0f;
-    if (valid && l8 == 0) {
-        for (uint32_t i = steps * 32; i < dim; ++i) {  // scalar tail, in element order
-            float x = row[i];
-            if (distance_type == VS_L2) {
-                const float diff = x - qv[i];
-                const float p = diff * diff;
-                dist = dist + p;
-            } else {
-                if (sdiv != 0.0f) x = x / sdiv;
-                const float p = x * qv[i];
-                dist = dist + p;
-            }
-        }
-        if (distance_type == VS_L2) r = dist;
-        else if (distance_type == VS_IP) r = -dist;
-        else r = fmaxf(1.0f - dist, 0.0f);
-    }
-    return r;
-}
-
 __device__ __forceinline__ uint64_t rfl64(uint64_t v) {
     uint32_t lo = rfl((uint32_t)v), hi = rfl((uint32_t)(v >> 32));
     return ((uint64_t)hi << 32) | lo;
@@ -680,8 +600,9 @@ int launch_search(vs_index* idx, const SearchLaunch& s, bool build_mode) {
     a.vec_stride = idx->vec_stride;
     a.dim = idx->d.dim_index;
     a.distance_type = idx->d.distance_type;
-    VS_REQUIRE(!plain || (!build_mode && idx->vecs && a.q_full && !s.qlabel_off),
+    VS_REQUIRE(!plain || (idx->vecs && a.q_full && !s.qlabel_off),
                "plain storage search needs the vector column and takes no label keys (AM/plain/storage.rs:262)");
+    VS_REQUIRE(!plain || a.distance_type != VS_COSINE || a.vnorm, "plain storage search: the cosine divisors of the index slices are missing");
     a.s = s;
     size_t lds = search_lds_bytes(idx, s);
     if (lds > 160 * 1024) {
@@ -701,9 +622,12 @@ int launch_search(vs_index* idx, const SearchLaunch& s, bool build_mode) {
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_search<false, true>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_search<true, true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set.done(attr_dev);
     }
-    if (plain) hipLaunchKernelGGL((k_search<false, true>), dim3(s.nq), dim3(WAVE), lds, idx->ctx->stream, a);
+    if (plain && build_mode) hipLaunchKernelGGL((k_search<true, true>), dim3(s.nq), dim3(WAVE), lds, idx->ctx->stream, a);
+    else if (plain) hipLaunchKernelGGL((k_search<false, true>), dim3(s.nq), dim3(WAVE), lds, idx->ctx->stream, a);
     else if (build_mode) hipLaunchKernelGGL((k_search<true, false>), dim3(s.nq), dim3(WAVE), lds, idx->ctx->stream, a);
     else hipLaunchKernelGGL((k_search<false, false>), dim3(s.nq), dim3(WAVE), lds, idx->ctx->stream, a);
     VS_HIP(hipGetLastError());

@@ -207,14 +207,18 @@ class DiskAnnIndex:
 
     @classmethod
     def alloc(cls, ctx, *, n, dim_full, dim_index=None, bits=None, num_neighbors=DEFAULT_NUM_NEIGHBORS,
-              distance_type=VS_L2, with_vecs=True):
+              distance_type=VS_L2, with_vecs=True, storage_type=_lib.VS_STORAGE_SBQ):
+        """an index of n rows with an empty graph (vs_index_alloc).  storage_type=VS_STORAGE_PLAIN: a `plain` index, built and grown
+        on its vectors (build_graph / insert score with full-precision distances); it needs with_vecs and carries no labels"""
         dim_index = dim_index or dim_full
+        if storage_type == _lib.VS_STORAGE_PLAIN:
+            bits = bits or 1  # (no SBQ code: the geometry of _upload_plain)
         bits = bits or default_bits(dim_index)
         d = IndexDesc()
         d.n, d.dim_full, d.dim_index, d.bits = n, dim_full, dim_index, bits
         d.words = quantized_size(dim_index, bits)
         d.num_neighbors, d.distance_type, d.has_labels = num_neighbors, distance_type, 0
-        d.default_start, d.n_label_starts = VS_INVALID_NODE, 0
+        d.default_start, d.n_label_starts, d.storage_type = VS_INVALID_NODE, 0, storage_type
         out = C.c_void_p()
         check(ctx._L.vs_index_alloc(ctx.h, C.byref(d), int(with_vecs), C.byref(out)))
         return cls(ctx, out)
@@ -407,6 +411,13 @@ class DiskAnnIndex:
         check(self._L.vs_index_insert_kernel_ms(self.h, ms, int(reset)))
         return {"batch_mates": float(ms[0]), "merge_mates": float(ms[1]), "anchor": float(ms[2])}
 
+    def build_kernel_ms(self, reset=True):
+        """HIP-event milliseconds of the batch machinery build_graph and insert share since the last reset (Context.profile_enable
+        first): the build-mode searches, the prune of the new nodes, the back-edges"""
+        ms = (C.c_double * 3)()
+        check(self._L.vs_index_build_kernel_ms(self.h, ms, int(reset)))
+        return {"search": float(ms[0]), "prune": float(ms[1]), "back_edges": float(ms[2])}
+
     def batch_mates(self, codes, c=16, labels=None):
         """for every row of codes [n][words] the c nearest other rows by (Hamming, row): (ids, hamming), VS_INVALID_NODE padded.
         labels (one sorted label list per row): only rows whose label sets overlap are mates (vs_batch_mates_filtered)"""
@@ -419,6 +430,28 @@ class DiskAnnIndex:
         lv, lo = self._label_keys(labels, codes.shape[0])
         check(self._L.vs_batch_mates_filtered(self.h, _p(codes), _p(lo), _p(lv), codes.shape[0], c, _p(ids), _p(ham)))
         return ids, ham
+
+    def batch_mates_plain(self, first_node, n, c=16):
+        """the plain-storage mates kernel on its own (vs_batch_mates_plain): for rows first_node .. first_node + n - 1 of a plain
+        index the c nearest other rows of that range by (d(row -> other), row), ties to the lower row -> (ids uint32 [n][c] as row
+        numbers inside the range, dist float32 [n][c]); VS_INVALID_NODE / bits 0xFFFFFFFF where there is no mate"""
+        ids = np.empty((n, c), np.uint32)
+        dist = np.empty((n, c), np.float32)
+        check(self._L.vs_batch_mates_plain(self.h, first_node, n, c, _p(ids), _p(dist)))
+        return ids, dist
+
+    def prune_plain(self, points, cand_lists, max_alpha=1.2):
+        """the plain-storage prune on its own (vs_prune_plain): for each point what add_neighbors makes of its candidate list (any
+        ids of the index; the point itself and repeats are dropped) -> (rows uint32 [len(points)][num_neighbors], VS_INVALID_NODE
+        padded, lengths uint32 [len(points)])"""
+        pts = np.ascontiguousarray(points, np.uint32)
+        if len(cand_lists) != pts.size:
+            raise ValueError("one candidate list per point")
+        ids, off = self._csr(cand_lists)
+        rows = np.empty((pts.size, self.desc.num_neighbors), np.uint32)
+        lens = np.empty(pts.size, np.uint32)
+        check(self._L.vs_prune_plain(self.h, _p(pts), _p(off), _p(ids), pts.size, max_alpha, _p(rows), _p(lens)))
+        return rows, lens
 
     def repair(self):
         """the repair pass of build_graph on its own (vs_index_repair) -> nodes still unreachable from the default start node"""
