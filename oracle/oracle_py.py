@@ -111,6 +111,9 @@ def lib():
     L.vso_heap_replay.argtypes = [vp, sz, vp]
     L.vso_build_graph.restype = None
     L.vso_build_graph.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, vp, u32p]
+    L.vso_search_for_build.restype = sz
+    L.vso_search_for_build.argtypes = [C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, C.c_uint32,
+                                       vp, vp, sz]
     L.vso_build_graph_labeled.restype = C.c_uint32
     L.vso_build_graph_labeled.argtypes = [C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, vp,
                                           u32p, vp, vp]
@@ -366,6 +369,26 @@ def build_graph(codes, num_neighbors=50, nbr_stride=None, search_list_size=100, 
     start = C.c_uint32()
     lib().vso_build_graph(n, w, _p(codes), num_neighbors, stride, search_list_size, max_alpha, _p(nbrs), C.byref(start))
     return nbrs, int(start.value)
+
+
+def search_for_build(codes, nbrs, num_neighbors, starts, qcode, search_list_size, label_off=None, label_val=None, qlabels=None):
+    """the sequential builder's own build search (what build_graph / build_graph_labeled run per node) over the given arrays, from
+    `starts` with query code `qcode`; label_off / label_val / qlabels: the filtered form -> (ids, hamming) in visit order"""
+    codes = np.ascontiguousarray(codes, np.uint64)
+    nbrs = np.ascontiguousarray(nbrs, np.uint32)
+    st = np.ascontiguousarray(starts, np.uint32).reshape(-1)
+    qc = np.ascontiguousarray(qcode, np.uint64)
+    lo = None if label_off is None else np.ascontiguousarray(label_off, np.uint32)
+    lv = None if label_off is None else np.ascontiguousarray(label_val, np.int16)
+    ql = None if label_off is None else np.ascontiguousarray(qlabels, np.int16)
+    cap = 4 * search_list_size + 256
+    while True:
+        ids, ham = np.empty(cap, np.uint32), np.empty(cap, np.uint32)
+        k = lib().vso_search_for_build(codes.shape[1], _p(codes), _p(nbrs), nbrs.shape[1], num_neighbors, _p(st), st.size, _p(lo), _p(lv),
+                                       _p(ql), 0 if ql is None else ql.size, _p(qc), search_list_size, _p(ids), _p(ham), cap)
+        if k <= cap:
+            return ids[:k], ham[:k]
+        cap = k
 
 
 def heap_replay(ops):

@@ -897,6 +897,42 @@ struct Cand {
 };
 inline bool cand_lt(const Cand& a, const Cand& b) { return a.d != b.d ? a.d < b.d : a.id < b.id; }
 
+/* greedy_search_for_build: all visited nodes in visit order, stop rule identical to visit_closest */
+/* filter: visit_lsn_internal's label test with the key (ql, nql) as the query (insert_internal with no_filter = false,
+ * AM/graph/mod.rs:664-672).  The one build search of this file: Builder::search and vso_search_for_build both call it. */
+std::vector<Cand> build_search(const uint64_t* codes, uint32_t w, const uint32_t* nbrs, uint32_t stride, uint32_t R, uint32_t L,
+                               const uint32_t* loff, const int16_t* lval, const uint64_t* qcode, const int16_t* ql, size_t nql,
+                               const uint32_t* starts, size_t n_starts, bool filter) {
+    auto ham = [&](uint32_t v) { return (uint32_t)vso_distance_xor(qcode, codes + (size_t)v * w, w); };
+    RustBinaryHeap<LSN, ReverseLsnLe> cand;
+    std::vector<LSN> visited;
+    U32Set inserted((size_t)L * R);
+    std::vector<Cand> out;
+    for (size_t t = 0; t < n_starts; ++t) {
+        if (!inserted.insert(starts[t])) continue;
+        cand.push(LSN{starts[t], (float)ham(starts[t])});
+    }
+    while (!cand.empty()) {
+        if (visited.size() > L && lsn_cmp(cand.peek(), visited[L - 1]) >= 0) break;
+        LSN head = cand.pop();
+        size_t lo = 0, hi = visited.size();
+        while (lo < hi) {
+            size_t mid = (lo + hi) / 2;
+            if (lsn_cmp(visited[mid], head) < 0) lo = mid + 1;
+            else hi = mid;
+        }
+        visited.insert(visited.begin() + (ptrdiff_t)lo, head);
+        out.push_back(Cand{head.id, (uint32_t)head.dist});
+        const uint32_t* r = nbrs + (size_t)head.id * stride;
+        for (uint32_t s = 0; s < R && r[s] != VSO_INVALID_NODE; ++s) {
+            if (!inserted.insert(r[s])) continue; /* marked before the label test (AM/sbq/storage.rs:148-172) */
+            if (filter && !vso_labels_overlap(ql, nql, lval + loff[r[s]], loff[r[s] + 1] - loff[r[s]])) continue;
+            cand.push(LSN{r[s], (float)ham(r[s])});
+        }
+    }
+    return out;
+}
+
 struct Builder {
     uint32_t n, w, R, stride, L;
     double max_alpha;
@@ -950,37 +986,10 @@ struct Builder {
         }
         return results;
     }
-    /* greedy_search_for_build: all visited nodes, stop rule identical to visit_closest */
-    /* filter: visit_lsn_internal's label test with the new node's own labels as the query (insert_internal with
-     * no_filter = false, AM/graph/mod.rs:664-672) */
+    /* greedy_search_for_build with node q's own code and label set as the query (build_search above) */
     std::vector<Cand> search(uint32_t q, const std::vector<uint32_t>& starts, bool filter) {
-        RustBinaryHeap<LSN, ReverseLsnLe> cand;
-        std::vector<LSN> visited;
-        U32Set inserted(L * R);
-        std::vector<Cand> out;
-        for (uint32_t start : starts) {
-            if (!inserted.insert(start)) continue;
-            cand.push(LSN{start, (float)ham(q, start)});
-        }
-        while (!cand.empty()) {
-            if (visited.size() > L && lsn_cmp(cand.peek(), visited[L - 1]) >= 0) break;
-            LSN head = cand.pop();
-            size_t lo = 0, hi = visited.size();
-            while (lo < hi) {
-                size_t mid = (lo + hi) / 2;
-                if (lsn_cmp(visited[mid], head) < 0) lo = mid + 1;
-                else hi = mid;
-            }
-            visited.insert(visited.begin() + (ptrdiff_t)lo, head);
-            out.push_back(Cand{head.id, (uint32_t)head.dist});
-            const uint32_t* r = nbrs + (size_t)head.id * stride;
-            for (uint32_t s = 0; s < R && r[s] != VSO_INVALID_NODE; ++s) {
-                if (!inserted.insert(r[s])) continue; /* marked before the label test (AM/sbq/storage.rs:148-172) */
-                if (filter && !vso_labels_overlap(lab(q), nlab(q), lab(r[s]), nlab(r[s]))) continue;
-                cand.push(LSN{r[s], (float)ham(q, r[s])});
-            }
-        }
-        return out;
+        return build_search(codes, w, nbrs, stride, R, L, loff, lval, code(q), filter ? lab(q) : nullptr, filter ? nlab(q) : 0,
+                            starts.data(), starts.size(), filter);
     }
     /* add_neighbors(neighbors_of, additional) */
     std::vector<Cand> add_neighbors(uint32_t of, const std::vector<Cand>& additional) {
@@ -1042,6 +1051,24 @@ size_t vso_heap_replay(const uint32_t* ops, size_t n_ops, uint32_t* out_ids) {
     }
     while (!h.empty()) out_ids[k++] = h.pop().id;
     return k;
+}
+
+/* The sequential builder's own build search (build_search, what vso_build_graph and vso_build_graph_labeled run for every node)
+ * over caller-held arrays: from `starts`, with query code `qcode` and list size L; label_off != NULL: only neighbors whose label
+ * set overlaps the key (qlabels, n_qlabels) are pushed.  Writes the visited nodes in visit order (ids and Hamming distances, room
+ * for out_cap entries) and returns how many the search visited (more than out_cap: the rest were not written). */
+size_t vso_search_for_build(uint32_t words, const uint64_t* codes, const uint32_t* nbrs, uint32_t nbr_stride, uint32_t num_neighbors,
+                            const uint32_t* starts, uint32_t n_starts, const uint32_t* label_off, const int16_t* label_val,
+                            const int16_t* qlabels, uint32_t n_qlabels, const uint64_t* qcode, uint32_t search_list_size,
+                            uint32_t* out_ids, uint32_t* out_ham, size_t out_cap) {
+    const bool filter = label_off != nullptr;
+    std::vector<Cand> v = build_search(codes, words, nbrs, nbr_stride, num_neighbors, search_list_size, label_off, label_val, qcode,
+                                       qlabels, n_qlabels, starts, n_starts, filter);
+    for (size_t i = 0; i < v.size() && i < out_cap; ++i) {
+        out_ids[i] = v[i].id;
+        out_ham[i] = v[i].d;
+    }
+    return v.size();
 }
 
 void vso_build_graph(uint32_t n, uint32_t words, const uint64_t* codes, uint32_t num_neighbors, uint32_t nbr_stride,

@@ -148,6 +148,12 @@ uint32_t vso_build_graph_labeled(uint32_t n, uint32_t words, const uint64_t* cod
                                  const int16_t* label_val, uint32_t num_neighbors, uint32_t nbr_stride,
                                  uint32_t search_list_size, double max_alpha, uint32_t* nbrs, uint32_t* default_start,
                                  int16_t* start_labels, uint32_t* start_nodes);
+/* the build search of the two builders above over caller-held arrays (they call the same function): visited nodes in visit order;
+ * label_off != NULL filters on the key (qlabels, n_qlabels); returns the number visited, of which the first out_cap are written */
+size_t vso_search_for_build(uint32_t words, const uint64_t* codes, const uint32_t* nbrs, uint32_t nbr_stride, uint32_t num_neighbors,
+                            const uint32_t* starts, uint32_t n_starts, const uint32_t* label_off, const int16_t* label_val,
+                            const int16_t* qlabels, uint32_t n_qlabels, const uint64_t* qcode, uint32_t search_list_size,
+                            uint32_t* out_ids, uint32_t* out_ham, size_t out_cap);
 /* exact f32 brute-force top-k by the reference distance function (ground truth for recall) */
 void vso_bruteforce_topk(const vso_index* idx, const float* queries, uint32_t nq, uint32_t k, uint32_t n_threads,
                          uint32_t* out_nodes, float* out_dist);

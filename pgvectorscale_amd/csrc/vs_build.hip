@@ -169,8 +169,9 @@ struct PlainPair {
     }
 };
 
-// prune_neighbors for one node by one wave.  cand_id/cand_d: C candidates sorted ascending by (distance, id) (LDS); pd: the pair
-// distance (above).  Writes up to R selected candidate *positions* into sel[] (LDS) and returns their number.
+// prune_neighbors for one node by one wave.  cand_id/cand_d: C candidates sorted ascending by distance (LDS) — candidates.sort() of
+// prune_neighbors is stable on the distance alone, the order among equal distances is the caller's: (distance, id) everywhere but
+// in k_build_prune_new, which takes the visited list as the search left it; pd: the pair distance (above).  Writes up to R selected candidate *positions* into sel[] (LDS) and returns their number.
 template <class P>
 __device__ uint32_t wave_prune(P& pd, const uint32_t* cand_d, uint32_t C, uint32_t R, float max_alpha, float* maxf /*LDS [C]*/,
                                uint32_t* sel /*LDS [R]*/, int lane,
@@ -265,7 +266,10 @@ __device__ uint32_t wave_prune_ham(const uint32_t* cand_id, const uint32_t* cand
 }
 
 // ---- out-edges of the new nodes of one batch ------------------------------------------------------------------
-// one wave per new node p = b0 + blockIdx.x.  Input: its visited list (sorted) from k_search<BUILD>.
+// one wave per new node p = b0 + blockIdx.x.  Input: its visited list from the build-mode search (either kernel), in the order of
+// ListSearchResult's visited vector — ascending distance, of equal distances the node visited later first
+// (visited.insert(partition_point(|x| x < head), head), AM/graph/mod.rs:167-168) — with the mates of an insert merged in; it is pruned in
+// that order.
 // PLAIN: the candidates' keys are plain_key(d(p -> candidate)) and pruning scores with PlainPair; the area behind sel[] holds the
 // selected candidate's prepared vector instead of code rows.
 template <bool PLAIN>
@@ -788,10 +792,14 @@ static size_t prune_plain_lds_bytes(uint32_t cap, uint32_t R, uint32_t dim) {
     return (size_t)cap * 20 + (size_t)round_up_u32(R, 4) * 4 + (size_t)round_up_u32(dim, 4) * 4;
 }
 
-// k_insert_merge_mates: the mates of new node b0 + b (row numbers inside the batch, sorted by (Hamming, row)) join its sorted
-// candidate list (vis_ids / vis_d of the build-mode search, ascending by (distance, id)) before pruning: every id once, never the
-// node itself, the closest vmax kept.  One wave per node; both lists are staged in LDS and every entry computes its own place in
-// the merged order (its index + the entries of the other list that sort before it).
+// k_insert_merge_mates: the mates of new node b0 + b (row numbers inside the batch, sorted by (Hamming, row)) join its candidate
+// list (vis_ids / vis_d of the build-mode search: ascending by distance, of equal distances the node visited later first) before
+// pruning: every id once, never the node itself, the first vmax kept.  The merge is the stable one on the distance alone, an entry
+// of the visited list before a mate at the same distance.  (Places used to come from whole (distance, id) keys.  That is the same
+// merge while every visited id is below every mate's — always, unless the second pass of a labeled set visits rows of its own
+// batch — but the list is not ordered by id among equal distances, so such keys are not monotone along it in general.)  One
+// wave per node; both lists are staged in LDS and every entry computes its own place in the merged order (its index + the
+// entries of the other list that come before it).
 __global__ __launch_bounds__(WAVE) void k_insert_merge_mates(uint32_t b0, uint32_t bn, uint32_t* __restrict__ vis_ids,
                                                              uint32_t* __restrict__ vis_d, uint32_t* __restrict__ vis_cnt, uint32_t vmax,
                                                              const uint32_t* __restrict__ mate_ids, const uint32_t* __restrict__ mate_ham,
@@ -826,7 +834,7 @@ __global__ __launch_bounds__(WAVE) void k_insert_merge_mates(uint32_t b0, uint32
     for (uint32_t t = lane; t < C0; t += WAVE) {
         const uint64_t k = vk[t];
         uint32_t before = 0;
-        for (uint32_t u = 0; u < nm; ++u) before += mk[u] < k;
+        for (uint32_t u = 0; u < nm; ++u) before += (uint32_t)(mk[u] >> 32) < (uint32_t)(k >> 32);  // mates strictly closer
         const uint32_t pos = t + before;
         if (pos < T) {
             vis_ids[(size_t)b * vmax + pos] = (uint32_t)k;
@@ -835,10 +843,10 @@ __global__ __launch_bounds__(WAVE) void k_insert_merge_mates(uint32_t b0, uint32
     }
     if ((uint32_t)lane < nm) {
         const uint64_t k = mk[lane];
-        uint32_t lo = 0, hi = C0;  // entries of the sorted list that sort before k
+        uint32_t lo = 0, hi = C0;  // entries of the visited list at most as far as k
         while (lo < hi) {
             const uint32_t mid = (lo + hi) >> 1;
-            if (vk[mid] < k) lo = mid + 1;
+            if ((uint32_t)(vk[mid] >> 32) <= (uint32_t)(k >> 32)) lo = mid + 1;
             else hi = mid;
         }
         const uint32_t pos = (uint32_t)lane + lo;

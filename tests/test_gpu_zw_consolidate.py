@@ -1,5 +1,5 @@
 """vs_index_consolidate_deletes: the rows that name a deleted node take over that node's neighbors and are pruned again (DESIGN.md
-section 6d).  The reference is `_twin`, a numpy restatement of rules 1-8 written here: np.bitwise_count for the Hamming distance,
+section 6d).  The reference is `_twin`, a numpy restatement of rules 1-8 written here (its prune in tests/build_twin.py): np.bitwise_count for the Hamming distance,
 np.float32 arithmetic for the alpha ladder, the general loop of wave_prune line by line (its inner loop over j as one numpy
 expression).  Every case asserts its own preconditions on the restatement before it looks at the device.  Also runs on the lockstep
 interpreter (tests/test_emu_consolidate.py)."""
@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+from build_twin import _ham, _pmask, _prune
 from helpers import TestIndex, make_vectors
 
 pytestmark = pytest.mark.gpu
@@ -19,52 +20,7 @@ EMU = bool(os.environ.get("VS_EMU"))
 COUNTERS = ("tombstones", "tombstones_kept", "rows_rewritten", "edges_dropped", "edges_added", "rows_pruned", "rows_capped", "rows_emptied")
 
 
-# ---- the restatement ----------------------------------------------------------------------------------------------------------------
-def _ham(codes, ids, p):
-    return np.bitwise_count(codes[ids] ^ codes[p]).sum(axis=1).astype(np.uint32)
-
-
-def _prune(codes, ids, d, R, max_alpha, pm):
-    """wave_prune's general loop: -> the selected candidate positions, in selection order"""
-    C = len(ids)
-    FMAX = np.float32(3.0e38)
-    ma = np.float32(max_alpha)
-    maxf = np.zeros(C, np.float32)
-    sel = []
-    alpha = np.float32(1.0)
-    while alpha <= ma and len(sel) < R:
-        for i in range(C):
-            if len(sel) >= R:
-                break
-            if maxf[i] > alpha:
-                continue
-            maxf[i] = FMAX
-            sel.append(i)
-            js = np.arange(i + 1, C)
-            go = ~(maxf[js] > ma)
-            if pm is not None:
-                go &= (pm[js] & ~pm[i]) == 0  # "Does it contain essential labels?"
-            js = js[go]
-            if js.size == 0:
-                continue
-            dij = _ham(codes, ids[js], ids[i])
-            with np.errstate(divide="ignore", invalid="ignore"):
-                factor = d[js].astype(np.float32) / dij.astype(np.float32)
-            factor = np.where(dij == 0, np.where(d[js] == 0, np.float32(1.0), FMAX), factor).astype(np.float32)
-            maxf[js] = np.maximum(maxf[js], factor)
-        alpha = np.float32(alpha * np.float32(1.2))
-    return sel
-
-
-def _pmask(sets, p, node):
-    """label_pmask: bit t <=> the t-th label of p (sorted) is in node's set"""
-    m = 0
-    for t, l in enumerate(sets[p]):
-        if l in sets[node]:
-            m |= 1 << t
-    return m
-
-
+# ---- the restatement (_ham, _prune and _pmask live in tests/build_twin.py, which the build and insert restatement shares) -----------
 def _twin(codes, nbrs, tids, starts, R, max_alpha=1.2, cand_max=0, sets=None):
     n = len(tids)
     dead = (tids & np.uint64(0xFFFF)) == 0
