@@ -524,6 +524,52 @@ int vs_pages_dev_meta(vs_pages_dev* d, const vs_meta_layout* layout, vs_meta_pag
  * extras: vecs / mean / m2 / count / label_start_labels / label_start_nodes (node ids); frees the raw pages */
 int vs_pages_dev_build(vs_pages_dev* d, const vs_index_desc* desc, const vs_index_host* extras, vs_pages_info* info, vs_index** out);
 void vs_pages_dev_close(vs_pages_dev* d);
+/* the block table the host read off the page headers, as vs_pages_block_table (borrowed pointers, valid until vs_pages_dev_close:
+ * the table outlives vs_pages_dev_build) */
+int vs_pages_dev_block_table(const vs_pages_dev* d, const uint32_t** blk_base, const uint32_t** blk_cnt, uint32_t* n_blocks);
+
+/* ---- following a relation that something else writes (vs_pages_dev.hip): a streaming-replication standby (WAL replay changes
+ * page images and nothing else), a primary where the CPU extension keeps aminsert and vacuum, any restart.  A follower knows the
+ * block table of the relation its index was staged from; it takes an ascending list of the blocks that changed, with their
+ * bytes as they are now, checks them on the device without touching the index (stage) and then scatters them into the resident
+ * arrays (apply).  That works because the reference only appends nodes at the end of the relation (Tape), patches neighbor
+ * lists in place at unchanged item size and clears heap offsets in place: node ids (SbqNode items on earlier blocks + offset - 1)
+ * are stable.  The rule, checked on the page headers: a listed block's item count may not shrink; it may grow only on a block
+ * behind which no block held nodes in the old table; every block in [n_blocks_before, n_blocks_total) must be listed (all-zero
+ * and non-node pages count 0 items); n_blocks_total < n_blocks_before is refused.  memory_optimized (SBQ) indexes, classic and
+ * labeled nodes; a plain index is refused (VS_ERR_INVALID).
+ * NOT read from the pages: the start nodes and the quantizer.  Block 0 is not interpreted — the caller decodes the MetaPage
+ * (vs_meta_page_decode) and calls vs_index_set_start_nodes / vs_index_set_quantizer after the apply, as it does at staging. */
+typedef struct vs_pages_follow vs_pages_follow;
+typedef struct vs_pages_follow_info {
+    uint32_t n_blocks_before, n_blocks_now, pages_listed, node_pages_listed;
+    uint32_t n_before, n_appended;
+    uint32_t rows_relinked;   /* existing nodes whose neighbour row differs from the resident one */
+    uint32_t tids_cleared;    /* existing nodes whose heap offset went from != 0 to 0 */
+    uint32_t tids_changed;    /* any other change of an existing heap tid */
+    uint32_t codes_changed;   /* existing nodes whose code row differs (the reference never does this; reported, applied) */
+    uint64_t label_vals_appended;
+} vs_pages_follow_info;
+/* blk_cnt [n_blocks]: SbqNode items per block of the relation the index was staged from (vs_pages_block_table /
+ * vs_pages_dev_block_table); the counts must sum to the index's n.  layout NULL = the default for the index's has_labels.
+ * The index must outlive the follower. */
+int vs_pages_follow_open(vs_index* idx, uint32_t page_size, const vs_node_layout* layout, const uint32_t* blk_cnt, uint32_t n_blocks,
+                         vs_pages_follow** out);
+/* blocks [n] strictly ascending; pages: n pages, page i = block blocks[i] as it is now.  The host reads the page headers only;
+ * the pages go to HBM through the pinned ring and the check pass fills `info` (may be NULL).  Nothing of the index is written;
+ * a malformed item is reported as the device reader reports it.  A second stage replaces the first; a refused one leaves none. */
+int vs_pages_follow_stage(vs_pages_follow* f, const uint32_t* blocks, const void* pages, uint32_t n, uint32_t n_blocks_total,
+                          vs_pages_follow_info* info);
+/* the appended nodes' heap tids in node order: the heap_tids array vs_heap_open takes, to read their vectors before the apply */
+int vs_pages_follow_new_tids(const vs_pages_follow* f, uint64_t* tids, uint32_t cap);
+/* VS_ERR_STATE without a staged list, on a view, while a view exists or a batch is in flight.  new_vecs [n_appended][vec_stride]
+ * floats: required when the index holds a vector column and rows are appended (else VS_ERR_INVALID, nothing written; ignored
+ * otherwise).  Capacity grows as vs_index_insert grows it; codes are taken from the pages, norms computed for the new rows,
+ * label sets appended, the own visibility mask gets 1 and every stored snapshot 0 for the new rows; derived state is treated as
+ * vs_index_insert treats it.  The follower's table advances only on success. */
+int vs_pages_follow_apply(vs_pages_follow* f, const float* new_vecs, uint32_t vec_stride, vs_pages_follow_info* info);
+int vs_pages_follow_discard(vs_pages_follow* f);  /* forget the staged list */
+void vs_pages_follow_close(vs_pages_follow* f);
 
 /* ---- the way back: a device-resident index written out as the pages of a `diskann` index relation (vs_pages.cpp,
  * vs_pages_dev.hip) — the layout the reference's ambuild leaves behind: block 0 = Meta chain (MetaPageHeader item 1, MetaPage

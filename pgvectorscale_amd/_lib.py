@@ -167,6 +167,14 @@ class LabelRepairStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class PagesFollowInfo(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("n_blocks_before", "n_blocks_now", "pages_listed", "node_pages_listed", "n_before", "n_appended",
+                                          "rows_relinked", "tids_cleared", "tids_changed", "codes_changed")] + [("label_vals_appended", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class DatagenParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("dim", C.c_uint32), ("latent_dim", C.c_uint32), ("n_clusters", C.c_uint32),
                 ("intra_pct", C.c_uint32), ("noise_pct", C.c_uint32), ("normalize", C.c_uint32)]
@@ -255,6 +263,13 @@ SYMBOLS = {
     "vs_pages_dev_sbq_means": (_i, [_vp, _u32, _u32, _vp, _vp, _u32, C.POINTER(_u32), C.POINTER(_u64)]),
     "vs_pages_dev_build": (_i, [_vp, C.POINTER(IndexDesc), C.POINTER(IndexHost), C.POINTER(PagesInfo), C.POINTER(_vp)]),
     "vs_pages_dev_close": (None, [_vp]),
+    "vs_pages_dev_block_table": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u32)]),
+    "vs_pages_follow_open": (_i, [_vp, _u32, C.POINTER(NodeLayout), _vp, _u32, C.POINTER(_vp)]),
+    "vs_pages_follow_stage": (_i, [_vp, _vp, _vp, _u32, _u32, C.POINTER(PagesFollowInfo)]),
+    "vs_pages_follow_new_tids": (_i, [_vp, _vp, _u32]),
+    "vs_pages_follow_apply": (_i, [_vp, _vp, _u32, C.POINTER(PagesFollowInfo)]),
+    "vs_pages_follow_discard": (_i, [_vp]),
+    "vs_pages_follow_close": (None, [_vp]),
     "vs_pages_out_open": (_i, [_vp, C.POINTER(PagesOutParams), C.POINTER(_vp), C.POINTER(PagesInfo)]),
     "vs_pages_out_read": (_i, [_vp, _u32, _u32, _vp]),
     "vs_pages_out_read_dev": (_i, [_vp, _u32, _u32, _vp]),

@@ -879,6 +879,17 @@ int vs_pages_headers_only(vs_pages* p) {
     return VS_OK;
 }
 
+// the header pass of vs_pages_add over ONE page that is not added to a reader (vs_pages_follow_stage): the same checks, and the
+// number of SbqNode items the block table would record for it (0 for a new page and for every other page type)
+int vs_pages_header_items(const void* page, uint32_t page_size, uint32_t block, uint32_t* sbq_items) {
+    if (!page || !sbq_items) return fail("vs_pages_header_items: null argument");
+    PageView v;
+    std::string err;
+    if (!view_page(static_cast<const uint8_t*>(page), page_size, v, err)) return fail("block %u: %s", block, err.c_str());
+    *sbq_items = v.type == VS_PAGE_SBQ_NODE ? v.n_items : 0;
+    return VS_OK;
+}
+
 int vs_pages_block_table(const vs_pages* p, const uint32_t** blk_base, const uint32_t** blk_cnt, uint32_t* n_blocks) {
     if (!p || !blk_base || !blk_cnt || !n_blocks) return fail("vs_pages_block_table: null argument");
     *blk_base = p->blk_base.data();

@@ -25,7 +25,13 @@ struct vs_pages_dev {
 };
 
 enum { PE_OK = 0, PE_LINE_POINTER = 1, PE_ITEM_BOUNDS = 2, PE_SHORT_ITEM = 3, PE_VEC_BOUNDS = 4, PE_CODE_WIDTH = 5, PE_NEIGHBOR_SLOTS = 6,
-       PE_DANGLING = 7, PE_LABELS = 8 };
+       PE_DANGLING = 7, PE_LABELS = 8, PE_LABELS_CHANGED = 9 };
+static const char* const kPageErrorText[] = {"", "line pointer is not LP_NORMAL", "item lies outside pd_upper..pd_special",
+                                             "item shorter than the archived node", "ArchivedVec points outside the item",
+                                             "bq_vector length differs from the index's code width",
+                                             "neighbor slot count differs from the index's num_neighbors",
+                                             "neighbor points at something that is not an SbqNode item of this relation",
+                                             "label set is not strictly increasing", "label set of an existing node changed"};
 
 __device__ __forceinline__ uint32_t ld16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
 __device__ __forceinline__ uint32_t ld32(const uint8_t* p) {  // items are MAXALIGNed: 4-byte aligned words
@@ -39,6 +45,41 @@ __device__ __forceinline__ void page_error(uint32_t* err, uint32_t code, uint32_
         err[2] = item;
         err[3] = detail;
     }
+}
+
+// Where item `off` of a page lies and what every reader of it may rely on: PageGetItemId / PageGetItem (UT/ports.rs:56-77) with the
+// bounds the reference leaves to PostgreSQL, and room for the archived root (rkyv::archived_root: the root object is the tail of
+// the item).  Shared by k_pages_decode and k_pages_follow.  -> PE_OK, or the reason with its detail word.
+struct PageItem {
+    const uint8_t* item;
+    uint32_t len, root;
+};
+__device__ __forceinline__ uint32_t page_item_at(const uint8_t* page, uint32_t upper, uint32_t special, uint32_t off, uint32_t root_size,
+                                                 PageItem& it, uint32_t& detail) {
+    const uint32_t lp = ld32(page + 24 + 4 * (off - 1));
+    const uint32_t lp_off = lp & 0x7FFFu, lp_flags = (lp >> 15) & 3u, len = lp >> 17;
+    detail = lp;
+    if (lp_flags != 1u || len == 0) return PE_LINE_POINTER;
+    if (lp_off < upper || lp_off + len > special || (lp_off & 3u)) return PE_ITEM_BOUNDS;
+    detail = len;
+    if (len < root_size) return PE_SHORT_ITEM;
+    it.item = page + lp_off;
+    it.len = len;
+    it.root = len - root_size;
+    return PE_OK;
+}
+// ArchivedVec<8-byte element> = {i32 offset relative to the field, u32 len} at byte `field_off` of the root: `want` elements (else
+// `mismatch`), all of them inside the item.  tgt = where the first element starts.
+__device__ __forceinline__ uint32_t page_item_vec8(const PageItem& it, uint32_t field_off, uint32_t want, uint32_t mismatch, int64_t& tgt,
+                                                   uint32_t& detail) {
+    const uint32_t fld = it.root + field_off;
+    tgt = (int64_t)fld + (int32_t)ld32(it.item + fld);
+    const uint32_t n = ld32(it.item + fld + 4);
+    detail = n;
+    if (n != want) return mismatch;
+    detail = fld;
+    if (tgt < 0 || (uint64_t)tgt + (uint64_t)n * 8 > it.len || (tgt & 3)) return PE_VEC_BOUNDS;
+    return PE_OK;
 }
 
 // one wave per block; blocks that hold no SbqNode items are skipped
@@ -55,75 +96,51 @@ __global__ __launch_bounds__(WAVE) void k_pages_decode(const uint8_t* __restrict
         const uint32_t upper = ld16(page + 14), special = ld16(page + 16);
         for (uint32_t off = 1; off <= cnt; ++off) {
             const uint32_t node = blk_base[b] + off - 1;
-            // PageGetItemId / PageGetItem (UT/ports.rs:56-77)
-            const uint32_t lp = ld32(page + 24 + 4 * (off - 1));
-            const uint32_t lp_off = lp & 0x7FFFu, lp_flags = (lp >> 15) & 3u, len = lp >> 17;
-            if (lp_flags != 1u || len == 0) {
-                if (lane == 0) page_error(err, PE_LINE_POINTER, b, off, lp);
+            PageItem it;
+            uint32_t detail;
+            int64_t tgt;
+            uint32_t pe = page_item_at(page, upper, special, off, lay.root_size, it, detail);
+            if (pe != PE_OK) {
+                if (lane == 0) page_error(err, pe, b, off, detail);
                 continue;
             }
-            if (lp_off < upper || lp_off + len > special || (lp_off & 3u)) {
-                if (lane == 0) page_error(err, PE_ITEM_BOUNDS, b, off, lp);
-                continue;
-            }
-            if (len < lay.root_size) {
-                if (lane == 0) page_error(err, PE_SHORT_ITEM, b, off, len);
-                continue;
-            }
-            const uint8_t* item = page + lp_off;
-            const uint32_t root = len - lay.root_size;  // rkyv::archived_root: the root object is the tail of the item
+            const uint8_t* item = it.item;
             // heap_item_pointer
             if (lane == 0) {
-                const uint8_t* hp = item + root + lay.off_heap_item_pointer;
+                const uint8_t* hp = item + it.root + lay.off_heap_item_pointer;
                 tids[node] = ((uint64_t)ld32(hp) << 16) | ld16(hp + 4);
             }
-            // bq_vector: ArchivedVec<u64> = {i32 offset relative to the field, u32 len}
-            {
-                const uint32_t fld = root + lay.off_bq_vector;
-                const int64_t tgt = (int64_t)fld + (int32_t)ld32(item + fld);
-                const uint32_t n = ld32(item + fld + 4);
-                if (n != W) {
-                    if (lane == 0) page_error(err, PE_CODE_WIDTH, b, off, n);
-                    continue;
-                }
-                if (tgt < 0 || (uint64_t)tgt + (uint64_t)n * 8 > len || (tgt & 3)) {
-                    if (lane == 0) page_error(err, PE_VEC_BOUNDS, b, off, fld);
-                    continue;
-                }
-                for (uint32_t w = lane; w < W; w += WAVE) {
-                    const uint8_t* src = item + tgt + 8 * w;
-                    codes[(size_t)node * code_stride + w] = (uint64_t)ld32(src) | ((uint64_t)ld32(src + 4) << 32);
-                }
+            // bq_vector: ArchivedVec<u64>
+            pe = page_item_vec8(it, lay.off_bq_vector, W, PE_CODE_WIDTH, tgt, detail);
+            if (pe != PE_OK) {
+                if (lane == 0) page_error(err, pe, b, off, detail);
+                continue;
+            }
+            for (uint32_t w = lane; w < W; w += WAVE) {
+                const uint8_t* src = item + tgt + 8 * w;
+                codes[(size_t)node * code_stride + w] = (uint64_t)ld32(src) | ((uint64_t)ld32(src + 4) << 32);
             }
             // neighbor_index_pointers: ArchivedVec<ArchivedItemPointer {u32 block, u16 offset, pad}>, the list ends at the
             // first InvalidBlockNumber (AM/sbq/node.rs:260-285)
-            {
-                const uint32_t fld = root + lay.off_neighbor_index_pointers;
-                const int64_t tgt = (int64_t)fld + (int32_t)ld32(item + fld);
-                const uint32_t n = ld32(item + fld + 4);
-                if (n != R) {
-                    if (lane == 0) page_error(err, PE_NEIGHBOR_SLOTS, b, off, n);
-                    continue;
+            pe = page_item_vec8(it, lay.off_neighbor_index_pointers, R, PE_NEIGHBOR_SLOTS, tgt, detail);
+            if (pe != PE_OK) {
+                if (lane == 0) page_error(err, pe, b, off, detail);
+                continue;
+            }
+            bool ended = false;
+            for (uint32_t j0 = 0; j0 < R && !ended; j0 += WAVE) {
+                const uint32_t j = j0 + (uint32_t)lane;
+                uint32_t nb = 0xFFFFFFFFu, no = 0;
+                if (j < R) {
+                    nb = ld32(item + tgt + 8 * j);
+                    no = ld16(item + tgt + 8 * j + 4);
                 }
-                if (tgt < 0 || (uint64_t)tgt + (uint64_t)n * 8 > len || (tgt & 3)) {
-                    if (lane == 0) page_error(err, PE_VEC_BOUNDS, b, off, fld);
-                    continue;
-                }
-                bool ended = false;
-                for (uint32_t j0 = 0; j0 < R && !ended; j0 += WAVE) {
-                    const uint32_t j = j0 + (uint32_t)lane;
-                    uint32_t nb = 0xFFFFFFFFu, no = 0;
-                    if (j < R) {
-                        nb = ld32(item + tgt + 8 * j);
-                        no = ld16(item + tgt + 8 * j + 4);
-                    }
-                    const uint64_t inval = __ballot(nb == 0xFFFFFFFFu);
-                    const uint32_t nvalid = inval ? (uint32_t)__builtin_ctzll(inval) : WAVE;
-                    if (nvalid < WAVE) ended = true;
-                    if ((uint32_t)lane < nvalid) {
-                        if (nb >= n_blocks || no < 1 || no > blk_cnt[nb]) page_error(err, PE_DANGLING, b, off, j);
-                        else nbrs[(size_t)node * nbr_stride + j] = blk_base[nb] + no - 1;
-                    }
+                const uint64_t inval = __ballot(nb == 0xFFFFFFFFu);
+                const uint32_t nvalid = inval ? (uint32_t)__builtin_ctzll(inval) : WAVE;
+                if (nvalid < WAVE) ended = true;
+                if ((uint32_t)lane < nvalid) {
+                    if (nb >= n_blocks || no < 1 || no > blk_cnt[nb]) page_error(err, PE_DANGLING, b, off, j);
+                    else nbrs[(size_t)node * nbr_stride + j] = blk_base[nb] + no - 1;
                 }
             }
         }
@@ -330,13 +347,7 @@ extern "C" int vs_pages_dev_build(vs_pages_dev* d, const vs_index_desc* desc, co
     if (d_cnt) (void)hipFree(d_cnt);
     if (d_err) (void)hipFree(d_err);
     if (r == VS_OK && herr[0] != PE_OK) {
-        static const char* what[] = {"", "line pointer is not LP_NORMAL", "item lies outside pd_upper..pd_special",
-                                     "item shorter than the archived node", "ArchivedVec points outside the item",
-                                     "bq_vector length differs from the index's code width",
-                                     "neighbor slot count differs from the index's num_neighbors",
-                                     "neighbor points at something that is not an SbqNode item of this relation",
-                                     "label set is not strictly increasing"};
-        vs_set_error("block %u item %u: %s (detail %u)", herr[1], herr[2], what[herr[0] <= PE_LABELS ? herr[0] : 0], herr[3]);
+        vs_set_error("block %u item %u: %s (detail %u)", herr[1], herr[2], kPageErrorText[herr[0] <= PE_LABELS ? herr[0] : 0], herr[3]);
         r = VS_ERR_INVALID;
     }
     // the raw pages are no longer needed
@@ -359,6 +370,613 @@ extern "C" int vs_pages_dev_build(vs_pages_dev* d, const vs_index_desc* desc, co
     }
     *out = ix;
     return VS_OK;
+}
+
+extern "C" int vs_pages_dev_block_table(const vs_pages_dev* d, const uint32_t** blk_base, const uint32_t** blk_cnt, uint32_t* n_blocks) {
+    VS_REQUIRE(d, "vs_pages_dev_block_table: null reader");
+    return vs_pages_block_table(d->hdr, blk_base, blk_cnt, n_blocks);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Following a relation that something else writes (vs_pages_follow_*): the blocks that changed, scattered into the resident arrays.
+//
+// The reference only ever appends nodes at the end of the relation (Tape), patches neighbor lists in place at unchanged item size
+// and clears heap offsets in place, so a node id — SbqNode items on earlier blocks + offset - 1 — never moves as long as item
+// counts grow only where no node page follows (the rule vs_pages_follow_stage enforces on the page headers).  k_pages_follow takes
+// its pages from the staged list (slot i holds block blocks[i]), locates and checks every item as k_pages_decode does, translates
+// neighbor pointers through the NEW block table, and splits at n_before: WRITE = false compares an existing node with the resident
+// row (one ballot per row kind, one atomic per wave and counter at the end) and leaves an appended node's heap tid in new_tids;
+// WRITE = true scatters.  Listed pages are distinct and a node lives on one page: the write pass has no race and no atomically
+// assigned slot.
+// ---------------------------------------------------------------------------------------------------------------
+enum { FC_RELINKED = 0, FC_TIDS_CLEARED, FC_TIDS_CHANGED, FC_CODES_CHANGED, FC_NODE_PAGES, FC_N = 8 };
+struct PagesFollowArgs {
+    const uint8_t* pages;     // [n_listed][page_size]
+    const uint32_t* blocks;   // [n_listed] ascending
+    const uint2* tab;         // [n_blocks] {dense id of the block's first node, SbqNode items on it} of the relation as it is now
+    uint32_t n_listed, page_size, n_blocks;
+    vs_node_layout lay;
+    uint32_t W, R, n_before, has_labels;
+    uint64_t* codes;
+    uint32_t* nbrs;
+    uint64_t* tids;
+    uint32_t code_stride, nbr_stride;
+    const uint32_t* label_off;  // check: the resident CSR; write: the offsets with the appended rows' behind them
+    int16_t* label_val;         // check: the resident values (read); write: the grown array
+    uint32_t* label_cnt;        // check: [n_appended] label count of every appended node
+    uint64_t* new_tids;         // check: [n_appended]
+    uint32_t* ctr;              // [FC_N]
+    uint32_t* err;
+};
+
+template <bool WRITE>
+__global__ __launch_bounds__(WAVE) void k_pages_follow(PagesFollowArgs a) {
+    const int lane = threadIdx.x;
+    const vs_node_layout lay = a.lay;
+    uint32_t c_relinked = 0, c_cleared = 0, c_changed = 0, c_codes = 0, c_pages = 0;  // (wave-uniform)
+    for (uint32_t i = blockIdx.x; i < a.n_listed; i += gridDim.x) {
+        const uint32_t b = a.blocks[i];
+        const uint2 ent = a.tab[b];
+        const uint32_t cnt = ent.y;
+        if (cnt == 0) continue;
+        c_pages++;
+        const uint8_t* page = a.pages + (size_t)i * a.page_size;
+        const uint32_t upper = ld16(page + 14), special = ld16(page + 16);
+        for (uint32_t off = 1; off <= cnt; ++off) {  // (107 one-word items fit a page: the items, not the lanes, bound the loop)
+            const uint32_t node = ent.x + off - 1;
+            const bool old = node < a.n_before;
+            PageItem it;
+            uint32_t detail;
+            int64_t tgt;
+            uint32_t pe = page_item_at(page, upper, special, off, lay.root_size, it, detail);
+            if (pe != PE_OK) {
+                if (lane == 0) page_error(a.err, pe, b, off, detail);
+                continue;
+            }
+            const uint8_t* item = it.item;
+            int64_t tgt_nbr;
+            pe = page_item_vec8(it, lay.off_bq_vector, a.W, PE_CODE_WIDTH, tgt, detail);
+            if (pe == PE_OK) pe = page_item_vec8(it, lay.off_neighbor_index_pointers, a.R, PE_NEIGHBOR_SLOTS, tgt_nbr, detail);
+            if (pe != PE_OK) {  // (nothing of a malformed item is written, by either pass)
+                if (lane == 0) page_error(a.err, pe, b, off, detail);
+                continue;
+            }
+            // heap_item_pointer
+            {
+                const uint8_t* hp = item + it.root + lay.off_heap_item_pointer;
+                const uint64_t tid = ((uint64_t)ld32(hp) << 16) | ld16(hp + 4);
+                if (WRITE) {
+                    if (lane == 0) a.tids[node] = tid;
+                } else if (old) {
+                    const uint64_t was = a.tids[node];
+                    if (was != tid) {
+                        if ((was & 0xFFFFu) != 0 && (tid & 0xFFFFu) == 0) c_cleared++;
+                        else c_changed++;
+                    }
+                } else if (lane == 0) {
+                    a.new_tids[node - a.n_before] = tid;
+                }
+            }
+            // bq_vector: the row's padding words stay zero
+            {
+                bool diff = false;
+                uint64_t* row = a.codes + (size_t)node * a.code_stride;
+                for (uint32_t w = lane; w < a.code_stride; w += WAVE) {
+                    uint64_t v = 0;
+                    if (w < a.W) {
+                        const uint8_t* src = item + tgt + 8 * w;
+                        v = (uint64_t)ld32(src) | ((uint64_t)ld32(src + 4) << 32);
+                    }
+                    if (WRITE) row[w] = v;
+                    else if (old && w < a.W) diff |= row[w] != v;
+                }
+                if (!WRITE && old && __ballot(diff)) c_codes++;
+            }
+            // neighbor_index_pointers: the list ends at the first InvalidBlockNumber; the row is padded to nbr_stride with the sentinel
+            {
+                bool diff = false, ended = false;
+                uint32_t* row = a.nbrs + (size_t)node * a.nbr_stride;
+                for (uint32_t j0 = 0; j0 < a.nbr_stride; j0 += WAVE) {
+                    const uint32_t j = j0 + (uint32_t)lane;
+                    uint32_t nb = 0xFFFFFFFFu, no = 0;
+                    if (j < a.R && !ended) {
+                        nb = ld32(item + tgt_nbr + 8 * j);
+                        no = ld16(item + tgt_nbr + 8 * j + 4);
+                    }
+                    const uint64_t inval = __ballot(nb == 0xFFFFFFFFu);
+                    const uint32_t nvalid = inval ? (uint32_t)__builtin_ctzll(inval) : WAVE;
+                    if (nvalid < WAVE) ended = true;
+                    uint32_t id = VS_INVALID_NODE;
+                    if ((uint32_t)lane < nvalid) {
+                        uint2 t = make_uint2(0, 0);
+                        if (nb < a.n_blocks) t = a.tab[nb];
+                        if (no < 1 || no > t.y) page_error(a.err, PE_DANGLING, b, off, j);
+                        else id = t.x + no - 1;
+                    }
+                    if (j < a.nbr_stride) {
+                        if (WRITE) row[j] = id;
+                        else if (old && j < a.R) diff |= row[j] != id;
+                    }
+                }
+                if (!WRITE && old && __ballot(diff)) c_relinked++;
+            }
+            // labels (LabeledSbqNode): an existing node's set is the resident CSR slice, an appended node's is counted, then copied
+            if (a.has_labels) {
+                const uint32_t fld = it.root + lay.off_labels;
+                const int64_t tl = (int64_t)fld + (int32_t)ld32(item + fld);
+                const uint32_t n = ld32(item + fld + 4);
+                if (n && (tl < 0 || (uint64_t)tl + (uint64_t)n * 2 > it.len || (tl & 1))) {
+                    if (lane == 0) page_error(a.err, PE_VEC_BOUNDS, b, off, fld);
+                    if (!WRITE && !old && lane == 0) a.label_cnt[node - a.n_before] = 0;
+                    continue;
+                }
+                if (old) {
+                    if (!WRITE) {
+                        const uint32_t o = a.label_off[node], have = a.label_off[node + 1] - o;
+                        bool diff = n != have;
+                        if (!diff)
+                            for (uint32_t j = lane; j < n; j += WAVE) diff |= (int16_t)ld16(item + tl + 2 * j) != a.label_val[o + j];
+                        if (__ballot(diff) && lane == 0) page_error(a.err, PE_LABELS_CHANGED, b, off, n);
+                    }
+                } else if (!WRITE) {
+                    for (uint32_t j = 1 + (uint32_t)lane; j < n; j += WAVE)
+                        if ((int16_t)ld16(item + tl + 2 * j) <= (int16_t)ld16(item + tl + 2 * j - 2)) page_error(a.err, PE_LABELS, b, off, j);
+                    if (lane == 0) a.label_cnt[node - a.n_before] = n;
+                } else {
+                    const uint32_t o = a.label_off[node];
+                    for (uint32_t j = lane; j < n; j += WAVE) a.label_val[o + j] = (int16_t)ld16(item + tl + 2 * j);
+                }
+            }
+        }
+    }
+    if (!WRITE && lane == 0) {
+        if (c_relinked) atomicAdd(&a.ctr[FC_RELINKED], c_relinked);
+        if (c_cleared) atomicAdd(&a.ctr[FC_TIDS_CLEARED], c_cleared);
+        if (c_changed) atomicAdd(&a.ctr[FC_TIDS_CHANGED], c_changed);
+        if (c_codes) atomicAdd(&a.ctr[FC_CODES_CHANGED], c_codes);
+        if (c_pages) atomicAdd(&a.ctr[FC_NODE_PAGES], c_pages);
+    }
+}
+
+struct vs_pages_follow {
+    vs_index* ix = nullptr;
+    vs_ctx* ctx = nullptr;
+    uint32_t page_size = VS_BLCKSZ;
+    vs_node_layout lay{};
+    bool labeled = false;
+    // the block table of the relation the index mirrors now (host), and the same on the device as {base, count} per block
+    std::vector<uint32_t> cnt, base;
+    uint32_t n = 0;
+    uint2* d_tab = nullptr;
+    uint32_t tab_cap = 0;
+    // a staged list
+    bool staged = false;
+    uint32_t tail0 = 0;  // first block whose device entry is the staged one, not the current one
+    std::vector<uint32_t> s_cnt, s_base;  // the table as the staged pages make it
+    std::vector<uint32_t> s_label_off;    // labeled: label_off[n_before + 1 ..] of the grown index
+    std::vector<uint64_t> s_new_tids;
+    vs_pages_follow_info info{};
+    uint8_t* d_pages = nullptr;
+    size_t pages_cap = 0;
+    uint32_t* d_list = nullptr;
+    size_t list_cap = 0;
+    uint64_t* d_new_tids = nullptr;
+    uint32_t* d_lcnt = nullptr;
+    size_t new_cap = 0;
+    uint32_t* d_ctr = nullptr;  // FC_N counters, then the error record
+};
+
+static void follow_table_entries(const std::vector<uint32_t>& base, const std::vector<uint32_t>& cnt, uint32_t b0, uint32_t b1,
+                                 std::vector<uint2>& out) {
+    out.resize(b1 - b0);
+    for (uint32_t b = b0; b < b1; ++b) out[b - b0] = make_uint2(base[b], cnt[b]);
+}
+
+// the device table is the current one again (the entries a staged list replaced are uploaded from the host's table)
+static int follow_unstage(vs_pages_follow* f) {
+    if (!f->staged) return VS_OK;
+    f->staged = false;
+    const uint32_t nb = (uint32_t)f->cnt.size();
+    if (f->tail0 < nb) {
+        std::vector<uint2> ent;
+        follow_table_entries(f->base, f->cnt, f->tail0, nb, ent);
+        VS_TRY(vs_dev_upload(f->ctx, f->d_tab + f->tail0, ent.data(), ent.size() * 8));
+    }
+    return VS_OK;
+}
+
+extern "C" void vs_pages_follow_close(vs_pages_follow* f) {
+    if (!f) return;
+    if (f->ctx) (void)hipSetDevice(f->ctx->device);
+    if (f->d_tab) (void)hipFree(f->d_tab);
+    if (f->d_pages) (void)hipFree(f->d_pages);
+    if (f->d_list) (void)hipFree(f->d_list);
+    if (f->d_new_tids) (void)hipFree(f->d_new_tids);
+    if (f->d_lcnt) (void)hipFree(f->d_lcnt);
+    if (f->d_ctr) (void)hipFree(f->d_ctr);
+    delete f;
+}
+
+static int follow_open_impl(vs_pages_follow* f, const uint32_t* blk_cnt, uint32_t n_blocks) {
+    vs_ctx* c = f->ctx;
+    VS_HIP(hipSetDevice(c->device));
+    f->cnt.assign(blk_cnt, blk_cnt + n_blocks);
+    f->base.resize(n_blocks);
+    uint64_t sum = 0;
+    for (uint32_t b = 0; b < n_blocks; ++b) {
+        f->base[b] = (uint32_t)sum;
+        sum += blk_cnt[b];
+        VS_REQUIRE(sum < VS_INVALID_NODE, "vs_pages_follow_open: the block table counts more than %u nodes", VS_INVALID_NODE - 1);
+    }
+    VS_REQUIRE(sum == f->ix->d.n, "vs_pages_follow_open: the block table counts %llu nodes, the index holds %u", (unsigned long long)sum,
+               f->ix->d.n);
+    f->n = (uint32_t)sum;
+    f->tab_cap = n_blocks + n_blocks / 2 + 64;
+    VS_HIP(hipMalloc(&f->d_tab, (size_t)f->tab_cap * 8));
+    VS_HIP(hipMalloc(&f->d_ctr, (FC_N + 4) * 4));
+    if (n_blocks) {
+        std::vector<uint2> ent;
+        follow_table_entries(f->base, f->cnt, 0, n_blocks, ent);
+        VS_TRY(vs_dev_upload(c, f->d_tab, ent.data(), ent.size() * 8));
+    }
+    return VS_OK;
+}
+
+extern "C" int vs_pages_follow_open(vs_index* idx, uint32_t page_size, const vs_node_layout* layout, const uint32_t* blk_cnt,
+                                    uint32_t n_blocks, vs_pages_follow** out) {
+    VS_REQUIRE(idx && out && (blk_cnt || !n_blocks), "vs_pages_follow_open: bad args");
+    *out = nullptr;
+    VS_REQUIRE(idx->d.storage_type == VS_STORAGE_SBQ, "vs_pages_follow_open: memory_optimized (SBQ) indexes only; a `plain` index keeps its "
+               "vectors in the nodes and is not followed");
+    VS_REQUIRE(idx->codes && idx->nbrs && idx->tids, "vs_pages_follow_open: the index holds no codes / neighbors");
+    VS_REQUIRE(page_size >= 512 && page_size <= 32768 && !(page_size & (page_size - 1)), "vs_pages_follow_open: page_size %u is not a PostgreSQL block size",
+               page_size);
+    return vs_guard("vs_pages_follow_open", [&] {
+        vs_pages_follow* f = new vs_pages_follow();
+        f->ix = idx;
+        f->ctx = idx->ctx;
+        f->page_size = page_size;
+        f->labeled = idx->label_off != nullptr;
+        if (layout) f->lay = *layout;
+        else vs_node_layout_default(f->labeled ? 1 : 0, &f->lay);
+        const vs_node_layout& l = f->lay;
+        const uint32_t offs[4] = {l.off_heap_item_pointer, l.off_bq_vector, l.off_neighbor_index_pointers, l.off_labels};
+        int r = VS_OK;
+        for (int i = 0; i < (f->labeled ? 4 : 3) && r == VS_OK; ++i)
+            if (offs[i] > l.root_size || l.root_size - offs[i] < 8 || l.root_size > 4096 || (offs[i] & 3u)) {
+                vs_set_error("vs_pages_follow_open: field offset %u does not fit a %u-byte archived node", offs[i], l.root_size);
+                r = VS_ERR_INVALID;
+            }
+        if (r == VS_OK) r = follow_open_impl(f, blk_cnt, n_blocks);
+        if (r != VS_OK) {
+            vs_pages_follow_close(f);
+            return r;
+        }
+        *out = f;
+        return (int)VS_OK;
+    });
+}
+
+template <class T>
+static int follow_reserve(T** p, size_t* cap, size_t n) {
+    if (n <= *cap) return VS_OK;
+    if (*p) VS_HIP(hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
+    VS_HIP(hipMalloc(p, n * sizeof(T)));
+    *cap = n;
+    return VS_OK;
+}
+
+static int follow_launch(vs_pages_follow* f, bool write, const PagesFollowArgs& a) {
+    vs_ctx* c = f->ctx;
+    const uint32_t grid = std::min<uint32_t>(a.n_listed, 1u << 20);
+    hipEvent_t ev = prof_begin(c);
+    if (write) hipLaunchKernelGGL((k_pages_follow<true>), dim3(grid), dim3(WAVE), 0, c->stream, a);
+    else hipLaunchKernelGGL((k_pages_follow<false>), dim3(grid), dim3(WAVE), 0, c->stream, a);
+    VS_HIP(hipGetLastError());
+    prof_end(c, PK_PAGES, ev);
+    return VS_OK;
+}
+
+static PagesFollowArgs follow_args(const vs_pages_follow* f, uint32_t n_listed, uint32_t n_blocks_now) {
+    const vs_index* ix = f->ix;
+    PagesFollowArgs a{};
+    a.pages = f->d_pages;
+    a.blocks = f->d_list;
+    a.tab = f->d_tab;
+    a.n_listed = n_listed;
+    a.page_size = f->page_size;
+    a.n_blocks = n_blocks_now;
+    a.lay = f->lay;
+    a.W = ix->d.words;
+    a.R = ix->d.num_neighbors;
+    a.n_before = f->n;
+    a.has_labels = f->labeled ? 1u : 0u;
+    a.codes = ix->codes;
+    a.nbrs = ix->nbrs;
+    a.tids = ix->tids;
+    a.code_stride = ix->code_stride;
+    a.nbr_stride = ix->nbr_stride;
+    a.label_off = ix->label_off;
+    a.label_val = ix->label_val;
+    a.label_cnt = f->d_lcnt;
+    a.new_tids = f->d_new_tids;
+    a.ctr = f->d_ctr;
+    a.err = f->d_ctr + FC_N;
+    return a;
+}
+
+// what a pass reported (after the stream has been synchronised)
+static int follow_page_error(const uint32_t* herr, const char* what) {
+    if (herr[0] == PE_OK) return VS_OK;
+    vs_set_error("%s: block %u item %u: %s (detail %u)", what, herr[1], herr[2], kPageErrorText[herr[0] <= PE_LABELS_CHANGED ? herr[0] : 0], herr[3]);
+    return VS_ERR_INVALID;
+}
+
+static int follow_stage_impl(vs_pages_follow* f, const uint32_t* blocks, const void* pages, uint32_t n, uint32_t n_blocks_total,
+                             vs_pages_follow_info* info) {
+    const char* what = "vs_pages_follow_stage";
+    vs_ctx* c = f->ctx;
+    vs_index* ix = f->ix;
+    VS_HIP(hipSetDevice(c->device));
+    VS_TRY(follow_unstage(f));  // (a second stage replaces the first, a refused one leaves none)
+    if (f->n != ix->d.n) {
+        vs_set_error("%s: the index holds %u nodes, the follower's table %u: something else changed the index (open a new follower)", what,
+                     ix->d.n, f->n);
+        return VS_ERR_STATE;
+    }
+    const uint32_t nb_before = (uint32_t)f->cnt.size();
+    VS_REQUIRE(n_blocks_total >= nb_before, "%s: the relation shrank from %u to %u blocks", what, nb_before, n_blocks_total);
+    VS_REQUIRE(n_blocks_total < 0xFFFFFFFFu, "%s: block number overflow", what);
+    // the last block that held nodes: an item count may grow there and behind it, nowhere else
+    uint32_t last_node_block = 0;
+    bool any_node_block = false;
+    for (uint32_t b = nb_before; b-- > 0;)
+        if (f->cnt[b]) {
+            last_node_block = b;
+            any_node_block = true;
+            break;
+        }
+    const uint8_t* src = static_cast<const uint8_t*>(pages);
+    std::vector<uint32_t> l_cnt(n);
+    uint32_t tail_listed = 0, first_changed = n_blocks_total;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t b = blocks[i];
+        VS_REQUIRE(i == 0 || blocks[i - 1] < b, "%s: blocks[%u] = %u after %u: the list must be strictly ascending", what, i, b, blocks[i - 1]);
+        VS_REQUIRE(b < n_blocks_total, "%s: blocks[%u] = %u of a relation of %u blocks", what, i, b, n_blocks_total);
+        VS_TRY(vs_pages_header_items(src + (size_t)i * f->page_size, f->page_size, b, &l_cnt[i]));
+        const uint32_t was = b < nb_before ? f->cnt[b] : 0;
+        VS_REQUIRE(l_cnt[i] >= was, "%s: block %u held %u nodes and holds %u now: existing nodes would move", what, b, was, l_cnt[i]);
+        VS_REQUIRE(l_cnt[i] == was || !any_node_block || b >= last_node_block,
+                   "%s: block %u gained %u item(s) in front of the node page %u: existing nodes would move", what, b, l_cnt[i] - was, last_node_block);
+        if (b >= nb_before) tail_listed++;
+        if (l_cnt[i] != was || b >= nb_before) first_changed = std::min(first_changed, b);
+    }
+    VS_REQUIRE(tail_listed == n_blocks_total - nb_before, "%s: %u of the %u blocks the relation grew by are in the list (every block from %u on must be)",
+               what, tail_listed, n_blocks_total - nb_before, nb_before);
+    first_changed = std::min(first_changed, nb_before);
+    // the table as it is now
+    f->s_cnt = f->cnt;
+    f->s_cnt.resize(n_blocks_total, 0);
+    for (uint32_t i = 0; i < n; ++i) f->s_cnt[blocks[i]] = l_cnt[i];
+    f->s_base = f->base;
+    f->s_base.resize(n_blocks_total, 0);
+    uint64_t sum = first_changed < nb_before ? f->base[first_changed] : f->n;
+    for (uint32_t b = first_changed; b < n_blocks_total; ++b) {
+        f->s_base[b] = (uint32_t)sum;
+        sum += f->s_cnt[b];
+        VS_REQUIRE(sum < VS_INVALID_NODE, "%s: more than %u index nodes", what, VS_INVALID_NODE - 1);
+    }
+    const uint32_t n_app = (uint32_t)sum - f->n;
+    vs_pages_follow_info fi{};
+    fi.n_blocks_before = nb_before;
+    fi.n_blocks_now = n_blocks_total;
+    fi.pages_listed = n;
+    fi.n_before = f->n;
+    fi.n_appended = n_app;
+    // device side: the table's tail, the list, the pages (through the pinned ring)
+    if (n_blocks_total > f->tab_cap) {
+        uint2* fresh = nullptr;
+        const uint32_t cap = n_blocks_total + n_blocks_total / 2 + 64;
+        VS_HIP(hipMalloc(&fresh, (size_t)cap * 8));
+        (void)hipFree(f->d_tab);
+        f->d_tab = fresh;
+        f->tab_cap = cap;
+        first_changed = 0;
+    }
+    f->tail0 = first_changed;
+    f->staged = true;  // (from here on the device table may differ from the current one: every way out below goes through follow_unstage)
+    auto run = [&]() -> int {
+        if (first_changed < n_blocks_total) {
+            std::vector<uint2> ent;
+            follow_table_entries(f->s_base, f->s_cnt, first_changed, n_blocks_total, ent);
+            VS_TRY(vs_dev_upload(c, f->d_tab + first_changed, ent.data(), ent.size() * 8));
+        }
+        VS_HIP(hipMemsetAsync(f->d_ctr, 0, (FC_N + 4) * 4, c->stream));
+        uint32_t h[FC_N + 4] = {0};
+        if (n) {
+            VS_TRY(follow_reserve(&f->d_list, &f->list_cap, (size_t)n));
+            VS_TRY(follow_reserve(&f->d_pages, &f->pages_cap, (size_t)n * f->page_size));
+            if (n_app > f->new_cap) {
+                size_t cap_t = f->new_cap, cap_l = f->new_cap;
+                VS_TRY(follow_reserve(&f->d_new_tids, &cap_t, (size_t)n_app));
+                VS_TRY(follow_reserve(&f->d_lcnt, &cap_l, (size_t)n_app));
+                f->new_cap = n_app;
+            }
+            VS_TRY(vs_dev_upload(c, f->d_list, blocks, (size_t)n * 4));
+            VS_TRY(vs_dev_upload(c, f->d_pages, pages, (size_t)n * f->page_size));
+            VS_TRY(follow_launch(f, false, follow_args(f, n, n_blocks_total)));
+            VS_HIP(hipMemcpyAsync(h, f->d_ctr, sizeof h, hipMemcpyDeviceToHost, c->stream));
+        }
+        VS_HIP(hipStreamSynchronize(c->stream));
+        VS_TRY(follow_page_error(h + FC_N, what));
+        fi.node_pages_listed = h[FC_NODE_PAGES];
+        fi.rows_relinked = h[FC_RELINKED];
+        fi.tids_cleared = h[FC_TIDS_CLEARED];
+        fi.tids_changed = h[FC_TIDS_CHANGED];
+        fi.codes_changed = h[FC_CODES_CHANGED];
+        f->s_new_tids.resize(n_app);
+        f->s_label_off.clear();
+        if (n_app) VS_TRY(vs_dev_download(c, f->s_new_tids.data(), f->d_new_tids, (size_t)n_app * 8));
+        if (f->labeled && n_app) {
+            f->s_label_off.resize(n_app);
+            VS_TRY(vs_dev_download(c, f->s_label_off.data(), f->d_lcnt, (size_t)n_app * 4));
+            uint64_t tot = ix->n_label_vals;
+            for (uint32_t i = 0; i < n_app; ++i) {
+                tot += f->s_label_off[i];
+                f->s_label_off[i] = (uint32_t)tot;
+            }
+            VS_REQUIRE(tot < 0xFFFFFFFFull, "%s: label CSR exceeds 2^32 entries", what);
+            fi.label_vals_appended = tot - ix->n_label_vals;
+        }
+        return VS_OK;
+    };
+    const int rc = run();
+    if (rc != VS_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        (void)follow_unstage(f);
+        return rc;
+    }
+    f->info = fi;
+    if (info) *info = fi;
+    return VS_OK;
+}
+
+extern "C" int vs_pages_follow_stage(vs_pages_follow* f, const uint32_t* blocks, const void* pages, uint32_t n, uint32_t n_blocks_total,
+                                     vs_pages_follow_info* info) {
+    VS_REQUIRE(f && (n == 0 || (blocks && pages)), "vs_pages_follow_stage: bad args");
+    if (info) memset(info, 0, sizeof *info);
+    return vs_guard("vs_pages_follow_stage", [&] { return follow_stage_impl(f, blocks, pages, n, n_blocks_total, info); });
+}
+
+extern "C" int vs_pages_follow_new_tids(const vs_pages_follow* f, uint64_t* tids, uint32_t cap) {
+    VS_REQUIRE(f, "vs_pages_follow_new_tids: null follower");
+    if (!f->staged) {
+        vs_set_error("vs_pages_follow_new_tids: no list is staged");
+        return VS_ERR_STATE;
+    }
+    VS_REQUIRE(cap >= f->s_new_tids.size() && (tids || f->s_new_tids.empty()), "vs_pages_follow_new_tids: room for %u of %zu tids", cap,
+               f->s_new_tids.size());
+    if (!f->s_new_tids.empty()) memcpy(tids, f->s_new_tids.data(), f->s_new_tids.size() * 8);
+    return VS_OK;
+}
+
+extern "C" int vs_pages_follow_discard(vs_pages_follow* f) {
+    VS_REQUIRE(f, "vs_pages_follow_discard: null follower");
+    return vs_guard("vs_pages_follow_discard", [&]() -> int {
+        VS_HIP(hipSetDevice(f->ctx->device));
+        return follow_unstage(f);
+    });
+}
+
+static int follow_apply_impl(vs_pages_follow* f, const float* new_vecs, uint32_t vec_stride, vs_pages_follow_info* info) {
+    const char* what = "vs_pages_follow_apply";
+    vs_index* ix = f->ix;
+    vs_ctx* c = f->ctx;
+    hipStream_t st = c->stream;
+    auto state_error = [&](const char* msg) {
+        vs_set_error("%s: %s", what, msg);
+        return VS_ERR_STATE;
+    };
+    if (!f->staged) return state_error("no list is staged (vs_pages_follow_stage first)");
+    VS_REQUIRE_OWNER(ix, what);
+    VS_REQUIRE_NO_VIEWS(ix, what);
+    if (ix->ws.pending) return state_error("a batch of this handle is in flight (vs_search_batch_dev_finish first)");
+    if (f->n != ix->d.n) return state_error("the index changed after the list was staged (open a new follower)");
+    const uint32_t n_old = f->n, n_app = f->info.n_appended, n = n_old + n_app;
+    if (n_app && ix->visible && ix->visible != ix->visible_own) {
+        bool ours = false;
+        for (const uint8_t* sp : ix->snap) ours |= sp == ix->visible;
+        if (!ours) return state_error("a caller-owned device visibility mask is in force and cannot be grown by the library (clear or replace it)");
+    }
+    const bool want_vecs = ix->vecs != nullptr && n_app > 0;
+    VS_REQUIRE(!want_vecs || new_vecs, "%s: the index holds a vector column and %u rows are appended: new_vecs is NULL (vs_pages_follow_new_tids "
+               "names the heap tuples to read)", what, n_app);
+    VS_REQUIRE(!want_vecs || vec_stride >= ix->d.dim_full, "%s: vec_stride %u < num_dimensions %u", what, vec_stride, ix->d.dim_full);
+    VS_HIP(hipSetDevice(c->device));
+    if (n > ix->capacity) {  // the insert's rule: by half, at least to fit; a failed growth leaves the index as it was
+        const uint64_t want = std::max<uint64_t>(n, (uint64_t)ix->capacity + ix->capacity / 2);
+        VS_TRY(vs_index_reserve_impl(ix, (uint32_t)std::min<uint64_t>(want, VS_INVALID_NODE - 1), what));
+    }
+    // the grown label CSR: the values are built aside and swapped in at the end, the offsets are appended behind the live ones
+    int16_t* new_val = nullptr;
+    const uint64_t old_vals = ix->n_label_vals, add_vals = f->info.label_vals_appended;
+    if (f->labeled && add_vals) {
+        VS_HIP(hipMalloc(&new_val, (old_vals + add_vals) * 2));
+        hipError_t e = hipSuccess;
+        if (old_vals) e = hipMemcpyAsync(new_val, ix->label_val, old_vals * 2, hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) {
+            (void)hipFree(new_val);
+            vs_set_error("%s: copying the label sets failed: %s", what, hipGetErrorString(e));
+            return VS_ERR_HIP;
+        }
+    }
+    auto run = [&]() -> int {
+        if (f->labeled && n_app) {
+            if (n_old == 0) {
+                const uint32_t zero = 0;
+                VS_HIP(hipMemcpy(ix->label_off, &zero, 4, hipMemcpyHostToDevice));
+            }
+            VS_TRY(vs_dev_upload(c, ix->label_off + n_old + 1, f->s_label_off.data(), (size_t)n_app * 4));
+        }
+        if (want_vecs)
+            VS_TRY(vs_upload_rows(c, ix->vecs + (size_t)n_old * ix->vec_stride, ix->vec_stride * 4ull, new_vecs, vec_stride * 4ull,
+                                  ix->d.dim_full * 4ull, n_app));
+        uint32_t herr[4] = {0, 0, 0, 0};
+        if (f->info.pages_listed) {
+            VS_HIP(hipMemsetAsync(f->d_ctr, 0, (FC_N + 4) * 4, st));
+            PagesFollowArgs a = follow_args(f, f->info.pages_listed, f->info.n_blocks_now);  // (after the reserve: the arrays may have moved)
+            if (new_val) a.label_val = new_val;
+            VS_TRY(follow_launch(f, true, a));
+            if (f->info.codes_changed) ix->codes_epoch++;
+            VS_HIP(hipMemcpyAsync(herr, f->d_ctr + FC_N, 16, hipMemcpyDeviceToHost, st));
+        }
+        if (n_app) {
+            // a new tuple is visible to the library's own mask and to no snapshot that was stored before it existed
+            if (ix->visible_own) VS_HIP(hipMemsetAsync(ix->visible_own + n_old, 1, n_app, st));
+            for (int sn = 1; sn < VS_MAX_SNAPSHOTS; ++sn)
+                if (ix->snap[sn]) VS_HIP(hipMemsetAsync(ix->snap[sn] + n_old, 0, n_app, st));
+            VS_TRY(launch_row_norms_range(ix, n_old, n_app));  // (the codes come from the pages: nothing is quantized again)
+        }
+        VS_HIP(hipStreamSynchronize(st));
+        return follow_page_error(herr, what);  // (the check pass saw the same bytes: this does not happen)
+    };
+    const int rc = run();
+    if (rc != VS_OK) {
+        (void)hipStreamSynchronize(st);
+        if (new_val) (void)hipFree(new_val);
+        return rc;
+    }
+    if (new_val) {
+        if (ix->label_val) (void)hipFree(ix->label_val);
+        ix->label_val = new_val;
+        ix->n_label_vals = old_vals + add_vals;
+    }
+    ix->d.n = n;
+    // derived state, as vs_index_insert leaves it: the neighbor masks dropped, the label masks re-derived, the planner's memory reset
+    if (ix->nbr_mask) {
+        (void)hipFree(ix->nbr_mask);
+        ix->nbr_mask = nullptr;
+    }
+    ix->nbr_mask_valid = false;
+    ix->nbr_mask_tried = false;
+    ix->obs = ScanObs{};
+    ix->last_fast = FastSig{};
+    ix->last_ins_limit = 0;
+    // the follower's table advances: the device already holds it
+    f->cnt.swap(f->s_cnt);
+    f->base.swap(f->s_base);
+    f->n = n;
+    f->staged = false;
+    if (info) *info = f->info;
+    if (f->labeled) VS_TRY(vs_refresh_label_masks(ix));
+    return VS_OK;
+}
+
+extern "C" int vs_pages_follow_apply(vs_pages_follow* f, const float* new_vecs, uint32_t vec_stride, vs_pages_follow_info* info) {
+    VS_REQUIRE(f, "vs_pages_follow_apply: null follower");
+    return vs_guard("vs_pages_follow_apply", [&] { return follow_apply_impl(f, new_vecs, vec_stride, info); });
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -7,6 +7,9 @@
 
 #include "../../include/vsgpu.h"
 
+// vs_pages_add's header checks over one page outside a reader -> the SbqNode items on it (0: a new page, another page type)
+extern "C" int vs_pages_header_items(const void* page, uint32_t page_size, uint32_t block, uint32_t* sbq_items);
+
 // The whole layout of the relation a vs_pages_out writes, fixed at open.
 struct PagesOutPlan {
     uint32_t page_size = VS_BLCKSZ;

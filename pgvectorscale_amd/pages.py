@@ -10,13 +10,18 @@ column (`vecs`, needed for rerank).  The MetaPage body (geometry, start nodes, t
 The way back is `PagesOut` (vs_pages_out_*): a device-resident index written out as the same relation, block range by block
 range — or, against a `PagesBase`, only the blocks that changed since it was last written (`delta` / `read_blocks` /
 `patch_file`) — and `encode_meta_page` next to `decode_meta_page`.
+
+`PagesFollower` (vs_pages_follow_*) is the opposite direction page by page: when something else writes the relation (a standby's
+WAL replay, the CPU extension's aminsert and vacuum), the blocks that changed are staged, checked on the device and scattered
+into the resident arrays; `dirty_blocks` is the bytewise page compare that finds them where nothing better names them.
 """
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
-from ._lib import HeapAttr, HeapInfo, IndexDesc, IndexHost, MetaLayout, MetaPage, NodeLayout, PagesInfo, PagesOutParams, check
+from ._lib import (HeapAttr, HeapInfo, IndexDesc, IndexHost, MetaLayout, MetaPage, NodeLayout, PagesFollowInfo, PagesInfo, PagesOutParams,
+                   check)
 
 BLCKSZ = 8192
 PAGE_SBQ_MEANS, PAGE_META = 7, 8
@@ -190,6 +195,14 @@ class IndexPages:
         b, o = C.c_uint32(), C.c_uint32()
         check(self._L.vs_pages_item_pointer_of(self.h, node, C.byref(b), C.byref(o)))
         return int(b.value), int(o.value)
+
+    def block_table(self):
+        """-> (blk_base, blk_cnt): dense id of every block's first node, SbqNode items on every block (copies)"""
+        return _block_table(self._L.vs_pages_block_table, self.h)
+
+    def follower(self, index, layout=None):
+        """a PagesFollower of `index` (staged from these pages) that starts at this relation's block table"""
+        return PagesFollower(index, self.block_table()[1], layout=layout, page_size=self.page_size)
 
     def read_chain(self, block, offset, page_type):
         n = C.c_size_t()
@@ -398,10 +411,106 @@ class DevicePages:
         self.info = info
         return DiskAnnIndex(self.ctx, out)
 
+    def block_table(self):
+        """-> (blk_base, blk_cnt) as IndexPages.block_table; the host-side table outlives build()"""
+        return _block_table(self._L.vs_pages_dev_block_table, self.h)
+
+    def follower(self, index, layout=None):
+        """a PagesFollower of `index` (built from these pages) that starts at this relation's block table"""
+        return PagesFollower(index, self.block_table()[1], layout=layout, page_size=self.page_size)
+
     def close(self):
         if self.h:
             self._L.vs_pages_dev_close(self.h)
             self.h = None
+
+
+def _block_table(fn, handle):
+    pb, pc, nb = C.c_void_p(), C.c_void_p(), C.c_uint32()
+    check(fn(handle, C.byref(pb), C.byref(pc), C.byref(nb)))
+    n = int(nb.value)
+    if n == 0:
+        return np.zeros(0, np.uint32), np.zeros(0, np.uint32)
+    as_u32 = lambda p: np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), (n,)).copy()
+    return as_u32(pb), as_u32(pc)
+
+
+def dirty_blocks(old_bytes, new_bytes, page_size=BLCKSZ):
+    """the blocks of new_bytes that are not, byte for byte, what old_bytes holds at the same place (every block past its end
+    included), ascending uint32: what a PagesFollower.stage takes when nothing better (WAL records, the writer's own list)
+    names the changed pages"""
+    old = np.frombuffer(old_bytes, np.uint8)
+    new = np.frombuffer(new_bytes, np.uint8)
+    if old.size % page_size or new.size % page_size:
+        raise ValueError(f"not a whole number of {page_size}-byte pages")
+    nb_old, nb_new = old.size // page_size, new.size // page_size
+    both = min(nb_old, nb_new)
+    diff = (old[:both * page_size].reshape(both, page_size) != new[:both * page_size].reshape(both, page_size)).any(1)
+    return np.concatenate([np.flatnonzero(diff), np.arange(both, nb_new)]).astype(np.uint32)
+
+
+class PagesFollower:
+    """Brings a device-resident memory_optimized index up to date from the blocks of its relation that something else changed
+    (vs_pages_follow_*): `stage` checks the listed pages on the device and reports what they would do, `new_tids` names the heap
+    tuples of the appended nodes (HeapColumn reads their vectors), `apply` scatters.  The start nodes and the quantizer are not
+    read from block 0: decode the MetaPage (decode_meta_page) and call set_start_nodes / set_quantizer after the apply."""
+
+    def __init__(self, index, blk_cnt, layout=None, page_size=BLCKSZ):
+        self._L = index._L
+        self.index = index
+        self.page_size = page_size
+        lay = None if layout is None else NodeLayout(*layout)
+        cnt = np.ascontiguousarray(blk_cnt, np.uint32)
+        h = C.c_void_p()
+        check(self._L.vs_pages_follow_open(index.h, page_size, None if lay is None else C.byref(lay), cnt.ctypes.data_as(C.c_void_p),
+                                           cnt.size, C.byref(h)))
+        self.h = h
+        self._n_appended = None  # rows the staged list appends (None: nothing is staged)
+
+    def stage(self, blocks, pages, n_blocks_total):
+        """blocks: strictly ascending block numbers; pages: their bytes as they are now, in list order -> info dict"""
+        b = np.ascontiguousarray(blocks, np.uint32)
+        buf = np.frombuffer(pages, np.uint8)
+        if buf.size != b.size * self.page_size:
+            raise ValueError(f"{buf.size} bytes for {b.size} blocks of {self.page_size} bytes")
+        info = PagesFollowInfo()
+        self._n_appended = None
+        check(self._L.vs_pages_follow_stage(self.h, b.ctypes.data_as(C.c_void_p), buf.ctypes.data_as(C.c_void_p), b.size, n_blocks_total,
+                                            C.byref(info)))
+        self._n_appended = int(info.n_appended)
+        return info.as_dict()
+
+    def new_tids(self):
+        out = np.empty(self._n_appended or 0, np.uint64)
+        check(self._L.vs_pages_follow_new_tids(self.h, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    def apply(self, new_vecs=None):
+        """new_vecs [n_appended][dim_full] float32: required when the index holds the vector column and rows are appended"""
+        info = PagesFollowInfo()
+        v = None if new_vecs is None else np.ascontiguousarray(new_vecs, np.float32).reshape(-1, np.shape(new_vecs)[-1])
+        if v is not None and self._n_appended is not None and v.shape[0] != self._n_appended:
+            raise ValueError(f"{v.shape[0]} vectors for {self._n_appended} appended rows")
+        check(self._L.vs_pages_follow_apply(self.h, None if v is None else v.ctypes.data_as(C.c_void_p), 0 if v is None else v.shape[1],
+                                            C.byref(info)))
+        self._n_appended = None
+        self.index._refresh()
+        return info.as_dict()
+
+    def discard(self):
+        check(self._L.vs_pages_follow_discard(self.h))
+        self._n_appended = None
+
+    def close(self):
+        if self.h:
+            self._L.vs_pages_follow_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class PagesBase:
