@@ -596,8 +596,25 @@ typedef struct vs_pages_out_params {
 } vs_pages_out_params;
 /* fixes the whole layout: info->n_blocks is the relation's size, the other fields are what a reader of the result reports.
  * The index's arrays, start nodes and quantizer must not change until vs_pages_out_close.  VS_ERR_INVALID for an index of
- * another storage type or without codes / neighbors. */
+ * another storage type (a `plain` index goes through vs_pages_out_open_plain) or without codes / neighbors. */
 int vs_pages_out_open(vs_index* idx, const vs_pages_out_params* p, vs_pages_out** out, vs_pages_info* info);
+/* The writer-side twin of vs_pages_open_plain: a `plain` index (VS_STORAGE_PLAIN) written out as the relation the reference's
+ * ambuild leaves behind for plain storage — block 0 = Meta chain (storage_type 0, quantizer_metadata invalid, has_labels 0, start
+ * nodes None while default_start is VS_INVALID_NODE, else the node's ItemPointer without labeled entries), NO SbqMeans chain, then
+ * from block 1 on the PlainNode items (AM/plain/node.rs:15-22) in node order on PageType::Node pages filled by the Tape rule; the
+ * first node page exists even for an index of zero rows (vs_index_alloc makes one: 2 blocks).  An item is the dim_index floats of
+ * PlainNode.vector, the empty pq_vector, num_neighbors ItemPointers and the archived root: 4 * dim_index + 8 * num_neighbors +
+ * root_size bytes for every node, so node -> (block, offset) is arithmetic.  PlainNode.vector is the first dim_index floats of the
+ * row in the vector column, for cosine divided by the divisor of that slice where it has one (preprocess_cosine, as the plain
+ * scans apply it).  p->node_layout: NULL = vs_plain_layout_default (off_bq_vector names the vector field; off_labels is ignored,
+ * the pq_vector field takes the lowest free 8-byte slot of the root).  The node pages are composed on the device
+ * (k_pages_encode_plain).  The handle is an ordinary vs_pages_out: every call below works on it unchanged, and it counts among the
+ * index's open writers.  info is what vs_pages_open_plain + vs_pages_finish report for the written bytes (words = dim_index,
+ * pages_by_type[VS_PAGE_NODE]).  It makes no difference whether vs_index_alloc or vs_index_upload made the index.
+ * VS_ERR_INVALID, nothing written and no writer opened: an SBQ index (vs_pages_out_open writes those), an index without vector
+ * column / neighbor lists / heap tids, a cosine index without the divisor cache, page_size != VS_BLCKSZ, an item that does not
+ * fit a fresh page (with the default layout and 50 neighbor slots: more than 1930 dimensions). */
+int vs_pages_out_open_plain(vs_index* idx, const vs_pages_out_params* p, vs_pages_out** out, vs_pages_info* info);
 /* blocks first_block .. first_block + n_blocks - 1 into the host buffer `pages`: any range, in any order, any number of
  * times, always the same bytes (stream to a file or to smgrextend in chunks of the caller's choosing) */
 int vs_pages_out_read(vs_pages_out* w, uint32_t first_block, uint32_t n_blocks, void* pages);
@@ -957,7 +974,7 @@ int vs_sbq_quantize_corpus(vs_index* idx);
  * inner-product distance (DistanceWithTieBreak::new asserts distance >= 0, which -dot violates: the reference has no behaviour to
  * mirror; IP search on an uploaded plain index is unaffected), label sets, or a missing vector column — the index is left byte
  * for byte as it was.  Still refused for plain storage, unchanged: vs_index_consolidate_deletes, vs_index_repair_labels,
- * vs_pages_out_open. */
+ * vs_pages_follow_open (a plain index is written back with vs_pages_out_open_plain, not vs_pages_out_open). */
 int vs_build_graph(vs_index* idx, uint32_t search_list_size, double max_alpha, uint32_t batch_max, uint64_t seed);
 /* nodes the last vs_build_graph could not make reachable from the default start node (its repair pass gives every such
  * node an in-edge where that strands nobody else; 0 on well-formed input, 0xFFFFFFFF = graph deeper than the pass can judge).
@@ -985,14 +1002,15 @@ uint32_t vs_index_build_unreachable(const vs_index* idx);
  * and searches, pruning, back-edges and the batch's mates score with the pair distance of vs_build_graph's plain form (mates by
  * (key of d(row -> other), id)); vs_insert_stats is filled the same way.  VS_ERR_INVALID, the index left byte for byte as it was,
  * for a plain index whose distance is the inner product (see vs_build_graph), that is handed label sets, or that came from
- * vs_index_upload: such an index mirrors a relation, vs_pages_out_open cannot write plain storage back, and rows inserted on the
- * device alone would never reach it — only plain indexes made with vs_index_alloc take rows (vs_build_graph takes both).  VS_ERR_STATE: the
- * quantizer of an SBQ index is untrained (count == 0), a view of the index is alive, a batch is in flight, or a caller-owned device visibility
+ * vs_index_upload: such an index mirrors a relation; the refusal predates vs_pages_out_open_plain, which writes plain storage
+ * back, and lifting it is follow-up work — only plain indexes made with vs_index_alloc take rows (vs_build_graph takes both).  VS_ERR_STATE: the
+ * quantizer of an SBQ index is untrained (count == 0), a view of the index is alive, a batch is in flight, a vs_pages_out writer of the
+ * index is open (SBQ and plain alike: the insert may move the arrays it points into), or a caller-owned device visibility
  * mask (vs_index_set_visibility_dev) is in force — the library cannot grow it; clear or replace it first.  New rows are visible
  * (1) in the library's own mask and invisible (0) in every stored snapshot mask: a snapshot taken before the insert cannot see the
  * tuple.  An insert changes n and may MOVE every array: open vs_scans, scan pools (vs_scanpool_*, whose prefetched round must have
  * been settled — no pool call in flight) and brokers of the index must be ended or rescanned afterwards, pointers taken with
- * vs_index_array asked for again, and a writer opened with vs_pages_out_open closed first; vs_pages_out_* afterwards writes the
+ * vs_index_array asked for again, and a writer opened with vs_pages_out_open / _open_plain closed first; vs_pages_out_* afterwards writes the
  * grown relation.  Not thread safe against any other call on the index.
  * The refusals above (and a growth that fails) leave the index exactly as it was.  An error AFTER the rows were staged — device
  * memory running out for the batch buffers, VS_ERR_CAPACITY from a batch's searches, a HIP error — cannot be undone, because

@@ -271,6 +271,7 @@ SYMBOLS = {
     "vs_pages_follow_discard": (_i, [_vp]),
     "vs_pages_follow_close": (None, [_vp]),
     "vs_pages_out_open": (_i, [_vp, C.POINTER(PagesOutParams), C.POINTER(_vp), C.POINTER(PagesInfo)]),
+    "vs_pages_out_open_plain": (_i, [_vp, C.POINTER(PagesOutParams), C.POINTER(_vp), C.POINTER(PagesInfo)]),
     "vs_pages_out_read": (_i, [_vp, _u32, _u32, _vp]),
     "vs_pages_out_read_dev": (_i, [_vp, _u32, _u32, _vp]),
     "vs_pages_out_item_pointer_of": (_i, [_vp, _u32, C.POINTER(_u32), C.POINTER(_u32)]),

@@ -1741,10 +1741,10 @@ static int index_insert_impl(vs_index* ix, const float* vectors, bool vectors_on
         VS_REQUIRE(!label_off && !ix->label_off, "%s: Plain storage does not support label filters", what);
         PlainVecs pv;
         VS_TRY(plain_pair_args(ix, what, &pv));
-        // an uploaded plain index mirrors a relation that cannot be written back (vs_pages_out_open refuses plain storage): rows
-        // inserted here would exist on the device alone
-        VS_REQUIRE(!ix->uploaded, "%s: plain storage is not supported for an uploaded index (the page writer cannot write the rows back); "
-                   "plain indexes allocated on the device (vs_index_alloc) take rows", what);
+        // an uploaded plain index mirrors a relation: the refusal predates vs_pages_out_open_plain, which can write the rows back now;
+        // lifting it (and testing an insert into a staged relation) is follow-up work
+        VS_REQUIRE(!ix->uploaded, "%s: an uploaded plain index does not take rows yet (vs_pages_out_open_plain writes plain storage back; "
+                   "inserting into a staged relation is follow-up work); plain indexes allocated on the device (vs_index_alloc) take rows", what);
     }
     VS_REQUIRE(n_new == 0 || (vectors && heap_tids), "%s: vectors / heap_tids are NULL", what);
     VS_REQUIRE(L >= 1 && L <= 1000, "%s: search_list_size outside [1,1000]", what);
@@ -1770,6 +1770,9 @@ static int index_insert_impl(vs_index* ix, const float* vectors, bool vectors_on
     };
     if (!plain && ix->count == 0) return state_error("the quantizer is untrained (vs_sbq_train / vs_index_set_quantizer first; an insert never trains)");
     if (ix->ws.pending) return state_error("a batch of this handle is in flight (vs_search_batch_dev_finish first)");
+    // an insert may move every array an open writer (vs_pages_out_open / _open_plain) holds pointers into
+    if (vs_index_open_writers(ix) > 0)
+        return state_error("a vs_pages_out writer of this index is open (its layout and array pointers were fixed at open; vs_pages_out_close first)");
     if (ix->visible && ix->visible != ix->visible_own) {
         bool ours = false;
         for (const uint8_t* sp : ix->snap) ours |= sp == ix->visible;

@@ -1244,42 +1244,54 @@ void vs_pages_out_host_delta(const PagesOutPlan& plan, const vs_pages_base& base
     }
 }
 
-int vs_pages_out_plan(const vs_index_desc& d, const vs_pages_out_params& p, const float* mean, const float* m2, uint64_t count,
-                      const uint32_t* label_off, const int16_t* ls_labels, const uint32_t* ls_nodes, PagesOutPlan& plan) {
-    if (p.page_size != VS_BLCKSZ) return fail("vs_pages_out_open: page_size %u (the writer lays out %u-byte pages)", p.page_size, VS_BLCKSZ);
-    if (d.words == 0 || d.num_neighbors == 0) return fail("vs_pages_out_open: an index of %u code words and %u neighbor slots", d.words, d.num_neighbors);
-    if (d.has_labels && !label_off) return fail("vs_pages_out_open: the index says has_labels but holds no label sets");
+// plain: PlainNode items (AM/plain/node.rs:15-22) instead of SbqNode items — W = num_dimensions_to_index floats where the code words
+// are, the always-empty pq_vector where the classic node's _neighbor_vectors is, PageType::Node pages, no SbqMeans chain, no labels
+static int pages_out_plan_impl(const char* what, bool plain, const vs_index_desc& d, const vs_pages_out_params& p, const float* mean,
+                               const float* m2, uint64_t count, const uint32_t* label_off, const int16_t* ls_labels, const uint32_t* ls_nodes,
+                               PagesOutPlan& plan) {
+    if (p.page_size != VS_BLCKSZ) return fail("%s: page_size %u (the writer lays out %u-byte pages)", what, p.page_size, VS_BLCKSZ);
+    if (plain) {
+        if (d.dim_index == 0 || d.num_neighbors == 0) return fail("%s: an index of %u dimensions and %u neighbor slots", what, d.dim_index, d.num_neighbors);
+        if (d.has_labels || d.n_label_starts) return fail("%s: plain storage carries no labels", what);
+    } else if (d.words == 0 || d.num_neighbors == 0) {
+        return fail("%s: an index of %u code words and %u neighbor slots", what, d.words, d.num_neighbors);
+    }
+    if (d.has_labels && !label_off) return fail("%s: the index says has_labels but holds no label sets", what);
     const char* ver = p.extension_version ? p.extension_version : "";
     if (strlen(ver) >= sizeof(vs_meta_page().extension_version_when_built))
-        return fail("vs_pages_out_open: extension_version of %zu bytes (at most 63)", strlen(ver));
+        return fail("%s: extension_version of %zu bytes (at most 63)", what, strlen(ver));
     try {
-        const uint32_t ps = p.page_size, n = d.n, W = d.words, R = d.num_neighbors;
+        const uint32_t ps = p.page_size, n = d.n, W = plain ? d.dim_index : d.words, R = d.num_neighbors;
         plan = PagesOutPlan();
+        plan.plain = plain;
         plan.page_size = ps;
         plan.n = n;
         plan.W = W;
         plan.R = R;
         plan.has_labels = d.has_labels != 0;
-        // node layout: three named fields and the slot of the fourth (labels, or the classic node's empty _neighbor_vectors)
+        // node layout: three named fields and the slot of the fourth (labels, or the classic node's empty _neighbor_vectors, or the
+        // plain node's empty pq_vector: off_labels of a plain layout is unused, the field always takes the lowest free slot)
         vs_node_layout lay;
         if (p.node_layout) lay = *p.node_layout;
+        else if (plain) vs_plain_layout_default(&lay);
         else vs_node_layout_default(plan.has_labels, &lay);
+        if (plain) lay.off_labels = 0xFFFFFFFFu;
         const uint32_t named[3] = {lay.off_heap_item_pointer, lay.off_bq_vector, lay.off_neighbor_index_pointers};
         auto fits = [&](uint32_t o) { return o <= lay.root_size && lay.root_size - o >= 8 && (o & 3) == 0; };
-        if (lay.root_size > 4096 || (lay.root_size & 3)) return fail("vs_pages_out_open: a %u-byte archived node", lay.root_size);
+        if (lay.root_size > 4096 || (lay.root_size & 3)) return fail("%s: a %u-byte archived node", what, lay.root_size);
         for (uint32_t o : named)
-            if (!fits(o)) return fail("vs_pages_out_open: field offset %u does not fit a %u-byte archived node", o, lay.root_size);
+            if (!fits(o)) return fail("%s: field offset %u does not fit a %u-byte archived node", what, o, lay.root_size);
         if (!fits(lay.off_labels)) {
-            if (plan.has_labels) return fail("vs_pages_out_open: the node layout has no labels field");
+            if (plan.has_labels) return fail("%s: the node layout has no labels field", what);
             lay.off_labels = 0xFFFFFFFFu;
             for (uint32_t o = 0; o + 8 <= lay.root_size && lay.off_labels == 0xFFFFFFFFu; o += 8)
                 if (o != named[0] && o != named[1] && o != named[2]) lay.off_labels = o;
-            if (lay.off_labels == 0xFFFFFFFFu) return fail("vs_pages_out_open: no room for the fourth field in a %u-byte archived node", lay.root_size);
+            if (lay.off_labels == 0xFFFFFFFFu) return fail("%s: no room for the fourth field in a %u-byte archived node", what, lay.root_size);
         }
         const uint32_t four[4] = {named[0], named[1], named[2], lay.off_labels};
         for (int a = 0; a < 4; a++)
             for (int b2 = a + 1; b2 < 4; b2++)
-                if (four[a] < four[b2] + 8 && four[b2] < four[a] + 8) return fail("vs_pages_out_open: fields at +%u and +%u of the archived node overlap", four[a], four[b2]);
+                if (four[a] < four[b2] + 8 && four[b2] < four[a] + 8) return fail("%s: fields at +%u and +%u of the archived node overlap", what, four[a], four[b2]);
         plan.lay = lay;
         vs_meta_layout ML;
         if (p.meta_layout) ML = *p.meta_layout;
@@ -1290,26 +1302,26 @@ int vs_pages_out_plan(const vs_index_desc& d, const vs_pages_out_params& p, cons
         const uint32_t special = ps - 8, fresh_free = ((special - kPageHeaderSize - 4) / 8) * 8;
         // block 0: the Meta chain (MetaPage::create stores the header and a first MetaPage here; both are rewritten below)
         const size_t meta0 = rel.new_page(VS_PAGE_META);
-        // the SbqMeans chain: to_bytes(SbqMeans {count, means, m2})
-        std::vector<uint8_t> means((size_t)8 * d.dim_index + 24, 0);
-        memcpy(means.data(), mean, (size_t)4 * d.dim_index);
-        if (m2) memcpy(means.data() + (size_t)4 * d.dim_index, m2, (size_t)4 * d.dim_index);
-        {
+        // the SbqMeans chain: to_bytes(SbqMeans {count, means, m2}); plain storage has no quantizer, its MetaPage points nowhere
+        uint32_t q_blk = kInvalidBlock, q_off = 0;
+        if (!plain) {
+            std::vector<uint8_t> means((size_t)8 * d.dim_index + 24, 0);
+            memcpy(means.data(), mean, (size_t)4 * d.dim_index);
+            if (m2) memcpy(means.data() + (size_t)4 * d.dim_index, m2, (size_t)4 * d.dim_index);
             uint8_t* r = means.data() + (size_t)8 * d.dim_index;
             memcpy(r, &count, 8);
             wr32(r + 8, (uint32_t)(int32_t)(-(int64_t)((size_t)8 * d.dim_index + 8)));
             wr32(r + 12, d.dim_index);
             wr32(r + 16, (uint32_t)(int32_t)((int64_t)4 * d.dim_index - (int64_t)((size_t)8 * d.dim_index + 16)));
             wr32(r + 20, d.dim_index);
+            rel.chain_write(VS_PAGE_SBQ_MEANS, rel.new_page(VS_PAGE_SBQ_MEANS), means, q_blk, q_off);
         }
-        uint32_t q_blk = 0, q_off = 0;
-        rel.chain_write(VS_PAGE_SBQ_MEANS, rel.new_page(VS_PAGE_SBQ_MEANS), means, q_blk, q_off);
-        // the SbqNode pages: Tape::new takes a page at once, Tape::write a new one when aligned free space < item size
+        // the node pages: Tape::new takes a page at once, Tape::write a new one when aligned free space < item size
         plan.first_node_block = rel.next_block;
-        const uint32_t body0 = 8 * W + 8 * R;
+        const uint32_t body0 = (plain ? 4 : 8) * W + 8 * R;
         if (!plan.has_labels) {
             plan.item_size = ((body0 + 3) & ~3u) + lay.root_size;
-            if (plan.item_size > fresh_free) return fail("vs_pages_out_open: a node item of %u bytes does not fit a page", plan.item_size);
+            if (plan.item_size > fresh_free) return fail("%s: a node item of %u bytes does not fit a page", what, plan.item_size);
             uint32_t lower = kPageHeaderSize, upper = special, k = 0;
             for (;;) {
                 const uint32_t space = upper - lower, fs = space < 4 ? 0 : space - 4;
@@ -1326,9 +1338,9 @@ int vs_pages_out_plan(const vs_index_desc& d, const vs_pages_out_params& p, cons
             plan.node_lpoff.resize(n);
             uint32_t lower = kPageHeaderSize, upper = special, page = 0;
             for (uint32_t i = 0; i < n; ++i) {
-                if (label_off[i + 1] < label_off[i]) return fail("vs_pages_out_open: label offsets decrease at node %u", i);
+                if (label_off[i + 1] < label_off[i]) return fail("%s: label offsets decrease at node %u", what, i);
                 const uint64_t body = (uint64_t)body0 + 2ull * (label_off[i + 1] - label_off[i]);
-                if (body + lay.root_size + 3 > fresh_free) return fail("vs_pages_out_open: the item of node %u does not fit a page", i);
+                if (body + lay.root_size + 3 > fresh_free) return fail("%s: the item of node %u does not fit a page", what, i);
                 const uint32_t size = (((uint32_t)body + 3) & ~3u) + lay.root_size;
                 const uint32_t space = upper - lower, fs = space < 4 ? 0 : space - 4;
                 if (fs - fs % 8 < size) {
@@ -1346,9 +1358,9 @@ int vs_pages_out_plan(const vs_index_desc& d, const vs_pages_out_params& p, cons
             plan.page_first.push_back(n);
             plan.n_label_vals = label_off[n];
         }
-        if ((uint64_t)plan.first_node_block + plan.n_node_pages + 64 >= kInvalidBlock) return fail("vs_pages_out_open: block number overflow");
+        if ((uint64_t)plan.first_node_block + plan.n_node_pages + 64 >= kInvalidBlock) return fail("%s: block number overflow", what);
         rel.next_block = plan.first_node_block + plan.n_node_pages;
-        rel.by_type[VS_PAGE_SBQ_NODE] = plan.n_node_pages;
+        rel.by_type[plain ? VS_PAGE_NODE : VS_PAGE_SBQ_NODE] = plan.n_node_pages;
         // MetaPage::store on the re-initialised block 0, start nodes and quantizer pointer now known
         vs_meta_page m;
         memset(&m, 0, sizeof m);
@@ -1359,7 +1371,7 @@ int vs_pages_out_plan(const vs_index_desc& d, const vs_pages_out_params& p, cons
         m.num_dimensions = d.dim_full;
         m.num_dimensions_to_index = d.dim_index;
         m.bq_num_bits_per_dimension = d.bits;
-        m.storage_type = 2;  // StorageType::SbqCompression
+        m.storage_type = plain ? 0 : 2;  // StorageType::Plain / StorageType::SbqCompression
         m.num_neighbors = R;
         m.search_list_size = p.search_list_size;
         m.max_alpha = p.max_alpha;
@@ -1386,14 +1398,23 @@ int vs_pages_out_plan(const vs_index_desc& d, const vs_pages_out_params& p, cons
         uint32_t b_, o_;
         rel.chain_write(VS_PAGE_META, meta0, std::vector<uint8_t>(header, header + 8), b_, o_);
         rel.chain_write(VS_PAGE_META, meta0, body, b_, o_);
-        if (b_ != 0 || o_ != 2) return fail("vs_pages_out_open: the MetaPage landed at (%u,%u)", b_, o_);
+        if (b_ != 0 || o_ != 2) return fail("%s: the MetaPage landed at (%u,%u)", what, b_, o_);
         plan.n_blocks = rel.next_block;
         for (int t = 0; t < 9; t++) plan.pages_by_type[t] = rel.by_type[t];
         plan.host_pages.swap(rel.pages);
         std::sort(plan.host_pages.begin(), plan.host_pages.end(), [](const auto& a, const auto& b2) { return a.first < b2.first; });
     } catch (const std::bad_alloc&) {
-        vs_set_error("vs_pages_out_open: out of host memory");
+        vs_set_error("%s: out of host memory", what);
         return VS_ERR_OOM;
     }
     return VS_OK;
+}
+
+int vs_pages_out_plan(const vs_index_desc& d, const vs_pages_out_params& p, const float* mean, const float* m2, uint64_t count,
+                      const uint32_t* label_off, const int16_t* ls_labels, const uint32_t* ls_nodes, PagesOutPlan& plan) {
+    return pages_out_plan_impl("vs_pages_out_open", false, d, p, mean, m2, count, label_off, ls_labels, ls_nodes, plan);
+}
+
+int vs_pages_out_plan_plain(const vs_index_desc& d, const vs_pages_out_params& p, PagesOutPlan& plan) {
+    return pages_out_plan_impl("vs_pages_out_open_plain", true, d, p, nullptr, nullptr, 0, nullptr, nullptr, nullptr, plan);
 }

@@ -1049,12 +1049,101 @@ struct PagesDigestArgs {
     uint32_t base_n_blocks, base_first_node_block, base_n_node_pages;
 };
 
+// ---- what k_pages_encode and k_pages_encode_plain share: everything about a node page that does not depend on what its items hold ----
+// PageInit + cnt x PageAddItemExtended as the header sees them (pd_lsn, pd_checksum, pd_flags, pd_prune_xid stay zero) and the
+// TsvPageOpaqueData special area; one thread, on the zeroed page
+__device__ __forceinline__ void page_out_header(uint8_t* pg, uint32_t cnt, uint32_t upper, uint32_t page_type) {
+    *reinterpret_cast<po_u32*>(pg + 12) = (24 + 4 * cnt) | (upper << 16);        // pd_lower, pd_upper
+    *reinterpret_cast<po_u32*>(pg + 16) = kOutSpecial | ((kOutPage | 4u) << 16);  // pd_special, pd_pagesize_version
+    *reinterpret_cast<po_u32*>(pg + kOutSpecial) = page_type | (0xAE24u << 16);
+}
+// the line pointer of item k (0-based): LP_NORMAL
+__device__ __forceinline__ void page_out_line_pointer(uint8_t* pg, uint32_t k, uint32_t lp_off, uint32_t size) {
+    *reinterpret_cast<po_u32*>(pg + 24 + 4 * k) = lp_off | (1u << 15) | (size << 17);
+}
+// One wave turns a neighbor row into the R ArchivedItemPointers at `nb` (8-byte aligned LDS): the list ends at the first
+// VS_INVALID_NODE, (InvalidBlockNumber, 0) from there on.  pointer_of(u) = the item pointer word of node u < n.  An id the index does
+// not have is written as an invalid pointer; the item's lowest such slot is the one reported (PO_NEIGHBOR at block blk, item item_no).
+template <class PointerOf>
+__device__ __forceinline__ void page_out_neighbors(const uint32_t* __restrict__ nrow, uint8_t* nb, uint32_t R, uint32_t n, uint32_t lane,
+                                                   uint32_t* __restrict__ err, uint32_t blk, uint32_t item_no, PointerOf&& pointer_of) {
+    bool ended = false;
+    for (uint32_t j0 = 0; j0 < R; j0 += 4 * WAVE) {
+        const uint32_t j = j0 + 4 * lane;
+        uint4 v = make_uint4(VS_INVALID_NODE, VS_INVALID_NODE, VS_INVALID_NODE, VS_INVALID_NODE);
+        if (j < R) v = *reinterpret_cast<const uint4*>(nrow + j);  // (rows are nbr_stride = a multiple of 16 ids: 64-byte aligned)
+        const uint32_t ids[4] = {v.x, v.y, v.z, v.w};
+        uint32_t fi = 4;  // first slot of this lane's four that ends the list (or lies past R)
+        for (int t = 3; t >= 0; --t)
+            if (j + t >= R || ids[t] == VS_INVALID_NODE) fi = (uint32_t)t;
+        const uint64_t enders = __ballot(fi < 4);
+        const uint32_t fl = enders ? (uint32_t)__builtin_ctzll(enders) : WAVE;
+        const uint32_t nvalid = ended ? 0u : (lane < fl ? 4u : (lane == fl ? fi : 0u));
+        uint32_t bad = 4;
+        for (int t = 3; t >= 0; --t)
+            if ((uint32_t)t < nvalid && ids[t] >= n) bad = (uint32_t)t;
+        const uint64_t bads = __ballot(bad < 4);
+        if (bads && lane == (uint32_t)__builtin_ctzll(bads)) page_error(err, PO_NEIGHBOR, blk, item_no, j + bad);
+        for (uint32_t t = 0; t < 4; ++t) {
+            if (j + t >= R) break;
+            uint64_t word = item_pointer_word(0xFFFFFFFFu, 0);
+            if (t < nvalid && ids[t] < n) word = pointer_of(ids[t]);
+            *reinterpret_cast<po_u64*>(nb + 8 * (j + t)) = word;
+        }
+        if (enders) ended = true;
+    }
+}
+// The way out of a finished page (after the workgroup's barrier).  DIGEST = false: 512 full-lane 16-byte stores into slot blockIdx.x
+// of `out`; true: the 128-bit digest of the page's bytes goes to dg.digest[block b] and, against a baseline, the dirty-byte rule to
+// dg.dirty[p] (red: 2 * kOutThreads / WAVE words of LDS).
+template <bool DIGEST>
+__device__ __forceinline__ void page_out_leave(const uint4* pg4, uint4* __restrict__ out, const PagesDigestArgs& dg, uint64_t* red, uint32_t b,
+                                               uint32_t p) {
+    const uint32_t tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    if (!DIGEST) {
+        uint4* dst = out + (size_t)blockIdx.x * (kOutPage / 16);
+        dst[tid] = pg4[tid];
+        dst[tid + kOutThreads] = pg4[tid + kOutThreads];
+        return;
+    }
+    uint64_t sa = 0, sb = 0;
+    for (uint32_t i = tid; i < kOutPage / 16; i += kOutThreads) {
+        const uint4 v = pg4[i];
+        digest_piece(i, (uint64_t)v.x | ((uint64_t)v.y << 32), (uint64_t)v.z | ((uint64_t)v.w << 32), sa, sb);
+    }
+    for (int m = 1; m < WAVE; m <<= 1) {
+        sa += __shfl_xor(sa, m);
+        sb += __shfl_xor(sb, m);
+    }
+    if (lane == 0) {
+        red[2 * wave] = sa;
+        red[2 * wave + 1] = sb;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        sa = sb = 0;
+        for (uint32_t w = 0; w < kOutThreads / WAVE; ++w) {
+            sa += red[2 * w];
+            sb += red[2 * w + 1];
+        }
+        dg.digest[2 * (size_t)b] = sa;
+        dg.digest[2 * (size_t)b + 1] = sb;
+        if (dg.dirty) {
+            // the byte rule for a node page: past the baseline's end, not a node page then, or other bytes
+            bool same = b < dg.base_n_blocks && b >= dg.base_first_node_block && b - dg.base_first_node_block < dg.base_n_node_pages;
+            if (same) same = dg.base_digest[2 * (size_t)b] == sa && dg.base_digest[2 * (size_t)b + 1] == sb;
+            dg.dirty[p] = same ? 0 : 1;
+        }
+    }
+}
+
 // DIGEST = false: the page leaves as 512 full-lane 16-byte stores (slot blockIdx.x of `out`); true: 16 bytes of digest leave instead.
 // page_list (may be null: pages page0, page0 + 1, ...): the node page of every workgroup; VS_INVALID_NODE = this slot is not a node page
 template <bool DIGEST>
 __global__ __launch_bounds__(kOutThreads) void k_pages_encode(PagesEncodeArgs a, uint32_t page0, const uint32_t* __restrict__ page_list,
                                                               uint4* __restrict__ out, PagesDigestArgs dg, uint32_t* __restrict__ err) {
     __shared__ uint4 pg4[kOutPage / 16];
+    __shared__ uint64_t red[2 * kOutThreads / WAVE];
     uint8_t* pg = reinterpret_cast<uint8_t*>(pg4);
     const uint32_t tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
     const uint32_t p = page_list ? page_list[blockIdx.x] : page0 + blockIdx.x;  // node page number: block first_node_block + p
@@ -1073,12 +1162,9 @@ __global__ __launch_bounds__(kOutThreads) void k_pages_encode(PagesEncodeArgs a,
     const uint32_t body0 = 8 * a.W + 8 * a.R;
     const uint32_t classic_step = (a.item_size + 7u) & ~7u;
     if (tid == 0) {
-        // PageInit + cnt x PageAddItemExtended: pd_lsn, pd_checksum, pd_flags, pd_prune_xid stay zero
         uint32_t upper = kOutSpecial;
         if (cnt) upper = a.has_labels ? (uint32_t)a.node_lpoff[first + cnt - 1] : kOutSpecial - cnt * classic_step;
-        *reinterpret_cast<po_u32*>(pg + 12) = (24 + 4 * cnt) | (upper << 16);        // pd_lower, pd_upper
-        *reinterpret_cast<po_u32*>(pg + 16) = kOutSpecial | ((kOutPage | 4u) << 16);  // pd_special, pd_pagesize_version
-        *reinterpret_cast<po_u32*>(pg + kOutSpecial) = (uint32_t)VS_PAGE_SBQ_NODE | (0xAE24u << 16);  // TsvPageOpaqueData
+        page_out_header(pg, cnt, upper, (uint32_t)VS_PAGE_SBQ_NODE);
     }
     for (uint32_t k = wave; k < cnt; k += kOutThreads / WAVE) {
         const uint32_t node = first + k;
@@ -1100,7 +1186,7 @@ __global__ __launch_bounds__(kOutThreads) void k_pages_encode(PagesEncodeArgs a,
             continue;
         }
         uint8_t* item = pg + lp_off;
-        if (lane == 0) *reinterpret_cast<po_u32*>(pg + 24 + 4 * k) = lp_off | (1u << 15) | (size << 17);  // LP_NORMAL
+        if (lane == 0) page_out_line_pointer(pg, k, lp_off, size);
         // bq_vector: code rows are code_stride (even) words, 16-byte aligned
         const uint64_t* crow = a.codes + (size_t)node * a.code_stride;
         for (uint32_t w = 2 * lane; w < a.W; w += 2 * WAVE) {
@@ -1110,41 +1196,13 @@ __global__ __launch_bounds__(kOutThreads) void k_pages_encode(PagesEncodeArgs a,
         }
         // neighbor_index_pointers: R slots, the list ends at the first VS_INVALID_NODE, (InvalidBlockNumber, 0) from there on
         const uint32_t* nrow = a.nbrs + (size_t)node * a.nbr_stride;  // nbr_stride is a multiple of 16: 64-byte aligned rows
-        uint8_t* nb = item + 8 * a.W;
-        bool ended = false;
-        for (uint32_t j0 = 0; j0 < a.R; j0 += 4 * WAVE) {
-            const uint32_t j = j0 + 4 * lane;
-            uint4 v = make_uint4(VS_INVALID_NODE, VS_INVALID_NODE, VS_INVALID_NODE, VS_INVALID_NODE);
-            if (j < a.R) v = *reinterpret_cast<const uint4*>(nrow + j);
-            const uint32_t ids[4] = {v.x, v.y, v.z, v.w};
-            uint32_t fi = 4;  // first slot of this lane's four that ends the list (or lies past R)
-            for (int t = 3; t >= 0; --t)
-                if (j + t >= a.R || ids[t] == VS_INVALID_NODE) fi = (uint32_t)t;
-            const uint64_t enders = __ballot(fi < 4);
-            const uint32_t fl = enders ? (uint32_t)__builtin_ctzll(enders) : WAVE;
-            const uint32_t nvalid = ended ? 0u : (lane < fl ? 4u : (lane == fl ? fi : 0u));
-            // an id the index does not have is written as an invalid pointer; the item's lowest such slot is the one reported
-            uint32_t bad = 4;
-            for (int t = 3; t >= 0; --t)
-                if ((uint32_t)t < nvalid && ids[t] >= a.n) bad = (uint32_t)t;
-            const uint64_t bads = __ballot(bad < 4);
-            if (bads && lane == (uint32_t)__builtin_ctzll(bads)) page_error(err, PO_NEIGHBOR, a.first_node_block + p, k + 1, j + bad);
-            for (uint32_t t = 0; t < 4; ++t) {
-                if (j + t >= a.R) break;
-                uint64_t word = item_pointer_word(0xFFFFFFFFu, 0);
-                if (t < nvalid && ids[t] < a.n) {
-                    const uint32_t u = ids[t];
-                    if (a.has_labels) {
-                        const uint32_t blk = a.node_block[u];
-                        word = item_pointer_word(blk, u - a.page_first[blk - a.first_node_block] + 1);
-                    } else {
-                        word = item_pointer_word(a.first_node_block + u / a.K, u % a.K + 1);
-                    }
-                }
-                *reinterpret_cast<po_u64*>(nb + 8 * (j + t)) = word;
+        page_out_neighbors(nrow, item + 8 * a.W, a.R, a.n, lane, err, a.first_node_block + p, k + 1, [&](uint32_t u) {
+            if (a.has_labels) {
+                const uint32_t blk = a.node_block[u];
+                return item_pointer_word(blk, u - a.page_first[blk - a.first_node_block] + 1);
             }
-            if (enders) ended = true;
-        }
+            return item_pointer_word(a.first_node_block + u / a.K, u % a.K + 1);
+        });
         // labels (ArchivedLabelSet = ArchivedVec<i16>)
         for (uint32_t j = lane; j < L; j += WAVE) *reinterpret_cast<po_u16*>(item + body0 + 2 * j) = (uint16_t)a.label_val[lo + j];
         // the archived root: heap_item_pointer and three ArchivedVec {i32 offset relative to the field, u32 len}
@@ -1173,43 +1231,127 @@ __global__ __launch_bounds__(kOutThreads) void k_pages_encode(PagesEncodeArgs a,
         }
     }
     __syncthreads();
-    if (!DIGEST) {
-        uint4* dst = out + (size_t)blockIdx.x * (kOutPage / 16);
-        dst[tid] = pg4[tid];
-        dst[tid + kOutThreads] = pg4[tid + kOutThreads];
-        return;
-    }
+    page_out_leave<DIGEST>(pg4, out, dg, red, a.first_node_block + p, p);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The same for `plain` storage (vs_pages_out_open_plain): PlainNode items (AM/plain/node.rs:15-22) on PageType::Node pages.  An item
+// is D = num_dimensions_to_index floats, the empty pq_vector, R ArchivedItemPointers and the archived root — 4D + 8R + root_size
+// bytes for every node, so K items fill a page and node -> (block, offset) is arithmetic, as for classic SBQ nodes.
+//
+// k_pages_encode_plain: k_pages_encode's grid, page list convention, error record and way out.  What differs is where the bytes are:
+// the vector is most of the page (3 KB of a 3.5 KB item at 768 dimensions, K = 2; K = 1 at 1536), so a wave per item would leave
+// three waves idle where it matters.  The vector copy runs over (item, 64 pieces of 16 bytes) units dealt to the four waves: one
+// unit is one item's divisor (wave-uniform, loaded once) and one 16-byte global load per lane — rows are vec_stride floats, a
+// multiple of 4, so 16-byte aligned; the piece that holds the last floats of an odd D is cut so that nothing is written past 4D.
+// Items are MAXALIGNed, not 16-byte aligned: the LDS side is two 8-byte stores per piece.  A 16-lane group of an 8-byte LDS store
+// meets 32 banks of 4 bytes; lanes 16 bytes apart would put lanes l and l + 8 on one bank, so lanes 8 .. 15 of every group store
+// their high half first and their low half second: each store of a group then covers the 32 banks once.
+// PlainNode.vector is the index slice of the row, for cosine divided by the slice's divisor where it has one (preprocess_cosine:
+// vnorm, or vnorm_idx when D < dim_full): the `/` of lds_preprocess_cosine, correctly rounded under this unit's compile flags.
+// Line pointer, neighbor pointers and the root stay a wave per item.
+// ---------------------------------------------------------------------------------------------------------------
+struct PagesEncodePlainArgs {
+    const float* vecs;
+    const float* vdiv;  // cosine: the divisor of every node's index slice (0 = leave the slice alone); else null
+    const uint32_t* nbrs;
+    const uint64_t* tids;
+    uint32_t vec_stride, nbr_stride;
+    uint32_t n, D, R;
+    uint32_t K, item_size;  // items per page, bytes per item
+    uint32_t first_node_block;
+    uint32_t root_size, o_heap, o_vec, o_nbr, o_pq;
+};
+
+template <bool DIGEST>
+__global__ __launch_bounds__(kOutThreads) void k_pages_encode_plain(PagesEncodePlainArgs a, uint32_t page0, const uint32_t* __restrict__ page_list,
+                                                                    uint4* __restrict__ out, PagesDigestArgs dg, uint32_t* __restrict__ err) {
+    __shared__ uint4 pg4[kOutPage / 16];
     __shared__ uint64_t red[2 * kOutThreads / WAVE];
-    uint64_t sa = 0, sb = 0;
-    for (uint32_t i = tid; i < kOutPage / 16; i += kOutThreads) {
-        const uint4 v = pg4[i];
-        digest_piece(i, (uint64_t)v.x | ((uint64_t)v.y << 32), (uint64_t)v.z | ((uint64_t)v.w << 32), sa, sb);
+    uint8_t* pg = reinterpret_cast<uint8_t*>(pg4);
+    const uint32_t tid = threadIdx.x, lane = tid & (WAVE - 1), wave = rfl(tid / WAVE);
+    const uint32_t p = page_list ? page_list[blockIdx.x] : page0 + blockIdx.x;  // node page number: block first_node_block + p
+    if (p == VS_INVALID_NODE) return;  // (the whole workgroup)
+    pg4[tid] = make_uint4(0, 0, 0, 0);
+    pg4[tid + kOutThreads] = make_uint4(0, 0, 0, 0);
+    const uint32_t first = p * a.K;
+    const uint32_t cnt = first < a.n ? min(a.K, a.n - first) : 0u;
+    __syncthreads();
+    const uint32_t root = 4 * a.D + 8 * a.R, size = root + a.root_size;
+    const uint32_t step = (a.item_size + 7u) & ~7u;
+    if (tid == 0) page_out_header(pg, cnt, kOutSpecial - cnt * step, (uint32_t)VS_PAGE_NODE);
+    // the layout was fixed at open: an item that is not where it was planned, or would run into the line pointers, is left out and
+    // reported (by the wave that owns the item), never written
+    auto planned = [&](uint32_t k, uint32_t& lp_off) {
+        const uint32_t used = (k + 1) * step;  // (size <= step: the item ends at or below the one above it)
+        lp_off = kOutSpecial - used;
+        return size == a.item_size && used <= kOutSpecial - 24 - 4 * cnt;
+    };
+    // the vectors: unit u = 64 pieces of item u / C
+    const uint32_t P = (a.D + 3) / 4, C = (P + WAVE - 1) / WAVE;
+    for (uint32_t u = wave; u < cnt * C; u += kOutThreads / WAVE) {
+        const uint32_t k = u / C, q = (u % C) * WAVE + lane;
+        uint32_t lp_off;
+        if (!planned(k, lp_off)) continue;
+        const uint32_t node = first + k;
+        const float s = a.vdiv ? a.vdiv[node] : 0.0f;
+        if (q >= P) continue;
+        float4 v = *reinterpret_cast<const float4*>(a.vecs + (size_t)node * a.vec_stride + 4 * q);
+        if (s != 0.0f) {
+            v.x = v.x / s;
+            v.y = v.y / s;
+            v.z = v.z / s;
+            v.w = v.w / s;
+        }
+        const uint32_t have = a.D - 4 * q;  // floats of this piece that belong to the vector (>= 1)
+        const bool hi_first = (lane & 8u) != 0;
+        uint8_t* dst = pg + lp_off + 16 * q;
+        for (int t = 0; t < 2; ++t) {
+            const bool hi = (t == 0) == hi_first;
+            const uint32_t f0 = __float_as_uint(hi ? v.z : v.x), f1 = __float_as_uint(hi ? v.w : v.y), at = hi ? 2u : 0u;
+            if (have >= at + 2) *reinterpret_cast<po_u64*>(dst + 4 * at) = (uint64_t)f0 | ((uint64_t)f1 << 32);
+            else if (have > at) *reinterpret_cast<po_u32*>(dst + 4 * at) = f0;
+        }
     }
-    for (int m = 1; m < WAVE; m <<= 1) {
-        sa += __shfl_xor(sa, m);
-        sb += __shfl_xor(sb, m);
-    }
-    if (lane == 0) {
-        red[2 * wave] = sa;
-        red[2 * wave + 1] = sb;
+    for (uint32_t k = wave; k < cnt; k += kOutThreads / WAVE) {
+        const uint32_t node = first + k;
+        uint32_t lp_off;
+        if (!planned(k, lp_off)) {
+            if (lane == 0) page_error(err, PO_LAYOUT, a.first_node_block + p, k + 1, node);
+            continue;
+        }
+        uint8_t* item = pg + lp_off;
+        if (lane == 0) page_out_line_pointer(pg, k, lp_off, size);
+        page_out_neighbors(a.nbrs + (size_t)node * a.nbr_stride, item + 4 * a.D, a.R, a.n, lane, err, a.first_node_block + p, k + 1,
+                           [&](uint32_t v) { return item_pointer_word(a.first_node_block + v / a.K, v % a.K + 1); });
+        // the archived root: heap_item_pointer and three ArchivedVec {i32 offset relative to the field, u32 len}; the empty pq_vector
+        // points at the end of the vector, where rkyv's serializer stood when it met it
+        if (lane < 4) {
+            uint32_t fld, w0, w1;
+            if (lane == 0) {
+                const uint64_t tid64 = a.tids[node];
+                fld = a.o_heap;
+                w0 = (uint32_t)(tid64 >> 16);
+                w1 = (uint32_t)(tid64 & 0xFFFFu);
+            } else if (lane == 1) {
+                fld = a.o_vec;
+                w0 = 0u - (root + fld);
+                w1 = a.D;
+            } else if (lane == 2) {
+                fld = a.o_nbr;
+                w0 = 4 * a.D - (root + fld);
+                w1 = a.R;
+            } else {
+                fld = a.o_pq;
+                w0 = 4 * a.D - (root + fld);
+                w1 = 0;
+            }
+            *reinterpret_cast<po_u32*>(item + root + fld) = w0;
+            *reinterpret_cast<po_u32*>(item + root + fld + 4) = w1;
+        }
     }
     __syncthreads();
-    if (tid == 0) {
-        sa = sb = 0;
-        for (uint32_t w = 0; w < kOutThreads / WAVE; ++w) {
-            sa += red[2 * w];
-            sb += red[2 * w + 1];
-        }
-        const uint32_t b = a.first_node_block + p;
-        dg.digest[2 * (size_t)b] = sa;
-        dg.digest[2 * (size_t)b + 1] = sb;
-        if (dg.dirty) {
-            // the byte rule for a node page: past the baseline's end, not a node page then, or other bytes
-            bool same = b < dg.base_n_blocks && b >= dg.base_first_node_block && b - dg.base_first_node_block < dg.base_n_node_pages;
-            if (same) same = dg.base_digest[2 * (size_t)b] == sa && dg.base_digest[2 * (size_t)b + 1] == sb;
-            dg.dirty[p] = same ? 0 : 1;
-        }
-    }
+    page_out_leave<DIGEST>(pg4, out, dg, red, a.first_node_block + p, p);
 }
 
 // The dirty node pages as an ascending list of block numbers.  Three passes, so that the order is the pages' own and not that of an
@@ -1265,6 +1407,7 @@ struct vs_pages_out {
     vs_ctx* ctx = nullptr;
     PagesOutPlan plan;
     PagesEncodeArgs args{};
+    PagesEncodePlainArgs plain_args{};  // plan.plain: what k_pages_encode_plain takes instead
     uint32_t* d_page_first = nullptr;
     uint32_t* d_node_block = nullptr;
     uint16_t* d_node_lpoff = nullptr;
@@ -1293,6 +1436,8 @@ extern "C" void vs_pages_out_close(vs_pages_out* w) {
     if (w->d_list) (void)hipFree(w->d_list);
     delete w;
 }
+
+static int pages_out_open_finish(vs_index* ix, vs_pages_out* w, vs_pages_info* info);
 
 static int pages_out_open_impl(vs_index* ix, const vs_pages_out_params* p, vs_pages_out* w, vs_pages_info* info) {
     vs_ctx* c = ix->ctx;
@@ -1328,13 +1473,6 @@ static int pages_out_open_impl(vs_index* ix, const vs_pages_out_params* p, vs_pa
         std::vector<uint32_t>().swap(plan.node_block);  // the host keeps page_first only (vs_pages_out_item_pointer_of)
         std::vector<uint16_t>().swap(plan.node_lpoff);
     }
-    w->chunk_pages = (uint32_t)std::min<size_t>(c->pinned_bytes / plan.page_size, std::max<uint32_t>(plan.n_node_pages, 1));
-    for (int i = 0; i < 2; ++i) {
-        VS_HIP(hipMalloc(&w->d_stage[i], (size_t)w->chunk_pages * plan.page_size));
-        VS_HIP(hipEventCreateWithFlags(&w->ev_done[i], hipEventDisableTiming));
-    }
-    VS_HIP(hipMalloc(&w->d_err, 32));
-    VS_HIP(hipMemsetAsync(w->d_err, 0, 32, c->stream));
     PagesEncodeArgs& a = w->args;
     a.codes = ix->codes;
     a.nbrs = ix->nbrs;
@@ -1358,6 +1496,21 @@ static int pages_out_open_impl(vs_index* ix, const vs_pages_out_params* p, vs_pa
     a.o_nbr = plan.lay.off_neighbor_index_pointers;
     a.o_last = plan.lay.off_labels;
     a.has_labels = plan.has_labels ? 1u : 0u;
+    return pages_out_open_finish(ix, w, info);
+}
+
+// what both opens end with, the plan made: the staging chunks, the error record, and what a reader of the result reports
+static int pages_out_open_finish(vs_index* ix, vs_pages_out* w, vs_pages_info* info) {
+    vs_ctx* c = ix->ctx;
+    const vs_index_desc& d = ix->d;
+    const PagesOutPlan& plan = w->plan;
+    w->chunk_pages = (uint32_t)std::min<size_t>(c->pinned_bytes / plan.page_size, std::max<uint32_t>(plan.n_node_pages, 1));
+    for (int i = 0; i < 2; ++i) {
+        VS_HIP(hipMalloc(&w->d_stage[i], (size_t)w->chunk_pages * plan.page_size));
+        VS_HIP(hipEventCreateWithFlags(&w->ev_done[i], hipEventDisableTiming));
+    }
+    VS_HIP(hipMalloc(&w->d_err, 32));
+    VS_HIP(hipMemsetAsync(w->d_err, 0, 32, c->stream));
     // n_deleted, as a reader of the result counts it
     uint32_t n_deleted = 0;
     if (d.n) {
@@ -1371,7 +1524,7 @@ static int pages_out_open_impl(vs_index* ix, const vs_pages_out_params* p, vs_pa
         memset(info, 0, sizeof *info);
         info->n_blocks = plan.n_blocks;
         info->n_nodes = d.n;
-        info->words = d.words;
+        info->words = plan.W;
         info->num_neighbors = d.num_neighbors;
         info->has_labels = plan.has_labels;
         info->n_deleted = n_deleted;
@@ -1386,13 +1539,67 @@ static int pages_out_open_impl(vs_index* ix, const vs_pages_out_params* p, vs_pa
 extern "C" int vs_pages_out_open(vs_index* ix, const vs_pages_out_params* p, vs_pages_out** out, vs_pages_info* info) {
     VS_REQUIRE(ix && p && out, "vs_pages_out_open: bad args");
     *out = nullptr;
-    VS_REQUIRE(ix->d.storage_type == VS_STORAGE_SBQ, "vs_pages_out_open: memory_optimized (SBQ) indexes only; writing `plain` storage is not supported");
+    VS_REQUIRE(ix->d.storage_type == VS_STORAGE_SBQ, "vs_pages_out_open: memory_optimized (SBQ) indexes only; a `plain` index is written with vs_pages_out_open_plain");
     VS_REQUIRE(ix->codes && ix->nbrs && ix->tids, "vs_pages_out_open: the index holds no codes / neighbors");
     return vs_guard("vs_pages_out_open", [&] {
         vs_pages_out* w = new vs_pages_out();
         w->ix = ix;
         w->ctx = ix->ctx;
         const int r = pages_out_open_impl(ix, p, w, info);
+        if (r != VS_OK) {
+            vs_pages_out_close(w);
+            return r;
+        }
+        w->owner_id = ix->owner_id;
+        vs_index_writer_opened(w->owner_id);
+        *out = w;
+        return (int)VS_OK;
+    });
+}
+
+static int pages_out_open_plain_impl(vs_index* ix, const vs_pages_out_params* p, vs_pages_out* w, vs_pages_info* info) {
+    vs_ctx* c = ix->ctx;
+    const vs_index_desc& d = ix->d;
+    VS_HIP(hipSetDevice(c->device));
+    VS_REQUIRE(c->pinned_bytes >= p->page_size, "vs_pages_out_open_plain: the context's staging buffers (%zu bytes) do not hold one page", c->pinned_bytes);
+    VS_TRY(vs_pages_out_plan_plain(d, *p, w->plan));
+    const PagesOutPlan& plan = w->plan;
+    PagesEncodePlainArgs& a = w->plain_args;
+    a.vecs = ix->vecs;
+    a.vdiv = d.distance_type == VS_COSINE ? (d.dim_index < d.dim_full ? ix->vnorm_idx : ix->vnorm) : nullptr;
+    a.nbrs = ix->nbrs;
+    a.tids = ix->tids;
+    a.vec_stride = ix->vec_stride;
+    a.nbr_stride = ix->nbr_stride;
+    a.n = d.n;
+    a.D = d.dim_index;
+    a.R = d.num_neighbors;
+    a.K = plan.K;
+    a.item_size = plan.item_size;
+    a.first_node_block = plan.first_node_block;
+    a.root_size = plan.lay.root_size;
+    a.o_heap = plan.lay.off_heap_item_pointer;
+    a.o_vec = plan.lay.off_bq_vector;
+    a.o_nbr = plan.lay.off_neighbor_index_pointers;
+    a.o_pq = plan.lay.off_labels;
+    return pages_out_open_finish(ix, w, info);
+}
+
+extern "C" int vs_pages_out_open_plain(vs_index* ix, const vs_pages_out_params* p, vs_pages_out** out, vs_pages_info* info) {
+    VS_REQUIRE(ix && p && out, "vs_pages_out_open_plain: bad args");
+    *out = nullptr;
+    VS_REQUIRE(ix->d.storage_type == VS_STORAGE_PLAIN, "vs_pages_out_open_plain: `plain` indexes only; a memory_optimized (SBQ) index is written with "
+               "vs_pages_out_open");
+    VS_REQUIRE(ix->vecs && ix->nbrs && ix->tids, "vs_pages_out_open_plain: the index holds no vector column / neighbors / heap tids");
+    VS_REQUIRE(ix->d.distance_type != VS_COSINE || (ix->d.dim_index < ix->d.dim_full ? ix->vnorm_idx : ix->vnorm),
+               "vs_pages_out_open_plain: the index has no divisors for its index slices (vs_index_refresh_norms)");
+    VS_REQUIRE(ix->vec_stride % 4 == 0 && ix->d.dim_index <= ix->d.dim_full, "vs_pages_out_open_plain: vector rows of %u floats for %u dimensions",
+               ix->vec_stride, ix->d.dim_index);
+    return vs_guard("vs_pages_out_open_plain", [&] {
+        vs_pages_out* w = new vs_pages_out();
+        w->ix = ix;
+        w->ctx = ix->ctx;
+        const int r = pages_out_open_plain_impl(ix, p, w, info);
         if (r != VS_OK) {
             vs_pages_out_close(w);
             return r;
@@ -1413,8 +1620,12 @@ extern "C" int vs_pages_out_item_pointer_of(const vs_pages_out* w, uint32_t node
 static int launch_pages_encode(vs_pages_out* w, uint32_t p0, const uint32_t* d_list, uint32_t np, void* d_out) {
     vs_ctx* c = w->ctx;
     hipEvent_t ev = prof_begin(c);
-    hipLaunchKernelGGL((k_pages_encode<false>), dim3(np), dim3(kOutThreads), 0, c->stream, w->args, p0, d_list, reinterpret_cast<uint4*>(d_out),
-                       PagesDigestArgs{}, w->d_err);
+    if (w->plan.plain)
+        hipLaunchKernelGGL((k_pages_encode_plain<false>), dim3(np), dim3(kOutThreads), 0, c->stream, w->plain_args, p0, d_list,
+                           reinterpret_cast<uint4*>(d_out), PagesDigestArgs{}, w->d_err);
+    else
+        hipLaunchKernelGGL((k_pages_encode<false>), dim3(np), dim3(kOutThreads), 0, c->stream, w->args, p0, d_list, reinterpret_cast<uint4*>(d_out),
+                           PagesDigestArgs{}, w->d_err);
     VS_HIP(hipGetLastError());
     prof_end(c, PK_PAGES, ev);
     return VS_OK;
@@ -1427,6 +1638,7 @@ static int pages_out_check(vs_pages_out* w) {
     if (herr[0] == PO_OK) return VS_OK;
     VS_HIP(hipMemset(w->d_err, 0, 16));
     if (herr[0] == PO_NEIGHBOR) vs_set_error("block %u item %u: neighbor slot %u names a node the index does not have", herr[1], herr[2], herr[3]);
+    else if (w->plan.plain) vs_set_error("block %u item %u (node %u): the item does not lie where vs_pages_out_open_plain planned it", herr[1], herr[2], herr[3]);
     else vs_set_error("block %u item %u (node %u): the label sets changed after vs_pages_out_open fixed the layout", herr[1], herr[2], herr[3]);
     return VS_ERR_INVALID;
 }
@@ -1596,8 +1808,12 @@ static int pages_out_digest_impl(vs_pages_out* w, const char* what, const vs_pag
             dg.base_first_node_block = base ? base->first_node_block : 0;
             dg.base_n_node_pages = base ? base->n_node_pages : 0;
             hipEvent_t ev = prof_begin(c);
-            hipLaunchKernelGGL((k_pages_encode<true>), dim3(np), dim3(kOutThreads), 0, c->stream, w->args, 0u, (const uint32_t*)nullptr,
-                               (uint4*)nullptr, dg, w->d_err);
+            if (plan.plain)
+                hipLaunchKernelGGL((k_pages_encode_plain<true>), dim3(np), dim3(kOutThreads), 0, c->stream, w->plain_args, 0u,
+                                   (const uint32_t*)nullptr, (uint4*)nullptr, dg, w->d_err);
+            else
+                hipLaunchKernelGGL((k_pages_encode<true>), dim3(np), dim3(kOutThreads), 0, c->stream, w->args, 0u, (const uint32_t*)nullptr,
+                                   (uint4*)nullptr, dg, w->d_err);
             VS_HIP(hipGetLastError());
             prof_end(c, PK_PAGES, ev);
             if (base) {

@@ -13,11 +13,13 @@ extern "C" int vs_pages_header_items(const void* page, uint32_t page_size, uint3
 // The whole layout of the relation a vs_pages_out writes, fixed at open.
 struct PagesOutPlan {
     uint32_t page_size = VS_BLCKSZ;
-    uint32_t n = 0, W = 0, R = 0;
+    uint32_t n = 0, W = 0, R = 0;  // plain: W = the dimensions of PlainNode.vector (num_dimensions_to_index)
     bool has_labels = false;
-    vs_node_layout lay{};        // off_labels = where the last 8-byte field goes (labels, or the empty _neighbor_vectors)
+    bool plain = false;          // PlainNode items on PageType::Node pages, no SbqMeans chain (vs_pages_out_plan_plain)
+    vs_node_layout lay{};        // off_labels = where the last 8-byte field goes (labels, the empty _neighbor_vectors, or a plain
+                                 // node's empty pq_vector)
     uint32_t first_node_block = 0, n_node_pages = 0, n_blocks = 0;
-    // classic nodes: every item has item_size bytes, K of them fill a page
+    // classic and plain nodes: every item has item_size bytes, K of them fill a page
     uint32_t item_size = 0, K = 0;
     // labeled nodes: first node of every node page (n_node_pages + 1 entries, the last one = n) and, until the device half has
     // taken them over, block and lp_off of every node's item
@@ -34,6 +36,8 @@ struct PagesOutPlan {
 // labeled start nodes (d.n_label_starts entries, node ids)
 int vs_pages_out_plan(const vs_index_desc& d, const vs_pages_out_params& p, const float* mean, const float* m2, uint64_t count,
                       const uint32_t* label_off, const int16_t* ls_labels, const uint32_t* ls_nodes, PagesOutPlan& plan);
+// the same for a `plain` index (vs_pages_out_open_plain): Meta chain on block 0, node pages from block 1 on
+int vs_pages_out_plan_plain(const vs_index_desc& d, const vs_pages_out_params& p, PagesOutPlan& plan);
 int vs_pages_out_plan_item_pointer(const PagesOutPlan& plan, uint32_t node, uint32_t* block, uint32_t* offset);
 
 // What a relation looked like when it was last written (vs_pages_out_baseline / vs_pages_out_delta): one 128-bit digest per block

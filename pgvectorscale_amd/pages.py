@@ -538,15 +538,20 @@ class PagesBase:
 
 
 class PagesOut:
-    """A device-resident memory_optimized index written out as the pages of a `diskann` index relation (vs_pages_out_*): the
-    layout is fixed here, `read` hands out any block range any number of times.  layout: a vs_node_layout 5-tuple (root size, heap
-    pointer, code, neighbors, labels / fourth field), meta_layout: a dict as oracle/pages_py.meta_layout() gives."""
+    """A device-resident index written out as the pages of a `diskann` index relation (vs_pages_out_*): the layout is fixed here,
+    `read` hands out any block range any number of times.  layout: a vs_node_layout 5-tuple (root size, heap pointer, code,
+    neighbors, labels / fourth field), meta_layout: a dict as oracle/pages_py.meta_layout() gives.  plain=True: a `plain` storage
+    index (vs_pages_out_open_plain; PlainNode items, as IndexPages(plain=True) reads them) — layout is then a plain-layout tuple
+    (root size, heap pointer, vector, neighbors, unused)."""
 
     def __init__(self, index, extension_version="0.8.0", search_list_size=100, max_alpha=1.2, layout=None, meta_layout=None,
-                 page_size=BLCKSZ):
+                 page_size=BLCKSZ, plain=False):
         self._L = index._L
         self.index = index
         self.page_size = page_size
+        self.plain = bool(plain)
+        if layout is not None and plain:
+            layout = tuple(0xFFFFFFFF if v is None else v for v in layout)
         self._lay = None if layout is None else NodeLayout(*layout)
         self._mlay = _meta_layout(meta_layout)
         p = PagesOutParams()
@@ -556,7 +561,8 @@ class PagesOut:
         p.extension_version = extension_version.encode()
         p.search_list_size, p.max_alpha = search_list_size, max_alpha
         h, info = C.c_void_p(), PagesInfo()
-        check(self._L.vs_pages_out_open(index.h, C.byref(p), C.byref(h), C.byref(info)))
+        opener = self._L.vs_pages_out_open_plain if plain else self._L.vs_pages_out_open
+        check(opener(index.h, C.byref(p), C.byref(h), C.byref(info)))
         self.h = h
         self.info = info
         self.n_blocks = int(info.n_blocks)

@@ -27,8 +27,17 @@ the full read by roughly the ratio of blocks moved.
 the label sets only), so that the labeled open pass can be timed at a size whose build would take minutes:
 
     python scripts/bench_pages_write.py --open-only --n 50000000 --labels 32 --append --out profiles/r09/s1_pages_write_4m.txt
+
+--plain writes a `plain` storage index instead (vs_pages_out_open_plain, k_pages_encode_plain; default 1M x 768, R = 50): legs (a)
+and (b) only, as GB/s of pages produced.  The index is not built: its neighbor rows are filled with random node ids, full lists,
+because what the writer does with a row does not depend on which nodes it names.  Run it next to the SBQ mode at the same --n in
+one session to compare the two page rates:
+
+    python scripts/bench_pages_write.py --n 1000000 --out out/pages_write_1m.txt
+    python scripts/bench_pages_write.py --plain --append --out out/pages_write_1m.txt
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -155,9 +164,75 @@ def delta_leg(P, PagesOut, ctx, ix, out, dbuf, host, a, say):
                 full_read_ms=[round(x * 1e3, 1) for x in tf], bytes_identical=same)
 
 
+def plain_leg(P, PagesOut, ctx, a, say):
+    """--plain (module docstring) -> the result dict"""
+    from pgvectorscale_amd import _lib
+    from pgvectorscale_amd.datagen import DatagenParams, fill_device
+    n = a.n
+    ix = P.DiskAnnIndex.alloc(ctx, n=n, dim_full=a.dim, num_neighbors=a.R, distance_type=P.VS_COSINE if a.cosine else P.VS_L2,
+                              storage_type=_lib.VS_STORAGE_PLAIN)
+    vp, vec_stride = ix.array(_lib.ARR_VECS)
+    fill_device(ctx, DatagenParams(seed=8, dim=a.dim), 0, n, vp)
+    ix.refresh_norms()
+    ctx.upload(ix.array(_lib.ARR_TIDS)[0], ((np.arange(n, dtype=np.uint64) + 1) << np.uint64(16)) | np.uint64(1))
+    np_ptr, nbr_stride = ix.array(_lib.ARR_NBRS)
+    rng = np.random.default_rng(13)
+    step = 1 << 18
+    for r0 in range(0, n, step):  # rows of nbr_stride ids: R random nodes, the sentinel behind them
+        rows = np.full((min(step, n - r0), nbr_stride), 0xFFFFFFFF, np.uint32)
+        rows[:, :a.R] = rng.integers(0, n, (rows.shape[0], a.R), dtype=np.uint32)
+        ctx.upload(C.c_void_p(np_ptr.value + r0 * nbr_stride * 4), rows)
+    ix.set_start_nodes(0, {})
+    ctx.sync()
+    t0 = time.perf_counter()
+    out = PagesOut(ix, search_list_size=a.build_list, plain=True)
+    t_open = time.perf_counter() - t0
+    nb, ps = out.n_blocks, out.page_size
+    node_pages = int(out.info.pages_by_type[1])
+    total = nb * ps
+    say(f"vs_pages_out_open_plain: {t_open * 1e3:.1f} ms; relation = {nb} blocks = {total / 1e9:.3f} GB, {node_pages} node pages, "
+        f"{n / max(node_pages, 1):.2f} nodes per page")
+    dbuf = ctx.alloc(total)
+    out.read_dev(dbuf)  # warm-up: code object load
+    ctx.profile_enable(True)
+    ctx.profile_read(reset=True)
+    k_ms = []
+    for _ in range(a.reps):
+        out.read_dev(dbuf)
+        ms, launches = ctx.profile_read(reset=True)["pages_encode"]
+        assert launches == 1
+        k_ms.append(ms)
+    ctx.profile_enable(False)
+    read_bytes = n * (4 * ((a.dim + 3) // 4 * 4) + 4 * a.R + 8 + (4 if a.cosine else 0))
+    written = node_pages * ps
+    kb = min(k_ms)
+    say(f"(a) k_pages_encode_plain, whole relation, one launch of {node_pages} workgroups: {' '.join(f'{x:.3f}' for x in k_ms)} ms; best {kb:.3f} ms = "
+        f"{written / kb / 1e6:.1f} GB/s of pages written; algorithmic bytes {read_bytes / 1e9:.3f} GB read + {written / 1e9:.3f} GB written = "
+        f"{(read_bytes + written) / kb / 1e6:.1f} GB/s = {(read_bytes + written) / (kb * 1e-3) / HBM_PEAK * 100:.1f} % of 8 TB/s")
+    host = np.zeros(total, np.uint8)
+    out.read(out=host)  # warm-up
+    composed = ctx.download(dbuf, np.empty(total, np.uint8))
+    same = bool((host == composed).all())
+    del composed
+    say(f"bytes of vs_pages_out_read == bytes composed in device memory: {same}")
+    tb = []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        out.read(out=host)
+        tb.append(time.perf_counter() - t0)
+    say(f"(b) vs_pages_out_read, whole relation to the host: {' '.join(f'{x * 1e3:.1f}' for x in tb)} ms; median {np.median(tb) * 1e3:.1f} ms = "
+        f"{total / np.median(tb) / 1e9:.2f} GB/s")
+    ctx.free(dbuf)
+    out.close()
+    ix.close()
+    return dict(plain=True, n=n, dim=a.dim, R=a.R, blocks=nb, node_pages=node_pages, open_ms=round(t_open * 1e3, 1),
+                kernel_ms=[round(x, 3) for x in k_ms], kernel_gbs=round(written / kb / 1e6, 1), read_ms=[round(x * 1e3, 1) for x in tb],
+                read_gbs=round(total / np.median(tb) / 1e9, 2), bytes_identical=same)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--n", type=int, default=4_000_000)
+    ap.add_argument("--n", type=int, default=None, help="default 4 000 000 (1 000 000 with --plain)")
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--bits", type=int, default=0, help="0 = the reference's default for the dimension")
     ap.add_argument("--R", type=int, default=50)
@@ -169,7 +244,12 @@ def main():
     ap.add_argument("--append", action="store_true")
     ap.add_argument("--delta", action="store_true", help="add the baseline / bulk_delete / insert / delta + read_blocks leg")
     ap.add_argument("--open-only", action="store_true", help="time vs_pages_out_open on an allocated, unbuilt index and stop")
+    ap.add_argument("--plain", action="store_true", help="a `plain` storage index through vs_pages_out_open_plain: legs (a) and (b)")
     a = ap.parse_args()
+    if a.n is None:
+        a.n = 1_000_000 if a.plain else 4_000_000
+    if a.plain and (a.labels or a.delta or a.open_only):
+        ap.error("--plain goes with neither --labels, --delta nor --open-only")
 
     import pgvectorscale_amd as P
     from pgvectorscale_amd import _lib
@@ -190,6 +270,13 @@ def main():
 
     ctx = P.Context(0)
     dist = P.VS_COSINE if a.cosine else P.VS_L2
+    if a.plain:
+        say(f"# pages write, plain storage: n={a.n} dim={a.dim} R={a.R} on {ctx.device_name()}")
+        res = plain_leg(P, PagesOut, ctx, a, say)
+        say(json.dumps(res))
+        ctx.close()
+        flush()
+        return 0 if res["bytes_identical"] else 1
     if a.open_only:
         say(f"# pages write, open only: n={a.n} dim={a.dim} R={a.R} labels={a.labels} on {ctx.device_name()}")
         ix = P.DiskAnnIndex.alloc(ctx, n=a.n, dim_full=a.dim, bits=a.bits or None, num_neighbors=a.R, distance_type=dist, with_vecs=False)
