@@ -273,9 +273,10 @@ int vs_index_bulk_delete_dev(vs_index* idx, const uint64_t* d_dead_tids_sorted, 
  * What it does not do: it never reclaims a tombstone's node (n and the page layout stay, D rows keep their bytes, so their pages
  * stay clean for vs_pages_out_delta; vs_index_compact below is the call that reclaims them); it does not re-elect a deleted start node (it stays in K with a clean list); it gives no
  * guarantee for label-filtered reachability beyond what Graph::insert gives (vs_index_label_reach audits it, vs_index_repair_labels repairs it).
- * Refusals leave every byte as it was: VS_ERR_INVALID for plain storage, an index without codes / neighbor lists / heap tids, a
+ * Refusals leave every byte as it was: VS_ERR_INVALID for plain storage (vs_index_consolidate_deletes_plain below is the call
+ * for it), an index without codes / neighbor lists / heap tids, a
  * node with more than 64 labels, max_alpha outside [1,5], a bad cand_max or unknown flags; VS_ERR_STATE while a view of the index
- * is alive, a batch of this handle is in flight, or a writer opened with vs_pages_out_open has not been closed.  n does not change
+ * is alive, a batch of this handle is in flight, or a writer opened with vs_pages_out_open / _open_plain has not been closed.  n does not change
  * and no array moves, but open vs_scans, scan pools and brokers of the index must be ended or rescanned afterwards: their device
  * state names rows that changed.  Not thread safe against any other call on the index; ordered on the context's stream.
  * An error after the first rewritten row (a HIP error, memory running out for the repair pass) leaves a usable graph: every row
@@ -296,8 +297,23 @@ typedef struct vs_consolidate_stats {
 } vs_consolidate_stats;
 int vs_index_consolidate_deletes(vs_index* idx, double max_alpha, uint32_t cand_max /* 0 = default */, uint32_t flags,
                                  vs_consolidate_stats* out /* may be NULL */);
+/* The same pass over a `plain` index (VS_STORAGE_PLAIN): the same K and D, the same candidates one level deep, the same cut to
+ * cand_max (same default, same bound), the same counters, the same repair pass and flag.  The one difference is the distance: the
+ * candidates of row p are sorted ascending by (key of d(p -> w), id), d the full-precision pair distance vs_build_graph scores a
+ * plain index with (p's prepared index slice is the query side, w's raw row the row side; keys order like f32::total_cmp), and
+ * pruned with that distance ("plain storage").  A plain index has no labels, so there is no label rule.
+ * Only neighbor lists are written.  Indexes made with vs_index_alloc, vs_index_upload or from pages are taken alike: a mirrored
+ * relation stays writable with vs_pages_out_open_plain.  The cosine divisors of the rows are recomputed from the vector column
+ * first, as vs_build_graph does (a derived cache, not a byte of the index).
+ * Refusals leave every byte as it was: VS_ERR_INVALID for an SBQ index (vs_index_consolidate_deletes is the call for it), an
+ * index the pair distance cannot score (the inner-product distance, no vector column on the device, a cosine index with dim_index
+ * < dim_full that holds no divisors of its index slices), an index without neighbor lists / heap tids, max_alpha outside [1,5], a
+ * bad cand_max, unknown flags, or a num_neighbors / cand_max / dim_index whose LDS layout exceeds 160 KiB; VS_ERR_STATE for a view
+ * handle, live views, a batch in flight, or an open writer of either kind.  Everything else said above holds unchanged. */
+int vs_index_consolidate_deletes_plain(vs_index* idx, double max_alpha, uint32_t cand_max /* 0 = default */, uint32_t flags,
+                                       vs_consolidate_stats* out /* may be NULL */);
 /* HIP-event milliseconds of the two passes on this index since the last reset, collected while vs_profile_enable is on:
- * ms[0] the flag pass (node classes, flags, work list), ms[1] k_consolidate_rows */
+ * ms[0] the flag pass (node classes, flags, work list), ms[1] k_consolidate_rows (either form) */
 int vs_index_consolidate_kernel_ms(vs_index* idx, double* ms, int reset);
 /* ---- compaction: the tombstones leave the arrays and the nodes are renumbered in place (after the consolidation above) --------
  * The last step of delete -> consolidate -> compact -> insert into the freed room.  Node ids are internal: what leaves the boundary
@@ -311,7 +327,7 @@ int vs_index_consolidate_kernel_ms(vs_index* idx, double* ms, int reset);
  *      (a plain index has no codes).
  *   4. A neighbor row handles its entries in list order: an entry v becomes new_of[v]; an entry with v in D is removed and the list
  *      closes up, order preserved; the row is padded to its stride with VS_INVALID_NODE.  CONSOLIDATE FIRST: after
- *      vs_index_consolidate_deletes with its repair no K row names a D node, nothing is cut and every list is a pure rename.
+ *      vs_index_consolidate_deletes (on a plain index: vs_index_consolidate_deletes_plain) with its repair no K row names a D node, nothing is cut and every list is a pure rename.
  *      Without it the cut is legal but the edges are simply lost — nothing takes over the dropped node's neighbors, rows may end
  *      up empty (rows_emptied) and live rows unreachable.  With VS_COMPACT_KEEP_EDGES_CHECK a first read-only pass counts edges_cut
  *      and the call returns VS_ERR_STATE with every byte as it was when it is not 0.
@@ -973,8 +989,9 @@ int vs_sbq_quantize_corpus(vs_index* idx);
  * search_list_size outside [1,1000], a max_alpha outside [1,5], a node with more than 64 labels, and on a plain index for the
  * inner-product distance (DistanceWithTieBreak::new asserts distance >= 0, which -dot violates: the reference has no behaviour to
  * mirror; IP search on an uploaded plain index is unaffected), label sets, or a missing vector column — the index is left byte
- * for byte as it was.  Still refused for plain storage, unchanged: vs_index_consolidate_deletes, vs_index_repair_labels,
- * vs_pages_follow_open (a plain index is written back with vs_pages_out_open_plain, not vs_pages_out_open). */
+ * for byte as it was.  Still refused for plain storage, unchanged: vs_pages_follow_open, and the SBQ forms of calls that have a
+ * plain one (vs_index_consolidate_deletes: a plain index is consolidated with vs_index_consolidate_deletes_plain; vs_pages_out_open:
+ * it is written back with vs_pages_out_open_plain).  vs_index_repair_labels does not apply: plain storage has no labels. */
 int vs_build_graph(vs_index* idx, uint32_t search_list_size, double max_alpha, uint32_t batch_max, uint64_t seed);
 /* nodes the last vs_build_graph could not make reachable from the default start node (its repair pass gives every such
  * node an in-edge where that strands nobody else; 0 on well-formed input, 0xFFFFFFFF = graph deeper than the pass can judge).
@@ -1003,7 +1020,8 @@ uint32_t vs_index_build_unreachable(const vs_index* idx);
  * (key of d(row -> other), id)); vs_insert_stats is filled the same way.  VS_ERR_INVALID, the index left byte for byte as it was,
  * for a plain index whose distance is the inner product (see vs_build_graph), that is handed label sets, or that came from
  * vs_index_upload: such an index mirrors a relation; the refusal predates vs_pages_out_open_plain, which writes plain storage
- * back, and lifting it is follow-up work — only plain indexes made with vs_index_alloc take rows (vs_build_graph takes both).  VS_ERR_STATE: the
+ * back, and lifting it is follow-up work — only plain indexes made with vs_index_alloc take rows (vs_build_graph and
+ * vs_index_consolidate_deletes_plain take both).  VS_ERR_STATE: the
  * quantizer of an SBQ index is untrained (count == 0), a view of the index is alive, a batch is in flight, a vs_pages_out writer of the
  * index is open (SBQ and plain alike: the insert may move the arrays it points into), or a caller-owned device visibility
  * mask (vs_index_set_visibility_dev) is in force — the library cannot grow it; clear or replace it first.  New rows are visible

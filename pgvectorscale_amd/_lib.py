@@ -230,6 +230,7 @@ SYMBOLS = {
     "vs_index_bulk_delete": (_i, [_vp, _vp, _u64, C.POINTER(BulkDeleteStats)]),
     "vs_index_bulk_delete_dev": (_i, [_vp, _vp, _u64, C.POINTER(BulkDeleteStats)]),
     "vs_index_consolidate_deletes": (_i, [_vp, C.c_double, _u32, _u32, C.POINTER(ConsolidateStats)]),
+    "vs_index_consolidate_deletes_plain": (_i, [_vp, C.c_double, _u32, _u32, C.POINTER(ConsolidateStats)]),
     "vs_index_consolidate_kernel_ms": (_i, [_vp, C.POINTER(C.c_double), _i]),
     "vs_index_compact": (_i, [_vp, C.c_uint64, _u32, _vp, C.POINTER(CompactStats)]),
     "vs_index_compact_kernel_ms": (_i, [_vp, C.POINTER(C.c_double), _i]),

@@ -2097,6 +2097,8 @@ extern "C" int vs_index_bulk_delete_dev(vs_index* ix, const uint64_t* d_dead_tid
 // Every row of K that names a node of D is rewritten from { its entries in K } + { the entries in K of the rows of its D
 // entries }, one level deep, sorted by (Hamming to the row's node, id), cut to cand_max and pruned like any other candidate
 // list.  Rows of D are never written and rows of K read only their own list and lists of D nodes: the pass runs in place.
+// vs_index_consolidate_deletes_plain: the same pass over a `plain` index, "Hamming" read as the PlainPair distance d(p -> w) —
+// sorted by (plain_key(d), id), pruned with wave_prune<PlainPair>; no labels.  One implementation (consolidate_impl), two entries.
 // ---------------------------------------------------------------------------------------------------------------
 enum { CN_TOMB = 0, CN_KEPT, CN_EDGES_DROPPED, CN_EDGES_ADDED, CN_PRUNED, CN_CAPPED, CN_EMPTIED, CN_WIDE_LABELS, CN_N = 8 };
 
@@ -2187,7 +2189,8 @@ __global__ __launch_bounds__(256) void k_cons_work_scatter(const uint8_t* __rest
 
 // LDS of k_consolidate_rows (bytes): two key lists of cap entries (the merge writes one from the other), the keys of the rows being
 // gathered, the arrays wave_prune works on, and the code rows — of the <= R rows in flight while merging, of the surviving
-// candidates while pruning (the same area; cap > R)
+// candidates while pruning (the same area; cap > R).  The plain form has no code rows and no label masks: the area behind gid[]
+// holds one prepared vector of round_up(dim_index, 4) floats (cons_lds_plain).
 struct ConsLds {
     uint32_t cap4, R4, code_rows;
     size_t bytes;
@@ -2200,14 +2203,25 @@ static ConsLds cons_lds(uint32_t cap, uint32_t R, uint32_t stride, bool labeled,
     l.bytes = (size_t)l.cap4 * (16 + (labeled ? 8 : 0) + 12) + (size_t)l.R4 * (8 + 16) + (size_t)l.code_rows * stride * 8;
     return l;
 }
+static ConsLds cons_lds_plain(uint32_t cap, uint32_t R, uint32_t dim) {
+    ConsLds l = cons_lds(cap, R, 0, false, false, false);
+    l.bytes += (size_t)round_up_u32(dim, 4) * 4;
+    return l;
+}
 
 // one wave per work-list entry p
+// PLAIN: keys are (plain_key(d(p -> w)) << 32) | w with the PlainPair distance — p's prepared index slice is the staged query side
+// of every merge of the work item, eight lanes score one gathered row straight from global memory (a gathered row is read once
+// per merge, so there is no stage_rows / use_lds_codes choice) — and the prune is wave_prune<PlainPair>.  That prune overwrites
+// the staged vector with each candidate it selects: every key of a work item is finished before it, and p is staged again at the
+// top of every iteration of the grid-stride loop.
+template <bool PLAIN>
 __global__ __launch_bounds__(WAVE) void k_consolidate_rows(const uint64_t* __restrict__ codes, uint32_t stride, uint32_t* nbrs,
                                                            uint32_t nbr_stride, uint32_t R, uint32_t n, float max_alpha, uint32_t cap,
                                                            const uint32_t* __restrict__ work, uint32_t nwork,
                                                            const uint8_t* __restrict__ cls, uint32_t use_lds_codes, uint32_t stage_rows,
                                                            const uint32_t* __restrict__ label_off, const int16_t* __restrict__ label_val,
-                                                           unsigned long long* __restrict__ cnt) {
+                                                           unsigned long long* __restrict__ cnt, PlainVecs pv) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
     const uint64_t below = (1ull << lane) - 1ull;
@@ -2223,17 +2237,19 @@ __global__ __launch_bounds__(WAVE) void k_consolidate_rows(const uint64_t* __res
     uint32_t* oldrow = sel + R4;                                // [R4] p's list as it was
     uint32_t* tomb = oldrow + R4;                               // [R4] its entries in D
     uint32_t* gid = tomb + R4;                                  // [R4] ids of the rows being gathered
-    uint64_t* ccode = reinterpret_cast<uint64_t*>(gid + R4);
+    uint64_t* ccode = reinterpret_cast<uint64_t*>(gid + R4);    // (PLAIN: the prepared vector qv[round_up(dim, 4)])
+    PlainPair ppd{pv.vecs, pv.vdiv, cid, reinterpret_cast<float*>(ccode), pv.vec_stride, pv.dim, pv.distance_type};
     for (uint32_t wi = blockIdx.x; wi < nwork; wi += gridDim.x) {
         const uint32_t p = work[wi];
         uint32_t* row = nbrs + (size_t)p * nbr_stride;
+        if constexpr (PLAIN) ppd.stage(p, lane);  // (the prune of the work item before left its last selected candidate there)
         const uint64_t* cp = codes + (size_t)p * stride;
         ulonglong2 pc[12];  // p's code (768 x 2 bit / 1536 x 1 bit): every distance of this row is taken against it
-        if (stride == 24) {
+        if (!PLAIN && stride == 24) {
 #pragma unroll
             for (int t = 0; t < 12; ++t) pc[t] = *reinterpret_cast<const ulonglong2*>(cp + 2 * t);
         }
-        auto dist_to_p = [&](const uint64_t* c) -> uint32_t {
+        [[maybe_unused]] auto dist_to_p = [&](const uint64_t* c) -> uint32_t {  // (the SBQ form's distance)
             if (stride != 24) return ham_words(c, cp, stride);
             ulonglong2 x[12];
 #pragma unroll
@@ -2250,13 +2266,23 @@ __global__ __launch_bounds__(WAVE) void k_consolidate_rows(const uint64_t* __res
         // gid[0 .. ng) -> keys, each new id once, merged into the sorted list cur[0 .. T), the closest `cap` kept
         auto merge_gathered = [&](uint32_t ng) {
             if (ng == 0) return;  // (uniform)
-            if (stage_rows) {  // the rows' codes in flight together, not one latency per candidate
-                stage_codes(ccode, codes, gid, ng, stride, lane);
-                __syncthreads();
-            }
-            for (uint32_t t = lane; t < ng; t += WAVE) {
-                const uint32_t id = gid[t];
-                inc[t] = ((uint64_t)dist_to_p(stage_rows ? ccode + (size_t)t * stride : codes + (size_t)id * stride) << 32) | id;
+            if constexpr (PLAIN) {
+                for (uint32_t t0 = 0; t0 < ng; t0 += WAVE / 8) {  // (uniform trip count: dist() is a call of the whole wave)
+                    const uint32_t t = t0 + (uint32_t)lane / 8;
+                    const bool act = t < ng;
+                    const uint32_t id = act ? gid[t] : 0u;
+                    const float d = ppd.dist(id, act, lane);
+                    if (act && (lane & 7) == 0) inc[t] = ((uint64_t)plain_key(d) << 32) | id;
+                }
+            } else {
+                if (stage_rows) {  // the rows' codes in flight together, not one latency per candidate
+                    stage_codes(ccode, codes, gid, ng, stride, lane);
+                    __syncthreads();
+                }
+                for (uint32_t t = lane; t < ng; t += WAVE) {
+                    const uint32_t id = gid[t];
+                    inc[t] = ((uint64_t)dist_to_p(stage_rows ? ccode + (size_t)t * stride : codes + (size_t)id * stride) << 32) | id;
+                }
             }
             __syncthreads();
             for (uint32_t t = lane; t < ng; t += WAVE) {  // an equal key is a duplicate (the distance is a function of the id)
@@ -2349,6 +2375,8 @@ __global__ __launch_bounds__(WAVE) void k_consolidate_rows(const uint64_t* __res
             for (uint32_t t = lane; t < T; t += WAVE) sel[t] = t;
             nres = T;
             __syncthreads();
+        } else if constexpr (PLAIN) {
+            nres = wave_prune(ppd, cd, T, R, max_alpha, maxf, sel, lane);
         } else {
             if (use_lds_codes) {
                 stage_codes(ccode, codes, cid, T, stride, lane);
@@ -2378,14 +2406,24 @@ __global__ __launch_bounds__(WAVE) void k_consolidate_rows(const uint64_t* __res
     }
 }
 
-static int consolidate_impl(vs_index* ix, double max_alpha, uint32_t cand_max, uint32_t flags, vs_consolidate_stats* out) {
-    const char* what = "vs_index_consolidate_deletes";
+// plain: the call is vs_index_consolidate_deletes_plain — a plain storage index, keys and prune by the PlainPair distance
+static int consolidate_impl(vs_index* ix, double max_alpha, uint32_t cand_max, uint32_t flags, vs_consolidate_stats* out, bool plain) {
+    const char* what = plain ? "vs_index_consolidate_deletes_plain" : "vs_index_consolidate_deletes";
     VS_REQUIRE(ix, "%s: index is NULL", what);
     if (out) memset(out, 0, sizeof(*out));
     VS_REQUIRE_OWNER(ix, what);
     VS_REQUIRE_NO_VIEWS(ix, what);
-    VS_REQUIRE(ix->d.storage_type == VS_STORAGE_SBQ, "%s: plain storage is not supported (memory_optimized indexes only)", what);
-    VS_REQUIRE(ix->codes && ix->nbrs && ix->tids, "%s: needs codes, neighbor lists and heap tids on the device", what);
+    PlainVecs pv{nullptr, nullptr, 0, 0, 0};
+    if (plain) {
+        VS_REQUIRE(ix->d.storage_type == VS_STORAGE_PLAIN,
+                   "%s: plain storage indexes only (vs_index_consolidate_deletes is the call for a memory_optimized index)", what);
+        VS_TRY(plain_pair_args(ix, what, &pv));
+        VS_REQUIRE(ix->nbrs && ix->tids, "%s: needs neighbor lists and heap tids on the device", what);
+    } else {
+        VS_REQUIRE(ix->d.storage_type == VS_STORAGE_SBQ,
+                   "%s: plain storage is not supported (memory_optimized indexes only; vs_index_consolidate_deletes_plain is the call for it)", what);
+        VS_REQUIRE(ix->codes && ix->nbrs && ix->tids, "%s: needs codes, neighbor lists and heap tids on the device", what);
+    }
     VS_REQUIRE(max_alpha >= 1.0 && max_alpha <= 5.0, "%s: max_alpha outside [1,5]", what);
     VS_REQUIRE((flags & ~(uint32_t)VS_CONSOLIDATE_NO_REPAIR) == 0, "%s: unknown flags 0x%x", what, flags);
     const uint32_t n = ix->d.n, R = ix->d.num_neighbors, stride = ix->code_stride;
@@ -2419,9 +2457,9 @@ static int consolidate_impl(vs_index* ix, double max_alpha, uint32_t cand_max, u
     VS_REQUIRE(starts.back() < n, "%s: start node %u of an index of %u nodes", what, starts.back(), n);
     const bool labeled = ix->label_off != nullptr;
     // the candidate codes sit in LDS while a row is pruned when they fit; failing that, at least the <= R rows a merge gathers
-    bool lds_codes = cons_lds(cand_max, R, stride, labeled, true, true).bytes <= 150 * 1024;
-    bool stage_rows = lds_codes || cons_lds(cand_max, R, stride, labeled, false, true).bytes <= 150 * 1024;
-    const ConsLds lds = cons_lds(cand_max, R, stride, labeled, lds_codes, stage_rows);
+    bool lds_codes = !plain && cons_lds(cand_max, R, stride, labeled, true, true).bytes <= 150 * 1024;
+    bool stage_rows = !plain && (lds_codes || cons_lds(cand_max, R, stride, labeled, false, true).bytes <= 150 * 1024);
+    const ConsLds lds = plain ? cons_lds_plain(cand_max, R, pv.dim) : cons_lds(cand_max, R, stride, labeled, lds_codes, stage_rows);
     VS_REQUIRE(lds.bytes <= 160 * 1024, "%s: num_neighbors %u / cand_max %u need %zu bytes of LDS", what, R, cand_max, lds.bytes);
     const uint32_t n_waves = (n + WAVE - 1) / WAVE;
     uint8_t *d_cls = nullptr, *d_flag = nullptr;
@@ -2454,6 +2492,10 @@ static int consolidate_impl(vs_index* ix, double max_alpha, uint32_t cand_max, u
         VS_HIP(hipMemcpyAsync(d_starts, starts.data(), starts.size() * 4, hipMemcpyHostToDevice, st));
         VS_HIP(hipMemsetAsync(d_cnt, 0, sizeof h_cnt, st));
         VS_HIP(hipMemsetAsync(d_flag, 0, (size_t)n, st));
+        if (plain) {  // the divisors the pair distance divides by, from the rows as they stand (as vs_build_graph derives them)
+            VS_TRY(launch_row_norms(ix));
+            VS_TRY(launch_slice_norms_range(ix, 0, n));
+        }
         tick();
         const dim3 ngrid((n + 255) / 256);
         hipLaunchKernelGGL(k_cons_classify, ngrid, dim3(256), 0, st, (const uint64_t*)ix->tids, (const uint32_t*)ix->label_off, n, d_cls, d_cnt);
@@ -2480,13 +2522,20 @@ static int consolidate_impl(vs_index* ix, double max_alpha, uint32_t cand_max, u
         }
         tock(0);
         if (nwork) {
-            VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_consolidate_rows), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            const void* kern = plain ? reinterpret_cast<const void*>(k_consolidate_rows<true>) : reinterpret_cast<const void*>(k_consolidate_rows<false>);
+            VS_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             ix->nbr_mask_valid = false;  // (the neighbor lists are about to change: what was derived from them is stale)
             tick();
-            hipLaunchKernelGGL(k_consolidate_rows, dim3(std::min<uint32_t>(nwork, 1u << 20)), dim3(WAVE), lds.bytes, st, (const uint64_t*)ix->codes,
-                               stride, ix->nbrs, ix->nbr_stride, R, n, (float)max_alpha, cand_max, (const uint32_t*)d_work, nwork,
-                               (const uint8_t*)d_cls, lds_codes ? 1u : 0u, stage_rows ? 1u : 0u, (const uint32_t*)ix->label_off,
-                               (const int16_t*)ix->label_val, d_cnt);
+            const dim3 rgrid(std::min<uint32_t>(nwork, 1u << 20));
+            if (plain)
+                hipLaunchKernelGGL(k_consolidate_rows<true>, rgrid, dim3(WAVE), lds.bytes, st, (const uint64_t*)nullptr, 0u, ix->nbrs, ix->nbr_stride,
+                                   R, n, (float)max_alpha, cand_max, (const uint32_t*)d_work, nwork, (const uint8_t*)d_cls, 0u, 0u,
+                                   (const uint32_t*)nullptr, (const int16_t*)nullptr, d_cnt, pv);
+            else
+                hipLaunchKernelGGL(k_consolidate_rows<false>, rgrid, dim3(WAVE), lds.bytes, st, (const uint64_t*)ix->codes, stride, ix->nbrs,
+                                   ix->nbr_stride, R, n, (float)max_alpha, cand_max, (const uint32_t*)d_work, nwork, (const uint8_t*)d_cls,
+                                   lds_codes ? 1u : 0u, stage_rows ? 1u : 0u, (const uint32_t*)ix->label_off, (const int16_t*)ix->label_val,
+                                   d_cnt, pv);
             VS_HIP(hipGetLastError());
             tock(1);
             VS_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
@@ -2524,7 +2573,11 @@ static int consolidate_impl(vs_index* ix, double max_alpha, uint32_t cand_max, u
     return rc;
 }
 extern "C" int vs_index_consolidate_deletes(vs_index* ix, double max_alpha, uint32_t cand_max, uint32_t flags, vs_consolidate_stats* out) {
-    return vs_guard("vs_index_consolidate_deletes", [&] { return consolidate_impl(ix, max_alpha, cand_max, flags, out); });
+    return vs_guard("vs_index_consolidate_deletes", [&] { return consolidate_impl(ix, max_alpha, cand_max, flags, out, false); });
+}
+extern "C" int vs_index_consolidate_deletes_plain(vs_index* ix, double max_alpha, uint32_t cand_max, uint32_t flags,
+                                                  vs_consolidate_stats* out) {
+    return vs_guard("vs_index_consolidate_deletes_plain", [&] { return consolidate_impl(ix, max_alpha, cand_max, flags, out, true); });
 }
 extern "C" int vs_index_consolidate_kernel_ms(vs_index* ix, double* ms /*[2]*/, int reset) {
     VS_REQUIRE(ix && ms, "vs_index_consolidate_kernel_ms: bad args");

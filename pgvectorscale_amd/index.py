@@ -305,15 +305,17 @@ class DiskAnnIndex:
         check(self._L.vs_index_bulk_delete_dev(self.h, d_dead_tids_sorted, n_dead, C.byref(st)))
         return st.as_dict()
 
-    def consolidate_deletes(self, max_alpha=1.2, cand_max=0, repair=True):
+    def consolidate_deletes(self, max_alpha=1.2, cand_max=0, repair=True, plain=False):
         """vs_index_consolidate_deletes (after bulk_delete): every kept row that names a deleted node takes over that node's
         neighbors and is pruned again; the tombstones leave the graph (not the arrays).  cand_max 0 = min(4 * num_neighbors, 256).
-        repair=False stops after the row rewrite.  Open scans, pools and brokers of the index must be rescanned afterwards.
+        repair=False stops after the row rewrite.  plain=True: vs_index_consolidate_deletes_plain, the call for a `plain` storage
+        index (as write_pages(plain=True); the storage type picks nothing by itself).  Open scans, pools and brokers of the index
+        must be rescanned afterwards.
         -> dict of vs_consolidate_stats"""
         st = _lib.ConsolidateStats()
+        call = self._L.vs_index_consolidate_deletes_plain if plain else self._L.vs_index_consolidate_deletes
         try:
-            check(self._L.vs_index_consolidate_deletes(self.h, max_alpha, cand_max, 0 if repair else _lib.VS_CONSOLIDATE_NO_REPAIR,
-                                                       C.byref(st)))
+            check(call(self.h, max_alpha, cand_max, 0 if repair else _lib.VS_CONSOLIDATE_NO_REPAIR, C.byref(st)))
         finally:
             self._refresh()
         return st.as_dict()
