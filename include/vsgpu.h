@@ -552,8 +552,8 @@ int vs_pages_dev_block_table(const vs_pages_dev* d, const uint32_t** blk_base, c
  * lists in place at unchanged item size and clears heap offsets in place: node ids (SbqNode items on earlier blocks + offset - 1)
  * are stable.  The rule, checked on the page headers: a listed block's item count may not shrink; it may grow only on a block
  * behind which no block held nodes in the old table; every block in [n_blocks_before, n_blocks_total) must be listed (all-zero
- * and non-node pages count 0 items); n_blocks_total < n_blocks_before is refused.  memory_optimized (SBQ) indexes, classic and
- * labeled nodes; a plain index is refused (VS_ERR_INVALID).
+ * and non-node pages count 0 items); n_blocks_total < n_blocks_before is refused.  vs_pages_follow_open: memory_optimized (SBQ)
+ * indexes, classic and labeled nodes; it refuses a plain index (VS_ERR_INVALID), which vs_pages_follow_open_plain follows.
  * NOT read from the pages: the start nodes and the quantizer.  Block 0 is not interpreted — the caller decodes the MetaPage
  * (vs_meta_page_decode) and calls vs_index_set_start_nodes / vs_index_set_quantizer after the apply, as it does at staging. */
 typedef struct vs_pages_follow vs_pages_follow;
@@ -563,7 +563,8 @@ typedef struct vs_pages_follow_info {
     uint32_t rows_relinked;   /* existing nodes whose neighbour row differs from the resident one */
     uint32_t tids_cleared;    /* existing nodes whose heap offset went from != 0 to 0 */
     uint32_t tids_changed;    /* any other change of an existing heap tid */
-    uint32_t codes_changed;   /* existing nodes whose code row differs (the reference never does this; reported, applied) */
+    uint32_t codes_changed;   /* existing nodes whose code row differs (the reference never does this; reported, applied); on a plain
+                               * follower: whose PlainNode.vector differs from the writer's composition (reported, NOT applied) */
     uint64_t label_vals_appended;
 } vs_pages_follow_info;
 /* blk_cnt [n_blocks]: SbqNode items per block of the relation the index was staged from (vs_pages_block_table /
@@ -571,6 +572,32 @@ typedef struct vs_pages_follow_info {
  * The index must outlive the follower. */
 int vs_pages_follow_open(vs_index* idx, uint32_t page_size, const vs_node_layout* layout, const uint32_t* blk_cnt, uint32_t n_blocks,
                          vs_pages_follow** out);
+/* The plain twin, in the manner of vs_pages_out_open_plain: a follower of a `plain` index (VS_STORAGE_PLAIN) whose relation holds
+ * PlainNode items (AM/plain/node.rs:15-22) on PageType::Node pages.  The handle is an ordinary vs_pages_follow: stage, new_tids, apply,
+ * discard and close work on it unchanged, and the rule checked on the page headers is the one above with VS_PAGE_NODE pages as the
+ * node pages (an SbqNode-typed page counts 0 items).  blk_cnt [n_blocks]: PlainNode items per block, the table vs_pages_open_plain +
+ * vs_pages_block_table report.  layout NULL = vs_plain_layout_default (off_bq_vector names the vector field, off_labels is ignored).
+ * It makes no difference whether vs_index_alloc or vs_index_upload made the index.  The pages are checked and scattered by
+ * k_pages_follow_plain (a wave per listed page).
+ * vs_pages_follow_info on a plain follower: every field keeps its meaning; label_vals_appended is 0; codes_changed counts the EXISTING
+ * nodes (on the listed pages) whose PlainNode.vector differs, bit for bit, from what the plain page writer would compose for that node
+ * from the resident row — the first dim_index floats of the row, for cosine each float divided by the divisor of that slice (vnorm,
+ * or vnorm_idx when dim_index < dim_full) where the divisor is not zero: k_pages_encode_plain's rule, evaluated by the same code
+ * under the same flags.  That difference is REPORTED, NOT APPLIED: the reference never rewrites a node's vector, the vector column
+ * holds the heap's raw rows, and a normalised slice cannot be turned back into one — so on an existing node the write pass writes
+ * the heap tid and the neighbor row only, and the resident vector row, vnorm and vnorm_idx stay byte for byte.  The count is meaningful
+ * where the vector column holds the heap's rows, or the node vectors under L2 / inner product; for a cosine index uploaded with the
+ * node vectors as its column it counts the rows whose second normalisation is not the identity.
+ * Appended rows: vs_pages_follow_apply with new_vecs stages the rows behind n as for an SBQ index and computes the divisors as
+ * vs_index_insert does for a plain index (vnorm, and vnorm_idx where the index keeps one).  With new_vecs == NULL and dim_index ==
+ * dim_full the write pass copies the appended nodes' vectors FROM THE PAGES into the vector column (for cosine these are the
+ * normalised vectors) and the divisors are computed over those rows; either way a row's padding floats [dim_full, vec_stride) are
+ * zero.  With dim_index < dim_full a NULL new_vecs on an append is VS_ERR_INVALID, nothing written: the pages hold only the index slice.
+ * VS_ERR_INVALID with nothing allocated: an SBQ index (vs_pages_follow_open follows those), an index without vector column /
+ * neighbor lists / heap tids, a cosine index without the divisor cache, a block table that does not sum to n, a layout whose
+ * offsets do not fit the root. */
+int vs_pages_follow_open_plain(vs_index* idx, uint32_t page_size, const vs_node_layout* layout, const uint32_t* blk_cnt, uint32_t n_blocks,
+                               vs_pages_follow** out);
 /* blocks [n] strictly ascending; pages: n pages, page i = block blocks[i] as it is now.  The host reads the page headers only;
  * the pages go to HBM through the pinned ring and the check pass fills `info` (may be NULL).  Nothing of the index is written;
  * a malformed item is reported as the device reader reports it.  A second stage replaces the first; a refused one leaves none. */
@@ -580,7 +607,8 @@ int vs_pages_follow_stage(vs_pages_follow* f, const uint32_t* blocks, const void
 int vs_pages_follow_new_tids(const vs_pages_follow* f, uint64_t* tids, uint32_t cap);
 /* VS_ERR_STATE without a staged list, on a view, while a view exists or a batch is in flight.  new_vecs [n_appended][vec_stride]
  * floats: required when the index holds a vector column and rows are appended (else VS_ERR_INVALID, nothing written; ignored
- * otherwise).  Capacity grows as vs_index_insert grows it; codes are taken from the pages, norms computed for the new rows,
+ * otherwise; a plain follower whose index has dim_index == dim_full takes NULL as "the vectors are in the pages", see
+ * vs_pages_follow_open_plain).  Capacity grows as vs_index_insert grows it; codes are taken from the pages, norms computed for the new rows,
  * label sets appended, the own visibility mask gets 1 and every stored snapshot 0 for the new rows; derived state is treated as
  * vs_index_insert treats it.  The follower's table advances only on success. */
 int vs_pages_follow_apply(vs_pages_follow* f, const float* new_vecs, uint32_t vec_stride, vs_pages_follow_info* info);
@@ -989,9 +1017,9 @@ int vs_sbq_quantize_corpus(vs_index* idx);
  * search_list_size outside [1,1000], a max_alpha outside [1,5], a node with more than 64 labels, and on a plain index for the
  * inner-product distance (DistanceWithTieBreak::new asserts distance >= 0, which -dot violates: the reference has no behaviour to
  * mirror; IP search on an uploaded plain index is unaffected), label sets, or a missing vector column — the index is left byte
- * for byte as it was.  Still refused for plain storage, unchanged: vs_pages_follow_open, and the SBQ forms of calls that have a
- * plain one (vs_index_consolidate_deletes: a plain index is consolidated with vs_index_consolidate_deletes_plain; vs_pages_out_open:
- * it is written back with vs_pages_out_open_plain).  vs_index_repair_labels does not apply: plain storage has no labels. */
+ * for byte as it was.  Still refused for plain storage, unchanged: the SBQ forms of calls that have a plain one
+ * (vs_index_consolidate_deletes: a plain index is consolidated with vs_index_consolidate_deletes_plain; vs_pages_out_open: it is
+ * written back with vs_pages_out_open_plain; vs_pages_follow_open: it is followed with vs_pages_follow_open_plain).  vs_index_repair_labels does not apply: plain storage has no labels. */
 int vs_build_graph(vs_index* idx, uint32_t search_list_size, double max_alpha, uint32_t batch_max, uint64_t seed);
 /* nodes the last vs_build_graph could not make reachable from the default start node (its repair pass gives every such
  * node an in-edge where that strands nobody else; 0 on well-formed input, 0xFFFFFFFF = graph deeper than the pass can judge).

@@ -266,6 +266,7 @@ SYMBOLS = {
     "vs_pages_dev_close": (None, [_vp]),
     "vs_pages_dev_block_table": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u32)]),
     "vs_pages_follow_open": (_i, [_vp, _u32, C.POINTER(NodeLayout), _vp, _u32, C.POINTER(_vp)]),
+    "vs_pages_follow_open_plain": (_i, [_vp, _u32, C.POINTER(NodeLayout), _vp, _u32, C.POINTER(_vp)]),
     "vs_pages_follow_stage": (_i, [_vp, _vp, _vp, _u32, _u32, C.POINTER(PagesFollowInfo)]),
     "vs_pages_follow_new_tids": (_i, [_vp, _vp, _u32]),
     "vs_pages_follow_apply": (_i, [_vp, _vp, _u32, C.POINTER(PagesFollowInfo)]),

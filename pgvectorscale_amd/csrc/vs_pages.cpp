@@ -882,11 +882,15 @@ int vs_pages_headers_only(vs_pages* p) {
 // the header pass of vs_pages_add over ONE page that is not added to a reader (vs_pages_follow_stage): the same checks, and the
 // number of SbqNode items the block table would record for it (0 for a new page and for every other page type)
 int vs_pages_header_items(const void* page, uint32_t page_size, uint32_t block, uint32_t* sbq_items) {
-    if (!page || !sbq_items) return fail("vs_pages_header_items: null argument");
+    return vs_pages_header_items_of(page, page_size, block, VS_PAGE_SBQ_NODE, sbq_items);
+}
+// the same for the node pages of either storage type: node_page_type = VS_PAGE_SBQ_NODE, or VS_PAGE_NODE for PlainNode items
+int vs_pages_header_items_of(const void* page, uint32_t page_size, uint32_t block, uint32_t node_page_type, uint32_t* items) {
+    if (!page || !items) return fail("vs_pages_header_items: null argument");
     PageView v;
     std::string err;
     if (!view_page(static_cast<const uint8_t*>(page), page_size, v, err)) return fail("block %u: %s", block, err.c_str());
-    *sbq_items = v.type == VS_PAGE_SBQ_NODE ? v.n_items : 0;
+    *items = v.type == (int)node_page_type ? v.n_items : 0;
     return VS_OK;
 }
 

@@ -25,13 +25,15 @@ struct vs_pages_dev {
 };
 
 enum { PE_OK = 0, PE_LINE_POINTER = 1, PE_ITEM_BOUNDS = 2, PE_SHORT_ITEM = 3, PE_VEC_BOUNDS = 4, PE_CODE_WIDTH = 5, PE_NEIGHBOR_SLOTS = 6,
-       PE_DANGLING = 7, PE_LABELS = 8, PE_LABELS_CHANGED = 9 };
+       PE_DANGLING = 7, PE_LABELS = 8, PE_LABELS_CHANGED = 9, PE_VECTOR_DIM = 10, PE_DANGLING_PLAIN = 11, PE_LAST = PE_DANGLING_PLAIN };
 static const char* const kPageErrorText[] = {"", "line pointer is not LP_NORMAL", "item lies outside pd_upper..pd_special",
                                              "item shorter than the archived node", "ArchivedVec points outside the item",
                                              "bq_vector length differs from the index's code width",
                                              "neighbor slot count differs from the index's num_neighbors",
                                              "neighbor points at something that is not an SbqNode item of this relation",
-                                             "label set is not strictly increasing", "label set of an existing node changed"};
+                                             "label set is not strictly increasing", "label set of an existing node changed",
+                                             "vector length differs from the index's dimensions",
+                                             "neighbor points at something that is not a PlainNode item of this relation"};
 
 __device__ __forceinline__ uint32_t ld16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
 __device__ __forceinline__ uint32_t ld32(const uint8_t* p) {  // items are MAXALIGNed: 4-byte aligned words
@@ -79,6 +81,19 @@ __device__ __forceinline__ uint32_t page_item_vec8(const PageItem& it, uint32_t 
     if (n != want) return mismatch;
     detail = fld;
     if (tgt < 0 || (uint64_t)tgt + (uint64_t)n * 8 > it.len || (tgt & 3)) return PE_VEC_BOUNDS;
+    return PE_OK;
+}
+
+// The same for an ArchivedVec<4-byte element> (PlainNode.vector: f32): `want` elements, all of them inside the item, 4-byte aligned.
+__device__ __forceinline__ uint32_t page_item_vec4(const PageItem& it, uint32_t field_off, uint32_t want, uint32_t mismatch, int64_t& tgt,
+                                                   uint32_t& detail) {
+    const uint32_t fld = it.root + field_off;
+    tgt = (int64_t)fld + (int32_t)ld32(it.item + fld);
+    const uint32_t n = ld32(it.item + fld + 4);
+    detail = n;
+    if (n != want) return mismatch;
+    detail = fld;
+    if (tgt < 0 || (uint64_t)tgt + (uint64_t)n * 4 > it.len || (tgt & 3)) return PE_VEC_BOUNDS;
     return PE_OK;
 }
 
@@ -538,12 +553,164 @@ __global__ __launch_bounds__(WAVE) void k_pages_follow(PagesFollowArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The same for `plain` storage (vs_pages_follow_open_plain): PlainNode items on PageType::Node pages.  k_pages_follow_plain is
+// k_pages_follow's sibling — its grid (a wave per listed page), list convention, table, split at n_before, counters and error record
+// — with the vector where the code row was.  PlainNode.vector is an ArchivedVec<f32> of D = num_dimensions_to_index floats; the
+// resident side is the vector column (rows of vec_stride floats, a multiple of 4: 16-byte loads and stores), the page side is
+// MAXALIGNed (an item starts on 8 bytes): 4-byte loads there.  A lane owns pieces of 4 floats, the piece loop runs until the vector
+// ends (1930 floats fit a page: 483 pieces, 8 trips); the last piece of a D that is no multiple of 4 is cut at D — the neighbor
+// pointers start there.
+//   check, existing node: the page's floats against what k_pages_encode_plain would compose from the resident row — the index slice,
+//     for cosine each float divided by the slice's divisor (one wave-uniform load per item) where that is not zero; the `/` below is
+//     the one of k_pages_encode_plain, in this translation unit under its flags.  Bit patterns are compared; one ballot per item.
+//   write, existing node: tid and neighbor row.  The vector row and the divisors are NOT written: the reference never rewrites a
+//     node's vector, and a normalised slice cannot be turned back into the heap's row.
+//   write, appended node: tid, neighbor row and — copy_vecs, when the caller handed no rows and D = dim_full — the D floats of the page
+//     into the row, its padding floats [D, vec_stride) zero, which is what vs_upload_rows leaves there.
+// ---------------------------------------------------------------------------------------------------------------
+struct PagesFollowPlainArgs {
+    const uint8_t* pages;    // [n_listed][page_size]
+    const uint32_t* blocks;  // [n_listed] ascending
+    const uint2* tab;        // [n_blocks] {dense id of the block's first node, PlainNode items on it} of the relation as it is now
+    uint32_t n_listed, page_size, n_blocks;
+    vs_node_layout lay;      // off_bq_vector names the vector field
+    uint32_t D, R, n_before;
+    float* vecs;
+    const float* vdiv;       // cosine: the divisor of every resident node's index slice (0 = the slice is left alone); else null
+    uint32_t* nbrs;
+    uint64_t* tids;
+    uint32_t vec_stride, nbr_stride;
+    uint32_t copy_vecs;      // write: the appended nodes' vectors come from the pages
+    uint64_t* new_tids;      // check: [n_appended]
+    uint32_t* ctr;           // [FC_N]
+    uint32_t* err;
+};
+
+template <bool WRITE>
+__global__ __launch_bounds__(WAVE) void k_pages_follow_plain(PagesFollowPlainArgs a) {
+    const int lane = threadIdx.x;
+    const vs_node_layout lay = a.lay;
+    const uint32_t P = (a.D + 3) / 4;  // 16-byte pieces of a vector
+    uint32_t c_relinked = 0, c_cleared = 0, c_changed = 0, c_vecs = 0, c_pages = 0;  // (wave-uniform)
+    for (uint32_t i = blockIdx.x; i < a.n_listed; i += gridDim.x) {
+        const uint32_t b = a.blocks[i];
+        const uint2 ent = a.tab[b];
+        const uint32_t cnt = ent.y;
+        if (cnt == 0) continue;
+        c_pages++;
+        const uint8_t* page = a.pages + (size_t)i * a.page_size;
+        const uint32_t upper = ld16(page + 14), special = ld16(page + 16);
+        for (uint32_t off = 1; off <= cnt; ++off) {  // (about 75 items fit a page at 10 dimensions and 4 slots: the items bound the loop)
+            const uint32_t node = ent.x + off - 1;
+            const bool old = node < a.n_before;
+            PageItem it;
+            uint32_t detail;
+            int64_t tgt, tgt_nbr;
+            uint32_t pe = page_item_at(page, upper, special, off, lay.root_size, it, detail);
+            if (pe == PE_OK) pe = page_item_vec4(it, lay.off_bq_vector, a.D, PE_VECTOR_DIM, tgt, detail);
+            if (pe == PE_OK) pe = page_item_vec8(it, lay.off_neighbor_index_pointers, a.R, PE_NEIGHBOR_SLOTS, tgt_nbr, detail);
+            if (pe != PE_OK) {  // (nothing of a malformed item is written, by either pass)
+                if (lane == 0) page_error(a.err, pe, b, off, detail);
+                continue;
+            }
+            const uint8_t* item = it.item;
+            // heap_item_pointer
+            {
+                const uint8_t* hp = item + it.root + lay.off_heap_item_pointer;
+                const uint64_t tid = ((uint64_t)ld32(hp) << 16) | ld16(hp + 4);
+                if (WRITE) {
+                    if (lane == 0) a.tids[node] = tid;
+                } else if (old) {
+                    const uint64_t was = a.tids[node];
+                    if (was != tid) {
+                        if ((was & 0xFFFFu) != 0 && (tid & 0xFFFFu) == 0) c_cleared++;
+                        else c_changed++;
+                    }
+                } else if (lane == 0) {
+                    a.new_tids[node - a.n_before] = tid;
+                }
+            }
+            // vector
+            if (!WRITE && old) {
+                const float s = a.vdiv ? a.vdiv[node] : 0.0f;
+                const float* row = a.vecs + (size_t)node * a.vec_stride;
+                const uint8_t* src = item + tgt;
+                bool diff = false;
+                for (uint32_t q = lane; q < P; q += WAVE) {
+                    float4 v = *reinterpret_cast<const float4*>(row + 4 * q);
+                    if (s != 0.0f) {
+                        v.x = v.x / s;
+                        v.y = v.y / s;
+                        v.z = v.z / s;
+                        v.w = v.w / s;
+                    }
+                    const uint32_t have = a.D - 4 * q;  // floats of this piece that belong to the vector (>= 1)
+                    diff |= ld32(src + 16 * q) != __float_as_uint(v.x);
+                    if (have > 1) diff |= ld32(src + 16 * q + 4) != __float_as_uint(v.y);
+                    if (have > 2) diff |= ld32(src + 16 * q + 8) != __float_as_uint(v.z);
+                    if (have > 3) diff |= ld32(src + 16 * q + 12) != __float_as_uint(v.w);
+                }
+                if (__ballot(diff)) c_vecs++;
+            } else if (WRITE && !old && a.copy_vecs) {
+                float* row = a.vecs + (size_t)node * a.vec_stride;
+                const uint8_t* src = item + tgt;
+                for (uint32_t q = lane; 4 * q < a.vec_stride; q += WAVE) {
+                    const uint32_t have = 4 * q < a.D ? a.D - 4 * q : 0u;
+                    uint4 v = make_uint4(0, 0, 0, 0);
+                    if (have > 0) v.x = ld32(src + 16 * q);
+                    if (have > 1) v.y = ld32(src + 16 * q + 4);
+                    if (have > 2) v.z = ld32(src + 16 * q + 8);
+                    if (have > 3) v.w = ld32(src + 16 * q + 12);
+                    *reinterpret_cast<uint4*>(row + 4 * q) = v;
+                }
+            }
+            // neighbor_index_pointers: the list ends at the first InvalidBlockNumber; the row is padded to nbr_stride with the sentinel
+            {
+                bool diff = false, ended = false;
+                uint32_t* row = a.nbrs + (size_t)node * a.nbr_stride;
+                for (uint32_t j0 = 0; j0 < a.nbr_stride; j0 += WAVE) {
+                    const uint32_t j = j0 + (uint32_t)lane;
+                    uint32_t nb = 0xFFFFFFFFu, no = 0;
+                    if (j < a.R && !ended) {
+                        nb = ld32(item + tgt_nbr + 8 * j);
+                        no = ld16(item + tgt_nbr + 8 * j + 4);
+                    }
+                    const uint64_t inval = __ballot(nb == 0xFFFFFFFFu);
+                    const uint32_t nvalid = inval ? (uint32_t)__builtin_ctzll(inval) : WAVE;
+                    if (nvalid < WAVE) ended = true;
+                    uint32_t id = VS_INVALID_NODE;
+                    if ((uint32_t)lane < nvalid) {
+                        uint2 t = make_uint2(0, 0);
+                        if (nb < a.n_blocks) t = a.tab[nb];
+                        if (no < 1 || no > t.y) page_error(a.err, PE_DANGLING_PLAIN, b, off, j);
+                        else id = t.x + no - 1;
+                    }
+                    if (j < a.nbr_stride) {
+                        if (WRITE) row[j] = id;
+                        else if (old && j < a.R) diff |= row[j] != id;
+                    }
+                }
+                if (!WRITE && old && __ballot(diff)) c_relinked++;
+            }
+        }
+    }
+    if (!WRITE && lane == 0) {
+        if (c_relinked) atomicAdd(&a.ctr[FC_RELINKED], c_relinked);
+        if (c_cleared) atomicAdd(&a.ctr[FC_TIDS_CLEARED], c_cleared);
+        if (c_changed) atomicAdd(&a.ctr[FC_TIDS_CHANGED], c_changed);
+        if (c_vecs) atomicAdd(&a.ctr[FC_CODES_CHANGED], c_vecs);
+        if (c_pages) atomicAdd(&a.ctr[FC_NODE_PAGES], c_pages);
+    }
+}
+
 struct vs_pages_follow {
     vs_index* ix = nullptr;
     vs_ctx* ctx = nullptr;
     uint32_t page_size = VS_BLCKSZ;
     vs_node_layout lay{};
     bool labeled = false;
+    bool plain = false;  // PlainNode items on PageType::Node pages (vs_pages_follow_open_plain): k_pages_follow_plain
     // the block table of the relation the index mirrors now (host), and the same on the device as {base, count} per block
     std::vector<uint32_t> cnt, base;
     uint32_t n = 0;
@@ -597,7 +764,7 @@ extern "C" void vs_pages_follow_close(vs_pages_follow* f) {
     delete f;
 }
 
-static int follow_open_impl(vs_pages_follow* f, const uint32_t* blk_cnt, uint32_t n_blocks) {
+static int follow_open_impl(vs_pages_follow* f, const uint32_t* blk_cnt, uint32_t n_blocks, const char* what = "vs_pages_follow_open") {
     vs_ctx* c = f->ctx;
     VS_HIP(hipSetDevice(c->device));
     f->cnt.assign(blk_cnt, blk_cnt + n_blocks);
@@ -606,10 +773,9 @@ static int follow_open_impl(vs_pages_follow* f, const uint32_t* blk_cnt, uint32_
     for (uint32_t b = 0; b < n_blocks; ++b) {
         f->base[b] = (uint32_t)sum;
         sum += blk_cnt[b];
-        VS_REQUIRE(sum < VS_INVALID_NODE, "vs_pages_follow_open: the block table counts more than %u nodes", VS_INVALID_NODE - 1);
+        VS_REQUIRE(sum < VS_INVALID_NODE, "%s: the block table counts more than %u nodes", what, VS_INVALID_NODE - 1);
     }
-    VS_REQUIRE(sum == f->ix->d.n, "vs_pages_follow_open: the block table counts %llu nodes, the index holds %u", (unsigned long long)sum,
-               f->ix->d.n);
+    VS_REQUIRE(sum == f->ix->d.n, "%s: the block table counts %llu nodes, the index holds %u", what, (unsigned long long)sum, f->ix->d.n);
     f->n = (uint32_t)sum;
     f->tab_cap = n_blocks + n_blocks / 2 + 64;
     VS_HIP(hipMalloc(&f->d_tab, (size_t)f->tab_cap * 8));
@@ -627,7 +793,7 @@ extern "C" int vs_pages_follow_open(vs_index* idx, uint32_t page_size, const vs_
     VS_REQUIRE(idx && out && (blk_cnt || !n_blocks), "vs_pages_follow_open: bad args");
     *out = nullptr;
     VS_REQUIRE(idx->d.storage_type == VS_STORAGE_SBQ, "vs_pages_follow_open: memory_optimized (SBQ) indexes only; a `plain` index keeps its "
-               "vectors in the nodes and is not followed");
+               "vectors in the nodes and is followed with vs_pages_follow_open_plain");
     VS_REQUIRE(idx->codes && idx->nbrs && idx->tids, "vs_pages_follow_open: the index holds no codes / neighbors");
     VS_REQUIRE(page_size >= 512 && page_size <= 32768 && !(page_size & (page_size - 1)), "vs_pages_follow_open: page_size %u is not a PostgreSQL block size",
                page_size);
@@ -657,6 +823,46 @@ extern "C" int vs_pages_follow_open(vs_index* idx, uint32_t page_size, const vs_
     });
 }
 
+extern "C" int vs_pages_follow_open_plain(vs_index* idx, uint32_t page_size, const vs_node_layout* layout, const uint32_t* blk_cnt,
+                                          uint32_t n_blocks, vs_pages_follow** out) {
+    const char* what = "vs_pages_follow_open_plain";
+    VS_REQUIRE(idx && out && (blk_cnt || !n_blocks), "%s: bad args", what);
+    *out = nullptr;
+    VS_REQUIRE(idx->d.storage_type == VS_STORAGE_PLAIN, "%s: `plain` indexes only; a memory_optimized (SBQ) index is followed with "
+               "vs_pages_follow_open", what);
+    VS_REQUIRE(idx->vecs && idx->nbrs && idx->tids, "%s: the index holds no vector column / neighbors / heap tids", what);
+    VS_REQUIRE(idx->d.distance_type != VS_COSINE || (idx->d.dim_index < idx->d.dim_full ? idx->vnorm_idx : idx->vnorm),
+               "%s: the index has no divisors for its index slices (vs_index_refresh_norms)", what);
+    VS_REQUIRE(idx->vec_stride % 4 == 0 && idx->d.dim_index <= idx->d.dim_full && idx->d.dim_full <= idx->vec_stride,
+               "%s: vector rows of %u floats for %u dimensions", what, idx->vec_stride, idx->d.dim_index);
+    VS_REQUIRE(page_size >= 512 && page_size <= 32768 && !(page_size & (page_size - 1)), "%s: page_size %u is not a PostgreSQL block size", what,
+               page_size);
+    return vs_guard(what, [&] {
+        vs_pages_follow* f = new vs_pages_follow();
+        f->ix = idx;
+        f->ctx = idx->ctx;
+        f->page_size = page_size;
+        f->plain = true;
+        if (layout) f->lay = *layout;
+        else vs_plain_layout_default(&f->lay);
+        const vs_node_layout& l = f->lay;
+        const uint32_t offs[3] = {l.off_heap_item_pointer, l.off_bq_vector, l.off_neighbor_index_pointers};  // (off_labels is ignored)
+        int r = VS_OK;
+        for (int i = 0; i < 3 && r == VS_OK; ++i)
+            if (offs[i] > l.root_size || l.root_size - offs[i] < 8 || l.root_size > 4096 || (offs[i] & 3u)) {
+                vs_set_error("%s: field offset %u does not fit a %u-byte archived node", what, offs[i], l.root_size);
+                r = VS_ERR_INVALID;
+            }
+        if (r == VS_OK) r = follow_open_impl(f, blk_cnt, n_blocks, what);
+        if (r != VS_OK) {
+            vs_pages_follow_close(f);
+            return r;
+        }
+        *out = f;
+        return (int)VS_OK;
+    });
+}
+
 template <class T>
 static int follow_reserve(T** p, size_t* cap, size_t n) {
     if (n <= *cap) return VS_OK;
@@ -677,6 +883,44 @@ static int follow_launch(vs_pages_follow* f, bool write, const PagesFollowArgs& 
     VS_HIP(hipGetLastError());
     prof_end(c, PK_PAGES, ev);
     return VS_OK;
+}
+
+static int follow_launch_plain(vs_pages_follow* f, bool write, const PagesFollowPlainArgs& a) {
+    vs_ctx* c = f->ctx;
+    const uint32_t grid = std::min<uint32_t>(a.n_listed, 1u << 20);
+    hipEvent_t ev = prof_begin(c);
+    if (write) hipLaunchKernelGGL((k_pages_follow_plain<true>), dim3(grid), dim3(WAVE), 0, c->stream, a);
+    else hipLaunchKernelGGL((k_pages_follow_plain<false>), dim3(grid), dim3(WAVE), 0, c->stream, a);
+    VS_HIP(hipGetLastError());
+    prof_end(c, PK_PAGES, ev);
+    return VS_OK;
+}
+
+static PagesFollowPlainArgs follow_args_plain(const vs_pages_follow* f, uint32_t n_listed, uint32_t n_blocks_now, bool copy_vecs) {
+    const vs_index* ix = f->ix;
+    const vs_index_desc& d = ix->d;
+    PagesFollowPlainArgs a{};
+    a.pages = f->d_pages;
+    a.blocks = f->d_list;
+    a.tab = f->d_tab;
+    a.n_listed = n_listed;
+    a.page_size = f->page_size;
+    a.n_blocks = n_blocks_now;
+    a.lay = f->lay;
+    a.D = d.dim_index;
+    a.R = d.num_neighbors;
+    a.n_before = f->n;
+    a.vecs = ix->vecs;
+    a.vdiv = d.distance_type == VS_COSINE ? (d.dim_index < d.dim_full ? ix->vnorm_idx : ix->vnorm) : nullptr;  // (as the page writer)
+    a.nbrs = ix->nbrs;
+    a.tids = ix->tids;
+    a.vec_stride = ix->vec_stride;
+    a.nbr_stride = ix->nbr_stride;
+    a.copy_vecs = copy_vecs ? 1u : 0u;
+    a.new_tids = f->d_new_tids;
+    a.ctr = f->d_ctr;
+    a.err = f->d_ctr + FC_N;
+    return a;
 }
 
 static PagesFollowArgs follow_args(const vs_pages_follow* f, uint32_t n_listed, uint32_t n_blocks_now) {
@@ -710,7 +954,7 @@ static PagesFollowArgs follow_args(const vs_pages_follow* f, uint32_t n_listed, 
 // what a pass reported (after the stream has been synchronised)
 static int follow_page_error(const uint32_t* herr, const char* what) {
     if (herr[0] == PE_OK) return VS_OK;
-    vs_set_error("%s: block %u item %u: %s (detail %u)", what, herr[1], herr[2], kPageErrorText[herr[0] <= PE_LABELS_CHANGED ? herr[0] : 0], herr[3]);
+    vs_set_error("%s: block %u item %u: %s (detail %u)", what, herr[1], herr[2], kPageErrorText[herr[0] <= PE_LAST ? herr[0] : 0], herr[3]);
     return VS_ERR_INVALID;
 }
 
@@ -745,7 +989,7 @@ static int follow_stage_impl(vs_pages_follow* f, const uint32_t* blocks, const v
         const uint32_t b = blocks[i];
         VS_REQUIRE(i == 0 || blocks[i - 1] < b, "%s: blocks[%u] = %u after %u: the list must be strictly ascending", what, i, b, blocks[i - 1]);
         VS_REQUIRE(b < n_blocks_total, "%s: blocks[%u] = %u of a relation of %u blocks", what, i, b, n_blocks_total);
-        VS_TRY(vs_pages_header_items(src + (size_t)i * f->page_size, f->page_size, b, &l_cnt[i]));
+        VS_TRY(vs_pages_header_items_of(src + (size_t)i * f->page_size, f->page_size, b, f->plain ? VS_PAGE_NODE : VS_PAGE_SBQ_NODE, &l_cnt[i]));
         const uint32_t was = b < nb_before ? f->cnt[b] : 0;
         VS_REQUIRE(l_cnt[i] >= was, "%s: block %u held %u nodes and holds %u now: existing nodes would move", what, b, was, l_cnt[i]);
         VS_REQUIRE(l_cnt[i] == was || !any_node_block || b >= last_node_block,
@@ -806,7 +1050,8 @@ static int follow_stage_impl(vs_pages_follow* f, const uint32_t* blocks, const v
             }
             VS_TRY(vs_dev_upload(c, f->d_list, blocks, (size_t)n * 4));
             VS_TRY(vs_dev_upload(c, f->d_pages, pages, (size_t)n * f->page_size));
-            VS_TRY(follow_launch(f, false, follow_args(f, n, n_blocks_total)));
+            if (f->plain) VS_TRY(follow_launch_plain(f, false, follow_args_plain(f, n, n_blocks_total, false)));
+            else VS_TRY(follow_launch(f, false, follow_args(f, n, n_blocks_total)));
             VS_HIP(hipMemcpyAsync(h, f->d_ctr, sizeof h, hipMemcpyDeviceToHost, c->stream));
         }
         VS_HIP(hipStreamSynchronize(c->stream));
@@ -890,7 +1135,14 @@ static int follow_apply_impl(vs_pages_follow* f, const float* new_vecs, uint32_t
         for (const uint8_t* sp : ix->snap) ours |= sp == ix->visible;
         if (!ours) return state_error("a caller-owned device visibility mask is in force and cannot be grown by the library (clear or replace it)");
     }
-    const bool want_vecs = ix->vecs != nullptr && n_app > 0;
+    bool want_vecs = ix->vecs != nullptr && n_app > 0;
+    // a plain relation carries the appended nodes' vectors itself when every dimension is indexed: without rows from the caller the
+    // write pass copies them out of the pages (what IndexPages.upload_plain(vecs=None) does for a whole index)
+    const bool vecs_from_pages = f->plain && want_vecs && !new_vecs && ix->d.dim_index == ix->d.dim_full;
+    VS_REQUIRE(!(f->plain && want_vecs && !new_vecs) || vecs_from_pages, "%s: %u rows are appended and new_vecs is NULL: the pages hold only the "
+               "index slice (%u of %u dimensions; vs_pages_follow_new_tids names the heap tuples to read)", what, n_app, ix->d.dim_index,
+               ix->d.dim_full);
+    if (vecs_from_pages) want_vecs = false;
     VS_REQUIRE(!want_vecs || new_vecs, "%s: the index holds a vector column and %u rows are appended: new_vecs is NULL (vs_pages_follow_new_tids "
                "names the heap tuples to read)", what, n_app);
     VS_REQUIRE(!want_vecs || vec_stride >= ix->d.dim_full, "%s: vec_stride %u < num_dimensions %u", what, vec_stride, ix->d.dim_full);
@@ -926,10 +1178,14 @@ static int follow_apply_impl(vs_pages_follow* f, const float* new_vecs, uint32_t
         uint32_t herr[4] = {0, 0, 0, 0};
         if (f->info.pages_listed) {
             VS_HIP(hipMemsetAsync(f->d_ctr, 0, (FC_N + 4) * 4, st));
-            PagesFollowArgs a = follow_args(f, f->info.pages_listed, f->info.n_blocks_now);  // (after the reserve: the arrays may have moved)
-            if (new_val) a.label_val = new_val;
-            VS_TRY(follow_launch(f, true, a));
-            if (f->info.codes_changed) ix->codes_epoch++;
+            if (f->plain) {  // (nothing of an existing node's vector is written: codes_changed is a report)
+                VS_TRY(follow_launch_plain(f, true, follow_args_plain(f, f->info.pages_listed, f->info.n_blocks_now, vecs_from_pages)));
+            } else {
+                PagesFollowArgs a = follow_args(f, f->info.pages_listed, f->info.n_blocks_now);  // (after the reserve: the arrays may have moved)
+                if (new_val) a.label_val = new_val;
+                VS_TRY(follow_launch(f, true, a));
+                if (f->info.codes_changed) ix->codes_epoch++;
+            }
             VS_HIP(hipMemcpyAsync(herr, f->d_ctr + FC_N, 16, hipMemcpyDeviceToHost, st));
         }
         if (n_app) {
@@ -938,6 +1194,7 @@ static int follow_apply_impl(vs_pages_follow* f, const float* new_vecs, uint32_t
             for (int sn = 1; sn < VS_MAX_SNAPSHOTS; ++sn)
                 if (ix->snap[sn]) VS_HIP(hipMemsetAsync(ix->snap[sn] + n_old, 0, n_app, st));
             VS_TRY(launch_row_norms_range(ix, n_old, n_app));  // (the codes come from the pages: nothing is quantized again)
+            if (f->plain) VS_TRY(launch_slice_norms_range(ix, n_old, n_app));  // (as vs_index_insert does for a plain index)
         }
         VS_HIP(hipStreamSynchronize(st));
         return follow_page_error(herr, what);  // (the check pass saw the same bytes: this does not happen)

@@ -9,6 +9,8 @@
 
 // vs_pages_add's header checks over one page outside a reader -> the SbqNode items on it (0: a new page, another page type)
 extern "C" int vs_pages_header_items(const void* page, uint32_t page_size, uint32_t block, uint32_t* sbq_items);
+// the same with the page type that counts named: VS_PAGE_SBQ_NODE, or VS_PAGE_NODE for the PlainNode items of a `plain` relation
+extern "C" int vs_pages_header_items_of(const void* page, uint32_t page_size, uint32_t block, uint32_t node_page_type, uint32_t* items);
 
 // The whole layout of the relation a vs_pages_out writes, fixed at open.
 struct PagesOutPlan {

@@ -13,7 +13,7 @@ range — or, against a `PagesBase`, only the blocks that changed since it was l
 
 `PagesFollower` (vs_pages_follow_*) is the opposite direction page by page: when something else writes the relation (a standby's
 WAL replay, the CPU extension's aminsert and vacuum), the blocks that changed are staged, checked on the device and scattered
-into the resident arrays; `dirty_blocks` is the bytewise page compare that finds them where nothing better names them.
+into the resident arrays (SBQ and, with plain=True, `plain` storage indexes); `dirty_blocks` is the bytewise page compare that finds them where nothing better names them.
 """
 import ctypes as C
 
@@ -202,7 +202,7 @@ class IndexPages:
 
     def follower(self, index, layout=None):
         """a PagesFollower of `index` (staged from these pages) that starts at this relation's block table"""
-        return PagesFollower(index, self.block_table()[1], layout=layout, page_size=self.page_size)
+        return PagesFollower(index, self.block_table()[1], layout=layout, page_size=self.page_size, plain=self.plain)
 
     def read_chain(self, block, offset, page_type):
         n = C.c_size_t()
@@ -450,20 +450,26 @@ def dirty_blocks(old_bytes, new_bytes, page_size=BLCKSZ):
 
 
 class PagesFollower:
-    """Brings a device-resident memory_optimized index up to date from the blocks of its relation that something else changed
+    """Brings a device-resident index up to date from the blocks of its relation that something else changed
     (vs_pages_follow_*): `stage` checks the listed pages on the device and reports what they would do, `new_tids` names the heap
     tuples of the appended nodes (HeapColumn reads their vectors), `apply` scatters.  The start nodes and the quantizer are not
-    read from block 0: decode the MetaPage (decode_meta_page) and call set_start_nodes / set_quantizer after the apply."""
+    read from block 0: decode the MetaPage (decode_meta_page) and call set_start_nodes / set_quantizer after the apply.
+    plain=True: a `plain` storage index (vs_pages_follow_open_plain; PlainNode items, blk_cnt as IndexPages(plain=True) reports
+    it) — layout is then a plain-layout tuple as PagesOut(plain=True) takes it, and `apply(None)` takes the appended rows' vectors
+    from the pages when the index indexes every dimension.  The storage type of `index` does not select the call: the keyword does."""
 
-    def __init__(self, index, blk_cnt, layout=None, page_size=BLCKSZ):
+    def __init__(self, index, blk_cnt, layout=None, page_size=BLCKSZ, plain=False):
         self._L = index._L
         self.index = index
         self.page_size = page_size
+        self.plain = bool(plain)
+        if layout is not None and plain:
+            layout = tuple(0xFFFFFFFF if v is None else v for v in layout)
         lay = None if layout is None else NodeLayout(*layout)
         cnt = np.ascontiguousarray(blk_cnt, np.uint32)
         h = C.c_void_p()
-        check(self._L.vs_pages_follow_open(index.h, page_size, None if lay is None else C.byref(lay), cnt.ctypes.data_as(C.c_void_p),
-                                           cnt.size, C.byref(h)))
+        opener = self._L.vs_pages_follow_open_plain if plain else self._L.vs_pages_follow_open
+        check(opener(index.h, page_size, None if lay is None else C.byref(lay), cnt.ctypes.data_as(C.c_void_p), cnt.size, C.byref(h)))
         self.h = h
         self._n_appended = None  # rows the staged list appends (None: nothing is staged)
 
@@ -486,7 +492,8 @@ class PagesFollower:
         return out
 
     def apply(self, new_vecs=None):
-        """new_vecs [n_appended][dim_full] float32: required when the index holds the vector column and rows are appended"""
+        """new_vecs [n_appended][dim_full] float32: required when the index holds the vector column and rows are appended — except on
+        a plain follower whose index indexes every dimension: None then takes the appended nodes' vectors from the pages"""
         info = PagesFollowInfo()
         v = None if new_vecs is None else np.ascontiguousarray(new_vecs, np.float32).reshape(-1, np.shape(new_vecs)[-1])
         if v is not None and self._n_appended is not None and v.shape[0] != self._n_appended:
