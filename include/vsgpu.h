@@ -104,6 +104,18 @@ typedef struct vs_stats {
 
 const char* vs_last_error(void);
 
+/* Which kernel the first attempt of a handle's last batch (its last chunk) ran, and with which planned capacities.  Read-only: it
+ * changes no launch.  VS_ERR_INVALID for NULL arguments, VS_ERR_STATE before the first batch of the handle. */
+enum { VS_SEARCH_GENERAL = 0, VS_SEARCH_FAST_SBQ = 1, VS_SEARCH_FAST_PLAIN = 2 };
+typedef struct vs_search_info {
+    uint32_t kernel;       /* what the first attempt of the last batch (chunk) ran */
+    uint32_t resident;     /* scans in flight on the persistent grid (0: general kernel) */
+    uint32_t lds_bytes;    /* dynamic LDS per scan of that launch */
+    uint32_t heap_lds, dedup_slots, visited_cap;  /* the planned on-chip capacities (0 where not applicable) */
+    uint32_t reserved[2];
+} vs_search_info;
+int vs_index_last_search_info(const vs_index* idx, vs_search_info* out);
+
 /* Tuning options (launch variants, capacities, slab placement, diagnostics), process wide.  `name` is one of the
  * VS_* names listed there, `value` its text ("3", "0", a path ...; NULL unsets it again).  An option set here wins over the environment
  * variable of the same name; the environment itself is only SNAPSHOT — at the first lookup and again when the process's VS_* variables
@@ -118,7 +130,13 @@ const char* vs_last_error(void);
  * by the first batch that needs it and rebuilt when the codes or the row numbers have changed; under "2" (and on a view handle) the
  * seed row nearest to the query's own code, computed per batch.  VS_RERANK_SEEDS corpus rows define the neighbourhoods (up to 4096;
  * default 2048 for the labels, 1024 for the per-batch seed pass); VS_RERANK_DEAL "0" keeps the order but not the per-XCD split.  The
- * rows returned are the same, bit for bit, under every setting. */
+ * rows returned are the same, bit for bit, under every setting.
+ * VS_PLAIN_FAST: which kernel a batch over a `plain` storage index tries first — "1" (default) k_search_plain, one wave per scan on a
+ * persistent grid with the scan's state on chip, the general kernel re-running the scans that outgrow it (counted in
+ * vs_stats.fallback_scans); "0" the general kernel alone.  Rows, distance bits and the reference counters are the same under both.
+ * Its capacities, for tests and measurement (0 / unset = planned from n, num_neighbors, the search list size and the stream length):
+ * VS_PF_HEAP_LDS (heap entries kept in LDS), VS_PF_HEAP_CAP (heap entries in all), VS_PF_DEDUP_SLOTS (slots of the dedup table,
+ * rounded up to a power of two), VS_PF_VISITED (visited-list capacity), VS_PF_SCANS_PER_CU (upper bound of the persistent grid). */
 int vs_set_option(const char* name, const char* value);
 int vs_get_option(const char* name, char* out, size_t cap);
 const char* vs_version(void);

@@ -41,6 +41,17 @@ class Stats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+VS_SEARCH_GENERAL, VS_SEARCH_FAST_SBQ, VS_SEARCH_FAST_PLAIN = 0, 1, 2
+
+
+class SearchInfo(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("kernel", "resident", "lds_bytes", "heap_lds", "dedup_slots", "visited_cap")] + [
+        ("reserved", C.c_uint32 * 2)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_[:6]}
+
+
 class TuneEntry(C.Structure):
     _fields_ = [("name", C.c_char * 40), ("step_ms", C.c_float), ("search_ms", C.c_float), ("applicable", C.c_uint32),
                 ("rows_identical", C.c_uint32), ("chosen", C.c_uint32), ("error", C.c_int32)]
@@ -218,6 +229,7 @@ SYMBOLS = {
     "vs_index_get_desc": (_i, [_vp, C.POINTER(IndexDesc)]),
     "vs_index_array": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_u32)]),
     "vs_index_rerank_order": (_i, [_vp, _vp, _u32, C.POINTER(_u32)]),
+    "vs_index_last_search_info": (_i, [_vp, C.POINTER(SearchInfo)]),
     "vs_index_set_quantizer": (_i, [_vp, _vp, _vp, _u64]),
     "vs_index_set_start_nodes": (_i, [_vp, _u32, _vp, _vp, _u32]),
     "vs_index_set_labels": (_i, [_vp, _vp, _vp]),

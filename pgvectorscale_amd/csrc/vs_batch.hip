@@ -191,6 +191,16 @@ static int ensure_region_labels(vs_index* ix, uint32_t S) {
     return VS_OK;
 }
 
+extern "C" int vs_index_last_search_info(const vs_index* ix, vs_search_info* out) {
+    VS_REQUIRE(ix && out, "vs_index_last_search_info: bad args");
+    if (!ix->last_info_valid) {
+        vs_set_error("vs_index_last_search_info: no batch has run on this handle yet");
+        return VS_ERR_STATE;
+    }
+    *out = ix->last_info;
+    return VS_OK;
+}
+
 extern "C" int vs_index_rerank_order(vs_index* ix, uint32_t* out_perm, uint32_t cap, uint32_t* out_n) {
     VS_REQUIRE(ix && out_n && (cap == 0 || out_perm), "vs_index_rerank_order: bad args");
     VS_HIP(hipStreamSynchronize(ix->ctx->stream));
@@ -677,6 +687,8 @@ static int run_fast_attempts(vs_index* ix, const BatchPlan& bp, Caps& caps, cons
     prof_end(c, PK_SEARCH, ev);
     if (f.timeline) VS_TRY(dump_timeline(ix, bp.nq, tl_path));
     ix->last_fast = FastSig{f.vwords, f.minw, f.gcap, f.lh, f.vr, 1u};
+    ix->last_info = vs_search_info{VS_SEARCH_FAST_SBQ, f.persist, (uint32_t)fast_lds_bytes(ix, f), f.hl, f.lh + f.gcap, f.vr ? 512u : f.vcap, {0, 0}};
+    ix->last_info_valid = true;
     FastLaunch r;
     if (env_u32("VS_F_RETRY", 1) && second_attempt_of(ix, f, bp.nq, &r)) {
         VS_TRY(devbuf_reserve(c, w.heap_g4b, (size_t)r.pool_slots * r.gstride * 4));
@@ -688,6 +700,94 @@ static int run_fast_attempts(vs_index* ix, const BatchPlan& bp, Caps& caps, cons
         prof_end(c, PK_SEARCH_FB, ev2);
     }
     if (env_u32("VS_DEBUG_STATUS", 0)) VS_TRY(dump_fast_status(ix, f, caps.f_pool_frac));
+    return VS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// the first attempt of a plain-storage chunk: k_search_plain (vs_search.hip).  plan_plain_launch decides whether it runs and with
+// which capacities; run_plain_attempt binds buffers and launches.  Nothing is remembered between batches: every capacity follows
+// from (n, num_neighbors, L, M) of the batch at hand, so an index that grew, was compacted or followed a relation is planned anew.
+// ---------------------------------------------------------------------------------------------------------------
+// LDS a scan of k_search_plain may take: a quarter of a CU's 160 KB, i.e. at least 4 scans per CU.  A state that does not fit
+// (huge dimensions: the query slice alone is 4 * vec_stride bytes) is left to the general kernel.
+static const size_t PLAIN_LDS_BUDGET = 40 * 1024;
+// ... and what the heap's LDS part is sized to: 8 scans per CU, the lower end of the range the row gathers need
+// (MI355X_MICROARCH.md "Indexed rows": 16 waves per CU at 4 rows in flight)
+static const size_t PLAIN_LDS_TARGET = 20 * 1024;
+static const uint32_t PLAIN_LDS_TABLE_MAX = 1024;  // slots up to which the dedup table's ids live in LDS (4 KB)
+
+// Enqueues nothing and touches no buffer; its only device-facing call is the occupancy query.  *on = false: the general kernel
+// runs alone, as before.
+static int plan_plain_launch(vs_index* ix, const BatchPlan& bp, bool masked, PlainLaunch* out, bool* on) {
+    *on = false;
+    if (ix->d.storage_type != VS_STORAGE_PLAIN || env_u32("VS_PLAIN_FAST", 1) == 0 || ix->d.n == 0) return VS_OK;
+    const uint32_t n = ix->d.n, R = ix->d.num_neighbors, L = bp.L, M = bp.M;
+    PlainLaunch p{};
+    p.nq = bp.nq;
+    p.L = L;
+    p.M = M;
+    // Capacities clamp to the index: a scan inserts at most n ids, holds at most n heap entries and visits at most n nodes, so
+    // a small index is planned for every possible scan and hands nothing over.
+    const uint64_t typ_visits = (uint64_t)L + L / 4 + M + 16;               // as initial_caps
+    const uint64_t typ_ins = typ_visits * std::min<uint32_t>(R, 32) + 64;   // up to 32 new ids per visit
+    p.slots = std::max<uint32_t>(next_pow2_u32(std::min<uint64_t>(std::min<uint64_t>(typ_ins, n) * 4 / 3 + 1, 1u << 22)), 64);
+    if (const uint32_t v = env_u32("VS_PF_DEDUP_SLOTS", 0)) p.slots = std::max<uint32_t>(next_pow2_u32(std::min<uint32_t>(v, 1u << 22)), 64);
+    p.ins_limit = n <= p.slots / 4 * 3 ? 0xFFFFFFFFu : p.slots / 4 * 3;  // load limit 75 %
+    p.lds_table = p.slots <= PLAIN_LDS_TABLE_MAX ? 1u : 0u;
+    const uint64_t pushes = (2ull * L + M + 32) * R;  // as initial_caps
+    p.hcap = (uint32_t)std::max<uint64_t>(std::min<uint64_t>(std::min<uint64_t>(pushes, n), 1u << 22), 1);
+    p.vcap = (uint32_t)std::max<uint64_t>(std::min<uint64_t>(3ull * L + M + 64, n), 1);
+    if (const uint32_t v = env_u32("VS_PF_VISITED", 0)) p.vcap = v;
+    // the heap's LDS part: the largest of 1023 / 511 / 255 / 127 entries that keeps the scan within PLAIN_LDS_TARGET
+    p.hl = 127;
+    for (uint32_t hl : {1023u, 511u, 255u}) {
+        PlainLaunch t = p;
+        t.hl = hl;
+        if (plain_lds_bytes(ix, t) <= PLAIN_LDS_TARGET) {
+            p.hl = hl;
+            break;
+        }
+    }
+    if (const uint32_t v = env_u32("VS_PF_HEAP_LDS", 0)) p.hl = v;
+    if (const uint32_t v = env_u32("VS_PF_HEAP_CAP", 0)) p.hcap = v;
+    p.hl = std::min(p.hl, p.hcap);
+    if (plain_lds_bytes(ix, p) > PLAIN_LDS_BUDGET) return VS_OK;
+    p.visible = masked ? fast_select<const uint8_t>() : nullptr;
+    uint32_t res = 0;
+    VS_TRY(plain_resident_scans(ix, p, &res));
+    if (const uint32_t v = env_u32("VS_PF_SCANS_PER_CU", 0)) res = std::min<uint32_t>(res, std::max<uint32_t>(v, 1) * (uint32_t)ix->ctx->prop.multiProcessorCount);
+    p.resident = std::max<uint32_t>(res, 1);
+    p.persist = std::min(p.resident, bp.nq);
+    *out = p;
+    *on = true;
+    return VS_OK;
+}
+
+static int run_plain_attempt(vs_index* ix, const BatchPlan& bp, PlainLaunch p) {
+    vs_ctx* c = ix->ctx;
+    SearchWorkspace& w = ix->ws;
+    ix->last_ins_limit = 0;  // (the sizing feedback of ScanObs is the SBQ tables': off for plain launches)
+    // the two per-workgroup regions: never cleared, so they only have to exist
+    VS_TRY(devbuf_reserve(c, w.heap_g4, std::max<size_t>((size_t)p.persist * (p.hcap - p.hl) * 8, 16)));
+    VS_TRY(devbuf_reserve(c, w.ghash4, std::max<size_t>(p.lds_table ? 0 : (size_t)p.persist * p.slots * 4, 16)));
+    VS_TRY(devbuf_reserve(c, w.pool_ctr, 64));
+    VS_HIP(hipMemsetAsync(w.pool_ctr.p, 0, 64, c->stream));
+    VS_TRY(devbuf_reserve(c, w.fb_flag, (size_t)p.nq * 4));
+    VS_HIP(hipMemsetAsync(w.fb_flag.p, 0, (size_t)p.nq * 4, c->stream));
+    p.visible = (!bp.stream_only && bp.rescore > 0) ? ix->visible : nullptr;
+    p.heap_g = (uint64_t*)w.heap_g4.p;
+    p.table_g = (uint32_t*)w.ghash4.p;
+    p.scan_counter = (uint32_t*)w.pool_ctr.p + 2;
+    p.out_ids = (uint32_t*)w.stream_ids.p;
+    p.out_ham = (uint32_t*)w.stream_ham.p;
+    p.out_cnt = (uint32_t*)w.stream_cnt.p;
+    p.stats = (uint32_t*)w.stats.p;
+    p.status = (uint32_t*)w.status.p;
+    hipEvent_t ev = prof_begin(c);
+    VS_TRY(launch_search_plain(ix, p));
+    prof_end(c, PK_SEARCH, ev);
+    ix->last_info = vs_search_info{VS_SEARCH_FAST_PLAIN, p.resident, (uint32_t)plain_lds_bytes(ix, p), p.hl, p.slots, p.vcap, {0, 0}};
+    ix->last_info_valid = true;
     return VS_OK;
 }
 
@@ -716,8 +816,17 @@ static int run_search_chunk(vs_index* ix, const BatchPlan& bp, const float* d_ra
         prof_end(c, PK_PREPARE, ev);
     }
     ix->last_fast = FastSig{};
-    const bool fast_done = caps.f_on;
-    if (fast_done) VS_TRY(run_fast_attempts(ix, bp, caps, d_qlabels, d_qlabel_off));
+    PlainLaunch pl;
+    bool plain_first = false;
+    VS_TRY(plan_plain_launch(ix, bp, !bp.stream_only && bp.rescore > 0 && ix->visible, &pl, &plain_first));
+    const bool fast_done = caps.f_on || plain_first;  // a first attempt ran: the general kernel takes only what it handed over
+    if (caps.f_on) VS_TRY(run_fast_attempts(ix, bp, caps, d_qlabels, d_qlabel_off));
+    else if (plain_first) VS_TRY(run_plain_attempt(ix, bp, pl));
+    else {
+        SearchLaunch g = general_launch(ix, bp, caps, d_qlabels, d_qlabel_off);
+        ix->last_info = vs_search_info{VS_SEARCH_GENERAL, 0, (uint32_t)search_lds_bytes(ix, g), caps.hl, caps.lh, caps.vcap, {0, 0}};
+        ix->last_info_valid = true;
+    }
     w.fb_valid = fast_done;
     {
         // after the fast kernel only a few scans are left: they claim their regions from a small pool

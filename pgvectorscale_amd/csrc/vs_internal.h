@@ -238,6 +238,8 @@ struct vs_index {
     uint32_t last_ins_limit = 0;  // LDS-table admission limit of the last fast launch
     TuneVariant tune;
     FastSig last_fast;
+    vs_search_info last_info{};  // what the first attempt of the last chunk ran (vs_index_last_search_info)
+    bool last_info_valid = false;
     vs_stats last_stats{};
 };
 
@@ -419,6 +421,31 @@ static inline bool fast_tables16_geometry(const vs_index* idx, FastLaunch& f) {
 }
 int launch_search_fast(vs_index* idx, const FastLaunch& s);
 int fast_resident_scans(vs_index* idx, const FastLaunch& s, uint32_t* out);  // size of a persistent grid for this instantiation
+// plain storage (vs_search.hip, k_search_plain): one wave per scan on a persistent grid, all state of a scan in LDS or in the
+// workgroup's own regions of heap_g / table_g, which are never cleared
+struct PlainLaunch {
+    uint32_t nq, L, M;
+    uint32_t hl;         // candidate-heap entries (8 bytes each) resident in LDS: heap positions [0, hl)
+    uint32_t hcap;       // total heap capacity; positions [hl, hcap) live in the workgroup's region of heap_g
+    uint32_t vcap;       // visited-list capacity (LDS)
+    uint32_t slots;      // slots of the dedup table (a power of two >= 64); one occupancy bit per slot in LDS
+    uint32_t ins_limit;  // ids the table may hold (<= 3/4 of the slots); 0xFFFFFFFF: the index has fewer rows than that
+    uint32_t lds_table;  // 1: the table's ids live in LDS as well, 0: in the workgroup's region of table_g
+    uint32_t persist;    // workgroups of the persistent grid: min(resident, nq)
+    uint32_t resident = 0;  // (host side) single-wave workgroups of this LDS size the device holds at once
+    const uint8_t* visible = nullptr;
+    uint64_t* heap_g = nullptr;       // [persist][hcap - hl]
+    uint32_t* table_g = nullptr;      // [persist][slots] (lds_table == 0)
+    uint32_t* scan_counter = nullptr;  // next scan to run (zero before the launch)
+    uint32_t* out_ids = nullptr;
+    uint32_t* out_ham = nullptr;
+    uint32_t* out_cnt = nullptr;
+    uint32_t* stats = nullptr;
+    uint32_t* status = nullptr;
+};
+size_t plain_lds_bytes(const vs_index* idx, const PlainLaunch& s);
+int launch_search_plain(vs_index* idx, const PlainLaunch& s);
+int plain_resident_scans(vs_index* idx, const PlainLaunch& s, uint32_t* out);  // workgroups of k_search_plain the device holds at once
 enum { ST_VISITS = 0, ST_CAND = 1, ST_DQ = 2, ST_READS = 3, ST_NEXT = 4, ST_GSPILL = 5, ST_INVIS = 6, ST_INS = 7 /* ids the fast kernel inserted */, ST_N = 8 };
 enum { OVF_HEAP = 1, OVF_VISITED = 2, OVF_HASH = 4, OVF_POOL = 8,
        OVF_KEY = 16 };  // (fast kernel only) the scan key has more labels than its LDS slot holds: the general kernel runs the scan

@@ -633,3 +633,487 @@ int launch_search(vs_index* idx, const SearchLaunch& s, bool build_mode) {
     VS_HIP(hipGetLastError());
     return VS_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// k_search_plain — the scans of a `plain` storage index (AM/plain/storage.rs) on a persistent grid: the semantics of
+// k_search<false, true> above, expansion for expansion, with every piece of a scan's state on chip or in a region that belongs
+// to the WORKGROUP (not to the scan) and is never cleared:
+//   * the prepared query slice in LDS;
+//   * candidate heap: 8-byte entries (key << 32 | node — plain keys use all 32 bits), positions [0, hl) in LDS, the rest in the
+//     workgroup's spill region.  A push is ONE wave step instead of a chain of dependent round trips: lane r reads the r-th
+//     ancestor of the new leaf, a ballot finds the leading run of ancestors with a greater key, those lanes store their value one
+//     position down the path and lane 0 stores the element where the run ends — the array sift_up leaves (it only ever shifts the
+//     path by one position, and compares the element with the ORIGINAL ancestors).  Pushes of a visit stay in list order;
+//   * dedup set: an open-addressing table of node ids with one occupancy bit per slot in LDS.  A slot whose bit is clear has
+//     never been written by this scan, whatever an earlier scan left in it, so only the bits are cleared per scan (slots / 8
+//     bytes of LDS) and a new id is stored without reading the table.  The ids live in LDS when the table is small, else in the
+//     workgroup's region of table_g: plain loads and stores — the vector memory operations of one wave reach its CU's L1 in
+//     program order and no other CU touches the region (vs_search_fast.hip states and relies on the same);
+//   * visited list: sorted (key, node) arrays in LDS with a moving head, so consume's remove(0) moves nothing and an insert
+//     shifts the shorter side.
+// A wave is its own workgroup: nothing waits at a barrier (psync() only pins the compiler's order).  The row gathers of a pass
+// (8 rows, 8 lanes x 16 B per step) are issued PLAIN_CH steps at a time before the first is consumed; the adds keep
+// plain_dist8's order.  A scan that outgrows a capacity publishes an empty stream and its status and is re-run whole by
+// k_search<false, true> (run_search_chunk).
+// ---------------------------------------------------------------------------------------------------------------
+struct PlainArgs {
+    const uint32_t* nbrs;
+    const uint64_t* tids;
+    const float* vecs;
+    const float* vnorm;
+    const float* q_full;
+    uint32_t nbr_stride, R, n, default_start, vec_stride, dim, distance_type;
+    PlainLaunch s;
+};
+
+#define PLAIN_CH 12  // 32-element steps of a row whose loads are in flight together (12 x 16 B per lane = 48 VGPRs)
+
+typedef __attribute__((address_space(1))) uint32_t pg_u32;
+typedef __attribute__((address_space(1))) uint64_t pg_u64;
+typedef __attribute__((address_space(3))) uint32_t pl_u32;
+typedef __attribute__((address_space(3))) uint64_t pl_u64;
+
+__device__ __forceinline__ void psync() {  // single-wave workgroup: see wave_sync() in vs_search_fast.hip (no instruction is emitted)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// BinaryHeap<Reverse<ListSearchNeighbor>>, laid out as WaveHeap: position i at l[i + 1] while i < hl, else g[i - hl]
+struct PlainHeap {
+    uint64_t* l;
+    uint64_t* g;
+    uint32_t hl, len, maxlen;
+    __device__ __forceinline__ static uint32_t key(uint64_t e) { return (uint32_t)(e >> 32); }
+    __device__ __forceinline__ uint64_t get(uint32_t i) const { return i < hl ? *(const pl_u64*)(l + i + 1) : *(const pg_u64*)(g + (i - hl)); }
+    __device__ __forceinline__ void set(uint32_t i, uint64_t v) const {
+        if (i < hl) *(pl_u64*)(l + i + 1) = v;
+        else *(pg_u64*)(g + (i - hl)) = v;
+    }
+    // sift_up(0, pos) of `elem` (not yet stored; wave-uniform) in one step: see the header comment
+    __device__ __forceinline__ void sift_up(uint32_t pos, uint64_t elem, int lane) const {
+        const uint32_t p1 = pos + 1, r = (uint32_t)lane;
+        const uint32_t ar1 = r < 32 ? (p1 >> r) : 0u;  // (r-th ancestor) + 1; 0: above the root
+        const bool valid = r >= 1 && ar1 >= 1;
+        uint64_t e = 0;
+        if (valid) e = get(ar1 - 1);
+        const bool cmp = valid && key(elem) < key(e);  // Reverse: a parent with key <= the element's stops the climb
+        const uint64_t bal = __ballot(cmp) >> 1;       // bit r - 1 <-> ancestor r
+        const uint32_t t = (uint32_t)__builtin_ctzll(~bal);
+        if (r >= 1 && r <= t) set((p1 >> (r - 1)) - 1, e);
+        if (lane == 0) set((p1 >> t) - 1, elem);
+        psync();
+    }
+    __device__ __forceinline__ void push(uint64_t elem, int lane) {
+        const uint32_t pos = len;
+        len = pos + 1;
+        maxlen = max(maxlen, len);
+        sift_up(pos, elem, lane);
+    }
+    // pop(): Vec::pop, swap with data[0], sift_down_to_bottom(0) (always to a leaf), then sift_up.  len > 0.
+    __device__ __forceinline__ uint64_t pop(int lane) {
+        const uint64_t item = get(len - 1);
+        len -= 1;
+        if (len == 0) return item;
+        const uint64_t top = get(0);
+        const uint32_t end = len;
+        uint32_t pos = 0, child = 1;
+        const uint32_t lim = end >= 2 ? end - 2 : 0;
+        while (child <= lim) {
+            const uint64_t le = get(child), ri = get(child + 1);
+            // child += (data[child] <= data[child+1]); Reverse => right.d <= left.d picks the right child
+            const uint32_t pick = rfl((key(ri) <= key(le)) ? 1u : 0u);
+            child += pick;
+            if (lane == 0) set(pos, pick ? ri : le);
+            pos = child;
+            child = 2 * pos + 1;
+        }
+        if (child == end - 1) {
+            const uint64_t ce = get(child);
+            if (lane == 0) set(pos, ce);
+            pos = child;
+        }
+        psync();  // the path lane 0 just stored is what sift_up reads
+        sift_up(pos, item, lane);
+        return top;
+    }
+};
+
+// plain_dist8 (vs_device.h) with the row loads of PLAIN_CH steps issued before the first is consumed: the same operations on the
+// same operands in the same order — lane l8 owns elements 32 t + 4 l8 .. + 3, its four accumulators are summed over t in order, L2
+// is mul + add, dot is FMA, then horizontal_add_ps, the scalar tail in element order and the cosine divisor per element
+__device__ __forceinline__ float plain_dist8_hoisted(const float* __restrict__ row, float sdiv, const float* qv, uint32_t dim,
+                                                     uint32_t distance_type, int lane, bool valid) {
+    const int l8 = lane & 7;
+    const uint32_t steps = dim / 32;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    for (uint32_t t0 = 0; t0 < steps; t0 += PLAIN_CH) {
+        float4 x[PLAIN_CH];
+#pragma unroll
+        for (int u = 0; u < PLAIN_CH; ++u) {
+            x[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (valid && t0 + (uint32_t)u < steps) x[u] = *reinterpret_cast<const float4*>(row + 32 * (t0 + (uint32_t)u) + 4 * l8);
+        }
+        if (distance_type == VS_L2) {
+#pragma unroll
+            for (int u = 0; u < PLAIN_CH; ++u) {
+                if (valid && t0 + (uint32_t)u < steps) {
+                    const float4 y = *reinterpret_cast<const float4*>(qv + 32 * (t0 + (uint32_t)u) + 4 * l8);
+                    const float d0 = x[u].x - y.x, d1 = x[u].y - y.y, d2 = x[u].z - y.z, d3 = x[u].w - y.w;
+                    const float p0 = d0 * d0, p1 = d1 * d1, p2 = d2 * d2, p3 = d3 * d3;
+                    a0 = a0 + p0;
+                    a1 = a1 + p1;
+                    a2 = a2 + p2;
+                    a3 = a3 + p3;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < PLAIN_CH; ++u) {
+                if (valid && t0 + (uint32_t)u < steps) {
+                    const float4 y = *reinterpret_cast<const float4*>(qv + 32 * (t0 + (uint32_t)u) + 4 * l8);
+                    float4 xx = x[u];
+                    if (sdiv != 0.0f) {
+                        xx.x = xx.x / sdiv;
+                        xx.y = xx.y / sdiv;
+                        xx.z = xx.z / sdiv;
+                        xx.w = xx.w / sdiv;
+                    }
+                    a0 = __builtin_fmaf(xx.x, y.x, a0);
+                    a1 = __builtin_fmaf(xx.y, y.y, a1);
+                    a2 = __builtin_fmaf(xx.z, y.z, a2);
+                    a3 = __builtin_fmaf(xx.w, y.w, a3);
+                }
+            }
+        }
+    }
+    const float s0 = a0 + __shfl(a0, lane ^ 1, WAVE);
+    const float s1 = a1 + __shfl(a1, lane ^ 1, WAVE);
+    const float s2 = a2 + __shfl(a2, lane ^ 1, WAVE);
+    const float s3 = a3 + __shfl(a3, lane ^ 1, WAVE);
+    const float t0 = s0 + s1;
+    const float t1 = s2 + s3;
+    const float h = t0 + t1;
+    const int g0 = lane & ~7;
+    const float h0 = __shfl(h, g0 + 0, WAVE), h1 = __shfl(h, g0 + 2, WAVE), h2 = __shfl(h, g0 + 4, WAVE), h3 = __shfl(h, g0 + 6, WAVE);
+    float dist = h0 + h1;
+    dist = dist + h2;
+    dist = dist + h3;
+    float r = 0.0f;
+    if (valid && l8 == 0) {
+        for (uint32_t i = steps * 32; i < dim; ++i) {  // scalar tail, in element order
+            float x = row[i];
+            if (distance_type == VS_L2) {
+                const float diff = x - qv[i];
+                const float p = diff * diff;
+                dist = dist + p;
+            } else {
+                if (sdiv != 0.0f) x = x / sdiv;
+                const float p = x * qv[i];
+                dist = dist + p;
+            }
+        }
+        if (distance_type == VS_L2) r = dist;
+        else if (distance_type == VS_IP) r = -dist;
+        else r = fmaxf(1.0f - dist, 0.0f);
+    }
+    return r;
+}
+
+__device__ __forceinline__ void plain_scan(const PlainArgs& a, const uint32_t q, const uint32_t wg, unsigned char* smem) {
+    const int lane = threadIdx.x;
+    const PlainLaunch& s = a.s;
+    // ---- LDS carve (plain_lds_bytes; every offset a multiple of 16 B) ----
+    float* qf = reinterpret_cast<float*>(smem);                                      // vec_stride floats
+    uint64_t* heap_l = reinterpret_cast<uint64_t*>(qf + a.vec_stride);              // hl + 2 entries
+    uint32_t* bm = reinterpret_cast<uint32_t*>(heap_l + round_up_u32(s.hl + 2, 2));  // one bit per slot
+    uint32_t* ltab = bm + round_up_u32(s.slots / 32, 4);                             // the ids (lds_table)
+    uint32_t* vkey = ltab + (s.lds_table ? s.slots : 0u);
+    uint32_t* vid = vkey + round_up_u32(s.vcap, 4);
+    uint32_t* surv_id = vid + round_up_u32(s.vcap, 4);
+    uint32_t* surv_d = surv_id + 64;
+
+    for (uint32_t i = lane; i < a.vec_stride; i += WAVE) qf[i] = a.q_full[(size_t)q * a.vec_stride + i];
+    for (uint32_t i = lane; i < s.slots / 32; i += WAVE) bm[i] = 0u;
+    psync();
+
+    uint32_t* gtab = s.table_g + (size_t)wg * (s.lds_table ? 0u : s.slots);
+    const uint32_t smask = s.slots - 1;
+    const bool ltable = s.lds_table != 0;
+    uint32_t nins = 0;
+    PlainHeap heap{heap_l, s.heap_g + (size_t)wg * (s.hcap > s.hl ? s.hcap - s.hl : 0), s.hl, 0, 0};
+    uint32_t vhead = 0, vlen = 0, emitted = 0, status = 0;
+    uint32_t st_visits = 0, st_cand = 0, st_dq = 0, st_reads = 0, st_next = 0, st_invis = 0;
+
+    // HashSet::insert for the active lanes' node ids; returns true where the id was not present before.  The caller has checked
+    // that the table has room for every active lane (ins_limit), so a probe run always ends at a clear bit.
+    auto prepare_insert = [&](uint32_t nid, bool act) -> bool {
+        bool fresh = false, pending = act;
+        uint32_t slot = hash_u32(nid) & smask;
+        while (__ballot(pending)) {
+            if (pending) {
+                const uint32_t bit = 1u << (slot & 31u);
+                const uint32_t old = atomicOr(&bm[slot >> 5], bit);  // ds_or_rtn_b32
+                if (!(old & bit)) {                                 // first write of this slot by this scan: no load of the table
+                    if (ltable) *(pl_u32*)(ltab + slot) = nid;
+                    else *(pg_u32*)(gtab + slot) = nid;
+                    fresh = true;
+                    pending = false;
+                }
+            }
+            psync();  // a slot claimed in this round is stored before any lane that met its bit reads it
+            if (pending) {
+                const uint32_t v = ltable ? *(const pl_u32*)(ltab + slot) : *(const pg_u32*)(gtab + slot);
+                if (v == nid) pending = false;
+                else slot = (slot + 1) & smask;
+            }
+        }
+        nins += (uint32_t)__popcll(__ballot(fresh));
+        return fresh;
+    };
+
+    // ---- ListSearchResult::new from the default start node (AM/graph/mod.rs:97-124); empty() when there is none ----
+    if (a.default_start != VS_INVALID_NODE && a.n != 0) {
+        const uint32_t sn = a.default_start;
+        prepare_insert(sn, lane == 0);
+        st_reads++;
+        const float sdiv = a.distance_type == VS_COSINE ? a.vnorm[sn] : 0.0f;
+        const uint32_t d = rfl(plain_key(plain_dist8_hoisted(a.vecs + (size_t)sn * a.vec_stride, sdiv, qf, a.dim, a.distance_type, lane, lane < 8)));
+        st_dq++;
+        st_cand++;
+        if (s.hcap == 0) status |= OVF_HEAP;
+        else heap.push(((uint64_t)d << 32) | sn, lane);
+    }
+
+    uint32_t pf_node = VS_INVALID_NODE, pf_val = VS_INVALID_NODE;  // prefetched first chunk of a neighbor row
+
+    // ---- TSVResponseIterator::next, repeated until M rows are emitted (AM/scan.rs:210-242) ----
+    while (emitted < s.M && status == 0) {
+        st_next++;
+        bool got = false;
+        while (true) {  // "Iterate until we find a non-deleted tuple"
+            // ---- greedy_search_iterate (AM/graph/mod.rs:357-385) ----
+            while (true) {
+                // visit_closest(L) (AM/graph/mod.rs:153-170)
+                if (heap.len == 0) break;
+                if (vlen > s.L) {
+                    const uint32_t node_at_pos = rfl(vkey[vhead + s.L - 1]);
+                    if (rfl(PlainHeap::key(heap.get(0))) >= node_at_pos) break;
+                }
+                if (vlen + 1 > s.vcap) { status |= OVF_VISITED; break; }
+                const uint64_t head = heap.pop(lane);
+                const uint32_t hd = rfl(PlainHeap::key(head));
+                const uint32_t node = rfl((uint32_t)head);
+                // neighbor row (first 64 slots): prefetched during the previous expansion if the prediction held
+                const uint32_t* nrow = a.nbrs + (size_t)node * a.nbr_stride;
+                uint32_t row0;
+                if (node == pf_node) row0 = pf_val;
+                else row0 = ((uint32_t)lane < a.R) ? nrow[lane] : VS_INVALID_NODE;
+                // request the row of the new heap root: the most likely next expansion
+                if (heap.len > 0) {
+                    pf_node = rfl((uint32_t)heap.get(0));
+                    pf_val = ((uint32_t)lane < a.R) ? a.nbrs[(size_t)pf_node * a.nbr_stride + lane] : VS_INVALID_NODE;
+                } else {
+                    pf_node = VS_INVALID_NODE;
+                }
+                // visited.insert(partition_point(|x| *x < head), head): before the first element >= head
+                {
+                    uint32_t idx = 0;
+                    for (uint32_t base = 0; base < vlen; base += WAVE) {
+                        const uint32_t i = base + lane;
+                        const bool lt = i < vlen && vkey[vhead + i] < hd;
+                        idx += (uint32_t)__popcll(__ballot(lt));
+                    }
+                    uint32_t at;
+                    if (vhead > 0 && (2 * idx <= vlen || vhead + vlen >= s.vcap)) {
+                        // shift [0, idx) left by one into the room consume left at the head, bottom chunk first
+                        for (uint32_t lo = 0; lo < idx; lo += WAVE) {
+                            const uint32_t i = lo + lane;
+                            uint32_t td = 0, ti = 0;
+                            if (i < idx) { td = vkey[vhead + i]; ti = vid[vhead + i]; }
+                            psync();
+                            if (i < idx) { vkey[vhead + i - 1] = td; vid[vhead + i - 1] = ti; }
+                            psync();
+                        }
+                        vhead--;
+                        at = vhead + idx;
+                    } else {
+                        uint32_t hi = vlen;
+                        while (hi > idx) {  // shift [idx, vlen) right by one, top chunk first
+                            const uint32_t lo = (hi - idx > WAVE) ? hi - WAVE : idx;
+                            const uint32_t i = lo + lane;
+                            uint32_t td = 0, ti = 0;
+                            if (i < hi) { td = vkey[vhead + i]; ti = vid[vhead + i]; }
+                            psync();
+                            if (i < hi) { vkey[vhead + i + 1] = td; vid[vhead + i + 1] = ti; }
+                            psync();
+                            hi = lo;
+                        }
+                        at = vhead + idx;
+                    }
+                    if (lane == 0) { vkey[at] = hd; vid[at] = node; }
+                    vlen++;
+                    psync();
+                }
+                st_visits++;
+                // ---- visit_lsn_internal (AM/plain/storage.rs) ----
+                st_reads++;
+                bool list_ended = false;
+                for (uint32_t c0 = 0; c0 < a.R && !list_ended && status == 0; c0 += WAVE) {
+                    const uint32_t slot = c0 + lane;
+                    const uint32_t nid = c0 == 0 ? row0 : ((slot < a.R) ? nrow[slot] : VS_INVALID_NODE);
+                    // list ends at the first InvalidBlockNumber
+                    const uint64_t inval = __ballot(nid == VS_INVALID_NODE);
+                    const uint32_t nvalid = inval ? (uint32_t)__builtin_ctzll(inval) : WAVE;
+                    if (nvalid < WAVE) list_ended = true;
+                    const bool act = (uint32_t)lane < nvalid;
+                    if (s.ins_limit != 0xFFFFFFFFu && nins + nvalid > s.ins_limit) { status |= OVF_HASH; break; }
+                    const bool fresh = prepare_insert(nid, act);
+                    const uint64_t pm = __ballot(fresh);
+                    const uint32_t c = (uint32_t)__popcll(pm);
+                    st_reads += c;
+                    if (c == 0) continue;
+                    // compact survivors in neighbor-list order
+                    if (fresh) surv_id[__popcll(pm & ((1ull << lane) - 1ull))] = nid;
+                    psync();
+                    for (uint32_t p0 = 0; p0 < c; p0 += 8) {  // 8 lanes per vector row, 8 rows per pass
+                        const uint32_t j = p0 + (uint32_t)(lane >> 3);
+                        const bool valid = j < c;
+                        const uint32_t id = valid ? surv_id[j] : 0;
+                        const float sdiv = (valid && a.distance_type == VS_COSINE) ? a.vnorm[id] : 0.0f;
+                        const float r = plain_dist8_hoisted(a.vecs + (size_t)id * a.vec_stride, sdiv, qf, a.dim, a.distance_type, lane, valid);
+                        if (valid && (lane & 7) == 0) surv_d[j] = plain_key(r);
+                    }
+                    st_dq += c;
+                    st_cand += c;
+                    if (heap.len + c > s.hcap) { status |= OVF_HEAP; break; }
+                    psync();
+                    // insert_neighbor in list order (AM/graph/mod.rs:144-147)
+                    const uint32_t my_d = (uint32_t)lane < c ? surv_d[lane] : 0u, my_id = (uint32_t)lane < c ? surv_id[lane] : 0u;
+                    for (uint32_t j = 0; j < c; ++j) {
+                        const uint32_t d = (uint32_t)__builtin_amdgcn_readlane((int)my_d, (int)j);
+                        const uint32_t id = (uint32_t)__builtin_amdgcn_readlane((int)my_id, (int)j);
+                        heap.push(((uint64_t)d << 32) | id, lane);
+                    }
+                }
+                if (status) break;
+            }
+            if (status) break;
+            // ---- consume (AM/graph/mod.rs:174-184): visited.remove(0) moves the head ----
+            if (vlen == 0) break;  // None
+            const uint32_t fd = rfl(vkey[vhead]);
+            const uint32_t fnode = rfl(vid[vhead]);
+            vhead++;
+            vlen--;
+            if (vlen == 0) vhead = 0;
+            st_reads++;
+            const uint64_t tid = a.tids[fnode];
+            if ((tid & 0xFFFFull) == 0) continue;  // InvalidOffsetNumber: deleted tuple (AM/scan.rs:231-234)
+            if (s.visible && s.visible[fnode] == 0) {  // get_full_distance_for_resort -> None (AM/scan.rs:268-272)
+                st_invis++;
+                st_next++;  // the caller's loop asks `next` again
+                continue;
+            }
+            if (lane == 0) {
+                s.out_ids[(size_t)q * s.M + emitted] = fnode;
+                s.out_ham[(size_t)q * s.M + emitted] = fd;
+            }
+            emitted++;
+            got = true;
+            break;
+        }
+        if (!got) break;
+    }
+    if (status) emitted = 0;  // a scan that outgrew a capacity publishes an empty stream: the general kernel re-runs it whole
+    for (uint32_t i = emitted + lane; i < s.M; i += WAVE) {
+        s.out_ids[(size_t)q * s.M + i] = VS_INVALID_NODE;
+        s.out_ham[(size_t)q * s.M + i] = 0xFFFFFFFFu;
+    }
+    if (lane == 0) {
+        s.out_cnt[q] = emitted;
+        s.status[q] = status;
+        uint32_t* st = s.stats + (size_t)q * ST_N;
+        st[ST_VISITS] = st_visits;
+        st[ST_CAND] = st_cand;
+        st[ST_DQ] = st_dq;
+        st[ST_READS] = st_reads;
+        st[ST_NEXT] = st_next;
+        st[ST_GSPILL] = heap.maxlen;
+        st[ST_INVIS] = st_invis;
+        st[ST_INS] = nins;
+    }
+}
+
+__global__ __launch_bounds__(WAVE) void k_search_plain(PlainArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    // persistent grid: each single-wave workgroup takes scan after scan from the counter and reuses its own regions
+    while (true) {
+        uint32_t q = 0;
+        if (threadIdx.x == 0) q = atomicAdd(a.s.scan_counter, 1u);
+        q = rfl(q);
+        if (q >= a.s.nq) return;
+        plain_scan(a, q, blockIdx.x, smem);
+        psync();  // the next scan re-initialises the LDS state: every lane is done with this one's
+    }
+}
+
+// LDS of one scan of k_search_plain, in bytes:
+//   4 * vec_stride                      the prepared query slice
+// + 8 * round_up(hl + 2, 2)             the heap's LDS part
+// + 4 * round_up(slots / 32, 4)         one occupancy bit per dedup slot
+// + 4 * slots (lds_table only)          the dedup table's ids
+// + 8 * round_up(vcap, 4)               visited list (keys, nodes)
+// + 512                                 the survivors of a pass (ids, keys)
+size_t plain_lds_bytes(const vs_index* idx, const PlainLaunch& s) {
+    const size_t b = (size_t)idx->vec_stride * 4 + (size_t)round_up_u32(s.hl + 2, 2) * 8 + (size_t)round_up_u32(s.slots / 32, 4) * 4 +
+                     (s.lds_table ? (size_t)s.slots * 4 : 0) + 2 * (size_t)round_up_u32(s.vcap, 4) * 4 + 128 * 4;
+    return (b + 15) / 16 * 16;
+}
+
+static int plain_dispatch(vs_index* idx, const PlainLaunch& s, uint32_t* resident) {
+    VS_REQUIRE(idx->d.storage_type == VS_STORAGE_PLAIN && idx->vecs, "plain search kernel: not a plain-storage index with its vector column");
+    VS_REQUIRE(s.slots >= 64 && (s.slots & (s.slots - 1)) == 0 && (s.ins_limit == 0xFFFFFFFFu ? idx->d.n < s.slots : s.ins_limit <= s.slots / 4 * 3),
+               "plain search kernel: the dedup table must be a power of two of slots with room beyond its limit");
+    VS_REQUIRE(s.vcap >= 1 && s.L >= 1, "plain search kernel: bad capacities");
+    const size_t lds = plain_lds_bytes(idx, s);
+    VS_REQUIRE(lds <= 160 * 1024, "plain search state does not fit LDS (%zu B)", lds);
+    static DeviceOnce attr_set;
+    const int attr_dev = idx->ctx->device;
+    if (attr_set.pending(attr_dev)) {
+        VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_search_plain), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_set.done(attr_dev);
+    }
+    if (resident) {
+        int per_cu = 0;
+        VS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_search_plain, WAVE, lds));
+        *resident = (uint32_t)std::max(per_cu, 1) * (uint32_t)idx->ctx->prop.multiProcessorCount;
+        return VS_OK;
+    }
+    VS_REQUIRE(s.persist >= 1 && s.scan_counter && s.heap_g && (s.lds_table || s.table_g), "plain search kernel: a persistent grid needs its counter and regions");
+    PlainArgs a;
+    a.nbrs = idx->nbrs;
+    a.tids = idx->tids;
+    a.vecs = idx->vecs;
+    const bool truncated = idx->d.dim_index < idx->d.dim_full;  // index slice: its own norm cache / prepared query
+    a.vnorm = truncated ? idx->vnorm_idx : idx->vnorm;
+    a.q_full = (const float*)(truncated ? idx->ws.q_index.p : idx->ws.q_full.p);
+    a.nbr_stride = idx->nbr_stride;
+    a.R = idx->d.num_neighbors;
+    a.n = idx->d.n;
+    a.default_start = idx->d.default_start;
+    a.vec_stride = idx->vec_stride;
+    a.dim = idx->d.dim_index;
+    a.distance_type = idx->d.distance_type;
+    VS_REQUIRE(a.q_full, "plain search kernel: no prepared queries");
+    VS_REQUIRE(a.distance_type != VS_COSINE || a.vnorm, "plain storage search: the cosine divisors of the index slices are missing");
+    a.s = s;
+    hipLaunchKernelGGL(k_search_plain, dim3(std::min(s.persist, s.nq)), dim3(WAVE), lds, idx->ctx->stream, a);
+    VS_HIP(hipGetLastError());
+    return VS_OK;
+}
+
+int launch_search_plain(vs_index* idx, const PlainLaunch& s) {
+    if (s.nq == 0) return VS_OK;
+    return plain_dispatch(idx, s, nullptr);
+}
+int plain_resident_scans(vs_index* idx, const PlainLaunch& s, uint32_t* out) { return plain_dispatch(idx, s, out); }

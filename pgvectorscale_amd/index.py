@@ -226,6 +226,13 @@ class DiskAnnIndex:
     def _refresh(self):
         check(self._L.vs_index_get_desc(self.h, C.byref(self.desc)))
 
+    def last_search_info(self):
+        """which kernel the first attempt of this handle's last batch ran (kernel: VS_SEARCH_GENERAL / _FAST_SBQ / _FAST_PLAIN), the scans
+        resident on its persistent grid, its LDS per scan and planned capacities (vs_index_last_search_info)"""
+        info = _lib.SearchInfo()
+        check(self._L.vs_index_last_search_info(self.h, C.byref(info)))
+        return info.as_dict()
+
     def rerank_order(self):
         """the rerank order of the last batch (VS_RERANK_ORDER): place -> scan number; empty when it took the scans' own order"""
         n = C.c_uint32()

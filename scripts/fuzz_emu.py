@@ -123,12 +123,19 @@ def plain_case(ctx, O, case_seed, verbose):
         os.environ.pop(v, None)
     ix = pi.upload(ctx)
     try:
-        gi, gt, gd, gst = ix.search_batch(q, search_list_size=L, rescore=50, k=k)
+        from pgvectorscale_amd.index import set_option
         oi, od, ost = pi.oracle.search_batch(q, L=L, rescore=50, k=k)
-        assert (gi == oi).all(), f"{where}: ids differ"
-        assert (gd.view(np.uint32) == od.view(np.uint32)).all(), f"{where}: distance bits differ"
-        for c in ("visited_nodes", "candidate_nodes", "full_distance_comparisons"):
-            assert gst[c] == ost[c], f"{where}: counter {c}"
+        for fast in ("1", "0"):  # k_search_plain first / the general kernel alone: both against the oracle
+            set_option("VS_PLAIN_FAST", fast)
+            try:
+                gi, gt, gd, gst = ix.search_batch(q, search_list_size=L, rescore=50, k=k)
+            finally:
+                set_option("VS_PLAIN_FAST", None)
+            w = f"{where} VS_PLAIN_FAST={fast}"
+            assert (gi == oi).all(), f"{w}: ids differ"
+            assert (gd.view(np.uint32) == od.view(np.uint32)).all(), f"{w}: distance bits differ"
+            for c in ("visited_nodes", "candidate_nodes", "full_distance_comparisons"):
+                assert gst[c] == ost[c], f"{w}: counter {c}"
         gettuple_mirror(ix, pi.oracle, q, None, L, 50, np.random.default_rng(case_seed + 1), where, exact_dist=True)
     finally:
         ix.close()
