@@ -136,7 +136,12 @@ int vs_index_last_search_info(const vs_index* idx, vs_search_info* out);
  * vs_stats.fallback_scans); "0" the general kernel alone.  Rows, distance bits and the reference counters are the same under both.
  * Its capacities, for tests and measurement (0 / unset = planned from n, num_neighbors, the search list size and the stream length):
  * VS_PF_HEAP_LDS (heap entries kept in LDS), VS_PF_HEAP_CAP (heap entries in all), VS_PF_DEDUP_SLOTS (slots of the dedup table,
- * rounded up to a power of two), VS_PF_VISITED (visited-list capacity), VS_PF_SCANS_PER_CU (upper bound of the persistent grid). */
+ * rounded up to a power of two), VS_PF_VISITED (visited-list capacity), VS_PF_SCANS_PER_CU (upper bound of the persistent grid).
+ * VS_POOL_PLAIN_FAST: which kernel continues the scans of a scan pool (vs_scanpool_*) over a `plain` storage index — "1" (default) the
+ * resumable form of k_search_plain, one wave per pool slot with the scan's state on chip during a launch and saved per slot between
+ * launches, where that state fits 96 KB of LDS; "0" (or VS_POOL_FAST "0") the general kernel.  Read when a pool is created, as
+ * are VS_PF_HEAP_LDS / VS_PF_HEAP_CAP / VS_PF_DEDUP_SLOTS / VS_PF_VISITED, which override the pool's planned capacities too (a pooled
+ * scan that outgrows one fails with VS_ERR_CAPACITY).  Rows, distance bits and the reference counters are the same under both. */
 int vs_set_option(const char* name, const char* value);
 int vs_get_option(const char* name, char* out, size_t cap);
 const char* vs_version(void);
@@ -844,7 +849,12 @@ void vs_endscan(vs_scan* scan);                                                 
  * does with the amgettuple calls of many backends that arrive together.  Rows and GreedySearchStats are the single cursor's, row
  * for row.  All scans of a pool share the GUCs (search_list_size, rescore) and the visibility mask in force; scan keys are per
  * scan (slot).  kmax = most rows one fetch asks for; rows_cap = most stream rows a pooled scan may produce (0: 4096) — a scan that
- * needs more fails with VS_ERR_CAPACITY in its out_rows entry and is continued by a vs_scan of its own.  One thread at a time. */
+ * needs more fails with VS_ERR_CAPACITY in its out_rows entry and is continued by a vs_scan of its own.  One thread at a time.
+ * Which kernel continues the scans is decided at creation: for SBQ storage the resumable instantiation of the fast kernel, for
+ * `plain` storage the resumable form of k_search_plain (VS_POOL_PLAIN_FAST, above) — both sized for the worst case of a scan of
+ * rows_cap rows — and the general kernel where neither applies (wide codes, a state beyond 96 KB of LDS, VS_POOL_FAST "0").  The
+ * plain form clamps its capacities to the n of the pool's creation: after vs_index_insert has grown a plain index, free the pool and
+ * create it again (one that is kept and rescanned may fail scans the grown index makes longer with VS_ERR_CAPACITY). */
 typedef struct vs_scan_pool vs_scan_pool;
 int vs_scanpool_create(vs_index* idx, uint32_t capacity, uint32_t search_list_size, uint32_t rescore, uint32_t kmax, uint32_t rows_cap,
                        vs_scan_pool** out);
@@ -858,6 +868,11 @@ int vs_scanpool_fetch(vs_scan_pool* pool, const uint32_t* slots, uint32_t n, uin
                       float* out_dist, int32_t* out_rows);
 int vs_scanpool_get_stats(const vs_scan_pool* pool, uint32_t slot, vs_stats* out);  /* as vs_scan_get_stats */
 int vs_scanpool_get_work(const vs_scan_pool* pool, uint64_t* launches, uint64_t* rounds);  /* shared search launches / rounds so far */
+/* Which kernel the pool's continuations run (kernel: VS_SEARCH_GENERAL / _FAST_SBQ / _FAST_PLAIN) — valid before the first fetch.
+ * resident = the pool's capacity for the two fast kernels (one single-wave workgroup per slot), 0 for the general one; lds_bytes =
+ * dynamic LDS per scan; heap_lds / dedup_slots / visited_cap = the planned on-chip capacities of the fast kernels (0 for the general
+ * one).  Read-only.  VS_ERR_INVALID for NULL arguments. */
+int vs_scanpool_info(const vs_scan_pool* pool, vs_search_info* out);
 
 /* ---- coalescing concurrent scans into batched launches (vs_broker.cpp) -------------------
  * The reference serves one query per single-threaded backend (amcanparallel = false, AM/mod.rs:63); a GPU needs thousands

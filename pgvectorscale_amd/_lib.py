@@ -222,6 +222,7 @@ SYMBOLS = {
     "vs_scanpool_fetch": (_i, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
     "vs_scanpool_get_stats": (_i, [_vp, _u32, _vp]),
     "vs_scanpool_get_work": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
+    "vs_scanpool_info": (_i, [_vp, C.POINTER(SearchInfo)]),
     "vs_index_set_slab": (_i, [_vp, _vp, C.c_size_t]),
     "vs_ws_probe": (_i, [_vp, _vp, C.c_size_t, C.c_uint32, C.POINTER(C.c_float)]),
     "vs_ws_probe_mix": (_i, [_vp, _vp, C.c_size_t, C.c_uint32, C.POINTER(C.c_float)]),

@@ -714,7 +714,6 @@ static const size_t PLAIN_LDS_BUDGET = 40 * 1024;
 // ... and what the heap's LDS part is sized to: 8 scans per CU, the lower end of the range the row gathers need
 // (MI355X_MICROARCH.md "Indexed rows": 16 waves per CU at 4 rows in flight)
 static const size_t PLAIN_LDS_TARGET = 20 * 1024;
-static const uint32_t PLAIN_LDS_TABLE_MAX = 1024;  // slots up to which the dedup table's ids live in LDS (4 KB)
 
 // Enqueues nothing and touches no buffer; its only device-facing call is the occupancy query.  *on = false: the general kernel
 // runs alone, as before.

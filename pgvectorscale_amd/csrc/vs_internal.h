@@ -442,9 +442,26 @@ struct PlainLaunch {
     uint32_t* out_cnt = nullptr;
     uint32_t* stats = nullptr;
     uint32_t* status = nullptr;
+    // the prepared queries [nq][vec_stride] (for a truncated index: the index slices); null: the batch workspace's
+    const float* q_prepared = nullptr;
+    // resumable scans (the scan pools; k_search_plain_rs, as FastLaunch::resume): one single-wave workgroup per pool slot, no
+    // persistent grid and no scan_counter.  status[q] != 0 on entry marks the scans that run.  resume[q * resume_stride ..] is scan
+    // q's saved state — header RSP_* + the LDS image (heap top, occupancy bits, LDS table, visited keys and nodes); region q of
+    // heap_g / table_g belongs to the SLOT and lives on between launches.  A launch continues the scan for M more rows
+    // (out_ids[q][0..M)); row_stats: [nq][M][ST_N] the work counters as each row left next() (or null).
+    uint32_t* resume = nullptr;
+    uint32_t resume_stride = 0;
+    uint32_t* row_stats = nullptr;
 };
+// header of a saved plain scan (u32 words), followed by the LDS image; RSP_ENDED: next() has returned None (the stream is over for good)
+enum { RSP_INIT = 0, RSP_HLEN, RSP_HMAX, RSP_VHEAD, RSP_VLEN, RSP_NINS, RSP_VISITS, RSP_CAND, RSP_DQ, RSP_READS, RSP_NEXT, RSP_INVIS,
+       RSP_STATUS, RSP_EMITTED, RSP_ENDED, RSP_HDR = 16 };
+static_assert((int)RSP_HDR == (int)RS_HDR && (int)RSP_HDR == (int)RSF_HDR, "a pool clears one header size at amrescan, whichever kernel continues its scans");
+static const uint32_t PLAIN_LDS_TABLE_MAX = 1024;  // slots up to which the dedup table's ids live in LDS (4 KB)
 size_t plain_lds_bytes(const vs_index* idx, const PlainLaunch& s);
+size_t plain_resume_words(const PlainLaunch& s);  // u32 words of one saved scan at these capacities (a multiple of 4)
 int launch_search_plain(vs_index* idx, const PlainLaunch& s);
+int launch_search_plain_rs(vs_index* idx, const PlainLaunch& s);  // grid = s.nq pool slots; persist / scan_counter are not used
 int plain_resident_scans(vs_index* idx, const PlainLaunch& s, uint32_t* out);  // workgroups of k_search_plain the device holds at once
 enum { ST_VISITS = 0, ST_CAND = 1, ST_DQ = 2, ST_READS = 3, ST_NEXT = 4, ST_GSPILL = 5, ST_INVIS = 6, ST_INS = 7 /* ids the fast kernel inserted */, ST_N = 8 };
 enum { OVF_HEAP = 1, OVF_VISITED = 2, OVF_HASH = 4, OVF_POOL = 8,

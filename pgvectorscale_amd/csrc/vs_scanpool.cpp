@@ -10,6 +10,11 @@
 // k_rerank launch and one round of k_resort_cursor launches serve every scan that asked for rows in this round.  Nothing here is a new
 // kernel: the launch wrappers of vs_internal.h are the single cursor's.
 //
+// Which kernel continues the scans is decided when the pool is created (vs_scanpool_info tells): the resumable instantiation of
+// k_search_fast for SBQ indexes, the resumable form of k_search_plain (k_search_plain_rs) for `plain` storage — both keep a scan's
+// state on chip during a launch and save it per slot between launches — and the general kernel wherever those do not apply (codes
+// wider than the register-resident widths, a state beyond 96 KB of LDS, VS_POOL_FAST=0, VS_POOL_PLAIN_FAST=0, an empty index).
+//
 // Semantics are the single cursor's, row for row (tests/test_gpu_zt_scanpool.py holds the pool to the oracle and to vs_gettuple):
 // rows in next_with_resort order (AM/scan.rs:244-305), GreedySearchStats as they stand after exactly the calls made so far (the work
 // counters are recorded per emitted stream row).  All scans of a pool share the GUCs (diskann.query_search_list_size, query_rescore:
@@ -42,10 +47,14 @@ struct vs_scan_pool {
     uint32_t cap = 0, L = 0, rescore = 0, S = 0, kmax = 0, rows_cap = 0, mmax = 0;
     uint32_t hl = 0, hcap = 0, vcap = 0, lh = 0, hashcap = 0, g0 = 0, rw = 0;
     // round 6: the continuations run the RESUMABLE instantiation of the fast kernel (k_search_fast, OPT_RS: heap top, occupancy bits and
-    // visited ring on chip, 16-bit dedup tables) where the index and the capacities allow it — the general kernel otherwise (plain
-    // storage, codes wider than the register-resident widths, a state that does not fit LDS, VS_POOL_FAST=0).  `fl` holds the geometry.
+    // visited ring on chip, 16-bit dedup tables) where the index and the capacities allow it — the general kernel otherwise (codes
+    // wider than the register-resident widths, a state that does not fit LDS, VS_POOL_FAST=0).  `fl` holds the geometry.
     bool fast = false;
     FastLaunch fl{};
+    // `plain` storage: the continuations run k_search_plain_rs (vs_search.hip) with the geometry in `pl`, planned once for the worst
+    // case of a scan of rows_cap rows (plan_plain_pool)
+    bool plain_fast = false;
+    PlainLaunch pl{};
     std::vector<Slot> slots;
     bool csr_dirty = true;
     DevBuf raw_q, q_full, q_index, qcodes, qlabels, qlabel_off, heap_g, hash, state, cnt, stats, status, row_stats, stage, all, resort_heap,
@@ -93,6 +102,50 @@ static uint32_t pool_env_u32(const char* name, uint32_t dflt) {
     return v && *v ? (uint32_t)strtoul(v, nullptr, 10) : dflt;
 }
 
+// LDS a pooled scan's state may take on either fast kernel (as little as one scan per CU: a pool's launch is one wave per slot, and
+// what bounds a round is the life of its longest scan, not how many share a CU)
+static const size_t POOL_LDS_BUDGET = 96 * 1024;
+
+// The geometry of k_search_plain_rs for a pool of scans of up to rows_cap rows, or false: the pool stays on the general kernel.  A
+// pooled scan that outgrows a capacity is a hard VS_ERR_CAPACITY for its backend, so — unlike plan_plain_launch, which sizes a batch
+// for the expected scan and hands the rest over — every capacity is the general pool's worst case (`pushes` ids), clamped to the
+// index: a scan inserts at most n ids, holds at most n heap entries and has at most n nodes in its visited list.
+static bool plan_plain_pool(const vs_index* ix, uint32_t L, uint64_t pushes, PlainLaunch* out) {
+    if (ix->d.storage_type != VS_STORAGE_PLAIN || !ix->vecs || ix->d.n == 0) return false;
+    if (pool_env_u32("VS_POOL_FAST", 1) == 0 || pool_env_u32("VS_POOL_PLAIN_FAST", 1) == 0) return false;
+    const uint64_t n = ix->d.n;
+    PlainLaunch p{};
+    p.L = L;
+    // the table holds min(pushes + 1, n) ids (every push and the start node) under its 3/4 load limit; the kernel asks for room for a
+    // whole chunk of a neighbor list before it looks which of its ids are new, hence one wave of slack
+    const uint64_t ids = std::min<uint64_t>(pushes + 1 + 64, n);
+    if (ids * 4 / 3 + 1 > (1u << 22)) return false;
+    p.slots = std::max<uint32_t>(next_pow2_u32((uint32_t)(ids * 4 / 3 + 1)), 64);
+    if (const uint32_t v = pool_env_u32("VS_PF_DEDUP_SLOTS", 0)) p.slots = std::max<uint32_t>(next_pow2_u32(std::min<uint32_t>(v, 1u << 22)), 64);
+    p.ins_limit = n <= p.slots / 4 * 3 ? 0xFFFFFFFFu : p.slots / 4 * 3;
+    p.lds_table = p.slots <= PLAIN_LDS_TABLE_MAX ? 1u : 0u;
+    p.vcap = (uint32_t)std::min<uint64_t>(2ull * L + 256, n + 1);
+    if (const uint32_t v = pool_env_u32("VS_PF_VISITED", 0)) p.vcap = v;
+    // the heap's LDS part: the largest of 1023 / 511 / 255 / 127 entries that keeps the scan within the budget
+    p.hl = 0;
+    for (uint32_t hl : {1023u, 511u, 255u, 127u}) {
+        PlainLaunch t = p;
+        t.hl = hl;
+        if (plain_lds_bytes(ix, t) <= POOL_LDS_BUDGET) {
+            p.hl = hl;
+            break;
+        }
+    }
+    if (p.hl == 0) return false;
+    p.hcap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(pushes, p.hl), n);
+    if (const uint32_t v = pool_env_u32("VS_PF_HEAP_LDS", 0)) p.hl = v;
+    if (const uint32_t v = pool_env_u32("VS_PF_HEAP_CAP", 0)) p.hcap = v;
+    p.hl = std::min(p.hl, p.hcap);
+    if (p.vcap < 1 || plain_lds_bytes(ix, p) > POOL_LDS_BUDGET) return false;
+    *out = p;
+    return true;
+}
+
 static int scanpool_create_impl(vs_index* ix, uint32_t capacity, uint32_t L, uint32_t rescore, uint32_t kmax, uint32_t rows_cap, vs_scan_pool** out) {
     VS_REQUIRE(ix && out && capacity >= 1 && capacity <= 4096, "vs_scanpool_create: bad args (1..4096 slots)");
     VS_REQUIRE(L >= 1 && L <= 10000, "diskann.query_search_list_size %u outside [1,10000]", L);
@@ -135,11 +188,15 @@ static int scanpool_create_impl(vs_index* ix, uint32_t capacity, uint32_t L, uin
         f.gcap = std::max<uint32_t>(next_pow2_u32(std::min<uint64_t>(pushes * 4 / 3 + 256, 1u << 22)), 1024);
         f.glimit = (uint32_t)((uint64_t)f.gcap * 3 / 4) - 64u;
         const uint32_t nch = (ix->code_stride + 7) / 8;
-        if (fast_tables16_geometry(ix, f) && nch <= 6 && fast_lds_bytes(ix, f) <= 96 * 1024) {
+        if (fast_tables16_geometry(ix, f) && nch <= 6 && fast_lds_bytes(ix, f) <= POOL_LDS_BUDGET) {
             p->fast = true;
             p->fl = f;
             p->rw = (uint32_t)fast_resume_words(f);
         }
+    }
+    if (plan_plain_pool(ix, L, pushes, &p->pl)) {
+        p->plain_fast = true;
+        p->rw = (uint32_t)plain_resume_words(p->pl);
     }
     p->slots.resize(capacity);
     const size_t G = capacity;
@@ -153,6 +210,9 @@ static int scanpool_create_impl(vs_index* ix, uint32_t capacity, uint32_t L, uin
         if (p->fast) {
             VS_TRY(devbuf_reserve(c, p->heap_g, std::max<size_t>(G * (size_t)p->fl.gstride * 4, 16)));
             VS_TRY(devbuf_reserve(c, p->hash, G * (size_t)p->fl.gregion * 4));
+        } else if (p->plain_fast) {  // the slots' regions: never cleared, so they only have to exist
+            VS_TRY(devbuf_reserve(c, p->heap_g, std::max<size_t>(G * (size_t)(p->pl.hcap - p->pl.hl) * 8, 16)));
+            VS_TRY(devbuf_reserve(c, p->hash, std::max<size_t>(p->pl.lds_table ? 0 : G * (size_t)p->pl.slots * 4, 16)));
         } else {
             VS_TRY(devbuf_reserve(c, p->heap_g, std::max<size_t>(G * (size_t)(p->hcap > p->hl ? p->hcap - p->hl : 0) * 8, 16)));
             VS_TRY(devbuf_reserve(c, p->hash, G * (size_t)p->hashcap * 4));
@@ -195,7 +255,7 @@ extern "C" void vs_scanpool_free(vs_scan_pool* p) {
     if (!p) return;
     if (pool_env_u32("VS_POOL_DEBUG", 0))
         fprintf(stderr, "[VS_POOL_DEBUG] pool L=%u rescore=%u (%s kernel): %llu fetch calls serving %llu scan chunks in %llu rounds (%llu search launches); host ms: "
-                        "search %.1f, rerank+append %.1f, resort+rows %.1f\n", p->L, p->rescore, p->fast ? "resumable fast" : "general", (unsigned long long)p->fetches,
+                        "search %.1f, rerank+append %.1f, resort+rows %.1f\n", p->L, p->rescore, p->fast ? "resumable fast" : p->plain_fast ? "resumable plain" : "general", (unsigned long long)p->fetches,
                 (unsigned long long)p->scans_served, (unsigned long long)p->rounds, (unsigned long long)p->launches, p->t_search * 1e3, p->t_append * 1e3,
                 p->t_resort * 1e3);
     if (pool_env_u32("VS_POOL_DEBUG", 0))
@@ -322,6 +382,33 @@ static int round_launch(vs_scan_pool* p, const std::vector<uint32_t>& run, uint3
             f.row_stats = (uint32_t*)p->row_stats.p;
             hipEvent_t ev = prof_begin(c);
             const int lr = launch_search_fast(ix, f);
+            prof_end(c, PK_SEARCH, ev);
+            VS_TRY(lr);
+            p->launches++;
+            continue;
+        }
+        if (p->plain_fast) {
+            const bool truncated = ix->d.dim_index < ix->d.dim_full;  // the index slice has its own prepared queries
+            PlainLaunch f = p->pl;
+            f.nq = nq;
+            f.M = M;
+            // (the capacities were clamped to the n of the pool's creation; an index that has grown since may fill the table, so the
+            // load limit is taken from the n of today: a scan that outgrows the plan fails for its backend like any other)
+            f.ins_limit = ix->d.n <= f.slots / 4 * 3 ? 0xFFFFFFFFu : f.slots / 4 * 3;
+            f.q_prepared = (const float*)(truncated ? p->q_index.p : p->q_full.p);
+            f.heap_g = (uint64_t*)p->heap_g.p;
+            f.table_g = (uint32_t*)p->hash.p;
+            f.out_ids = stage_ids;  // [slot][M]
+            f.out_ham = stage_ham;
+            f.out_cnt = (uint32_t*)p->cnt.p;
+            f.stats = (uint32_t*)p->stats.p;
+            f.status = d_status;  // the run mask on entry, the scan's outcome on exit
+            f.visible = p->S > 0 ? ix->visible : nullptr;
+            f.resume = (uint32_t*)p->state.p;
+            f.resume_stride = p->rw;
+            f.row_stats = (uint32_t*)p->row_stats.p;
+            hipEvent_t ev = prof_begin(c);
+            const int lr = launch_search_plain_rs(ix, f);
             prof_end(c, PK_SEARCH, ev);
             VS_TRY(lr);
             p->launches++;
@@ -468,13 +555,14 @@ static int pool_round(vs_scan_pool* p, const std::vector<uint32_t>& run, uint32_
 // (0.6 ms for 64 rows at search_list_size 100) during which every backend of that fetch waits: with 64 backends streaming 1 000 rows each the
 // rounds were 15 of the 35 ms.  Launched one fetch early on a stream of its own, the round runs while the rows already there are
 // handed out.  What keeps it simple: ONE round in flight; only scans without label keys, only while no snapshot mask is in force
-// (a mask may be replaced while the round runs) and only on the resumable fast kernel — everything else takes the rounds it waits
+// (a mask may be replaced while the round runs) and only on the two resumable fast kernels, which take their queries from the pool's own
+// arrays (the general kernel's plain launch borrows the batch workspace's query slots) — everything else takes the rounds it waits
 // for; a scan is carried at most two rounds ahead of its executor and never past its row budget; the per-row counters hide what the
 // executor has not pulled.
 static int prefetch_round(vs_scan_pool* p, const uint32_t* slots, uint32_t n, uint32_t k) {
     vs_index* ix = p->ix;
     vs_ctx* c = ix->ctx;
-    if (p->fly.active || !p->fast || ix->visible != nullptr || !pool_env_u32("VS_POOL_PREFETCH", 1)) return VS_OK;
+    if (p->fly.active || !(p->fast || p->plain_fast) || ix->visible != nullptr || !pool_env_u32("VS_POOL_PREFETCH", 1)) return VS_OK;
     const uint32_t S = p->S;
     const uint32_t M = std::min<uint32_t>(4 * k, p->mmax);
     std::vector<uint32_t> run;
@@ -676,6 +764,30 @@ extern "C" int vs_scanpool_get_stats(const vs_scan_pool* p, uint32_t slot, vs_st
         st.node_heap_reads += nr;
     }
     *out = st;
+    return VS_OK;
+}
+
+// which kernel the pool's continuations run and with which planned capacities: decided at creation, so valid before the first fetch
+extern "C" int vs_scanpool_info(const vs_scan_pool* p, vs_search_info* out) {
+    if (!p || !out) {
+        vs_set_error("vs_scanpool_info: NULL argument");
+        return VS_ERR_INVALID;
+    }
+    vs_search_info i{};
+    if (p->fast) {
+        const FastLaunch& f = p->fl;
+        i = vs_search_info{VS_SEARCH_FAST_SBQ, p->cap, (uint32_t)fast_lds_bytes(p->ix, f), f.hl, f.lh + f.gcap, f.vr ? 512u : f.vcap, {0, 0}};
+    } else if (p->plain_fast) {
+        const PlainLaunch& f = p->pl;
+        i = vs_search_info{VS_SEARCH_FAST_PLAIN, p->cap, (uint32_t)plain_lds_bytes(p->ix, f), f.hl, f.slots, f.vcap, {0, 0}};
+    } else {
+        SearchLaunch g{};
+        g.hl = p->hl;
+        g.lh = p->lh;
+        g.vcap = p->vcap;
+        i = vs_search_info{VS_SEARCH_GENERAL, 0, (uint32_t)search_lds_bytes(p->ix, g), 0, 0, 0, {0, 0}};
+    }
+    *out = i;
     return VS_OK;
 }
 

@@ -820,6 +820,14 @@ __device__ __forceinline__ float plain_dist8_hoisted(const float* __restrict__ r
     return r;
 }
 
+// RS = RESUMABLE scans (the amgettuple continuations of the scan pools; as OPT_RS of k_search_fast and SearchLaunch::resume of
+// k_search): `wg` is the pool slot, whose regions of heap_g / table_g live on between launches; the on-chip state — everything from
+// the heap top to the visited nodes is ONE contiguous, 16-byte aligned stretch of LDS — is restored from and saved to s.resume with
+// 16-byte accesses per lane, next to a header of scalars (RSP_*).  The occupancy bits are part of that image: a clear bit still means
+// "never written by this scan", launches later, so the regions are never cleared; the bits are cleared only when a slot starts a new scan
+// (RSP_INIT == 0 after amrescan).  The neighbor-row prefetch is not state: it restarts empty.  A launch continues the scan for M more
+// rows and records the counters as each row left next().
+template <bool RS>
 __device__ __forceinline__ void plain_scan(const PlainArgs& a, const uint32_t q, const uint32_t wg, unsigned char* smem) {
     const int lane = threadIdx.x;
     const PlainLaunch& s = a.s;
@@ -834,7 +842,17 @@ __device__ __forceinline__ void plain_scan(const PlainArgs& a, const uint32_t q,
     uint32_t* surv_d = surv_id + 64;
 
     for (uint32_t i = lane; i < a.vec_stride; i += WAVE) qf[i] = a.q_full[(size_t)q * a.vec_stride + i];
-    for (uint32_t i = lane; i < s.slots / 32; i += WAVE) bm[i] = 0u;
+    uint32_t* const rs = RS ? s.resume + (size_t)q * s.resume_stride : nullptr;
+    const bool resumed = RS && rfl(rs[RSP_INIT]) == 1u;
+    // (resumable scans) the image of a saved scan: heap top | occupancy bits | LDS table | visited keys | visited nodes — every piece a
+    // multiple of 16 bytes, heap_l 16-byte aligned (vec_stride is a multiple of 4) and so is the saved copy (plain_resume_words)
+    const uint32_t image_words = RS ? (uint32_t)((vid + round_up_u32(s.vcap, 4)) - reinterpret_cast<uint32_t*>(heap_l)) : 0u;
+    if (resumed) {
+        uint32_t* const img = reinterpret_cast<uint32_t*>(heap_l);
+        for (uint32_t i = 4u * lane; i < image_words; i += 4u * WAVE) *reinterpret_cast<uint4*>(img + i) = *reinterpret_cast<const uint4*>(rs + RSP_HDR + i);
+    } else {
+        for (uint32_t i = lane; i < s.slots / 32; i += WAVE) bm[i] = 0u;
+    }
     psync();
 
     uint32_t* gtab = s.table_g + (size_t)wg * (s.lds_table ? 0u : s.slots);
@@ -844,6 +862,22 @@ __device__ __forceinline__ void plain_scan(const PlainArgs& a, const uint32_t q,
     PlainHeap heap{heap_l, s.heap_g + (size_t)wg * (s.hcap > s.hl ? s.hcap - s.hl : 0), s.hl, 0, 0};
     uint32_t vhead = 0, vlen = 0, emitted = 0, status = 0;
     uint32_t st_visits = 0, st_cand = 0, st_dq = 0, st_reads = 0, st_next = 0, st_invis = 0;
+    bool ended = false;  // (resumable scans) next() has returned None before: the stream is over for good
+    if (resumed) {       // (all wave-uniform)
+        heap.len = rfl(rs[RSP_HLEN]);
+        heap.maxlen = rfl(rs[RSP_HMAX]);
+        vhead = rfl(rs[RSP_VHEAD]);
+        vlen = rfl(rs[RSP_VLEN]);
+        nins = rfl(rs[RSP_NINS]);
+        st_visits = rfl(rs[RSP_VISITS]);
+        st_cand = rfl(rs[RSP_CAND]);
+        st_dq = rfl(rs[RSP_DQ]);
+        st_reads = rfl(rs[RSP_READS]);
+        st_next = rfl(rs[RSP_NEXT]);
+        st_invis = rfl(rs[RSP_INVIS]);
+        status = rfl(rs[RSP_STATUS]);
+        ended = rfl(rs[RSP_ENDED]) != 0;
+    }
 
     // HashSet::insert for the active lanes' node ids; returns true where the id was not present before.  The caller has checked
     // that the table has room for every active lane (ins_limit), so a probe run always ends at a clear bit.
@@ -873,7 +907,7 @@ __device__ __forceinline__ void plain_scan(const PlainArgs& a, const uint32_t q,
     };
 
     // ---- ListSearchResult::new from the default start node (AM/graph/mod.rs:97-124); empty() when there is none ----
-    if (a.default_start != VS_INVALID_NODE && a.n != 0) {
+    if (!resumed && a.default_start != VS_INVALID_NODE && a.n != 0) {
         const uint32_t sn = a.default_start;
         prepare_insert(sn, lane == 0);
         st_reads++;
@@ -888,7 +922,7 @@ __device__ __forceinline__ void plain_scan(const PlainArgs& a, const uint32_t q,
     uint32_t pf_node = VS_INVALID_NODE, pf_val = VS_INVALID_NODE;  // prefetched first chunk of a neighbor row
 
     // ---- TSVResponseIterator::next, repeated until M rows are emitted (AM/scan.rs:210-242) ----
-    while (emitted < s.M && status == 0) {
+    while (emitted < s.M && status == 0 && !(RS && ended)) {
         st_next++;
         bool got = false;
         while (true) {  // "Iterate until we find a non-deleted tuple"
@@ -1000,7 +1034,10 @@ __device__ __forceinline__ void plain_scan(const PlainArgs& a, const uint32_t q,
             }
             if (status) break;
             // ---- consume (AM/graph/mod.rs:174-184): visited.remove(0) moves the head ----
-            if (vlen == 0) break;  // None
+            if (vlen == 0) {  // None
+                if (RS) ended = true;
+                break;
+            }
             const uint32_t fd = rfl(vkey[vhead]);
             const uint32_t fnode = rfl(vid[vhead]);
             vhead++;
@@ -1017,6 +1054,17 @@ __device__ __forceinline__ void plain_scan(const PlainArgs& a, const uint32_t q,
             if (lane == 0) {
                 s.out_ids[(size_t)q * s.M + emitted] = fnode;
                 s.out_ham[(size_t)q * s.M + emitted] = fd;
+                if (RS && s.row_stats) {  // the counters as the reference's stood when this row left next() (as k_search)
+                    uint32_t* r = s.row_stats + ((size_t)q * s.M + emitted) * ST_N;
+                    r[ST_VISITS] = st_visits;
+                    r[ST_CAND] = st_cand;
+                    r[ST_DQ] = st_dq;
+                    r[ST_READS] = st_reads;
+                    r[ST_NEXT] = st_next;
+                    r[ST_GSPILL] = heap.maxlen;
+                    r[ST_INVIS] = st_invis;
+                    r[ST_INS] = nins;
+                }
             }
             emitted++;
             got = true;
@@ -1024,7 +1072,30 @@ __device__ __forceinline__ void plain_scan(const PlainArgs& a, const uint32_t q,
         }
         if (!got) break;
     }
-    if (status) emitted = 0;  // a scan that outgrew a capacity publishes an empty stream: the general kernel re-runs it whole
+    // a scan that outgrew a capacity publishes an empty stream: the general kernel re-runs it whole (a pooled scan fails for its backend)
+    if (status) emitted = 0;
+    if (RS) {  // save the scan for the next launch (a failed scan keeps its flag until the slot is rescanned)
+        psync();
+        const uint32_t* const img = reinterpret_cast<const uint32_t*>(heap_l);
+        for (uint32_t i = 4u * lane; i < image_words; i += 4u * WAVE) *reinterpret_cast<uint4*>(rs + RSP_HDR + i) = *reinterpret_cast<const uint4*>(img + i);
+        if (lane == 0) {
+            rs[RSP_EMITTED] = (resumed ? rs[RSP_EMITTED] : 0u) + emitted;
+            rs[RSP_INIT] = 1u;
+            rs[RSP_HLEN] = heap.len;
+            rs[RSP_HMAX] = heap.maxlen;
+            rs[RSP_VHEAD] = vhead;
+            rs[RSP_VLEN] = vlen;
+            rs[RSP_NINS] = nins;
+            rs[RSP_VISITS] = st_visits;
+            rs[RSP_CAND] = st_cand;
+            rs[RSP_DQ] = st_dq;
+            rs[RSP_READS] = st_reads;
+            rs[RSP_NEXT] = st_next;
+            rs[RSP_INVIS] = st_invis;
+            rs[RSP_STATUS] = status;
+            rs[RSP_ENDED] = ended ? 1u : 0u;
+        }
+    }
     for (uint32_t i = emitted + lane; i < s.M; i += WAVE) {
         s.out_ids[(size_t)q * s.M + i] = VS_INVALID_NODE;
         s.out_ham[(size_t)q * s.M + i] = 0xFFFFFFFFu;
@@ -1052,9 +1123,18 @@ __global__ __launch_bounds__(WAVE) void k_search_plain(PlainArgs a) {
         if (threadIdx.x == 0) q = atomicAdd(a.s.scan_counter, 1u);
         q = rfl(q);
         if (q >= a.s.nq) return;
-        plain_scan(a, q, blockIdx.x, smem);
+        plain_scan<false>(a, q, blockIdx.x, smem);
         psync();  // the next scan re-initialises the LDS state: every lane is done with this one's
     }
+}
+
+// the resumable form: one single-wave workgroup per pool slot, status[q] the run mask on entry (a slot that is not marked returns at
+// once and keeps its saved state) and the scan's outcome on exit
+__global__ __launch_bounds__(WAVE) void k_search_plain_rs(PlainArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const uint32_t q = blockIdx.x;
+    if (q >= a.s.nq || a.s.status[q] == 0) return;  // (wave-uniform)
+    plain_scan<true>(a, q, q, smem);
 }
 
 // LDS of one scan of k_search_plain, in bytes:
@@ -1070,7 +1150,13 @@ size_t plain_lds_bytes(const vs_index* idx, const PlainLaunch& s) {
     return (b + 15) / 16 * 16;
 }
 
-static int plain_dispatch(vs_index* idx, const PlainLaunch& s, uint32_t* resident) {
+// u32 words of one saved scan: the header and the image plain_scan<true> saves (heap top, occupancy bits, LDS table, visited list)
+size_t plain_resume_words(const PlainLaunch& s) {
+    return RSP_HDR + 2 * (size_t)round_up_u32(s.hl + 2, 2) + round_up_u32(s.slots / 32, 4) + (s.lds_table ? (size_t)s.slots : 0) +
+           2 * (size_t)round_up_u32(s.vcap, 4);
+}
+
+static int plain_dispatch(vs_index* idx, const PlainLaunch& s, uint32_t* resident, bool rs = false) {
     VS_REQUIRE(idx->d.storage_type == VS_STORAGE_PLAIN && idx->vecs, "plain search kernel: not a plain-storage index with its vector column");
     VS_REQUIRE(s.slots >= 64 && (s.slots & (s.slots - 1)) == 0 && (s.ins_limit == 0xFFFFFFFFu ? idx->d.n < s.slots : s.ins_limit <= s.slots / 4 * 3),
                "plain search kernel: the dedup table must be a power of two of slots with room beyond its limit");
@@ -1081,6 +1167,7 @@ static int plain_dispatch(vs_index* idx, const PlainLaunch& s, uint32_t* residen
     const int attr_dev = idx->ctx->device;
     if (attr_set.pending(attr_dev)) {
         VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_search_plain), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_search_plain_rs), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set.done(attr_dev);
     }
     if (resident) {
@@ -1089,14 +1176,20 @@ static int plain_dispatch(vs_index* idx, const PlainLaunch& s, uint32_t* residen
         *resident = (uint32_t)std::max(per_cu, 1) * (uint32_t)idx->ctx->prop.multiProcessorCount;
         return VS_OK;
     }
-    VS_REQUIRE(s.persist >= 1 && s.scan_counter && s.heap_g && (s.lds_table || s.table_g), "plain search kernel: a persistent grid needs its counter and regions");
+    if (rs) {
+        VS_REQUIRE(s.heap_g && (s.lds_table || s.table_g) && s.resume && s.resume_stride >= plain_resume_words(s) && s.resume_stride % 4 == 0 &&
+                       ((uintptr_t)s.resume & 15u) == 0 && s.q_prepared && s.hl <= s.hcap,
+                   "plain search kernel: resumable scans need their regions, their 16-byte aligned saved state and their prepared queries");
+    } else {
+        VS_REQUIRE(s.persist >= 1 && s.scan_counter && s.heap_g && (s.lds_table || s.table_g), "plain search kernel: a persistent grid needs its counter and regions");
+    }
     PlainArgs a;
     a.nbrs = idx->nbrs;
     a.tids = idx->tids;
     a.vecs = idx->vecs;
     const bool truncated = idx->d.dim_index < idx->d.dim_full;  // index slice: its own norm cache / prepared query
     a.vnorm = truncated ? idx->vnorm_idx : idx->vnorm;
-    a.q_full = (const float*)(truncated ? idx->ws.q_index.p : idx->ws.q_full.p);
+    a.q_full = s.q_prepared ? s.q_prepared : (const float*)(truncated ? idx->ws.q_index.p : idx->ws.q_full.p);
     a.nbr_stride = idx->nbr_stride;
     a.R = idx->d.num_neighbors;
     a.n = idx->d.n;
@@ -1107,7 +1200,8 @@ static int plain_dispatch(vs_index* idx, const PlainLaunch& s, uint32_t* residen
     VS_REQUIRE(a.q_full, "plain search kernel: no prepared queries");
     VS_REQUIRE(a.distance_type != VS_COSINE || a.vnorm, "plain storage search: the cosine divisors of the index slices are missing");
     a.s = s;
-    hipLaunchKernelGGL(k_search_plain, dim3(std::min(s.persist, s.nq)), dim3(WAVE), lds, idx->ctx->stream, a);
+    if (rs) hipLaunchKernelGGL(k_search_plain_rs, dim3(s.nq), dim3(WAVE), lds, idx->ctx->stream, a);
+    else hipLaunchKernelGGL(k_search_plain, dim3(std::min(s.persist, s.nq)), dim3(WAVE), lds, idx->ctx->stream, a);
     VS_HIP(hipGetLastError());
     return VS_OK;
 }
@@ -1115,5 +1209,9 @@ static int plain_dispatch(vs_index* idx, const PlainLaunch& s, uint32_t* residen
 int launch_search_plain(vs_index* idx, const PlainLaunch& s) {
     if (s.nq == 0) return VS_OK;
     return plain_dispatch(idx, s, nullptr);
+}
+int launch_search_plain_rs(vs_index* idx, const PlainLaunch& s) {
+    if (s.nq == 0) return VS_OK;
+    return plain_dispatch(idx, s, nullptr, true);
 }
 int plain_resident_scans(vs_index* idx, const PlainLaunch& s, uint32_t* out) { return plain_dispatch(idx, s, out); }

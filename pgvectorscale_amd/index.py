@@ -720,6 +720,13 @@ class ScanPool:
         check(self._L.vs_scanpool_get_work(self.h, C.byref(a), C.byref(b)))
         return {"launches": int(a.value), "rounds": int(b.value)}
 
+    def info(self):
+        """which kernel this pool's continuations run (kernel: VS_SEARCH_GENERAL / _FAST_SBQ / _FAST_PLAIN; decided at creation), the
+        pool's capacity as `resident` for the two fast kernels, the LDS per scan and the planned on-chip capacities (vs_scanpool_info)"""
+        info = _lib.SearchInfo()
+        check(self._L.vs_scanpool_info(self.h, C.byref(info)))
+        return info.as_dict()
+
     def close(self):
         if self.h:
             self._L.vs_scanpool_free(self.h)
