@@ -500,7 +500,10 @@ extern "C" int vs_bruteforce_topk(vs_index* ix, const float* d_queries, uint32_t
     VS_HIP(hipMemsetAsync(w.resort_heap.p, 0xFF, (size_t)nq * k * 8, c->stream));
     for (uint64_t r0 = 0; r0 < n; r0 += chunk) {
         const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n - r0);
-        VS_TRY(launch_rerank(ix, (const float*)w.q_full.p, nullptr, nullptr, nullptr, m, nq, (float*)w.rr_dist.p, (uint32_t)r0));
+        hipEvent_t ev = prof_begin(c);  // one "rerank" span per chunk: the profile tells how many chunks a call folded
+        const int rc = launch_rerank(ix, (const float*)w.q_full.p, nullptr, nullptr, nullptr, m, nq, (float*)w.rr_dist.p, (uint32_t)r0);
+        prof_end(c, PK_RERANK, ev);
+        VS_TRY(rc);
         hipLaunchKernelGGL(k_bf_fold, dim3(nq), dim3(WAVE), 0, c->stream, (const float*)w.rr_dist.p, ix->tids, m, (uint32_t)r0, nq, k,
                            (uint64_t*)w.resort_heap.p);
         VS_HIP(hipGetLastError());

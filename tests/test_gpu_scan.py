@@ -1,7 +1,11 @@
 """K5 flat SBQ scan (vs_scan_topk) and the exact brute force (vs_bruteforce_topk) against numpy / the oracle.
 Hamming ranking is bit-exact with ties broken by node id; brute-force distances are bit-identical to the oracle's
-AVX2-order distance (asserted at the 1e-5 bar of north_star)."""
-import ctypes as C
+AVX2-order distance (asserted at the 1e-5 bar of north_star).  Every instantiation of the scan kernel (query tile x chunk count) and
+its refusals are here; the step loop at sizes taken from the device is in test_gpu_scan_steps.py, the brute force over several chunks
+and at its special values in test_gpu_scan_bruteforce.py."""
+import contextlib
+import os
+import re
 
 import numpy as np
 import pytest
@@ -9,6 +13,20 @@ import pytest
 from helpers import cached_index
 
 pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INV = 0xFFFFFFFF
+
+
+@contextlib.contextmanager
+def options(**kv):
+    from pgvectorscale_amd.index import set_option
+    for k, v in kv.items():
+        set_option(k, v)
+    try:
+        yield
+    finally:
+        for k in kv:
+            set_option(k, None)
 
 
 def _popcount(a):
@@ -47,6 +65,109 @@ def test_scan_topk_exact(gpu_ctx, words, n, nq, k):
         assert (ids[q] == want_ids).all(), (q, ids[q], want_ids)
         assert (ham[q] == want_ham).all()
     ix.close()
+
+
+def _tied_codes(rng, rows, words):
+    """few distinct values per word => ties at the k-th place are the rule"""
+    return rng.integers(0, 4, (rows, words), dtype=np.uint64) * np.uint64(0x0101010101010101)
+
+
+def _check_against_lexsort(codes, qcodes, k, ids, ham):
+    n = len(codes)
+    assert ids.shape == ham.shape == (len(qcodes), k)
+    for q in range(len(qcodes)):
+        d = _popcount(codes ^ qcodes[q]).sum(axis=1).astype(np.int64)
+        order = np.lexsort((np.arange(n), d))[:k]
+        want_ids = np.full(k, INV, np.uint32)
+        want_ham = np.full(k, INV, np.uint32)
+        want_ids[:len(order)] = order
+        want_ham[:len(order)] = d[order]
+        assert (ids[q] == want_ids).all(), (q, ids[q], want_ids)
+        assert (ham[q] == want_ham).all(), (q, ham[q], want_ham)
+
+
+# every chunk-count instantiation NCH of k_scan_topk at both ends of its range of code widths (1-8 words: 1, 9-16: 2, 17-24: 3,
+# 25-32: 4, 33-48: 6, where 33-40 words need five chunks and run the <6> instantiation with a sixth chunk that loads nothing);
+# odd widths have a stride padded to even
+SCAN_WORDS = (1, 8, 9, 16, 17, 25, 32, 33, 39, 47, 48)
+SCAN_TILES = (4, 8, 16)
+# words x tile is complete; k walks 1, 10, 64 along it so that every k meets every tile (11 widths per tile, k of period 3)
+SCAN_MATRIX = [(w, t, (1, 10, 64)[(wi + ti) % 3]) for wi, w in enumerate(SCAN_WORDS) for ti, t in enumerate(SCAN_TILES)]
+
+
+@pytest.mark.parametrize("words,tile,k", SCAN_MATRIX)
+def test_scan_topk_every_instantiation(gpu_ctx, words, tile, k):
+    n, nq = 1511, 2 * tile + 3  # n is no multiple of the 64-row step; the third tile of queries is ragged (3 of Q)
+    rng = np.random.default_rng(words * 100 + tile)
+    codes, qcodes = _tied_codes(rng, n, words), _tied_codes(rng, nq, words)
+    ix = _flat_index(gpu_ctx, codes)
+    try:
+        with options(VS_SCAN_Q=tile):
+            ids, ham = ix.scan_topk(qcodes, k)
+    finally:
+        ix.close()
+    _check_against_lexsort(codes, qcodes, k, ids, ham)
+
+
+@pytest.mark.parametrize("tile", SCAN_TILES)
+@pytest.mark.parametrize("n,k", [(7, 10), (1, 64), (1, 1)])
+def test_scan_topk_fewer_rows_than_k(gpu_ctx, n, k, tile):
+    rng = np.random.default_rng(n + k)
+    codes, qcodes = _tied_codes(rng, n, 5), _tied_codes(rng, tile + 1, 5)
+    ix = _flat_index(gpu_ctx, codes)
+    try:
+        with options(VS_SCAN_Q=tile):
+            ids, ham = ix.scan_topk(qcodes, k)
+    finally:
+        ix.close()
+    _check_against_lexsort(codes, qcodes, k, ids, ham)
+    assert (ids[:, min(n, k):] == INV).all() and (ham[:, min(n, k):] == INV).all()
+
+
+def _argument_error_code():
+    """what VS_REQUIRE returns (vs_internal.h), by its value in the public header"""
+    macro = open(os.path.join(ROOT, "pgvectorscale_amd", "csrc", "vs_internal.h")).read()
+    name = re.search(r"#define VS_REQUIRE\(cond, \.\.\.\).*?return (\w+);", macro, re.S).group(1)
+    return int(re.search(name + r" = (-?\d+)", open(os.path.join(ROOT, "include", "vsgpu.h")).read()).group(1))
+
+
+def test_flat_scan_refusals(gpu_ctx):
+    """arguments the flat scan refuses before it launches anything, and the empty batch"""
+    import pgvectorscale_amd as P
+    invalid = _argument_error_code()
+    assert invalid == -1
+    rng = np.random.default_rng(1)
+    codes, qcodes = _tied_codes(rng, 200, 4), _tied_codes(rng, 3, 4)
+    ix = _flat_index(gpu_ctx, codes)
+    try:
+        gpu_ctx.profile_read()
+        gpu_ctx.profile_enable(True)
+        for k in (0, 65):
+            for kw in ({}, dict(live_only=True)):
+                with pytest.raises(P.VsError, match=r"k must be in \[1, 64\]") as e:
+                    ix.scan_topk(qcodes, k, **kw)
+                assert e.value.code == invalid
+        ids, ham = ix.scan_topk(qcodes[:0], 10)
+        assert ids.shape == ham.shape == (0, 10) and ids.dtype == ham.dtype == np.uint32
+        ids, ham = ix.scan_topk(qcodes[:0], 10, live_only=True)
+        assert ids.shape == ham.shape == (0, 10)
+        assert gpu_ctx.profile_read()["scan"][1] == 0  # nothing was launched
+        ids, _ = ix.scan_topk(qcodes, 64)  # the index still scans
+        assert gpu_ctx.profile_read()["scan"][1] == 1 and (ids[:, 0] != INV).all()
+    finally:
+        gpu_ctx.profile_enable(False)
+        ix.close()
+    # 49 words: stride 50, seven chunks of four lanes x 16 B — one more than the widest instantiation
+    wide = _flat_index(gpu_ctx, _tied_codes(rng, 100, 49))
+    try:
+        gpu_ctx.profile_enable(True)
+        with pytest.raises(P.VsError, match="not supported by the flat scan") as e:
+            wide.scan_topk(_tied_codes(rng, 2, 49), 10)
+        assert e.value.code == invalid
+        assert gpu_ctx.profile_read()["scan"][1] == 0
+    finally:
+        gpu_ctx.profile_enable(False)
+        wide.close()
 
 
 def test_scan_topk_matches_oracle_hamming(gpu_ctx, oracle):
@@ -92,10 +213,16 @@ def test_scan_topk_filtered_is_the_exact_filtered_ranking(gpu_ctx, oracle):
     keys[0], keys[1], keys[2] = [], [6], [99]  # no filter / one label / a label nobody carries
     for live in (False, True):
         for k in (1, 10, 64):
-            gi, gh = ix.scan_topk(qcodes, k, qlabels=keys, live_only=live)
             oi, oh = oracle.hamming_scan_topk(ti.codes, qcodes, k, label_off=ti.label_off, label_val=ti.label_val,
                                               heap_tids=ti.tids if live else None, qlabels=keys)
+            gi, gh = ix.scan_topk(qcodes, k, qlabels=keys, live_only=live)
             assert (gi == oi).all() and (gh == oh).all()
+            # every tile width: the key of query q0 + qi in the second and later tiles (24 queries: 6, 3 and 2 tiles, the last of
+            # 16 ragged)
+            for tile in SCAN_TILES:
+                with options(VS_SCAN_Q=tile):
+                    gi, gh = ix.scan_topk(qcodes, k, qlabels=keys, live_only=live)
+                assert (gi == oi).all() and (gh == oh).all(), (live, k, tile)
     assert (gi[2] == 0xFFFFFFFF).all()
     # no key at all = the plain flat scan
     a, _ = ix.scan_topk(qcodes, 10)

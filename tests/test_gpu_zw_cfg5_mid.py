@@ -5,7 +5,8 @@ unfiltered pass, per-label start nodes), label-filtered scans in the TABLE-LESS 
 neighbor rows (`nbr_mask`: the default above 8M nodes, forced here) — rows, distance bits and GreedySearchStats against the oracle on 256
 one- and two-label keys, the SBQ-ordered stream, and the recall of that stream against the exact filtered Hamming top-k of the flat
 scan (vs_scan_topk_filtered).  Filtered-DiskANN predicate = LabelSet overlap (AM/labels/mod.rs:124-142), start nodes per label
-(AM/graph/start_nodes.rs:39-48), marking before the label test (AM/sbq/storage.rs:148-172)."""
+(AM/graph/start_nodes.rs:39-48), marking before the label test (AM/sbq/storage.rs:148-172).
+The filtered flat scan that serves as ground truth here is itself held to the oracle in tests/test_gpu_scan.py and test_gpu_scan_steps.py."""
 import os
 import sys
 
