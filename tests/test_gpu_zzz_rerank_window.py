@@ -5,6 +5,7 @@ distance bits and the counters the call returns.  Also runs on the lockstep inte
 import numpy as np
 import pytest
 
+from helpers import Corpus, tie_vectors
 from oracle import oracle_py as O
 
 pytestmark = pytest.mark.gpu
@@ -13,55 +14,6 @@ MODES = (0, 1, 2)
 COUNTERS = ("visited_nodes", "candidate_nodes", "quantized_distance_comparisons", "full_distance_comparisons", "node_reads",
             "node_heap_reads", "next_calls")
 INVALID = 0xFFFFFFFF
-
-
-class Corpus:
-    """An index over the given vectors, manufactured with the oracle like tests/helpers.TestIndex (which draws its own vectors)."""
-
-    def __init__(self, X, distance=O.L2, bits=None, R=24, L_build=40, n_labels=0, seed=5):
-        X = np.ascontiguousarray(X, np.float32)
-        n, dim = X.shape
-        self.n, self.dim, self.distance, self.R = n, dim, distance, R
-        self.bits = bits or O.default_bits(dim)
-        self.vecs = X
-        rows = X.copy()
-        if distance == O.COSINE:
-            for i in range(n):
-                rows[i] = O.preprocess_cosine(rows[i])[0]
-        self.mean, self.m2, self.count = O.train(rows, self.bits)
-        self.codes = O.quantize(self.mean, self.m2, self.count, self.bits, rows)
-        self.nbrs, self.start = O.build_graph(self.codes, num_neighbors=R, search_list_size=L_build)
-        self.tids = ((np.arange(n, dtype=np.uint64) + 7) << np.uint64(16)) | np.uint64(1)
-        self.label_off = self.label_val = None
-        self.label_starts = {}
-        if n_labels:
-            rng = np.random.default_rng(seed)
-            off, vals = np.zeros(n + 1, np.uint32), []
-            for i in range(n):
-                ls = sorted(set(int(v) for v in rng.integers(1, n_labels + 1, 2)))
-                vals.extend(ls)
-                off[i + 1] = len(vals)
-                for l in ls:
-                    self.label_starts.setdefault(l, i)
-            self.label_off, self.label_val = off, np.array(vals, np.int16)
-        self.oracle = O.OracleIndex(codes=self.codes, nbrs=self.nbrs, heap_tids=self.tids, vecs=self.vecs, mean=self.mean,
-                                    m2=self.m2, count=self.count, bits=self.bits, dim_index=dim, num_neighbors=R,
-                                    distance_type=distance, default_start=self.start, label_off=self.label_off,
-                                    label_val=self.label_val, label_starts=self.label_starts)
-
-    def upload(self, ctx):
-        import pgvectorscale_amd as P
-        return P.DiskAnnIndex.upload(ctx, codes=self.codes, nbrs=self.nbrs, heap_tids=self.tids, vecs=self.vecs, mean=self.mean,
-                                     m2=self.m2, count=self.count, bits=self.bits, dim_index=self.dim, num_neighbors=self.R,
-                                     distance_type=self.distance, default_start=self.start, label_off=self.label_off,
-                                     label_val=self.label_val, label_starts=self.label_starts)
-
-
-def tie_vectors(n, distinct, dim, seed):
-    """n rows drawn with replacement from `distinct` vectors: the f32 distances of equal rows tie bit for bit"""
-    rng = np.random.default_rng(seed)
-    base = rng.random((distinct, dim), dtype=np.float32)
-    return base[rng.integers(0, distinct, n)]
 
 
 def check(ctx, corpus, q, L, rescore, k, qlabels=None, expect_rows=None):
