@@ -254,6 +254,13 @@ int vs_index_download(const vs_index* idx, uint64_t* codes, uint32_t* nbrs /*[n]
  * AM/distance/mod.rs:225-253), and on a plain cosine index with dim_index < dim_full the cache of the index slices' divisors too;
  * called by upload automatically */
 int vs_index_refresh_norms(vs_index* idx);
+/* Gives an index that was made without a vector column (vs_pages_dev_build / vs_index_upload with vecs == NULL) a zeroed one: the
+ * stride and rows vs_index_alloc(with_vecs = 1) would choose, plus the cosine divisor cache.  The caller fills the rows through
+ * vs_index_array(VS_ARR_VECS) (vs_heap_dev_* writes there directly) and calls vs_index_refresh_norms; searches with rescore > 0 and
+ * vs_rerank then work as if the index had been uploaded with the column.  VS_OK and nothing done if the column exists.
+ * VS_ERR_STATE: a view handle, live views, a batch in flight, an open page writer.  A column that does not fit leaves the index as
+ * it was (VS_ERR_OOM). */
+int vs_index_alloc_vecs(vs_index* idx);
 /* mark heap tuples deleted (what ambulkdelete does to heap_item_pointer, AM/vacuum.rs:24-78) */
 int vs_index_mark_deleted(vs_index* idx, const uint32_t* nodes, uint32_t n);
 /* ambulkdelete by heap TID (bulk_delete_for_storage, AM/vacuum.rs:80-136: every live node's heap_item_pointer is put to the
@@ -545,6 +552,39 @@ int vs_heap_toast_add(vs_heap* h, uint32_t first_block, const void* pages, uint3
 int vs_heap_finish(vs_heap* h, vs_heap_info* info, uint8_t* found);
 void vs_heap_close(vs_heap* h);
 
+/* ---- the same column decoded ON the device (vs_heap_dev.h, part of vs_pages_dev.hip) -----------------------------------------------
+ * The host copies pages and does nothing else: they go through the context's pinned ring to HBM as they are, chunk by chunk (two
+ * staged chunks, never retained), and kernels deform the tuples and scatter the floats straight into device rows — a buffer from
+ * vs_dev_alloc, or the index's own column (vs_index_alloc_vecs, vs_index_array(VS_ARR_VECS) plus a row offset).  No host copy of
+ * the column exists at any time: host memory is O(1) in n beyond heap_tids, device memory a few tens of bytes per node.
+ * The semantics are those of vs_heap_* above (vs_heap.cpp is the specification: line pointers with LP_REDIRECT followed for at most
+ * 8 hops, heap_deform_tuple up to the vector attribute, in-line vectors under 1-byte and 4-byte headers, external ones assembled
+ * from their TOAST chunks with every check the host makes), with these differences:
+ *   - block ranges need not be contiguous: first_block must be >= the end of the previous call of the same pass (else
+ *     VS_ERR_INVALID), gaps are allowed.  A tid on a block that was never fed is n_not_found, a referenced value whose chunks were
+ *     never fed is n_toast_incomplete; heap_blocks / toast_blocks report the end of the last range fed.  A follower reads only the
+ *     blocks its new rows live on.
+ *   - compressed vectors (pglz or lz4; in line, VARATT_IS_4B_C, or external with extsize < rawsize) are NOT decoded: the row stays
+ *     zero with found = 0 and is counted in *n_compressed and in no field of vs_heap_info; its TOAST chunks are skipped and not
+ *     counted in n_chunks.  The caller reads those rows with vs_heap_* over heap_tids[found == 0] and uploads them.  (pgvector's own
+ *     storage is `external`, which never compresses.)  n_inline + n_external + n_deleted + n_null + n_dead_line_pointer +
+ *     n_not_found + n_toast_incomplete + n_compressed == n.
+ *   - a malformed page, item or tuple is VS_ERR_INVALID with the relation (heap / TOAST), the block, the offset and the reason in
+ *     vs_last_error; it may be returned by the add that fed the page, by a later add, or by the finish at the latest (the copy of
+ *     chunk i+1 runs under the kernel of chunk i).  When several items are malformed, which one is named is unspecified.  After an
+ *     error only vs_heap_dev_close is defined.  A malformed page never makes a kernel read or write outside its buffers.
+ * Open: the argument checks of vs_heap_open; the first dim floats of every target row are zeroed, the padding floats
+ * [dim, out_stride) are never written.  Finish: info and found[] as vs_heap_finish fills them; EVERY row that is not found is zero,
+ * a value whose chunks did not all arrive included.  No output depends on the order in which waves or pages are scheduled.
+ * heap_tids: HOST [n], (block << 16) | offset; d_out_vecs: DEVICE [n][out_stride] floats, out_stride >= dim. */
+typedef struct vs_heap_dev vs_heap_dev;
+int vs_heap_dev_open(vs_ctx* ctx, uint32_t page_size, const vs_heap_attr* attrs, uint32_t natts, uint32_t vector_attno, uint32_t dim,
+                     const uint64_t* heap_tids, uint32_t n, float* d_out_vecs, uint32_t out_stride, vs_heap_dev** out);
+int vs_heap_dev_add(vs_heap_dev* h, uint32_t first_block, const void* pages, uint32_t n_blocks);        /* heap main fork  */
+int vs_heap_dev_toast_add(vs_heap_dev* h, uint32_t first_block, const void* pages, uint32_t n_blocks);  /* then TOAST      */
+int vs_heap_dev_finish(vs_heap_dev* h, vs_heap_info* info, uint8_t* found /* host [n], may be NULL */, uint32_t* n_compressed /* may be NULL */);
+void vs_heap_dev_close(vs_heap_dev* h);
+
 /* The same, decoded ON the device (vs_pages_dev.hip): the blocks are copied to HBM as they are (pinned ring,
  * hipMemcpyAsync), the host only reads the page headers on the way past, and one kernel (a wave per node page) walks the
  * line pointers and rkyv relative pointers and writes codes / neighbor ids / heap tids into the index arrays; label sets
@@ -635,6 +675,10 @@ int vs_pages_follow_new_tids(const vs_pages_follow* f, uint64_t* tids, uint32_t 
  * label sets appended, the own visibility mask gets 1 and every stored snapshot 0 for the new rows; derived state is treated as
  * vs_index_insert treats it.  The follower's table advances only on success. */
 int vs_pages_follow_apply(vs_pages_follow* f, const float* new_vecs, uint32_t vec_stride, vs_pages_follow_info* info);
+/* vs_pages_follow_apply with the appended rows already in DEVICE memory (d_new_vecs [n_appended][vec_stride], e.g. what vs_heap_dev_*
+ * read over vs_pages_follow_new_tids): a strided device-to-device copy in place of the upload.  Every other rule is unchanged and the
+ * result is byte-identical to the host form given the same rows (padding floats of the new rows zero). */
+int vs_pages_follow_apply_dev(vs_pages_follow* f, const float* d_new_vecs, uint32_t vec_stride, vs_pages_follow_info* info);
 int vs_pages_follow_discard(vs_pages_follow* f);  /* forget the staged list */
 void vs_pages_follow_close(vs_pages_follow* f);
 

@@ -239,6 +239,7 @@ SYMBOLS = {
     "vs_index_get_quantizer": (_i, [_vp, _vp, _vp, C.POINTER(_u64)]),
     "vs_index_download": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32]),
     "vs_index_refresh_norms": (_i, [_vp]),
+    "vs_index_alloc_vecs": (_i, [_vp]),
     "vs_index_mark_deleted": (_i, [_vp, _vp, _u32]),
     "vs_index_bulk_delete": (_i, [_vp, _vp, _u64, C.POINTER(BulkDeleteStats)]),
     "vs_index_bulk_delete_dev": (_i, [_vp, _vp, _u64, C.POINTER(BulkDeleteStats)]),
@@ -265,6 +266,11 @@ SYMBOLS = {
     "vs_heap_toast_add": (_i, [_vp, _u32, _vp, _u32]),
     "vs_heap_finish": (_i, [_vp, C.POINTER(HeapInfo), _vp]),
     "vs_heap_close": (None, [_vp]),
+    "vs_heap_dev_open": (_i, [_vp, _u32, C.POINTER(HeapAttr), _u32, _u32, _u32, _vp, _u32, _vp, _u32, C.POINTER(_vp)]),
+    "vs_heap_dev_add": (_i, [_vp, _u32, _vp, _u32]),
+    "vs_heap_dev_toast_add": (_i, [_vp, _u32, _vp, _u32]),
+    "vs_heap_dev_finish": (_i, [_vp, C.POINTER(HeapInfo), _vp, C.POINTER(_u32)]),
+    "vs_heap_dev_close": (None, [_vp]),
     "vs_meta_layout_default": (_i, [C.POINTER(MetaLayout)]),
     "vs_meta_page_decode": (_i, [_vp, _sz, C.POINTER(MetaLayout), C.POINTER(MetaPage), _vp, _vp, _vp, _u32]),
     "vs_pages_meta": (_i, [_vp, C.POINTER(MetaLayout), C.POINTER(MetaPage), C.POINTER(IndexDesc), _vp, _vp, _u32]),
@@ -283,6 +289,7 @@ SYMBOLS = {
     "vs_pages_follow_stage": (_i, [_vp, _vp, _vp, _u32, _u32, C.POINTER(PagesFollowInfo)]),
     "vs_pages_follow_new_tids": (_i, [_vp, _vp, _u32]),
     "vs_pages_follow_apply": (_i, [_vp, _vp, _u32, C.POINTER(PagesFollowInfo)]),
+    "vs_pages_follow_apply_dev": (_i, [_vp, _vp, _u32, C.POINTER(PagesFollowInfo)]),
     "vs_pages_follow_discard": (_i, [_vp]),
     "vs_pages_follow_close": (None, [_vp]),
     "vs_pages_out_open": (_i, [_vp, C.POINTER(PagesOutParams), C.POINTER(_vp), C.POINTER(PagesInfo)]),

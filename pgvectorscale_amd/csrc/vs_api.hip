@@ -540,6 +540,52 @@ extern "C" int vs_index_alloc(vs_ctx* c, const vs_index_desc* desc, int with_vec
     return r;
 }
 
+// The vector column for an index that was made without one (vs_pages_dev_build / vs_index_upload with vecs == NULL): zeroed rows at
+// the stride and capacity vs_index_alloc(with_vecs) would have chosen, and the cosine divisor cache.  The caller fills the rows
+// (vs_index_array(VS_ARR_VECS), vs_heap_dev_*) and calls vs_index_refresh_norms.
+static int index_alloc_vecs_impl(vs_index* ix) {
+    const char* what = "vs_index_alloc_vecs";
+    VS_REQUIRE_OWNER(ix, what);
+    VS_REQUIRE_NO_VIEWS(ix, what);
+    if (ix->ws.pending) {
+        vs_set_error("%s: a batch of this handle is in flight (vs_search_batch_dev_finish first)", what);
+        return VS_ERR_STATE;
+    }
+    if (vs_index_open_writers(ix) > 0) {
+        vs_set_error("%s: a page writer is open on this index (vs_pages_out_close first)", what);
+        return VS_ERR_STATE;
+    }
+    if (ix->vecs) return VS_OK;
+    vs_ctx* c = ix->ctx;
+    VS_HIP(hipSetDevice(c->device));
+    const size_t rows = std::max<uint32_t>(std::max(ix->d.n, ix->capacity), 1);
+    const bool want_idx = ix->d.storage_type == VS_STORAGE_PLAIN && ix->d.dim_index < ix->d.dim_full && ix->d.distance_type == VS_COSINE && !ix->vnorm_idx;
+    float *vecs = nullptr, *vnorm = nullptr, *vnorm_idx = nullptr;
+    hipError_t e = hipMalloc(&vecs, rows * ix->vec_stride * sizeof(float));
+    if (e == hipSuccess && !ix->vnorm) e = hipMalloc(&vnorm, rows * sizeof(float));
+    if (e == hipSuccess && want_idx) e = hipMalloc(&vnorm_idx, rows * sizeof(float));
+    if (e == hipSuccess) e = hipMemsetAsync(vecs, 0, rows * ix->vec_stride * sizeof(float), c->stream);
+    if (e == hipSuccess && vnorm) e = hipMemsetAsync(vnorm, 0, rows * sizeof(float), c->stream);
+    if (e == hipSuccess && vnorm_idx) e = hipMemsetAsync(vnorm_idx, 0, rows * sizeof(float), c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {  // (a column that does not fit leaves the index as it was)
+        (void)hipGetLastError();
+        if (vecs) (void)hipFree(vecs);
+        if (vnorm) (void)hipFree(vnorm);
+        if (vnorm_idx) (void)hipFree(vnorm_idx);
+        vs_set_error("%s: %zu rows of %u floats: %s", what, rows, ix->vec_stride, hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? VS_ERR_OOM : VS_ERR_HIP;
+    }
+    ix->vecs = vecs;
+    if (vnorm) ix->vnorm = vnorm;
+    if (vnorm_idx) ix->vnorm_idx = vnorm_idx;
+    return VS_OK;
+}
+extern "C" int vs_index_alloc_vecs(vs_index* ix) {
+    VS_REQUIRE(ix, "vs_index_alloc_vecs: index is NULL");
+    return vs_guard("vs_index_alloc_vecs", [&] { return index_alloc_vecs_impl(ix); });
+}
+
 extern "C" int vs_index_set_quantizer(vs_index* ix, const float* mean, const float* m2, uint64_t count) {
     VS_REQUIRE(ix && mean, "vs_index_set_quantizer: bad args");
     VS_REQUIRE(ix->d.bits == 1 || m2 != nullptr, "m2 is required when num_bits_per_dimension > 1");

@@ -40,6 +40,8 @@ __device__ __forceinline__ uint32_t ld32(const uint8_t* p) {  // items are MAXAL
     return *reinterpret_cast<const uint32_t*>(p);
 }
 
+#include "vs_heap_dev.h"  // vs_heap_dev_*: the heap's vector column from heap and TOAST pages (kernels and their host code)
+
 // err[0] = first error code (0 = none), err[1] = block, err[2] = item, err[3] = detail
 __device__ __forceinline__ void page_error(uint32_t* err, uint32_t code, uint32_t blk, uint32_t item, uint32_t detail) {
     if (atomicCAS(&err[0], 0u, code) == 0u) {
@@ -1115,8 +1117,9 @@ extern "C" int vs_pages_follow_discard(vs_pages_follow* f) {
     });
 }
 
-static int follow_apply_impl(vs_pages_follow* f, const float* new_vecs, uint32_t vec_stride, vs_pages_follow_info* info) {
-    const char* what = "vs_pages_follow_apply";
+// new_in_hbm: new_vecs is device memory (vs_pages_follow_apply_dev); the rows then reach the column by a strided copy on the device
+static int follow_apply_impl(vs_pages_follow* f, const float* new_vecs, uint32_t vec_stride, vs_pages_follow_info* info, bool new_in_hbm) {
+    const char* what = new_in_hbm ? "vs_pages_follow_apply_dev" : "vs_pages_follow_apply";
     vs_index* ix = f->ix;
     vs_ctx* c = f->ctx;
     hipStream_t st = c->stream;
@@ -1172,9 +1175,15 @@ static int follow_apply_impl(vs_pages_follow* f, const float* new_vecs, uint32_t
             }
             VS_TRY(vs_dev_upload(c, ix->label_off + n_old + 1, f->s_label_off.data(), (size_t)n_app * 4));
         }
-        if (want_vecs)
+        if (want_vecs && new_in_hbm) {
+            const uint64_t total = (uint64_t)n_app * ix->vec_stride;
+            hipLaunchKernelGGL(k_rows_copy_pad, dim3((uint32_t)std::min<uint64_t>((total + 255) / 256, 4096)), dim3(256), 0, st,
+                               ix->vecs + (size_t)n_old * ix->vec_stride, ix->vec_stride, new_vecs, vec_stride, ix->d.dim_full, n_app);
+            VS_HIP(hipGetLastError());
+        } else if (want_vecs) {
             VS_TRY(vs_upload_rows(c, ix->vecs + (size_t)n_old * ix->vec_stride, ix->vec_stride * 4ull, new_vecs, vec_stride * 4ull,
                                   ix->d.dim_full * 4ull, n_app));
+        }
         uint32_t herr[4] = {0, 0, 0, 0};
         if (f->info.pages_listed) {
             VS_HIP(hipMemsetAsync(f->d_ctr, 0, (FC_N + 4) * 4, st));
@@ -1233,7 +1242,12 @@ static int follow_apply_impl(vs_pages_follow* f, const float* new_vecs, uint32_t
 
 extern "C" int vs_pages_follow_apply(vs_pages_follow* f, const float* new_vecs, uint32_t vec_stride, vs_pages_follow_info* info) {
     VS_REQUIRE(f, "vs_pages_follow_apply: null follower");
-    return vs_guard("vs_pages_follow_apply", [&] { return follow_apply_impl(f, new_vecs, vec_stride, info); });
+    return vs_guard("vs_pages_follow_apply", [&] { return follow_apply_impl(f, new_vecs, vec_stride, info, false); });
+}
+
+extern "C" int vs_pages_follow_apply_dev(vs_pages_follow* f, const float* d_new_vecs, uint32_t vec_stride, vs_pages_follow_info* info) {
+    VS_REQUIRE(f, "vs_pages_follow_apply_dev: null follower");
+    return vs_guard("vs_pages_follow_apply_dev", [&] { return follow_apply_impl(f, d_new_vecs, vec_stride, info, true); });
 }
 
 // ---------------------------------------------------------------------------------------------------------------

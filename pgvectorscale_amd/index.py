@@ -364,6 +364,12 @@ class DiskAnnIndex:
     def refresh_norms(self):
         check(self._L.vs_index_refresh_norms(self.h))
 
+    def alloc_vecs(self):
+        """vs_index_alloc_vecs: a zeroed vector column (and the cosine divisor cache) for an index that was staged without one; fill
+        it through array(VS_ARR_VECS) — pages.HeapColumnDev writes there directly — then refresh_norms().  Nothing happens if the
+        column exists."""
+        check(self._L.vs_index_alloc_vecs(self.h))
+
     # -- build-side helpers -----------------------------------------------------------------------------------------
     def sbq_train(self):
         check(self._L.vs_sbq_train(self.h))

@@ -135,6 +135,62 @@ class HeapColumn:
             pass
 
 
+class HeapColumnDev:
+    """The same column decoded on the device (vs_heap_dev_*): the pages go to HBM as they are and kernels scatter the floats into
+    rows of device memory `d_out` ([n][out_stride] floats: Context.alloc, or DiskAnnIndex.array(VS_ARR_VECS) plus a row offset).
+    Block ranges may have gaps (first_block ascending); compressed vectors are counted, not decoded: read those rows with
+    HeapColumn over heap_tids[found == 0]."""
+
+    def __init__(self, ctx, attrs, vector_attno, dim, heap_tids, d_out, out_stride, page_size=BLCKSZ):
+        self._L = _lib.load()
+        self.ctx = ctx
+        self.page_size = page_size
+        self._attrs = (HeapAttr * len(attrs))(*[HeapAttr(int(l), a.encode()) for l, a in attrs])
+        self._tids = np.ascontiguousarray(heap_tids, np.uint64)
+        self.h = None
+        h = C.c_void_p()
+        d_out = d_out if isinstance(d_out, C.c_void_p) else C.c_void_p(d_out)
+        check(self._L.vs_heap_dev_open(ctx.h, page_size, self._attrs, len(attrs), vector_attno, dim, self._tids.ctypes.data_as(C.c_void_p),
+                                       self._tids.size, d_out, out_stride, C.byref(h)))
+        self.h = h
+        self._nb = [0, 0]
+
+    def _add(self, fn, which, pages, first_block):
+        buf = np.frombuffer(pages, np.uint8)
+        if buf.size % self.page_size:
+            raise ValueError(f"{buf.size} bytes is not a whole number of {self.page_size}-byte pages")
+        nb = buf.size // self.page_size
+        fb = self._nb[which] if first_block is None else first_block
+        check(fn(self.h, fb, buf.ctypes.data_as(C.c_void_p), nb))
+        self._nb[which] = fb + nb
+
+    def add(self, pages, first_block=None):
+        """blocks of the heap's main fork from first_block on (None: behind the previous range)"""
+        self._add(self._L.vs_heap_dev_add, 0, pages, first_block)
+
+    def toast_add(self, pages, first_block=None):
+        self._add(self._L.vs_heap_dev_toast_add, 1, pages, first_block)
+
+    def finish(self):
+        """-> (info dict as HeapColumn.finish gives it, found uint8 [n], n_compressed)"""
+        info = HeapInfo()
+        found = np.zeros(self._tids.size, np.uint8)
+        nc = C.c_uint32(0)
+        check(self._L.vs_heap_dev_finish(self.h, C.byref(info), found.ctypes.data_as(C.c_void_p), C.byref(nc)))
+        return info.as_dict(), found, int(nc.value)
+
+    def close(self):
+        if self.h:
+            self._L.vs_heap_dev_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class IndexPages:
     def __init__(self, has_labels=False, page_size=BLCKSZ, layout=None, threads=0, plain=False):
         """plain=True: a `plain` storage index (PlainNode items: full-precision vectors in the nodes, no SBQ codes, no labels)"""
@@ -500,6 +556,16 @@ class PagesFollower:
             raise ValueError(f"{v.shape[0]} vectors for {self._n_appended} appended rows")
         check(self._L.vs_pages_follow_apply(self.h, None if v is None else v.ctypes.data_as(C.c_void_p), 0 if v is None else v.shape[1],
                                             C.byref(info)))
+        self._n_appended = None
+        self.index._refresh()
+        return info.as_dict()
+
+    def apply_dev(self, d_new_vecs, vec_stride):
+        """apply with the appended rows in device memory ([n_appended][vec_stride] floats, e.g. what HeapColumnDev read over
+        new_tids()): vs_pages_follow_apply_dev"""
+        info = PagesFollowInfo()
+        d = d_new_vecs if isinstance(d_new_vecs, C.c_void_p) or d_new_vecs is None else C.c_void_p(d_new_vecs)
+        check(self._L.vs_pages_follow_apply_dev(self.h, d, vec_stride, C.byref(info)))
         self._n_appended = None
         self.index._refresh()
         return info.as_dict()
