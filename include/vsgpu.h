@@ -585,6 +585,128 @@ int vs_heap_dev_toast_add(vs_heap_dev* h, uint32_t first_block, const void* page
 int vs_heap_dev_finish(vs_heap_dev* h, vs_heap_info* info, uint8_t* found /* host [n], may be NULL */, uint32_t* n_compressed /* may be NULL */);
 void vs_heap_dev_close(vs_heap_dev* h);
 
+/* ---- heap visibility decided ON the device from resident heap pages (vs_heap_vis.h, part of vs_pages_dev.hip) ------------------------
+ * The one byte per node of vs_index_set_visibility / vs_index_snapshot_put is what table_index_fetch_tuple would say for the node's
+ * heap tid under the scan's snapshot.  Visibility needs only the heap's MAIN fork (line pointers and 23-byte tuple headers; the
+ * vectors live in TOAST), the snapshot and the commit log.  vs_heap_res keeps that fork in HBM, indexed by block number: the shim
+ * puts the whole fork once and afterwards only the blocks that changed; a snapshot's mask is then one kernel pass (k_heap_vis, a
+ * lane per node) over memory that is already there, and nothing crosses PCIe but the snapshot.
+ *
+ * vs_heap_res_put: host pages, any order, through the context's pinned ring; a later put of a block overwrites it; a put beyond the
+ * capacity grows the buffer by the rule of vs_index_reserve (by half, at least to fit, device to device; a growth that fails leaves
+ * the buffer as it was); a block never put is all zero, which reads as PageIsNew: no items.  vs_heap_res_blocks: one past the
+ * highest block ever put.  Argument checks are those of vs_heap_dev_open / _add and come before any device call.
+ *
+ * THE RULE (PostgreSQL 13-17; little endian).  Tuple header: t_xmin at 0, t_xmax at 4, t_cid at 8, the offset number of t_ctid at
+ * 16..17, t_infomask2 at 18 (HOT_UPDATED 0x4000, ONLY_TUPLE 0x8000), t_infomask at 20: XMIN_COMMITTED 0x0100, XMIN_INVALID 0x0200
+ * (both = frozen), XMAX_COMMITTED 0x0400, XMAX_INVALID 0x0800, XMAX_IS_MULTI 0x1000, XMAX_LOCK_ONLY 0x0080, EXCL_LOCK 0x0040,
+ * KEYSHR_LOCK 0x0010, COMBOCID 0x0020, MOVED_OFF 0x4000, MOVED_IN 0x8000.
+ *   normal(x)       = x >= 3
+ *   precedes(a,b)   = normal(a) && normal(b) ? (int32)(a-b) < 0  : a < b          (TransactionIdPrecedes)
+ *   follows_eq(a,b) = normal(a) && normal(b) ? (int32)(a-b) >= 0 : a >= b         (TransactionIdFollowsOrEquals)
+ *   locked_only(m)  = (m & LOCK_ONLY) || (m & (IS_MULTI|EXCL_LOCK|KEYSHR_LOCK)) == EXCL_LOCK   (HEAP_XMAX_IS_LOCKED_ONLY)
+ *   did_commit(x)   = x==1||x==2 -> yes; x==0 -> no; outside the window -> UNDECIDED(CLOG_RANGE); status 3 -> UNDECIDED(SUBCOMMITTED);
+ *                     status==1                                                   (TransactionIdDidCommit)
+ *   in_snapshot(x)  = precedes(x,xmin) -> no; follows_eq(x,xmax) -> yes;          (XidInMVCCSnapshot)
+ *                     not recovery: !suboverflowed: x in subxip -> yes, else x in xip
+ *                                    suboverflowed: x in xip -> yes, else UNDECIDED(SUBOVERFLOW)
+ *                     recovery:     x in subxip -> yes; else suboverflowed ? UNDECIDED(SUBOVERFLOW) : no
+ *   own(x)          = x in own_xids                                               (TransactionIdIsCurrentTransactionId)
+ *   HeapTupleSatisfiesMVCC(t):
+ *     if !(m & XMIN_COMMITTED):
+ *         if (m & 0x0300) == XMIN_INVALID: invisible
+ *         if m & (MOVED_OFF|MOVED_IN): UNDECIDED(MOVED)
+ *         if own(xmin):
+ *             if m & COMBOCID: UNDECIDED(COMBOCID)
+ *             if cid >= curcid: invisible
+ *             if m & XMAX_INVALID: visible;  if locked_only(m): visible
+ *             if m & IS_MULTI: UNDECIDED(MULTIXACT)
+ *             if !own(xmax): visible
+ *             return cid >= curcid ? visible : invisible
+ *         else if in_snapshot(xmin): invisible
+ *         else if !did_commit(xmin): invisible
+ *     else if (m & 0x0300) != 0x0300 && in_snapshot(xmin): invisible
+ *     if m & XMAX_INVALID: visible;  if locked_only(m): visible
+ *     if m & IS_MULTI: UNDECIDED(MULTIXACT)
+ *     if !(m & XMAX_COMMITTED):
+ *         if own(xmax): (COMBOCID -> UNDECIDED) return cid >= curcid ? visible : invisible
+ *         if in_snapshot(xmax): visible
+ *         if !did_commit(xmax): visible
+ *     else if in_snapshot(xmax): visible
+ *     invisible
+ *   heap_hot_search_buffer(tid):      (what table_index_fetch_tuple runs; all within the tid's page)
+ *     off = tid.offset; at_start = true; prev_xmax = 0
+ *     loop (at most as many rounds as the page has line pointers; more is a cycle -> VS_ERR_INVALID):
+ *         off outside 1..nitems -> invisible
+ *         lp not NORMAL: if REDIRECT && at_start { off = lp_off; at_start = false; continue } else invisible
+ *         if at_start && (m2 & ONLY_TUPLE): invisible
+ *         if prev_xmax != 0 && prev_xmax != (frozen ? 2 : xmin): invisible
+ *         r = HeapTupleSatisfiesMVCC(t):  visible -> visible;  UNDECIDED -> UNDECIDED
+ *         if (m2 & HOT_UPDATED) && !(m & XMAX_INVALID) && (m & 0x0300) != XMIN_INVALID:
+ *             if (m & IS_MULTI) && !locked_only(m): UNDECIDED(MULTIXACT)
+ *             off = ctid.offset; at_start = false; prev_xmax = xmax
+ *         else invisible
+ * An undecided inner answer makes the whole verdict undecided with that reason.  Hint bits are never written: the pages are
+ * read-only copies and the verdict does not depend on them.
+ *
+ * A node's byte is 1 (visible) or 0 (invisible).  An UNDECIDED node — multixact members, pg_subtrans, combo command ids and the
+ * MOVED bits are not evaluated; an xid may lie outside the pg_xact window — gets 1, the conservative value, is counted by reason and
+ * appears in undecided_nodes, ascending (the first `cap` of them; *n_undecided is their full number): the shim settles those few
+ * with index_fetch_tuple and vs_index_snapshot_patch.  Parts of n_invisible: a tid with offset 0 (a vacuumed index tuple) is
+ * n_deleted; a block at or beyond vs_heap_res_blocks, or an offset beyond the page's line pointers, is n_not_found; a first line
+ * pointer that is LP_UNUSED / LP_DEAD is n_dead_line_pointer.  n_visible + n_invisible + n_undecided == n.  chain_hops: tuple headers
+ * read beyond the first of each node.  No output depends on how the lanes are scheduled.
+ * A malformed page — a wrong pd_pagesize_version, an inconsistent page header, an LP_NORMAL item outside pd_upper..pd_special or
+ * shorter than 23 bytes, a HOT chain that cycles — is VS_ERR_INVALID naming the block, the offset and the reason (when several are
+ * malformed, which one is unspecified); d_visible is then unspecified.  A malformed page never makes the kernel read outside the
+ * resident buffer.  The kernel runs on the context's stream; the call synchronises to hand back the counters and the list.
+ * d_heap_tids: DEVICE [n] (vs_index_array(VS_ARR_TIDS)); d_visible: DEVICE [n]; xip / subxip / own_xids: HOST, unsorted as
+ * PostgreSQL keeps them (the library sorts copies). */
+typedef struct vs_heap_res vs_heap_res;
+int vs_heap_res_open(vs_ctx* ctx, uint32_t page_size, uint32_t n_blocks_capacity, vs_heap_res** out);
+int vs_heap_res_put(vs_heap_res* h, uint32_t first_block, const void* pages, uint32_t n_blocks); /* host pages, any order */
+uint32_t vs_heap_res_blocks(const vs_heap_res* h);                                              /* one past the highest block ever put */
+void vs_heap_res_close(vs_heap_res* h);
+
+typedef struct vs_mvcc_snapshot { /* SnapshotData of an MVCC snapshot, plus what the backend knows about itself */
+    uint32_t xmin, xmax;
+    const uint32_t* xip; /* unsorted, as PostgreSQL keeps it */
+    uint32_t xcnt;
+    const uint32_t* subxip;
+    uint32_t subxcnt;
+    int32_t suboverflowed, taken_during_recovery;
+    const uint32_t* own_xids; /* every xid TransactionIdIsCurrentTransactionId says yes to */
+    uint32_t n_own;
+    uint32_t curcid;
+} vs_mvcc_snapshot;
+typedef struct vs_xact_status { /* a window of pg_xact: 2 bits per xid, 4 xids per byte, xid % 4 lowest first */
+    uint32_t first_xid;         /* multiple of 4 */
+    uint32_t n_xids;            /* the window is (xid - first_xid) mod 2^32 < n_xids */
+    const uint8_t* bits;        /* 0 in progress, 1 committed, 2 aborted, 3 sub-committed */
+} vs_xact_status;
+enum { VS_VIS_R_MULTIXACT, VS_VIS_R_SUBCOMMITTED, VS_VIS_R_CLOG_RANGE, VS_VIS_R_COMBOCID, VS_VIS_R_MOVED, VS_VIS_R_SUBOVERFLOW, VS_VIS_R_N };
+typedef struct vs_vis_stats {
+    uint64_t n_visible, n_invisible, n_undecided;
+    uint64_t n_deleted, n_not_found, n_dead_line_pointer; /* parts of n_invisible, classified as vs_heap_info classifies them */
+    uint64_t chain_hops;                                  /* members looked at beyond the first, summed */
+    uint64_t undecided_by_reason[VS_VIS_R_N];
+} vs_vis_stats;
+int vs_heap_res_visibility(vs_heap_res* h, const uint64_t* d_heap_tids, uint32_t n, const vs_mvcc_snapshot* snapshot,
+                           const vs_xact_status* xact, uint8_t* d_visible /* device [n] */, vs_vis_stats* out /* may be NULL */,
+                           uint32_t* undecided_nodes /* host, may be NULL */, uint32_t cap, uint32_t* n_undecided /* may be NULL */);
+/* The same over the index's own heap tid column, written straight into the library-owned mask of snapshot id 1 ..
+ * VS_MAX_SNAPSHOTS - 1 (allocated as vs_index_snapshot_put allocates it, at capacity: rows inserted later read 0 in it).
+ * vs_index_snapshot_put_dev: vs_index_snapshot_put with the n bytes already in device memory (copied; the buffer stays the
+ * caller's).  vs_index_snapshot_patch: mask[nodes[i]] = values[i] != 0 for host arrays of n entries (the last entry of a node
+ * wins) — how the shim settles the undecided few after index_fetch_tuple.  Refusals are those of vs_index_snapshot_put, plus
+ * VS_ERR_STATE while a batch of the handle is in flight and, for _patch, when the id has no mask or a node is >= n; a refused call
+ * changes nothing.  An evaluation that ends in VS_ERR_INVALID (a malformed page) drops the mask of that id.  With a broker attached
+ * only its dispatcher may call these (vs_broker_call). */
+int vs_index_snapshot_eval(vs_index* idx, vs_heap_res* h, uint32_t snapshot, const vs_mvcc_snapshot* snap, const vs_xact_status* xact,
+                           vs_vis_stats* out, uint32_t* undecided_nodes, uint32_t cap, uint32_t* n_undecided);
+int vs_index_snapshot_put_dev(vs_index* idx, uint32_t snapshot, const uint8_t* d_visible);
+int vs_index_snapshot_patch(vs_index* idx, uint32_t snapshot, const uint32_t* nodes, const uint8_t* values, uint32_t n);
+
 /* The same, decoded ON the device (vs_pages_dev.hip): the blocks are copied to HBM as they are (pinned ring,
  * hipMemcpyAsync), the host only reads the page headers on the way past, and one kernel (a wave per node page) walks the
  * line pointers and rkyv relative pointers and writes codes / neighbor ids / heap tids into the index arrays; label sets

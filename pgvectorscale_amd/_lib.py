@@ -101,6 +101,29 @@ class HeapInfo(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+VIS_REASONS = ("multixact", "subcommitted", "clog_range", "combocid", "moved", "suboverflow")  # VS_VIS_R_*
+
+
+class MvccSnapshot(C.Structure):
+    _fields_ = [("xmin", C.c_uint32), ("xmax", C.c_uint32), ("xip", C.c_void_p), ("xcnt", C.c_uint32), ("subxip", C.c_void_p),
+                ("subxcnt", C.c_uint32), ("suboverflowed", C.c_int32), ("taken_during_recovery", C.c_int32), ("own_xids", C.c_void_p),
+                ("n_own", C.c_uint32), ("curcid", C.c_uint32)]
+
+
+class XactStatus(C.Structure):
+    _fields_ = [("first_xid", C.c_uint32), ("n_xids", C.c_uint32), ("bits", C.c_void_p)]
+
+
+class VisStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_visible", "n_invisible", "n_undecided", "n_deleted", "n_not_found", "n_dead_line_pointer",
+                                          "chain_hops")] + [("undecided_by_reason", C.c_uint64 * len(VIS_REASONS))]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_[:7]}
+        d["undecided_by_reason"] = {r: int(self.undecided_by_reason[i]) for i, r in enumerate(VIS_REASONS)}
+        return d
+
+
 class PagesInfo(C.Structure):
     _fields_ = [("n_blocks", C.c_uint32), ("n_nodes", C.c_uint32), ("words", C.c_uint32), ("num_neighbors", C.c_uint32),
                 ("has_labels", C.c_uint32), ("n_deleted", C.c_uint32), ("n_label_vals", C.c_uint64),
@@ -271,6 +294,16 @@ SYMBOLS = {
     "vs_heap_dev_toast_add": (_i, [_vp, _u32, _vp, _u32]),
     "vs_heap_dev_finish": (_i, [_vp, C.POINTER(HeapInfo), _vp, C.POINTER(_u32)]),
     "vs_heap_dev_close": (None, [_vp]),
+    "vs_heap_res_open": (_i, [_vp, _u32, _u32, C.POINTER(_vp)]),
+    "vs_heap_res_put": (_i, [_vp, _u32, _vp, _u32]),
+    "vs_heap_res_blocks": (_u32, [_vp]),
+    "vs_heap_res_close": (None, [_vp]),
+    "vs_heap_res_visibility": (_i, [_vp, _vp, _u32, C.POINTER(MvccSnapshot), C.POINTER(XactStatus), _vp, C.POINTER(VisStats), _vp, _u32,
+                                    C.POINTER(_u32)]),
+    "vs_index_snapshot_eval": (_i, [_vp, _vp, _u32, C.POINTER(MvccSnapshot), C.POINTER(XactStatus), C.POINTER(VisStats), _vp, _u32,
+                                    C.POINTER(_u32)]),
+    "vs_index_snapshot_put_dev": (_i, [_vp, _u32, _vp]),
+    "vs_index_snapshot_patch": (_i, [_vp, _u32, _vp, _vp, _u32]),
     "vs_meta_layout_default": (_i, [C.POINTER(MetaLayout)]),
     "vs_meta_page_decode": (_i, [_vp, _sz, C.POINTER(MetaLayout), C.POINTER(MetaPage), _vp, _vp, _vp, _u32]),
     "vs_pages_meta": (_i, [_vp, C.POINTER(MetaLayout), C.POINTER(MetaPage), C.POINTER(IndexDesc), _vp, _vp, _u32]),
@@ -420,6 +453,25 @@ def load():
         f.argtypes = args
     _lib = L
     return L
+
+
+def vis_args(snapshot, xact):
+    """the C form of an MVCC snapshot and a pg_xact window (include/vsgpu.h: vs_mvcc_snapshot, vs_xact_status).
+    snapshot: dict with xmin, xmax and optionally xip, subxip, own_xids (xid sequences, any order), suboverflowed,
+    taken_during_recovery, curcid; xact: (first_xid, n_xids, bits uint8 [(n_xids + 3) // 4]) -> (MvccSnapshot, XactStatus, arrays
+    the two point into: keep them until the call has returned)"""
+    import numpy as np
+    arr = {k: np.ascontiguousarray(snapshot.get(k, ()), np.uint32).ravel() for k in ("xip", "subxip", "own_xids")}
+    first_xid, n_xids, bits = xact
+    bits = np.ascontiguousarray(bits, np.uint8).ravel()
+    if bits.size < (int(n_xids) + 3) // 4:
+        raise ValueError(f"{bits.size} status bytes do not hold {n_xids} xids")
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None  # noqa: E731
+    s = MvccSnapshot(int(snapshot["xmin"]), int(snapshot["xmax"]), ptr(arr["xip"]), arr["xip"].size, ptr(arr["subxip"]), arr["subxip"].size,
+                     int(bool(snapshot.get("suboverflowed", False))), int(bool(snapshot.get("taken_during_recovery", False))),
+                     ptr(arr["own_xids"]), arr["own_xids"].size, int(snapshot.get("curcid", 0)))
+    x = XactStatus(int(first_xid), int(n_xids), ptr(bits))
+    return s, x, (arr, bits)
 
 
 def check(code):

@@ -26,7 +26,7 @@ enum : uint8_t { HS_PENDING = 0, HS_INLINE = 1, HS_WAIT_TOAST = 2, HS_NULL = 3, 
 enum { HE_OK = 0, HE_PAGE_SIZE, HE_PAGE_HEADER, HE_ITEM_BOUNDS, HE_TUPLE_SHORT, HE_HOFF, HE_DESC_SHORT, HE_ATTR_START, HE_EXT_TRUNC,
        HE_VARTAG, HE_1B_ZERO, HE_4B_TRUNC, HE_4B_SHORT, HE_CSTRING, HE_ATTLEN, HE_ATTR_PAST, HE_DATUM_SHORT, HE_DIM, HE_DATUM_SIZE,
        HE_RAWSIZE, HE_EXT_RAW, HE_EXTSIZE, HE_REF_TABLE, HE_CHUNK_NULL, HE_CHUNK_EXTERNAL, HE_CHUNK_COMPRESSED, HE_CHUNK_RANGE,
-       HE_CHUNK_BYTES, HE_DUP_VALUE, HE_LAST = HE_DUP_VALUE };
+       HE_CHUNK_BYTES, HE_DUP_VALUE, HE_CHAIN_CYCLE, HE_LAST = HE_CHAIN_CYCLE };
 static const char* const kHeapErrorText[] = {
     "", "pd_pagesize_version does not say the reader's pagesize", "inconsistent page header (pd_lower, pd_upper, pd_special)",
     "item lies outside pd_upper..pd_special", "tuple shorter than its header", "t_hoff does not fit the tuple and its attributes",
@@ -39,7 +39,8 @@ static const char* const kHeapErrorText[] = {
     "external vector's raw size does not match the dimensions", "external size above raw size",
     "more external vectors than wanted tuples", "NULL in a chunk row", "external chunk data", "compressed chunk data",
     "chunk does not fit its value (negative chunk_seq, short non-final chunk or bytes past the value's size)",
-    "more chunk bytes than the value's size", "TOAST value is referenced by two heap tuples"};
+    "more chunk bytes than the value's size", "TOAST value is referenced by two heap tuples",
+    "HOT chain visits more members than the page has line pointers (a cycle)"};
 static_assert(sizeof(kHeapErrorText) / sizeof(kHeapErrorText[0]) == HE_LAST + 1, "one text per HE_* code");
 
 // counters / records of a reader in device memory (u32 words)
@@ -82,6 +83,11 @@ __device__ __forceinline__ uint32_t heap_page_view(const uint8_t* page, uint32_t
     if (!(lower >= 24 && lower <= v.upper && v.upper <= v.special && v.special <= page_size)) return HE_PAGE_HEADER;
     v.nitems = (lower - 24) / 4;
     return HE_OK;
+}
+
+// an LP_NORMAL line pointer names bytes that can hold a tuple: inside pd_upper..pd_special and no shorter than the 23-byte header
+__device__ __forceinline__ bool heap_item_in_bounds(const HeapPage& pg, uint32_t lp_off, uint32_t lp_len) {
+    return lp_off >= pg.upper && lp_off + lp_len <= pg.special && lp_len >= 23;
 }
 
 // heap_deform_tuple up to attribute `want` (0-based) of the tuple of `len` bytes at byte t0 of the page (t0 + len <= pd_special was
@@ -239,7 +245,7 @@ __device__ __forceinline__ HeapHit heap_resolve(const HeapDevArgs& a, const uint
             break;
         }
         hit.st = HS_N;
-        if (lp_off < pg.upper || lp_off + lp_len > pg.special || lp_len < 23) {
+        if (!heap_item_in_bounds(pg, lp_off, lp_len)) {
             heap_error(a.ctr, HE_ITEM_BOUNDS, 0, blk, off, lp);
             break;
         }
@@ -381,7 +387,7 @@ __global__ __launch_bounds__(WAVE) void k_heap_dev_toast(HeapDevArgs a) {
                 const uint32_t lp = ld32(page + 24 + 4 * (off - 1));
                 const uint32_t lp_off = lp & 0x7FFFu, fl = (lp >> 15) & 3u, lp_len = lp >> 17;
                 if (fl != 1u) break;
-                if (lp_off < pg.upper || lp_off + lp_len > pg.special || lp_len < 23) {
+                if (!heap_item_in_bounds(pg, lp_off, lp_len)) {
                     heap_error(a.ctr, HE_ITEM_BOUNDS, 1, blk, off, lp);
                     break;
                 }

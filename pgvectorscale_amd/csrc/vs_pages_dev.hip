@@ -41,6 +41,7 @@ __device__ __forceinline__ uint32_t ld32(const uint8_t* p) {  // items are MAXAL
 }
 
 #include "vs_heap_dev.h"  // vs_heap_dev_*: the heap's vector column from heap and TOAST pages (kernels and their host code)
+#include "vs_heap_vis.h"  // vs_heap_res_*, vs_index_snapshot_eval: heap visibility from a resident copy of the heap's main fork
 
 // err[0] = first error code (0 = none), err[1] = block, err[2] = item, err[3] = detail
 __device__ __forceinline__ void page_error(uint32_t* err, uint32_t code, uint32_t blk, uint32_t item, uint32_t detail) {

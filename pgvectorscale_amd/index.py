@@ -283,6 +283,30 @@ class DiskAnnIndex:
             raise ValueError(f"visibility mask must have shape ({self.desc.n},), got {v.shape}")
         check(self._L.vs_index_set_visibility(self.h, _p(v)))
 
+    def snapshot_eval(self, heap, snapshot_id, snapshot, xact, cap=None):
+        """The visibility mask of snapshot id 1..15 decided on the device from the resident heap fork `heap` (pages.HeapResident)
+        over this index's heap tid column (vs_index_snapshot_eval; snapshot / xact as _lib.vis_args takes them) -> (stats dict,
+        undecided nodes uint32 ascending (their bytes are 1: settle them with snapshot_patch), their full number)"""
+        s, x, _keep = _lib.vis_args(snapshot, xact)
+        cap = self.desc.n if cap is None else cap
+        und = np.empty(max(cap, 1), np.uint32)
+        st, nu = _lib.VisStats(), C.c_uint32(0)
+        check(self._L.vs_index_snapshot_eval(self.h, heap.h, snapshot_id, C.byref(s), C.byref(x), C.byref(st), _p(und), cap, C.byref(nu)))
+        return st.as_dict(), und[:min(cap, int(nu.value))].copy(), int(nu.value)
+
+    def snapshot_put_dev(self, snapshot_id, d_visible):
+        """vs_index_snapshot_put with the n bytes already in device memory (copied into the library's own mask)"""
+        d = d_visible if isinstance(d_visible, C.c_void_p) or d_visible is None else C.c_void_p(d_visible)
+        check(self._L.vs_index_snapshot_put_dev(self.h, snapshot_id, d))
+
+    def snapshot_patch(self, snapshot_id, nodes, values):
+        """mask[nodes[i]] = values[i] != 0 in the mask of snapshot id (the last entry of a node wins)"""
+        nd = np.ascontiguousarray(nodes, np.uint32).ravel()
+        v = np.ascontiguousarray(values, np.uint8).ravel()
+        if nd.shape != v.shape:
+            raise ValueError(f"{nd.size} nodes but {v.size} values")
+        check(self._L.vs_index_snapshot_patch(self.h, snapshot_id, _p(nd), _p(v), nd.size))
+
     def download(self, codes=True, nbrs=True, tids=True, vecs=False, row_begin=0, row_count=None):
         n = self.desc.n if row_count is None else row_count
         out = {}

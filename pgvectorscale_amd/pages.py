@@ -191,6 +191,55 @@ class HeapColumnDev:
             pass
 
 
+class HeapResident:
+    """The heap's main fork resident in device memory (vs_heap_res_*), indexed by block number: put() the whole fork once and the
+    changed blocks afterwards; visibility() then decides, on the device, what table_index_fetch_tuple would find behind every heap
+    tid under an MVCC snapshot (include/vsgpu.h has the rule).  DiskAnnIndex.snapshot_eval runs it over an index's own tid column."""
+
+    def __init__(self, ctx, capacity_blocks=0, page_size=BLCKSZ):
+        self._L = _lib.load()
+        self.ctx = ctx
+        self.page_size = page_size
+        self.h = None
+        h = C.c_void_p()
+        check(self._L.vs_heap_res_open(ctx.h, page_size, capacity_blocks, C.byref(h)))
+        self.h = h
+
+    def put(self, pages, first_block=0):
+        """host pages of blocks first_block.. (any order across calls; a later put of a block overwrites it)"""
+        buf = np.frombuffer(pages, np.uint8)
+        if buf.size % self.page_size:
+            raise ValueError(f"{buf.size} bytes is not a whole number of {self.page_size}-byte pages")
+        check(self._L.vs_heap_res_put(self.h, first_block, buf.ctypes.data_as(C.c_void_p), buf.size // self.page_size))
+
+    def blocks(self):
+        """one past the highest block ever put"""
+        return int(self._L.vs_heap_res_blocks(self.h))
+
+    def visibility(self, d_heap_tids, n, snapshot, xact, d_visible, cap=None):
+        """d_heap_tids: device uint64 [n]; d_visible: device uint8 [n], written.  snapshot / xact: see _lib.vis_args.  cap: how many
+        undecided nodes to hand back (None: all of them) -> (stats dict, undecided nodes uint32 ascending, their full number)"""
+        s, x, _keep = _lib.vis_args(snapshot, xact)
+        cap = n if cap is None else cap
+        und = np.empty(max(cap, 1), np.uint32)
+        st, nu = _lib.VisStats(), C.c_uint32(0)
+        as_ptr = lambda p: p if isinstance(p, C.c_void_p) or p is None else C.c_void_p(p)  # noqa: E731
+        check(self._L.vs_heap_res_visibility(self.h, as_ptr(d_heap_tids), n, C.byref(s), C.byref(x), as_ptr(d_visible), C.byref(st),
+                                             und.ctypes.data_as(C.c_void_p), cap, C.byref(nu)))
+        return st.as_dict(), und[:min(cap, int(nu.value))].copy(), int(nu.value)
+
+    def close(self):
+        if self.h:
+            self._L.vs_heap_res_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class IndexPages:
     def __init__(self, has_labels=False, page_size=BLCKSZ, layout=None, threads=0, plain=False):
         """plain=True: a `plain` storage index (PlainNode items: full-precision vectors in the nodes, no SBQ codes, no labels)"""
