@@ -66,7 +66,8 @@ static Caps initial_caps(const vs_index* ix, uint32_t L, uint32_t M) {
         const double want = 0.75 * ix->obs.ins_mean;
         hl_auto = want > 2047 ? 4095 : (want > 1023 ? 2047 : 1023);
     }
-    // table-less regime: 80 VGPRs (6 waves per SIMD = 24 scans per CU) need 6.6 KB of LDS per scan at most: a 511-entry heap
+    // table-less regime: 80 VGPRs (6 waves per SIMD = 24 scans per CU) need 6.6 KB of LDS per scan at most (the plain unit of the usual
+    // index is held to 72 VGPRs, 7 waves = 28 per CU: 5.7 KB, vs_search_fast.hip FAST_WAVES): a 511-entry heap
     // top (measured: 105.2 vs 108.1 ms at 50M against 5 waves with 1023 entries)
     if (!lds_table) hl_auto = 511;
     c.f_hl = env_u32("VS_F_HL", hl_auto);
@@ -420,7 +421,9 @@ static int choose_tables16(vs_index* ix, FastLaunch& f, uint32_t vmode, bool slo
     // ... or (VS_F_VIRGIN=3) 16-BIT entries: buckets of eight slots (one 16-byte load), the entry is the remainder of a bijective
     // hash of the node id given its bucket (quotienting), a small overflow table of whole ids behind the buckets.  Half the bytes
     // per slot: the tables of the scans in flight are the largest part of the kernel's hot private state (fast_scan, VG == 3).
-    // Needs a power-of-two number of buckets and ceil(log2 n) - log2(buckets) <= 16 remainder bits.
+    // Any number of buckets (the fitted gcap as it is, a multiple of 256 slots, since round 20: the cut of the hashed id into bucket and
+    // entry is a division by a constant of the launch, vs_q16.h — rounding the table up to a power of two cost up to twice the
+    // footprint the fit had asked for); needs at least 2^(ceil(log2 n) - 16) buckets, so that an entry fits 16 bits.
     // Round 6 (profiles/r06/s20-s22): the rule used to be "only while it costs no scans per CU", against the 4-byte slot bitmap, which
     // itself had to cost none against the bucket bitmap — and at search_list_size 100 (a visited ring of 3 KB per scan) it does:
     // 19 resident scans per CU against 23.  So the reference's default GUCs, the label-filtered configuration and every other long
@@ -433,7 +436,7 @@ static int choose_tables16(vs_index* ix, FastLaunch& f, uint32_t vmode, bool slo
     // heap spill arrays carrying most of the traffic) runs 436.6 ms with them against 382.2 without (s24).
     if (vmode != 3 || !f.vwords || !slot_eligible || f.lh != 0) return VS_OK;
     FastLaunch g = f;
-    g.gcap = std::max<uint32_t>(next_pow2_u32(f.gcap), 1024);
+    g.gcap = std::max<uint32_t>(round_up_u32(f.gcap, 256), 1024);
     if (!fast_tables16_geometry(ix, g)) return VS_OK;
     g.glimit = (uint32_t)((uint64_t)g.gcap * gload_pct() / 100) - 64u;
     char tail[48];
@@ -464,6 +467,10 @@ static int choose_heap_top(vs_index* ix, FastLaunch& f, Caps& caps, bool phase) 
         caps.f_hl = h.hl;  // (the batch's later chunks and its finish see the smaller heap top: the rule runs once per batch)
         caps.f_gstride = h.gstride;
     }
+    // (The mirror image — a heap top of 1 023 entries where the registers, not LDS, hold the launch — is not built.  At search_list_size 3
+    // a scan's LDS is 5 088 B with a top of 511 and 7 136 B with 1 023, which fits 22 times into a CU's 160 KB: the plain unit's 28
+    // scans per CU (seven waves per SIMD) have 5 851 B each and even 24 would have only 6 826 B, so "costs no resident scan" never
+    // holds — at 24 it is the visited ring's 1 KB that puts it over.)
     return VS_OK;
 }
 
@@ -663,6 +670,9 @@ static int dump_fast_status(vs_index* ix, const FastLaunch& f, double pool_frac)
     for (uint32_t v : stv) hist[v & 15]++;
     fprintf(stderr, "[VS_DEBUG_STATUS] fast kernel: lh=%u gcap=%u vr=%u minw=%u bitmap_words=%u (per %s); pool claims=%u of %u;",
             f.lh, f.gcap, f.vr, f.minw, f.vwords, f.vslot == 2 ? "slot, 16-bit entries" : f.vslot ? "slot" : "bucket", ctr[0], fast_pool_slots(f.nq, pool_frac));
+    if (f.vslot == 2)  // (the 16-bit tables as they really are: buckets x entries per bucket, overflow slots, bytes of one table)
+        fprintf(stderr, " q16: %u buckets x %u entries (qd=%u qm=%#x qs=%u) ocap=%u table_bytes=%u;", f.gcap >> 3, f.qe, f.qd, f.qm, f.qs, f.ocap, f.gregion * 4);
+    fprintf(stderr, " hl=%u vcap=%u lds_bytes=%zu resident=%u;", f.hl, f.vr ? 512u : f.vcap, fast_lds_bytes(ix, f), f.persist);
     for (int i = 0; i < 16; ++i)
         if (hist[i]) fprintf(stderr, " status[%d]=%u", i, hist[i]);
     fprintf(stderr, "\n");

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/vsgpu.h"
+#include "vs_q16.h"
 
 #define VS_EMPTY 0xFFFFFFFFu
 
@@ -356,10 +357,10 @@ struct FastLaunch {
     uint32_t vwords = 0;  // != 0: words of the LDS bitmap of written buckets (one bit per four slots of gcap): tables are neither cleared nor read before their first write
     uint32_t vslot = 0;   // with vwords: the bitmap has one bit per SLOT (gcap / 32 words) and the table is probed slot by slot (linear probing)
                           // 2: ... and the table holds 16-BIT entries in buckets of eight (quotienting, see fast_scan VG == 3)
-    // vslot == 2: an id is mapped by a bijection on qd bits to x; bucket = x >> qk (gcap / 8 buckets, a power of two), the entry is the
-    // remainder x & (2^qk - 1) (qk <= 16); ids whose bucket is full go to an overflow table of ocap 32-bit slots behind the buckets
-    // (handles gcap ..); gregion = u32 words per region (gcap / 2 + ocap)
-    uint32_t qd = 0, qk = 0, ocap = 0, gregion = 0;
+    // vslot == 2: an id is mapped by a bijection on qd bits to x; bucket = x / qe = mulhi(x, qm) >> qs (gcap / 8 buckets, any number),
+    // the entry is the remainder x - bucket qe (qe <= 2^16, vs_q16.h); ids whose bucket is full go to an overflow table of ocap 32-bit
+    // slots behind the buckets (handles gcap ..); gregion = u32 words per region (gcap / 2 + ocap)
+    uint32_t qd = 0, qe = 0, qm = 0, qs = 0, ocap = 0, gregion = 0;
     uint32_t build = 0; // 1: greedy_search_for_build (the visited list is the output; needs vr == 0)
     uint32_t flags = 0; // FAST_* (measurement switches)
     // second attempt of the scans a first launch gave up on (bigger capacities): only scans whose status[q] != 0 run, their
@@ -399,25 +400,24 @@ enum {
     FAST_FULL_VARIANT = 8,     // run the instantiation that handles label keys and a visibility mask even when the batch has neither
 };
 size_t fast_lds_bytes(const vs_index* idx, const FastLaunch& s);
-// The 16-bit table form (vslot == 2) of a launch whose gcap is set (a power of two >= 1024): fills ocap, vwords, vslot, sb, qd, qk
-// and gregion as fast_scan (VG == 3) lays the tables out.  false: the form cannot be represented for this index — more than 16
-// remainder bits, more than 32 hashed bits, or no room for the Hamming key beside a slot handle in a heap entry.
+// The 16-bit table form (vslot == 2) of a launch whose gcap is set (any multiple of 256 slots): fills ocap, vwords, vslot, sb, qd, qe, qm,
+// qs and gregion as fast_scan (VG == 3) lays the tables out (q16_geometry).  false: the form cannot be represented for this index —
+// fewer than 2^(qd - 16) buckets (an entry of more than 16 bits), more than 32 hashed bits, or no room for the Hamming key beside a
+// slot handle in a heap entry.
 static inline bool fast_tables16_geometry(const vs_index* idx, FastLaunch& f) {
-    uint32_t qd = 1, lb = 0;
-    while ((1ull << qd) < (uint64_t)(idx->d.n > 2 ? idx->d.n : 2)) qd++;
-    while ((1u << lb) < (f.gcap >> 3)) lb++;
-    if (qd < lb + 3) qd = lb + 3;  // (a small index: more hash bits than id bits — the bijection works on any width)
-    f.qd = qd;
-    f.qk = qd - lb;
-    const uint32_t o = round_up_u32(f.gcap / 16, 32);
-    f.ocap = o > 256 ? o : 256;
-    f.vwords = (f.gcap + f.ocap) / 32;
+    Q16Geometry g;
+    const bool ok = q16_geometry(idx->d.n, f.gcap, &g);
+    f.qd = g.qd;
+    f.qe = g.qe;
+    f.qm = g.qm;
+    f.qs = g.qs;
+    f.ocap = g.ocap;
+    f.vwords = g.vwords;
     f.vslot = 2;
-    f.gregion = (f.gcap >> 1) + f.ocap;
-    f.sb = 0;
-    while ((1ull << f.sb) < (uint64_t)f.gcap + f.ocap) f.sb++;
+    f.gregion = g.gregion;
+    f.sb = g.sb;
     const uint64_t nbits = (uint64_t)idx->d.dim_index * idx->d.bits;
-    return f.qk <= 16 && f.qd <= 32 && nbits < (1ull << (32 - f.sb));
+    return ok && nbits < (1ull << (32 - f.sb));
 }
 int launch_search_fast(vs_index* idx, const FastLaunch& s);
 int fast_resident_scans(vs_index* idx, const FastLaunch& s, uint32_t* out);  // size of a persistent grid for this instantiation

@@ -185,7 +185,8 @@ static int scanpool_create_impl(vs_index* ix, uint32_t capacity, uint32_t L, uin
         f.gstride = round_up_u32(f.hcap - f.hl + 2, 2);
         f.vcap = round_up_u32(std::max<uint32_t>(2u * (uint32_t)std::min<uint64_t>((uint64_t)L + L / 2 + 32, 1u << 16), 64), 64);
         f.minw = 1;
-        f.gcap = std::max<uint32_t>(next_pow2_u32(std::min<uint64_t>(pushes * 4 / 3 + 256, 1u << 22)), 1024);
+        // (the table the horizon asks for as it is, a multiple of 256 slots: the 16-bit tables take any number of buckets)
+        f.gcap = std::max<uint32_t>(round_up_u32((uint32_t)std::min<uint64_t>(pushes * 4 / 3 + 256, 1u << 22), 256), 1024);
         f.glimit = (uint32_t)((uint64_t)f.gcap * 3 / 4) - 64u;
         const uint32_t nch = (ix->code_stride + 7) / 8;
         if (fast_tables16_geometry(ix, f) && nch <= 6 && fast_lds_bytes(ix, f) <= POOL_LDS_BUDGET) {

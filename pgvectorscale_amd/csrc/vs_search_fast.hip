@@ -47,12 +47,7 @@
 #include "vs_device.h"
 
 #define MAX_QLABELS 64
-// odd multipliers of the 16-bit table's bijection (fast_scan, VG == 3) and their inverses mod 2^32
-#define VS_Q16_A 0x9E3779B1u
-#define VS_Q16_B 0x85EBCA6Bu
-#define VS_Q16_AI 0x0E8B2F51u
-#define VS_Q16_BI 0xA5CB9243u
-static_assert((uint32_t)(VS_Q16_A * VS_Q16_AI) == 1u && (uint32_t)(VS_Q16_B * VS_Q16_BI) == 1u, "inverse multipliers");
+// (the 16-bit table's bijection and its cut into bucket and entry — fast_scan, VG == 3 — are vs_q16.h, shared with the launch planning)
 #define ARB_SLOTS 128
 
 struct FastArgs {
@@ -955,27 +950,19 @@ __device__ __forceinline__ void fast_scan(const FastArgs& a, const uint32_t q, c
     // build mode, LDS-table regime overflow)
     auto g_empty = [&](uint32_t v) -> bool { return v == VS_EMPTY; };
     // ---- VG == 3: 16-bit entries.  The id is mapped by a bijection on qd bits (multiply, xor-shift, multiply, xor-shift: each step is
-    // invertible mod 2^qd) to x; the bucket of eight slots is x >> qk, the entry the remainder x & (2^qk - 1), the preferred slot x & 7.
+    // invertible mod 2^qd) to x; the bucket of eight slots is x / qe — a multiply-high and a shift, for any number of buckets —, the
+    // entry the remainder x - bucket qe < 2^16, the preferred slot x & 7 (vs_q16.h).
     // (bucket, entry) names the id: q_inv gives it back, so a heap entry's handle (the slot) still finds the node without a second array.
     const uint32_t qdm = in_vgpr(VG == 3 ? (s.qd >= 32 ? 0xFFFFFFFFu : (1u << s.qd) - 1u) : 0u);
     const uint32_t qxs = in_vgpr((s.qd + 1u) >> 1);  // (2 qxs >= qd: x ^= x >> qxs is its own inverse)
-    const uint32_t qk_v = in_vgpr(s.qk), rmask_v = in_vgpr((1u << s.qk) - 1u);
+    // (two vector registers, as the shift and the mask they replace: qc = qe << 5 | qs — a shift only reads the low five bits of its count)
+    const uint32_t qm_v = in_vgpr(s.qm), qc_v = in_vgpr((s.qe << 5) | s.qs);
     const uint32_t ovf_lim_v = in_vgpr(s.ocap - s.ocap / 4);  // (the overflow table's load limit)
-    // (the multipliers are compile-time constants — the kernel lives at its scalar-register limit; the launch wrapper checks that the
-    // host's copies agree)
-    auto q_fwd = [&](uint32_t id) -> uint32_t {
-        uint32_t x = (id * VS_Q16_A) & qdm;
-        x ^= x >> qxs;
-        x = (x * VS_Q16_B) & qdm;
-        x ^= x >> qxs;
-        return x;
-    };
-    auto q_inv = [&](uint32_t x) -> uint32_t {
-        x ^= x >> qxs;
-        x = (x * VS_Q16_BI) & qdm;
-        x ^= x >> qxs;
-        return (x * VS_Q16_AI) & qdm;
-    };
+    // (the hash multipliers are compile-time constants — the kernel lives at its scalar-register limit; the launch's own constants
+    // live in vector registers, and the launch wrapper checks them against the geometry it computes itself)
+    auto q_fwd = [&](uint32_t id) -> uint32_t { return q16_fwd(id, qdm, qxs); };
+    auto q_inv = [&](uint32_t x) -> uint32_t { return q16_inv(x, qdm, qxs); };
+    auto q_bucket = [&](uint32_t x) -> uint32_t { return q16_bucket(x, qm_v, qc_v); };
     auto node_load = [&](uint32_t handle) -> uint32_t {
         if (VG == 3) {  // (table-less regime only: lhv == 0)
             if (handle < s.gcap) return gload16(reinterpret_cast<const uint16_t*>(ghash) + handle);
@@ -986,7 +973,7 @@ __device__ __forceinline__ void fast_scan(const FastArgs& a, const uint32_t q, c
     };
     // what node_load returned (made uniform by the caller) -> the node id
     auto node_of = [&](uint32_t handle, uint32_t raw) -> uint32_t {
-        if (VG == 3 && handle < s.gcap) return rfl(q_inv(((handle >> 3) << qk_v) | raw));  // (vector instructions: the masks live in vector registers)
+        if (VG == 3 && handle < s.gcap) return rfl(q_inv(q16_join(handle >> 3, raw, qc_v >> 5)));  // (vector instructions: the constants live in vector registers)
         return raw;
     };
     // true where the id was not present before; slot_out = its handle
@@ -1136,11 +1123,11 @@ __device__ __forceinline__ void fast_scan(const FastArgs& a, const uint32_t q, c
     // eight entries of the bucket are other ids.  Half the bytes per slot of the 4-byte table and never a second dependent load.
     auto b16_occ = [&](uint32_t hb) -> uint32_t { return (vmap[hb >> 2] >> ((hb & 3u) << 3)) & 0xFFu; };
     auto b16_run = [&](uint32_t x) -> uint32_t {  // occupied slots in a row, cyclic, from x's preferred slot (0: it is free, 8: full)
-        const uint32_t occ = b16_occ(x >> qk_v);
+        const uint32_t occ = b16_occ(q_bucket(x));
         const uint32_t rot = ((occ | (occ << 8)) >> (x & 7u)) & 0xFFu;
         return (uint32_t)__builtin_ctz(~rot);
     };
-    auto b16_load = [&](uint32_t x) -> uint4 { return *reinterpret_cast<const uint4*>(ghash + ((size_t)(x >> qk_v) << 2)); };
+    auto b16_load = [&](uint32_t x) -> uint4 { return *reinterpret_cast<const uint4*>(ghash + ((size_t)q_bucket(x) << 2)); };
     uint32_t n_ovf = 0;
     auto ovf_insert = [&](uint32_t nid, bool act, uint32_t& slot_out) -> bool {  // (as slot_insert, on the overflow table)
         uint32_t* const ot = ghash + (s.gcap >> 1);
@@ -1197,7 +1184,7 @@ __device__ __forceinline__ void fast_scan(const FastArgs& a, const uint32_t q, c
             v = make_uint4(0, 0, 0, 0);
             if (t) v = b16_load(x);
         }
-        const uint32_t hb = x >> qk_v, r = x & rmask_v, pref = x & 7u;
+        const uint32_t hb = q_bucket(x), r = q16_entry(x, hb, qc_v >> 5), pref = x & 7u;
         // In the run of the snapshot, or new.  Straight-line for every lane (round 6; t == 0 is an empty run mask, a lane without a load
         // compares zeros): which of the eight entries equal the remainder — per 16-bit half min(entry ^ r, 1) is 0 exactly where they do
         // (v_pk_min_u16; the constant is kept opaque, or the compiler turns the minimum into eight compares and selects), the halves'
@@ -1743,12 +1730,26 @@ __device__ __forceinline__ void fast_scan(const FastArgs& a, const uint32_t q, c
     }
 }
 
+// Waves per SIMD the register allocation is held to: MINW, except for the unit the unfiltered scans of the usual index run (MINW 6,
+// no label keys, 16-bit tables, compile-time row geometry).  That one came out at 72 VGPRs — the seven-wave class, 28 scans per CU —
+// with room for 80, by the allocator's grace: the division that cuts a hashed id into bucket and entry (round 20) moved it to 76, six
+// waves, and no equivalent spelling of the arithmetic brought it back.  So the class it ran in is now stated: asked for seven waves the
+// compiler allocates 64 VGPRs without scratch, and the kernel marks v71 as used, so that the code object asks for 72 registers —
+// seven waves, not eight: the resident scans, and with them every rule of the launch planning that compares them, stay what they
+// were in every regime (8 waves per SIMD were measured neutral or slower at 10M and 50M in rounds 2, 5 and 6 and are not this
+// change).  The LDS layout and the heap stay MINW 6's.
+// (The lean unit — MINW 7, same geometry — has no such statement: with the division it compiles to 66 VGPRs, the seven-wave class its
+// name states, 28 scans per CU.)
+#define FAST_WAVES(MINW, FULL, VG, OPT) (((MINW) == 6 && !(FULL) && (VG) == 3 && (OPT) == (OPT_XW | OPT_R1 | OPT_NS64)) ? 7 : (MINW))
 template <int NCH, int VR, bool TIMING, int MINW, bool BUILD, bool FULL = true, int VG = 0, int OPT = 0>
-__global__ __launch_bounds__(WAVE, MINW) void k_search_fast(FastArgs a) {
+__global__ __launch_bounds__(WAVE, FAST_WAVES(MINW, FULL, VG, OPT)) void k_search_fast(FastArgs a) {
     // persistent grid (a.s.persist): the launch has no tail of its own beyond the last scans' lives, and the hardware never has to place a
     // new workgroup (LDS, registers, a wave slot) while the chip is full; otherwise one workgroup per scan.  ONE inlined copy of the scan
     // for both (round 6): as two copies the register allocator spilled differently in each, and a change that was neutral for the
     // launches of one kind cost those of the other 35 % in scratch traffic (profiles/r06/s12, s13).
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (FAST_WAVES(MINW, FULL, VG, OPT) != MINW) asm volatile("" ::: "v71");  // (the register count of the seven-wave class, see FAST_WAVES)
+#endif
     for (uint32_t it = 0;; ++it) {
         uint32_t q = blockIdx.x;
         if (a.s.persist) {
@@ -1827,17 +1828,27 @@ static int launch_fast_t(vs_index* idx, const FastArgs& a, size_t lds, uint32_t*
         if (a.s.vr == 8) return launch_fast_tt<3, 8, true, 1, false>(idx, a, lds, res);
         return launch_fast_tt<3, 0, true, 1, false>(idx, a, lds, res);
     }
+    if (a.s.vwords && a.s.vslot == 2) {  // the 16-bit tables, whichever instantiation runs them (the resumable one included)
+        VS_REQUIRE(a.s.vr == 0 && a.s.lh == 0 && a.s.rc == 0 && a.s.gcap >= 256 && a.s.gcap % 256 == 0 && a.s.ocap % 32 == 0 && a.s.ocap >= 64 &&
+                       (uint64_t)a.s.vwords * 32 >= (uint64_t)a.s.gcap + a.s.ocap && a.s.qd <= 32 && (a.s.qd >= 32 || a.n <= (1ull << a.s.qd)) &&
+                       a.s.gregion >= (a.s.gcap >> 1) + a.s.ocap,
+                   "fast search: bad geometry of the 16-bit dedup table");
+        // the cut of a hashed id into (bucket, entry): every x < 2^qd lands in a bucket below gcap / 8 with an entry of 16 bits, and the
+        // constants are the ones vs_q16.h derives for this index and this gcap (the kernel divides by them without a check)
+        Q16Geometry qg;
+        VS_REQUIRE(q16_geometry(a.n, a.s.gcap, &qg) && qg.qd == a.s.qd && qg.qe == a.s.qe && qg.qm == a.s.qm && qg.qs == a.s.qs && a.s.qe >= 8 &&
+                       a.s.qe <= 65536 && (uint64_t)a.s.qe * (a.s.gcap >> 3) >= (1ull << a.s.qd) && (a.s.gcap >> 3) < (1u << 24),
+                   "fast search: the 16-bit dedup table's bucket / entry constants do not belong to this index and table size");
+    }
     if (a.s.resume) {  // resumable scans (the scan pools): one workgroup per pool slot, registers unconstrained
         VS_REQUIRE(a.s.vwords && a.s.vslot == 2 && !a.s.persist && a.s.vr == 0 && a.s.lh == 0 && a.s.rc == 0 && !a.s.only_failed && a.s.pool_slots >= a.s.nq,
                    "fast search: resumable scans run the 16-bit tables with one region per slot");
+        // (a saved scan's LDS image — heap top, ring, occupancy words — is copied in 16-byte steps: q16_geometry rounds the overflow
+        // table to 128 slots for this)
+        VS_REQUIRE(a.s.vwords % 4 == 0 && (a.s.hl + 1) % 4 == 0, "fast search: a resumable scan's LDS image must be whole 16-byte words");
         return launch_fast_tt<NCH, 0, false, 1, false, true, 3, OPT_RS>(idx, a, lds, res);
     }
     if (a.s.vwords && a.s.vslot == 2) {  // 16-bit entries in buckets of eight + overflow table, occupancy bits in LDS (see fast_scan)
-        VS_REQUIRE(a.s.vr == 0 && a.s.lh == 0 && a.s.rc == 0 && a.s.gcap >= 256 && (a.s.gcap & (a.s.gcap - 1)) == 0 && a.s.ocap % 32 == 0 && a.s.ocap >= 64 &&
-                       (uint64_t)a.s.vwords * 32 >= (uint64_t)a.s.gcap + a.s.ocap && a.s.qk >= 3 && a.s.qk <= 16 && a.s.qd <= 32 &&
-                       (1ull << a.s.qd) == ((uint64_t)(a.s.gcap >> 3) << a.s.qk) && (a.s.qd >= 32 || a.n <= (1ull << a.s.qd)) &&
-                       a.s.gregion >= (a.s.gcap >> 1) + a.s.ocap,
-                   "fast search: bad geometry of the 16-bit dedup table");
         const bool plain = !a.s.qlabel_off && !a.s.visible && !(a.s.flags & FAST_FULL_VARIANT);
         // (the usual index: 24-word code rows — 768 x 2 bit, 1536 x 1 bit — and num_neighbors <= 64)
         const bool std_geom = a.code_stride == 24 && a.R <= WAVE && a.nbr_stride == 64;

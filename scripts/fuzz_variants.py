@@ -26,7 +26,10 @@ VARIANTS = [{"VS_F_MINW": "5"}, {"VS_F_MINW": "5", "VS_F_VIRGIN": "1"}, {"VS_F_V
             {"VS_F_VIRGIN": "3", "VS_F_MINW": "7"}, {"VS_F_VIRGIN": "3", "VS_F_MINW": "7", "VS_F_GCAP": "2048"},  # ... the lean 7-wave layout
             {"VS_F_VIRGIN": "3"}, {"VS_F_VIRGIN": "3", "VS_F_GCAP": "2048"}, {"VS_F_VIRGIN": "3", "VS_F_GCAP": "1024", "VS_F_GLOAD_PCT": "90"},
             # ... as long lists run them since round 6 (taken although they cost resident scans, heap top 255)
-            {"VS_F_VIRGIN": "3", "VS_F_SLOTMAP_FORCE": "1", "VS_F_HL": "255"}]
+            {"VS_F_VIRGIN": "3", "VS_F_SLOTMAP_FORCE": "1", "VS_F_HL": "255"},
+            # ... at bucket counts that are no power of two (round 20: the fitted tables as they are): 288 buckets, and 160 near the load limit
+            {"VS_F_VIRGIN": "3", "VS_F_SLOTMAP_FORCE": "1", "VS_F_GCAP": "2304"},
+            {"VS_F_VIRGIN": "3", "VS_F_SLOTMAP_FORCE": "1", "VS_F_GCAP": "1280", "VS_F_GLOAD_PCT": "90"}]
 KNOBS = sorted({k for v in VARIANTS for k in v})
 COUNTERS = ("visited_nodes", "candidate_nodes", "quantized_distance_comparisons", "node_reads", "next_calls")
 
