@@ -707,6 +707,85 @@ int vs_index_snapshot_eval(vs_index* idx, vs_heap_res* h, uint32_t snapshot, con
 int vs_index_snapshot_put_dev(vs_index* idx, uint32_t snapshot, const uint8_t* d_visible);
 int vs_index_snapshot_patch(vs_index* idx, uint32_t snapshot, const uint32_t* nodes, const uint8_t* values, uint32_t n);
 
+/* ---- Scans of different snapshots in one launch: a base of classes and per-snapshot overlays --------------------------------------
+ * A mask is one byte per node and one pass of the rule per snapshot, and a launch runs under one mask: with writers about, every
+ * READ COMMITTED statement has a snapshot of its own and would get a launch of its own.  But almost every tuple is visible, or
+ * invisible, to every snapshot that can exist; only rows touched at or after the oldest-running horizon depend on who asks.
+ *
+ * THE CLASS RULE (next to THE RULE above, whose functions it uses unchanged).  vs_index_vis_base_eval walks
+ * heap_hot_search_buffer(tid) for every node under the synthetic snapshot S_H: xmin = xmax = horizon, xip / subxip / own_xids empty,
+ * not suboverflowed, not taken during recovery.  It remembers whether any normal xid x (x >= 3) that the walk hands to own(),
+ * in_snapshot() or did_commit() has follows_eq(x, horizon) — "recent".  The node's class byte is
+ *     0  invisible to all: the verdict is invisible and nothing recent was consulted (includes offset 0, not found, a dead or unused
+ *        first line pointer)
+ *     1  visible to all:   the verdict is visible and nothing recent was consulted
+ *     2  depends:          something recent was consulted, or the verdict is UNDECIDED for any reason
+ * Soundness: under any snapshot with xmin >= horizon and every own xid >= horizon, a consulted x < horizon gives own(x) = no,
+ * in_snapshot(x) = no (precedes(x, xmin) decides first in every mode) and did_commit(x) a settled fact, and command ids are compared
+ * only under own(): the verdict of a class-0 / class-1 node does not depend on the snapshot.
+ * PRECONDITION (the caller's): horizon <= the oldest xid still running — what RecentXmin / GetOldestNonRemovableTransactionId give
+ * the shim.  The class-2 nodes are also kept as the ascending "depends list" of r entries (vs_index_vis_base_info reads it back);
+ * nothing about it depends on how the lanes are scheduled, and xids compare modulo 2^32 as in THE RULE.
+ * changed_blocks != NULL (ascending, distinct heap block numbers; n_changed may be 0) refreshes a base that exists: only nodes whose
+ * tid lies on a listed block are walked again, every other node keeps its class — with a later horizon that is conservative, never
+ * wrong — the list is rebuilt from the classes and the horizon passed is stored.  changed_blocks == NULL walks every node.
+ * Stats: n_class[] and r count the whole index after the call; the other fields count the nodes this call walked (n_walked):
+ * the parts of the invisible verdicts as vs_vis_stats names them, n_recent (class 2 with a decided verdict), n_undecided and its
+ * reasons (class 2 whatever was consulted), chain_hops.
+ * LIFETIME: every base evaluation, full or refresh, drops every overlay (overlays index list positions).  Rows inserted later read
+ * class 0 until the next evaluation that walks them, as in stored masks.  vs_index_compact drops the base and the overlays;
+ * vs_index_vis_base_drop frees them.  A malformed page is reported as by vs_index_snapshot_eval and the base is dropped.
+ *
+ * OVERLAYS.  vs_index_vis_slot_eval gathers the tids of the depends list and runs THE RULE under `snap` over those r nodes only;
+ * the result is the slot's overlay, r bytes (1 visible, 0 invisible; UNDECIDED gets 1, is counted in *out and listed ascending as
+ * NODE ids exactly as vs_index_snapshot_eval lists them; *out counts the r nodes).  Slots are 1 .. VS_MAX_VIS_SLOTS - 1; slot 0 means
+ * every tuple visible and holds no overlay.  vs_index_vis_slot_patch settles nodes of the depends list (overlay[pos(node)] =
+ * values[i] != 0, the last entry of a node wins); a node that is not on the list is VS_ERR_INVALID.  vs_index_vis_slot_drop drops
+ * one overlay.  vs_index_vis_materialize writes the byte mask of legacy snapshot id 1 .. VS_MAX_SNAPSHOTS - 1 from the base and the
+ * slot's overlay: the bridge for what still runs under a legacy id (cursors, scan pools, vs_scan_set_snapshot, the shm server).
+ * Refusals, each changing nothing: a snapshot whose xmin or any own xid precedes the stored horizon (VS_ERR_INVALID naming the xid);
+ * no base, or for _patch / _materialize no overlay (VS_ERR_STATE); a batch of the handle in flight (VS_ERR_STATE); a view handle
+ * (VS_ERR_STATE); the argument checks of vs_index_snapshot_eval.  With a broker attached only its dispatcher may call these
+ * (vs_broker_call).  vs_index_vis_share: a view takes the base and overlays of its source over, as vs_index_snapshot_share hands
+ * over the masks. */
+#define VS_MAX_VIS_SLOTS 1024
+typedef struct vs_vis_base_stats {
+    uint64_t n_class[3];                                  /* nodes of class 0 / 1 / 2 in the whole index after the call */
+    uint64_t r;                                           /* entries of the depends list == n_class[2] */
+    uint64_t n_walked;                                    /* nodes this call walked: all, or those on the changed blocks */
+    uint64_t n_deleted, n_not_found, n_dead_line_pointer; /* of the walked: parts of the invisible verdicts, as in vs_vis_stats */
+    uint64_t n_recent;                                    /* of the walked: decided, but a consulted xid is at or after the horizon */
+    uint64_t n_undecided;                                 /* of the walked: UNDECIDED verdicts */
+    uint64_t undecided_by_reason[VS_VIS_R_N];
+    uint64_t chain_hops;
+} vs_vis_base_stats;
+int vs_index_vis_base_eval(vs_index* idx, vs_heap_res* h, uint32_t horizon_xid, const vs_xact_status* xact,
+                           const uint32_t* changed_blocks /* host, NULL: every node */, uint32_t n_changed, vs_vis_base_stats* out /* may be NULL */);
+int vs_index_vis_base_drop(vs_index* idx);
+/* the stored horizon, r and the first `cap` nodes of the depends list (each output may be NULL); VS_ERR_STATE without a base */
+int vs_index_vis_base_info(const vs_index* idx, uint32_t* horizon_xid, uint32_t* r, uint32_t* depends_nodes /* host */, uint32_t cap);
+int vs_index_vis_slot_eval(vs_index* idx, vs_heap_res* h, uint32_t slot, const vs_mvcc_snapshot* snap, const vs_xact_status* xact,
+                           vs_vis_stats* out, uint32_t* undecided_nodes, uint32_t cap, uint32_t* n_undecided);
+int vs_index_vis_slot_patch(vs_index* idx, uint32_t slot, const uint32_t* nodes, const uint8_t* values, uint32_t n);
+int vs_index_vis_slot_drop(vs_index* idx, uint32_t slot);
+int vs_index_vis_materialize(vs_index* idx, uint32_t slot, uint32_t snapshot);
+int vs_index_vis_share(vs_index* view, const vs_index* src);
+/* vs_search_batch / vs_search_batch_dev with a slot per scan: scan_slots[q] (HOST for _vis, DEVICE for _dev_vis, where it must stay
+ * valid until the finish) names the overlay scan q runs under.  rescore == 0: the heap is not looked at and the slots do not matter.
+ * Slot 0: every tuple visible.  Otherwise node v is hidden iff class[v] == 0, or class[v] == 2 and the slot's overlay says 0; a
+ * hidden row is fetched, counted and dropped before the rescore window exactly as under a mask.  The index's mask in force
+ * (vs_index_set_visibility*, vs_index_snapshot_use) is not consulted by these calls.  A slot >= VS_MAX_VIS_SLOTS is VS_ERR_INVALID
+ * and a slot without an overlay VS_ERR_STATE, before anything is launched (the device slots are read back once for that).  A batch
+ * whose slots are all 0 launches what a batch without any mask launches.  Follow-up, not built yet: slots in the shm server's
+ * request layout, in scan pools and in cursors — those run under a materialized legacy id. */
+int vs_search_batch_vis(vs_index* idx, const float* queries, const int16_t* qlabels, const uint32_t* qlabel_off, const uint32_t* scan_slots,
+                        uint32_t nq, uint32_t search_list_size, uint32_t rescore, uint32_t k, uint32_t* out_ids, uint64_t* out_tids,
+                        float* out_dist, vs_stats* stats);
+int vs_search_batch_dev_vis(vs_index* idx, const float* d_queries, const int16_t* d_qlabels, const uint32_t* d_qlabel_off,
+                            const uint32_t* d_scan_slots, uint32_t nq, uint32_t search_list_size, uint32_t rescore, uint32_t k,
+                            uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist);
+int vs_search_batch_dev_vis_finish(vs_index* idx, vs_stats* stats);
+
 /* The same, decoded ON the device (vs_pages_dev.hip): the blocks are copied to HBM as they are (pinned ring,
  * hipMemcpyAsync), the host only reads the page headers on the way past, and one kernel (a wave per node page) walks the
  * line pointers and rkyv relative pointers and writes codes / neighbor ids / heap tids into the index arrays; label sets
@@ -1087,6 +1166,16 @@ int vs_broker_search(vs_broker* b, const float* query, const int16_t* labels, ui
 int vs_broker_search_snapshot(vs_broker* b, const float* query, const int16_t* labels, uint32_t n_labels, int has_label_key,
                               uint32_t search_list_size, uint32_t rescore, uint32_t k, uint32_t snapshot, uint32_t* out_ids,
                               uint64_t* out_tids, float* out_dist);
+/* the same for a scan that names a visibility slot (vs_index_vis_slot_eval; 0 = every tuple visible): such scans group by
+ * (search_list_size, rescore, k, label key present) only — the snapshot leaves the key — and run as one vs_search_batch_vis(), each
+ * scan under the overlay of its own slot.  A slot >= VS_MAX_VIS_SLOTS is VS_ERR_INVALID; a slot without an overlay fails the launch
+ * it joined with VS_ERR_STATE.  The base and the overlays are evaluated on the dispatcher thread (vs_broker_call_exclusive with
+ * vs_index_vis_base_eval / vs_index_vis_slot_eval ... on vs_broker_index); cursor lanes take them over before every task as they
+ * take over the masks.  Follow-up, not built yet: slots in the shm server's request layout, in scan pools and in cursors — those
+ * run under a materialized legacy id (vs_index_vis_materialize). */
+int vs_broker_search_vis(vs_broker* b, const float* query, const int16_t* labels, uint32_t n_labels, int has_label_key,
+                         uint32_t search_list_size, uint32_t rescore, uint32_t k, uint32_t slot, uint32_t* out_ids, uint64_t* out_tids,
+                         float* out_dist);
 /* hands a snapshot's mask (n host bytes; NULL drops it) to the dispatcher; returns when it is in place.  Thread safe. */
 int vs_broker_snapshot_put(vs_broker* b, uint32_t snapshot, const uint8_t* visible);
 int vs_broker_get_stats(vs_broker* b, vs_broker_stats* out);
@@ -1104,6 +1193,12 @@ int vs_scan_set_snapshot(vs_scan* scan, uint32_t snapshot);
 /* runs fn(arg) on the dispatcher thread between two launches and returns its result (the error text comes along): the way work
  * on ONE scan's device state reaches the only thread that may touch the index.  Thread safe; blocks. */
 int vs_broker_call(vs_broker* b, int (*fn)(void*), void* arg);
+/* The same, run while no cursor lane is inside a task (what vs_broker_snapshot_put does for a mask): for work that REWRITES what
+ * lanes read — vs_index_snapshot_eval / _patch, vs_index_vis_base_eval, vs_index_vis_slot_eval / _patch / _drop and
+ * vs_index_vis_materialize into a legacy id that a cursor may be scanning under.  Through plain vs_broker_call such a call may run
+ * while a lane's cursor reads the mask it rewrites in place, or while a lane takes the base over; on a broker with cursor lanes use
+ * this one.  VS_ERR_STATE when called from inside a dispatcher task. */
+int vs_broker_call_exclusive(vs_broker* b, int (*fn)(void*), void* arg);
 void vs_broker_destroy(vs_broker* b); /* serves what is queued, then stops the dispatcher */
 
 /* ---- the same across PROCESSES (vs_shm.cpp): PostgreSQL backends are processes, so the request queue is a POSIX shared-memory

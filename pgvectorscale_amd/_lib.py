@@ -124,6 +124,19 @@ class VisStats(C.Structure):
         return d
 
 
+class VisBaseStats(C.Structure):
+    _fields_ = [("n_class", C.c_uint64 * 3)] + [(k, C.c_uint64) for k in ("r", "n_walked", "n_deleted", "n_not_found", "n_dead_line_pointer",
+                                                                         "n_recent", "n_undecided")] + \
+               [("undecided_by_reason", C.c_uint64 * len(VIS_REASONS)), ("chain_hops", C.c_uint64)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in ("r", "n_walked", "n_deleted", "n_not_found", "n_dead_line_pointer", "n_recent",
+                                                "n_undecided", "chain_hops")}
+        d["n_class"] = [int(v) for v in self.n_class]
+        d["undecided_by_reason"] = {r: int(self.undecided_by_reason[i]) for i, r in enumerate(VIS_REASONS)}
+        return d
+
+
 class PagesInfo(C.Structure):
     _fields_ = [("n_blocks", C.c_uint32), ("n_nodes", C.c_uint32), ("words", C.c_uint32), ("num_neighbors", C.c_uint32),
                 ("has_labels", C.c_uint32), ("n_deleted", C.c_uint32), ("n_label_vals", C.c_uint64),
@@ -304,6 +317,18 @@ SYMBOLS = {
                                     C.POINTER(_u32)]),
     "vs_index_snapshot_put_dev": (_i, [_vp, _u32, _vp]),
     "vs_index_snapshot_patch": (_i, [_vp, _u32, _vp, _vp, _u32]),
+    "vs_index_vis_base_eval": (_i, [_vp, _vp, _u32, C.POINTER(XactStatus), _vp, _u32, C.POINTER(VisBaseStats)]),
+    "vs_index_vis_base_drop": (_i, [_vp]),
+    "vs_index_vis_base_info": (_i, [_vp, _vp, _vp, _vp, _u32]),
+    "vs_index_vis_slot_eval": (_i, [_vp, _vp, _u32, C.POINTER(MvccSnapshot), C.POINTER(XactStatus), C.POINTER(VisStats), _vp, _u32,
+                                    _vp]),
+    "vs_index_vis_slot_patch": (_i, [_vp, _u32, _vp, _vp, _u32]),
+    "vs_index_vis_slot_drop": (_i, [_vp, _u32]),
+    "vs_index_vis_materialize": (_i, [_vp, _u32, _u32]),
+    "vs_index_vis_share": (_i, [_vp, _vp]),
+    "vs_search_batch_vis": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, C.POINTER(Stats)]),
+    "vs_search_batch_dev_vis": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "vs_search_batch_dev_vis_finish": (_i, [_vp, C.POINTER(Stats)]),
     "vs_meta_layout_default": (_i, [C.POINTER(MetaLayout)]),
     "vs_meta_page_decode": (_i, [_vp, _sz, C.POINTER(MetaLayout), C.POINTER(MetaPage), _vp, _vp, _vp, _u32]),
     "vs_pages_meta": (_i, [_vp, C.POINTER(MetaLayout), C.POINTER(MetaPage), C.POINTER(IndexDesc), _vp, _vp, _u32]),
@@ -362,6 +387,7 @@ SYMBOLS = {
     "vs_broker_create": (_i, [_vp, C.POINTER(BrokerConfig), C.POINTER(_vp)]),
     "vs_broker_search": (_i, [_vp, _vp, _vp, _u32, _i, _u32, _u32, _u32, _vp, _vp, _vp]),
     "vs_broker_search_snapshot": (_i, [_vp, _vp, _vp, _u32, _i, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "vs_broker_search_vis": (_i, [_vp, _vp, _vp, _u32, _i, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     "vs_broker_snapshot_put": (_i, [_vp, _u32, _vp]),
     "vs_index_snapshot_put": (_i, [_vp, _u32, _vp]),
     "vs_index_has_neighbor_masks": (_i, [_vp]),
@@ -373,6 +399,7 @@ SYMBOLS = {
     "vs_broker_index": (_vp, [_vp]),
     "vs_beginscan_on_broker": (_i, [_vp, C.POINTER(_vp)]),
     "vs_broker_call": (_i, [_vp, _vp, _vp]),
+    "vs_broker_call_exclusive": (_i, [_vp, _vp, _vp]),
     "vs_scan_set_snapshot": (_i, [_vp, _u32]),
     "vs_scan_prefetch": (_i, [_vp, _u32]),
     "vs_shm_client_fetch": (_i, [_vp, C.c_uint64, _vp, _vp, _u32, _i, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, C.POINTER(_u32)]),

@@ -466,8 +466,9 @@ extern "C" void vs_index_free(vs_index* ix) {
     SearchWorkspace& w = ix->ws;
     DevBuf* bufs[] = {&w.q_full, &w.qcodes, &w.qlabels, &w.qlabel_off, &w.hash, &w.heap_g, &w.heap_g4, &w.ghash4, &w.heap_g4b, &w.ghash4b, &w.pool_ctr, &w.fb_flag, &w.phase, &w.timeline, &w.raw_q2, &w.out_ids2, &w.out_tids2, &w.out_dist2, &w.stream_ids,
                       &w.stream_ham, &w.stream_cnt, &w.stats, &w.status, &w.rr_dist, &w.out_ids, &w.out_tids,
-                      &w.out_dist, &w.resort_heap, &w.raw_q, &w.misc, &w.q_index, &w.red, &w.order_work, &w.order_perm, &w.order_labels};
+                      &w.out_dist, &w.resort_heap, &w.raw_q, &w.misc, &w.q_index, &w.red, &w.order_work, &w.order_perm, &w.order_labels, &w.vis_slots};
     for (DevBuf* b : bufs) devbuf_free(*b);
+    if (!ix->is_view) vs_vis_base_free(ix);
     if (w.red_host) (void)hipHostFree(w.red_host);
     w.red_host = nullptr;
     vs_slab_release(ix->slab);  // (after the stream synchronisation above; the last handle frees the allocation)
@@ -696,6 +697,7 @@ int vs_index_reserve_impl(vs_index* ix, uint32_t capacity, const char* what) {
     add(&ix->label_off, 4, 0, 1);
     add(&ix->visible_own, 1, 1);
     for (int sn = 1; sn < VS_MAX_SNAPSHOTS; ++sn) add(&ix->snap[sn], 1, 0);
+    if (ix->vb) add(&ix->vb->cls, 1, 0);  // (the class bytes of the visibility base: new rows read class 0, invisible to all)
     const size_t live = ix->d.n;
     int r = VS_OK;
     for (Item& it : items) {
@@ -726,6 +728,7 @@ int vs_index_reserve_impl(vs_index* ix, uint32_t capacity, const char* what) {
         *it.slot = it.fresh;
     }
     ix->capacity = capacity;
+    if (ix->vb && ix->vb->cls) ix->vb->cls_rows = capacity;
     return VS_OK;
 }
 extern "C" int vs_index_reserve(vs_index* ix, uint32_t capacity) {

@@ -211,6 +211,23 @@ extern "C" int vs_index_rerank_order(vs_index* ix, uint32_t* out_perm, uint32_t 
     return VS_OK;
 }
 
+// what the scans of a chunk may see of the heap (the heap is only fetched for the rescore window: without one nothing is hidden)
+static VisView batch_vis(const vs_index* ix, const BatchPlan& bp) {
+    VisView v;
+    if (bp.stream_only || bp.rescore == 0 || bp.vis_mode == BV_NONE) return v;
+    if (bp.vis_mode == BV_SLOTS) {
+        const VisBase* b = ix->vb;
+        v.bytes = b->cls;
+        v.slots = bp.d_slots;
+        v.dep = b->dep;
+        v.overlay = b->tab;
+        v.r = b->r;
+    } else {
+        v.bytes = ix->visible;
+    }
+    return v;
+}
+
 // rerank + rescore window over the streams the search kernels left in the workspace
 static int run_post_search(vs_index* ix, const BatchPlan& bp, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist) {
     vs_ctx* c = ix->ctx;
@@ -275,7 +292,7 @@ static int enqueue_reduce(vs_index* ix, const BatchPlan& bp) {
     VS_HIP(hipMemsetAsync(w.red.p, 0, RED_N * 8, c->stream));
     VS_TRY(launch_reduce_stats(ix, (const uint32_t*)w.stats.p, w.fb_valid ? (const uint32_t*)w.fb_flag.p : nullptr,
                                (const uint32_t*)w.stream_cnt.p, (const uint32_t*)w.status.p, bp.nq, bp.M, bp.rescore,
-                               !bp.stream_only && bp.rescore > 0, ix->last_ins_limit, (uint64_t*)w.red.p));
+                               !bp.stream_only && bp.rescore > 0, batch_vis(ix, bp).bytes != nullptr, ix->last_ins_limit, (uint64_t*)w.red.p));
     VS_HIP(hipMemcpyAsync(w.red_host, w.red.p, RED_N * 8, hipMemcpyDeviceToHost, c->stream));
     return VS_OK;
 }
@@ -305,7 +322,7 @@ static SearchLaunch general_launch(const vs_index* ix, const BatchPlan& bp, cons
     s.out_cnt = (uint32_t*)w.stream_cnt.p;
     s.stats = (uint32_t*)w.stats.p;
     s.status = (uint32_t*)w.status.p;
-    s.visible = (!bp.stream_only && bp.rescore > 0) ? ix->visible : nullptr;
+    s.vis = batch_vis(ix, bp);
     return s;
 }
 
@@ -534,7 +551,7 @@ static int plan_fast_launch(vs_index* ix, const BatchPlan& bp, Caps& caps, bool 
     f.sb = caps.f_sb;
     f.vcap = caps.f_vcap;
     f.qlabel_off = keyed ? fast_select<const uint32_t>() : nullptr;
-    f.visible = masked ? fast_select<const uint8_t>() : nullptr;
+    f.vis.bytes = masked ? fast_select<const uint8_t>() : nullptr;
     f.rc = caps.f_lh == 0 ? env_u32("VS_F_RC", 0) : 0;  // (measurement: LDS id cache in front of the dedup table in HBM)
     if (f.rc) f.rc = next_pow2_u32(f.rc);
     p.gregion = f.gcap;
@@ -581,7 +598,7 @@ static bool second_attempt_of(const vs_index* ix, const FastLaunch& first, uint3
 }
 
 // reserves the regions the plan asks for, clears the counters and the fallback marks, and puts the workspace's pointers into p.f
-static int bind_fast_buffers(vs_index* ix, FastPlan& p, const int16_t* d_qlabels, const uint32_t* d_qlabel_off, const uint8_t* visible) {
+static int bind_fast_buffers(vs_index* ix, FastPlan& p, const int16_t* d_qlabels, const uint32_t* d_qlabel_off, const VisView& vis) {
     vs_ctx* c = ix->ctx;
     SearchWorkspace& w = ix->ws;
     FastLaunch& f = p.f;
@@ -608,7 +625,7 @@ static int bind_fast_buffers(vs_index* ix, FastPlan& p, const int16_t* d_qlabels
     VS_HIP(hipMemsetAsync(w.fb_flag.p, 0, (size_t)f.nq * 4, c->stream));
     f.qlabels = d_qlabels;
     f.qlabel_off = d_qlabel_off;
-    f.visible = visible;
+    f.vis = vis;
     f.heap_g = (uint32_t*)w.heap_g4.p;
     f.ghash = (uint32_t*)w.ghash4.p;
     f.pool_counter = (uint32_t*)w.pool_ctr.p;
@@ -683,12 +700,12 @@ static int dump_fast_status(vs_index* ix, const FastLaunch& f, double pool_frac)
 static int run_fast_attempts(vs_index* ix, const BatchPlan& bp, Caps& caps, const int16_t* d_qlabels, const uint32_t* d_qlabel_off) {
     vs_ctx* c = ix->ctx;
     SearchWorkspace& w = ix->ws;
-    const uint8_t* const visible = (!bp.stream_only && bp.rescore > 0) ? ix->visible : nullptr;  // the heap is only fetched for the rescore window
+    const VisView vis = batch_vis(ix, bp);
     ix->last_ins_limit = caps.f_lh ? caps.f_lh - caps.f_lh / 8 - 64 : 0xFFFFFFFFu;
     FastPlan p;
-    VS_TRY(plan_fast_launch(ix, bp, caps, d_qlabel_off != nullptr, visible != nullptr, &p));
+    VS_TRY(plan_fast_launch(ix, bp, caps, d_qlabel_off != nullptr, vis.bytes != nullptr, &p));
     FastLaunch& f = p.f;
-    VS_TRY(bind_fast_buffers(ix, p, d_qlabels, d_qlabel_off, visible));
+    VS_TRY(bind_fast_buffers(ix, p, d_qlabels, d_qlabel_off, vis));
     VS_TRY(bind_phase_buffer(ix, f));
     std::string tl_path;
     VS_TRY(bind_timeline_buffer(ix, f, &tl_path));
@@ -761,7 +778,7 @@ static int plan_plain_launch(vs_index* ix, const BatchPlan& bp, bool masked, Pla
     if (const uint32_t v = env_u32("VS_PF_HEAP_CAP", 0)) p.hcap = v;
     p.hl = std::min(p.hl, p.hcap);
     if (plain_lds_bytes(ix, p) > PLAIN_LDS_BUDGET) return VS_OK;
-    p.visible = masked ? fast_select<const uint8_t>() : nullptr;
+    p.vis.bytes = masked ? fast_select<const uint8_t>() : nullptr;
     uint32_t res = 0;
     VS_TRY(plain_resident_scans(ix, p, &res));
     if (const uint32_t v = env_u32("VS_PF_SCANS_PER_CU", 0)) res = std::min<uint32_t>(res, std::max<uint32_t>(v, 1) * (uint32_t)ix->ctx->prop.multiProcessorCount);
@@ -783,7 +800,7 @@ static int run_plain_attempt(vs_index* ix, const BatchPlan& bp, PlainLaunch p) {
     VS_HIP(hipMemsetAsync(w.pool_ctr.p, 0, 64, c->stream));
     VS_TRY(devbuf_reserve(c, w.fb_flag, (size_t)p.nq * 4));
     VS_HIP(hipMemsetAsync(w.fb_flag.p, 0, (size_t)p.nq * 4, c->stream));
-    p.visible = (!bp.stream_only && bp.rescore > 0) ? ix->visible : nullptr;
+    p.vis = batch_vis(ix, bp);
     p.heap_g = (uint64_t*)w.heap_g4.p;
     p.table_g = (uint32_t*)w.ghash4.p;
     p.scan_counter = (uint32_t*)w.pool_ctr.p + 2;
@@ -827,7 +844,7 @@ static int run_search_chunk(vs_index* ix, const BatchPlan& bp, const float* d_ra
     ix->last_fast = FastSig{};
     PlainLaunch pl;
     bool plain_first = false;
-    VS_TRY(plan_plain_launch(ix, bp, !bp.stream_only && bp.rescore > 0 && ix->visible, &pl, &plain_first));
+    VS_TRY(plan_plain_launch(ix, bp, batch_vis(ix, bp).bytes != nullptr, &pl, &plain_first));
     const bool fast_done = caps.f_on || plain_first;  // a first attempt ran: the general kernel takes only what it handed over
     if (caps.f_on) VS_TRY(run_fast_attempts(ix, bp, caps, d_qlabels, d_qlabel_off));
     else if (plain_first) VS_TRY(run_plain_attempt(ix, bp, pl));
@@ -914,7 +931,7 @@ static int dump_phase_clocks(vs_index* ix, uint32_t nq, const std::vector<uint32
 }
 
 // the same counters from the per-scan arrays themselves (VS_PHASE: diagnostics)
-static int collect_stats(vs_index* ix, uint32_t nq, uint32_t M, uint32_t rescore, bool stream_only, vs_stats* st,
+static int collect_stats(vs_index* ix, uint32_t nq, uint32_t M, uint32_t rescore, bool stream_only, bool has_visible, vs_stats* st,
                          uint32_t obs_L = 0) {
     if (!st) return VS_OK;
     SearchWorkspace& w = ix->ws;
@@ -966,7 +983,7 @@ static int collect_stats(vs_index* ix, uint32_t nq, uint32_t M, uint32_t rescore
         if (!stream_only && rescore > 0) {
             // every row handed to the rescore window was fetched from the heap; so was every candidate the snapshot cannot
             // see (counted by the kernel, AM/scan.rs:258 + UT/table_slot.rs:45)
-            const uint32_t nr = std::min(cnt[q], M) + (ix->visible ? hs[(size_t)q * ST_N + ST_INVIS] : 0u);
+            const uint32_t nr = std::min(cnt[q], M) + (has_visible ? hs[(size_t)q * ST_N + ST_INVIS] : 0u);
             st->full_distance_comparisons += nr;
             st->node_heap_reads += nr;
         }
@@ -988,7 +1005,7 @@ static int finish_launch(vs_index* ix, const BatchPlan& bp, const int16_t* d_qla
         VS_TRY(enqueue_reduce(ix, bp));
         VS_HIP(hipStreamSynchronize(c->stream));  // (stage_out does not wait for the compute stream)
     }
-    if (env_u32("VS_PHASE", 0)) return collect_stats(ix, bp.nq, bp.M, bp.rescore, bp.stream_only, st, bp.L);
+    if (env_u32("VS_PHASE", 0)) return collect_stats(ix, bp.nq, bp.M, bp.rescore, bp.stream_only, batch_vis(ix, bp).bytes != nullptr, st, bp.L);
     return collect_stats_reduced(ix, bp.nq, bp.M, bp.rescore, bp.stream_only, st, bp.L);
 }
 
@@ -1051,10 +1068,30 @@ static int upload_label_keys(vs_index* ix, const int16_t* qlabels, const uint32_
     return VS_OK;
 }
 
+// The slots the scans of a batch name (HOST [nq]): each inside the table and, unless 0, with an overlay over the index's base.
+// *mode: BV_NONE when every slot is 0 (the launch is the one a batch without any mask gets), else BV_SLOTS.
+static int check_scan_slots(const vs_index* ix, const char* what, const uint32_t* slots, uint32_t nq, uint32_t* mode) {
+    bool any = false;
+    for (uint32_t q = 0; q < nq; ++q) {
+        const uint32_t sl = slots[q];
+        VS_REQUIRE(sl < VS_MAX_VIS_SLOTS, "%s: scan %u names slot %u outside [0,%d]", what, q, sl, VS_MAX_VIS_SLOTS - 1);
+        if (!sl) continue;
+        any = true;
+        if (!ix->vb || !ix->vb->cls || !ix->vb->overlay[sl]) {
+            vs_set_error("%s: scan %u names slot %u, which has no overlay (vs_index_vis_base_eval, then vs_index_vis_slot_eval)", what, q, sl);
+            return VS_ERR_STATE;
+        }
+    }
+    *mode = any ? BV_SLOTS : BV_NONE;
+    return VS_OK;
+}
+
 static int search_host(vs_index* ix, const float* queries, const int16_t* qlabels, const uint32_t* qlabel_off,
                        uint32_t nq, uint32_t L, uint32_t rescore, uint32_t k, bool stream_only, uint32_t* out_ids,
-                       uint64_t* out_tids, float* out_dist, uint32_t* out_ham, vs_stats* stats) {
+                       uint64_t* out_tids, float* out_dist, uint32_t* out_ham, vs_stats* stats, const uint32_t* scan_slots = nullptr) {
     VS_REQUIRE(ix && (nq == 0 || queries), "search: bad args");
+    uint32_t vis_mode = BV_INDEX_MASK;
+    if (scan_slots) VS_TRY(check_scan_slots(ix, "vs_search_batch_vis", scan_slots, nq, &vis_mode));
     VS_REQUIRE(L >= 1 && L <= 10000, "diskann.query_search_list_size %u outside [1,10000]", L);  // AM/guc.rs:11-26
     VS_REQUIRE(rescore <= 1000, "diskann.query_rescore %u outside [0,1000]", rescore);           // AM/guc.rs:28-43
     VS_REQUIRE(k >= 1, "k must be >= 1");
@@ -1073,6 +1110,12 @@ static int search_host(vs_index* ix, const float* queries, const int16_t* qlabel
     const int16_t* d_labels_all = nullptr;
     const uint32_t* d_off_all = nullptr;
     VS_TRY(upload_label_keys(ix, qlabels, qlabel_off, nq, &d_labels_all, &d_off_all));
+    const uint32_t* d_slots_all = nullptr;
+    if (vis_mode == BV_SLOTS) {
+        VS_TRY(devbuf_reserve(c, w.vis_slots, (size_t)nq * 4));
+        VS_TRY(vs_dev_upload(c, w.vis_slots.p, scan_slots, (size_t)nq * 4));
+        d_slots_all = (const uint32_t*)w.vis_slots.p;
+    }
     // Chunks of the batch run as a pipeline: while the device searches chunk i the host stages chunk i + 1 into the pinned ring and
     // hipMemcpyAsync moves it (copy stream), and the rows of chunk i - 1 go back to the caller — the PCIe time of a call is the
     // first chunk's way in and the last chunk's way out.  A batch that fits one launch is still cut into a few chunks when it is
@@ -1102,7 +1145,7 @@ static int search_host(vs_index* ix, const float* queries, const int16_t* qlabel
         VS_TRY(devbuf_reserve(c, *oids[ci & 1], (size_t)chunk * k * 4));
         VS_TRY(devbuf_reserve(c, *otids[ci & 1], (size_t)chunk * k * 8));
         VS_TRY(devbuf_reserve(c, *odist[ci & 1], (size_t)chunk * k * 4));
-        bp = BatchPlan{cq, L, rescore, k, M, stream_only};
+        bp = BatchPlan{cq, L, rescore, k, M, stream_only, vis_mode, d_slots_all ? d_slots_all + q0 : nullptr};
         // label CSR offsets are absolute into d_labels_all, so a chunk just offsets the off pointer
         return run_search_chunk(ix, bp, (const float*)rawq[ci & 1]->p, d_labels_all, d_off_all ? d_off_all + q0 : nullptr,
                                 (uint32_t*)oids[ci & 1]->p, (uint64_t*)otids[ci & 1]->p, (float*)odist[ci & 1]->p, caps);
@@ -1162,6 +1205,14 @@ extern "C" int vs_search_batch(vs_index* ix, const float* queries, const int16_t
                                uint64_t* out_tids, float* out_dist, vs_stats* stats) {
     return vs_guard("vs_search_batch", [&] { return vs_search_batch_impl(ix, queries, qlabels, qlabel_off, nq, L, rescore, k, out_ids, out_tids, out_dist, stats); });
 }
+extern "C" int vs_search_batch_vis(vs_index* ix, const float* queries, const int16_t* qlabels, const uint32_t* qlabel_off,
+                                   const uint32_t* scan_slots, uint32_t nq, uint32_t L, uint32_t rescore, uint32_t k, uint32_t* out_ids,
+                                   uint64_t* out_tids, float* out_dist, vs_stats* stats) {
+    return vs_guard("vs_search_batch_vis", [&]() -> int {
+        VS_REQUIRE(ix && (nq == 0 || (scan_slots && out_ids)), "vs_search_batch_vis: null argument");
+        return search_host(ix, queries, qlabels, qlabel_off, nq, L, rescore, k, false, out_ids, out_tids, out_dist, nullptr, stats, scan_slots);
+    });
+}
 
 
 static int vs_stream_batch_impl(vs_index* ix, const float* queries, const int16_t* qlabels, const uint32_t* qlabel_off,
@@ -1177,8 +1228,15 @@ extern "C" int vs_stream_batch(vs_index* ix, const float* queries, const int16_t
 
 int vs_search_batch_dev_impl(vs_index* ix, const float* d_queries, const int16_t* d_qlabels,
                                    const uint32_t* d_qlabel_off, uint32_t nq, uint32_t L, uint32_t rescore, uint32_t k,
-                                   uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist) {
+                                   uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, const uint32_t* d_scan_slots) {
     VS_REQUIRE(ix && (nq == 0 || (d_queries && d_out_ids)), "vs_search_batch_dev: bad args");
+    uint32_t vis_mode = BV_INDEX_MASK;
+    if (d_scan_slots && nq) {  // the slots come back once, so that a slot without an overlay is refused before anything is launched
+        std::vector<uint32_t> slots(nq);
+        VS_HIP(hipSetDevice(ix->ctx->device));
+        VS_TRY(vs_dev_download(ix->ctx, slots.data(), d_scan_slots, (size_t)nq * 4));
+        VS_TRY(check_scan_slots(ix, "vs_search_batch_dev_vis", slots.data(), nq, &vis_mode));
+    }
     VS_REQUIRE(L >= 1 && L <= 10000 && rescore <= 1000 && k >= 1, "vs_search_batch_dev: GUC out of range");
     if (ix->d.storage_type == VS_STORAGE_PLAIN) {
         VS_REQUIRE(!d_qlabel_off, "Plain storage does not support label filters");
@@ -1191,7 +1249,7 @@ int vs_search_batch_dev_impl(vs_index* ix, const float* d_queries, const int16_t
     const uint32_t M = stream_len(rescore, k);
     Caps caps = initial_caps(ix, L, M);
     VS_REQUIRE(chunk_queries(ix, caps, M, nq) == nq, "vs_search_batch_dev: batch of %u queries exceeds the workspace budget", nq);
-    BatchPlan bp{nq, L, rescore, k, M, false};
+    BatchPlan bp{nq, L, rescore, k, M, false, vis_mode, vis_mode == BV_SLOTS ? d_scan_slots : nullptr};
     VS_TRY(run_search_chunk(ix, bp, d_queries, d_qlabels, d_qlabel_off, d_out_ids, d_out_tids, d_out_dist, caps));
     w.pending = true;
     w.pend = PendingBatch{bp, caps, d_qlabels, d_qlabel_off, d_out_ids, d_out_tids, d_out_dist};
@@ -1202,6 +1260,17 @@ extern "C" int vs_search_batch_dev(vs_index* ix, const float* d_queries, const i
                                    const uint32_t* d_qlabel_off, uint32_t nq, uint32_t L, uint32_t rescore, uint32_t k,
                                    uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist) {
     return vs_guard("vs_search_batch_dev", [&] { return vs_search_batch_dev_impl(ix, d_queries, d_qlabels, d_qlabel_off, nq, L, rescore, k, d_out_ids, d_out_tids, d_out_dist); });
+}
+extern "C" int vs_search_batch_dev_vis(vs_index* ix, const float* d_queries, const int16_t* d_qlabels, const uint32_t* d_qlabel_off,
+                                       const uint32_t* d_scan_slots, uint32_t nq, uint32_t L, uint32_t rescore, uint32_t k,
+                                       uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist) {
+    return vs_guard("vs_search_batch_dev_vis", [&]() -> int {
+        VS_REQUIRE(ix && (nq == 0 || d_scan_slots), "vs_search_batch_dev_vis: null argument");
+        return vs_search_batch_dev_impl(ix, d_queries, d_qlabels, d_qlabel_off, nq, L, rescore, k, d_out_ids, d_out_tids, d_out_dist, d_scan_slots);
+    });
+}
+extern "C" int vs_search_batch_dev_vis_finish(vs_index* ix, vs_stats* stats) {
+    return vs_guard("vs_search_batch_dev_vis_finish", [&] { return vs_search_batch_dev_finish_impl(ix, stats); });
 }
 
 

@@ -43,11 +43,14 @@ struct Request {
     bool has_label_key;
     uint32_t L, rescore, k;
     uint32_t snapshot = 0;             // visibility mask the scan runs under (0 = every tuple visible)
+    bool by_slot = false;              // vs_broker_search_vis: the scan names a visibility slot instead (vs_index_vis_slot_eval)
+    uint32_t slot = 0;
     bool is_put = false;               // control request: install `put_mask` (n bytes or nullptr) as mask `snapshot`
     const uint8_t* put_mask = nullptr;
     int (*task)(void*) = nullptr;      // control request: run task(task_arg) on the dispatcher thread (scan cursors: vs_broker_call)
     int (*task_via)(void*, vs_index*) = nullptr;  // ... or task_via(task_arg, <the handle of the thread that runs it>) (vs_broker_call_lane)
     void* task_arg = nullptr;
+    bool exclusive = false;            // (task) run it while no lane is inside a task: it rewrites what lanes read (vs_broker_call_exclusive)
     uint32_t* out_ids;
     uint64_t* out_tids;
     float* out_dist;
@@ -59,9 +62,10 @@ struct Request {
     std::condition_variable cv;
 
     bool same_group(const Request& o) const {
-        // (scans of different snapshots never share a launch: a launch runs under ONE visibility mask)
+        // (scans of different snapshot MASKS never share a launch: a launch runs under ONE visibility mask; scans that name slots
+        // do, whatever their slots: each scan of a launch reads the overlay of its own)
         return !is_put && !o.is_put && !task && !o.task && !task_via && !o.task_via && L == o.L && rescore == o.rescore && k == o.k && has_label_key == o.has_label_key &&
-               snapshot == o.snapshot;
+               by_slot == o.by_slot && (by_slot || snapshot == o.snapshot);
     }
 };
 
@@ -160,6 +164,14 @@ void vs_broker::run_group_launch(std::vector<Request*>& grp, std::vector<float>&
     // scans with a label key and NULL-query scans (no key) cannot share a launch: the caller keeps them in separate groups
     const bool keys = head.has_label_key;
     vs_stats stats{};
+    if (head.by_slot) {  // one launch for the whole group; a slot without an overlay fails the launch for every scan of it
+        std::vector<uint32_t> slots(nq);
+        for (uint32_t i = 0; i < nq; ++i) slots[i] = grp[i]->slot;
+        rc = vs_search_batch_vis(ix, q.data(), keys ? lab.data() : nullptr, keys ? off.data() : nullptr, slots.data(), nq, head.L, head.rescore, k,
+                                 ids.data(), tids.data(), dist.data(), &stats);
+        if (rc != VS_OK) err = vs_last_error();
+        return;
+    }
     // the group's snapshot mask for the duration of the launch (the index-level mask of direct callers is put back)
     const uint8_t* prev = nullptr;
     rc = vs_index_snapshot_use(ix, head.snapshot, &prev);
@@ -196,17 +208,24 @@ void vs_broker::run() {
             lk.unlock();
             int prc;
             std::string perr;
+            struct Waiting {
+                std::atomic<int>& n;
+                explicit Waiting(std::atomic<int>& n_) : n(n_) { n.fetch_add(1, std::memory_order_acq_rel); }
+                ~Waiting() { n.fetch_sub(1, std::memory_order_acq_rel); }
+            };
             try {
                 if (head->task_via) {
                     prc = head->task_via(head->task_arg, ix);
+                } else if (head->task && head->exclusive) {
+                    // a mask, the base or an overlay is rewritten: as a put, when no lane is inside a task that could be reading it (or
+                    // taking the base over: vs_index_vis_share)
+                    Waiting waiting(put_waiting);
+                    std::unique_lock<std::shared_mutex> xl(snap_mu);
+                    prc = head->task(head->task_arg);
                 } else if (head->task) {
                     prc = head->task(head->task_arg);
                 } else {
-                    struct Waiting {
-                        std::atomic<int>& n;
-                        explicit Waiting(std::atomic<int>& n_) : n(n_) { n.fetch_add(1, std::memory_order_acq_rel); }
-                        ~Waiting() { n.fetch_sub(1, std::memory_order_acq_rel); }
-                    } waiting(put_waiting);
+                    Waiting waiting(put_waiting);
                     std::unique_lock<std::shared_mutex> xl(snap_mu);  // (no lane is inside a task)
                     prc = vs_index_snapshot_put(ix, head->snapshot, head->put_mask);
                 }
@@ -255,6 +274,7 @@ void vs_broker::run_lane(Lane& ln) {
             while (put_waiting.load(std::memory_order_acquire) > 0) std::this_thread::sleep_for(std::chrono::microseconds(50));
             std::shared_lock<std::shared_mutex> sl(snap_mu);
             rc = vs_index_snapshot_share(ln.view, ix);
+            if (rc == VS_OK) rc = vs_index_vis_share(ln.view, ix);  // (the base and the overlays with them)
             if (rc == VS_OK) rc = r->task_via(r->task_arg, ln.view);
             if (rc != VS_OK) err = vs_last_error();
         } catch (const std::bad_alloc&) {
@@ -321,14 +341,16 @@ int vs_broker_create(vs_index* idx, const vs_broker_config* cfg, vs_broker** out
     return VS_OK;
 }
 
-int vs_broker_search_snapshot(vs_broker* b, const float* query, const int16_t* labels, uint32_t n_labels, int has_label_key,
-                              uint32_t search_list_size, uint32_t rescore, uint32_t k, uint32_t snapshot, uint32_t* out_ids,
-                              uint64_t* out_tids, float* out_dist) {
-    if (!b || !out_ids || k == 0 || snapshot >= VS_MAX_SNAPSHOTS) {
+static int broker_search(vs_broker* b, const float* query, const int16_t* labels, uint32_t n_labels, int has_label_key, uint32_t search_list_size,
+                         uint32_t rescore, uint32_t k, uint32_t snapshot, bool by_slot, uint32_t slot, uint32_t* out_ids, uint64_t* out_tids,
+                         float* out_dist) {
+    if (!b || !out_ids || k == 0 || snapshot >= VS_MAX_SNAPSHOTS || slot >= VS_MAX_VIS_SLOTS) {
         vs_set_error("vs_broker_search: bad arguments");
         return VS_ERR_INVALID;
     }
     Request r;
+    r.by_slot = by_slot;
+    r.slot = slot;
     r.query = query;
     // a NULL query ignores its keys (amrescan: LabeledVector::from_scan_key_data with a NULL vector)
     r.has_label_key = has_label_key != 0 && query != nullptr;
@@ -352,6 +374,18 @@ int vs_broker_search_snapshot(vs_broker* b, const float* query, const int16_t* l
     lk.unlock();
     if (r.rc != VS_OK) vs_set_error("%s", r.err.c_str());
     return r.rc;
+}
+
+int vs_broker_search_snapshot(vs_broker* b, const float* query, const int16_t* labels, uint32_t n_labels, int has_label_key,
+                              uint32_t search_list_size, uint32_t rescore, uint32_t k, uint32_t snapshot, uint32_t* out_ids,
+                              uint64_t* out_tids, float* out_dist) {
+    return broker_search(b, query, labels, n_labels, has_label_key, search_list_size, rescore, k, snapshot, false, 0, out_ids, out_tids, out_dist);
+}
+
+int vs_broker_search_vis(vs_broker* b, const float* query, const int16_t* labels, uint32_t n_labels, int has_label_key,
+                         uint32_t search_list_size, uint32_t rescore, uint32_t k, uint32_t slot, uint32_t* out_ids, uint64_t* out_tids,
+                         float* out_dist) {
+    return broker_search(b, query, labels, n_labels, has_label_key, search_list_size, rescore, k, 0, true, slot, out_ids, out_tids, out_dist);
 }
 
 int vs_broker_search(vs_broker* b, const float* query, const int16_t* labels, uint32_t n_labels, int has_label_key,
@@ -393,13 +427,25 @@ int vs_broker_snapshot_put(vs_broker* b, uint32_t snapshot, const uint8_t* visib
 // Runs fn(arg) on the dispatcher thread, between two launches, and returns its result: how work that belongs to ONE scan (the
 // continuation of its cursor on the device, the release of its device buffers) reaches the only thread allowed to touch the index.
 // A non-zero result carries the dispatcher thread's vs_last_error() text over to the caller's.
-int vs_broker_call(vs_broker* b, int (*fn)(void*), void* arg) {
+static int broker_call(vs_broker* b, int (*fn)(void*), void* arg, bool exclusive);
+int vs_broker_call(vs_broker* b, int (*fn)(void*), void* arg) { return broker_call(b, fn, arg, false); }
+int vs_broker_call_exclusive(vs_broker* b, int (*fn)(void*), void* arg) { return broker_call(b, fn, arg, true); }
+}  // extern "C"
+
+static int broker_call(vs_broker* b, int (*fn)(void*), void* arg, bool exclusive) {
     if (!b || !fn) {
         vs_set_error("vs_broker_call: null argument");
         return VS_ERR_INVALID;
     }
-    if (std::this_thread::get_id() == b->dispatcher.get_id()) return fn(arg);  // (already there)
+    if (std::this_thread::get_id() == b->dispatcher.get_id()) {  // (already there)
+        if (exclusive) {
+            vs_set_error("vs_broker_call_exclusive: called from a dispatcher task (the task it is inside would have to end first)");
+            return VS_ERR_STATE;
+        }
+        return fn(arg);
+    }
     Request r;
+    r.exclusive = exclusive;
     r.query = nullptr;
     r.has_label_key = false;
     r.L = r.rescore = r.k = 0;
@@ -424,6 +470,7 @@ int vs_broker_call(vs_broker* b, int (*fn)(void*), void* arg) {
     return r.rc;
 }
 
+extern "C" {
 // fn(arg, handle) on the lane `lane_key` names (its thread, its view of the index), or — a broker without lanes — on the dispatcher
 // thread with the broker's own index; blocks until it is done.  Work of ONE scan: the scan stays on the lane it was assigned.
 int vs_broker_call_lane(vs_broker* b, uint32_t lane_key, int (*fn)(void*, vs_index*), void* arg) {

@@ -223,8 +223,8 @@ static int cursor_extend(vs_scan* s, uint32_t want_rows) {
         sl.out_cnt = (uint32_t*)k.cnt.p;
         sl.stats = (uint32_t*)k.stats.p;
         sl.status = (uint32_t*)k.status.p;
-        sl.visible = S > 0 ? ix->visible : nullptr;  // the heap is only fetched for the rescore window
-        k.masked = sl.visible != nullptr;
+        sl.vis.bytes = S > 0 ? ix->visible : nullptr;  // the heap is only fetched for the rescore window
+        k.masked = sl.vis.bytes != nullptr;
         sl.resume = (uint32_t*)k.state.p;
         sl.resume_stride = 0;
         sl.row_stats = (uint32_t*)k.row_stats.p;

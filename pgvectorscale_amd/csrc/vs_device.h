@@ -66,6 +66,43 @@ __device__ __forceinline__ uint32_t hash_u32(uint32_t x) {
     return x;
 }
 
+// ---- heap visibility of one scan of a launch (VisView, vs_internal.h) ----------------------------------------------
+// bytes == nullptr: nothing is hidden from this scan.  ov == nullptr: legacy mode, a node is hidden iff its byte is 0.  Otherwise the
+// byte is the node's class, and only a class-2 node is looked up in the ascending depends list for the scan's overlay byte.
+struct ScanVis {
+    const uint8_t* bytes;
+    const uint32_t* dep;
+    const uint8_t* ov;
+    uint32_t r;
+};
+__device__ __forceinline__ ScanVis vis_of_scan(const VisView& v, uint32_t q) {
+    ScanVis s{v.bytes, nullptr, nullptr, 0u};
+    if (v.slots && v.bytes) {
+        const uint32_t slot = v.slots[q];  // (wave-uniform: one scan per wave)
+        if (slot == 0 || slot >= VS_MAX_VIS_SLOTS) {
+            s.bytes = nullptr;  // slot 0: every tuple visible (the host has refused anything beyond the table)
+        } else {
+            s.dep = v.dep;
+            s.ov = v.overlay[slot];
+            s.r = v.r;
+        }
+    }
+    return s;
+}
+// is `node` hidden from the scan, given its byte of s.bytes (the fast kernel requests that byte ahead of its use)
+__device__ __forceinline__ bool vis_hidden(const ScanVis& s, uint32_t node, uint32_t byte) {
+    if (!s.ov) return byte == 0;
+    if (byte != VIS_CLASS_DEPENDS) return byte == VIS_CLASS_NONE;
+    uint32_t lo = 0, hi = s.r;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (s.dep[mid] < node) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo >= s.r || s.dep[lo] != node || s.ov[lo] == 0;  // (a class-2 node is always on the list: the list is built from the classes)
+}
+__device__ __forceinline__ bool vis_hidden(const ScanVis& s, uint32_t node) { return s.bytes && vis_hidden(s, node, s.bytes[node]); }
+
 // Hamming distance of one code row against the query code held in LDS, computed by a group of 4 lanes
 // (lane l4 covers words 2*l4 + 8t, 2*l4+1 + 8t: 16 B per lane per step, 64 B contiguous per group per step).
 // Rows are code_stride (even) words, zero padded, so the padded tail contributes popcount(0^0)=0.

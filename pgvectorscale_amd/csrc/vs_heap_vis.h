@@ -43,6 +43,11 @@ struct HeapVisArgs {
     uint8_t* visible;     // [n]
     uint32_t* undecided;  // [n] in the order the waves appended, or nullptr: the list is not wanted
     uint32_t* ctr;
+    // k_heap_vis_base only: the horizon the consulted xids are held against, and the bitmap of changed blocks (one bit per block below
+    // map_blocks; nullptr: every node is walked)
+    uint32_t horizon;
+    const uint32_t* block_map;
+    uint32_t map_blocks;
 };
 
 // TransactionIdPrecedes / TransactionIdFollowsOrEquals (access/transam.c): modulo-2^32 for normal xids, plain for the special ones
@@ -63,7 +68,21 @@ __device__ __forceinline__ bool vis_member(const uint32_t* __restrict__ v, uint3
 }
 // TransactionIdDidCommit over the window of pg_xact (TransactionLogFetch: the bootstrap and frozen xids committed, the invalid one
 // did not); sub-committed needs pg_subtrans -> VV_INVISIBLE (no) / VV_VISIBLE (yes) / VV_UNDECIDED + reason
-__device__ __forceinline__ uint32_t vis_did_commit(const HeapVisArgs& a, uint32_t x) {
+// What the base evaluation (k_heap_vis_base) remembers of a walk: whether any normal xid handed to own(), in_snapshot() or
+// did_commit() follows or equals the horizon.  The snapshot evaluation (k_heap_vis) tracks nothing: TRACK = false compiles to the rule alone.
+template <bool TRACK>
+__device__ __forceinline__ void vis_consult(const HeapVisArgs& a, uint32_t x, bool& recent) {
+    if (TRACK && x >= 3u && vis_follows_eq(x, a.horizon)) recent = true;
+}
+// TransactionIdIsCurrentTransactionId over the backend's own xids
+template <bool TRACK>
+__device__ __forceinline__ bool vis_own(const HeapVisArgs& a, uint32_t x, bool& recent) {
+    vis_consult<TRACK>(a, x, recent);
+    return vis_member(a.own, a.n_own, x);
+}
+template <bool TRACK>
+__device__ __forceinline__ uint32_t vis_did_commit(const HeapVisArgs& a, uint32_t x, bool& recent) {
+    vis_consult<TRACK>(a, x, recent);
     if (x == 1u || x == 2u) return VV_VISIBLE;
     if (x == 0u) return VV_INVISIBLE;
     const uint32_t i = x - a.clog_first;
@@ -73,7 +92,9 @@ __device__ __forceinline__ uint32_t vis_did_commit(const HeapVisArgs& a, uint32_
     return st == 1u ? VV_VISIBLE : VV_INVISIBLE;
 }
 // XidInMVCCSnapshot (utils/time/snapmgr.c) -> no / yes / undecided, encoded as above
-__device__ __forceinline__ uint32_t vis_in_snapshot(const HeapVisArgs& a, uint32_t x) {
+template <bool TRACK>
+__device__ __forceinline__ uint32_t vis_in_snapshot(const HeapVisArgs& a, uint32_t x, bool& recent) {
+    vis_consult<TRACK>(a, x, recent);
     if (vis_precedes(x, a.xmin)) return VV_INVISIBLE;
     if (vis_follows_eq(x, a.xmax)) return VV_VISIBLE;
     if (!a.recovery) {
@@ -89,25 +110,26 @@ __device__ __forceinline__ uint32_t vis_in_snapshot(const HeapVisArgs& a, uint32
 }
 
 // HeapTupleSatisfiesMVCC (access/heap/heapam_visibility.c), statement by statement, without the hint-bit writes
-__device__ __forceinline__ uint32_t vis_satisfies_mvcc(const HeapVisArgs& a, uint32_t xmin, uint32_t xmax, uint32_t cid, uint32_t m) {
+template <bool TRACK>
+__device__ __forceinline__ uint32_t vis_satisfies_mvcc(const HeapVisArgs& a, uint32_t xmin, uint32_t xmax, uint32_t cid, uint32_t m, bool& recent) {
     if (!(m & HV_XMIN_COMMITTED)) {
         if (m & HV_XMIN_INVALID) return VV_INVISIBLE;
         if (m & HV_MOVED) return VV_UNDECIDED + VS_VIS_R_MOVED;  // HEAP_MOVED_OFF / HEAP_MOVED_IN: pre-9.0 VACUUM FULL
-        if (vis_member(a.own, a.n_own, xmin)) {                  // TransactionIdIsCurrentTransactionId(xmin)
+        if (vis_own<TRACK>(a, xmin, recent)) {                  // TransactionIdIsCurrentTransactionId(xmin)
             if (m & HV_COMBOCID) return VV_UNDECIDED + VS_VIS_R_COMBOCID;
             if (cid >= a.curcid) return VV_INVISIBLE;  // inserted after the scan started
             if (m & HV_XMAX_INVALID) return VV_VISIBLE;
             if (vis_locked_only(m)) return VV_VISIBLE;
             if (m & HV_XMAX_IS_MULTI) return VV_UNDECIDED + VS_VIS_R_MULTIXACT;  // HeapTupleGetUpdateXid
-            if (!vis_member(a.own, a.n_own, xmax)) return VV_VISIBLE;            // the deleting subtransaction must have aborted
+            if (!vis_own<TRACK>(a, xmax, recent)) return VV_VISIBLE;            // the deleting subtransaction must have aborted
             return cid >= a.curcid ? VV_VISIBLE : VV_INVISIBLE;                  // deleted after / before the scan started
         }
-        const uint32_t s = vis_in_snapshot(a, xmin);
+        const uint32_t s = vis_in_snapshot<TRACK>(a, xmin, recent);
         if (s != VV_INVISIBLE) return s == VV_VISIBLE ? (uint32_t)VV_INVISIBLE : s;
-        const uint32_t c = vis_did_commit(a, xmin);
+        const uint32_t c = vis_did_commit<TRACK>(a, xmin, recent);
         if (c != VV_VISIBLE) return c;  // aborted or crashed: invisible; or undecided
     } else if ((m & HV_XMIN_FROZEN) != HV_XMIN_FROZEN) {  // xmin is committed, but maybe not according to our snapshot
-        const uint32_t s = vis_in_snapshot(a, xmin);
+        const uint32_t s = vis_in_snapshot<TRACK>(a, xmin, recent);
         if (s != VV_INVISIBLE) return s == VV_VISIBLE ? (uint32_t)VV_INVISIBLE : s;
     }
     // by here, the inserting transaction has committed
@@ -115,16 +137,16 @@ __device__ __forceinline__ uint32_t vis_satisfies_mvcc(const HeapVisArgs& a, uin
     if (vis_locked_only(m)) return VV_VISIBLE;
     if (m & HV_XMAX_IS_MULTI) return VV_UNDECIDED + VS_VIS_R_MULTIXACT;
     if (!(m & HV_XMAX_COMMITTED)) {
-        if (vis_member(a.own, a.n_own, xmax)) {
+        if (vis_own<TRACK>(a, xmax, recent)) {
             if (m & HV_COMBOCID) return VV_UNDECIDED + VS_VIS_R_COMBOCID;
             return cid >= a.curcid ? VV_VISIBLE : VV_INVISIBLE;
         }
-        const uint32_t s = vis_in_snapshot(a, xmax);
+        const uint32_t s = vis_in_snapshot<TRACK>(a, xmax, recent);
         if (s != VV_INVISIBLE) return s;  // the deleter is still running for us: visible; or undecided
-        const uint32_t c = vis_did_commit(a, xmax);
+        const uint32_t c = vis_did_commit<TRACK>(a, xmax, recent);
         if (c != VV_VISIBLE) return c == VV_INVISIBLE ? (uint32_t)VV_VISIBLE : c;  // it aborted or crashed: visible
     } else {
-        const uint32_t s = vis_in_snapshot(a, xmax);
+        const uint32_t s = vis_in_snapshot<TRACK>(a, xmax, recent);
         if (s != VV_INVISIBLE) return s;
     }
     return VV_INVISIBLE;  // the deleting transaction committed
@@ -132,7 +154,8 @@ __device__ __forceinline__ uint32_t vis_satisfies_mvcc(const HeapVisArgs& a, uin
 
 // heap_hot_search_buffer (access/heap/heapam.c; what table_index_fetch_tuple runs) for one tid -> VK_*; reason: VS_VIS_R_* of
 // VK_UNDECIDED; hops: chain members whose header was read beyond the first
-__device__ __forceinline__ uint32_t vis_hot_search(const HeapVisArgs& a, uint64_t tid, uint32_t& reason, uint32_t& hops) {
+template <bool TRACK>
+__device__ __forceinline__ uint32_t vis_hot_search(const HeapVisArgs& a, uint64_t tid, uint32_t& reason, uint32_t& hops, bool& recent) {
     reason = 0;
     hops = 0;
     uint32_t off = (uint32_t)(tid & 0xFFFFu);
@@ -178,7 +201,7 @@ __device__ __forceinline__ uint32_t vis_hot_search(const HeapVisArgs& a, uint64_
         if (at_start && (m2 & HV2_ONLY_TUPLE)) return VK_INVISIBLE;  // a heap-only tuple cannot start a chain
         // the xmin must match the previous member's xmax, else the chain is broken (HeapTupleHeaderGetXmin: a frozen xmin reads as 2)
         if (prev_xmax != 0 && prev_xmax != ((m & HV_XMIN_FROZEN) == HV_XMIN_FROZEN ? 2u : xmin)) return VK_INVISIBLE;
-        const uint32_t r = vis_satisfies_mvcc(a, xmin, xmax, cid, m);
+        const uint32_t r = vis_satisfies_mvcc<TRACK>(a, xmin, xmax, cid, m, recent);
         if (r == VV_VISIBLE) return VK_VISIBLE;
         if (r >= VV_UNDECIDED) {
             reason = r - VV_UNDECIDED;
@@ -211,7 +234,8 @@ __global__ __launch_bounds__(WAVE) void k_heap_vis(HeapVisArgs a) {
         const uint32_t i = base + lane;
         uint32_t kind = VK_ERROR, reason = 0, hops = 0;
         if (i < a.n) {
-            kind = vis_hot_search(a, a.tids[i], reason, hops);
+            bool unused = false;
+            kind = vis_hot_search<false>(a, a.tids[i], reason, hops, unused);
             a.visible[i] = (kind == VK_VISIBLE || kind == VK_UNDECIDED) ? 1 : 0;
         }
         hops_lane += hops;
@@ -572,4 +596,504 @@ extern "C" int vs_index_snapshot_patch(vs_index* ix, uint32_t snapshot, const ui
         if (d_vals) (void)hipFree(d_vals);
         return r;
     });
+}
+
+// ---- the base and its overlays (vs_index_vis_base_eval, vs_index_vis_slot_*; include/vsgpu.h has the rule) -----------------------------
+// Almost every tuple is visible, or invisible, to every snapshot that can exist: only rows touched at or after the oldest-running horizon
+// depend on who asks.  k_heap_vis_base walks every node once per heap state under the synthetic snapshot xmin = xmax = horizon and
+// gives it a class byte; the class-2 nodes form the ascending depends list, and a snapshot's overlay is the rule run under that
+// snapshot over the list's r nodes only (k_heap_vis over the gathered tids).  The search kernels read the class byte where they read
+// a mask byte and look a class-2 node up in the list (vis_hidden, vs_device.h).
+enum { BSUM_WALKED = 0, BSUM_DELETED, BSUM_NOT_FOUND, BSUM_DEAD_LP, BSUM_RECENT, BSUM_UNDECIDED, BSUM_HOPS, BSUM_REASON, BSUM_N = BSUM_REASON + VS_VIS_R_N,
+       BC_N = VC_SUMS + 2 * BSUM_N };
+enum { LC_CLASS = 0 /* three counts */, LC_NLIST = 3, LC_N = 4 };  // counters of k_vis_list (u32)
+
+// k_heap_vis with the class for a verdict: a lane per node, the counters reduced per wave.  With a block bitmap only the nodes whose
+// tid lies on a listed block are walked; every other class byte is left as it is.
+__global__ __launch_bounds__(WAVE) void k_heap_vis_base(HeapVisArgs a) {
+    const uint32_t lane = threadIdx.x;
+    uint32_t sum[BSUM_N] = {0};
+    uint32_t hops_lane = 0;
+    for (uint32_t base = blockIdx.x * WAVE; base < a.n; base += gridDim.x * WAVE) {
+        const uint32_t i = base + lane;
+        uint32_t kind = VK_ERROR, reason = 0, hops = 0;
+        bool walk = false, recent = false;
+        if (i < a.n) {
+            const uint64_t tid = a.tids[i];
+            walk = true;
+            if (a.block_map) {
+                const uint64_t blk = tid >> 16;
+                walk = blk < a.map_blocks && ((a.block_map[blk >> 5] >> (blk & 31u)) & 1u) != 0;
+            }
+            if (walk) {
+                kind = vis_hot_search<true>(a, tid, reason, hops, recent);
+                a.visible[i] = (kind == VK_UNDECIDED || recent) ? VIS_CLASS_DEPENDS : kind == VK_VISIBLE ? VIS_CLASS_ALL : VIS_CLASS_NONE;
+            }
+        }
+        hops_lane += hops;
+        const uint64_t m_und = __ballot(walk && kind == VK_UNDECIDED);
+        sum[BSUM_WALKED] += (uint32_t)__popcll(__ballot(walk));
+        sum[BSUM_DELETED] += (uint32_t)__popcll(__ballot(walk && kind == VK_DELETED));
+        sum[BSUM_NOT_FOUND] += (uint32_t)__popcll(__ballot(walk && kind == VK_NOT_FOUND));
+        sum[BSUM_DEAD_LP] += (uint32_t)__popcll(__ballot(walk && kind == VK_DEAD_LP));
+        sum[BSUM_RECENT] += (uint32_t)__popcll(__ballot(walk && recent && kind != VK_UNDECIDED && kind != VK_ERROR));
+        if (m_und) {  // (wave-uniform)
+            sum[BSUM_UNDECIDED] += (uint32_t)__popcll(m_und);
+            for (uint32_t r = 0; r < VS_VIS_R_N; ++r) sum[BSUM_REASON + r] += (uint32_t)__popcll(__ballot(walk && kind == VK_UNDECIDED && reason == r));
+        }
+    }
+    for (uint32_t o = WAVE / 2; o; o >>= 1) hops_lane += __shfl_xor(hops_lane, o);
+    sum[BSUM_HOPS] = hops_lane;
+    if (lane == 0) {
+        unsigned long long* sums = reinterpret_cast<unsigned long long*>(a.ctr + VC_SUMS);
+        for (uint32_t k = 0; k < BSUM_N; ++k)
+            if (sum[k]) atomicAdd(&sums[k], (unsigned long long)sum[k]);
+    }
+}
+
+// the classes counted and the class-2 nodes appended behind one counter (sorted afterwards: nothing depends on scheduling)
+__global__ __launch_bounds__(WAVE) void k_vis_list(const uint8_t* __restrict__ cls, uint32_t n, uint32_t* __restrict__ list, uint32_t* __restrict__ ctr) {
+    const uint32_t lane = threadIdx.x;
+    uint32_t n0 = 0, n1 = 0;
+    for (uint32_t base = blockIdx.x * WAVE; base < n; base += gridDim.x * WAVE) {
+        const uint32_t i = base + lane;
+        const uint32_t c = i < n ? (uint32_t)cls[i] : 0xFFu;
+        n0 += (uint32_t)__popcll(__ballot(c == VIS_CLASS_NONE));
+        n1 += (uint32_t)__popcll(__ballot(c == VIS_CLASS_ALL));
+        const uint64_t m2 = __ballot(c == VIS_CLASS_DEPENDS);
+        if (m2) {  // (wave-uniform)
+            uint32_t at = 0;
+            if (lane == 0) at = atomicAdd(&ctr[LC_NLIST], (uint32_t)__popcll(m2));
+            at = __shfl(at, 0);
+            // (at most one entry per node: at + popc <= n, the list's size)
+            if (c == VIS_CLASS_DEPENDS) list[at + (uint32_t)__popcll(m2 & ((1ull << lane) - 1ull))] = i;
+        }
+    }
+    if (lane == 0) {
+        if (n0) atomicAdd(&ctr[LC_CLASS + 0], n0);
+        if (n1) atomicAdd(&ctr[LC_CLASS + 1], n1);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_vis_gather_tids(const uint64_t* __restrict__ tids, const uint32_t* __restrict__ dep, uint32_t r,
+                                                         uint64_t* __restrict__ out) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < r; i += gridDim.x * blockDim.x) out[i] = tids[dep[i]];
+}
+
+// the byte mask of a legacy snapshot id from the base and one overlay: what vis_hidden tells a scan of that slot, node by node
+__global__ __launch_bounds__(256) void k_vis_materialize(const uint8_t* __restrict__ cls, const uint32_t* __restrict__ dep, uint32_t r,
+                                                         const uint8_t* __restrict__ ov, uint8_t* __restrict__ mask, uint32_t n) {
+    const ScanVis s{cls, dep, ov, r};
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) mask[i] = vis_hidden(s, i, cls[i]) ? 0 : 1;
+}
+
+// TransactionIdPrecedes on the host (the admission of a snapshot against the stored horizon)
+static inline bool vis_precedes_host(uint32_t a, uint32_t b) { return (a >= 3 && b >= 3) ? (int32_t)(a - b) < 0 : a < b; }
+
+// the scratch buffers of vis_base_run in VisBase::wk: the block bitmap + pg_xact window, both kernels' counters, the unsorted list,
+// and what the radix sort wants (the interface of the sort used here takes values with its keys)
+enum { VW_AUX = 0, VW_CTR, VW_LIST, VW_VALS, VW_TMP, VW_N };
+static int vis_wk(VisBase* b, int which, size_t bytes, void** out) {
+    if (b->wk_bytes[which] < bytes) {
+        if (b->wk[which]) (void)hipFree(b->wk[which]);
+        b->wk[which] = nullptr;
+        b->wk_bytes[which] = 0;
+        const size_t want = bytes + bytes / 2;  // (by half, as the index's arrays grow)
+        VS_HIP(hipMalloc(&b->wk[which], want));
+        b->wk_bytes[which] = want;
+    }
+    *out = b->wk[which];
+    return VS_OK;
+}
+static void vis_wk_free(VisBase* b) {
+    for (int k = 0; k < VW_N; ++k) {
+        if (b->wk[k]) (void)hipFree(b->wk[k]);
+        b->wk[k] = nullptr;
+        b->wk_bytes[k] = 0;
+    }
+}
+
+static void vis_overlays_drop(VisBase* b) {
+    for (uint32_t s = 0; s < VS_MAX_VIS_SLOTS; ++s)
+        if (b->overlay[s]) {
+            (void)hipFree(b->overlay[s]);
+            b->overlay[s] = nullptr;
+        }
+    if (b->tab) (void)hipMemset(b->tab, 0, sizeof(uint8_t*) * VS_MAX_VIS_SLOTS);
+}
+void vs_vis_base_drop(vs_index* ix) {
+    VisBase* b = ix->vb;
+    if (!b || ix->is_view) return;
+    (void)hipSetDevice(ix->ctx->device);
+    (void)hipStreamSynchronize(ix->ctx->stream);  // no launch may still read them
+    vis_overlays_drop(b);
+    if (b->cls) (void)hipFree(b->cls);
+    if (b->dep) (void)hipFree(b->dep);
+    vis_wk_free(b);
+    b->cls = nullptr;
+    b->dep = nullptr;
+    b->dep_cap = 0;
+    b->dep_host.clear();
+    b->cls_rows = 0;
+    b->n = b->r = b->horizon = 0;
+}
+void vs_vis_base_free(vs_index* ix) {
+    if (!ix->vb || ix->is_view) return;
+    vs_vis_base_drop(ix);
+    if (ix->vb->tab) (void)hipFree(ix->vb->tab);
+    delete ix->vb;
+    ix->vb = nullptr;
+}
+
+// the refusals every call that writes the base or an overlay shares: a view handle, a batch in flight
+static int vis_write_check(const char* what, vs_index* ix) {
+    VS_REQUIRE(ix, "%s: index is NULL", what);
+    if (ix->is_view) {
+        vs_set_error("%s: this handle is a view; the base and its overlays belong to the index it was made from", what);
+        return VS_ERR_STATE;
+    }
+    if (ix->ws.pending) {
+        vs_set_error("%s: a batch of this handle is in flight (vs_search_batch_dev_finish first)", what);
+        return VS_ERR_STATE;
+    }
+    return VS_OK;
+}
+static int vis_slot_check(const char* what, vs_index* ix, uint32_t slot) {
+    VS_TRY(vis_write_check(what, ix));
+    VS_REQUIRE(slot >= 1 && slot < VS_MAX_VIS_SLOTS, "%s: slot %u outside [1,%d]", what, slot, VS_MAX_VIS_SLOTS - 1);
+    return VS_OK;
+}
+static int vis_need_base(const char* what, const vs_index* ix) {
+    if (!ix->vb || !ix->vb->cls) {
+        vs_set_error("%s: the index has no visibility base (vs_index_vis_base_eval)", what);
+        return VS_ERR_STATE;
+    }
+    return VS_OK;
+}
+// one entry of the device table of overlay pointers
+static int vis_tab_set(vs_index* ix, uint32_t slot, uint8_t* p) {
+    VS_HIP(hipMemcpyAsync(ix->vb->tab + slot, &p, sizeof(p), hipMemcpyHostToDevice, ix->ctx->stream));
+    VS_HIP(hipStreamSynchronize(ix->ctx->stream));
+    return VS_OK;
+}
+
+static int vis_base_run(vs_index* ix, vs_heap_res* h, uint32_t horizon, const vs_xact_status* x, const uint32_t* changed, uint32_t n_changed,
+                        vs_vis_base_stats* out) {
+    vs_ctx* c = ix->ctx;
+    hipStream_t st = c->stream;
+    VS_HIP(hipSetDevice(c->device));
+    VS_HIP(hipStreamSynchronize(st));  // (replacing classes a launch may still be reading)
+    if (!ix->vb) ix->vb = new VisBase();
+    VisBase* b = ix->vb;
+    if (!b->tab) {
+        VS_HIP(hipMalloc(&b->tab, sizeof(uint8_t*) * VS_MAX_VIS_SLOTS));
+        VS_HIP(hipMemset(b->tab, 0, sizeof(uint8_t*) * VS_MAX_VIS_SLOTS));
+    }
+    vis_overlays_drop(b);  // overlays index positions of the list that is about to be rebuilt
+    const uint32_t n = ix->d.n;
+    const bool refresh = changed != nullptr;
+    const size_t rows = std::max<size_t>(std::max(n, ix->capacity), 1);
+    if (!refresh || b->cls_rows < rows) {  // (a refresh after the index grew past the array: the kept classes move, the new rows read 0)
+        uint8_t* fresh = nullptr;
+        VS_HIP(hipMalloc(&fresh, rows));
+        VS_HIP(hipMemsetAsync(fresh, 0, rows, st));
+        if (refresh && b->n) VS_HIP(hipMemcpyAsync(fresh, b->cls, std::min<size_t>(b->n, rows), hipMemcpyDeviceToDevice, st));
+        VS_HIP(hipStreamSynchronize(st));
+        if (b->cls) (void)hipFree(b->cls);
+        b->cls = fresh;
+        b->cls_rows = rows;
+    }
+    b->dep_host.clear();
+    b->r = 0;
+    const size_t clog_bytes = ((size_t)x->n_xids + 3) / 4;
+    // The bitmap covers the resident fork and no more: a tid on a block at or beyond n_blocks is "not found" whether it is walked or
+    // not (class 0, as it was), so a listed block out there changes nothing and costs no bit.  (ascending: the last is the highest)
+    const uint32_t map_blocks = n_changed ? (uint32_t)std::min<uint64_t>((uint64_t)changed[n_changed - 1] + 1, h->n_blocks) : 0u;
+    const size_t map_words = ((size_t)map_blocks + 31) / 32;
+    std::vector<uint32_t> aux(map_words + (clog_bytes + 3) / 4 + 1, 0u);
+    uint32_t n_listed = 0;  // changed blocks inside the fork
+    for (uint32_t i = 0; i < n_changed && changed[i] < map_blocks; ++i, ++n_listed) aux[changed[i] >> 5] |= 1u << (changed[i] & 31u);
+    if (clog_bytes) memcpy(aux.data() + map_words, x->bits, clog_bytes);
+    uint32_t *d_aux = nullptr, *d_ctr = nullptr, *d_lctr = nullptr, *d_list = nullptr, *d_vals = nullptr;
+    void* d_tmp = nullptr;
+    uint32_t h_ctr[BC_N] = {0}, h_lctr[LC_N] = {0};
+    const uint64_t resident = (uint64_t)std::max(c->prop.multiProcessorCount, 1) * 32;
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(std::min<uint64_t>(((uint64_t)n + WAVE - 1) / WAVE, resident), 1);
+    auto run = [&]() -> int {
+        VS_TRY(vis_wk(b, VW_AUX, aux.size() * 4, (void**)&d_aux));
+        VS_TRY(vis_wk(b, VW_CTR, (size_t)(BC_N + LC_N) * 4, (void**)&d_ctr));
+        d_lctr = d_ctr + BC_N;
+        if (n) VS_TRY(vis_wk(b, VW_LIST, (size_t)n * 4, (void**)&d_list));
+        VS_TRY(vs_dev_upload(c, d_aux, aux.data(), aux.size() * 4));
+        VS_HIP(hipMemsetAsync(d_ctr, 0, BC_N * 4, st));
+        VS_HIP(hipMemsetAsync(d_lctr, 0, LC_N * 4, st));
+        if (n && (!refresh || n_listed)) {
+            HeapVisArgs a{};
+            a.pages = h->d_pages;
+            a.page_size = h->page_size;
+            a.n_blocks = h->n_blocks;
+            a.tids = ix->tids;
+            a.n = n;
+            a.xmin = a.xmax = a.horizon = horizon;  // S_H: empty xip / subxip / own xids, not suboverflowed, not in recovery
+            a.xip = a.subxip = a.own = d_aux;       // (counts of 0: never read)
+            a.clog_first = x->first_xid;
+            a.clog_n = x->n_xids;
+            a.clog = reinterpret_cast<const uint8_t*>(d_aux + map_words);
+            a.visible = b->cls;
+            a.ctr = d_ctr;
+            a.block_map = refresh ? d_aux : nullptr;
+            a.map_blocks = map_blocks;
+            hipEvent_t ev = prof_begin(c);
+            hipLaunchKernelGGL(k_heap_vis_base, dim3(grid), dim3(WAVE), 0, st, a);
+            VS_HIP(hipGetLastError());
+            prof_end(c, PK_PAGES, ev);
+        }
+        VS_HIP(hipMemcpyAsync(h_ctr, d_ctr, BC_N * 4, hipMemcpyDeviceToHost, st));
+        VS_HIP(hipStreamSynchronize(st));
+        if (h_ctr[HC_ERR] != HE_OK) {
+            const uint32_t* e = h_ctr + HC_ERR;
+            vs_set_error("heap block %u item %u: %s (detail %u)", e[1], e[2], kHeapErrorText[e[0] <= HE_LAST ? e[0] : 0], e[3]);
+            return VS_ERR_INVALID;
+        }
+        if (n) {
+            hipLaunchKernelGGL(k_vis_list, dim3(grid), dim3(WAVE), 0, st, (const uint8_t*)b->cls, n, d_list, d_lctr);
+            VS_HIP(hipGetLastError());
+        }
+        VS_HIP(hipMemcpyAsync(h_lctr, d_lctr, LC_N * 4, hipMemcpyDeviceToHost, st));
+        VS_HIP(hipStreamSynchronize(st));
+        const uint32_t r = std::min(h_lctr[LC_NLIST], n);
+        if (!b->dep || b->dep_cap < std::max(r, 1u)) {
+            if (b->dep) (void)hipFree(b->dep);
+            b->dep = nullptr;
+            b->dep_cap = 0;
+            const size_t cap = (size_t)std::max(r, 1u) + r / 8;
+            VS_HIP(hipMalloc(&b->dep, cap * 4));
+            b->dep_cap = cap;
+        }
+        b->dep_host.assign(r, 0u);
+        if (r) {  // ascending, whatever order the waves appended in
+            VS_TRY(vis_wk(b, VW_VALS, (size_t)r * 4, (void**)&d_vals));
+            size_t tmp_bytes = 0;
+            VS_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (const uint32_t*)d_list, b->dep, (const uint32_t*)d_list, d_vals, (int)r, 0, 32, st));
+            VS_TRY(vis_wk(b, VW_TMP, tmp_bytes + 16, &d_tmp));
+            VS_HIP(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, (const uint32_t*)d_list, b->dep, (const uint32_t*)d_list, d_vals, (int)r, 0, 32, st));
+            VS_HIP(hipStreamSynchronize(st));
+            VS_TRY(vs_dev_download(c, b->dep_host.data(), b->dep, (size_t)r * 4));
+        }
+        b->r = r;
+        return VS_OK;
+    };
+    const int rc = run();
+    if (rc != VS_OK) (void)hipStreamSynchronize(st);
+    if (rc != VS_OK) {
+        vs_vis_base_drop(ix);  // (classes half written are no base)
+        return rc;
+    }
+    b->n = n;
+    b->horizon = horizon;
+    if (out) {
+        uint64_t sums[BSUM_N];
+        memcpy(sums, h_ctr + VC_SUMS, sizeof(sums));
+        vs_vis_base_stats S{};
+        S.n_class[0] = h_lctr[LC_CLASS + 0];
+        S.n_class[1] = h_lctr[LC_CLASS + 1];
+        S.n_class[2] = b->r;
+        S.r = b->r;
+        S.n_walked = sums[BSUM_WALKED];
+        S.n_deleted = sums[BSUM_DELETED];
+        S.n_not_found = sums[BSUM_NOT_FOUND];
+        S.n_dead_line_pointer = sums[BSUM_DEAD_LP];
+        S.n_recent = sums[BSUM_RECENT];
+        S.n_undecided = sums[BSUM_UNDECIDED];
+        S.chain_hops = sums[BSUM_HOPS];
+        for (int k = 0; k < VS_VIS_R_N; ++k) S.undecided_by_reason[k] = sums[BSUM_REASON + k];
+        *out = S;
+    }
+    return VS_OK;
+}
+
+extern "C" int vs_index_vis_base_eval(vs_index* ix, vs_heap_res* h, uint32_t horizon_xid, const vs_xact_status* xact, const uint32_t* changed_blocks,
+                                      uint32_t n_changed, vs_vis_base_stats* out) {
+    const char* what = "vs_index_vis_base_eval";
+    VS_TRY(vis_write_check(what, ix));
+    VS_REQUIRE(h, "%s: the resident heap fork is NULL", what);
+    VS_REQUIRE(h->ctx == ix->ctx, "%s: the index and the resident heap fork belong to different contexts", what);
+    VS_REQUIRE(xact, "%s: the transaction status window is required", what);
+    VS_REQUIRE(!(xact->first_xid & 3u), "%s: first_xid %u is not a multiple of 4", what, xact->first_xid);
+    VS_REQUIRE(xact->bits || !xact->n_xids, "%s: the transaction status bits are NULL with n_xids above 0", what);
+    VS_REQUIRE(horizon_xid >= 3u, "%s: the horizon %u is no normal xid", what, horizon_xid);
+    VS_REQUIRE(changed_blocks || !n_changed, "%s: changed_blocks is NULL with n_changed above 0", what);
+    for (uint32_t i = 1; i < n_changed; ++i)
+        VS_REQUIRE(changed_blocks[i - 1] < changed_blocks[i], "%s: changed_blocks must be ascending and distinct (entry %u)", what, i);
+    VS_REQUIRE(!n_changed || changed_blocks[n_changed - 1] != 0xFFFFFFFFu, "%s: block 0xFFFFFFFF is no block of a relation", what);
+    VS_REQUIRE(ix->tids || !ix->d.n, "%s: the index has no heap tid column", what);
+    VS_REQUIRE(ix->d.n <= 0x7FFFFFFFu, "%s: %u nodes", what, ix->d.n);
+    if (changed_blocks) VS_TRY(vis_need_base(what, ix));
+    return vs_guard(what, [&] { return vis_base_run(ix, h, horizon_xid, xact, changed_blocks, n_changed, out); });
+}
+
+extern "C" int vs_index_vis_base_drop(vs_index* ix) {
+    VS_TRY(vis_write_check("vs_index_vis_base_drop", ix));
+    vs_vis_base_drop(ix);
+    return VS_OK;
+}
+
+extern "C" int vs_index_vis_base_info(const vs_index* ix, uint32_t* horizon_xid, uint32_t* r, uint32_t* depends_nodes, uint32_t cap) {
+    VS_REQUIRE(ix && (depends_nodes || !cap), "vs_index_vis_base_info: null argument");
+    VS_TRY(vis_need_base("vs_index_vis_base_info", ix));
+    const VisBase* b = ix->vb;
+    if (horizon_xid) *horizon_xid = b->horizon;
+    if (r) *r = b->r;
+    if (cap) memcpy(depends_nodes, b->dep_host.data(), (size_t)std::min(cap, b->r) * 4);
+    return VS_OK;
+}
+
+extern "C" int vs_index_vis_slot_drop(vs_index* ix, uint32_t slot) {
+    VS_TRY(vis_slot_check("vs_index_vis_slot_drop", ix, slot));
+    VisBase* b = ix->vb;
+    if (!b || !b->overlay[slot]) return VS_OK;
+    return vs_guard("vs_index_vis_slot_drop", [&]() -> int {
+        VS_HIP(hipSetDevice(ix->ctx->device));
+        VS_HIP(hipStreamSynchronize(ix->ctx->stream));  // no launch may still read it
+        VS_TRY(vis_tab_set(ix, slot, nullptr));
+        (void)hipFree(b->overlay[slot]);
+        b->overlay[slot] = nullptr;
+        return VS_OK;
+    });
+}
+
+extern "C" int vs_index_vis_slot_eval(vs_index* ix, vs_heap_res* h, uint32_t slot, const vs_mvcc_snapshot* snap, const vs_xact_status* xact,
+                                      vs_vis_stats* out, uint32_t* undecided_nodes, uint32_t cap, uint32_t* n_undecided) {
+    const char* what = "vs_index_vis_slot_eval";
+    VS_TRY(vis_slot_check(what, ix, slot));
+    VS_REQUIRE(h, "%s: the resident heap fork is NULL", what);
+    VS_REQUIRE(h->ctx == ix->ctx, "%s: the index and the resident heap fork belong to different contexts", what);
+    VS_TRY(heap_vis_check(what, snap, xact, undecided_nodes, cap));
+    VS_TRY(vis_need_base(what, ix));
+    VisBase* b = ix->vb;
+    // the base holds for snapshots that cannot see behind its horizon: xmin and every own xid at or after it
+    VS_REQUIRE(!vis_precedes_host(snap->xmin, b->horizon), "%s: the snapshot's xmin %u precedes the base's horizon %u", what, snap->xmin, b->horizon);
+    for (uint32_t i = 0; i < snap->n_own; ++i)
+        VS_REQUIRE(!vis_precedes_host(snap->own_xids[i], b->horizon), "%s: the own xid %u precedes the base's horizon %u", what, snap->own_xids[i], b->horizon);
+    return vs_guard(what, [&]() -> int {
+        vs_ctx* c = ix->ctx;
+        VS_HIP(hipSetDevice(c->device));
+        VS_HIP(hipStreamSynchronize(c->stream));  // (replacing an overlay a launch may still be reading)
+        const uint32_t r = b->r;
+        uint64_t* d_tids = nullptr;
+        std::vector<uint32_t> und(std::min(cap, r));
+        uint32_t nu = 0;
+        auto run = [&]() -> int {
+            if (!b->overlay[slot]) {
+                uint8_t* p = nullptr;
+                VS_HIP(hipMalloc(&p, std::max(r, 1u)));
+                b->overlay[slot] = p;
+                VS_TRY(vis_tab_set(ix, slot, p));
+            }
+            VS_HIP(hipMalloc(&d_tids, (size_t)std::max(r, 1u) * 8));
+            if (r) {
+                hipLaunchKernelGGL(k_vis_gather_tids, dim3(heap_dev_grid(r, 256)), dim3(256), 0, c->stream, (const uint64_t*)ix->tids, (const uint32_t*)b->dep, r, d_tids);
+                VS_HIP(hipGetLastError());
+            }
+            // the list positions of the undecided come back ascending; so are their nodes, the list being ascending
+            return heap_vis_run(h, d_tids, r, snap, xact, b->overlay[slot], out, und.data(), (uint32_t)und.size(), &nu);
+        };
+        const int rc = run();
+        if (rc != VS_OK) (void)hipStreamSynchronize(c->stream);
+        if (d_tids) (void)hipFree(d_tids);
+        if (rc != VS_OK) {  // (an overlay half written is no overlay)
+            if (b->overlay[slot]) {
+                (void)vis_tab_set(ix, slot, nullptr);
+                (void)hipFree(b->overlay[slot]);
+                b->overlay[slot] = nullptr;
+            }
+            return rc;
+        }
+        for (size_t i = 0; i < und.size() && i < nu; ++i) undecided_nodes[i] = b->dep_host[und[i]];
+        if (n_undecided) *n_undecided = nu;
+        return VS_OK;
+    });
+}
+
+extern "C" int vs_index_vis_slot_patch(vs_index* ix, uint32_t slot, const uint32_t* nodes, const uint8_t* values, uint32_t n) {
+    const char* what = "vs_index_vis_slot_patch";
+    VS_TRY(vis_slot_check(what, ix, slot));
+    VS_REQUIRE((nodes && values) || !n, "%s: null argument", what);
+    VS_TRY(vis_need_base(what, ix));
+    VisBase* b = ix->vb;
+    if (!b->overlay[slot]) {
+        vs_set_error("%s: slot %u has no overlay (vs_index_vis_slot_eval)", what, slot);
+        return VS_ERR_STATE;
+    }
+    return vs_guard(what, [&]() -> int {
+        // node -> its position in the depends list; one entry per position, the last one given
+        std::vector<std::pair<uint32_t, uint32_t>> order(n);
+        for (uint32_t i = 0; i < n; ++i) {
+            const auto it = std::lower_bound(b->dep_host.begin(), b->dep_host.end(), nodes[i]);
+            VS_REQUIRE(it != b->dep_host.end() && *it == nodes[i], "%s: node %u is not on the depends list", what, nodes[i]);
+            order[i] = {(uint32_t)(it - b->dep_host.begin()), i};
+        }
+        if (!n) return VS_OK;
+        std::sort(order.begin(), order.end());
+        std::vector<uint32_t> up;
+        std::vector<uint8_t> uv;
+        for (uint32_t i = 0; i < n; ++i)
+            if (i + 1 == n || order[i + 1].first != order[i].first) {
+                up.push_back(order[i].first);
+                uv.push_back(values[order[i].second]);
+            }
+        vs_ctx* c = ix->ctx;
+        VS_HIP(hipSetDevice(c->device));
+        uint32_t* d_pos = nullptr;
+        uint8_t* d_vals = nullptr;
+        auto run = [&]() -> int {
+            VS_HIP(hipMalloc(&d_pos, up.size() * 4));
+            VS_HIP(hipMalloc(&d_vals, uv.size()));
+            VS_TRY(vs_dev_upload(c, d_pos, up.data(), up.size() * 4));
+            VS_TRY(vs_dev_upload(c, d_vals, uv.data(), uv.size()));
+            hipLaunchKernelGGL(k_mask_patch, dim3(heap_dev_grid(up.size(), 256)), dim3(256), 0, c->stream, b->overlay[slot], (const uint32_t*)d_pos,
+                               (const uint8_t*)d_vals, (uint32_t)up.size());
+            VS_HIP(hipGetLastError());
+            VS_HIP(hipStreamSynchronize(c->stream));
+            return VS_OK;
+        };
+        const int rc = run();
+        if (rc != VS_OK) (void)hipStreamSynchronize(c->stream);
+        if (d_pos) (void)hipFree(d_pos);
+        if (d_vals) (void)hipFree(d_vals);
+        return rc;
+    });
+}
+
+extern "C" int vs_index_vis_materialize(vs_index* ix, uint32_t slot, uint32_t snapshot) {
+    const char* what = "vs_index_vis_materialize";
+    VS_TRY(vis_slot_check(what, ix, slot));
+    VS_TRY(snapshot_write_check(what, ix, snapshot));
+    VS_TRY(vis_need_base(what, ix));
+    VisBase* b = ix->vb;
+    if (!b->overlay[slot]) {
+        vs_set_error("%s: slot %u has no overlay (vs_index_vis_slot_eval)", what, slot);
+        return VS_ERR_STATE;
+    }
+    return vs_guard(what, [&]() -> int {
+        vs_ctx* c = ix->ctx;
+        VS_HIP(hipSetDevice(c->device));
+        bool fresh = false;
+        VS_TRY(snapshot_mask(ix, snapshot, &fresh));
+        const uint32_t n = ix->d.n;  // (rows past the evaluated ones read class 0: hidden, as in every stored mask)
+        if (n) {
+            hipLaunchKernelGGL(k_vis_materialize, dim3(heap_dev_grid(n, 256)), dim3(256), 0, c->stream, (const uint8_t*)b->cls, (const uint32_t*)b->dep, b->r,
+                               (const uint8_t*)b->overlay[slot], ix->snap[snapshot], n);
+            VS_HIP(hipGetLastError());
+        }
+        VS_HIP(hipStreamSynchronize(c->stream));
+        return VS_OK;
+    });
+}
+
+// a view takes the base and the overlays of its source over, as vs_index_snapshot_share hands over the masks
+extern "C" int vs_index_vis_share(vs_index* view, const vs_index* src) {
+    VS_REQUIRE(view && src && view->is_view, "vs_index_vis_share: needs a view and its source");
+    view->vb = src->vb;
+    return VS_OK;
 }

@@ -129,9 +129,42 @@ struct Caps {
     double f_pool_frac;  // share of the scans expected to need a global dedup-overflow table
 };
 // one launch (a chunk of the batch): nq scans of search list L that each leave a stream of M rows
+enum { BV_INDEX_MASK = 0, BV_NONE = 1, BV_SLOTS = 2 };
 struct BatchPlan {
     uint32_t nq, L, rescore, k, M;
     bool stream_only;  // vs_stream_batch: no rerank
+    // heap visibility of the chunk's scans: BV_INDEX_MASK the mask in force on the index (vs_index_set_visibility*, vs_index_snapshot_use),
+    // BV_NONE the caller named slots and every one is 0, BV_SLOTS d_slots (DEVICE [nq]) names each scan's slot (vs_search_batch_vis)
+    uint32_t vis_mode = 0;
+    const uint32_t* d_slots = nullptr;
+};
+
+// ---- what a launch knows about heap visibility (vs_heap_vis.h) ----------------------------------------------------
+// Legacy mode (slots == nullptr): bytes is one mask for the whole launch, a node with bytes[node] == 0 is hidden; bytes == nullptr:
+// every tuple visible.  Classed mode (slots != nullptr): bytes is the class byte of the base (VIS_CLASS_*), dep the ascending depends
+// list of r nodes, overlay[slot] the r bytes of a slot's overlay and slots[q] the slot scan q runs under (0: every tuple visible).
+enum { VIS_CLASS_NONE = 0, VIS_CLASS_ALL = 1, VIS_CLASS_DEPENDS = 2 };
+struct VisView {
+    const uint8_t* bytes = nullptr;
+    const uint32_t* slots = nullptr;
+    const uint32_t* dep = nullptr;
+    const uint8_t* const* overlay = nullptr;
+    uint32_t r = 0;
+};
+// the base of an index (vs_index_vis_base_eval) and the overlays of its slots; shared by the views that took it over
+struct VisBase {
+    uint8_t* cls = nullptr;     // DEVICE, one class byte per node, allocated at capacity: rows past the evaluated ones read 0
+    size_t cls_rows = 0;        // rows cls has room for
+    uint32_t n = 0;             // nodes the last evaluation saw
+    uint32_t* dep = nullptr;    // DEVICE [r] ascending
+    std::vector<uint32_t> dep_host;
+    uint32_t r = 0, horizon = 0;
+    uint8_t* overlay[VS_MAX_VIS_SLOTS] = {nullptr};  // DEVICE [r] each (host mirror of tab)
+    uint8_t** tab = nullptr;    // DEVICE [VS_MAX_VIS_SLOTS]
+    size_t dep_cap = 0;         // entries dep has room for
+    // DEVICE scratch of an evaluation, kept between the rounds of a shim and grown on demand (VW_*; freed with the base)
+    void* wk[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t wk_bytes[5] = {0, 0, 0, 0, 0};
 };
 // plan + capacities + the caller's device pointers of the batch in flight between vs_search_batch_dev and its finish
 struct PendingBatch {
@@ -150,7 +183,8 @@ struct SearchWorkspace {
         raw_q2, out_ids2, out_tids2, out_dist2,  // second set of a pipelined host batch (search_host)
         red,                                      // RED_N u64 sums of the last launch's per-scan arrays (k_reduce_stats)
         order_work, order_perm,                   // VS_RERANK_ORDER: keys + counting-sort tables, and the batch's rerank order
-        order_labels;                             // ... and the region label (u16: nearest seed row) of corpus rows [0, lab_rows)
+        order_labels,                             // ... and the region label (u16: nearest seed row) of corpus rows [0, lab_rows)
+        vis_slots;                                // the visibility slots of a host batch's scans (vs_search_batch_vis)
     uint32_t order_nq = 0;         // scans of the last batch's rerank order in order_perm (0: it took the scans' own order)
     // what order_labels was built from: the seed rows s * lab_step for s < lab_S of the codes at epoch lab_epoch (vs_index::codes_epoch)
     uint32_t lab_rows = 0, lab_S = 0, lab_step = 0;
@@ -216,6 +250,7 @@ struct vs_index {
     const uint8_t* visible = nullptr;  // per node, 0 = the heap fetch finds nothing under the scan's snapshot (nullptr: all visible)
     uint8_t* visible_own = nullptr;    // the library's own copy (vs_index_set_visibility)
     uint8_t* snap[VS_MAX_SNAPSHOTS] = {nullptr};  // per-snapshot masks of shared launches (vs_index_snapshot_put); slot 0 unused
+    VisBase* vb = nullptr;     // the visibility base and its overlays (vs_index_vis_base_eval); a view's is its source's (vs_index_vis_share)
     float* vecs = nullptr;
     float* vnorm = nullptr;  // per node: 0 => leave vector alone, else divisor sqrt(norm) (preprocess_cosine)
     float* vnorm_idx = nullptr;  // the same for the index slice (plain storage, cosine, num_dimensions_to_index < num_dimensions)
@@ -301,8 +336,11 @@ hipEvent_t pool_event(vs_ctx* c);                                  // vs_api.hip
 int download_async_rows(vs_ctx* c, void* dst, const void* src, size_t bytes);  // vs_api.hip: rows back through the pinned ring
 void stage_copy(void* dst, const void* src, size_t n);                         // vs_api.hip: pageable <-> pinned, split over VS_STAGE_THREADS
 int vs_search_batch_dev_impl(vs_index* ix, const float* d_queries, const int16_t* d_qlabels, const uint32_t* d_qlabel_off, uint32_t nq,
-                             uint32_t L, uint32_t rescore, uint32_t k, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist);  // vs_batch.hip
+                             uint32_t L, uint32_t rescore, uint32_t k, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist,
+                             const uint32_t* d_scan_slots = nullptr);  // vs_batch.hip; d_scan_slots: vs_search_batch_dev_vis
 int vs_search_batch_dev_finish_impl(vs_index* ix, vs_stats* stats);  // vs_batch.hip
+void vs_vis_base_drop(vs_index* ix);  // vs_heap_vis.h: frees the base and every overlay of an owner (synchronises its stream first)
+void vs_vis_base_free(vs_index* ix);  // ... and the record itself (vs_index_free)
 
 // ---- kernel launch wrappers (defined in the .hip files) -------------------------------------------------------
 struct SearchLaunch {
@@ -327,7 +365,7 @@ struct SearchLaunch {
     uint32_t* pool_counter = nullptr;  // non-null: heap_g / hash hold pool_slots regions claimed with an atomic counter
     uint32_t pool_slots = 0;
     uint32_t* fb_flag = nullptr;   // [nq] set to 1 for every scan this launch ran in only_failed mode
-    const uint8_t* visible = nullptr;  // non-null: rows whose node has visible[node] == 0 are counted and left out of the stream
+    VisView vis;  // rows whose node it hides (vis_hidden, vs_device.h) are counted and left out of the stream
     // resumable scans (the amgettuple cursor, AM/scan.rs:162-174,370-405): resume[q * resume_stride ..] is scan q's saved state —
     // header RS_* + the LDS image (heap top, LDS dedup table, visited list); its heap spill array / dedup ladder are region q of
     // heap_g / hash and live on between launches.  A launch continues the scan for M more rows (written to out_ids[q][0..M)).
@@ -368,7 +406,7 @@ struct FastLaunch {
     // fb_flag[q] is set for the statistics
     uint32_t only_failed = 0;
     uint32_t* fb_flag = nullptr;
-    const uint8_t* visible = nullptr;  // non-null: rows whose node has visible[node] == 0 are counted and left out of the stream
+    VisView vis;  // rows whose node it hides (vis_hidden, vs_device.h) are counted and left out of the stream
     const uint64_t* qcodes;
     const int16_t* qlabels;
     const uint32_t* qlabel_off;
@@ -433,7 +471,7 @@ struct PlainLaunch {
     uint32_t lds_table;  // 1: the table's ids live in LDS as well, 0: in the workgroup's region of table_g
     uint32_t persist;    // workgroups of the persistent grid: min(resident, nq)
     uint32_t resident = 0;  // (host side) single-wave workgroups of this LDS size the device holds at once
-    const uint8_t* visible = nullptr;
+    VisView vis;
     uint64_t* heap_g = nullptr;       // [persist][hcap - hl]
     uint32_t* table_g = nullptr;      // [persist][slots] (lds_table == 0)
     uint32_t* scan_counter = nullptr;  // next scan to run (zero before the launch)
@@ -500,7 +538,7 @@ int launch_label_order(vs_index* idx, const uint16_t* d_labels, uint32_t lab_row
 enum { RED_STATUS = 0, RED_VISITS, RED_CAND, RED_DQ, RED_READS, RED_NEXT, RED_FB_SCANS, RED_FB_VISITS, RED_FB_DQ, RED_HEAP_ROWS,
        RED_INS_SUM, RED_INS_MAX, RED_INS_FAST, RED_INS_OV, RED_N = 16 };
 int launch_reduce_stats(vs_index* idx, const uint32_t* d_stats, const uint32_t* d_fb, const uint32_t* d_cnt, const uint32_t* d_status,
-                        uint32_t nq, uint32_t M, uint32_t rescore, bool windowed, uint32_t ins_limit, uint64_t* d_red);
+                        uint32_t nq, uint32_t M, uint32_t rescore, bool windowed, bool has_visible, uint32_t ins_limit, uint64_t* d_red);
 int launch_resort_cursor(vs_index* idx, uint32_t n, bool exhausted, uint32_t rescore, uint32_t k, const uint32_t* d_stream,
                          const float* d_dist, const uint32_t* d_keys, uint64_t* d_heap, uint32_t* d_cur, uint32_t* d_out_ids,
                          uint64_t* d_out_tids, float* d_out_dist);

@@ -1238,11 +1238,11 @@ int launch_label_order(vs_index* idx, const uint16_t* d_labels, uint32_t lab_row
 
 // d_red: RED_N u64 words, zeroed by the caller on the same stream
 int launch_reduce_stats(vs_index* idx, const uint32_t* d_stats, const uint32_t* d_fb, const uint32_t* d_cnt, const uint32_t* d_status,
-                        uint32_t nq, uint32_t M, uint32_t rescore, bool windowed, uint32_t ins_limit, uint64_t* d_red) {
+                        uint32_t nq, uint32_t M, uint32_t rescore, bool windowed, bool has_visible, uint32_t ins_limit, uint64_t* d_red) {
     if (nq == 0) return VS_OK;
     const uint32_t blocks = (nq + 255) / 256 < 256 ? (nq + 255) / 256 : 256;
     hipLaunchKernelGGL(k_reduce_stats, dim3(blocks), dim3(256), 0, idx->ctx->stream, d_stats, d_fb, d_cnt, d_status, nq, M, rescore,
-                       windowed ? 1u : 0u, idx->visible ? 1u : 0u, ins_limit, (unsigned long long*)d_red);
+                       windowed ? 1u : 0u, has_visible ? 1u : 0u, ins_limit, (unsigned long long*)d_red);
     VS_HIP(hipGetLastError());
     return VS_OK;
 }

@@ -377,7 +377,7 @@ static int round_launch(vs_scan_pool* p, const std::vector<uint32_t>& run, uint3
             f.out_cnt = (uint32_t*)p->cnt.p;
             f.stats = (uint32_t*)p->stats.p;
             f.status = d_status;  // the run mask on entry, the scan's outcome on exit
-            f.visible = p->S > 0 ? ix->visible : nullptr;
+            f.vis.bytes = p->S > 0 ? ix->visible : nullptr;
             f.resume = (uint32_t*)p->state.p;
             f.resume_stride = p->rw;
             f.row_stats = (uint32_t*)p->row_stats.p;
@@ -404,7 +404,7 @@ static int round_launch(vs_scan_pool* p, const std::vector<uint32_t>& run, uint3
             f.out_cnt = (uint32_t*)p->cnt.p;
             f.stats = (uint32_t*)p->stats.p;
             f.status = d_status;  // the run mask on entry, the scan's outcome on exit
-            f.visible = p->S > 0 ? ix->visible : nullptr;
+            f.vis.bytes = p->S > 0 ? ix->visible : nullptr;
             f.resume = (uint32_t*)p->state.p;
             f.resume_stride = p->rw;
             f.row_stats = (uint32_t*)p->row_stats.p;
@@ -436,7 +436,7 @@ static int round_launch(vs_scan_pool* p, const std::vector<uint32_t>& run, uint3
         sl.stats = (uint32_t*)p->stats.p;
         sl.status = d_status;
         sl.only_failed = 1;  // only the slots marked above run; the others return at once and keep their saved state
-        sl.visible = p->S > 0 ? ix->visible : nullptr;  // the heap is only fetched for the rescore window
+        sl.vis.bytes = p->S > 0 ? ix->visible : nullptr;  // the heap is only fetched for the rescore window
         sl.resume = (uint32_t*)p->state.p;
         sl.resume_stride = p->rw;
         sl.row_stats = (uint32_t*)p->row_stats.p;  // [slot][M][ST_N]

@@ -164,6 +164,7 @@ __global__ __launch_bounds__(WAVE) void k_search(SearchArgs a) {
     } else {
         for (uint32_t w = lane; w < a.code_stride; w += WAVE) qc[w] = s.qcodes[(size_t)q * a.code_stride + w];
     }
+    const ScanVis svis = vis_of_scan(s.vis, q);  // what this scan may see of the heap
     // resumable scan: state saved by an earlier launch (header + LDS image of heap top / dedup table / visited list)
     uint32_t* rs = s.resume ? s.resume + (size_t)q * s.resume_stride : nullptr;
     const bool resumed = rs != nullptr && rfl(rs[RS_INIT]) == 1u;
@@ -489,7 +490,7 @@ __global__ __launch_bounds__(WAVE) void k_search(SearchArgs a) {
             st_reads++;
             const uint64_t tid = a.tids[fnode];
             if ((tid & 0xFFFFull) == 0) continue;  // InvalidOffsetNumber: deleted tuple (AM/scan.rs:231-234)
-            if (s.visible && s.visible[fnode] == 0) {  // get_full_distance_for_resort -> None (AM/scan.rs:268-272)
+            if (vis_hidden(svis, fnode)) {  // get_full_distance_for_resort -> None (AM/scan.rs:268-272)
                 st_invis++;
                 st_next++;  // the caller's loop asks `next` again
                 continue;
@@ -842,6 +843,7 @@ __device__ __forceinline__ void plain_scan(const PlainArgs& a, const uint32_t q,
     uint32_t* surv_d = surv_id + 64;
 
     for (uint32_t i = lane; i < a.vec_stride; i += WAVE) qf[i] = a.q_full[(size_t)q * a.vec_stride + i];
+    const ScanVis svis = vis_of_scan(s.vis, q);  // what this scan may see of the heap
     uint32_t* const rs = RS ? s.resume + (size_t)q * s.resume_stride : nullptr;
     const bool resumed = RS && rfl(rs[RSP_INIT]) == 1u;
     // (resumable scans) the image of a saved scan: heap top | occupancy bits | LDS table | visited keys | visited nodes — every piece a
@@ -1046,7 +1048,7 @@ __device__ __forceinline__ void plain_scan(const PlainArgs& a, const uint32_t q,
             st_reads++;
             const uint64_t tid = a.tids[fnode];
             if ((tid & 0xFFFFull) == 0) continue;  // InvalidOffsetNumber: deleted tuple (AM/scan.rs:231-234)
-            if (s.visible && s.visible[fnode] == 0) {  // get_full_distance_for_resort -> None (AM/scan.rs:268-272)
+            if (vis_hidden(svis, fnode)) {  // get_full_distance_for_resort -> None (AM/scan.rs:268-272)
                 st_invis++;
                 st_next++;  // the caller's loop asks `next` again
                 continue;

@@ -862,7 +862,9 @@ __device__ __forceinline__ void fast_scan(const FastArgs& a, const uint32_t q, c
     const uint32_t image_words = RS ? (uint32_t)((vmap + s.vwords) - hp) : 0u;
     if (resumed)  // (16 bytes per lane: the image is padded to whole uint4, hp and the saved image are 16-byte aligned)
         for (uint32_t i = 4u * lane; i < image_words; i += 4u * WAVE) *reinterpret_cast<uint4*>(hp + i) = *reinterpret_cast<const uint4*>(rs + RSF_HDR + i);
-    const uint8_t* const visible = FULL ? s.visible : nullptr;
+    // what this scan may see of the heap: a legacy mask, or the base's classes with the overlay of the slot the scan names
+    const ScanVis svis = FULL ? vis_of_scan(s.vis, q) : ScanVis{nullptr, nullptr, nullptr, 0u};
+    const uint8_t* const visible = svis.bytes;  // (the byte requested ahead of a visit is the mask byte, resp. the class byte)
     const bool labels_some = FULL && s.qlabel_off != nullptr;  // LabeledVector.labels is Some (AM/labels/mod.rs:222-236)
     uint32_t nql = 0;
     bool wide_key = false;  // a key of more than MAX_QLABELS labels does not fit the LDS slot: the general kernel runs the scan
@@ -1394,7 +1396,7 @@ __device__ __forceinline__ void fast_scan(const FastArgs& a, const uint32_t q, c
             if (VR > 0) {
                 const uint64_t tid = fnode == ft_node ? ft_val : load_stream64(tids_v + fnode);
                 fflags = (tid & 0xFFFFull) == 0 ? VIS_DEAD : 0u;
-                if (visible) fflags |= rfl(fnode == ft_node ? ft_vis : (uint32_t)visible[fnode]) == 0 ? VIS_HIDDEN : 0u;
+                if (visible) fflags |= vis_hidden(svis, fnode, rfl(fnode == ft_node ? ft_vis : (uint32_t)visible[fnode])) ? VIS_HIDDEN : 0u;
             }
             if (fflags & VIS_DEAD) continue;  // InvalidOffsetNumber: deleted tuple (AM/scan.rs:231-234)
             if (visible && (fflags & VIS_HIDDEN)) {  // get_full_distance_for_resort -> None: fetched, counted, never enters
@@ -1533,7 +1535,7 @@ __device__ __forceinline__ void fast_scan(const FastArgs& a, const uint32_t q, c
             // ... visited.insert(partition_point(|x| *x < head), head) runs in registers meanwhile ...
             if (!vis_done) {
                 vis_done = true;
-                vis.insert(hd, node, ((vtid & 0xFFFFull) == 0 ? VIS_DEAD : 0u) | (vvis == 0 ? VIS_HIDDEN : 0u));
+                vis.insert(hd, node, ((vtid & 0xFFFFull) == 0 ? VIS_DEAD : 0u) | ((visible && vis_hidden(svis, node, vvis)) ? VIS_HIDDEN : 0u));
                 lap(2);
             }
             // ... then the probe sequence is finished
@@ -1655,7 +1657,7 @@ __device__ __forceinline__ void fast_scan(const FastArgs& a, const uint32_t q, c
             lap(5);
         }
         if (status) break;
-        if (!vis_done) vis.insert(hd, node, ((vtid & 0xFFFFull) == 0 ? VIS_DEAD : 0u) | (vvis == 0 ? VIS_HIDDEN : 0u));  // (an empty neighbor list)
+        if (!vis_done) vis.insert(hd, node, ((vtid & 0xFFFFull) == 0 ? VIS_DEAD : 0u) | ((visible && vis_hidden(svis, node, vvis)) ? VIS_HIDDEN : 0u));  // (an empty neighbor list)
         if (!pfa_issued) {  // nothing new to score: the old root is the next expansion
             pfa_node = VS_INVALID_NODE;
             pfa_h = 0xFFFFFFFFu;
@@ -1773,7 +1775,7 @@ size_t fast_lds_bytes(const vs_index* idx, const FastLaunch& s) {
     // LDS copy of the query code: the generic variant (NCH == 0), and the register-capped variants (minw >= 6: 8 NCH words, zero padded)
     const size_t qcopy = nch > 6 ? (size_t)idx->code_stride * 8 : (s.minw >= 6 && !s.build && !s.phase ? nch * 64 : 0);
     const bool lean = s.minw == 7 && s.vslot == 2 && nch == 3 && !s.build && !s.phase;  // (fast_scan: LEAN)
-    const bool plain = !s.qlabel_off && !s.visible && !(s.flags & FAST_FULL_VARIANT);
+    const bool plain = !s.qlabel_off && !s.vis.bytes && !(s.flags & FAST_FULL_VARIANT);
     size_t b = (size_t)(s.hl + 1) * 4 + (size_t)s.lh * 4 + (lean ? 2 : 3) * 64 * 4 + (s.vslot ? 0 : ARB_SLOTS * 4) + (s.vr ? 0 : (size_t)s.vcap * 8) +
                (lean && plain ? 0 : MAX_QLABELS * 2) + qcopy + (size_t)s.rc * 4 + (size_t)s.vwords * 4 + (lean ? 16 : 32);
     return (b + 15) / 16 * 16;
@@ -1849,7 +1851,7 @@ static int launch_fast_t(vs_index* idx, const FastArgs& a, size_t lds, uint32_t*
         return launch_fast_tt<NCH, 0, false, 1, false, true, 3, OPT_RS>(idx, a, lds, res);
     }
     if (a.s.vwords && a.s.vslot == 2) {  // 16-bit entries in buckets of eight + overflow table, occupancy bits in LDS (see fast_scan)
-        const bool plain = !a.s.qlabel_off && !a.s.visible && !(a.s.flags & FAST_FULL_VARIANT);
+        const bool plain = !a.s.qlabel_off && !a.s.vis.bytes && !(a.s.flags & FAST_FULL_VARIANT);
         // (the usual index: 24-word code rows — 768 x 2 bit, 1536 x 1 bit — and num_neighbors <= 64)
         const bool std_geom = a.code_stride == 24 && a.R <= WAVE && a.nbr_stride == 64;
         // (OPT_G2 at six waves per SIMD — two code rows per 4-lane group in flight, 78 VGPRs, no spills — was timed at 50M in round 6:
@@ -1865,7 +1867,7 @@ static int launch_fast_t(vs_index* idx, const FastArgs& a, size_t lds, uint32_t*
     if (a.s.vwords && a.s.vslot) {  // occupancy bitmap of the dedup table's slots in LDS (table-less regime, LDS-ring visited list)
         VS_REQUIRE(a.s.vr == 0 && a.s.lh == 0 && (uint64_t)a.s.vwords * 32 >= a.s.gcap && a.s.rc == 0,
                    "fast search: the slot bitmap needs the table-less regime and one bit per slot");
-        const bool plain = !a.s.qlabel_off && !a.s.visible && !(a.s.flags & FAST_FULL_VARIANT);
+        const bool plain = !a.s.qlabel_off && !a.s.vis.bytes && !(a.s.flags & FAST_FULL_VARIANT);
         if (NCH == 3 && a.s.minw == 6 && plain) return launch_fast_tt<3, 0, false, 6, false, false, 2>(idx, a, lds, res);
         if (NCH == 3 && a.s.minw == 6) return launch_fast_tt<3, 0, false, 6, false, true, 2>(idx, a, lds, res);
         return launch_fast_tt<NCH, 0, false, 1, false, true, 2>(idx, a, lds, res);
@@ -1873,7 +1875,7 @@ static int launch_fast_t(vs_index* idx, const FastArgs& a, size_t lds, uint32_t*
     if (a.s.vwords) {  // written-bucket bitmap in LDS instead of cleared tables (table-less regime, LDS-ring visited list)
         VS_REQUIRE(a.s.vr == 0 && a.s.lh == 0 && (uint64_t)a.s.vwords * 128 >= a.s.gcap,
                    "fast search: the written-bucket bitmap needs the table-less regime and one bit per bucket");
-        const bool plain = !a.s.qlabel_off && !a.s.visible && !(a.s.flags & FAST_FULL_VARIANT);
+        const bool plain = !a.s.qlabel_off && !a.s.vis.bytes && !(a.s.flags & FAST_FULL_VARIANT);
         if (NCH == 3 && a.s.minw == 6 && plain) return launch_fast_tt<3, 0, false, 6, false, false, 1>(idx, a, lds, res);
         if (NCH == 3 && a.s.minw == 6) return launch_fast_tt<3, 0, false, 6, false, true, 1>(idx, a, lds, res);
         if (NCH == 3 && a.s.minw == 5 && plain) return launch_fast_tt<3, 0, false, 5, false, false, 1>(idx, a, lds, res);
@@ -1889,7 +1891,7 @@ static int launch_fast_t(vs_index* idx, const FastArgs& a, size_t lds, uint32_t*
         return launch_fast_tt<NCH, 8, false, 1, false>(idx, a, lds, res);
     }
     if (NCH == 3) {
-        const bool plain = !a.s.qlabel_off && !a.s.visible && !(a.s.flags & FAST_FULL_VARIANT);  // no label keys, no visibility mask
+        const bool plain = !a.s.qlabel_off && !a.s.vis.bytes && !(a.s.flags & FAST_FULL_VARIANT);  // no label keys, no visibility mask
         if (a.s.minw == 5 && plain) return launch_fast_tt<3, 0, false, 5, false, false>(idx, a, lds, res);
         if (a.s.minw == 5) return launch_fast_tt<3, 0, false, 5, false>(idx, a, lds, res);
         if (a.s.minw == 6 && plain) return launch_fast_tt<3, 0, false, 6, false, false>(idx, a, lds, res);

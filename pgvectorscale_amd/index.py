@@ -307,6 +307,56 @@ class DiskAnnIndex:
             raise ValueError(f"{nd.size} nodes but {v.size} values")
         check(self._L.vs_index_snapshot_patch(self.h, snapshot_id, _p(nd), _p(v), nd.size))
 
+    # -- the visibility base and its overlays: scans of different snapshots in one launch (include/vsgpu.h has the class rule) --
+    def vis_base_eval(self, heap, horizon_xid, xact, changed_blocks=None):
+        """One class byte per node, independent of any snapshot, from the resident heap fork `heap`: 0 invisible to all, 1 visible to
+        all, 2 depends (vs_index_vis_base_eval).  horizon_xid must not exceed the oldest running xid.  changed_blocks (ascending,
+        distinct) refreshes an existing base for those heap blocks only.  Drops every overlay -> stats dict"""
+        _, x, _keep = _lib.vis_args(dict(xmin=horizon_xid, xmax=horizon_xid), xact)
+        cb = None if changed_blocks is None else np.ascontiguousarray(changed_blocks, np.uint32).ravel()
+        n_changed = 0 if cb is None else cb.size
+        if cb is not None and cb.size == 0:
+            cb = np.zeros(1, np.uint32)  # (an empty list is still a refresh: the pointer must not be NULL)
+        st = _lib.VisBaseStats()
+        check(self._L.vs_index_vis_base_eval(self.h, heap.h, int(horizon_xid) & 0xFFFFFFFF, C.byref(x), _p(cb), n_changed, C.byref(st)))
+        return st.as_dict()
+
+    def vis_base_drop(self):
+        check(self._L.vs_index_vis_base_drop(self.h))
+
+    def vis_base_info(self):
+        """-> (stored horizon, the depends list: class-2 nodes ascending, uint32)"""
+        hz, r = C.c_uint32(0), C.c_uint32(0)
+        check(self._L.vs_index_vis_base_info(self.h, C.byref(hz), C.byref(r), None, 0))
+        dep = np.empty(max(int(r.value), 1), np.uint32)
+        check(self._L.vs_index_vis_base_info(self.h, None, None, _p(dep), int(r.value)))
+        return int(hz.value), dep[:int(r.value)].copy()
+
+    def vis_slot_eval(self, heap, slot, snapshot, xact, cap=None):
+        """What `snapshot` sees of the depends list, kept as the overlay of slot 1..VS_MAX_VIS_SLOTS-1 (vs_index_vis_slot_eval)
+        -> (stats dict over the list's nodes, undecided nodes uint32 ascending, their full number)"""
+        s, x, _keep = _lib.vis_args(snapshot, xact)
+        cap = self.desc.n if cap is None else cap
+        und = np.empty(max(cap, 1), np.uint32)
+        st, nu = _lib.VisStats(), C.c_uint32(0)
+        check(self._L.vs_index_vis_slot_eval(self.h, heap.h, slot, C.byref(s), C.byref(x), C.byref(st), _p(und), cap, C.byref(nu)))
+        return st.as_dict(), und[:min(cap, int(nu.value))].copy(), int(nu.value)
+
+    def vis_slot_patch(self, slot, nodes, values):
+        """settles nodes of the depends list in the overlay of `slot` (the last entry of a node wins)"""
+        nd = np.ascontiguousarray(nodes, np.uint32).ravel()
+        v = np.ascontiguousarray(values, np.uint8).ravel()
+        if nd.shape != v.shape:
+            raise ValueError(f"{nd.size} nodes but {v.size} values")
+        check(self._L.vs_index_vis_slot_patch(self.h, slot, _p(nd), _p(v), nd.size))
+
+    def vis_slot_drop(self, slot):
+        check(self._L.vs_index_vis_slot_drop(self.h, slot))
+
+    def vis_materialize(self, slot, snapshot_id):
+        """the byte mask of legacy snapshot id 1..15 from the base and the overlay of `slot`"""
+        check(self._L.vs_index_vis_materialize(self.h, slot, snapshot_id))
+
     def download(self, codes=True, nbrs=True, tids=True, vecs=False, row_begin=0, row_count=None):
         n = self.desc.n if row_count is None else row_count
         out = {}
@@ -638,8 +688,9 @@ class DiskAnnIndex:
         return np.array(vals, np.int16), off
 
     def search_batch(self, queries, search_list_size=DEFAULT_QUERY_SEARCH_LIST_SIZE, rescore=DEFAULT_QUERY_RESCORE,
-                     k=10, qlabels=None):
-        """For each query: the rows of the first k amgettuple calls (node ids, heap TIDs, reranked distances)."""
+                     k=10, qlabels=None, vis_slots=None):
+        """For each query: the rows of the first k amgettuple calls (node ids, heap TIDs, reranked distances).  vis_slots: one
+        visibility slot per query (vis_slot_eval; 0 = every tuple visible) instead of the index's mask in force."""
         q = np.ascontiguousarray(queries, np.float32).reshape(-1, self.desc.dim_full)
         nq = q.shape[0]
         lv, lo = self._label_keys(qlabels, nq)
@@ -647,6 +698,14 @@ class DiskAnnIndex:
         tids = np.empty((nq, k), np.uint64)
         dist = np.empty((nq, k), np.float32)
         st = Stats()
+        if vis_slots is not None:
+            sl = np.ascontiguousarray(vis_slots, np.uint32).ravel()
+            if sl.shape != (nq,):
+                raise ValueError(f"vis_slots must have shape ({nq},), got {sl.shape}")
+            sl = sl if nq else np.zeros(1, np.uint32)
+            check(self._L.vs_search_batch_vis(self.h, _p(q), _p(lv), _p(lo), _p(sl), nq, search_list_size, rescore, k, _p(ids),
+                                              _p(tids), _p(dist), C.byref(st)))
+            return ids, tids, dist, st.as_dict()
         check(self._L.vs_search_batch(self.h, _p(q), _p(lv), _p(lo), nq, search_list_size, rescore, k, _p(ids), _p(tids),
                                       _p(dist), C.byref(st)))
         return ids, tids, dist, st.as_dict()
@@ -663,8 +722,13 @@ class DiskAnnIndex:
         return ids, ham, st.as_dict()
 
     def search_batch_dev(self, d_queries, nq, search_list_size, rescore, k, d_out_ids, d_out_tids=None, d_out_dist=None,
-                         d_qlabels=None, d_qlabel_off=None):
-        """d_qlabels / d_qlabel_off: device CSR of the label keys (sorted, de-duplicated per query) or None"""
+                         d_qlabels=None, d_qlabel_off=None, d_vis_slots=None):
+        """d_qlabels / d_qlabel_off: device CSR of the label keys (sorted, de-duplicated per query) or None; d_vis_slots: device
+        [nq] uint32, the visibility slot of every scan (vs_search_batch_dev_vis) or None"""
+        if d_vis_slots is not None:
+            check(self._L.vs_search_batch_dev_vis(self.h, d_queries, d_qlabels, d_qlabel_off, d_vis_slots, nq, search_list_size, rescore,
+                                                  k, d_out_ids, d_out_tids, d_out_dist))
+            return
         check(self._L.vs_search_batch_dev(self.h, d_queries, d_qlabels, d_qlabel_off, nq, search_list_size, rescore, k, d_out_ids,
                                           d_out_tids, d_out_dist))
 
@@ -779,13 +843,19 @@ class Broker:
         self.h = h
 
     def search(self, query, labels=None, search_list_size=DEFAULT_QUERY_SEARCH_LIST_SIZE, rescore=DEFAULT_QUERY_RESCORE, k=10,
-               snapshot=0):
-        """snapshot: id of the visibility mask the scan runs under (snapshot_put; 0 = every heap tuple visible)"""
+               snapshot=0, vis_slot=None):
+        """snapshot: id of the visibility mask the scan runs under (snapshot_put; 0 = every heap tuple visible).  vis_slot: the scan
+        names a visibility slot instead (DiskAnnIndex.vis_slot_eval; 0 = every tuple visible) and shares its launch with scans of
+        any other slot"""
         q = None if query is None else np.ascontiguousarray(query, np.float32).reshape(self.index.desc.dim_full)
         lab = None if labels is None else np.ascontiguousarray(labels, np.int16)
         ids = np.empty(k, np.uint32)
         tids = np.empty(k, np.uint64)
         dist = np.empty(k, np.float32)
+        if vis_slot is not None:
+            check(self._L.vs_broker_search_vis(self.h, _p(q), _p(lab), 0 if lab is None else lab.size, int(labels is not None),
+                                               search_list_size, rescore, k, vis_slot, _p(ids), _p(tids), _p(dist)))
+            return ids, tids, dist
         check(self._L.vs_broker_search_snapshot(self.h, _p(q), _p(lab), 0 if lab is None else lab.size, int(labels is not None),
                                                 search_list_size, rescore, k, snapshot, _p(ids), _p(tids), _p(dist)))
         return ids, tids, dist
@@ -796,6 +866,26 @@ class Broker:
         if v is not None and v.shape != (self.index.desc.n,):
             raise ValueError("one byte per node")
         check(self._L.vs_broker_snapshot_put(self.h, snapshot, _p(v)))
+
+    def call(self, fn, exclusive=True):
+        """runs fn() on the dispatcher thread, the only one that may touch the broker's index: how a base evaluation, a slot's
+        overlay or a materialized mask reaches it while the broker serves.  exclusive (vs_broker_call_exclusive): while no cursor
+        lane is inside a task — what anything that rewrites a mask, the base or an overlay needs; False is vs_broker_call.  An
+        exception fn raises is raised here"""
+        box = []
+
+        def task(_arg):
+            try:
+                fn()
+                return 0
+            except BaseException as e:  # noqa: BLE001  (carried across the C frame)
+                box.append(e)
+                return -1
+        cb = C.CFUNCTYPE(C.c_int, C.c_void_p)(task)
+        rc = (self._L.vs_broker_call_exclusive if exclusive else self._L.vs_broker_call)(self.h, cb, None)
+        if box:
+            raise box[0]
+        check(rc)
 
     def beginscan(self):
         """ambeginscan for a backend whose scans go through this broker"""

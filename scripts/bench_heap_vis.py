@@ -57,8 +57,9 @@ def headers(n):
     return xmin, xmax, m.astype("<u2"), (k < 8).astype(np.uint8)
 
 
-def fabricate(n):
-    """-> (pages uint8 [nb][B], tids uint64 [n] in heap order, expected mask) as HP.HeapRelation.add_item lays the same rows out"""
+def fabricate(n, headers=headers):
+    """-> (pages uint8 [nb][B], tids uint64 [n] in heap order, expected mask) as HP.HeapRelation.add_item lays the same rows out;
+    headers: the header mix (scripts/bench_vis_overlay.py brings its own)"""
     xmin, xmax, m, expect = headers(n)
     tup = np.zeros((n, TLEN), np.uint8)
     tup[:, 0:4] = xmin.view(np.uint8).reshape(n, 4)
@@ -85,8 +86,8 @@ def fabricate(n):
     return pages, tids, expect
 
 
-def check_fabricator(rows=1000):
-    pages, tids, _ = fabricate(rows)
+def check_fabricator(rows=1000, headers=headers):
+    pages, tids, _ = fabricate(rows, headers)
     xmin, xmax, m, _ = headers(rows)
     rel = HP.HeapRelation()
     otids = []
