@@ -25,7 +25,7 @@ struct vs_pages_dev {
 };
 
 enum { PE_OK = 0, PE_LINE_POINTER = 1, PE_ITEM_BOUNDS = 2, PE_SHORT_ITEM = 3, PE_VEC_BOUNDS = 4, PE_CODE_WIDTH = 5, PE_NEIGHBOR_SLOTS = 6,
-       PE_DANGLING = 7, PE_LABELS = 8, PE_LABELS_CHANGED = 9, PE_VECTOR_DIM = 10, PE_DANGLING_PLAIN = 11, PE_LAST = PE_DANGLING_PLAIN };
+       PE_DANGLING = 7, PE_LABELS = 8, PE_LABELS_CHANGED = 9, PE_VECTOR_DIM = 10, PE_DANGLING_PLAIN = 11, PE_UNALIGNED = 12, PE_LAST = PE_UNALIGNED };
 static const char* const kPageErrorText[] = {"", "line pointer is not LP_NORMAL", "item lies outside pd_upper..pd_special",
                                              "item shorter than the archived node", "ArchivedVec points outside the item",
                                              "bq_vector length differs from the index's code width",
@@ -33,7 +33,9 @@ static const char* const kPageErrorText[] = {"", "line pointer is not LP_NORMAL"
                                              "neighbor points at something that is not an SbqNode item of this relation",
                                              "label set is not strictly increasing", "label set of an existing node changed",
                                              "vector length differs from the index's dimensions",
-                                             "neighbor points at something that is not a PlainNode item of this relation"};
+                                             "neighbor points at something that is not a PlainNode item of this relation",
+                                             "item or ArchivedVec is not 4-byte aligned"};
+static_assert(sizeof kPageErrorText / sizeof kPageErrorText[0] == PE_LAST + 1, "one text per reason code");
 
 __device__ __forceinline__ uint32_t ld16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
 __device__ __forceinline__ uint32_t ld32(const uint8_t* p) {  // items are MAXALIGNed: 4-byte aligned words
@@ -65,7 +67,8 @@ __device__ __forceinline__ uint32_t page_item_at(const uint8_t* page, uint32_t u
     const uint32_t lp_off = lp & 0x7FFFu, lp_flags = (lp >> 15) & 3u, len = lp >> 17;
     detail = lp;
     if (lp_flags != 1u || len == 0) return PE_LINE_POINTER;
-    if (lp_off < upper || lp_off + len > special || (lp_off & 3u)) return PE_ITEM_BOUNDS;
+    if (lp_off < upper || lp_off + len > special) return PE_ITEM_BOUNDS;
+    if (lp_off & 3u) return PE_UNALIGNED;  // (the host reader memcpys and accepts; ld32 here is an aligned dword load)
     detail = len;
     if (len < root_size) return PE_SHORT_ITEM;
     it.item = page + lp_off;
@@ -83,7 +86,8 @@ __device__ __forceinline__ uint32_t page_item_vec8(const PageItem& it, uint32_t 
     detail = n;
     if (n != want) return mismatch;
     detail = fld;
-    if (tgt < 0 || (uint64_t)tgt + (uint64_t)n * 8 > it.len || (tgt & 3)) return PE_VEC_BOUNDS;
+    if (tgt < 0 || (uint64_t)tgt + (uint64_t)n * 8 > it.len) return PE_VEC_BOUNDS;
+    if (tgt & 3) return PE_UNALIGNED;
     return PE_OK;
 }
 
@@ -96,7 +100,8 @@ __device__ __forceinline__ uint32_t page_item_vec4(const PageItem& it, uint32_t 
     detail = n;
     if (n != want) return mismatch;
     detail = fld;
-    if (tgt < 0 || (uint64_t)tgt + (uint64_t)n * 4 > it.len || (tgt & 3)) return PE_VEC_BOUNDS;
+    if (tgt < 0 || (uint64_t)tgt + (uint64_t)n * 4 > it.len) return PE_VEC_BOUNDS;
+    if (tgt & 3) return PE_UNALIGNED;
     return PE_OK;
 }
 
@@ -365,7 +370,7 @@ extern "C" int vs_pages_dev_build(vs_pages_dev* d, const vs_index_desc* desc, co
     if (d_cnt) (void)hipFree(d_cnt);
     if (d_err) (void)hipFree(d_err);
     if (r == VS_OK && herr[0] != PE_OK) {
-        vs_set_error("block %u item %u: %s (detail %u)", herr[1], herr[2], kPageErrorText[herr[0] <= PE_LABELS ? herr[0] : 0], herr[3]);
+        vs_set_error("block %u item %u: %s (detail %u)", herr[1], herr[2], kPageErrorText[herr[0] <= PE_LAST ? herr[0] : 0], herr[3]);
         r = VS_ERR_INVALID;
     }
     // the raw pages are no longer needed
