@@ -919,6 +919,90 @@ static int plain_pair_args(vs_index* ix, const char* what, PlainVecs* pv) {
     return VS_OK;
 }
 
+// ---- what the entry points below share ------------------------------------------------------------------------------------
+// The states a call that rewrites or moves the index refuses to work in (VS_ERR_STATE), each with the caller's reason in its text.
+static int state_error(const char* what, const char* fmt, const char* arg = "") {
+    char msg[256];
+    snprintf(msg, sizeof msg, fmt, arg);
+    vs_set_error("%s: %s", what, msg);
+    return VS_ERR_STATE;
+}
+static int require_no_batch(vs_index* ix, const char* what) {
+    return ix->ws.pending ? state_error(what, "a batch of this handle is in flight (vs_search_batch_dev_finish first)") : VS_OK;
+}
+// why: what the writer fixed at open that the call would change
+static int require_no_writer(vs_index* ix, const char* what, const char* why) {
+    return vs_index_open_writers(ix) > 0 ? state_error(what, "a vs_pages_out writer of this index is open (%s; vs_pages_out_close first)", why) : VS_OK;
+}
+// done: what the call would have to do to a mask the library does not own ("grown", "compacted")
+static int require_own_mask(vs_index* ix, const char* what, const char* done) {
+    if (!ix->visible || ix->visible == ix->visible_own) return VS_OK;
+    for (const uint8_t* sp : ix->snap)
+        if (sp == ix->visible) return VS_OK;
+    return state_error(what, "a caller-owned device visibility mask is in force and cannot be %s by the library (clear or replace it)", done);
+}
+static const char* const WRITER_ROWS_MIX = "its pages would mix rows from before and after";
+
+// The nodes scans start from — the default start node and every per-label one — ascending and unique.  label_nodes: the host copy of
+// ls_nodes when the caller has fetched it already.
+static int collect_start_nodes(vs_index* ix, const char* what, std::vector<uint32_t>* starts, const uint32_t* label_nodes = nullptr) {
+    const size_t ns = ix->d.n_label_starts;
+    starts->assign(1 + ns, ix->d.default_start);
+    if (ns && label_nodes) memcpy(starts->data() + 1, label_nodes, ns * 4);
+    else if (ns) VS_HIP(hipMemcpy(starts->data() + 1, ix->ls_nodes, ns * 4, hipMemcpyDeviceToHost));
+    std::sort(starts->begin(), starts->end());
+    starts->erase(std::unique(starts->begin(), starts->end()), starts->end());
+    VS_REQUIRE(starts->back() < ix->d.n, "%s: start node %u of an index of %u nodes", what, starts->back(), ix->d.n);
+    return VS_OK;
+}
+
+// the label sets of n rows as a caller hands them over: CSR offsets from 0, at most 64 labels per row, each set ascending
+static int validate_label_csr(const char* what, const uint32_t* label_off, const int16_t* label_val, uint32_t n) {
+    VS_REQUIRE(label_off[0] == 0, "%s: label_off[0] must be 0", what);
+    for (uint32_t i = 0; i < n; ++i) {
+        VS_REQUIRE(label_off[i] <= label_off[i + 1], "%s: label_off must be non-decreasing", what);
+        VS_REQUIRE(label_off[i + 1] - label_off[i] <= 64, "%s: row %u carries more than 64 labels", what, i);
+        VS_REQUIRE(label_off[i + 1] == label_off[i] || label_val, "%s: label_val is NULL", what);
+        for (uint32_t j = label_off[i] + 1; j < label_off[i + 1]; ++j)
+            VS_REQUIRE(label_val[j - 1] < label_val[j], "%s: row %u: label set must be sorted and de-duplicated", what, i);
+    }
+    return VS_OK;
+}
+
+// What the default start node reaches (k_reach_sweep, one BFS level per sweep): mark[i] = 1 + the level of node i, 0 = not reached.
+// mark holds n + 8 bytes: the flags, then (4-byte aligned) the `changed` word.  *converged = false: more than 254 levels deep.
+static int reach_from_default_start(vs_index* ix, uint8_t* mark, bool* converged) {
+    hipStream_t st = ix->ctx->stream;
+    const uint32_t n = ix->d.n, R = ix->d.num_neighbors;
+    uint32_t* d_changed = reinterpret_cast<uint32_t*>(mark + (((size_t)n + 3) & ~(size_t)3));
+    const dim3 cgrid((unsigned)(((size_t)n * R + 255) / 256));
+    VS_HIP(hipMemsetAsync(mark, 0, (size_t)n + 8, st));
+    const uint8_t one = 1;
+    VS_HIP(hipMemcpyAsync(mark + ix->d.default_start, &one, 1, hipMemcpyHostToDevice, st));
+    *converged = false;
+    for (uint32_t level = 1; level < 255 && !*converged; ++level) {
+        uint32_t changed = 0;
+        VS_HIP(hipMemsetAsync(d_changed, 0, 4, st));
+        hipLaunchKernelGGL(k_reach_sweep, cgrid, dim3(256), 0, st, (const uint32_t*)ix->nbrs, ix->nbr_stride, R, n, mark, level, d_changed);
+        VS_HIP(hipGetLastError());
+        VS_HIP(hipMemcpyAsync(&changed, d_changed, 4, hipMemcpyDeviceToHost, st));
+        VS_HIP(hipStreamSynchronize(st));
+        *converged = changed == 0;
+    }
+    return VS_OK;
+}
+
+// the five vs_index_*_kernel_ms getters: what accumulated in acc[0 .. n), cleared on request
+static int read_kernel_ms(const char* what, vs_index* ix, double* acc, int n, double* ms, int reset) {
+    VS_REQUIRE(ix && ms, "%s: bad args", what);
+    for (int k = 0; k < n; ++k) {
+        ms[k] = acc[k];
+        if (reset) acc[k] = 0;
+    }
+    return VS_OK;
+}
+
+// the scratch of the batch machinery (non-owning: every buffer belongs to the DevScope of the call)
 struct BuildBufs {
     uint32_t *vis_ids = nullptr, *vis_d = nullptr, *vis_cnt = nullptr, *stats = nullptr, *status = nullptr;
     uint32_t* hash = nullptr;
@@ -929,22 +1013,16 @@ struct BuildBufs {
     void* cub_tmp = nullptr;
     size_t cub_bytes = 0;
     uint32_t *f_ghash = nullptr, *f_heap = nullptr, *f_pool = nullptr;  // fast-kernel overflow table / heap spill / pool counter
-    uint8_t* mark = nullptr;                                             // repair pass: node is reachable from the start node
     uint32_t *mate_ids = nullptr, *mate_ham = nullptr;                   // insert: [batch][c] mates of the batch's nodes
     uint32_t* anch = nullptr;                                            // insert: [rows of the call] anchored flags, then `changed`, then the mate-edge count
-    void free_all() {
-        void* ps[] = {vis_ids, vis_d, vis_cnt, stats, status, hash, heap_g, edge_q, edge_q_sorted, seg_start, nseg,
-                      edge_pd, edge_pd_sorted, cub_tmp, f_ghash, f_heap, f_pool, mark, mate_ids, mate_ham, anch};
-        for (void* p : ps)
-            if (p) (void)hipFree(p);
-    }
 };
 
 // The batch machinery shared by vs_build_graph and vs_index_insert: capacities and buffers of the build-mode search (init), and one
 // batch (run): searches for the new nodes b0 .. b0 + bn - 1 over the graph as it stands, their out-edges, the back-edges.
 struct BatchRunner {
     vs_index* ix = nullptr;
-    BuildBufs* Bp = nullptr;
+    DevScope* sc = nullptr;
+    BuildBufs B;
     hipStream_t st = nullptr;
     uint32_t R = 0, stride = 0, L = 0, batch_max = 0;
     float max_alpha = 1.0f;
@@ -963,12 +1041,14 @@ struct BatchRunner {
     // back-edges (sort, segment heads, k_build_backedges)
     uint32_t mates = 0;
     double ms[6] = {0, 0, 0, 0, 0, 0};
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    StageTimer tm;
+    const char* what = "";  // the entry point, for its error texts
 
     // n: the nodes the graph will have when the last batch is in (sizes the default batch and picks the dedup regime)
-    int init(vs_index* ix_, BuildBufs& B, uint32_t L_, float max_alpha_, uint32_t batch_max_, uint32_t n) {
+    int init(vs_index* ix_, DevScope& sc_, const char* what_, uint32_t L_, float max_alpha_, uint32_t batch_max_, uint32_t n) {
+        what = what_;
         ix = ix_;
-        Bp = &B;
+        sc = &sc_;
         vs_ctx* c = ix->ctx;
         st = c->stream;
         R = ix->d.num_neighbors;
@@ -1017,20 +1097,20 @@ struct BatchRunner {
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 
         const size_t bm = batch_max;
-        VS_HIP(hipMalloc(&B.vis_ids, bm * vmax * 4));
-        VS_HIP(hipMalloc(&B.vis_d, bm * vmax * 4));
-        VS_HIP(hipMalloc(&B.vis_cnt, bm * 4));
-        VS_HIP(hipMalloc(&B.stats, bm * ST_N * 4));
-        VS_HIP(hipMalloc(&B.status, bm * 4));
-        VS_HIP(hipMalloc(&B.edge_q, bm * R * 8));
-        VS_HIP(hipMalloc(&B.edge_q_sorted, bm * R * 8));
-        VS_HIP(hipMalloc(&B.edge_pd, bm * R * 8));
-        VS_HIP(hipMalloc(&B.edge_pd_sorted, bm * R * 8));
-        VS_HIP(hipMalloc(&B.seg_start, bm * R * 4));
-        VS_HIP(hipMalloc(&B.nseg, 4));
+        VS_TRY(sc->alloc(&B.vis_ids, bm * vmax * 4, what));
+        VS_TRY(sc->alloc(&B.vis_d, bm * vmax * 4, what));
+        VS_TRY(sc->alloc(&B.vis_cnt, bm * 4, what));
+        VS_TRY(sc->alloc(&B.stats, bm * ST_N * 4, what));
+        VS_TRY(sc->alloc(&B.status, bm * 4, what));
+        VS_TRY(sc->alloc(&B.edge_q, bm * R * 8, what));
+        VS_TRY(sc->alloc(&B.edge_q_sorted, bm * R * 8, what));
+        VS_TRY(sc->alloc(&B.edge_pd, bm * R * 8, what));
+        VS_TRY(sc->alloc(&B.edge_pd_sorted, bm * R * 8, what));
+        VS_TRY(sc->alloc(&B.seg_start, bm * R * 4, what));
+        VS_TRY(sc->alloc(&B.nseg, 4, what));
         VS_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, B.cub_bytes, B.edge_q, B.edge_q_sorted, B.edge_pd,
                                                   B.edge_pd_sorted, (int)(bm * R), 0, 64, st));
-        VS_HIP(hipMalloc(&B.cub_tmp, B.cub_bytes + 16));
+        VS_TRY(sc->alloc(&B.cub_tmp, B.cub_bytes + 16, what));
 
         // The searches of a batch run on the LDS-resident kernel (vs_search_fast.hip, BUILD variant); the general kernel only
         // re-runs the scans that outgrow it.  Same operating-point rule as for queries: dedup table in LDS for small graphs,
@@ -1056,30 +1136,18 @@ struct BatchRunner {
             f.build = 1;
             if (nbits >= (1ull << (32 - f.sb)) || fast_lds_bytes(ix, f) > 64 * 1024) use_fast = false;
             if (use_fast) {
-                VS_HIP(hipMalloc(&B.f_ghash, bm * f.gcap * 4));
-                VS_HIP(hipMalloc(&B.f_heap, bm * f.gstride * 4));
-                VS_HIP(hipMalloc(&B.f_pool, 64));
+                VS_TRY(sc->alloc(&B.f_ghash, bm * f.gcap * 4, what));
+                VS_TRY(sc->alloc(&B.f_heap, bm * f.gstride * 4, what));
+                VS_TRY(sc->alloc(&B.f_pool, 64, what));
             }
         }
-        return VS_OK;
-    }
-
-    void tick() {
-        if (ev[0]) (void)hipEventRecord(ev[0], st);
-    }
-    void tock(int which) {
-        if (!ev[0]) return;
-        float t = 0.f;
-        if (hipEventRecord(ev[1], st) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
-            hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess)
-            ms[which] += t;
+        return tm.start(*sc, c->profiling, ms, what);  // (vs_profile_enable: HIP-event time of the batch kernels)
     }
 
     // filtered: the pass from the label start nodes with the label filter (labeled sets only); otherwise from the default
     // start node.  A labeled set's unfiltered pass merges into the rows the filtered pass wrote.  with_mates (insert): the c
     // nearest nodes of the same batch join every node's candidates before pruning.
     int run(uint32_t b0, uint32_t bn, bool filtered, bool with_mates = false) {
-        BuildBufs& B = *Bp;
         const uint64_t* qcodes = ix->codes + (size_t)b0 * stride;
         // label keys of the searches = the new nodes' own label sets (CSR offsets are absolute into label_val)
         const int16_t* ql = filtered ? ix->label_val : nullptr;
@@ -1090,17 +1158,15 @@ struct BatchRunner {
         }
         for (int attempt = 0;; ++attempt) {
             if ((size_t)bn * hashcap * 4 > hash_alloc || !B.hash) {
-                if (B.hash) VS_HIP(hipFree(B.hash));
-                B.hash = nullptr;
+                sc->free(B.hash);
                 hash_alloc = (size_t)batch_max * hashcap * 4;
-                VS_HIP(hipMalloc(&B.hash, hash_alloc));
+                VS_TRY(sc->alloc(&B.hash, hash_alloc, what));
             }
             const size_t hg = hcap > hl ? hcap - hl : 0;
             if ((size_t)bn * hg * 8 > ids_alloc || !B.heap_g) {
-                if (B.heap_g) VS_HIP(hipFree(B.heap_g));
-                B.heap_g = nullptr;
+                sc->free(B.heap_g);
                 ids_alloc = std::max<size_t>((size_t)batch_max * hg * 8, 16);
-                VS_HIP(hipMalloc(&B.heap_g, ids_alloc));
+                VS_TRY(sc->alloc(&B.heap_g, ids_alloc, what));
             }
             SearchLaunch s;
             s.nq = bn;
@@ -1122,7 +1188,7 @@ struct BatchRunner {
             s.out_cnt = B.vis_cnt;
             s.stats = B.stats;
             s.status = B.status;
-            tick();
+            tm.tick();
             if (use_fast && attempt == 0) {
                 f.nq = bn;
                 f.hcap = std::max(std::min(hcap, f.hl + f.gstride - 2), f.hl);  // (the spill area was sized before the loop)
@@ -1144,7 +1210,7 @@ struct BatchRunner {
             // after the fast kernel (or a failed attempt) only the scans whose status is non-zero are (re)run
             s.only_failed = (use_fast || attempt > 0) ? 1u : 0u;
             VS_TRY(launch_search(ix, s, true));
-            tock(3);
+            tm.tock(3);
             std::vector<uint32_t> status(bn);
             VS_HIP(hipMemcpyAsync(status.data(), B.status, (size_t)bn * 4, hipMemcpyDeviceToHost, st));
             VS_HIP(hipStreamSynchronize(st));
@@ -1169,7 +1235,7 @@ struct BatchRunner {
         }
         if (with_mates && mates && bn > 1) {
             const uint32_t c = mates;
-            tick();
+            tm.tick();
             if (plain)
                 hipLaunchKernelGGL(k_batch_mates_plain, dim3((bn + MATESP_ROWS - 1) / MATESP_ROWS), dim3(WAVE), mates_plain_lds_bytes(c, pv.dim), st,
                                    pv, b0, bn, c, B.mate_ids, B.mate_ham);
@@ -1178,15 +1244,15 @@ struct BatchRunner {
                                    stride, bn, c, B.mate_ids, B.mate_ham, filtered ? ix->label_off : nullptr,
                                    filtered ? ix->label_val : nullptr, b0);
             VS_HIP(hipGetLastError());
-            tock(0);
-            tick();
+            tm.tock(0);
+            tm.tick();
             hipLaunchKernelGGL(k_insert_merge_mates, dim3(bn), dim3(WAVE), ((size_t)vmax + 64) * 8, st, b0, bn, B.vis_ids, B.vis_d,
                                B.vis_cnt, vmax, B.mate_ids, B.mate_ham, c);
             VS_HIP(hipGetLastError());
-            tock(1);
+            tm.tock(1);
         }
         // out-edges of the new nodes + back-edge requests
-        tick();
+        tm.tick();
         if (labeled)
             hipLaunchKernelGGL(k_build_prune_merge, dim3(bn), dim3(WAVE), lds_merge, st, ix->codes, stride, ix->nbrs,
                                ix->nbr_stride, R, max_alpha, b0, bn, B.vis_ids, B.vis_d, B.vis_cnt, vmax, mcap, use_lds_merge,
@@ -1199,8 +1265,8 @@ struct BatchRunner {
                                ix->nbr_stride, R, max_alpha, b0, bn, B.vis_ids, B.vis_d, B.vis_cnt, vmax, use_lds_new,
                                B.edge_q, B.edge_pd, pv);
         VS_HIP(hipGetLastError());
-        tock(4);
-        tick();
+        tm.tock(4);
+        tm.tick();
         const uint32_t ne = bn * R;
         size_t tmp_bytes = B.cub_bytes;
         VS_HIP(hipcub::DeviceRadixSort::SortPairs(B.cub_tmp, tmp_bytes, B.edge_q, B.edge_q_sorted, B.edge_pd,
@@ -1218,7 +1284,7 @@ struct BatchRunner {
                                ix->nbr_stride, R, max_alpha, B.edge_q_sorted, B.edge_pd_sorted, ne, B.seg_start, B.nseg, cmax,
                                use_lds_back, labeled ? ix->label_off : nullptr, labeled ? ix->label_val : nullptr, pv);
         VS_HIP(hipGetLastError());
-        tock(5);
+        tm.tock(5);
         return VS_OK;
     }
 };
@@ -1228,37 +1294,26 @@ struct BatchRunner {
 // cls (vs_index_consolidate_deletes only; nullptr: every node counts, as always): per node 0 = live, 1 = a tombstone the consolidation
 // dropped from the graph, 2 = a tombstone kept as a start node.  A dropped tombstone is not "lost": it is meant to be unreachable and
 // is never handed an in-edge; build_unreachable then counts the LIVE nodes the sweep did not reach.
-static int repair_graph(vs_index* ix, BuildBufs& B, const uint8_t* cls = nullptr) {
+static int repair_graph(vs_index* ix, DevScope& sc, const uint8_t* cls = nullptr) {
+    const char* what = "vs_build_graph (repair)";
     hipStream_t st = ix->ctx->stream;
     const uint32_t n = ix->d.n, R = ix->d.num_neighbors;
     if (n <= 2) return VS_OK;  // (nothing a sweep could find)
     ix->build_unreachable = 0;
-    VS_HIP(hipMalloc(&B.mark, (size_t)n + 8));  // n flags, then (4-byte aligned) the `changed` word
-    uint32_t* d_changed = reinterpret_cast<uint32_t*>(B.mark + (((size_t)n + 3) & ~(size_t)3));
+    uint8_t* mark = nullptr;  // node is reachable from the start node
+    VS_TRY(sc.alloc(&mark, (size_t)n + 8, what));
     std::vector<uint8_t> reached(n);
     std::vector<uint32_t> lost, indeg, row0(R);
     const size_t cells = (size_t)n * R;
     const dim3 cgrid((unsigned)((cells + 255) / 256));
-    const uint32_t start = ix->d.default_start;
     for (int round = 0; round < 8; ++round) {
-        VS_HIP(hipMemsetAsync(B.mark, 0, (size_t)n + 8, st));
-        const uint8_t one = 1;
-        VS_HIP(hipMemcpyAsync(B.mark + start, &one, 1, hipMemcpyHostToDevice, st));
         bool converged = false;
-        for (uint32_t level = 1; level < 255 && !converged; ++level) {  // one BFS level per sweep
-            uint32_t changed = 0;
-            VS_HIP(hipMemsetAsync(d_changed, 0, 4, st));
-            hipLaunchKernelGGL(k_reach_sweep, cgrid, dim3(256), 0, st, ix->nbrs, ix->nbr_stride, R, n, B.mark, level, d_changed);
-            VS_HIP(hipGetLastError());
-            VS_HIP(hipMemcpyAsync(&changed, d_changed, 4, hipMemcpyDeviceToHost, st));
-            VS_HIP(hipStreamSynchronize(st));
-            converged = changed == 0;
-        }
+        VS_TRY(reach_from_default_start(ix, mark, &converged));
         if (!converged) {  // more than 254 levels deep: not a graph this pass can judge
             ix->build_unreachable = 0xFFFFFFFFu;
             break;
         }
-        VS_HIP(hipMemcpyAsync(reached.data(), B.mark, n, hipMemcpyDeviceToHost, st));
+        VS_HIP(hipMemcpyAsync(reached.data(), mark, n, hipMemcpyDeviceToHost, st));
         VS_HIP(hipStreamSynchronize(st));
         lost.clear();
         uint32_t lost_live = 0;
@@ -1275,43 +1330,35 @@ static int repair_graph(vs_index* ix, BuildBufs& B, const uint8_t* cls = nullptr
         // counting every reachable source would let two nodes that only reach each other vouch for one another).  Rare
         // (none on the bench corpora), so this runs on the host, in node order; the sweep of the next round re-checks.
         uint32_t* d_indeg = nullptr;
-        VS_HIP(hipMalloc(&d_indeg, (size_t)n * 4));
+        VS_TRY(sc.alloc(&d_indeg, (size_t)n * 4, what));
         indeg.assign(n, 0);
-        int r = VS_OK;
-        auto hip_ok = [&](hipError_t e) {
-            if (r == VS_OK && e != hipSuccess) {
-                vs_set_error("vs_build_graph (repair): %s", hipGetErrorString(e));
-                r = VS_ERR_HIP;
-            }
-        };
-        hip_ok(hipMemsetAsync(d_indeg, 0, (size_t)n * 4, st));
-        hipLaunchKernelGGL(k_count_reached_sources, cgrid, dim3(256), 0, st, ix->nbrs, ix->nbr_stride, R, n, B.mark, d_indeg);
-        hip_ok(hipGetLastError());
-        hip_ok(hipMemcpyAsync(indeg.data(), d_indeg, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        hip_ok(hipStreamSynchronize(st));
-        (void)hipFree(d_indeg);
+        VS_HIP(hipMemsetAsync(d_indeg, 0, (size_t)n * 4, st));
+        hipLaunchKernelGGL(k_count_reached_sources, cgrid, dim3(256), 0, st, ix->nbrs, ix->nbr_stride, R, n, mark, d_indeg);
+        VS_HIP(hipGetLastError());
+        VS_HIP(hipMemcpyAsync(indeg.data(), d_indeg, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        VS_HIP(hipStreamSynchronize(st));
+        sc.free(d_indeg);
         // the lists of the lost nodes, so that what becomes reachable through a node that was just given a way in is known
         // without another sweep
         std::vector<uint32_t> lrows(lost.size() * (size_t)R), lidx(n, 0xFFFFFFFFu), stack, level(n);
         for (uint32_t i = 0; i < n; ++i) level[i] = reached[i];  // 1 + BFS level (0: not reached); grows past 255 on the host
-        for (size_t oi = 0; oi < lost.size() && r == VS_OK; ++oi) {
+        for (size_t oi = 0; oi < lost.size(); ++oi) {
             lidx[lost[oi]] = (uint32_t)oi;
-            hip_ok(hipMemcpy(&lrows[oi * R], ix->nbrs + (size_t)lost[oi] * ix->nbr_stride, (size_t)R * 4, hipMemcpyDeviceToHost));
+            VS_HIP(hipMemcpy(&lrows[oi * R], ix->nbrs + (size_t)lost[oi] * ix->nbr_stride, (size_t)R * 4, hipMemcpyDeviceToHost));
         }
-        for (bool progress = true; progress && r == VS_OK;) {
+        for (bool progress = true; progress;) {
             progress = false;
-            for (size_t oi = 0; oi < lost.size() && r == VS_OK; ++oi) {
+            for (size_t oi = 0; oi < lost.size(); ++oi) {
                 const uint32_t x = lost[oi];
                 if (reached[x]) continue;
                 const uint32_t* rowx = &lrows[oi * R];
                 bool placed = false;
-                for (uint32_t c = 0; c < R && r == VS_OK && !placed && rowx[c] != VS_INVALID_NODE; ++c) {  // closest first
+                for (uint32_t c = 0; c < R && !placed && rowx[c] != VS_INVALID_NODE; ++c) {  // closest first
                     const uint32_t n0 = rowx[c];
                     if (!reached[n0]) continue;
                     uint32_t* rown = lidx[n0] != 0xFFFFFFFFu ? &lrows[(size_t)lidx[n0] * R] : row0.data();
                     if (rown == row0.data())
-                        hip_ok(hipMemcpy(row0.data(), ix->nbrs + (size_t)n0 * ix->nbr_stride, (size_t)R * 4, hipMemcpyDeviceToHost));
-                    if (r != VS_OK) break;
+                        VS_HIP(hipMemcpy(row0.data(), ix->nbrs + (size_t)n0 * ix->nbr_stride, (size_t)R * 4, hipMemcpyDeviceToHost));
                     int slot = -1;
                     for (uint32_t t = 0; t < R && slot < 0; ++t)
                         if (rown[t] == VS_INVALID_NODE) slot = (int)t;
@@ -1326,7 +1373,7 @@ static int repair_graph(vs_index* ix, BuildBufs& B, const uint8_t* cls = nullptr
                     level[x] = level[n0] + 1;
                     indeg[x]++;
                     placed = true;
-                    hip_ok(hipMemcpy(ix->nbrs + (size_t)n0 * ix->nbr_stride, rown, (size_t)R * 4, hipMemcpyHostToDevice));
+                    VS_HIP(hipMemcpy(ix->nbrs + (size_t)n0 * ix->nbr_stride, rown, (size_t)R * 4, hipMemcpyHostToDevice));
                 }
                 if (!placed) continue;
                 progress = true;
@@ -1351,12 +1398,11 @@ static int repair_graph(vs_index* ix, BuildBufs& B, const uint8_t* cls = nullptr
                 }
             }
         }
-        VS_TRY(r);
     }
     return VS_OK;
 }
 
-static int build_graph_impl(vs_index* ix, uint32_t L, double max_alpha_d, uint32_t batch_max, BuildBufs& B) {
+static int build_graph_impl(vs_index* ix, uint32_t L, double max_alpha_d, uint32_t batch_max, DevScope& sc, BatchRunner& br) {
     vs_ctx* c = ix->ctx;
     hipStream_t st = c->stream;
     const uint32_t n = ix->d.n;
@@ -1391,24 +1437,10 @@ static int build_graph_impl(vs_index* ix, uint32_t L, double max_alpha_d, uint32
         VS_TRY(launch_row_norms(ix));
         VS_TRY(launch_slice_norms_range(ix, 0, n));
     }
-    BatchRunner br;
-    VS_TRY(br.init(ix, B, L, (float)max_alpha_d, batch_max, n));
+    VS_TRY(br.init(ix, sc, "vs_build_graph", L, (float)max_alpha_d, batch_max, n));
     batch_max = br.batch_max;
     VS_HIP(hipMemsetAsync(ix->nbrs, 0xFF, (size_t)n * ix->nbr_stride * 4, st));
     ix->d.default_start = 0;
-    struct Events {  // (vs_profile_enable: HIP-event time of the batch kernels, vs_index_build_kernel_ms)
-        BatchRunner& br;
-        vs_index* ix;
-        ~Events() {
-            for (int k = 0; k < 3; ++k) ix->build_ms[k] += br.ms[3 + k];
-            if (br.ev[0]) (void)hipEventDestroy(br.ev[0]);
-            if (br.ev[1]) (void)hipEventDestroy(br.ev[1]);
-        }
-    } events{br, ix};
-    if (c->profiling) {
-        VS_HIP(hipEventCreate(&br.ev[0]));
-        VS_HIP(hipEventCreate(&br.ev[1]));
-    }
 
     uint32_t b0 = 1;  // node 0 is the start node and has no one to link to yet
     uint32_t bsz = 1;
@@ -1422,7 +1454,7 @@ static int build_graph_impl(vs_index* ix, uint32_t L, double max_alpha_d, uint32
     VS_HIP(hipStreamSynchronize(st));
 
     const char* rep_env = vs_opt_get("VS_BUILD_REPAIR");
-    if (!(rep_env && *rep_env == '0')) VS_TRY(repair_graph(ix, B));
+    if (!(rep_env && *rep_env == '0')) VS_TRY(repair_graph(ix, sc));
     return VS_OK;
 }
 
@@ -1436,17 +1468,17 @@ static int vs_build_graph_impl(vs_index* ix, uint32_t search_list_size, double m
         PlainVecs pv;
         VS_TRY(plain_pair_args(ix, "vs_build_graph", &pv));
         VS_REQUIRE(!ix->label_off, "vs_build_graph: Plain storage does not support label filters");
-        if (ix->ws.pending) {
-            vs_set_error("vs_build_graph: a batch of this handle is in flight (vs_search_batch_dev_finish first)");
-            return VS_ERR_STATE;
-        }
+        VS_TRY(require_no_batch(ix, "vs_build_graph"));
     }
     VS_HIP(hipSetDevice(ix->ctx->device));
-    BuildBufs B;
     ix->nbr_mask_valid = false;  // (the neighbor lists are about to change: what was derived from them is stale)
-    int r = build_graph_impl(ix, search_list_size, max_alpha, batch_max, B);
-    (void)hipStreamSynchronize(ix->ctx->stream);
-    B.free_all();
+    int r;
+    {
+        DevScope sc(ix->ctx->stream);
+        BatchRunner br;
+        r = build_graph_impl(ix, search_list_size, max_alpha, batch_max, sc, br);
+        for (int k = 0; k < 3; ++k) ix->build_ms[k] += br.ms[3 + k];  // (vs_index_build_kernel_ms)
+    }
     // the scan kernels rely on every neighbor list naming a node at most once (as vs_index_upload checks for staged
     // indexes): a list that does not is a defect of this builder, not something to search on
     if (r == VS_OK) r = vs_validate_graph(ix);
@@ -1466,12 +1498,11 @@ static int vs_index_repair_impl(vs_index* ix, uint32_t* unreachable) {
     VS_HIP(hipSetDevice(ix->ctx->device));
     ix->build_unreachable = 0;
     if (ix->d.default_start != VS_INVALID_NODE) {
-        BuildBufs B;
         ix->nbr_mask_valid = false;
-        int r = repair_graph(ix, B);
-        (void)hipStreamSynchronize(ix->ctx->stream);
-        B.free_all();
-        VS_TRY(r);
+        {
+            DevScope sc(ix->ctx->stream);
+            VS_TRY(repair_graph(ix, sc));
+        }
         VS_TRY(vs_validate_graph(ix));
     }
     if (unreachable) *unreachable = ix->build_unreachable;
@@ -1493,44 +1524,24 @@ static int vs_batch_mates_impl(vs_index* ix, const uint64_t* codes, const uint32
     uint64_t* d_codes = nullptr;
     uint32_t *d_out = nullptr, *d_off = nullptr;  // ids, then Hamming distances; the rows' label sets (filtered form)
     int16_t* d_val = nullptr;
-    int r = VS_OK;
+    if (label_off) VS_TRY(validate_label_csr("vs_batch_mates_filtered", label_off, label_val, n));
+    DevScope sc(ctx->stream);
+    VS_TRY(sc.alloc(&d_codes, (size_t)n * stride * 8, "vs_batch_mates"));
+    VS_TRY(sc.alloc(&d_out, (size_t)n * c * 8, "vs_batch_mates"));
+    VS_TRY(vs_upload_rows(ctx, d_codes, stride * 8ull, codes, ix->d.words * 8ull, ix->d.words * 8ull, n));
     if (label_off) {
-        VS_REQUIRE(label_off[0] == 0, "vs_batch_mates_filtered: label_off[0] must be 0");
-        for (uint32_t i = 0; i < n; ++i) {
-            VS_REQUIRE(label_off[i] <= label_off[i + 1], "vs_batch_mates_filtered: label_off must be non-decreasing");
-            VS_REQUIRE(label_off[i + 1] - label_off[i] <= 64, "vs_batch_mates_filtered: row %u carries more than 64 labels", i);
-            VS_REQUIRE(label_off[i + 1] == label_off[i] || label_val, "vs_batch_mates_filtered: label_val is NULL");
-            for (uint32_t j = label_off[i] + 1; j < label_off[i + 1]; ++j)
-                VS_REQUIRE(label_val[j - 1] < label_val[j], "vs_batch_mates_filtered: row %u: label set must be sorted and de-duplicated", i);
-        }
+        VS_TRY(sc.alloc(&d_off, ((size_t)n + 1) * 4, "vs_batch_mates"));
+        VS_TRY(sc.alloc(&d_val, std::max<size_t>(label_off[n], 1) * 2, "vs_batch_mates"));
+        VS_TRY(vs_dev_upload(ctx, d_off, label_off, ((size_t)n + 1) * 4));
+        if (label_off[n]) VS_TRY(vs_dev_upload(ctx, d_val, label_val, (size_t)label_off[n] * 2));
     }
-    auto hip_ok = [&](hipError_t e) {
-        if (r == VS_OK && e != hipSuccess) {
-            vs_set_error("vs_batch_mates: %s", hipGetErrorString(e));
-            r = e == hipErrorOutOfMemory ? VS_ERR_OOM : VS_ERR_HIP;
-        }
-    };
-    hip_ok(hipMalloc(&d_codes, (size_t)n * stride * 8));
-    if (r == VS_OK) hip_ok(hipMalloc(&d_out, (size_t)n * c * 8));
-    if (r == VS_OK) r = vs_upload_rows(ctx, d_codes, stride * 8ull, codes, ix->d.words * 8ull, ix->d.words * 8ull, n);
-    if (r == VS_OK && label_off) {
-        hip_ok(hipMalloc(&d_off, ((size_t)n + 1) * 4));
-        if (r == VS_OK) hip_ok(hipMalloc(&d_val, std::max<size_t>(label_off[n], 1) * 2));
-        if (r == VS_OK) r = vs_dev_upload(ctx, d_off, label_off, ((size_t)n + 1) * 4);
-        if (r == VS_OK && label_off[n]) r = vs_dev_upload(ctx, d_val, label_val, (size_t)label_off[n] * 2);
-    }
-    if (r == VS_OK) {
-        hipLaunchKernelGGL(k_batch_mates, dim3((n + 63) / 64), dim3(WAVE), mates_lds_bytes(c), ctx->stream, d_codes, stride, n, c, d_out,
-                           d_out + (size_t)n * c, (const uint32_t*)d_off, (const int16_t*)d_val, 0u);
-        hip_ok(hipGetLastError());
-    }
-    if (r == VS_OK) r = vs_dev_download(ctx, out_ids, d_out, (size_t)n * c * 4);
-    if (r == VS_OK && out_ham) r = vs_dev_download(ctx, out_ham, d_out + (size_t)n * c, (size_t)n * c * 4);
-    if (d_codes) (void)hipFree(d_codes);
-    if (d_out) (void)hipFree(d_out);
-    if (d_off) (void)hipFree(d_off);
-    if (d_val) (void)hipFree(d_val);
-    return r;
+    hipLaunchKernelGGL(k_batch_mates, dim3((n + 63) / 64), dim3(WAVE), mates_lds_bytes(c), ctx->stream, d_codes, stride, n, c, d_out,
+                       d_out + (size_t)n * c, (const uint32_t*)d_off, (const int16_t*)d_val, 0u);
+    VS_HIP(hipGetLastError());
+    VS_TRY(vs_dev_download(ctx, out_ids, d_out, (size_t)n * c * 4));
+    if (out_ham) VS_TRY(vs_dev_download(ctx, out_ham, d_out + (size_t)n * c, (size_t)n * c * 4));
+    sc.drained();  // (vs_dev_download returns when the bytes are on the host)
+    return VS_OK;
 }
 extern "C" int vs_batch_mates(vs_index* ix, const uint64_t* codes, uint32_t n, uint32_t c, uint32_t* out_ids, uint32_t* out_ham) {
     return vs_guard("vs_batch_mates", [&] { return vs_batch_mates_impl(ix, codes, nullptr, nullptr, n, c, out_ids, out_ham); });
@@ -1557,30 +1568,25 @@ static int vs_batch_mates_plain_impl(vs_index* ix, uint32_t first_node, uint32_t
     const size_t lds = mates_plain_lds_bytes(c, pv.dim);
     VS_REQUIRE(lds <= 160 * 1024, "vs_batch_mates_plain: %u dimensions do not fit LDS", pv.dim);
     VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_batch_mates_plain), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    DevScope sc(ctx->stream);
     uint32_t* d_out = nullptr;  // ids, then keys
-    VS_HIP(hipMalloc(&d_out, (size_t)n * c * 8));
-    int r = VS_OK;
+    VS_TRY(sc.alloc(&d_out, (size_t)n * c * 8, "vs_batch_mates_plain"));
     hipLaunchKernelGGL(k_batch_mates_plain, dim3((n + MATESP_ROWS - 1) / MATESP_ROWS), dim3(WAVE), lds, ctx->stream, pv, first_node, n, c, d_out,
                        d_out + (size_t)n * c);
-    if (hipGetLastError() != hipSuccess) {
-        vs_set_error("vs_batch_mates_plain: launch failed");
-        r = VS_ERR_HIP;
-    }
-    if (r == VS_OK) r = vs_dev_download(ctx, out_ids, d_out, (size_t)n * c * 4);
-    if (r == VS_OK && out_dist) {
-        r = vs_dev_download(ctx, out_dist, d_out + (size_t)n * c, (size_t)n * c * 4);
+    VS_HIP(hipGetLastError());
+    VS_TRY(vs_dev_download(ctx, out_ids, d_out, (size_t)n * c * 4));
+    if (out_dist) {
+        VS_TRY(vs_dev_download(ctx, out_dist, d_out + (size_t)n * c, (size_t)n * c * 4));
         // keys -> the f32 distances, bit for bit (the total_cmp image undoes itself); the padding keeps 0xFFFFFFFF
         uint32_t* k = reinterpret_cast<uint32_t*>(out_dist);
-        for (size_t i = 0; r == VS_OK && i < (size_t)n * c; ++i)
+        for (size_t i = 0; i < (size_t)n * c; ++i)
             if (out_ids[i] != VS_INVALID_NODE) {
                 uint32_t b = k[i] ^ 0x80000000u;
                 b ^= (uint32_t)((int32_t)b >> 31) >> 1;
                 k[i] = b;
             }
     }
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_out);
-    return r;
+    return VS_OK;
 }
 extern "C" int vs_batch_mates_plain(vs_index* ix, uint32_t first_node, uint32_t n, uint32_t c, uint32_t* out_ids, float* out_dist) {
     return vs_guard("vs_batch_mates_plain", [&] { return vs_batch_mates_plain_impl(ix, first_node, n, c, out_ids, out_dist); });
@@ -1610,26 +1616,18 @@ static int vs_prune_plain_impl(vs_index* ix, const uint32_t* points, const uint3
     vs_ctx* ctx = ix->ctx;
     VS_HIP(hipSetDevice(ctx->device));
     VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_prune_plain), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    DevScope sc(ctx->stream);
     uint32_t* d_buf = nullptr;  // points | cand_off | cand_ids | out_len | out_rows
     const size_t words = (size_t)np + (np + 1) + std::max<uint32_t>(total, 1) + np + (size_t)np * R;
-    VS_HIP(hipMalloc(&d_buf, words * 4));
+    VS_TRY(sc.alloc(&d_buf, words * 4, "vs_prune_plain"));
     uint32_t *d_points = d_buf, *d_off = d_points + np, *d_ids = d_off + np + 1, *d_len = d_ids + std::max<uint32_t>(total, 1), *d_rows = d_len + np;
-    int r = vs_dev_upload(ctx, d_points, points, (size_t)np * 4);
-    if (r == VS_OK) r = vs_dev_upload(ctx, d_off, cand_off, ((size_t)np + 1) * 4);
-    if (r == VS_OK && total) r = vs_dev_upload(ctx, d_ids, cand_ids, (size_t)total * 4);
-    if (r == VS_OK) {
-        hipLaunchKernelGGL(k_prune_plain, dim3(np), dim3(WAVE), lds, ctx->stream, pv, R, (float)max_alpha, d_points, d_off, d_ids, np, cap, d_rows,
-                           d_len);
-        if (hipGetLastError() != hipSuccess) {
-            vs_set_error("vs_prune_plain: launch failed");
-            r = VS_ERR_HIP;
-        }
-    }
-    if (r == VS_OK) r = vs_dev_download(ctx, out_len, d_len, (size_t)np * 4);
-    if (r == VS_OK) r = vs_dev_download(ctx, out_rows, d_rows, (size_t)np * R * 4);
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_buf);
-    return r;
+    VS_TRY(vs_dev_upload(ctx, d_points, points, (size_t)np * 4));
+    VS_TRY(vs_dev_upload(ctx, d_off, cand_off, ((size_t)np + 1) * 4));
+    if (total) VS_TRY(vs_dev_upload(ctx, d_ids, cand_ids, (size_t)total * 4));
+    hipLaunchKernelGGL(k_prune_plain, dim3(np), dim3(WAVE), lds, ctx->stream, pv, R, (float)max_alpha, d_points, d_off, d_ids, np, cap, d_rows, d_len);
+    VS_HIP(hipGetLastError());
+    VS_TRY(vs_dev_download(ctx, out_len, d_len, (size_t)np * 4));
+    return vs_dev_download(ctx, out_rows, d_rows, (size_t)np * R * 4);
 }
 extern "C" int vs_prune_plain(vs_index* ix, const uint32_t* points, const uint32_t* cand_off, const uint32_t* cand_ids, uint32_t np,
                               double max_alpha, uint32_t* out_rows, uint32_t* out_len) {
@@ -1645,7 +1643,7 @@ extern "C" int vs_prune_plain(vs_index* ix, const uint32_t* points, const uint32
 static int anchor_range(BatchRunner& br, uint32_t r0, uint32_t rn, bool count_mates, uint32_t* mate_edges, uint32_t* placed,
                         uint32_t* left) {
     vs_index* ix = br.ix;
-    BuildBufs& B = *br.Bp;
+    BuildBufs& B = br.B;
     hipStream_t st = br.st;
     const uint32_t R = br.R, ns = ix->nbr_stride;
     uint32_t* d_changed = B.anch + rn;
@@ -1658,7 +1656,7 @@ static int anchor_range(BatchRunner& br, uint32_t r0, uint32_t rn, bool count_ma
     *left = 0;
     for (int sweep = 0; sweep <= 8; ++sweep) {  // (the ninth pass only recomputes: *left is what the final graph shows)
         VS_HIP(hipMemsetAsync(B.anch, 0, ((size_t)rn + 2) * 4, st));
-        br.tick();
+        br.tm.tick();
         for (uint32_t round = 0; round <= rn; ++round) {  // (a round that anchors nobody ends it; rn rounds is the longest chain)
             uint32_t changed = 0;
             VS_HIP(hipMemsetAsync(d_changed, 0, 4, st));
@@ -1669,7 +1667,7 @@ static int anchor_range(BatchRunner& br, uint32_t r0, uint32_t rn, bool count_ma
             VS_HIP(hipStreamSynchronize(st));
             if (!changed) break;
         }
-        br.tock(2);
+        br.tm.tock(2);
         VS_HIP(hipMemcpy(anch.data(), B.anch, (size_t)rn * 4, hipMemcpyDeviceToHost));
         if (count_mates && sweep == 0) {
             uint32_t m = 0;
@@ -1727,6 +1725,44 @@ static int anchor_range(BatchRunner& br, uint32_t r0, uint32_t rn, bool count_ma
     return VS_OK;
 }
 
+// the batches of one vs_index_insert call over the staged rows n_old .. n - 1, then the anchoring rule over all of them
+static int insert_link_rows(vs_index* ix, DevScope& sc, BatchRunner& br, uint32_t L, double max_alpha, uint32_t batch_max, uint32_t n_old,
+                            uint32_t n_new, bool new_label, vs_insert_stats& s) {
+    const char* what = "vs_index_insert";
+    const uint32_t n = n_old + n_new;
+    const bool labeled = ix->label_off != nullptr;
+    // (the buffers are sized by the batch: a one-row call must not allocate what a 65 536-row batch needs)
+    if (batch_max == 0) batch_max = std::min<uint32_t>(65536, std::max<uint32_t>(1024, n / 64));
+    batch_max = std::max(1u, std::min(std::min<uint32_t>(batch_max, 65536), n_new));
+    VS_TRY(br.init(ix, sc, what, L, (float)max_alpha, batch_max, n));
+    br.mates = std::min<uint32_t>(env_u32("VS_INSERT_MATES", 16), 64);
+    const uint32_t bm = std::min(br.batch_max, n_new);
+    if (br.mates) {
+        VS_TRY(sc.alloc(&br.B.mate_ids, (size_t)bm * br.mates * 4, what));
+        VS_TRY(sc.alloc(&br.B.mate_ham, (size_t)bm * br.mates * 4, what));
+    }
+    VS_TRY(sc.alloc(&br.B.anch, ((size_t)n_new + 2) * 4, what));
+    // batches as in vs_build_graph: none is larger than the graph it searches (node 0 of an empty index has no one to link to)
+    // For a label the call is the first to bring, the graph under that label's filter IS empty: the batches then double from one
+    // row, as vs_build_graph's do, so that the label's carriers find the ones before them.
+    uint32_t b0 = std::max(n_old, 1u), bsz = new_label ? 1u : br.batch_max;
+    while (b0 < n) {
+        const uint32_t bn = std::min(std::min(std::min(br.batch_max, bsz), b0), n - b0);
+        if (bsz < br.batch_max) bsz = std::min(br.batch_max, bsz * 2);
+        s.batches++;
+        s.orphans_left = 0;
+        if (labeled) VS_TRY(br.run(b0, bn, true, true));  // Graph::insert: first with the label filter (mates: the batch's rows it admits) ...
+        VS_TRY(br.run(b0, bn, false, true));              // ... then from the default start node, the batch's mates among the candidates
+        VS_TRY(anchor_range(br, b0, bn, true, &s.mate_edges, &s.orphans_placed, &s.orphans_left));
+        b0 += bn;
+    }
+    // later batches re-prune rows that anchored the earlier ones: the rule once more over every row of the call, against the graph
+    // as it was before the call
+    // (node 0 of an index that was empty is the entry point itself)
+    if (s.batches > 1) VS_TRY(anchor_range(br, std::max(n_old, 1u), n - std::max(n_old, 1u), false, &s.mate_edges, &s.orphans_placed, &s.orphans_left));
+    return VS_OK;
+}
+
 static int index_insert_impl(vs_index* ix, const float* vectors, bool vectors_on_device, const uint64_t* heap_tids,
                              const uint32_t* label_off, const int16_t* label_val, uint32_t n_new, uint32_t L, double max_alpha,
                              uint32_t batch_max, vs_insert_stats* out) {
@@ -1754,30 +1790,17 @@ static int index_insert_impl(vs_index* ix, const float* vectors, bool vectors_on
     const bool labeled = ix->label_off != nullptr;
     VS_REQUIRE(labeled == (label_off != nullptr), labeled ? "%s: the index is labeled, the rows carry no label sets" : "%s: label sets for an index without labels", what);
     if (labeled && n_new) {
-        VS_REQUIRE(label_off[0] == 0, "%s: label_off[0] must be 0", what);
-        for (uint32_t i = 0; i < n_new; ++i) {
-            VS_REQUIRE(label_off[i] <= label_off[i + 1], "%s: label_off must be non-decreasing", what);
-            VS_REQUIRE(label_off[i + 1] - label_off[i] <= 64, "%s: row %u carries more than 64 labels", what, i);
-            VS_REQUIRE(label_off[i + 1] == label_off[i] || label_val, "%s: label_val is NULL", what);
-            for (uint32_t j = label_off[i] + 1; j < label_off[i + 1]; ++j)
-                VS_REQUIRE(label_val[j - 1] < label_val[j], "%s: row %u: label set must be sorted and de-duplicated", what, i);
-        }
+        VS_TRY(validate_label_csr(what, label_off, label_val, n_new));
         VS_REQUIRE(ix->n_label_vals + label_off[n_new] < (1ull << 32), "%s: more than 2^32 label values", what);
     }
-    auto state_error = [&](const char* msg) {
-        vs_set_error("%s: %s", what, msg);
+    if (!plain && ix->count == 0) {
+        vs_set_error("%s: the quantizer is untrained (vs_sbq_train / vs_index_set_quantizer first; an insert never trains)", what);
         return VS_ERR_STATE;
-    };
-    if (!plain && ix->count == 0) return state_error("the quantizer is untrained (vs_sbq_train / vs_index_set_quantizer first; an insert never trains)");
-    if (ix->ws.pending) return state_error("a batch of this handle is in flight (vs_search_batch_dev_finish first)");
-    // an insert may move every array an open writer (vs_pages_out_open / _open_plain) holds pointers into
-    if (vs_index_open_writers(ix) > 0)
-        return state_error("a vs_pages_out writer of this index is open (its layout and array pointers were fixed at open; vs_pages_out_close first)");
-    if (ix->visible && ix->visible != ix->visible_own) {
-        bool ours = false;
-        for (const uint8_t* sp : ix->snap) ours |= sp == ix->visible;
-        if (!ours) return state_error("a caller-owned device visibility mask is in force and cannot be grown by the library (clear or replace it)");
     }
+    // an insert may move every array an open writer (vs_pages_out_open / _open_plain) holds pointers into
+    VS_TRY(require_no_batch(ix, what));
+    VS_TRY(require_no_writer(ix, what, "its layout and array pointers were fixed at open"));
+    VS_TRY(require_own_mask(ix, what, "grown"));
     if (n_new == 0) {
         if (out) out->first_node = n_old;
         return VS_OK;
@@ -1793,19 +1816,14 @@ static int index_insert_impl(vs_index* ix, const float* vectors, bool vectors_on
         grew = 1;
     }
     // the label CSR of the grown set (the only array that is not sized by rows): built aside, swapped in when everything else is staged
+    DevScope sc(st);
     int16_t* new_val = nullptr;
     const uint64_t old_vals = ix->n_label_vals, add_vals = labeled ? label_off[n_new] : 0;
     if (labeled && add_vals) {
-        VS_HIP(hipMalloc(&new_val, (old_vals + add_vals) * 2));
-        int r = VS_OK;
-        if (old_vals && hipMemcpyAsync(new_val, ix->label_val, old_vals * 2, hipMemcpyDeviceToDevice, st) != hipSuccess) r = VS_ERR_HIP;
-        if (r == VS_OK && hipStreamSynchronize(st) != hipSuccess) r = VS_ERR_HIP;
-        if (r == VS_OK) r = vs_dev_upload(c, new_val + old_vals, label_val, add_vals * 2);
-        if (r != VS_OK) {
-            (void)hipFree(new_val);
-            if (r == VS_ERR_HIP) vs_set_error("%s: staging the label sets failed", what);
-            return r;
-        }
+        VS_TRY(sc.alloc(&new_val, (old_vals + add_vals) * 2, what));
+        if (old_vals) VS_HIP(hipMemcpyAsync(new_val, ix->label_val, old_vals * 2, hipMemcpyDeviceToDevice, st));
+        VS_HIP(hipStreamSynchronize(st));
+        VS_TRY(vs_dev_upload(c, new_val + old_vals, label_val, add_vals * 2));
     }
     // stage the rows: vectors (device rows are vec_stride floats, zero padded), heap tids, empty neighbor lists, visibility
     if (vectors_on_device) {
@@ -1837,7 +1855,7 @@ static int index_insert_impl(vs_index* ix, const float* vectors, bool vectors_on
         if (new_val) {
             VS_HIP(hipStreamSynchronize(st));
             if (ix->label_val) (void)hipFree(ix->label_val);
-            ix->label_val = new_val;
+            ix->label_val = sc.release(new_val);  // (the index's own from here on)
             ix->n_label_vals = old_vals + add_vals;
         }
     }
@@ -1889,55 +1907,10 @@ static int index_insert_impl(vs_index* ix, const float* vectors, bool vectors_on
     s.first_node = n_old;
     s.inserted = n_new;
     s.grew = grew;
-    BuildBufs B;
     BatchRunner br;
-    int r = VS_OK;
-    do {
-        // (the buffers are sized by the batch: a one-row call must not allocate what a 65 536-row batch needs)
-        if (batch_max == 0) batch_max = std::min<uint32_t>(65536, std::max<uint32_t>(1024, n / 64));
-        batch_max = std::max(1u, std::min(std::min<uint32_t>(batch_max, 65536), n_new));
-        if ((r = br.init(ix, B, L, (float)max_alpha, batch_max, n))) break;
-        br.mates = std::min<uint32_t>(env_u32("VS_INSERT_MATES", 16), 64);
-        const uint32_t bm = std::min(br.batch_max, n_new);
-        hipError_t e = hipSuccess;
-        if (br.mates) e = hipMalloc(&B.mate_ids, (size_t)bm * br.mates * 4);
-        if (e == hipSuccess && br.mates) e = hipMalloc(&B.mate_ham, (size_t)bm * br.mates * 4);
-        if (e == hipSuccess) e = hipMalloc(&B.anch, ((size_t)n_new + 2) * 4);
-        if (e == hipSuccess && c->profiling) {
-            e = hipEventCreate(&br.ev[0]);
-            if (e == hipSuccess) e = hipEventCreate(&br.ev[1]);
-        }
-        if (e != hipSuccess) {
-            vs_set_error("%s: %s", what, hipGetErrorString(e));
-            r = e == hipErrorOutOfMemory ? VS_ERR_OOM : VS_ERR_HIP;
-            break;
-        }
-        // batches as in vs_build_graph: none is larger than the graph it searches (node 0 of an empty index has no one to link to)
-        // For a label the call is the first to bring, the graph under that label's filter IS empty: the batches then double from one
-        // row, as vs_build_graph's do, so that the label's carriers find the ones before them.
-        uint32_t b0 = std::max(n_old, 1u), bsz = new_label ? 1u : br.batch_max;
-        while (b0 < n && r == VS_OK) {
-            const uint32_t bn = std::min(std::min(std::min(br.batch_max, bsz), b0), n - b0);
-            if (bsz < br.batch_max) bsz = std::min(br.batch_max, bsz * 2);
-            if (labeled) r = br.run(b0, bn, true, true);  // Graph::insert: first with the label filter (mates: the batch's rows it admits) ...
-            if (r == VS_OK) r = br.run(b0, bn, false, true);  // ... then from the default start node, the batch's mates among the candidates
-            uint32_t left = 0;
-            if (r == VS_OK) r = anchor_range(br, b0, bn, true, &s.mate_edges, &s.orphans_placed, &left);
-            s.orphans_left = left;
-            s.batches++;
-            b0 += bn;
-        }
-        if (r != VS_OK) break;
-        // later batches re-prune rows that anchored the earlier ones: the rule once more over every row of the call, against the graph
-        // as it was before the call
-        // (node 0 of an index that was empty is the entry point itself)
-        if (s.batches > 1) r = anchor_range(br, std::max(n_old, 1u), n - std::max(n_old, 1u), false, &s.mate_edges, &s.orphans_placed, &s.orphans_left);
-    } while (0);
-    (void)hipStreamSynchronize(st);
+    int r = insert_link_rows(ix, sc, br, L, max_alpha, batch_max, n_old, n_new, new_label, s);
     s.retries = br.retries;
-    if (br.ev[0]) (void)hipEventDestroy(br.ev[0]);
-    if (br.ev[1]) (void)hipEventDestroy(br.ev[1]);
-    B.free_all();
+    sc.close();
     if (r == VS_OK) r = vs_validate_graph(ix);
     for (int k = 0; k < 3; ++k) {
         ix->insert_ms[k] += br.ms[k];
@@ -1961,21 +1934,11 @@ extern "C" int vs_index_insert_dev(vs_index* ix, const float* d_vectors, const u
     });
 }
 extern "C" int vs_index_insert_kernel_ms(vs_index* ix, double* ms /*[3]*/, int reset) {
-    VS_REQUIRE(ix && ms, "vs_index_insert_kernel_ms: bad args");
-    for (int k = 0; k < 3; ++k) {
-        ms[k] = ix->insert_ms[k];
-        if (reset) ix->insert_ms[k] = 0;
-    }
-    return VS_OK;
+    return read_kernel_ms("vs_index_insert_kernel_ms", ix, ix ? ix->insert_ms : nullptr, 3, ms, reset);
 }
 
 extern "C" int vs_index_build_kernel_ms(vs_index* ix, double* ms /*[3]*/, int reset) {
-    VS_REQUIRE(ix && ms, "vs_index_build_kernel_ms: bad args");
-    for (int k = 0; k < 3; ++k) {
-        ms[k] = ix->build_ms[k];
-        if (reset) ix->build_ms[k] = 0;
-    }
-    return VS_OK;
+    return read_kernel_ms("vs_index_build_kernel_ms", ix, ix ? ix->build_ms : nullptr, 3, ms, reset);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2029,60 +1992,49 @@ static int bulk_delete_impl(vs_index* ix, const char* what, const uint64_t* dead
     if (!on_device)
         for (uint64_t i = 0; i < n_dead; ++i)
             VS_REQUIRE((dead[i] & 0xFFFFull) != 0, "%s: dead_tids[%llu] has offset 0 (InvalidOffsetNumber)", what, (unsigned long long)i);
-    if (ix->ws.pending) {
-        vs_set_error("%s: a batch of this handle is in flight (vs_search_batch_dev_finish first)", what);
-        return VS_ERR_STATE;
-    }
+    VS_TRY(require_no_batch(ix, what));
     vs_ctx* c = ix->ctx;
     hipStream_t st = c->stream;
     VS_HIP(hipSetDevice(c->device));
+    DevScope sc(st);
     uint64_t *d_in = nullptr, *d_sorted = nullptr;
     uint8_t* d_pay = nullptr;
     void* d_tmp = nullptr;
     unsigned long long* d_cnt = nullptr;
     unsigned long long h_cnt[3] = {0, 0, 0};
-    auto run = [&]() -> int {
-        const uint64_t* d_dead = dead;
-        if (!on_device && n_dead) {
-            // staged through the pinned ring, sorted on the device (the radix sort the build already uses: pairs, here with one byte
-            // of payload nobody reads); duplicates stay, a binary search does not mind them
-            VS_HIP(hipMalloc(&d_in, n_dead * 8));
-            VS_HIP(hipMalloc(&d_sorted, n_dead * 8));
-            VS_HIP(hipMalloc(&d_pay, n_dead * 2));
-            VS_HIP(hipMemsetAsync(d_pay, 0, n_dead * 2, st));
-            VS_TRY(vs_dev_upload(c, d_in, dead, n_dead * 8));
-            size_t tmp_bytes = 0;
-            VS_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (const uint64_t*)d_in, d_sorted, (const uint8_t*)d_pay, d_pay + n_dead,
-                                                      (int)n_dead, 0, 64, st));
-            VS_HIP(hipMalloc(&d_tmp, tmp_bytes + 16));
-            VS_HIP(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, (const uint64_t*)d_in, d_sorted, (const uint8_t*)d_pay, d_pay + n_dead,
-                                                      (int)n_dead, 0, 64, st));
-            d_dead = d_sorted;
-        }
-        VS_HIP(hipMalloc(&d_cnt, sizeof h_cnt));
-        VS_HIP(hipMemsetAsync(d_cnt, 0, sizeof h_cnt, st));
-        if (ix->d.n) {
-            const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)ix->d.n + 255) / 256, 8192);
-            hipLaunchKernelGGL(k_bulk_delete, dim3(grid), dim3(256), 0, st, ix->tids, ix->d.n, d_dead, n_dead, d_cnt);
-            VS_HIP(hipGetLastError());
-        }
-        VS_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
-        VS_HIP(hipStreamSynchronize(st));  // (the only wait: the three counters)
-        return VS_OK;
-    };
-    const int rc = run();
-    if (rc != VS_OK) (void)hipStreamSynchronize(st);
-    if (d_in) (void)hipFree(d_in);
-    if (d_sorted) (void)hipFree(d_sorted);
-    if (d_pay) (void)hipFree(d_pay);
-    if (d_tmp) (void)hipFree(d_tmp);
-    if (d_cnt) (void)hipFree(d_cnt);
-    if (rc == VS_OK && out) {
+    const uint64_t* d_dead = dead;
+    if (!on_device && n_dead) {
+        // staged through the pinned ring, sorted on the device (the radix sort the build already uses: pairs, here with one byte
+        // of payload nobody reads); duplicates stay, a binary search does not mind them
+        VS_TRY(sc.alloc(&d_in, n_dead * 8, what));
+        VS_TRY(sc.alloc(&d_sorted, n_dead * 8, what));
+        VS_TRY(sc.alloc(&d_pay, n_dead * 2, what));
+        VS_HIP(hipMemsetAsync(d_pay, 0, n_dead * 2, st));
+        VS_TRY(vs_dev_upload(c, d_in, dead, n_dead * 8));
+        size_t tmp_bytes = 0;
+        VS_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (const uint64_t*)d_in, d_sorted, (const uint8_t*)d_pay, d_pay + n_dead,
+                                                  (int)n_dead, 0, 64, st));
+        VS_TRY(sc.alloc(&d_tmp, tmp_bytes + 16, what));
+        VS_HIP(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, (const uint64_t*)d_in, d_sorted, (const uint8_t*)d_pay, d_pay + n_dead,
+                                                  (int)n_dead, 0, 64, st));
+        d_dead = d_sorted;
+    }
+    VS_TRY(sc.alloc(&d_cnt, sizeof h_cnt, what));
+    VS_HIP(hipMemsetAsync(d_cnt, 0, sizeof h_cnt, st));
+    if (ix->d.n) {
+        const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)ix->d.n + 255) / 256, 8192);
+        hipLaunchKernelGGL(k_bulk_delete, dim3(grid), dim3(256), 0, st, ix->tids, ix->d.n, d_dead, n_dead, d_cnt);
+        VS_HIP(hipGetLastError());
+    }
+    VS_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
+    VS_HIP(hipStreamSynchronize(st));  // (the only wait: the three counters)
+    sc.drained();
+    if (out) {
         out->tuples_removed = h_cnt[0];
         out->num_index_tuples = h_cnt[1];
         out->already_deleted = h_cnt[2];
     }
-    return rc;
+    return VS_OK;
 }
 extern "C" int vs_index_bulk_delete(vs_index* ix, const uint64_t* dead_tids, uint64_t n_dead, vs_bulk_delete_stats* out) {
     return vs_guard("vs_index_bulk_delete", [&] { return bulk_delete_impl(ix, "vs_index_bulk_delete", dead_tids, n_dead, false, out); });
@@ -2429,14 +2381,8 @@ static int consolidate_impl(vs_index* ix, double max_alpha, uint32_t cand_max, u
     const uint32_t n = ix->d.n, R = ix->d.num_neighbors, stride = ix->code_stride;
     if (cand_max == 0) cand_max = std::min<uint32_t>(4 * R, 256);
     VS_REQUIRE(cand_max > R && cand_max <= 1024, "%s: cand_max %u outside (num_neighbors = %u, 1024]", what, cand_max, R);
-    if (ix->ws.pending) {
-        vs_set_error("%s: a batch of this handle is in flight (vs_search_batch_dev_finish first)", what);
-        return VS_ERR_STATE;
-    }
-    if (vs_index_open_writers(ix) > 0) {
-        vs_set_error("%s: a vs_pages_out writer of this index is open (its pages would mix rows from before and after; vs_pages_out_close first)", what);
-        return VS_ERR_STATE;
-    }
+    VS_TRY(require_no_batch(ix, what));
+    VS_TRY(require_no_writer(ix, what, WRITER_ROWS_MIX));
     vs_consolidate_stats s{};
     s.unreachable_live = (flags & VS_CONSOLIDATE_NO_REPAIR) ? 0xFFFFFFFFu : 0u;
     if (n == 0 || ix->d.default_start == VS_INVALID_NODE) {
@@ -2447,14 +2393,8 @@ static int consolidate_impl(vs_index* ix, double max_alpha, uint32_t cand_max, u
     hipStream_t st = c->stream;
     VS_HIP(hipSetDevice(c->device));
     // K keeps the default start node and every per-label start node whatever their state: scans begin there
-    std::vector<uint32_t> starts(1, ix->d.default_start);
-    if (ix->d.n_label_starts) {
-        starts.resize(1 + (size_t)ix->d.n_label_starts);
-        VS_HIP(hipMemcpy(starts.data() + 1, ix->ls_nodes, (size_t)ix->d.n_label_starts * 4, hipMemcpyDeviceToHost));
-    }
-    std::sort(starts.begin(), starts.end());
-    starts.erase(std::unique(starts.begin(), starts.end()), starts.end());
-    VS_REQUIRE(starts.back() < n, "%s: start node %u of an index of %u nodes", what, starts.back(), n);
+    std::vector<uint32_t> starts;
+    VS_TRY(collect_start_nodes(ix, what, &starts));
     const bool labeled = ix->label_off != nullptr;
     // the candidate codes sit in LDS while a row is pruned when they fit; failing that, at least the <= R rows a merge gathers
     bool lds_codes = !plain && cons_lds(cand_max, R, stride, labeled, true, true).bytes <= 150 * 1024;
@@ -2462,33 +2402,20 @@ static int consolidate_impl(vs_index* ix, double max_alpha, uint32_t cand_max, u
     const ConsLds lds = plain ? cons_lds_plain(cand_max, R, pv.dim) : cons_lds(cand_max, R, stride, labeled, lds_codes, stage_rows);
     VS_REQUIRE(lds.bytes <= 160 * 1024, "%s: num_neighbors %u / cand_max %u need %zu bytes of LDS", what, R, cand_max, lds.bytes);
     const uint32_t n_waves = (n + WAVE - 1) / WAVE;
-    uint8_t *d_cls = nullptr, *d_flag = nullptr;
-    uint32_t *d_wave = nullptr, *d_work = nullptr, *d_starts = nullptr;
-    unsigned long long* d_cnt = nullptr;
     unsigned long long h_cnt[CN_N] = {0};
     uint32_t nwork = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    double ms[2] = {0, 0};
-    auto tick = [&] {
-        if (ev[0]) (void)hipEventRecord(ev[0], st);
-    };
-    auto tock = [&](int which) {
-        float t = 0.f;
-        if (ev[0] && hipEventRecord(ev[1], st) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
-            hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess)
-            ms[which] += t;
-    };
-    BuildBufs B;
-    auto run = [&]() -> int {
-        if (c->profiling) {
-            VS_HIP(hipEventCreate(&ev[0]));
-            VS_HIP(hipEventCreate(&ev[1]));
-        }
-        VS_HIP(hipMalloc(&d_cls, (size_t)n));
-        VS_HIP(hipMalloc(&d_flag, (size_t)n));
-        VS_HIP(hipMalloc(&d_wave, ((size_t)n_waves + 1) * 4));
-        VS_HIP(hipMalloc(&d_starts, starts.size() * 4));
-        VS_HIP(hipMalloc(&d_cnt, sizeof h_cnt));
+    auto run = [&]() -> int {  // (the stats are filled from what it got to, whatever it returns)
+        DevScope sc(st);
+        StageTimer tm;
+        VS_TRY(tm.start(sc, c->profiling, ix->consolidate_ms, what));
+        uint8_t *d_cls = nullptr, *d_flag = nullptr;
+        uint32_t *d_wave = nullptr, *d_work = nullptr, *d_starts = nullptr;
+        unsigned long long* d_cnt = nullptr;
+        VS_TRY(sc.alloc(&d_cls, (size_t)n, what));
+        VS_TRY(sc.alloc(&d_flag, (size_t)n, what));
+        VS_TRY(sc.alloc(&d_wave, ((size_t)n_waves + 1) * 4, what));
+        VS_TRY(sc.alloc(&d_starts, starts.size() * 4, what));
+        VS_TRY(sc.alloc(&d_cnt, sizeof h_cnt, what));
         VS_HIP(hipMemcpyAsync(d_starts, starts.data(), starts.size() * 4, hipMemcpyHostToDevice, st));
         VS_HIP(hipMemsetAsync(d_cnt, 0, sizeof h_cnt, st));
         VS_HIP(hipMemsetAsync(d_flag, 0, (size_t)n, st));
@@ -2496,7 +2423,7 @@ static int consolidate_impl(vs_index* ix, double max_alpha, uint32_t cand_max, u
             VS_TRY(launch_row_norms(ix));
             VS_TRY(launch_slice_norms_range(ix, 0, n));
         }
-        tick();
+        tm.tick();
         const dim3 ngrid((n + 255) / 256);
         hipLaunchKernelGGL(k_cons_classify, ngrid, dim3(256), 0, st, (const uint64_t*)ix->tids, (const uint32_t*)ix->label_off, n, d_cls, d_cnt);
         VS_HIP(hipGetLastError());
@@ -2516,16 +2443,16 @@ static int consolidate_impl(vs_index* ix, double max_alpha, uint32_t cand_max, u
         VS_HIP(hipStreamSynchronize(st));
         VS_REQUIRE(h_cnt[CN_WIDE_LABELS] == 0, "%s: %llu node(s) carry more than 64 labels", what, h_cnt[CN_WIDE_LABELS]);
         if (nwork) {
-            VS_HIP(hipMalloc(&d_work, (size_t)nwork * 4));
+            VS_TRY(sc.alloc(&d_work, (size_t)nwork * 4, what));
             hipLaunchKernelGGL(k_cons_work_scatter, ngrid, dim3(256), 0, st, (const uint8_t*)d_flag, n, (const uint32_t*)d_wave, d_work);
             VS_HIP(hipGetLastError());
         }
-        tock(0);
+        tm.tock(0);
         if (nwork) {
             const void* kern = plain ? reinterpret_cast<const void*>(k_consolidate_rows<true>) : reinterpret_cast<const void*>(k_consolidate_rows<false>);
             VS_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             ix->nbr_mask_valid = false;  // (the neighbor lists are about to change: what was derived from them is stale)
-            tick();
+            tm.tick();
             const dim3 rgrid(std::min<uint32_t>(nwork, 1u << 20));
             if (plain)
                 hipLaunchKernelGGL(k_consolidate_rows<true>, rgrid, dim3(WAVE), lds.bytes, st, (const uint64_t*)nullptr, 0u, ix->nbrs, ix->nbr_stride,
@@ -2537,7 +2464,7 @@ static int consolidate_impl(vs_index* ix, double max_alpha, uint32_t cand_max, u
                                    lds_codes ? 1u : 0u, stage_rows ? 1u : 0u, (const uint32_t*)ix->label_off, (const int16_t*)ix->label_val,
                                    d_cnt, pv);
             VS_HIP(hipGetLastError());
-            tock(1);
+            tm.tock(1);
             VS_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
             VS_HIP(hipStreamSynchronize(st));
         }
@@ -2546,20 +2473,12 @@ static int consolidate_impl(vs_index* ix, double max_alpha, uint32_t cand_max, u
             VS_HIP(hipMemcpy(cls.data(), d_cls, n, hipMemcpyDeviceToHost));
             ix->nbr_mask_valid = false;
             ix->build_unreachable = 0;
-            VS_TRY(repair_graph(ix, B, cls.data()));
+            VS_TRY(repair_graph(ix, sc, cls.data()));
             s.unreachable_live = ix->build_unreachable;
         }
         return VS_OK;
     };
     int rc = run();
-    (void)hipStreamSynchronize(st);
-    B.free_all();
-    void* ps[] = {d_cls, d_flag, d_wave, d_work, d_starts, d_cnt};
-    for (void* p : ps)
-        if (p) (void)hipFree(p);
-    for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-    for (int k = 0; k < 2; ++k) ix->consolidate_ms[k] += ms[k];
     s.tombstones = h_cnt[CN_TOMB];
     s.tombstones_kept = h_cnt[CN_KEPT];
     s.rows_rewritten = nwork;
@@ -2580,12 +2499,7 @@ extern "C" int vs_index_consolidate_deletes_plain(vs_index* ix, double max_alpha
     return vs_guard("vs_index_consolidate_deletes_plain", [&] { return consolidate_impl(ix, max_alpha, cand_max, flags, out, true); });
 }
 extern "C" int vs_index_consolidate_kernel_ms(vs_index* ix, double* ms /*[2]*/, int reset) {
-    VS_REQUIRE(ix && ms, "vs_index_consolidate_kernel_ms: bad args");
-    for (int k = 0; k < 2; ++k) {
-        ms[k] = ix->consolidate_ms[k];
-        if (reset) ix->consolidate_ms[k] = 0;
-    }
-    return VS_OK;
+    return read_kernel_ms("vs_index_consolidate_kernel_ms", ix, ix ? ix->consolidate_ms : nullptr, 2, ms, reset);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2731,18 +2645,9 @@ static int compact_impl(vs_index* ix, uint64_t stage_bytes, uint32_t flags, uint
     VS_REQUIRE_NO_VIEWS(ix, what);
     VS_REQUIRE((flags & ~(uint32_t)VS_COMPACT_KEEP_EDGES_CHECK) == 0, "%s: unknown flags 0x%x", what, flags);
     VS_REQUIRE(ix->nbrs && ix->tids, "%s: needs neighbor lists and heap tids on the device", what);
-    auto state_error = [&](const char* msg) {
-        vs_set_error("%s: %s", what, msg);
-        return VS_ERR_STATE;
-    };
-    if (ix->ws.pending) return state_error("a batch of this handle is in flight (vs_search_batch_dev_finish first)");
-    if (vs_index_open_writers(ix) > 0)
-        return state_error("a vs_pages_out writer of this index is open (its pages would mix rows from before and after; vs_pages_out_close first)");
-    if (ix->visible && ix->visible != ix->visible_own) {
-        bool ours = false;
-        for (const uint8_t* sp : ix->snap) ours |= sp == ix->visible;
-        if (!ours) return state_error("a caller-owned device visibility mask is in force and cannot be compacted by the library (clear or replace it)");
-    }
+    VS_TRY(require_no_batch(ix, what));
+    VS_TRY(require_no_writer(ix, what, WRITER_ROWS_MIX));
+    VS_TRY(require_own_mask(ix, what, "compacted"));
     const uint32_t n = ix->d.n;
     if (stage_bytes == 0) stage_bytes = VS_COMPACT_STAGE_DEFAULT;
     // the per-node columns (the list vs_index_reserve_impl copies, less the label CSR, which is rebuilt aside)
@@ -2780,48 +2685,30 @@ static int compact_impl(vs_index* ix, uint64_t stage_bytes, uint32_t flags, uint
     vs_ctx* c = ix->ctx;
     hipStream_t st = c->stream;
     VS_HIP(hipSetDevice(c->device));
-    std::vector<uint32_t> starts(1, ix->d.default_start);
-    if (ix->d.n_label_starts) {
-        starts.resize(1 + (size_t)ix->d.n_label_starts);
-        VS_HIP(hipMemcpy(starts.data() + 1, ix->ls_nodes, (size_t)ix->d.n_label_starts * 4, hipMemcpyDeviceToHost));
-    }
-    std::sort(starts.begin(), starts.end());
-    starts.erase(std::unique(starts.begin(), starts.end()), starts.end());
-    VS_REQUIRE(starts.back() < n, "%s: start node %u of an index of %u nodes", what, starts.back(), n);
+    std::vector<uint32_t> starts;
+    VS_TRY(collect_start_nodes(ix, what, &starts));
     const bool labeled = ix->label_off != nullptr;
     const uint32_t n_waves = (n + WAVE - 1) / WAVE;
-    uint8_t *d_cls = nullptr, *d_flag = nullptr, *d_stage = nullptr;
-    uint32_t *d_wave = nullptr, *d_lwave = nullptr, *d_starts = nullptr, *d_new_of = nullptr, *d_old_of = nullptr, *new_off = nullptr;
-    int16_t* new_val = nullptr;
-    unsigned long long* d_cnt = nullptr;
     unsigned long long h_cnt[CP_N] = {0};
     uint32_t new_default = ix->d.default_start, chunks = 0;
     bool moved = false;  // the first byte has moved: an error from here on leaves the index undefined
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    double ms[2] = {0, 0};
-    auto tick = [&] {
-        if (ev[0]) (void)hipEventRecord(ev[0], st);
-    };
-    auto tock = [&](int which) {
-        float t = 0.f;
-        if (ev[0] && hipEventRecord(ev[1], st) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
-            hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess)
-            ms[which] += t;
-    };
-    auto run = [&]() -> int {
-        if (c->profiling) {
-            VS_HIP(hipEventCreate(&ev[0]));
-            VS_HIP(hipEventCreate(&ev[1]));
-        }
-        VS_HIP(hipMalloc(&d_cls, (size_t)n));
-        VS_HIP(hipMalloc(&d_wave, ((size_t)n_waves + 1) * 4));
-        VS_HIP(hipMalloc(&d_starts, starts.size() * 4));
-        VS_HIP(hipMalloc(&d_cnt, sizeof h_cnt));
-        VS_HIP(hipMalloc(&d_new_of, (size_t)n * 4));
-        VS_HIP(hipMalloc(&d_old_of, (size_t)n * 4));
-        if (labeled) VS_HIP(hipMalloc(&d_lwave, ((size_t)n_waves + 1) * 4));
+    auto run = [&]() -> int {  // (the stats are filled from what it got to, whatever it returns)
+        DevScope sc(st);
+        StageTimer tm;
+        VS_TRY(tm.start(sc, c->profiling, ix->compact_ms, what));
+        uint8_t *d_cls = nullptr, *d_flag = nullptr, *d_stage = nullptr;
+        uint32_t *d_wave = nullptr, *d_lwave = nullptr, *d_starts = nullptr, *d_new_of = nullptr, *d_old_of = nullptr, *new_off = nullptr;
+        int16_t* new_val = nullptr;
+        unsigned long long* d_cnt = nullptr;
+        VS_TRY(sc.alloc(&d_cls, (size_t)n, what));
+        VS_TRY(sc.alloc(&d_wave, ((size_t)n_waves + 1) * 4, what));
+        VS_TRY(sc.alloc(&d_starts, starts.size() * 4, what));
+        VS_TRY(sc.alloc(&d_cnt, sizeof h_cnt, what));
+        VS_TRY(sc.alloc(&d_new_of, (size_t)n * 4, what));
+        VS_TRY(sc.alloc(&d_old_of, (size_t)n * 4, what));
+        if (labeled) VS_TRY(sc.alloc(&d_lwave, ((size_t)n_waves + 1) * 4, what));
         if (flags & VS_COMPACT_KEEP_EDGES_CHECK) {
-            VS_HIP(hipMalloc(&d_flag, (size_t)n));
+            VS_TRY(sc.alloc(&d_flag, (size_t)n, what));
             VS_HIP(hipMemsetAsync(d_flag, 0, (size_t)n, st));
         }
         VS_HIP(hipMemcpyAsync(d_starts, starts.data(), starts.size() * 4, hipMemcpyHostToDevice, st));
@@ -2829,7 +2716,7 @@ static int compact_impl(vs_index* ix, uint64_t stage_bytes, uint32_t flags, uint
         VS_HIP(hipMemsetAsync(d_cnt, 0, sizeof h_cnt, st));
         VS_HIP(hipMemcpyAsync(&d_cnt[CP_FIRST], &h_cnt[CP_FIRST], 8, hipMemcpyHostToDevice, st));  // (the atomicMin starts from n)
         VS_HIP(hipStreamSynchronize(st));
-        tick();
+        tm.tick();
         const dim3 ngrid((n + 255) / 256);
         hipLaunchKernelGGL(k_cons_classify, ngrid, dim3(256), 0, st, (const uint64_t*)ix->tids, (const uint32_t*)ix->label_off, n, d_cls, d_cnt);
         VS_HIP(hipGetLastError());
@@ -2859,7 +2746,7 @@ static int compact_impl(vs_index* ix, uint64_t stage_bytes, uint32_t flags, uint
         VS_HIP(hipMemcpyAsync(&d_cnt[CP_N_AFTER], d_wave + n_waves, 4, hipMemcpyDeviceToDevice, st));
         VS_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
         VS_HIP(hipStreamSynchronize(st));
-        tock(0);
+        tm.tock(0);
         const uint32_t n_after = (uint32_t)h_cnt[CP_N_AFTER], first = (uint32_t)h_cnt[CP_FIRST];
         s.n_after = n_after;
         s.tombstones = h_cnt[CN_TOMB];
@@ -2880,11 +2767,11 @@ static int compact_impl(vs_index* ix, uint64_t stage_bytes, uint32_t flags, uint
             const size_t rows = cl.form == 2 ? n_after : n_after - first;
             need = std::max(need, std::min<size_t>(rows, stage_bytes / cl.row_bytes) * cl.row_bytes);
         }
-        VS_HIP(hipMalloc(&d_stage, std::max<size_t>(need, 16)));
+        VS_TRY(sc.alloc(&d_stage, std::max<size_t>(need, 16), what));
         const uint64_t vals_after = h_cnt[CP_LABEL_VALS];
         if (labeled) {
-            VS_HIP(hipMalloc(&new_off, ((size_t)std::max(n, ix->capacity) + 1) * 4));
-            VS_HIP(hipMalloc(&new_val, std::max<uint64_t>(vals_after, 1) * 2));
+            VS_TRY(sc.alloc(&new_off, ((size_t)std::max(n, ix->capacity) + 1) * 4, what));
+            VS_TRY(sc.alloc(&new_val, std::max<uint64_t>(vals_after, 1) * 2, what));
         }
         if (labeled) {  // (reads the label CSR as it stands, writes the fresh arrays: nothing of the index has changed yet)
             hipLaunchKernelGGL(k_compact_labels, ngrid, dim3(256), 0, st, (const uint8_t*)d_cls, (const uint32_t*)ix->label_off,
@@ -2895,7 +2782,7 @@ static int compact_impl(vs_index* ix, uint64_t stage_bytes, uint32_t flags, uint
         VS_HIP(hipStreamSynchronize(st));
         moved = true;
         ix->nbr_mask_valid = false;
-        tick();
+        tm.tick();
         for (const Col& cl : cols) {
             const uint32_t from = cl.form == 2 ? 0 : first;  // (every neighbor row is renamed; the other columns start at the first hole)
             const uint32_t per = (uint32_t)std::min<uint64_t>(stage_bytes / cl.row_bytes, n_after - from);
@@ -2941,14 +2828,12 @@ static int compact_impl(vs_index* ix, uint64_t stage_bytes, uint32_t flags, uint
         // (the counters of the first copy stand; the neighbor form has added edges_cut — unless the check pass counted them — and rows_emptied)
         VS_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
         VS_HIP(hipStreamSynchronize(st));
-        tock(1);
+        tm.tock(1);
         if (labeled) {
             (void)hipFree(ix->label_off);
             (void)hipFree(ix->label_val);
-            ix->label_off = new_off;
-            ix->label_val = new_val;
-            new_off = nullptr;
-            new_val = nullptr;
+            ix->label_off = sc.release(new_off);  // (the index's own from here on)
+            ix->label_val = sc.release(new_val);
             ix->n_label_vals = vals_after;
         }
         ix->d.default_start = new_default;
@@ -2973,13 +2858,6 @@ static int compact_impl(vs_index* ix, uint64_t stage_bytes, uint32_t flags, uint
         return VS_OK;
     };
     int rc = run();
-    (void)hipStreamSynchronize(st);
-    void* ps[] = {d_cls, d_flag, d_stage, d_wave, d_lwave, d_starts, d_new_of, d_old_of, new_off, new_val, d_cnt};
-    for (void* p : ps)
-        if (p) (void)hipFree(p);
-    for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-    for (int k = 0; k < 2; ++k) ix->compact_ms[k] += ms[k];
     if (out) *out = s;
     if (rc == VS_OK && moved) rc = vs_validate_graph(ix);
     return rc;
@@ -2988,12 +2866,7 @@ extern "C" int vs_index_compact(vs_index* ix, uint64_t stage_bytes, uint32_t fla
     return vs_guard("vs_index_compact", [&] { return compact_impl(ix, stage_bytes, flags, out_new_of, out); });
 }
 extern "C" int vs_index_compact_kernel_ms(vs_index* ix, double* ms /*[2]*/, int reset) {
-    VS_REQUIRE(ix && ms, "vs_index_compact_kernel_ms: bad args");
-    for (int k = 0; k < 2; ++k) {
-        ms[k] = ix->compact_ms[k];
-        if (reset) ix->compact_ms[k] = 0;
-    }
-    return VS_OK;
+    return read_kernel_ms("vs_index_compact_kernel_ms", ix, ix ? ix->compact_ms : nullptr, 2, ms, reset);
 }
 
 // vs_index_shrink_to_fit: the arrays one at a time at d.n rows — allocate, copy device to device, swap, free the old one — so the
@@ -3413,7 +3286,7 @@ __global__ __launch_bounds__(WAVE) void k_lr_apply(const uint32_t* __restrict__ 
     }
 }
 
-struct LrState {
+struct LrState {  // (non-owning: every buffer belongs to the DevScope of the call)
     vs_index* ix = nullptr;
     const char* what = "";
     hipStream_t st = nullptr;
@@ -3437,29 +3310,12 @@ struct LrState {
              *d_starts = nullptr;
     unsigned long long *cnt = nullptr, *keys = nullptr, *cons_cnt = nullptr;
     size_t lost_cap = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    double ms[4] = {0, 0, 0, 0};
-    void tick() {
-        if (ev[0]) (void)hipEventRecord(ev[0], st);
-    }
-    void tock(int which) {
-        float t = 0.f;
-        if (ev[0] && hipEventRecord(ev[1], st) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
-            hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess)
-            ms[which] += t;
-    }
-    void free_all() {
-        void* ps[] = {cls, flag, any, rowchg, d_table, mark, mask_buf, reach, fresh[0], fresh[1], need, seed_bits, wave, strong, claim, lost,
-                      seed_nodes, bitcnt, changed, d_starts, cnt, keys, cons_cnt};
-        for (void* p : ps)
-            if (p) (void)hipFree(p);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
+    StageTimer tm;
 };
 
 // the labels, the node classes and the buffers every pass needs (repair: also those of steps 2-5)
-static int lr_init(LrState& S, vs_index* ix, const char* what, bool repair) {
+// ms [4]: where the stage times of the passes accumulate while the context is profiling
+static int lr_init(LrState& S, vs_index* ix, DevScope& sc, const char* what, bool repair, double* ms) {
     S.ix = ix;
     S.what = what;
     S.st = ix->ctx->stream;
@@ -3481,20 +3337,19 @@ static int lr_init(LrState& S, vs_index* ix, const char* what, bool repair) {
         for (uint32_t j = 0; j < nv; ++j) present[(uint16_t)val[j]] = 1;
     }
     std::map<int16_t, uint32_t> start_of;
-    std::vector<uint32_t> starts(1, ix->d.default_start);
-    if (ix->d.n_label_starts) {
-        const uint32_t ns = ix->d.n_label_starts;
-        std::vector<int16_t> sl(ns);
-        std::vector<uint32_t> sn(ns);
+    const uint32_t ns = ix->d.n_label_starts;
+    std::vector<int16_t> sl(ns);
+    std::vector<uint32_t> sn(ns), starts;
+    if (ns) {
         VS_TRY(vs_dev_download(c, sl.data(), ix->ls_labels, (size_t)ns * 2));
         VS_TRY(vs_dev_download(c, sn.data(), ix->ls_nodes, (size_t)ns * 4));
         for (uint32_t t = 0; t < ns; ++t) {
             VS_REQUIRE(sn[t] < n, "%s: start node %u of label %d in an index of %u nodes", what, sn[t], (int)sl[t], n);
             start_of.emplace(sl[t], sn[t]);
-            starts.push_back(sn[t]);
         }
     }
-    VS_REQUIRE(starts[0] < n, "%s: default start node %u of an index of %u nodes", what, starts[0], n);
+    VS_REQUIRE(ix->d.default_start < n, "%s: default start node %u of an index of %u nodes", what, ix->d.default_start, n);
+    VS_TRY(collect_start_nodes(ix, what, &starts, sn.data()));
     for (int v = -32768; v <= 32767; ++v) {
         const bool car = present[(uint16_t)(int16_t)v] != 0;
         const auto it = start_of.find((int16_t)v);
@@ -3506,39 +3361,34 @@ static int lr_init(LrState& S, vs_index* ix, const char* what, bool repair) {
     }
     S.ngroups = ((uint32_t)S.labels.size() + 63) / 64;
     S.own_masks = S.ngroups <= 1 && !S.own_bit.empty();
-    std::sort(starts.begin(), starts.end());
-    starts.erase(std::unique(starts.begin(), starts.end()), starts.end());
-    if (c->profiling) {
-        VS_HIP(hipEventCreate(&S.ev[0]));
-        VS_HIP(hipEventCreate(&S.ev[1]));
-    }
-    VS_HIP(hipMalloc(&S.cls, n));
-    VS_HIP(hipMalloc(&S.flag, n));
-    VS_HIP(hipMalloc(&S.any, n));
-    VS_HIP(hipMalloc(&S.reach, (size_t)n * 8));
-    VS_HIP(hipMalloc(&S.fresh[0], (size_t)n * 8));
-    VS_HIP(hipMalloc(&S.fresh[1], (size_t)n * 8));
-    VS_HIP(hipMalloc(&S.need, (size_t)n * 8));
-    VS_HIP(hipMalloc(&S.wave, ((size_t)S.n_waves + 1) * 4));
-    VS_HIP(hipMalloc(&S.seed_nodes, 64 * 4));
-    VS_HIP(hipMalloc(&S.seed_bits, 64 * 8));
-    VS_HIP(hipMalloc(&S.bitcnt, 128 * 4));
-    VS_HIP(hipMalloc(&S.changed, 4));
-    VS_HIP(hipMalloc(&S.cnt, LR_N * 8));
-    VS_HIP(hipMalloc(&S.cons_cnt, CN_N * 8));
-    VS_HIP(hipMalloc(&S.d_starts, starts.size() * 4));
+    VS_TRY(S.tm.start(sc, c->profiling, ms, what));
+    VS_TRY(sc.alloc(&S.cls, n, what));
+    VS_TRY(sc.alloc(&S.flag, n, what));
+    VS_TRY(sc.alloc(&S.any, n, what));
+    VS_TRY(sc.alloc(&S.reach, (size_t)n * 8, what));
+    VS_TRY(sc.alloc(&S.fresh[0], (size_t)n * 8, what));
+    VS_TRY(sc.alloc(&S.fresh[1], (size_t)n * 8, what));
+    VS_TRY(sc.alloc(&S.need, (size_t)n * 8, what));
+    VS_TRY(sc.alloc(&S.wave, ((size_t)S.n_waves + 1) * 4, what));
+    VS_TRY(sc.alloc(&S.seed_nodes, 64 * 4, what));
+    VS_TRY(sc.alloc(&S.seed_bits, 64 * 8, what));
+    VS_TRY(sc.alloc(&S.bitcnt, 128 * 4, what));
+    VS_TRY(sc.alloc(&S.changed, 4, what));
+    VS_TRY(sc.alloc(&S.cnt, LR_N * 8, what));
+    VS_TRY(sc.alloc(&S.cons_cnt, CN_N * 8, what));
+    VS_TRY(sc.alloc(&S.d_starts, starts.size() * 4, what));
     VS_HIP(hipMemsetAsync(S.cnt, 0, LR_N * 8, S.st));
     VS_HIP(hipMemsetAsync(S.cons_cnt, 0, CN_N * 8, S.st));
     if (!S.own_masks) {
-        VS_HIP(hipMalloc(&S.mask_buf, (size_t)n * 8));
-        VS_HIP(hipMalloc(&S.d_table, 65536));
+        VS_TRY(sc.alloc(&S.mask_buf, (size_t)n * 8, what));
+        VS_TRY(sc.alloc(&S.d_table, 65536, what));
         S.table.resize(65536);
     }
     if (repair) {
-        VS_HIP(hipMalloc(&S.rowchg, n));
-        VS_HIP(hipMalloc(&S.strong, (size_t)n * 4));
-        VS_HIP(hipMalloc(&S.claim, (size_t)n * 4));
-        VS_HIP(hipMalloc(&S.mark, (size_t)n + 8));
+        VS_TRY(sc.alloc(&S.rowchg, n, what));
+        VS_TRY(sc.alloc(&S.strong, (size_t)n * 4, what));
+        VS_TRY(sc.alloc(&S.claim, (size_t)n * 4, what));
+        VS_TRY(sc.alloc(&S.mark, (size_t)n + 8, what));
         VS_HIP(hipMemsetAsync(S.rowchg, 0, n, S.st));
     }
     // the node classes of section 6d
@@ -3598,7 +3448,7 @@ static int lr_group_reach(LrState& S, uint32_t g, bool collect_any, uint32_t* nl
         VS_HIP(hipGetLastError());
         VS_HIP(hipStreamSynchronize(S.st));  // (sn / sb are locals)
         const size_t cells = (size_t)n * R;
-        S.tick();
+        S.tm.tick();
         int in = 0;
         for (uint64_t it = 0;; ++it) {  // no level cap: a rare label's chain is deep
             if (it > n) {  // (every sweep that changes something lengthens some label's chain, and a chain has at most n nodes)
@@ -3617,7 +3467,7 @@ static int lr_group_reach(LrState& S, uint32_t g, bool collect_any, uint32_t* nl
             in ^= 1;
             if (!changed) break;
         }
-        S.tock(0);
+        S.tm.tock(0);
     }
     VS_HIP(hipMemsetAsync(S.bitcnt, 0, 128 * 4, S.st));
     const dim3 ngrid((n + 255) / 256);
@@ -3670,10 +3520,7 @@ static int label_reach_impl(vs_index* ix, vs_label_reach_stats* out, int16_t* ou
     if (out) memset(out, 0, sizeof(*out));
     VS_REQUIRE(ix->label_off && ix->label_val, "%s: the index has no label sets", what);
     VS_REQUIRE(ix->nbrs && ix->tids, "%s: the index has no neighbor lists", what);
-    if (ix->ws.pending) {
-        vs_set_error("%s: a batch of this handle is in flight (vs_search_batch_dev_finish first)", what);
-        return VS_ERR_STATE;
-    }
+    VS_TRY(require_no_batch(ix, what));
     vs_label_reach_stats s{};
     if (ix->d.n == 0 || ix->d.default_start == VS_INVALID_NODE) {
         if (out) *out = s;
@@ -3682,18 +3529,15 @@ static int label_reach_impl(vs_index* ix, vs_label_reach_stats* out, int16_t* ou
     VS_HIP(hipSetDevice(ix->ctx->device));
     LrState S;
     std::vector<uint32_t> carriers, lost;
-    auto run = [&]() -> int {
-        VS_TRY(lr_init(S, ix, what, false));
+    {
+        DevScope sc(ix->ctx->stream);
+        double audit_ms[4] = {0, 0, 0, 0};  // (vs_index_label_repair_kernel_ms reports the repair's kernels only)
+        VS_TRY(lr_init(S, ix, sc, what, false, audit_ms));
         carriers.assign(S.labels.size(), 0);
         lost.assign(S.labels.size(), 0);
         VS_TRY(lr_audit(S, &s.lost_pairs, &s.lost_nodes, carriers.data(), lost.data()));
         if (out_node_lost) VS_TRY(vs_dev_download(ix->ctx, out_node_lost, S.any, S.n));
-        return VS_OK;
-    };
-    const int rc = run();
-    (void)hipStreamSynchronize(S.st ? S.st : ix->ctx->stream);
-    S.free_all();
-    VS_TRY(rc);
+    }
     s.labels = (uint32_t)S.labels.size();
     s.labels_without_start = S.without_start;
     s.sweeps = S.sweeps;
@@ -3722,14 +3566,8 @@ static int repair_labels_impl(vs_index* ix, uint32_t max_rounds, uint32_t flags,
     VS_REQUIRE(flags == 0, "%s: unknown flags 0x%x", what, flags);
     VS_REQUIRE(max_rounds <= 64, "%s: max_rounds %u outside [0,64]", what, max_rounds);
     if (max_rounds == 0) max_rounds = 16;
-    if (ix->ws.pending) {
-        vs_set_error("%s: a batch of this handle is in flight (vs_search_batch_dev_finish first)", what);
-        return VS_ERR_STATE;
-    }
-    if (vs_index_open_writers(ix) > 0) {
-        vs_set_error("%s: a vs_pages_out writer of this index is open (its pages would mix rows from before and after; vs_pages_out_close first)", what);
-        return VS_ERR_STATE;
-    }
+    VS_TRY(require_no_batch(ix, what));
+    VS_TRY(require_no_writer(ix, what, WRITER_ROWS_MIX));
     vs_label_repair_stats s{};
     if (ix->d.n == 0 || ix->d.default_start == VS_INVALID_NODE) {
         if (out) *out = s;
@@ -3737,10 +3575,11 @@ static int repair_labels_impl(vs_index* ix, uint32_t max_rounds, uint32_t flags,
     }
     VS_HIP(hipSetDevice(ix->ctx->device));
     LrState S;
+    DevScope sc(ix->ctx->stream);
     const uint32_t n = ix->d.n, R = ix->d.num_neighbors;
     bool wrote = false;
-    auto run = [&]() -> int {
-        VS_TRY(lr_init(S, ix, what, true));
+    auto run = [&]() -> int {  // (the stats are filled from what it got to, whatever it returns)
+        VS_TRY(lr_init(S, ix, sc, what, true, ix->label_repair_ms));
         hipStream_t st = S.st;
         VS_TRY(lr_audit(S, &s.lost_pairs_before, &s.lost_nodes_before, nullptr, nullptr));
         s.lost_pairs_after = s.lost_pairs_before;
@@ -3755,27 +3594,25 @@ static int repair_labels_impl(vs_index* ix, uint32_t max_rounds, uint32_t flags,
                 if (!nl) continue;
                 any_lost = true;
                 if (nl > S.lost_cap) {
-                    if (S.lost) VS_HIP(hipFree(S.lost));
-                    if (S.keys) VS_HIP(hipFree(S.keys));
-                    S.lost = nullptr;
-                    S.keys = nullptr;
+                    sc.free(S.lost);
+                    sc.free(S.keys);
                     S.lost_cap = 0;
-                    VS_HIP(hipMalloc(&S.lost, (size_t)nl * 4));
-                    VS_HIP(hipMalloc(&S.keys, (size_t)nl * 8));
+                    VS_TRY(sc.alloc(&S.lost, (size_t)nl * 4, what));
+                    VS_TRY(sc.alloc(&S.keys, (size_t)nl * 8, what));
                     S.lost_cap = nl;
                 }
                 hipLaunchKernelGGL(k_cons_work_scatter, ngrid, dim3(256), 0, st, (const uint8_t*)S.flag, n, (const uint32_t*)S.wave, S.lost);
                 VS_HIP(hipGetLastError());
-                S.tick();
+                S.tm.tick();
                 VS_HIP(hipMemsetAsync(S.strong, 0, (size_t)n * 4, st));
                 hipLaunchKernelGGL(k_lr_strong, cgrid, dim3(256), 0, st, (const uint32_t*)ix->nbrs, ix->nbr_stride, R, n, (const uint8_t*)S.cls, S.mask,
                                    S.jmask, (const uint64_t*)S.reach, S.strong);
                 VS_HIP(hipGetLastError());
-                S.tock(1);
-                S.tick();
+                S.tm.tock(1);
+                S.tm.tick();
                 VS_TRY(launch_nearest_masked(ix, S.lost, nl, S.need, true, S.reach, S.cls, S.keys, &s.source_tiles));
-                S.tock(2);
-                S.tick();
+                S.tm.tock(2);
+                S.tm.tick();
                 VS_HIP(hipMemsetAsync(S.claim, 0xFF, (size_t)n * 4, st));
                 hipLaunchKernelGGL(k_lr_claim, dim3((nl + 255) / 256), dim3(256), 0, st, (const uint32_t*)S.lost, nl,
                                    (const unsigned long long*)S.keys, S.claim);
@@ -3786,27 +3623,15 @@ static int repair_labels_impl(vs_index* ix, uint32_t max_rounds, uint32_t flags,
                                    (const uint32_t*)S.claim, ix->nbrs, ix->nbr_stride, R, n, (const uint8_t*)S.cls, S.mask, S.jmask,
                                    (const uint64_t*)S.reach, (const uint32_t*)S.strong, S.rowchg, S.cnt);
                 VS_HIP(hipGetLastError());
-                S.tock(3);
+                S.tm.tock(3);
             }
             if (!any_lost) break;
             s.rounds++;
         }
         if (s.rounds) VS_TRY(lr_audit(S, &s.lost_pairs_after, &s.lost_nodes_after, nullptr, nullptr));
         // one unfiltered sweep from the default start node: no live row may have lost its way in
-        VS_HIP(hipMemsetAsync(S.mark, 0, (size_t)n + 8, st));
-        uint32_t* d_changed = reinterpret_cast<uint32_t*>(S.mark + (((size_t)n + 3) & ~(size_t)3));
-        const uint8_t one = 1;
-        VS_HIP(hipMemcpyAsync(S.mark + ix->d.default_start, &one, 1, hipMemcpyHostToDevice, st));
         bool converged = false;
-        for (uint32_t level = 1; level < 255 && !converged; ++level) {
-            uint32_t changed = 0;
-            VS_HIP(hipMemsetAsync(d_changed, 0, 4, st));
-            hipLaunchKernelGGL(k_reach_sweep, cgrid, dim3(256), 0, st, (const uint32_t*)ix->nbrs, ix->nbr_stride, R, n, S.mark, level, d_changed);
-            VS_HIP(hipGetLastError());
-            VS_HIP(hipMemcpyAsync(&changed, d_changed, 4, hipMemcpyDeviceToHost, st));
-            VS_HIP(hipStreamSynchronize(st));
-            converged = changed == 0;
-        }
+        VS_TRY(reach_from_default_start(ix, S.mark, &converged));
         s.unreachable_live = 0xFFFFFFFFu;
         if (converged) VS_TRY(lr_count_flags(S, S.mark, 0, S.cls, &s.unreachable_live));
         uint32_t rc_rows = 0;
@@ -3815,11 +3640,11 @@ static int repair_labels_impl(vs_index* ix, uint32_t max_rounds, uint32_t flags,
         return VS_OK;
     };
     int rc = run();
-    (void)hipStreamSynchronize(S.st ? S.st : ix->ctx->stream);
+    (void)hipStreamSynchronize(sc.st);
+    sc.drained();
     unsigned long long h[LR_N] = {0};
-    if (S.cnt) (void)hipMemcpy(h, S.cnt, sizeof h, hipMemcpyDeviceToHost);
-    S.free_all();
-    for (int k = 0; k < 4; ++k) ix->label_repair_ms[k] += S.ms[k];
+    if (S.cnt) (void)hipMemcpy(h, S.cnt, sizeof h, hipMemcpyDeviceToHost);  // (the placement counters as far as the call got)
+    sc.close();
     s.placed_free = h[LR_PLACED_FREE];
     s.placed_over_dropped = h[LR_PLACED_DROPPED];
     s.placed_victim = h[LR_PLACED_VICTIM];
@@ -3835,12 +3660,7 @@ extern "C" int vs_index_repair_labels(vs_index* ix, uint32_t max_rounds, uint32_
     return vs_guard("vs_index_repair_labels", [&] { return repair_labels_impl(ix, max_rounds, flags, out); });
 }
 extern "C" int vs_index_label_repair_kernel_ms(vs_index* ix, double* ms /*[4]*/, int reset) {
-    VS_REQUIRE(ix && ms, "vs_index_label_repair_kernel_ms: bad args");
-    for (int k = 0; k < 4; ++k) {
-        ms[k] = ix->label_repair_ms[k];
-        if (reset) ix->label_repair_ms[k] = 0;
-    }
-    return VS_OK;
+    return read_kernel_ms("vs_index_label_repair_kernel_ms", ix, ix ? ix->label_repair_ms : nullptr, 4, ms, reset);
 }
 
 // ---- vs_nearest_masked: k_nearest_masked on its own -------------------------------------------------------------------------
@@ -3859,29 +3679,24 @@ static int nearest_masked_impl(vs_index* ix, const uint32_t* nodes, const uint64
     uint8_t* d_skip = nullptr;
     unsigned long long* d_keys = nullptr;
     std::vector<unsigned long long> keys(nq);
-    auto run = [&]() -> int {
-        VS_HIP(hipMalloc(&d_nodes, (size_t)nq * 4));
-        VS_HIP(hipMalloc(&d_want, (size_t)nq * 8));
-        VS_HIP(hipMalloc(&d_bits, (size_t)n * 8));
-        VS_HIP(hipMalloc(&d_keys, (size_t)nq * 8));
+    {
+        DevScope sc(c->stream);
+        VS_TRY(sc.alloc(&d_nodes, (size_t)nq * 4, what));
+        VS_TRY(sc.alloc(&d_want, (size_t)nq * 8, what));
+        VS_TRY(sc.alloc(&d_bits, (size_t)n * 8, what));
+        VS_TRY(sc.alloc(&d_keys, (size_t)nq * 8, what));
         VS_TRY(vs_dev_upload(c, d_nodes, nodes, (size_t)nq * 4));
         VS_TRY(vs_dev_upload(c, d_want, want, (size_t)nq * 8));
         VS_TRY(vs_dev_upload(c, d_bits, node_bits, (size_t)n * 8));
         if (skip) {
             std::vector<uint8_t> sk(n);
             for (uint32_t i = 0; i < n; ++i) sk[i] = skip[i] != 0;
-            VS_HIP(hipMalloc(&d_skip, n));
+            VS_TRY(sc.alloc(&d_skip, n, what));
             VS_TRY(vs_dev_upload(c, d_skip, sk.data(), n));
         }
         VS_TRY(launch_nearest_masked(ix, d_nodes, nq, d_want, false, d_bits, d_skip, d_keys));
-        return vs_dev_download(c, keys.data(), d_keys, (size_t)nq * 8);
-    };
-    const int rc = run();
-    (void)hipStreamSynchronize(c->stream);
-    void* ps[] = {d_nodes, d_want, d_bits, d_skip, d_keys};
-    for (void* p : ps)
-        if (p) (void)hipFree(p);
-    VS_TRY(rc);
+        VS_TRY(vs_dev_download(c, keys.data(), d_keys, (size_t)nq * 8));
+    }
     for (uint32_t q = 0; q < nq; ++q) {
         out_ids[q] = keys[q] == ~0ull ? VS_INVALID_NODE : (uint32_t)keys[q];
         if (out_ham) out_ham[q] = keys[q] == ~0ull ? 0xFFFFFFFFu : (uint32_t)(keys[q] >> 32);

@@ -66,6 +66,103 @@ static inline int vs_guard(const char* what, F&& f) {
     }
 }
 
+// ---- the device scratch and HIP events of one call ----------------------------------------------------------------------
+// What a call allocates for its own duration is registered here and goes with the scope, on every way out: a return code, or an
+// exception on its way to vs_guard.  The destructor first waits for the stream once (kernels in flight may still use the buffers),
+// unless the call has told it that its last step was such a wait (drained()).
+struct DevScope {
+    hipStream_t st;
+    explicit DevScope(hipStream_t stream) : st(stream) {}
+    DevScope(const DevScope&) = delete;
+    DevScope& operator=(const DevScope&) = delete;
+    ~DevScope() { close(); }
+    // what the destructor does, for a call that goes on after its device work (a later alloc() or event() opens the scope again)
+    void close() {
+        if (!is_drained) (void)hipStreamSynchronize(st);
+        for (void* p : bufs) (void)hipFree(p);
+        for (hipEvent_t e : events) (void)hipEventDestroy(e);
+        bufs.clear();
+        events.clear();
+        is_drained = true;
+    }
+    template <class T>
+    int alloc(T** p, size_t bytes, const char* what) {
+        bufs.push_back(nullptr);  // (the slot before the allocation: nothing between it and its registration can throw)
+        is_drained = false;
+        const hipError_t e = hipMalloc(&bufs.back(), bytes);
+        if (e != hipSuccess) {
+            bufs.pop_back();
+            vs_set_error("%s: hipMalloc of %zu bytes failed: %s", what, bytes, hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? VS_ERR_OOM : VS_ERR_HIP;
+        }
+        *p = static_cast<T*>(bufs.back());
+        return VS_OK;
+    }
+    // a buffer leaves the scope: release() hands it to the caller (scratch that becomes the index's own), free() returns it to the
+    // device now (the sites that grow a buffer); both leave p null
+    template <class T>
+    T* release(T*& p) {
+        T* const out = p;
+        for (size_t i = 0; i < bufs.size(); ++i)
+            if (bufs[i] == static_cast<void*>(out)) {
+                bufs.erase(bufs.begin() + (long)i);
+                break;
+            }
+        p = nullptr;
+        return out;
+    }
+    template <class T>
+    void free(T*& p) {
+        if (p) (void)hipFree(release(p));
+    }
+    int event(hipEvent_t* ev, const char* what) {
+        events.push_back(nullptr);
+        is_drained = false;
+        const hipError_t e = hipEventCreate(&events.back());
+        if (e != hipSuccess) {
+            events.pop_back();
+            *ev = nullptr;
+            vs_set_error("%s: hipEventCreate failed: %s", what, hipGetErrorString(e));
+            return VS_ERR_HIP;
+        }
+        *ev = events.back();
+        return VS_OK;
+    }
+    void drained() { is_drained = true; }
+
+private:
+    std::vector<void*> bufs;
+    std::vector<hipEvent_t> events;
+    bool is_drained = false;
+};
+
+// HIP-event time of a call's stages (vs_profile_enable): tock(which) adds the milliseconds since the last tick() to ms[which] of the
+// caller's array.  Inert — no event, no wait — unless the context is profiling when start() is called.
+struct StageTimer {
+    hipStream_t st = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double* ms = nullptr;
+    int start(DevScope& sc, bool profiling, double* ms_, const char* what) {
+        st = sc.st;
+        ms = ms_;
+        if (!profiling) return VS_OK;
+        hipEvent_t a = nullptr;
+        VS_TRY(sc.event(&a, what));
+        VS_TRY(sc.event(&ev[1], what));
+        ev[0] = a;
+        return VS_OK;
+    }
+    void tick() {
+        if (ev[0]) (void)hipEventRecord(ev[0], st);
+    }
+    void tock(int which) {
+        float t = 0.f;
+        if (ev[0] && hipEventRecord(ev[1], st) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
+            hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess)
+            ms[which] += t;
+    }
+};
+
 __host__ __device__ static inline uint32_t round_up_u32(uint32_t x, uint32_t m) { return (x + m - 1) / m * m; }
 static inline uint32_t next_pow2_u32(uint64_t x) {
     uint64_t p = 1;

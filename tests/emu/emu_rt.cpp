@@ -138,7 +138,11 @@ static bool arena_free(void* p) {
     return false;
 }
 
+// test hook (vs_emu_fail_allocation): the countdown to the allocation that fails once; 0 = none pending
+static std::atomic<long> g_fail_in{0};
+
 void* guarded_alloc(size_t bytes) {
+    if (g_fail_in.load(std::memory_order_relaxed) > 0 && g_fail_in.fetch_sub(1) == 1) return nullptr;
     {
         std::lock_guard<std::mutex> lk(g_alloc_mu);
         if (arena_mode()) return arena_alloc(bytes);
@@ -202,6 +206,9 @@ extern "C" size_t vs_emu_live_allocations(void) {
     for (const auto& sg : emu::g_segs) n += sg.used ? 1 : 0;
     return n;
 }
+// test hook (tests/test_gpu_zz_hygiene.py): the k-th device or pinned allocation from now fails once (hipErrorOutOfMemory); k = 0 disarms.
+// Returns what was still pending of the countdown armed before (0: that failure was delivered, or none was armed).
+extern "C" long vs_emu_fail_allocation(long k) { return std::max<long>(emu::g_fail_in.exchange(k > 0 ? k : 0), 0); }
 namespace emu {
 
 static constexpr size_t kStackBytes = 512 * 1024;
