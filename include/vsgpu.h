@@ -1508,6 +1508,85 @@ int vs_datagen_fill(vs_ctx* ctx, const vs_datagen_params* p, uint64_t first_row,
 /* exact brute-force f32 top-k on the device (ground truth for recall): d_queries [nq][dim_full] raw */
 int vs_bruteforce_topk(vs_index* idx, const float* d_queries, uint32_t nq, uint32_t k, uint32_t* out_ids, float* out_dist);
 
+/* ---- qualified scans: the first k rows of a scan that pass a per-scan node bitmap (vs_qual.h) ----
+ * `ORDER BY embedding <=> $1 LIMIT k` under an ordinary WHERE clause: the executor post-filters the rows the index returns.  Here the
+ * predicate lives on the device as a QUALIFIER, one bit per node, and a batch keeps popping rows until k of them pass.
+ *
+ * SEMANTICS.  For scan q let r0, r1, ... be the rows the reference returns from successive amgettuple calls after amrescan with the
+ * GUCs search_list_size and rescore, under the mask in force on the index (vs_index_set_visibility*, vs_index_snapshot_use): the rows
+ * vs_search_batch returns, for any k.  Let Q be the qualifier scan q names.  The qualified scan returns the first k rows r_i with bit
+ * node(r_i) set in Q, in that order, with the tid and the distance bits vs_search_batch gives them.  A rejected row is left out AFTER
+ * its pop: it has taken its place in the rescore window and has been reranked like any other.  That is why a qualifier is no
+ * visibility mask, which hides a row BEFORE the window.  The scan never looks past r_(max_pops - 1).  Per scan:
+ *   out_rows[q]   rows returned (<= k); the remaining entries are VS_INVALID_NODE / 0 / NaN, as in vs_search_batch
+ *   out_pops[q]   amgettuple calls the reference would have made that returned a row: for a complete scan the index of its k-th
+ *                 qualifying row + 1, otherwise the number of rows the scan was taken to
+ *   out_state[q]  VS_QUAL_COMPLETE  k rows were returned
+ *                 VS_QUAL_ENDED     the scan returned None within max_pops calls, before k rows had passed: every row was looked at
+ *                 VS_QUAL_CUT       max_pops rows were looked at, fewer than k passed, and no call had returned None yet
+ * Slot 0 is "no qualifier": every node passes, and the rows are the first k rows of vs_search_batch bit for bit.
+ *
+ * QUALIFIERS.  Slots 1 .. VS_MAX_QUAL_SLOTS of an index hold one bit per node, node i at bit (i & 63) of word (i >> 6), in device
+ * memory allocated at the index's capacity.  vs_index_qual_put takes (n + 63) / 64 HOST words, _put_dev DEVICE words; bits at
+ * positions >= n are cleared by the library whatever the caller left there.  vs_index_qual_from_tids sets the bit of every LIVE node
+ * (tid offset != 0) whose heap tid is in the list — (block << 16) | offset, unsorted, duplicates allowed, the convention of
+ * vs_index_bulk_delete; _from_tids_dev takes a DEVICE array sorted ascending (duplicates allowed).  vs_qual_info: n_nodes the nodes
+ * of the index when the slot was filled, n_set the bits set, tids_unmatched the distinct tids of the list that no live node carries
+ * (0 after a _put).  vs_index_qual_info reads the record of a slot, vs_index_qual_drop frees it (VS_ERR_STATE for an empty slot).
+ * LIFETIME: vs_index_reserve and growing inserts carry the qualifiers over, rows added later read 0 and do not qualify;
+ * vs_index_compact renumbers the nodes and DROPS every qualifier.  Refusals, each before anything is written: NULL arguments, slot 0
+ * or a slot > VS_MAX_QUAL_SLOTS (VS_ERR_INVALID); a view handle, a batch of the handle in flight (VS_ERR_STATE).
+ *
+ * THE BATCH.  vs_search_batch_qual(.., k, qual_slots [nq] HOST, max_pops, ..): max_pops in [k, VS_QUAL_MAX_POPS] and qual_slots != NULL,
+ * else VS_ERR_INVALID (the unqualified calls exist for that); a slot > VS_MAX_QUAL_SLOTS is VS_ERR_INVALID and an empty slot
+ * VS_ERR_STATE, before anything is launched.  Owner handles only.  A scan needs an unknown number of pops, so the batch runs in
+ * ROUNDS: round 1 takes every scan to P1 pops, the scans that are neither complete nor ended are gathered and re-run from the start
+ * at twice the pops, up to max_pops (the row sequence is prefix-consistent in the number of pops, so a re-run is exact).  P1 follows
+ * from the density of the sparsest qualifier named, n_set / n: ceil(k / density) plus two standard deviations of that count, clamped to
+ * [k, max_pops] (max_pops for an empty qualifier); the option VS_QUAL_FIRST_POPS overrides it.  The rule is a cost choice: no row,
+ * count or state depends on it.  A round is the batch pipeline of vs_search_batch_dev with a stream long enough for P pops — the
+ * planners see the longer stream as they would for a larger k — whose rescore window (k_rerank_window_qual, or k_resort_qual for
+ * windows the fused kernel does not take, VS_RERANK_FUSED "0" and rescore == 0) reads the popped node's bit after each pop, keeps
+ * the row if it is set and stops at k kept rows.  A batch whose slots are all 0 launches what vs_search_batch_dev launches
+ * (vs_index_last_search_info is equal), straight into the caller's rows.  vs_qual_batch_stats: rounds run, first_pops (P1), scans_rerun (scans of rounds 2 ..), pops_launched (sum over rounds
+ * of scans x P) and the scans per final state.  *stats accumulates the DEVICE's work over all rounds, re-runs included, as it does
+ * over capacity retries: it is not the reference's GreedySearchStats of the qualified scan.
+ * vs_search_batch_dev_qual takes DEVICE queries, label keys (sorted and de-duplicated per query, as vs_search_batch_dev), slots and
+ * outputs (all of which stay valid until the finish); it checks the arguments and launches round 1;
+ * vs_search_batch_dev_qual_finish runs the remaining rounds and fills the outputs.  Per-scan visibility slots together with
+ * qualifiers, scan pools, cursors, the broker, the shm server and vs_multi with qualifiers are not built. */
+#define VS_MAX_QUAL_SLOTS 64
+#define VS_QUAL_MAX_POPS 65536
+enum { VS_QUAL_COMPLETE = 0, VS_QUAL_ENDED = 1, VS_QUAL_CUT = 2 };
+typedef struct vs_qual_info {
+    uint64_t n_nodes;
+    uint64_t n_set;
+    uint64_t tids_unmatched;
+} vs_qual_info;
+typedef struct vs_qual_batch_stats {
+    uint64_t rounds;
+    uint64_t first_pops;
+    uint64_t scans_rerun;
+    uint64_t pops_launched;
+    uint64_t complete, ended, cut;
+} vs_qual_batch_stats;
+int vs_index_qual_put(vs_index* idx, uint32_t slot, const uint64_t* bits);
+int vs_index_qual_put_dev(vs_index* idx, uint32_t slot, const uint64_t* d_bits);
+int vs_index_qual_from_tids(vs_index* idx, uint32_t slot, const uint64_t* heap_tids, size_t n_tids, vs_qual_info* info /* may be NULL */);
+int vs_index_qual_from_tids_dev(vs_index* idx, uint32_t slot, const uint64_t* d_heap_tids_sorted, size_t n_tids, vs_qual_info* info);
+int vs_index_qual_info(const vs_index* idx, uint32_t slot, vs_qual_info* info);
+int vs_index_qual_get(vs_index* idx, uint32_t slot, uint64_t* bits /* host, (n + 63) / 64 words */);
+int vs_index_qual_drop(vs_index* idx, uint32_t slot);
+int vs_search_batch_qual(vs_index* idx, const float* queries, const int16_t* qlabels, const uint32_t* qlabel_off, uint32_t nq,
+                         uint32_t search_list_size, uint32_t rescore, uint32_t k, const uint32_t* qual_slots, uint32_t max_pops,
+                         uint32_t* out_ids, uint64_t* out_tids, float* out_dist, uint32_t* out_rows, uint32_t* out_pops,
+                         uint32_t* out_state, vs_stats* stats, vs_qual_batch_stats* qstats);
+int vs_search_batch_dev_qual(vs_index* idx, const float* d_queries, const int16_t* d_qlabels, const uint32_t* d_qlabel_off, uint32_t nq,
+                             uint32_t search_list_size, uint32_t rescore, uint32_t k, const uint32_t* d_qual_slots, uint32_t max_pops,
+                             uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, uint32_t* d_out_rows, uint32_t* d_out_pops,
+                             uint32_t* d_out_state);
+int vs_search_batch_dev_qual_finish(vs_index* idx, vs_stats* stats, vs_qual_batch_stats* qstats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,6 +137,25 @@ class VisBaseStats(C.Structure):
         return d
 
 
+class QualInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_nodes", "n_set", "tids_unmatched")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class QualBatchStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("rounds", "first_pops", "scans_rerun", "pops_launched", "complete", "ended", "cut")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+MAX_QUAL_SLOTS = 64
+QUAL_MAX_POPS = 65536
+QUAL_COMPLETE, QUAL_ENDED, QUAL_CUT = 0, 1, 2
+
+
 class PagesInfo(C.Structure):
     _fields_ = [("n_blocks", C.c_uint32), ("n_nodes", C.c_uint32), ("words", C.c_uint32), ("num_neighbors", C.c_uint32),
                 ("has_labels", C.c_uint32), ("n_deleted", C.c_uint32), ("n_label_vals", C.c_uint64),
@@ -329,6 +348,17 @@ SYMBOLS = {
     "vs_search_batch_vis": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, C.POINTER(Stats)]),
     "vs_search_batch_dev_vis": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     "vs_search_batch_dev_vis_finish": (_i, [_vp, C.POINTER(Stats)]),
+    "vs_index_qual_put": (_i, [_vp, _u32, _vp]),
+    "vs_index_qual_put_dev": (_i, [_vp, _u32, _vp]),
+    "vs_index_qual_from_tids": (_i, [_vp, _u32, _vp, _sz, C.POINTER(QualInfo)]),
+    "vs_index_qual_from_tids_dev": (_i, [_vp, _u32, _vp, _sz, C.POINTER(QualInfo)]),
+    "vs_index_qual_info": (_i, [_vp, _u32, C.POINTER(QualInfo)]),
+    "vs_index_qual_get": (_i, [_vp, _u32, _vp]),
+    "vs_index_qual_drop": (_i, [_vp, _u32]),
+    "vs_search_batch_qual": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(Stats),
+                                  C.POINTER(QualBatchStats)]),
+    "vs_search_batch_dev_qual": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vs_search_batch_dev_qual_finish": (_i, [_vp, C.POINTER(Stats), C.POINTER(QualBatchStats)]),
     "vs_meta_layout_default": (_i, [C.POINTER(MetaLayout)]),
     "vs_meta_page_decode": (_i, [_vp, _sz, C.POINTER(MetaLayout), C.POINTER(MetaPage), _vp, _vp, _vp, _u32]),
     "vs_pages_meta": (_i, [_vp, C.POINTER(MetaLayout), C.POINTER(MetaPage), C.POINTER(IndexDesc), _vp, _vp, _u32]),

@@ -466,9 +466,11 @@ extern "C" void vs_index_free(vs_index* ix) {
     SearchWorkspace& w = ix->ws;
     DevBuf* bufs[] = {&w.q_full, &w.qcodes, &w.qlabels, &w.qlabel_off, &w.hash, &w.heap_g, &w.heap_g4, &w.ghash4, &w.heap_g4b, &w.ghash4b, &w.pool_ctr, &w.fb_flag, &w.phase, &w.timeline, &w.raw_q2, &w.out_ids2, &w.out_tids2, &w.out_dist2, &w.stream_ids,
                       &w.stream_ham, &w.stream_cnt, &w.stats, &w.status, &w.rr_dist, &w.out_ids, &w.out_tids,
-                      &w.out_dist, &w.resort_heap, &w.raw_q, &w.misc, &w.q_index, &w.red, &w.order_work, &w.order_perm, &w.order_labels, &w.vis_slots};
+                      &w.out_dist, &w.resort_heap, &w.raw_q, &w.misc, &w.q_index, &w.red, &w.order_work, &w.order_perm, &w.order_labels, &w.vis_slots,
+                      &w.qual_q, &w.qual_map, &w.qual_lab, &w.qual_laboff, &w.qual_slots, &w.qual_out};
     for (DevBuf* b : bufs) devbuf_free(*b);
     if (!ix->is_view) vs_vis_base_free(ix);
+    if (!ix->is_view) vs_qual_drop_all(ix);
     if (w.red_host) (void)hipHostFree(w.red_host);
     w.red_host = nullptr;
     vs_slab_release(ix->slab);  // (after the stream synchronisation above; the last handle frees the allocation)
@@ -495,6 +497,7 @@ static int vs_index_view_impl(vs_index* src, vs_ctx* c, vs_index** out) {
         v->slab->refs++;
     }
     v->visible_own = nullptr;
+    v->qs = nullptr;  // (qualifiers are the owner's: a view names none)
     v->ws = SearchWorkspace{};
     v->last_stats = vs_stats{};
     *out = v;
@@ -682,6 +685,7 @@ int vs_index_reserve_impl(vs_index* ix, uint32_t capacity, const char* what) {
         size_t row_bytes, extra_rows;  // extra_rows: label_off holds one entry more than there are rows
         int fill;                      // byte the rows past d.n are set to
         void* fresh;
+        size_t keep_bytes = 0, total_bytes = 0;  // total_bytes != 0: the sizes as they are (bitmaps: no whole bytes per row)
     };
     std::vector<Item> items;
     auto add = [&](void* slot, size_t row_bytes, int fill, size_t extra = 0) {
@@ -698,10 +702,16 @@ int vs_index_reserve_impl(vs_index* ix, uint32_t capacity, const char* what) {
     add(&ix->visible_own, 1, 1);
     for (int sn = 1; sn < VS_MAX_SNAPSHOTS; ++sn) add(&ix->snap[sn], 1, 0);
     if (ix->vb) add(&ix->vb->cls, 1, 0);  // (the class bytes of the visibility base: new rows read class 0, invisible to all)
+    // the qualifiers (one bit per node; bits past d.n are 0 by construction, so the old words are kept whole): new rows do not qualify
+    const size_t qual_words = ((size_t)capacity + 63) / 64;
+    if (ix->qs && qual_words > ix->qs->words)
+        for (uint32_t sl = 1; sl <= VS_MAX_QUAL_SLOTS; ++sl)
+            if (ix->qs->bits[sl]) items.push_back(Item{reinterpret_cast<void**>(&ix->qs->bits[sl]), 8, 0, 0, nullptr, ix->qs->words * 8, qual_words * 8});
     const size_t live = ix->d.n;
     int r = VS_OK;
     for (Item& it : items) {
-        const size_t total = ((size_t)capacity + it.extra_rows) * it.row_bytes, keep = (live + it.extra_rows) * it.row_bytes;
+        const size_t total = it.total_bytes ? it.total_bytes : ((size_t)capacity + it.extra_rows) * it.row_bytes;
+        const size_t keep = it.total_bytes ? it.keep_bytes : (live + it.extra_rows) * it.row_bytes;
         hipError_t e = hipMalloc(&it.fresh, total);
         if (e == hipSuccess && keep) e = hipMemcpyAsync(it.fresh, *it.slot, keep, hipMemcpyDeviceToDevice, c->stream);
         if (e == hipSuccess) e = hipMemsetAsync(static_cast<char*>(it.fresh) + keep, it.fill, total - keep, c->stream);
@@ -729,6 +739,10 @@ int vs_index_reserve_impl(vs_index* ix, uint32_t capacity, const char* what) {
     }
     ix->capacity = capacity;
     if (ix->vb && ix->vb->cls) ix->vb->cls_rows = capacity;
+    if (ix->qs && qual_words > ix->qs->words) {
+        ix->qs->words = qual_words;
+        if (ix->qs->tab) VS_HIP(hipMemcpy(ix->qs->tab, ix->qs->bits, sizeof ix->qs->bits, hipMemcpyHostToDevice));  // (the slots moved)
+    }
     return VS_OK;
 }
 extern "C" int vs_index_reserve(vs_index* ix, uint32_t capacity) {

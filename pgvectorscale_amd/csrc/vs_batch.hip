@@ -259,7 +259,14 @@ static int run_post_search(vs_index* ix, const BatchPlan& bp, uint32_t* d_out_id
         // same with the serial heap replay forced for every scan; 0 = the k_rerank + k_resort pair, which also takes the windows
         // that do not fit the fused kernel's LDS budget (rerank_window_fits)
         const uint32_t fused = env_u32("VS_RERANK_FUSED", 1);
-        if (fused && rerank_window_fits(ix, M, bp.rescore, bp.k)) {
+        if (fused && bp.qual.pops && rerank_window_fits(ix, M, bp.rescore, bp.k)) {
+            hipEvent_t ev = prof_begin(c);
+            VS_TRY(launch_rerank_window_qual(ix, (const float*)w.q_full.p, (const uint32_t*)w.stream_ids.p, (const uint32_t*)w.stream_cnt.p, M,
+                                             bp.rescore, bp.k, nq, d_out_ids, d_out_tids, d_out_dist, fused == 2 ? 2u : 1u, perm, deal, bp.qual));
+            prof_end(c, PK_RERANK, ev);
+            return VS_OK;
+        }
+        if (fused && !bp.qual.pops && rerank_window_fits(ix, M, bp.rescore, bp.k)) {
             hipEvent_t ev = prof_begin(c);
             VS_TRY(launch_rerank_window(ix, (const float*)w.q_full.p, (const uint32_t*)w.stream_ids.p, (const uint32_t*)w.stream_cnt.p, M,
                                         bp.rescore, bp.k, nq, d_out_ids, d_out_tids, d_out_dist, fused == 2 ? 2u : 1u, perm, deal));
@@ -272,6 +279,14 @@ static int run_post_search(vs_index* ix, const BatchPlan& bp, uint32_t* d_out_id
         VS_TRY(launch_rerank(ix, (const float*)w.q_full.p, (const uint32_t*)w.stream_ids.p, nullptr,
                              (const uint32_t*)w.stream_cnt.p, M, nq, (float*)w.rr_dist.p, 0, perm, deal));
         prof_end(c, PK_RERANK, ev);
+    }
+    if (bp.qual.pops) {
+        hipEvent_t ev = prof_begin(c);
+        VS_TRY(launch_resort_qual(ix, nq, M, bp.rescore, bp.k, (const uint32_t*)w.stream_ids.p, (const uint32_t*)w.stream_cnt.p,
+                                  bp.rescore ? (const float*)w.rr_dist.p : nullptr, (uint64_t*)w.resort_heap.p, d_out_ids, d_out_tids, d_out_dist,
+                                  bp.qual));
+        prof_end(c, PK_RESORT, ev);
+        return VS_OK;
     }
     hipEvent_t ev = prof_begin(c);
     VS_TRY(launch_resort(ix, nq, M, bp.rescore, bp.k, (const uint32_t*)w.stream_ids.p, (const uint32_t*)w.stream_cnt.p,
@@ -1228,7 +1243,8 @@ extern "C" int vs_stream_batch(vs_index* ix, const float* queries, const int16_t
 
 int vs_search_batch_dev_impl(vs_index* ix, const float* d_queries, const int16_t* d_qlabels,
                                    const uint32_t* d_qlabel_off, uint32_t nq, uint32_t L, uint32_t rescore, uint32_t k,
-                                   uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, const uint32_t* d_scan_slots) {
+                                   uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, const uint32_t* d_scan_slots,
+                                   const QualLaunch* qual) {
     VS_REQUIRE(ix && (nq == 0 || (d_queries && d_out_ids)), "vs_search_batch_dev: bad args");
     uint32_t vis_mode = BV_INDEX_MASK;
     if (d_scan_slots && nq) {  // the slots come back once, so that a slot without an overlay is refused before anything is launched
@@ -1244,12 +1260,14 @@ int vs_search_batch_dev_impl(vs_index* ix, const float* d_queries, const int16_t
     }
     SearchWorkspace& w = ix->ws;
     w.pending = false;
+    w.qual_pending = false;
     if (nq == 0) return VS_OK;
     VS_HIP(hipSetDevice(ix->ctx->device));
-    const uint32_t M = stream_len(rescore, k);
+    const uint32_t M = stream_len(rescore, qual ? qual->pops : k);  // (a qualified round: a window of up to qual->pops pops)
     Caps caps = initial_caps(ix, L, M);
     VS_REQUIRE(chunk_queries(ix, caps, M, nq) == nq, "vs_search_batch_dev: batch of %u queries exceeds the workspace budget", nq);
     BatchPlan bp{nq, L, rescore, k, M, false, vis_mode, vis_mode == BV_SLOTS ? d_scan_slots : nullptr};
+    if (qual) bp.qual = *qual;
     VS_TRY(run_search_chunk(ix, bp, d_queries, d_qlabels, d_qlabel_off, d_out_ids, d_out_tids, d_out_dist, caps));
     w.pending = true;
     w.pend = PendingBatch{bp, caps, d_qlabels, d_qlabel_off, d_out_ids, d_out_tids, d_out_dist};
@@ -1269,8 +1287,19 @@ extern "C" int vs_search_batch_dev_vis(vs_index* ix, const float* d_queries, con
         return vs_search_batch_dev_impl(ix, d_queries, d_qlabels, d_qlabel_off, nq, L, rescore, k, d_out_ids, d_out_tids, d_out_dist, d_scan_slots);
     });
 }
+// a qualified batch in flight (vs_search_batch_dev_qual) is finished by its own call: its rounds are not over with the launch
+static int refuse_qual_pending(const vs_index* ix, const char* what) {
+    if (ix && ix->ws.qual_pending) {
+        vs_set_error("%s: the batch in flight is a qualified one (vs_search_batch_dev_qual_finish)", what);
+        return VS_ERR_STATE;
+    }
+    return VS_OK;
+}
 extern "C" int vs_search_batch_dev_vis_finish(vs_index* ix, vs_stats* stats) {
-    return vs_guard("vs_search_batch_dev_vis_finish", [&] { return vs_search_batch_dev_finish_impl(ix, stats); });
+    return vs_guard("vs_search_batch_dev_vis_finish", [&]() -> int {
+        VS_TRY(refuse_qual_pending(ix, "vs_search_batch_dev_vis_finish"));
+        return vs_search_batch_dev_finish_impl(ix, stats);
+    });
 }
 
 
@@ -1291,5 +1320,11 @@ int vs_search_batch_dev_finish_impl(vs_index* ix, vs_stats* stats) {
     return VS_OK;
 }
 extern "C" int vs_search_batch_dev_finish(vs_index* ix, vs_stats* stats) {
-    return vs_guard("vs_search_batch_dev_finish", [&] { return vs_search_batch_dev_finish_impl(ix, stats); });
+    return vs_guard("vs_search_batch_dev_finish", [&]() -> int {
+        VS_TRY(refuse_qual_pending(ix, "vs_search_batch_dev_finish"));
+        return vs_search_batch_dev_finish_impl(ix, stats);
+    });
 }
+
+// vs_index_qual_* / vs_search_batch_qual: kernels and host code over the pipeline above
+#include "vs_qual.h"

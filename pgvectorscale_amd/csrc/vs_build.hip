@@ -2676,6 +2676,7 @@ static int compact_impl(vs_index* ix, uint64_t stage_bytes, uint32_t flags, uint
     VS_REQUIRE(stage_bytes >= widest, "%s: stage_bytes %llu holds no row of %zu bytes", what, (unsigned long long)stage_bytes, widest);
     VS_REQUIRE(ix->nbr_stride % 16 == 0, "%s: neighbor rows of %u entries", what, ix->nbr_stride);
     vs_vis_base_drop(ix);  // the classes and the depends list name rows by their old numbers
+    vs_qual_drop_all(ix);  // ... and so do the qualifiers: a bit per OLD node number
     vs_compact_stats s{};
     s.n_before = s.n_after = n;
     if (n == 0 || ix->d.default_start == VS_INVALID_NODE) {

@@ -225,6 +225,22 @@ struct Caps {
     uint32_t f_hl, f_hcap, f_gstride, f_lh, f_gcap, f_sb, f_vr, f_vcap;
     double f_pool_frac;  // share of the scans expected to need a global dedup-overflow table
 };
+// The qualifier side of a launch (vs_search_batch_qual, vs_qual.h).  pops == 0: an unqualified launch.  Otherwise the window pops up to
+// `pops` rows per scan — the stream is M = stream_len(rescore, pops) rows long — and keeps the rows whose node passes the scan's
+// qualifier, up to k.  Scan w of the launch is scan map[w] (or q_base + w) of the BATCH: slots, the output rows and out_* are indexed by
+// the batch's scan numbers.  All pointers DEVICE.
+enum { VS_QUAL_MORE = 3 };  // out_state between rounds: `pops` rows popped, fewer than k kept, the scan not ended, pops < max_pops: run it again
+struct QualLaunch {
+    uint32_t pops = 0;
+    uint32_t q_base = 0;
+    const uint32_t* map = nullptr;
+    const uint32_t* slots = nullptr;
+    const uint64_t* const* tab = nullptr;  // [VS_MAX_QUAL_SLOTS + 1] bitmaps, entry 0 null (QualSet::tab); null: every node passes
+    uint32_t final = 0;                    // the batch's last round: a scan neither complete nor ended after `pops` rows is CUT
+    uint32_t* out_rows = nullptr;
+    uint32_t* out_pops = nullptr;
+    uint32_t* out_state = nullptr;
+};
 // one launch (a chunk of the batch): nq scans of search list L that each leave a stream of M rows
 enum { BV_INDEX_MASK = 0, BV_NONE = 1, BV_SLOTS = 2 };
 struct BatchPlan {
@@ -234,6 +250,7 @@ struct BatchPlan {
     // BV_NONE the caller named slots and every one is 0, BV_SLOTS d_slots (DEVICE [nq]) names each scan's slot (vs_search_batch_vis)
     uint32_t vis_mode = 0;
     const uint32_t* d_slots = nullptr;
+    QualLaunch qual;  // (pops > 0: the window keeps the rows that pass a qualifier; the d_out_* of the launch are the batch's)
 };
 
 // ---- what a launch knows about heap visibility (vs_heap_vis.h) ----------------------------------------------------
@@ -274,6 +291,29 @@ struct PendingBatch {
     float* d_out_dist;
 };
 
+// ---- qualifiers of an index and the qualified batch in flight (vs_qual.h) -------------------------------------------
+// bits[slot]: DEVICE, `words` u64 each (room for the index's capacity), null = empty slot; bits at positions >= the index's n are 0.
+// tab: DEVICE [VS_MAX_QUAL_SLOTS + 1] mirror of bits for the kernels (entry 0 stays null: every node passes)
+struct QualSet {
+    uint64_t* bits[VS_MAX_QUAL_SLOTS + 1] = {nullptr};
+    vs_qual_info info[VS_MAX_QUAL_SLOTS + 1] = {};
+    size_t words = 0;
+    uint64_t** tab = nullptr;
+};
+// what vs_search_batch_dev_qual leaves for its finish: the caller's device pointers and the plan of the rounds
+struct PendingQual {
+    const float* d_queries = nullptr;
+    const int16_t* d_qlabels = nullptr;
+    const uint32_t* d_qlabel_off = nullptr;
+    const uint32_t* d_slots = nullptr;
+    uint32_t nq = 0, L = 0, rescore = 0, k = 0, max_pops = 0, first_pops = 0;
+    bool all_zero = false;   // every scan names slot 0
+    bool launched = false;   // round 1 is in flight as one launch of the batch pipeline
+    uint32_t *d_out_ids = nullptr, *d_out_rows = nullptr, *d_out_pops = nullptr, *d_out_state = nullptr;
+    uint64_t* d_out_tids = nullptr;
+    float* d_out_dist = nullptr;
+};
+
 struct SearchWorkspace {
     DevBuf q_full, qcodes, qlabels, qlabel_off, hash, heap_g, heap_g4, ghash4, heap_g4b, ghash4b, pool_ctr, fb_flag, phase, timeline, stream_ids, stream_ham, stream_cnt, stats, status,
         rr_dist, out_ids, out_tids, out_dist, resort_heap, raw_q, misc, q_index,
@@ -281,7 +321,9 @@ struct SearchWorkspace {
         red,                                      // RED_N u64 sums of the last launch's per-scan arrays (k_reduce_stats)
         order_work, order_perm,                   // VS_RERANK_ORDER: keys + counting-sort tables, and the batch's rerank order
         order_labels,                             // ... and the region label (u16: nearest seed row) of corpus rows [0, lab_rows)
-        vis_slots;                                // the visibility slots of a host batch's scans (vs_search_batch_vis)
+        vis_slots,                                // the visibility slots of a host batch's scans (vs_search_batch_vis)
+        qual_q, qual_map, qual_lab, qual_laboff,  // vs_search_batch_qual: the gathered queries, scan numbers and label keys of a later round
+        qual_slots, qual_out;                     // ... the slots of a host batch, and its rows, counts and states before they go back
     uint32_t order_nq = 0;         // scans of the last batch's rerank order in order_perm (0: it took the scans' own order)
     // what order_labels was built from: the seed rows s * lab_step for s < lab_S of the codes at epoch lab_epoch (vs_index::codes_epoch)
     uint32_t lab_rows = 0, lab_S = 0, lab_step = 0;
@@ -291,6 +333,8 @@ struct SearchWorkspace {
     // pending async call (vs_search_batch_dev)
     bool pending = false;
     PendingBatch pend{};
+    bool qual_pending = false;  // ... of vs_search_batch_dev_qual (pending stays true with it: the same entry points refuse)
+    PendingQual qpend{};
 };
 
 // what the last batches needed (per search_list_size / stream length): sizes the LDS dedup table of the next launch
@@ -347,6 +391,7 @@ struct vs_index {
     const uint8_t* visible = nullptr;  // per node, 0 = the heap fetch finds nothing under the scan's snapshot (nullptr: all visible)
     uint8_t* visible_own = nullptr;    // the library's own copy (vs_index_set_visibility)
     uint8_t* snap[VS_MAX_SNAPSHOTS] = {nullptr};  // per-snapshot masks of shared launches (vs_index_snapshot_put); slot 0 unused
+    QualSet* qs = nullptr;     // the qualifiers of an owner (vs_index_qual_*); a view holds none
     VisBase* vb = nullptr;     // the visibility base and its overlays (vs_index_vis_base_eval); a view's is its source's (vs_index_vis_share)
     float* vecs = nullptr;
     float* vnorm = nullptr;  // per node: 0 => leave vector alone, else divisor sqrt(norm) (preprocess_cosine)
@@ -434,10 +479,12 @@ int download_async_rows(vs_ctx* c, void* dst, const void* src, size_t bytes);  /
 void stage_copy(void* dst, const void* src, size_t n);                         // vs_api.hip: pageable <-> pinned, split over VS_STAGE_THREADS
 int vs_search_batch_dev_impl(vs_index* ix, const float* d_queries, const int16_t* d_qlabels, const uint32_t* d_qlabel_off, uint32_t nq,
                              uint32_t L, uint32_t rescore, uint32_t k, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist,
-                             const uint32_t* d_scan_slots = nullptr);  // vs_batch.hip; d_scan_slots: vs_search_batch_dev_vis
+                             const uint32_t* d_scan_slots = nullptr,   // vs_batch.hip; d_scan_slots: vs_search_batch_dev_vis
+                             const QualLaunch* qual = nullptr);        // qual: a round of vs_search_batch_qual (k kept rows of up to qual->pops)
 int vs_search_batch_dev_finish_impl(vs_index* ix, vs_stats* stats);  // vs_batch.hip
 void vs_vis_base_drop(vs_index* ix);  // vs_heap_vis.h: frees the base and every overlay of an owner (synchronises its stream first)
 void vs_vis_base_free(vs_index* ix);  // ... and the record itself (vs_index_free)
+void vs_qual_drop_all(vs_index* ix);  // vs_qual.h: frees every qualifier of an owner and the record (synchronises its stream first)
 
 // ---- kernel launch wrappers (defined in the .hip files) -------------------------------------------------------
 struct SearchLaunch {
@@ -620,6 +667,11 @@ bool rerank_window_fits(const vs_index* idx, uint32_t M, uint32_t rescore, uint3
 int launch_rerank_window(vs_index* idx, const float* d_q_full, const uint32_t* d_stream_ids, const uint32_t* d_cnt, uint32_t M,
                          uint32_t rescore, uint32_t k, uint32_t nq, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist,
                          uint32_t mode, const uint32_t* d_perm = nullptr, bool deal = false);
+int launch_rerank_window_qual(vs_index* idx, const float* d_q_full, const uint32_t* d_stream_ids, const uint32_t* d_cnt, uint32_t M,
+                              uint32_t rescore, uint32_t k, uint32_t nq, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist,
+                              uint32_t mode, const uint32_t* d_perm, bool deal, const QualLaunch& ql);
+int launch_resort_qual(vs_index* idx, uint32_t nq, uint32_t M, uint32_t rescore, uint32_t k, const uint32_t* d_stream_ids, const uint32_t* d_cnt,
+                       const float* d_dist, uint64_t* d_heap_ws, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, const QualLaunch& ql);
 // VS_RERANK_ORDER: the order in which a batch's rerank workgroups take the scans.  d_perm (null = the scans' own order): place ->
 // scan number; deal: workgroup b takes place (b % 8) * ceil(nq / 8) + b / 8, a contiguous eighth of the order per XCD
 bool scan_order_fits(const vs_index* idx);  // the index has codes k_scan_regions can tile (code rows of up to 38 words)

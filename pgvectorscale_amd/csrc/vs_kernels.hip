@@ -655,6 +655,244 @@ __global__ __launch_bounds__(256, 6) void k_rerank_window(const float* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// The window under a QUALIFIER (vs_search_batch_qual, vs_qual.h): siblings of k_resort and k_rerank_window, kernels of their own so
+// that the ones an unqualified batch runs come out of the compiler as they were.  The window pops up to P rows instead of k; after
+// each pop the popped node's bit of the scan's qualifier is read and the row is kept if it is set; the scan stops at k kept rows.
+// A rejected row has been pushed, reranked and popped like any other — it is left out AFTER the pop, which is what tells a qualifier
+// from a visibility mask.  Scan w of the launch is scan q = map[w] (or q_base + w) of the batch: its qualifier is tab[slots[q]]
+// (slot 0: every node passes) and its rows, counts and state go to row q of the outputs.  state: VS_QUAL_COMPLETE at k kept rows;
+// VS_QUAL_ENDED when the window ran dry before P pops (amgettuple returned None); after P pops without either, VS_QUAL_CUT when
+// this launch is the batch's last round (final), else VS_QUAL_MORE: the host runs the scan again at more pops.
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ const uint64_t* qual_bits_of(const QualLaunch& ql, uint32_t q) {
+    const uint32_t slot = ql.slots ? ql.slots[q] : 0u;
+    return (ql.tab && slot && slot <= VS_MAX_QUAL_SLOTS) ? ql.tab[slot] : nullptr;
+}
+__device__ __forceinline__ bool qual_passes(const uint64_t* bits, uint32_t id) { return !bits || ((bits[id >> 6] >> (id & 63u)) & 1ull); }
+__device__ __forceinline__ uint32_t qual_state(uint32_t kept, uint32_t k, uint32_t pops, uint32_t P, uint32_t final) {
+    return kept == k ? (uint32_t)VS_QUAL_COMPLETE : pops < P ? (uint32_t)VS_QUAL_ENDED : final ? (uint32_t)VS_QUAL_CUT : (uint32_t)VS_QUAL_MORE;
+}
+
+// window_replay with the keep / stop rule: emit(sp) takes every row popped and returns true when the scan has what it wants.
+// Returns the number of rows popped (<= P).
+template <class Emit>
+__device__ __forceinline__ uint32_t window_replay_until(uint64_t* h, const float* sd, uint32_t n, uint32_t rescore, uint32_t P, Emit emit) {
+    uint32_t popped = 0, len = 0, pos = 0;
+    auto kof = [](uint64_t e) { return (int32_t)(uint32_t)(e >> 32); };
+    auto sift_up = [&](uint32_t p, uint64_t elem) {
+        while (p > 0) {
+            uint32_t parent = (p - 1) >> 1;
+            uint64_t pe = h[parent];
+            if (kof(pe) <= kof(elem)) break;
+            h[p] = pe;
+            p = parent;
+        }
+        h[p] = elem;
+    };
+    while (popped < P) {
+        while (len < rescore && pos < n) {
+            uint64_t e = ((uint64_t)(uint32_t)total_key(sd[pos]) << 32) | pos;
+            uint32_t p = len++;
+            sift_up(p, e);
+            ++pos;
+        }
+        if (len == 0) break;
+        uint64_t item = h[--len];
+        uint64_t top = item;
+        if (len > 0) {
+            top = h[0];
+            uint32_t end = len, p = 0, child = 1;
+            uint32_t lim = end >= 2 ? end - 2 : 0;
+            while (child <= lim) {
+                uint64_t le = h[child], ri = h[child + 1];
+                uint32_t pick = (kof(ri) <= kof(le)) ? 1u : 0u;
+                child += pick;
+                h[p] = pick ? ri : le;
+                p = child;
+                child = 2 * p + 1;
+            }
+            if (child == end - 1) {
+                h[p] = h[child];
+                p = child;
+            }
+            sift_up(p, item);
+        }
+        ++popped;
+        if (emit((uint32_t)top)) break;
+    }
+    return popped;
+}
+
+// k_resort under a qualifier: one thread per scan of the launch (the windows the fused kernel does not take, and rescore == 0, where
+// the stream order is the output order and the qualifier filters it directly)
+__global__ void k_resort_qual(uint32_t nq, uint32_t M, uint32_t rescore, uint32_t k, const uint32_t* __restrict__ stream,
+                              const uint32_t* __restrict__ cnt, const float* __restrict__ dist, const uint64_t* __restrict__ tids,
+                              uint64_t* __restrict__ heap_ws, uint32_t* __restrict__ out_ids, uint64_t* __restrict__ out_tids,
+                              float* __restrict__ out_dist, const uint32_t* __restrict__ plain_keys, QualLaunch ql) {
+    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= nq) return;
+    const uint32_t q = ql.map ? ql.map[w] : ql.q_base + w;
+    const uint64_t* bits = qual_bits_of(ql, q);
+    const uint32_t P = ql.pops;
+    const uint32_t n = min(cnt[w], M);
+    const uint32_t* sid = stream + (size_t)w * M;
+    const float* sd = dist ? dist + (size_t)w * M : nullptr;
+    const size_t o = (size_t)q * k;
+    uint32_t kept = 0, pops = 0;
+    if (rescore == 0) {
+        for (; pops < P && pops < n && kept < k; ++pops) {
+            const uint32_t id = sid[pops];
+            if (!qual_passes(bits, id)) continue;
+            out_ids[o + kept] = id;
+            if (out_tids) out_tids[o + kept] = tids[id];
+            if (out_dist) out_dist[o + kept] = plain_keys ? plain_unkey(plain_keys[(size_t)w * M + pops]) : __int_as_float(0x7fc00000);
+            ++kept;
+        }
+    } else {
+        pops = window_replay_until(heap_ws + (size_t)w * rescore, sd, n, rescore, P, [&](uint32_t sp) {
+            const uint32_t id = sid[sp];
+            if (qual_passes(bits, id)) {
+                out_ids[o + kept] = id;
+                if (out_tids) out_tids[o + kept] = tids[id];
+                if (out_dist) out_dist[o + kept] = sd[sp];
+                ++kept;
+            }
+            return kept == k;
+        });
+    }
+    for (uint32_t j = kept; j < k; ++j) {
+        out_ids[o + j] = VS_INVALID_NODE;
+        if (out_tids) out_tids[o + j] = 0;
+        if (out_dist) out_dist[o + j] = __int_as_float(0x7fc00000);
+    }
+    ql.out_rows[q] = kept;
+    ql.out_pops[q] = pops;
+    ql.out_state[q] = qual_state(kept, k, pops, P, ql.final);
+}
+
+// k_rerank_window under a qualifier.  The rerank is k_rerank_window's; wave 0 then runs the selection for up to P pops: the popped
+// position is known to every lane (its holder's lane and bit), so the node id, the qualifier bit and the count of kept rows are
+// wave-uniform and sps[] still holds at most k positions — the LDS layout and size are k_rerank_window's at the same (M, rescore, k).
+// A minimum held by two live entries sends the scan to the serial replay from the start, with the same keep / stop rule.
+// The rows kept and the pops made are wave-uniform registers of wave 0.
+__global__ __launch_bounds__(256, 6) void k_rerank_window_qual(const float* __restrict__ vecs, uint32_t vec_stride, uint32_t dim_full,
+                                                            const float* __restrict__ vnorm, uint32_t distance_type,
+                                                            const float* __restrict__ q_full, const uint32_t* __restrict__ stream,
+                                                            const uint32_t* __restrict__ cnt, uint32_t M, uint32_t rescore, uint32_t k,
+                                                            uint32_t nq, const uint64_t* __restrict__ tids, uint32_t* __restrict__ out_ids,
+                                                            uint64_t* __restrict__ out_tids, float* __restrict__ out_dist, uint32_t mode,
+                                                            const uint32_t* __restrict__ perm, uint32_t deal, QualLaunch ql) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float* qv = reinterpret_cast<float*>(smem);
+    uint64_t* hh = reinterpret_cast<uint64_t*>(qv + vec_stride);
+    float* sd = reinterpret_cast<float*>(hh + rescore);
+    uint32_t* sps = reinterpret_cast<uint32_t*>(sd + M);
+    const uint32_t slot = rerank_slot(blockIdx.x, nq, deal);
+    if (slot >= nq) return;
+    const uint32_t w = perm ? perm[slot] : slot;
+    for (uint32_t i = threadIdx.x; i < vec_stride; i += blockDim.x) qv[i] = q_full[(size_t)w * vec_stride + i];
+    const uint32_t n = min(cnt[w], M);
+    const uint32_t* sid = stream + (size_t)w * M;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int l8 = lane & 7, grp = lane >> 3;
+    const uint32_t steps = dim_full / 32;
+    for (uint32_t base = 0; base < n; base += 32) {
+        const uint32_t j = base + (uint32_t)(wave * 8 + grp);
+        bool valid = j < n;
+        const uint32_t id = valid ? sid[j] : VS_INVALID_NODE;
+        if (id == VS_INVALID_NODE) valid = false;
+        const float* row = vecs + (size_t)(valid ? id : 0) * vec_stride;
+        float s = 0.0f;
+        if (valid && distance_type == VS_COSINE) s = vnorm[id];
+        const float r = rerank_row_dist(row, qv, s, distance_type, steps, dim_full, lane, l8, valid);
+        if (j < n && l8 == 0) sd[j] = valid ? r : __int_as_float(0x7fc00000);
+    }
+    __syncthreads();
+    const uint32_t q = ql.map ? ql.map[w] : ql.q_base + w;
+    const uint32_t P = ql.pops;
+    uint32_t kept = 0, pops = 0;  // (wave-uniform in wave 0, which is the only one to use them)
+    if (wave == 0) {
+        const uint64_t* bits = qual_bits_of(ql, q);
+        bool replay = mode == 2;
+        if (!replay) {
+            uint64_t taken = 0;  // bit j: this lane's position lane + 64 j has been popped (M <= 4096)
+            for (uint32_t i = 0; i < P && kept < k; ++i) {
+                const uint32_t limit = min(rescore + i, n);
+                if (limit <= i) break;  // the heap is empty
+                const int64_t none = 0x7fffffffffffffffll;
+                int64_t best = none;
+                uint32_t bj = 0, c = 0;
+                for (uint32_t j = 0, p = (uint32_t)lane; p < limit; ++j, p += 64) {
+                    if ((taken >> j) & 1ull) continue;
+                    const int64_t key = total_key(sd[p]);
+                    if (key < best) {
+                        best = key;
+                        bj = j;
+                        c = 1;
+                    } else if (key == best) {
+                        ++c;
+                    }
+                }
+                int64_t wbest = best;
+                for (int m = 1; m < WAVE; m <<= 1) {
+                    const int64_t o = __shfl_xor(wbest, m, WAVE);
+                    wbest = o < wbest ? o : wbest;
+                }
+                const bool mine = best == wbest && best != none;
+                const uint64_t holders = __ballot(mine);
+                if (__popcll(holders) != 1 || __ballot(mine && c > 1) != 0) {
+                    replay = true;
+                    break;
+                }
+                if (mine) taken |= 1ull << bj;
+                const int holder = (int)__builtin_ctzll(holders);
+                const uint32_t sp = (uint32_t)holder + 64u * (uint32_t)__shfl((int)bj, holder, WAVE);
+                ++pops;
+                if (qual_passes(bits, sid[sp])) {  // (wave-uniform)
+                    if (lane == 0) sps[kept] = sp;
+                    ++kept;
+                }
+            }
+        }
+        if (replay) {  // (from the start: rows kept before the tie are produced again)
+            kept = 0;
+            uint32_t kk = 0, pp = 0;
+            if (lane == 0) {
+                pp = window_replay_until(hh, sd, n, rescore, P, [&](uint32_t sp) {
+                    if (qual_passes(bits, sid[sp])) sps[kk++] = sp;
+                    return kk == k;
+                });
+            }
+            kept = (uint32_t)__shfl((int)kk, 0, WAVE);
+            pops = (uint32_t)__shfl((int)pp, 0, WAVE);
+        }
+    }
+    __syncthreads();  // (the positions lane 0 stored, for all of wave 0)
+    if (wave != 0) return;
+    const size_t o = (size_t)q * k;
+    for (uint32_t j = (uint32_t)lane; j < k; j += WAVE) {
+        uint32_t id = VS_INVALID_NODE;
+        uint64_t tid = 0;
+        float d = __int_as_float(0x7fc00000);
+        if (j < kept) {
+            const uint32_t sp = sps[j];
+            id = sid[sp];
+            if (out_tids) tid = tids[id];
+            d = sd[sp];
+        }
+        out_ids[o + j] = id;
+        if (out_tids) out_tids[o + j] = tid;
+        if (out_dist) out_dist[o + j] = d;
+    }
+    if (lane == 0) {
+        ql.out_rows[q] = kept;
+        ql.out_pops[q] = pops;
+        ql.out_state[q] = qual_state(kept, k, pops, P, ql.final);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // The order in which a batch's rerank workgroups take the scans (VS_RERANK_ORDER).  A batch whose scans fetch more rows than the
 // corpus has (nq * M > n) reads every row several times; the repeats only hit cache when the scans that share a row run at the same
 // time.  So the scans are grouped by where in the corpus they look: S seed rows (the SBQ codes of corpus rows i * (n / S), read in place
@@ -1179,6 +1417,32 @@ int launch_rerank_window(vs_index* idx, const float* d_q_full, const uint32_t* d
     hipLaunchKernelGGL(k_rerank_window, dim3(rerank_grid(nq, deal)), dim3(256), lds, idx->ctx->stream, idx->vecs, idx->vec_stride,
                        idx->d.dim_full, idx->vnorm, idx->d.distance_type, d_q_full, d_stream_ids, d_cnt, M, rescore, k, nq, idx->tids,
                        d_out_ids, d_out_tids, d_out_dist, mode, d_perm, deal ? 1u : 0u);
+    VS_HIP(hipGetLastError());
+    return VS_OK;
+}
+
+// the same two launches under a qualifier (ql.pops > 0): d_out_* are the BATCH's rows, indexed by the batch's scan numbers
+int launch_resort_qual(vs_index* idx, uint32_t nq, uint32_t M, uint32_t rescore, uint32_t k, const uint32_t* d_stream_ids, const uint32_t* d_cnt,
+                       const float* d_dist, uint64_t* d_heap_ws, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, const QualLaunch& ql) {
+    if (nq == 0) return VS_OK;
+    const uint32_t* plain_keys = (idx->d.storage_type == VS_STORAGE_PLAIN && idx->d.dim_index == idx->d.dim_full)
+                                     ? (const uint32_t*)idx->ws.stream_ham.p : nullptr;
+    hipLaunchKernelGGL(k_resort_qual, dim3((nq + 63) / 64), dim3(64), 0, idx->ctx->stream, nq, M, rescore, k, d_stream_ids, d_cnt, d_dist,
+                       idx->tids, d_heap_ws, d_out_ids, d_out_tids, d_out_dist, plain_keys, ql);
+    VS_HIP(hipGetLastError());
+    return VS_OK;
+}
+
+int launch_rerank_window_qual(vs_index* idx, const float* d_q_full, const uint32_t* d_stream_ids, const uint32_t* d_cnt, uint32_t M,
+                              uint32_t rescore, uint32_t k, uint32_t nq, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist,
+                              uint32_t mode, const uint32_t* d_perm, bool deal, const QualLaunch& ql) {
+    if (nq == 0) return VS_OK;
+    VS_REQUIRE(idx->vecs != nullptr, "index has no vector column: rerank impossible");
+    VS_REQUIRE(rescore > 0 && rerank_window_fits(idx, M, rescore, k), "fused rerank: window of %u rows does not fit", M);
+    const size_t lds = rerank_window_lds(idx->vec_stride, M, rescore, k);
+    hipLaunchKernelGGL(k_rerank_window_qual, dim3(rerank_grid(nq, deal)), dim3(256), lds, idx->ctx->stream, idx->vecs, idx->vec_stride,
+                       idx->d.dim_full, idx->vnorm, idx->d.distance_type, d_q_full, d_stream_ids, d_cnt, M, rescore, k, nq, idx->tids,
+                       d_out_ids, d_out_tids, d_out_dist, mode, d_perm, deal ? 1u : 0u, ql);
     VS_HIP(hipGetLastError());
     return VS_OK;
 }

@@ -737,6 +737,91 @@ class DiskAnnIndex:
         check(self._L.vs_search_batch_dev_finish(self.h, C.byref(st)))
         return st.as_dict()
 
+    # -- qualified scans: the first k rows that pass a per-scan node bitmap (include/vsgpu.h, "qualified scans") ---------
+    def _qual_words(self):
+        return (self.desc.n + 63) // 64
+
+    def qual_put(self, slot, bits):
+        """fills qualifier `slot` (1..64): a bool / 0-1 array with one entry per node, or uint64 words (node i at bit i & 63 of word
+        i >> 6, (n + 63) // 64 of them; bits at positions >= n are cleared by the library)"""
+        self._refresh()
+        a = np.asarray(bits)
+        if a.dtype != np.uint64:
+            a = np.asarray(a).astype(bool).ravel()
+            if a.size != self.desc.n:
+                raise ValueError(f"a qualifier has one entry per node ({self.desc.n}), got {a.size}")
+            a = np.packbits(np.concatenate([a, np.zeros(-a.size % 64, bool)]), bitorder="little").view(np.uint64)
+        a = np.ascontiguousarray(a, np.uint64).ravel()
+        if a.size < self._qual_words():
+            raise ValueError(f"{a.size} words do not hold {self.desc.n} nodes")
+        check(self._L.vs_index_qual_put(self.h, slot, _p(a) if a.size else None))
+
+    def qual_put_dev(self, slot, d_bits):
+        """the same from (n + 63) // 64 uint64 words in device memory"""
+        check(self._L.vs_index_qual_put_dev(self.h, slot, d_bits))
+
+    def qual_from_tids(self, slot, tids):
+        """the qualifier of the live nodes whose heap TID is in `tids` ((block << 16) | offset, unsorted, duplicates allowed) ->
+        {"n_nodes", "n_set", "tids_unmatched"}"""
+        a = np.ascontiguousarray(tids, np.uint64).ravel()
+        info = _lib.QualInfo()
+        check(self._L.vs_index_qual_from_tids(self.h, slot, _p(a) if a.size else None, a.size, C.byref(info)))
+        return info.as_dict()
+
+    def qual_from_tids_dev(self, slot, d_tids_sorted, n_tids):
+        """the same with the TIDs in device memory, sorted ascending"""
+        info = _lib.QualInfo()
+        check(self._L.vs_index_qual_from_tids_dev(self.h, slot, d_tids_sorted, n_tids, C.byref(info)))
+        return info.as_dict()
+
+    def qual_info(self, slot):
+        info = _lib.QualInfo()
+        check(self._L.vs_index_qual_info(self.h, slot, C.byref(info)))
+        return info.as_dict()
+
+    def qual_download(self, slot):
+        """the qualifier of `slot` as a bool array, one entry per node"""
+        self._refresh()
+        w = np.zeros(max(self._qual_words(), 1), np.uint64)
+        check(self._L.vs_index_qual_get(self.h, slot, _p(w)))
+        return np.unpackbits(w.view(np.uint8), bitorder="little")[:self.desc.n].astype(bool)
+
+    def qual_drop(self, slot):
+        check(self._L.vs_index_qual_drop(self.h, slot))
+
+    def search_batch_qual(self, queries, qual_slots, k=10, max_pops=None, search_list_size=DEFAULT_QUERY_SEARCH_LIST_SIZE,
+                          rescore=DEFAULT_QUERY_RESCORE, qlabels=None):
+        """For each query: the first k rows of its amgettuple sequence whose node passes the qualifier in qual_slots[q] (0: every
+        node), looking at no more than max_pops rows (default: k) -> ids, tids, dist [nq, k], rows, pops, state [nq] (state:
+        _lib.QUAL_COMPLETE / QUAL_ENDED / QUAL_CUT), stats (the device's work over all rounds), qstats (the rounds)."""
+        q = np.ascontiguousarray(queries, np.float32).reshape(-1, self.desc.dim_full)
+        nq = q.shape[0]
+        max_pops = k if max_pops is None else max_pops
+        lv, lo = self._label_keys(qlabels, nq)
+        sl = np.ascontiguousarray(qual_slots, np.uint32).ravel()
+        if sl.shape != (nq,):
+            raise ValueError(f"qual_slots must have shape ({nq},), got {sl.shape}")
+        sl = sl if nq else np.zeros(1, np.uint32)
+        ids = np.empty((nq, k), np.uint32)
+        tids = np.empty((nq, k), np.uint64)
+        dist = np.empty((nq, k), np.float32)
+        rows, pops, state = (np.empty(max(nq, 1), np.uint32) for _ in range(3))
+        st, qst = Stats(), _lib.QualBatchStats()
+        check(self._L.vs_search_batch_qual(self.h, _p(q), _p(lv), _p(lo), nq, search_list_size, rescore, k, _p(sl), max_pops, _p(ids),
+                                           _p(tids), _p(dist), _p(rows), _p(pops), _p(state), C.byref(st), C.byref(qst)))
+        return ids, tids, dist, rows[:nq], pops[:nq], state[:nq], st.as_dict(), qst.as_dict()
+
+    def search_batch_dev_qual(self, d_queries, nq, search_list_size, rescore, k, d_qual_slots, max_pops, d_out_ids, d_out_rows, d_out_pops,
+                              d_out_state, d_out_tids=None, d_out_dist=None, d_qlabels=None, d_qlabel_off=None):
+        """the device-resident form: every pointer is device memory and stays valid until search_batch_dev_qual_finish()"""
+        check(self._L.vs_search_batch_dev_qual(self.h, d_queries, d_qlabels, d_qlabel_off, nq, search_list_size, rescore, k, d_qual_slots,
+                                               max_pops, d_out_ids, d_out_tids, d_out_dist, d_out_rows, d_out_pops, d_out_state))
+
+    def search_batch_dev_qual_finish(self):
+        st, qst = Stats(), _lib.QualBatchStats()
+        check(self._L.vs_search_batch_dev_qual_finish(self.h, C.byref(st), C.byref(qst)))
+        return st.as_dict(), qst.as_dict()
+
     def autotune(self, d_queries, nq, search_list_size, rescore, k, d_qlabels=None, d_qlabel_off=None, reps=2, skip=()):
         """vs_index_autotune: times every applicable exact launch variant of the search kernel on this device-resident batch,
         disqualifies any whose rows / distance bits / counters differ from the default's, keeps the fastest -> report (list of dicts)"""
