@@ -1534,7 +1534,8 @@ int vs_bruteforce_topk(vs_index* idx, const float* d_queries, uint32_t nq, uint3
  * of the index when the slot was filled, n_set the bits set, tids_unmatched the distinct tids of the list that no live node carries
  * (0 after a _put).  vs_index_qual_info reads the record of a slot, vs_index_qual_drop frees it (VS_ERR_STATE for an empty slot).
  * LIFETIME: vs_index_reserve and growing inserts carry the qualifiers over, rows added later read 0 and do not qualify;
- * vs_index_compact renumbers the nodes and DROPS every qualifier.  Refusals, each before anything is written: NULL arguments, slot 0
+ * vs_index_compact renumbers the nodes and DROPS every qualifier (one that VS_COMPACT_KEEP_EDGES_CHECK refuses drops none: every byte
+ * stays as it was).  Refusals, each before anything is written: NULL arguments, slot 0
  * or a slot > VS_MAX_QUAL_SLOTS (VS_ERR_INVALID); a view handle, a batch of the handle in flight (VS_ERR_STATE).
  *
  * THE BATCH.  vs_search_batch_qual(.., k, qual_slots [nq] HOST, max_pops, ..): max_pops in [k, VS_QUAL_MAX_POPS] and qual_slots != NULL,

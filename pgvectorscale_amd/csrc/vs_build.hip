@@ -2675,11 +2675,16 @@ static int compact_impl(vs_index* ix, uint64_t stage_bytes, uint32_t flags, uint
     }
     VS_REQUIRE(stage_bytes >= widest, "%s: stage_bytes %llu holds no row of %zu bytes", what, (unsigned long long)stage_bytes, widest);
     VS_REQUIRE(ix->nbr_stride % 16 == 0, "%s: neighbor rows of %u entries", what, ix->nbr_stride);
-    vs_vis_base_drop(ix);  // the classes and the depends list name rows by their old numbers
-    vs_qual_drop_all(ix);  // ... and so do the qualifiers: a bit per OLD node number
+    // Dropped by every compaction that goes ahead, but not by one VS_COMPACT_KEEP_EDGES_CHECK refuses ("every byte as it was"): the
+    // classes and the depends list name rows by their old numbers, and so do the qualifiers (a bit per OLD node number)
+    auto drop_numbered = [&]() {
+        vs_vis_base_drop(ix);
+        vs_qual_drop_all(ix);
+    };
     vs_compact_stats s{};
     s.n_before = s.n_after = n;
     if (n == 0 || ix->d.default_start == VS_INVALID_NODE) {
+        drop_numbered();
         if (out) *out = s;
         return VS_OK;
     }
@@ -2759,6 +2764,7 @@ static int compact_impl(vs_index* ix, uint64_t stage_bytes, uint32_t flags, uint
                          what, (unsigned long long)s.edges_cut);
             return VS_ERR_STATE;
         }
+        drop_numbered();
         VS_REQUIRE(n_after >= 1 && n_after <= n && (n_after == n) == (first == n), "%s: %u of %u nodes kept, first dropped %u", what, n_after, n, first);
         if (out_new_of) VS_HIP(hipMemcpy(out_new_of, d_new_of, (size_t)n * 4, hipMemcpyDeviceToHost));
         if (n_after == n) return VS_OK;  // nothing in D: nothing is written

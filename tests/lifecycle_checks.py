@@ -154,9 +154,9 @@ def check_stream_batch(ix, oidx, q, qlabels=None, where=""):
         assert gst[key] == ost[key], (where, key, gst[key], ost[key])
 
 
-def pull_and_compare(scan, oscan, rows=CURSOR_ROWS, checkpoints=CURSOR_CHECKPOINTS, where="", stats=True):
-    """amgettuple one row at a time against the oracle's streaming scan: rows, heap tids, distance bits; GreedySearchStats at the
-    checkpoints -> rows pulled"""
+def pull_and_compare(scan, oscan, rows=CURSOR_ROWS, checkpoints=CURSOR_CHECKPOINTS, where="", stats=True, keys=CURSOR_KEYS):
+    """amgettuple one row at a time against the oracle's streaming scan: rows, heap tids, distance bits; GreedySearchStats (`keys`)
+    at the checkpoints -> rows pulled"""
     pulled = 0
     while pulled < rows:
         r, o = scan.gettuple(), oscan.gettuple()
@@ -168,7 +168,7 @@ def pull_and_compare(scan, oscan, rows=CURSOR_ROWS, checkpoints=CURSOR_CHECKPOIN
         pulled += 1
         if stats and pulled in checkpoints:
             g, ref = scan.stats(), oscan.stats()
-            for key in CURSOR_KEYS:
+            for key in keys:
                 assert g[key] == ref[key], (where, pulled, key, g[key], ref[key])
     return pulled
 
@@ -182,7 +182,7 @@ def check_cursor(ix, oidx, query, labels=None, where=""):
         scan.endscan()
 
 
-def check_pool_slot(pool, slot, oscan, k, rounds, where=""):
+def check_pool_slot(pool, slot, oscan, k, rounds, where="", keys=CURSOR_KEYS):
     """`rounds` chunks of k rows of one pool slot against the oracle's scan (as tests/test_gpu_zt_scanpool.py checks a chunk)"""
     for rnd in range(rounds):
         rows, ids, tids, dist = pool.fetch([slot], k)
@@ -198,17 +198,45 @@ def check_pool_slot(pool, slot, oscan, k, rounds, where=""):
             n += 1
         assert rows[0] == n, (where, rnd, rows[0], n)
         g, ref = pool.stats(slot), oscan.stats()
-        for key in CURSOR_KEYS:
+        for key in keys:
             assert g[key] == ref[key], (where, rnd, key, g[key], ref[key])
         if n < k:
             break
 
 
-def check_index_everywhere(ix, O, distance, q, keys=None, *, label_starts=None, label_sets=None, visible=None, snapshots=None, where=""):
+QUAL = dict(k=10, max_pops=64)
+
+
+def check_qualifier(ix, oidx, q, qualifier, where="", L=SEARCH["L"], rescore=SEARCH["rescore"]):
+    """qualifier = (slot, the bits the slot was filled with — fewer than n when rows were added since).  The slot holds those bits and
+    zeros behind them (include/vsgpu.h, qualified scans, LIFETIME: "vs_index_reserve and growing inserts carry the qualifiers over,
+    rows added later read 0 and do not qualify"); scans that name it, dealt among unqualified ones, are the oracle's rows
+    post-filtered on the host (tests/qual_checks.py), under whatever mask is in force on the oracle"""
+    import qual_checks as QC
+    slot, bits = qualifier
+    n = ix.desc.n
+    bits = np.asarray(bits, bool)
+    assert bits.size <= n, where
+    want = np.concatenate([bits, np.zeros(n - bits.size, bool)])
+    now = ix.qual_download(slot)
+    assert now.shape == (n,) and (now[:bits.size] == bits).all(), (where, "qualifier bits")
+    assert not now[bits.size:].any(), (where, "rows added later read 0")
+    assert ix.qual_info(slot)["n_set"] == int(bits.sum()), where
+    slots = np.where(np.arange(len(q)) % 2 == 0, slot, 0).astype(np.uint32)
+    exp = QC.expect(oidx, oidx.heap_tids, q, {slot: want}, slots, L, rescore, QUAL["k"], QUAL["max_pops"])
+    got = ix.search_batch_qual(q, slots, k=QUAL["k"], max_pops=QUAL["max_pops"], search_list_size=L, rescore=rescore)
+    QC.assert_equal(got, exp, (where, "qualified scans"))
+    picked = got[0][slots == slot]
+    assert want[picked[picked != INV]].all(), where
+
+
+def check_index_everywhere(ix, O, distance, q, keys=None, *, label_starts=None, label_sets=None, visible=None, snapshots=None, qualifier=None,
+                           where=""):
     """ix: a live DiskAnnIndex; O: the oracle module; q: queries [nq][dim_full]; keys: one non-empty label key per query (a labeled
     index).  label_starts {label: start node} / label_sets (one sorted list per node): what the test knows the index must hold.
     visible: the mask the test put in force with set_visibility, as it must stand NOW (uint8 [n]); snapshots: {id: mask as it
-    must stand now} of the stored snapshots the batched search and the cursor are also run under.  -> (downloaded arrays, the OracleIndex)"""
+    must stand now} of the stored snapshots the batched search and the cursor are also run under; qualifier: (slot, bits) as
+    check_qualifier takes it.  -> (downloaded arrays, the OracleIndex)"""
     from pgvectorscale_amd import _lib
     ix._refresh()
     d = ix.desc
@@ -261,6 +289,10 @@ def check_index_everywhere(ix, O, distance, q, keys=None, *, label_starts=None, 
     check_cursor(ix, oidx, q[0], None, (where, "cursor"))
     if labeled:
         check_cursor(ix, oidx, q[1], keys[1], (where, "cursor keyed"))
+
+    # -- qualified scans, under the mask in force
+    if qualifier is not None:
+        check_qualifier(ix, oidx, q, qualifier, where)
 
     # -- the stored snapshots
     for sid, smask in sorted((snapshots or {}).items()):

@@ -16,6 +16,7 @@ from consolidate_plain_checks import COUNTERS, WatchedRule, twin
 from helpers import make_vectors
 from lifecycle_checks import make_tids, well_formed
 from oracle import oracle_py as O
+from plain_lifecycle_checks import check_plain_everywhere
 from oracle import pages_py as PG
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(900)]
@@ -246,17 +247,11 @@ def test_nothing_deleted_nothing_changes_and_a_second_call_rewrites_nothing(gpu_
 
 
 # ---- case 5: the full call ------------------------------------------------------------------------------------------------------------
-def _oracle_plain(host, *, distance, dim_index, R, start):
-    n = host["vecs"].shape[0]
-    w = (dim_index + 63) // 64
-    return O.OracleIndex(codes=np.zeros((n, w), np.uint64), nbrs=host["nbrs"], heap_tids=host["heap_tids"], vecs=host["vecs"],
-                         mean=np.zeros(dim_index, np.float32), m2=np.zeros(dim_index, np.float32), count=0, bits=1, dim_index=dim_index,
-                         num_neighbors=R, distance_type=distance, default_start=start, storage_plain=True)
-
-
 def _scans_equal_the_oracle(ix, q, *, distance, dim_index, L=40, rescore=50, k=10):
-    host = _arrays(ix)
-    oidx = _oracle_plain(host, distance=distance, dim_index=dim_index, R=ix.desc.num_neighbors, start=ix.desc.default_start)
+    """every plain entry point against the oracle over the arrays as they stand (check_plain_everywhere: both search kernels and the
+    hand-over, stream, cursor, pools, brute force); then the default batch once more for what this file adds -> its ids"""
+    assert ix.desc.dim_index == dim_index
+    host, oidx = check_plain_everywhere(ix, O, distance, q, where="after the consolidation")
     gi, gt, gd, gst = ix.search_batch(q, search_list_size=L, rescore=rescore, k=k)
     oi, od, ost = oidx.search_batch(q, L=L, rescore=rescore, k=k)
     assert (gi == oi).all() and (gd.view(np.uint32) == od.view(np.uint32)).all() and gst["visited_nodes"] == ost["visited_nodes"]

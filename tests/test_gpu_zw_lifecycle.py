@@ -34,6 +34,7 @@ class Chain:
         self.tids = make_tids(0, n0)
         self.own = None      # the mask set_visibility put in force, grown by ones
         self.snaps = {}      # {id: mask} of the stored snapshots, grown by zeros
+        self.qual = None     # (slot, bits as they were put): carried over a growth, rows added later read 0
         self.sets = self.first = None
         ix = fresh_index(gpu_ctx, self.rows[:n0], distance=distance, bits=bits, dim_index=dim_index, R=R, L=L_BUILD, tids=self.tids,
                          build=not labeled)
@@ -111,9 +112,15 @@ class Chain:
         self.own = None if mask is None else np.ascontiguousarray(mask, np.uint8)
         self.ix.set_visibility(self.own)
 
+    def qual_put(self, slot, bits):
+        bits = np.ascontiguousarray(bits, bool)
+        assert bits.shape == (self.n,)
+        self.ix.qual_put(slot, bits)
+        self.qual = (slot, bits)
+
     def check(self, where):
         host, oidx = check_index_everywhere(self.ix, self.O, self.distance, self.q, self.keys, label_starts=self.first, label_sets=self.sets,
-                                            visible=self.own, snapshots=self.snaps, where=where)
+                                            visible=self.own, snapshots=self.snaps, qualifier=self.qual, where=where)
         assert (host["heap_tids"] == self.tids).all(), where
         assert host["vecs"].tobytes() == self.rows[:self.n].tobytes(), where
         return host, oidx
@@ -163,6 +170,7 @@ def test_chain_a_unlabeled_grow_vacuum_grow_vacuum_reserve(gpu_ctx, oracle, geom
     ch = Chain(gpu_ctx, oracle, seed=1, **GEOM_A[geom])
     try:
         n0 = ch.n
+        ch.qual_put(5, np.random.default_rng(12).random(n0) < 0.4)             # (carried through every growth and reserve below)
         ch.check("built")                                                      # 1
         assert ch.insert(65)["grew"] == 1                                      # 2: just over one wave, past the capacity of the upload
         ch.check("insert 65")
