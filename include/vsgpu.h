@@ -141,7 +141,9 @@ int vs_index_last_search_info(const vs_index* idx, vs_search_info* out);
  * resumable form of k_search_plain, one wave per pool slot with the scan's state on chip during a launch and saved per slot between
  * launches, where that state fits 96 KB of LDS; "0" (or VS_POOL_FAST "0") the general kernel.  Read when a pool is created, as
  * are VS_PF_HEAP_LDS / VS_PF_HEAP_CAP / VS_PF_DEDUP_SLOTS / VS_PF_VISITED, which override the pool's planned capacities too (a pooled
- * scan that outgrows one fails with VS_ERR_CAPACITY).  Rows, distance bits and the reference counters are the same under both. */
+ * scan that outgrows one fails with VS_ERR_CAPACITY).  Rows, distance bits and the reference counters are the same under both.
+ * VS_POOL_QUAL_CHUNK: the pops ONE window launch of vs_scanpool_fetch_qual may make per scan (default 4096, capped so that the launch
+ * stays within 64 KB of LDS); a fetch that needs more launches again.  A cost choice: no row, count or state depends on it. */
 int vs_set_option(const char* name, const char* value);
 int vs_get_option(const char* name, char* out, size_t cap);
 const char* vs_version(void);
@@ -1554,8 +1556,9 @@ int vs_bruteforce_topk(vs_index* idx, const float* d_queries, uint32_t nq, uint3
  * over capacity retries: it is not the reference's GreedySearchStats of the qualified scan.
  * vs_search_batch_dev_qual takes DEVICE queries, label keys (sorted and de-duplicated per query, as vs_search_batch_dev), slots and
  * outputs (all of which stay valid until the finish); it checks the arguments and launches round 1;
- * vs_search_batch_dev_qual_finish runs the remaining rounds and fills the outputs.  Per-scan visibility slots together with
- * qualifiers, scan pools, cursors, the broker, the shm server and vs_multi with qualifiers are not built. */
+ * vs_search_batch_dev_qual_finish runs the remaining rounds and fills the outputs.  Scan pools take qualifiers through
+ * vs_scanpool_fetch_qual (below).  Per-scan visibility slots together with qualifiers, and the single cursor (vs_gettuple), the broker,
+ * the shm server and vs_multi with qualifiers are not built. */
 #define VS_MAX_QUAL_SLOTS 64
 #define VS_QUAL_MAX_POPS 65536
 enum { VS_QUAL_COMPLETE = 0, VS_QUAL_ENDED = 1, VS_QUAL_CUT = 2 };
@@ -1587,6 +1590,61 @@ int vs_search_batch_dev_qual(vs_index* idx, const float* d_queries, const int16_
                              uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, uint32_t* d_out_rows, uint32_t* d_out_pops,
                              uint32_t* d_out_state);
 int vs_search_batch_dev_qual_finish(vs_index* idx, vs_stats* stats, vs_qual_batch_stats* qstats);
+
+/* ---- qualified scan pools: a pooled scan continued to its next k qualifying rows (vs_scanpool.cpp) ----
+ * vs_search_batch_qual is one-shot: it re-runs a scan that has not finished at P pops from the start at 2 P, and a scan that comes
+ * back VS_QUAL_CUT can only be taken further by running it again.  A scan pool continues its scans on the device and never re-runs
+ * one, so here a qualified scan costs the pops it needs, a CUT scan is resumable, and the next k qualifying rows — `FETCH k` from a
+ * cursor over `ORDER BY embedding <=> $1 ... WHERE ...` — are one call.
+ *
+ * SEMANTICS.  Let slot s have made c amgettuple calls so far, those of earlier vs_scanpool_fetch AND vs_scanpool_fetch_qual calls
+ * alike: the two share one cursor and may be interleaved freely.  The call makes the reference's calls c, c + 1, ... and stops at the
+ * first of four events: k of the returned rows have their node's bit set in qualifier qual_slots[i] (0: every node passes); a call
+ * returns None; max_pops calls of THIS fetch have returned a row; the pool's row budget is reached.  The rows that pass are returned
+ * in that order with the tid and the distance bits vs_scanpool_fetch would have given them.  A rejected row is consumed: it was
+ * reranked, it held its place in the rescore window, and it counts as a call.  Per listed slot:
+ *   out_rows[i]   rows returned (<= k), or a negative VS_ERR_* as in vs_scanpool_fetch (that scan failed, the others are served);
+ *                 entries past out_rows[i] are not written, as in vs_scanpool_fetch
+ *   out_pops[i]   calls of this fetch that returned a row
+ *   out_state[i]  VS_QUAL_COMPLETE  k rows were returned
+ *                 VS_QUAL_ENDED     a call returned None.  That call is booked as vs_scanpool_fetch books it; a further fetch_qual of the
+ *                                   slot returns 0 rows, 0 pops and ENDED (and books one more such call)
+ *                 VS_QUAL_CUT       max_pops rows were looked at in this fetch; the next fetch goes on from there
+ *                 VS_QUAL_BUDGET    the scan has not been seen to end and its next pop would stand on more than rows_cap stream rows:
+ *                                   the rows kept so far are returned, the cursor has advanced by out_pops, and any later fetch of the
+ *                                   slot returns VS_ERR_CAPACITY, as it does today.  A slot that can make no pop at all returns
+ *                                   VS_ERR_CAPACITY at once.
+ * After any sequence of fetch and fetch_qual calls vs_scanpool_get_stats equals the reference scan's GreedySearchStats after the same
+ * amgettuple calls (the counters are per emitted stream row: stream rows carried ahead do not show).  A fetch whose slots are all 0
+ * returns vs_scanpool_fetch's rows bit for bit, with pops = rows.
+ *
+ * HOW.  Per listed scan a pop target P starts at P1 — the rule of vs_search_batch_qual from the density of the scan's OWN qualifier,
+ * VS_QUAL_FIRST_POPS overrides it — clamped to what max_pops and the row budget allow.  The pool's rounds (shared resumed search
+ * launches, a prefetched round included) bring every unfinished scan to the stream rows P pops stand on, one window launch
+ * (k_resort_cursor_batch_qual, a wave per scan) pops past the rejected rows, only the small per-scan records come back, and scans
+ * that are neither final nor at their limit go on at 2 P.  The rows are copied back once, at the end.  Nothing is re-run.  P1 and
+ * VS_POOL_QUAL_CHUNK (the pops one window launch may make) are cost choices: no row, count or state depends on them.
+ *
+ * REFUSALS, each before anything is launched or any cursor moves: NULL slots, qual_slots, out_rows, out_pops or out_state; k outside
+ * [1, kmax]; max_pops outside [k, VS_QUAL_MAX_POPS]; a qualifier slot > VS_MAX_QUAL_SLOTS (all VS_ERR_INVALID); an empty qualifier
+ * slot, a pool on a view handle that names a non-zero slot (VS_ERR_STATE); a pool slot that is not open or is listed twice.
+ * vs_pool_qual_stats covers this call only: search rounds waited for, window launches, the largest P1 of the listed scans, the pops
+ * made, and the scans per final state.
+ * Not built: qualifiers in the broker, the shm server, vs_multi and the single cursor (vs_gettuple), and per-scan visibility slots in
+ * pools. */
+#define VS_QUAL_BUDGET 3
+typedef struct vs_pool_qual_stats {
+    uint64_t search_rounds;
+    uint64_t window_launches;
+    uint64_t first_pops;
+    uint64_t pops;
+    uint64_t complete, ended, cut, budget;
+} vs_pool_qual_stats;
+int vs_scanpool_fetch_qual(vs_scan_pool* pool, const uint32_t* slots, uint32_t n, uint32_t k,
+                           const uint32_t* qual_slots /* [n] host, 0 = no qualifier */, uint32_t max_pops,
+                           uint64_t* out_tids, uint32_t* out_ids, float* out_dist,   /* [n][k], may be NULL */
+                           int32_t* out_rows, uint32_t* out_pops, uint32_t* out_state, /* [n] */
+                           vs_pool_qual_stats* qstats /* may be NULL */);
 
 #ifdef __cplusplus
 }

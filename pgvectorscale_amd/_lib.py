@@ -154,6 +154,14 @@ class QualBatchStats(C.Structure):
 MAX_QUAL_SLOTS = 64
 QUAL_MAX_POPS = 65536
 QUAL_COMPLETE, QUAL_ENDED, QUAL_CUT = 0, 1, 2
+QUAL_BUDGET = 3  # vs_scanpool_fetch_qual only: the pool's row budget was reached
+
+
+class PoolQualStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("search_rounds", "window_launches", "first_pops", "pops", "complete", "ended", "cut", "budget")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
 class PagesInfo(C.Structure):
@@ -275,6 +283,7 @@ SYMBOLS = {
     "vs_scanpool_rescan": (_i, [_vp, _u32, _vp, _vp, _u32, _i]),
     "vs_scanpool_endscan": (_i, [_vp, _u32]),
     "vs_scanpool_fetch": (_i, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "vs_scanpool_fetch_qual": (_i, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(PoolQualStats)]),
     "vs_scanpool_get_stats": (_i, [_vp, _u32, _vp]),
     "vs_scanpool_get_work": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "vs_scanpool_info": (_i, [_vp, C.POINTER(SearchInfo)]),

@@ -696,6 +696,16 @@ int launch_resort_cursor_batch(vs_index* idx, uint32_t n, const uint32_t* d_list
                                uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, uint32_t out_stride);
 int launch_pool_append(vs_index* idx, uint32_t nq, const uint32_t* d_cnt, const uint32_t* d_off, const uint32_t* d_stage, uint32_t stage_kind_stride, uint32_t M,
                        uint32_t* d_all, uint32_t all_kind_stride, uint32_t rows_cap);
+// the resumable window under a qualifier (k_resort_cursor_batch_qual, vs_kernels.hip): what a launch reports per scan next to the
+// public states, and the most pops one launch may make within 64 KB of LDS (0: the window does not fit at all)
+enum { VS_PQ_LIMIT = 2, VS_PQ_STARVED = 4 };
+uint32_t resort_cursor_qual_max_chunk(uint32_t rescore, uint32_t k, uint32_t rows_cap);
+int launch_resort_cursor_batch_qual(vs_index* idx, uint32_t n, const uint32_t* d_list, uint32_t rescore, uint32_t k, uint32_t chunk,
+                                    const uint64_t* const* d_qtab, const uint32_t* d_stream, const float* d_dist, const uint32_t* d_keys,
+                                    uint32_t row_stride, uint64_t* d_heap, uint32_t* d_cur, uint32_t* d_rec, uint32_t* d_out_ids,
+                                    uint64_t* d_out_tids, float* d_out_dist, uint32_t out_stride);
+// P1 of a qualified scan (vs_qual.h): the pops after which a scan under a qualifier of this density is expected to have its k rows
+uint32_t vs_qual_first_pops(uint32_t k, uint32_t max_pops, double density);
 int launch_row_norms(vs_index* idx);
 int launch_row_norms_range(vs_index* idx, uint32_t row_begin, uint32_t rows);  // the same for rows [row_begin, row_begin + rows)
 int vs_quantize_row_range(vs_index* ix, uint32_t row_begin, uint32_t rows);     // vs_extra.hip: vs_sbq_quantize_corpus over a row range

@@ -1302,6 +1302,175 @@ __global__ __launch_bounds__(WAVE) void k_resort_cursor_batch(const uint32_t* __
     }
 }
 
+// The resumable window under a QUALIFIER (vs_scanpool_fetch_qual, vs_scanpool.cpp): k_resort_cursor_batch that pops PAST rows whose node
+// does not carry the bit of the qualifier its scan names, and keeps the rows that do.  A kernel of its own, so that the unqualified one
+// comes out of the compiler as it did.  list[6 b ..] = (pool slot, stream rows emitted so far, exhausted, qualifier slot, the pops of
+// this FETCH the scan may be taken to by this launch, 1 = first launch of the fetch); rec[4 q ..] = (rows kept, pops, state) of the
+// fetch in progress, carried from launch to launch; `chunk` = the pops ONE launch may make (it sizes the key slots in LDS).
+//
+// The heap is replayed by lane 0 on its LDS copy exactly as above — a rejected row has held its place in the window like any other —
+// but whether the loop goes on depends on the popped node's bit, and two dependent global round trips per pop (stream id, qualifier
+// word) on the serial path would cost more than the heap does.  So the wave resolves the bit of every row this launch can pop BEFORE the
+// loop, in parallel: the `len` rows in the heap and the `ahead` rows the refills will push, a lane per row, stream id then qualifier
+// word (two round trips for the whole wave), into an LDS bitmap indexed by STREAM POSITION (rows_cap bits; set with LDS atomicOr, so the
+// order of the lanes does not show).  The loop reads LDS only.  Qualifier slot 0 skips the test.
+//
+// A launch stops when the rows kept reach k (VS_QUAL_COMPLETE), when a pop finds the heap empty and the stream at its end
+// (VS_QUAL_ENDED), when the pops reach list[..+4] (VS_PQ_LIMIT: the host decides between CUT, the row budget and a longer stream), or
+// when the window cannot be refilled yet or `chunk` pops are made (VS_PQ_STARVED: the host launches again).  The kept rows are gathered
+// lane-parallel behind those of the fetch's earlier launches.  cur[] as above, except that cur[2] advances by the POPS (each is an
+// amgettuple call that returned a row) and cur[3] = rows kept by this launch.
+__global__ __launch_bounds__(WAVE) void k_resort_cursor_batch_qual(const uint32_t* __restrict__ list, uint32_t rescore, uint32_t k, uint32_t chunk,
+                                                                    uint32_t bm_words, const uint64_t* const* __restrict__ qtab,
+                                                                    const uint32_t* __restrict__ stream_base, const float* __restrict__ dist_base,
+                                                                    const uint32_t* __restrict__ keys_base, uint32_t row_stride, uint32_t plain_keys,
+                                                                    const uint64_t* __restrict__ tids, uint64_t* __restrict__ heap_base,
+                                                                    uint32_t* __restrict__ cur_base, uint32_t* __restrict__ rec_base,
+                                                                    uint32_t* __restrict__ out_ids_base, uint64_t* __restrict__ out_tids_base,
+                                                                    float* __restrict__ out_dist_base, uint32_t out_stride) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint64_t* hh = reinterpret_cast<uint64_t*>(smem);            // rescore entries
+    uint32_t* kk = reinterpret_cast<uint32_t*>(hh + rescore);    // rescore + chunk keys of the rows the refills will push
+    uint32_t* bm = kk + rescore + chunk;                         // bm_words: bit p = the node of stream row p passes
+    uint32_t* sps = bm + bm_words;                               // k stream positions of the rows kept, then the hand-over words
+    const uint32_t lane = threadIdx.x;
+    const uint32_t* const le = list + 6 * (size_t)blockIdx.x;
+    const uint32_t q = le[0], n = le[1], exhausted = le[2], qslot = le[3], target = le[4], fresh = le[5];
+    const uint32_t* stream = stream_base + (size_t)q * row_stride;
+    const float* dist = dist_base + (size_t)q * row_stride;
+    const uint32_t* keys = keys_base + (size_t)q * row_stride;
+    uint64_t* h = heap_base + (size_t)q * rescore;
+    uint32_t* cur = cur_base + (size_t)q * 4;
+    uint32_t* rec = rec_base + (size_t)q * 4;
+    const uint64_t* const qbits = (qslot != 0 && qtab != nullptr) ? qtab[qslot] : nullptr;
+    const uint32_t kept0 = fresh ? 0u : rec[0], pops0 = fresh ? 0u : rec[1];
+    const uint32_t allow = min(chunk, target > pops0 ? target - pops0 : 0u);  // pops this launch may make
+    uint32_t len = cur[0], pos = cur[1];
+    const uint32_t pos0 = pos;
+    // rows this launch can push (window) or pop (no window): at most that many
+    const uint32_t ahead = min(n > pos ? n - pos : 0u, rescore != 0 ? rescore - len + allow : allow);
+    if (rescore != 0) {
+        for (uint32_t i = lane; i < len; i += WAVE) hh[i] = h[i];
+        for (uint32_t i = lane; i < ahead; i += WAVE) kk[i] = (uint32_t)total_key(dist[pos0 + i]);
+    } else {
+        len = 0;
+    }
+    if (qbits) {
+        for (uint32_t i = lane; i < bm_words; i += WAVE) bm[i] = 0;
+        __syncthreads();
+        for (uint32_t i = lane; i < len + ahead; i += WAVE) {
+            const uint32_t sp = i < len ? (uint32_t)hh[i] : pos0 + (i - len);
+            const uint32_t id = stream[sp];
+            if ((qbits[id >> 6] >> (id & 63u)) & 1ull) atomicOr(&bm[sp >> 5], 1u << (sp & 31u));
+        }
+    }
+    __syncthreads();
+    if (lane == 0) {
+        uint32_t kept = 0, pops = 0, state = VS_PQ_STARVED;
+        auto passes = [&](uint32_t sp) { return qbits == nullptr || ((bm[sp >> 5] >> (sp & 31u)) & 1u) != 0; };
+        auto kof = [](uint64_t e) { return (int32_t)(uint32_t)(e >> 32); };
+        auto sift_up = [&](uint32_t p, uint64_t elem) {
+            while (p > 0) {
+                const uint32_t parent = (p - 1) >> 1;
+                const uint64_t pe = hh[parent];
+                if (kof(pe) <= kof(elem)) break;
+                hh[p] = pe;
+                p = parent;
+            }
+            hh[p] = elem;
+        };
+        for (;;) {
+            if (kept0 + kept >= k) {
+                state = VS_QUAL_COMPLETE;
+                break;
+            }
+            if (pops >= allow) {
+                state = pops0 + pops >= target ? (uint32_t)VS_PQ_LIMIT : (uint32_t)VS_PQ_STARVED;
+                break;
+            }
+            uint32_t sp;
+            if (rescore == 0) {  // resort_buffer.capacity() == 0 -> plain next(): the rows as they are
+                if (pos >= n) {
+                    state = exhausted ? (uint32_t)VS_QUAL_ENDED : (uint32_t)VS_PQ_STARVED;
+                    break;
+                }
+                sp = pos++;
+            } else {
+                while (len < rescore && pos < n) {
+                    const uint64_t e = ((uint64_t)kk[pos - pos0] << 32) | pos;
+                    sift_up(len++, e);
+                    ++pos;
+                }
+                if (len < rescore && !exhausted) break;  // the window cannot be filled yet
+                if (len == 0) {
+                    state = VS_QUAL_ENDED;
+                    break;
+                }
+                const uint64_t item = hh[--len];
+                uint64_t top = item;
+                if (len > 0) {
+                    top = hh[0];
+                    const uint32_t end = len;
+                    uint32_t p = 0, child = 1;
+                    const uint32_t lim = end >= 2 ? end - 2 : 0;
+                    while (child <= lim) {
+                        const uint64_t lc = hh[child], ri = hh[child + 1];
+                        const uint32_t pick = (kof(ri) <= kof(lc)) ? 1u : 0u;
+                        child += pick;
+                        hh[p] = pick ? ri : lc;
+                        p = child;
+                        child = 2 * p + 1;
+                    }
+                    if (child == end - 1) {
+                        hh[p] = hh[child];
+                        p = child;
+                    }
+                    sift_up(p, item);
+                }
+                sp = (uint32_t)top;
+            }
+            ++pops;
+            if (passes(sp)) sps[kept++] = sp;
+        }
+        sps[k] = kept;  // (past the k positions: the hand-over to the other lanes)
+        sps[k + 1] = len;
+        sps[k + 2] = pos;
+        sps[k + 3] = pops;
+        sps[k + 4] = state;
+    }
+    __syncthreads();
+    const uint32_t kept = sps[k], pops = sps[k + 3];
+    len = sps[k + 1];
+    pos = sps[k + 2];
+    for (uint32_t i = lane; i < len; i += WAVE) h[i] = hh[i];
+    uint32_t* out_ids = out_ids_base + (size_t)q * out_stride + kept0;
+    uint64_t* out_tids = out_tids_base + (size_t)q * out_stride + kept0;
+    float* out_dist = out_dist_base + (size_t)q * out_stride + kept0;
+    for (uint32_t j = lane; j < kept; j += WAVE) {
+        const uint32_t sp = sps[j];
+        const uint32_t id = stream[sp];
+        out_ids[j] = id;
+        out_tids[j] = tids[id];
+        float d = __int_as_float(0x7fc00000);
+        if (rescore != 0) d = dist[sp];
+        else if (plain_keys) {
+            int32_t b = (int32_t)(keys[sp] ^ 0x80000000u);
+            b ^= (int32_t)(((uint32_t)(b >> 31)) >> 1);
+            d = __int_as_float(b);
+        }
+        out_dist[j] = d;
+    }
+    if (lane == 0) {
+        cur[0] = len;
+        cur[1] = pos;
+        cur[2] += pops;
+        cur[3] = kept;
+        rec[0] = kept0 + kept;
+        rec[1] = pops0 + pops;
+        rec[2] = sps[k + 4];
+    }
+}
+
 // ===============================================================================================================
 // launch wrappers
 // ===============================================================================================================
@@ -1556,6 +1725,29 @@ int launch_resort_cursor_batch(vs_index* idx, uint32_t n, const uint32_t* d_list
     VS_REQUIRE(lds <= 64 * 1024, "resort window of %u rows / %u rows per fetch does not fit LDS", rescore, k);
     hipLaunchKernelGGL(k_resort_cursor_batch, dim3(n), dim3(WAVE), lds, idx->ctx->stream, d_list, rescore, k, d_stream, d_dist, d_keys, row_stride,
                        plain_keys, idx->tids, d_heap, d_cur, d_out_ids, d_out_tids, d_out_dist, out_stride);
+    VS_HIP(hipGetLastError());
+    return VS_OK;
+}
+
+// the pops one launch of k_resort_cursor_batch_qual may make so that its LDS stays within 64 KB: heap entries, keys, bitmap, positions
+uint32_t resort_cursor_qual_max_chunk(uint32_t rescore, uint32_t k, uint32_t rows_cap) {
+    const size_t fixed = (size_t)rescore * 12 + (size_t)((rows_cap + 31) / 32) * 4 + ((size_t)k + 8) * 4;
+    return fixed + 4 > 64 * 1024 ? 0u : (uint32_t)((64 * 1024 - fixed) / 4);
+}
+
+// d_list: [n][6] (pool slot, rows emitted, exhausted, qualifier slot, pops to take the fetch to, first launch) on the device; d_rec:
+// [slots][4] (kept, pops, state) of the fetch in progress; d_qtab: the owner's table of qualifier bitmaps (null: no scan names one)
+int launch_resort_cursor_batch_qual(vs_index* idx, uint32_t n, const uint32_t* d_list, uint32_t rescore, uint32_t k, uint32_t chunk,
+                                    const uint64_t* const* d_qtab, const uint32_t* d_stream, const float* d_dist, const uint32_t* d_keys,
+                                    uint32_t row_stride, uint64_t* d_heap, uint32_t* d_cur, uint32_t* d_rec, uint32_t* d_out_ids,
+                                    uint64_t* d_out_tids, float* d_out_dist, uint32_t out_stride) {
+    if (n == 0) return VS_OK;
+    const uint32_t plain_keys = (idx->d.storage_type == VS_STORAGE_PLAIN && idx->d.dim_index == idx->d.dim_full) ? 1u : 0u;
+    const uint32_t bm_words = (row_stride + 31) / 32;
+    const size_t lds = (size_t)rescore * 8 + ((size_t)rescore + chunk) * 4 + (size_t)bm_words * 4 + ((size_t)k + 8) * 4;
+    VS_REQUIRE(chunk >= 1 && lds <= 64 * 1024, "qualified resort window of %u rows / %u rows per fetch / %u pops per launch does not fit LDS", rescore, k, chunk);
+    hipLaunchKernelGGL(k_resort_cursor_batch_qual, dim3(n), dim3(WAVE), lds, idx->ctx->stream, d_list, rescore, k, chunk, bm_words, d_qtab, d_stream,
+                       d_dist, d_keys, row_stride, plain_keys, idx->tids, d_heap, d_cur, d_rec, d_out_ids, d_out_tids, d_out_dist, out_stride);
     VS_HIP(hipGetLastError());
     return VS_OK;
 }

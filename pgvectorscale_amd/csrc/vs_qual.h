@@ -333,6 +333,9 @@ static uint32_t qual_first_pops(uint32_t k, uint32_t max_pops, double density) {
     return (uint32_t)std::min<double>(std::max<double>(want, (double)k), (double)max_pops);
 }
 
+// (the same rule for the scan pools' qualified fetch, vs_scanpool.cpp)
+uint32_t vs_qual_first_pops(uint32_t k, uint32_t max_pops, double density) { return qual_first_pops(k, max_pops, density); }
+
 // (what needs no index comes first: a bad slot array or pop limit is named whatever the handle is)
 static int qual_check_gucs(const vs_index* ix, const char* what, const uint32_t* slots, uint32_t L, uint32_t rescore, uint32_t k, uint32_t max_pops) {
     VS_REQUIRE(slots, "%s: qual_slots is NULL (the unqualified calls exist for that)", what);

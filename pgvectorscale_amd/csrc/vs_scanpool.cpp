@@ -20,6 +20,9 @@
 // counters are recorded per emitted stream row).  All scans of a pool share the GUCs (diskann.query_search_list_size, query_rescore:
 // session-level in PostgreSQL) and the snapshot mask in force; scan keys are per scan.  A scan that outgrows the pool's fixed
 // capacities (more than rows_cap stream rows) fails with VS_ERR_CAPACITY and is continued by a cursor of its own.
+//
+// vs_scanpool_fetch_qual (at the end of this file) continues the listed scans to their next k rows that pass a per-scan QUALIFIER
+// (include/vsgpu.h, "qualified scan pools"): the same rounds, and a window kernel that pops past rejected rows.
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -58,7 +61,7 @@ struct vs_scan_pool {
     std::vector<Slot> slots;
     bool csr_dirty = true;
     DevBuf raw_q, q_full, q_index, qcodes, qlabels, qlabel_off, heap_g, hash, state, cnt, stats, status, row_stats, stage, all, resort_heap,
-        out_tids, list, roff;
+        out_tids, list, roff, qrec;
     uint64_t* d_tids = nullptr;
     uint32_t *d_cur = nullptr, *d_ids = nullptr;
     float* d_dist = nullptr;
@@ -87,7 +90,7 @@ struct vs_scan_pool {
         if (h_pin) (void)hipHostFree(h_pin);
         h_pin = nullptr;
         for (DevBuf* b : {&raw_q, &q_full, &q_index, &qcodes, &qlabels, &qlabel_off, &heap_g, &hash, &state, &cnt, &stats, &status, &row_stats,
-                          &stage, &all, &resort_heap, &out_tids, &list, &roff}) {
+                          &stage, &all, &resort_heap, &out_tids, &list, &roff, &qrec}) {
             if (b->p && !b->in_slab) (void)hipFree(b->p);
             b->p = nullptr;
             b->bytes = 0;
@@ -232,8 +235,9 @@ static int scanpool_create_impl(vs_index* ix, uint32_t capacity, uint32_t L, uin
         p->d_cur = (uint32_t*)(p->d_tids + G * (size_t)kmax);
         p->d_ids = p->d_cur + G * 4;
         p->d_dist = (float*)(p->d_ids + G * (size_t)kmax);
-        VS_TRY(devbuf_reserve(c, p->list, G * 12));  // (slot, rows, exhausted) of the scans a fetch lists
+        VS_TRY(devbuf_reserve(c, p->list, G * 24));  // (slot, rows, exhausted) of the scans a fetch lists; six words each for a qualified fetch
         VS_TRY(devbuf_reserve(c, p->roff, G * 4));   // where a round's new rows go in every slot's stream arrays
+        VS_TRY(devbuf_reserve(c, p->qrec, G * 16));  // (kept, pops, state) of every slot's qualified fetch in progress (vs_scanpool_fetch_qual)
         VS_HIP(hipStreamCreateWithFlags(&p->stream2, hipStreamNonBlocking));
         VS_HIP(hipEventCreateWithFlags(&p->ev_round, hipEventDisableTiming));
         VS_HIP(hipHostMalloc((void**)&p->h_pin, (G * ST_N + 2 * G + G + G * (size_t)p->mmax * ST_N) * 4, hipHostMallocDefault));
@@ -721,6 +725,241 @@ static int scanpool_fetch_impl(vs_scan_pool* p, const uint32_t* slots, uint32_t 
 extern "C" int vs_scanpool_fetch(vs_scan_pool* p, const uint32_t* slots, uint32_t n, uint32_t k, uint64_t* out_tids, uint32_t* out_ids,
                                  float* out_dist, int32_t* out_rows) {
     return vs_guard("vs_scanpool_fetch", [&] { return scanpool_fetch_impl(p, slots, n, k, out_tids, out_ids, out_dist, out_rows); });
+}
+
+// ---- qualified fetch --------------------------------------------------------------------------------------------------------------
+// amgettuple until k rows pass the scan's qualifier, for many scans at once (the contract: include/vsgpu.h, "qualified scan pools").
+// What the loop below keeps per listed scan: the pops of THIS fetch its stream rows are brought to (`target`: P1, then doubled), and
+// what the window launches have reported so far.  s.handed — the calls that returned a row — moves at the very end, by the pops.
+namespace {
+struct QualJob {
+    uint32_t q = 0, qslot = 0, target = 0, kept = 0, pops = 0, state = VS_PQ_STARVED;
+    bool done = false, fresh = true;
+};
+}  // namespace
+
+// pops a scan that has made `handed` calls may still make before its next pop would stand on more than rows_cap stream rows
+static uint32_t pool_budget_pops(const vs_scan_pool* p, const Slot& s) {
+    const uint64_t most_calls = p->S > 0 ? (p->rows_cap + 1 > p->S ? (uint64_t)p->rows_cap + 1 - p->S : 0) : p->rows_cap;
+    return most_calls > s.handed ? (uint32_t)(most_calls - s.handed) : 0u;
+}
+
+static int scanpool_fetch_qual_impl(vs_scan_pool* p, const uint32_t* slots, uint32_t n, uint32_t k, const uint32_t* qual_slots, uint32_t max_pops,
+                                    uint64_t* out_tids, uint32_t* out_ids, float* out_dist, int32_t* out_rows, uint32_t* out_pops,
+                                    uint32_t* out_state, vs_pool_qual_stats* qstats) {
+    const char* what = "vs_scanpool_fetch_qual";
+    // (what needs no pool comes first: a missing array or a bad pop limit is named whatever the handle is)
+    VS_REQUIRE(slots, "%s: slots is NULL", what);
+    VS_REQUIRE(qual_slots, "%s: qual_slots is NULL (vs_scanpool_fetch exists for that)", what);
+    VS_REQUIRE(out_rows, "%s: out_rows is NULL", what);
+    VS_REQUIRE(out_pops, "%s: out_pops is NULL", what);
+    VS_REQUIRE(out_state, "%s: out_state is NULL", what);
+    VS_REQUIRE(k >= 1, "%s: k must be >= 1", what);
+    VS_REQUIRE(max_pops >= k && max_pops <= VS_QUAL_MAX_POPS, "%s: max_pops %u outside [k = %u, %d]", what, max_pops, k, VS_QUAL_MAX_POPS);
+    VS_REQUIRE(p, "%s: pool is NULL", what);
+    VS_REQUIRE(n >= 1, "%s: no slot listed", what);
+    VS_REQUIRE(k <= p->kmax, "%s: k %u outside [1, the pool's rows per fetch = %u]", what, k, p->kmax);
+    vs_index* ix = p->ix;
+    vs_ctx* c = ix->ctx;
+    const uint32_t G = p->cap, S = p->S;
+    bool any_qual = false;
+    {
+        std::vector<uint8_t> listed(G, 0);
+        for (uint32_t i = 0; i < n; ++i) {
+            VS_REQUIRE(slots[i] < G && p->slots[slots[i]].active, "%s: slot %u is not an open scan", what, slots[i]);
+            VS_REQUIRE(!listed[slots[i]], "%s: slot %u listed twice", what, slots[i]);
+            listed[slots[i]] = 1;
+        }
+        for (uint32_t i = 0; i < n; ++i) {
+            const uint32_t sl = qual_slots[i];
+            VS_REQUIRE(sl <= VS_MAX_QUAL_SLOTS, "%s: scan %u names qualifier slot %u outside [0,%d]", what, i, sl, VS_MAX_QUAL_SLOTS);
+            if (!sl) continue;
+            if (ix->is_view) {
+                vs_set_error("%s: scan %u names qualifier slot %u, but the pool's handle is a view; qualifiers belong to the index it was made from", what, i, sl);
+                return VS_ERR_STATE;
+            }
+            if (!ix->qs || !ix->qs->bits[sl]) {
+                vs_set_error("%s: scan %u names qualifier slot %u, which is empty (vs_index_qual_put / vs_index_qual_from_tids)", what, i, sl);
+                return VS_ERR_STATE;
+            }
+            any_qual = true;
+        }
+    }
+    const uint32_t chunk_cap = resort_cursor_qual_max_chunk(S, k, p->rows_cap);
+    VS_REQUIRE(chunk_cap >= 1, "%s: a resort window of %u rows / %u rows per fetch / a budget of %u rows does not fit LDS", what, S, k, p->rows_cap);
+    const uint32_t chunk_opt = std::min(std::max<uint32_t>(pool_env_u32("VS_POOL_QUAL_CHUNK", 4096), 1), chunk_cap);
+    VS_HIP(hipSetDevice(c->device));
+    VS_TRY(settle_prefetch(p, false));  // (a prefetched round that has finished meanwhile is booked; one that has not stays in flight)
+    vs_pool_qual_stats qs{};
+    auto limit_of = [&](const Slot& s) { return s.exhausted ? max_pops : std::min(max_pops, pool_budget_pops(p, s)); };
+    auto need_of = [&](const Slot& s, uint32_t pops) { return S > 0 ? (uint64_t)S + s.handed + pops - 1 : (uint64_t)s.handed + pops; };
+    std::vector<QualJob> jobs(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        QualJob& j = jobs[i];
+        Slot& s = p->slots[slots[i]];
+        j.q = slots[i];
+        j.qslot = qual_slots[i];
+        if (s.failed) {
+            j.done = true;
+            continue;
+        }
+        const uint32_t lim = limit_of(s);
+        if (lim == 0) {  // not one pop within the row budget
+            s.failed = true;
+            j.done = true;
+            continue;
+        }
+        const double density = j.qslot == 0 ? 1.0 : (ix->d.n ? (double)ix->qs->info[j.qslot].n_set / (double)ix->d.n : 0.0);
+        const uint32_t p1 = vs_qual_first_pops(k, max_pops, density);
+        qs.first_pops = std::max<uint64_t>(qs.first_pops, p1);
+        j.target = std::min(p1, lim);
+    }
+    uint32_t* const all_ids = (uint32_t*)p->all.p;
+    uint32_t* const all_ham = all_ids + (size_t)G * p->rows_cap;
+    float* const all_dist = (float*)(all_ham + (size_t)G * p->rows_cap);
+    std::vector<uint32_t> rec((size_t)G * 4), list;
+    for (;;) {
+        // ---- search rounds until every unfinished scan has the stream rows its `target` pops stand on (or has ended)
+        for (;;) {
+            std::vector<uint32_t> run;
+            uint32_t M = 0;
+            for (QualJob& j : jobs) {
+                const Slot& s = p->slots[j.q];
+                if (j.done || s.failed || s.exhausted) continue;
+                const uint64_t need = need_of(s, j.target);
+                if (need <= s.rows) continue;
+                VS_REQUIRE(need <= p->rows_cap, "%s: internal: slot %u aimed past its row budget", what, j.q);
+                run.push_back(j.q);
+                M = std::max<uint32_t>(M, (uint32_t)(need - s.rows));
+            }
+            if (run.empty()) break;
+            if (p->fly.active) {  // the rows may be on their way already (and the staging arrays are the round's in flight either way)
+                VS_TRY(settle_prefetch(p, true));
+                continue;
+            }
+            M = std::min(M, p->mmax);
+            // the top-up of vs_scanpool_fetch: a round costs the life of its longest scan whoever takes part, so the other unfinished
+            // scans of the fetch that are being streamed are carried along (never past their budget, at most a round ahead)
+            bool streaming = true;
+            for (uint32_t q : run) streaming = streaming && p->slots[q].launches >= 2;
+            if (streaming && pool_env_u32("VS_POOL_TOPUP", 1)) {
+                std::vector<uint8_t> in_run(G, 0);
+                for (uint32_t q : run) in_run[q] = 1;
+                for (const QualJob& j : jobs) {
+                    const Slot& s = p->slots[j.q];
+                    if (j.done || in_run[j.q] || s.failed || s.exhausted || s.launches < 2) continue;
+                    if ((uint64_t)s.rows + M > p->rows_cap || s.rows >= need_of(s, j.target) + M) continue;
+                    run.push_back(j.q);
+                }
+            }
+            std::sort(run.begin(), run.end());
+            for (uint32_t q : run) M = std::min(M, p->rows_cap - p->slots[q].rows);
+            VS_REQUIRE(M >= 1, "%s: internal: empty round", what);
+            VS_TRY(pool_round(p, run, M));
+            qs.search_rounds++;
+        }
+        // ---- one window launch over the unfinished scans: a wave per scan pops past the rows its qualifier rejects
+        const auto tr0 = std::chrono::steady_clock::now();
+        list.clear();
+        uint32_t chunk = 1;
+        for (QualJob& j : jobs) {
+            const Slot& s = p->slots[j.q];
+            if (j.done) continue;
+            if (s.failed) {  // (a structure outgrew the pool's capacities in a round of this fetch)
+                j.done = true;
+                continue;
+            }
+            const uint32_t entry[6] = {j.q, s.rows, s.exhausted ? 1u : 0u, j.qslot, j.target, j.fresh ? 1u : 0u};
+            list.insert(list.end(), entry, entry + 6);
+            chunk = std::max(chunk, j.target - j.pops);
+        }
+        if (list.empty()) break;
+        chunk = std::min(chunk, chunk_opt);
+        VS_HIP(hipMemcpyAsync(p->list.p, list.data(), list.size() * 4, hipMemcpyHostToDevice, c->stream));  // (pageable source: staged before the call returns)
+        VS_TRY(launch_resort_cursor_batch_qual(ix, (uint32_t)(list.size() / 6), (const uint32_t*)p->list.p, S, k, chunk,
+                                               any_qual ? (const uint64_t* const*)ix->qs->tab : nullptr, all_ids, all_dist, all_ham, p->rows_cap,
+                                               (uint64_t*)p->resort_heap.p, p->d_cur, (uint32_t*)p->qrec.p, p->d_ids, p->d_tids, p->d_dist, p->kmax));
+        VS_HIP(hipMemcpyAsync(rec.data(), p->qrec.p, rec.size() * 4, hipMemcpyDeviceToHost, c->stream));  // only the small records come back
+        VS_HIP(hipStreamSynchronize(c->stream));
+        p->t_resort += std::chrono::duration<double>(std::chrono::steady_clock::now() - tr0).count();
+        qs.window_launches++;
+        bool progress = false, left = false;
+        for (QualJob& j : jobs) {
+            if (j.done) continue;
+            const Slot& s = p->slots[j.q];
+            const uint32_t* r = rec.data() + (size_t)j.q * 4;
+            VS_REQUIRE(r[0] >= j.kept && r[0] <= k && r[1] >= j.pops && r[1] <= j.target, "%s: record of slot %u out of step", what, j.q);
+            progress = progress || r[1] > j.pops || r[2] != VS_PQ_STARVED;
+            j.kept = r[0];
+            j.pops = r[1];
+            j.fresh = false;
+            if (r[2] == VS_QUAL_COMPLETE || r[2] == VS_QUAL_ENDED) {
+                j.state = r[2];
+                j.done = true;
+            } else if (r[2] == VS_PQ_LIMIT) {
+                const uint32_t lim = limit_of(s);  // (the scan may have been seen to end meanwhile: no budget bounds it then)
+                if (j.target >= lim) {
+                    j.state = j.pops >= max_pops ? (uint32_t)VS_QUAL_CUT : (uint32_t)VS_QUAL_BUDGET;
+                    j.done = true;
+                } else {
+                    j.target = (uint32_t)std::min<uint64_t>(2ull * j.target, lim);
+                    progress = true;
+                }
+            }  // (else starved: the launch's pop allowance is used up; the next launch goes on)
+            left = left || !j.done;
+        }
+        if (!left) break;
+        VS_REQUIRE(progress, "%s: internal: a window launch made no progress", what);
+    }
+    // ---- the rows, once
+    p->fetches++;
+    p->scans_served += n;
+    std::vector<uint64_t> pack((size_t)G * p->kmax * 2 + (size_t)G * 2);  // (u64 words of the layout of out_tids)
+    VS_HIP(hipMemcpyAsync(pack.data(), p->out_tids.p, pack.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    VS_HIP(hipStreamSynchronize(c->stream));
+    const uint64_t* const tids = pack.data();
+    const uint32_t* const cur = (const uint32_t*)(tids + (size_t)G * p->kmax);
+    const uint32_t* const ids = cur + (size_t)G * 4;
+    const float* const dist = (const float*)(ids + (size_t)G * p->kmax);
+    uint32_t most_pops = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const QualJob& j = jobs[i];
+        Slot& s = p->slots[j.q];
+        out_pops[i] = 0;
+        out_state[i] = VS_QUAL_CUT;
+        if (s.failed) {
+            out_rows[i] = VS_ERR_CAPACITY;
+            continue;
+        }
+        VS_REQUIRE(cur[(size_t)j.q * 4 + 2] == s.handed + j.pops && j.kept <= k, "%s: cursor of slot %u out of step", what, j.q);
+        for (uint32_t r = 0; r < j.kept; ++r) {
+            if (out_ids) out_ids[(size_t)i * k + r] = ids[(size_t)j.q * p->kmax + r];
+            if (out_tids) out_tids[(size_t)i * k + r] = tids[(size_t)j.q * p->kmax + r];
+            if (out_dist) out_dist[(size_t)i * k + r] = dist[(size_t)j.q * p->kmax + r];
+        }
+        s.handed += j.pops;  // every pop was a call that returned a row, kept or not
+        if (j.state == VS_QUAL_ENDED) s.calls_after_end += 1;  // the call that found the scan at its end
+        out_rows[i] = (int32_t)j.kept;
+        out_pops[i] = j.pops;
+        out_state[i] = j.state;
+        qs.pops += j.pops;
+        most_pops = std::max(most_pops, j.pops);
+        if (j.state == VS_QUAL_COMPLETE) qs.complete++;
+        else if (j.state == VS_QUAL_ENDED) qs.ended++;
+        else if (j.state == VS_QUAL_CUT) qs.cut++;
+        else qs.budget++;
+    }
+    if (qstats) *qstats = qs;
+    // the next rows of the scans that are being streamed, sized by the pops this fetch needed: searched while these rows are consumed
+    return prefetch_round(p, slots, n, std::max<uint32_t>(most_pops, 1));
+}
+extern "C" int vs_scanpool_fetch_qual(vs_scan_pool* p, const uint32_t* slots, uint32_t n, uint32_t k, const uint32_t* qual_slots, uint32_t max_pops,
+                                      uint64_t* out_tids, uint32_t* out_ids, float* out_dist, int32_t* out_rows, uint32_t* out_pops,
+                                      uint32_t* out_state, vs_pool_qual_stats* qstats) {
+    if (qstats) memset(qstats, 0, sizeof(*qstats));
+    return vs_guard("vs_scanpool_fetch_qual", [&] {
+        return scanpool_fetch_qual_impl(p, slots, n, k, qual_slots, max_pops, out_tids, out_ids, out_dist, out_rows, out_pops, out_state, qstats);
+    });
 }
 
 // GreedySearchStats of one pooled scan as the reference's scan holds them after the amgettuple calls made so far (vs_scan_get_stats,

@@ -889,6 +889,26 @@ class ScanPool:
         check(self._L.vs_scanpool_fetch(self.h, _p(sl), n, k, _p(tids), _p(ids), _p(dist), _p(rows)))
         return rows, ids, tids, dist
 
+    def fetch_qual(self, slots, k, qual_slots, max_pops=None):
+        """the next k rows of every listed slot that pass the qualifier the slot names (qual_slots [n], 0 = none; the bitmaps are the
+        index's, DiskAnnIndex.qual_put), looking at no more than max_pops rows per slot in this call (default: QUAL_MAX_POPS)
+        -> (rows [n] int32 (negative: that slot's error code), ids [n][k], tids [n][k], dist [n][k], pops [n], state [n]
+        (QUAL_COMPLETE / _ENDED / _CUT / _BUDGET), qstats dict); the cursor is the one fetch() moves"""
+        sl = np.ascontiguousarray(slots, np.uint32)
+        qsl = np.ascontiguousarray(qual_slots, np.uint32)
+        n = sl.size
+        assert qsl.size == n, "one qualifier slot per listed pool slot"
+        ids = np.full((n, k), 0xFFFFFFFF, np.uint32)
+        tids = np.zeros((n, k), np.uint64)
+        dist = np.zeros((n, k), np.float32)
+        rows = np.zeros(n, np.int32)
+        pops = np.zeros(n, np.uint32)
+        state = np.zeros(n, np.uint32)
+        qst = _lib.PoolQualStats()
+        check(self._L.vs_scanpool_fetch_qual(self.h, _p(sl), n, k, _p(qsl), _lib.QUAL_MAX_POPS if max_pops is None else max_pops, _p(tids),
+                                             _p(ids), _p(dist), _p(rows), _p(pops), _p(state), C.byref(qst)))
+        return rows, ids, tids, dist, pops, state, qst.as_dict()
+
     def stats(self, slot):
         st = _lib.Stats()
         check(self._L.vs_scanpool_get_stats(self.h, slot, C.byref(st)))
