@@ -143,7 +143,10 @@ int vs_index_last_search_info(const vs_index* idx, vs_search_info* out);
  * are VS_PF_HEAP_LDS / VS_PF_HEAP_CAP / VS_PF_DEDUP_SLOTS / VS_PF_VISITED, which override the pool's planned capacities too (a pooled
  * scan that outgrows one fails with VS_ERR_CAPACITY).  Rows, distance bits and the reference counters are the same under both.
  * VS_POOL_QUAL_CHUNK: the pops ONE window launch of vs_scanpool_fetch_qual may make per scan (default 4096, capped so that the launch
- * stays within 64 KB of LDS); a fetch that needs more launches again.  A cost choice: no row, count or state depends on it. */
+ * stays within 64 KB of LDS); a fetch that needs more launches again.  A cost choice: no row, count or state depends on it.
+ * VS_QUAL_EXACT_SLICES: the slices vs_search_batch_qual_exact cuts every slot's row list into (unset / 0: as many as fill the device;
+ * never more than the list has 32-row passes).  VS_QUAL_EXACT_TQ: the scans of one tile (1, 2, 4, 8, 16; default 8).  Cost choices
+ * both: no row, distance bit or count depends on them. */
 int vs_set_option(const char* name, const char* value);
 int vs_get_option(const char* name, char* out, size_t cap);
 const char* vs_version(void);
@@ -1645,6 +1648,46 @@ int vs_scanpool_fetch_qual(vs_scan_pool* pool, const uint32_t* slots, uint32_t n
                            uint64_t* out_tids, uint32_t* out_ids, float* out_dist,   /* [n][k], may be NULL */
                            int32_t* out_rows, uint32_t* out_pops, uint32_t* out_state, /* [n] */
                            vs_pool_qual_stats* qstats /* may be NULL */);
+
+/* ---- exact qualified top-k: the k nearest rows of a qualifier, no graph walked (vs_qual_exact.h) ----
+ * vs_search_batch_qual is a post-filter: its cost grows as 1 / density, and below a density of about 0.01 it returns CUT scans and
+ * whatever rows an approximate scan happened to reach.  For such selective predicates a planner fetches the qualifying rows and sorts
+ * them by exact distance; this call is that plan on the device.
+ *
+ * SEMANTICS.  Every scan q is handled on its own.  With s = qual_slots[q], let C be the nodes i < n for which bit i of qualifier s is
+ * set (slot 0: every node), whose heap tid offset is not 0 (not deleted), and which the mask in force on the index
+ * (vs_index_set_visibility*, vs_index_snapshot_use; no mask: nothing hidden) does not hide.  The call returns the min(k, |C|) rows of
+ * C with the smallest distance, ascending by (f32::total_cmp key of the distance, node id) — the order of vs_bruteforce_topk.  The
+ * distance is the full-precision distance over dim_full to the prepared query: the f32 the rerank and vs_bruteforce_topk give the
+ * row, bit for bit (cosine divisor, accumulator and horizontal-add order, the scalar tail in element order).
+ * out_ids / out_tids / out_dist are [nq][k] (each may be NULL); entries past the rows returned are VS_INVALID_NODE / 0 / NaN, as in
+ * vs_search_batch.  out_rows[q] = min(k, |C|).  k in [1, 64].
+ * This is NOT the row sequence of vs_search_batch_qual: it is the exact answer.  vs_search_batch_qual returns whichever of these rows
+ * the graph scan reaches, in the scan's order.  There are no label keys, no search_list_size and no rescore.  SBQ and plain storage
+ * are handled alike (a plain index uses dim_full, as vs_bruteforce_topk does).
+ * vs_search_batch_qual_exact takes HOST queries, slots and outputs; _dev takes DEVICE queries, slots and outputs and is synchronous
+ * on return, like vs_bruteforce_topk.  nq = 0 returns VS_OK.
+ * REFUSALS, each before anything is launched or written: NULL idx, qual_slots or out_rows; k outside [1, 64]; a slot >
+ * VS_MAX_QUAL_SLOTS (VS_ERR_INVALID); an empty slot, a view handle, a batch of the handle in flight, no vector column on the device
+ * (VS_ERR_STATE).
+ * HOW.  Per distinct slot of the batch the bitmap is compacted into an ascending row list; the scans are grouped by slot into tiles of
+ * tile_queries scans, each list is cut into slices, and one workgroup per (tile, slice) reads each row of its slice once for all the
+ * scans of the tile.  vs_qual_exact_stats: tile_queries (scans per tile), lists (distinct slots compacted), rows_listed (sum of the
+ * list lengths), tiles, slices (the largest slice count of a slot), row_reads (rows read from the vector column: sum over tiles of the
+ * tile's list length).  The number of slices is a cost choice — no row depends on it — as many as fill the device given the tiles,
+ * each at least one 32-row pass; the option VS_QUAL_EXACT_SLICES forces it, VS_QUAL_EXACT_TQ picks the tile (1, 2, 4, 8 or 16 scans;
+ * default 8, less where the tile's queries do not fit the LDS).
+ * Not built: an automatic switch inside vs_search_batch_qual (choose by vs_qual_info.n_set), per-scan
+ * visibility slots, label keys, and the broker, the shm server and vs_multi. */
+typedef struct vs_qual_exact_stats {
+    uint64_t tile_queries, lists, rows_listed, tiles, slices, row_reads;
+} vs_qual_exact_stats;
+int vs_search_batch_qual_exact(vs_index* idx, const float* queries, uint32_t nq, uint32_t k, const uint32_t* qual_slots,
+                               uint32_t* out_ids, uint64_t* out_tids, float* out_dist, /* [nq][k], may be NULL */
+                               uint32_t* out_rows /* [nq] */, vs_qual_exact_stats* stats /* may be NULL */);
+int vs_search_batch_qual_exact_dev(vs_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_qual_slots,
+                                   uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, uint32_t* d_out_rows,
+                                   vs_qual_exact_stats* stats /* may be NULL */);
 
 #ifdef __cplusplus
 }

@@ -339,6 +339,43 @@ static int upload_rows(vs_ctx* c, void* dst, size_t dev_row_bytes, const void* s
     return VS_OK;
 }
 
+// strided download: the first `host_row_bytes` of device rows of `dev_row_bytes` into dense host rows.  Whole device rows travel
+// through the pinned ring as one flat transfer per chunk and the host takes its part of each row out of the ring: a 2-D copy into
+// pageable memory is carried out a row at a time by the runtime (10M rows took minutes where the bytes take seconds).
+static int download_rows(vs_ctx* c, void* dst, size_t host_row_bytes, const void* src, size_t dev_row_bytes, size_t rows) {
+    if (rows == 0) return VS_OK;
+    if (dev_row_bytes == host_row_bytes) return vs_dev_download(c, dst, src, rows * host_row_bytes);
+    VS_HIP(hipStreamSynchronize(c->stream));
+    if (dev_row_bytes > c->pinned_bytes) {
+        VS_HIP(hipMemcpy2D(dst, host_row_bytes, src, dev_row_bytes, host_row_bytes, rows, hipMemcpyDeviceToHost));
+        return VS_OK;
+    }
+    const size_t rows_per_chunk = c->pinned_bytes / dev_row_bytes;
+    size_t r0 = 0;
+    int slot = 0;
+    size_t pend_r0[2] = {0, 0}, pend_n[2] = {0, 0};
+    while (r0 < rows || pend_n[0] || pend_n[1]) {
+        if (pend_n[slot]) {  // drain the older transfer in this slot
+            VS_HIP(hipEventSynchronize(c->pinned_ev[slot]));
+            const char* p = static_cast<const char*>(c->pinned[slot]);
+            char* d = static_cast<char*>(dst) + pend_r0[slot] * host_row_bytes;
+            for (size_t r = 0; r < pend_n[slot]; ++r) memcpy(d + r * host_row_bytes, p + r * dev_row_bytes, host_row_bytes);
+            pend_n[slot] = 0;
+        }
+        if (r0 < rows) {
+            const size_t nr = std::min(rows_per_chunk, rows - r0);
+            VS_HIP(hipMemcpyAsync(c->pinned[slot], static_cast<const char*>(src) + r0 * dev_row_bytes, nr * dev_row_bytes, hipMemcpyDeviceToHost,
+                                  c->copy_stream));
+            VS_HIP(hipEventRecord(c->pinned_ev[slot], c->copy_stream));
+            pend_r0[slot] = r0;
+            pend_n[slot] = nr;
+            r0 += nr;
+        }
+        slot ^= 1;
+    }
+    return VS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // index
 // ---------------------------------------------------------------------------------------------------------------
@@ -467,7 +504,8 @@ extern "C" void vs_index_free(vs_index* ix) {
     DevBuf* bufs[] = {&w.q_full, &w.qcodes, &w.qlabels, &w.qlabel_off, &w.hash, &w.heap_g, &w.heap_g4, &w.ghash4, &w.heap_g4b, &w.ghash4b, &w.pool_ctr, &w.fb_flag, &w.phase, &w.timeline, &w.raw_q2, &w.out_ids2, &w.out_tids2, &w.out_dist2, &w.stream_ids,
                       &w.stream_ham, &w.stream_cnt, &w.stats, &w.status, &w.rr_dist, &w.out_ids, &w.out_tids,
                       &w.out_dist, &w.resort_heap, &w.raw_q, &w.misc, &w.q_index, &w.red, &w.order_work, &w.order_perm, &w.order_labels, &w.vis_slots,
-                      &w.qual_q, &w.qual_map, &w.qual_lab, &w.qual_laboff, &w.qual_slots, &w.qual_out};
+                      &w.qual_q, &w.qual_map, &w.qual_lab, &w.qual_laboff, &w.qual_slots, &w.qual_out,
+                      &w.qx_list, &w.qx_counts, &w.qx_tab, &w.qx_part};
     for (DevBuf* b : bufs) devbuf_free(*b);
     if (!ix->is_view) vs_vis_base_free(ix);
     if (!ix->is_view) vs_qual_drop_all(ix);
@@ -963,16 +1001,13 @@ extern "C" int vs_index_download(const vs_index* ix, uint64_t* codes, uint32_t* 
     VS_HIP(hipStreamSynchronize(c->stream));
     const size_t nr = row_count;
     if (codes)
-        VS_HIP(hipMemcpy2D(codes, ix->d.words * 8ull, ix->codes + (size_t)row_begin * ix->code_stride,
-                           ix->code_stride * 8ull, ix->d.words * 8ull, nr, hipMemcpyDeviceToHost));
+        VS_TRY(download_rows(c, codes, ix->d.words * 8ull, ix->codes + (size_t)row_begin * ix->code_stride, ix->code_stride * 8ull, nr));
     if (nbrs)
-        VS_HIP(hipMemcpy2D(nbrs, ix->d.num_neighbors * 4ull, ix->nbrs + (size_t)row_begin * ix->nbr_stride,
-                           ix->nbr_stride * 4ull, ix->d.num_neighbors * 4ull, nr, hipMemcpyDeviceToHost));
+        VS_TRY(download_rows(c, nbrs, ix->d.num_neighbors * 4ull, ix->nbrs + (size_t)row_begin * ix->nbr_stride, ix->nbr_stride * 4ull, nr));
     if (heap_tids) VS_HIP(hipMemcpy(heap_tids, ix->tids + row_begin, nr * 8, hipMemcpyDeviceToHost));
     if (vecs) {
         VS_REQUIRE(ix->vecs, "index has no vector column");
-        VS_HIP(hipMemcpy2D(vecs, ix->d.dim_full * 4ull, ix->vecs + (size_t)row_begin * ix->vec_stride,
-                           ix->vec_stride * 4ull, ix->d.dim_full * 4ull, nr, hipMemcpyDeviceToHost));
+        VS_TRY(download_rows(c, vecs, ix->d.dim_full * 4ull, ix->vecs + (size_t)row_begin * ix->vec_stride, ix->vec_stride * 4ull, nr));
     }
     return VS_OK;
 }

@@ -1328,3 +1328,5 @@ extern "C" int vs_search_batch_dev_finish(vs_index* ix, vs_stats* stats) {
 
 // vs_index_qual_* / vs_search_batch_qual: kernels and host code over the pipeline above
 #include "vs_qual.h"
+// vs_search_batch_qual_exact: the exact top-k over a qualifier's rows (kernels and host code; no graph is walked)
+#include "vs_qual_exact.h"

@@ -323,7 +323,8 @@ struct SearchWorkspace {
         order_labels,                             // ... and the region label (u16: nearest seed row) of corpus rows [0, lab_rows)
         vis_slots,                                // the visibility slots of a host batch's scans (vs_search_batch_vis)
         qual_q, qual_map, qual_lab, qual_laboff,  // vs_search_batch_qual: the gathered queries, scan numbers and label keys of a later round
-        qual_slots, qual_out;                     // ... the slots of a host batch, and its rows, counts and states before they go back
+        qual_slots, qual_out,                     // ... the slots of a host batch, and its rows, counts and states before they go back
+        qx_list, qx_counts, qx_tab, qx_part;      // vs_search_batch_qual_exact (vs_qual_exact.h): row lists, their counts, scan + tile tables, partial lists
     uint32_t order_nq = 0;         // scans of the last batch's rerank order in order_perm (0: it took the scans' own order)
     // what order_labels was built from: the seed rows s * lab_step for s < lab_S of the codes at epoch lab_epoch (vs_index::codes_epoch)
     uint32_t lab_rows = 0, lab_S = 0, lab_step = 0;

@@ -822,6 +822,31 @@ class DiskAnnIndex:
         check(self._L.vs_search_batch_dev_qual_finish(self.h, C.byref(st), C.byref(qst)))
         return st.as_dict(), qst.as_dict()
 
+    def search_batch_qual_exact(self, queries, qual_slots, k=10):
+        """For each query: the exact k nearest rows among those that pass the qualifier in qual_slots[q] (0: every node), are not
+        deleted and are not hidden by the mask in force, ascending by (distance, node id); no graph is walked -> ids, tids, dist
+        [nq, k] (past the rows returned: INVALID / 0 / NaN), rows [nq], stats (_lib.QualExactStats as a dict)."""
+        q = np.ascontiguousarray(queries, np.float32).reshape(-1, self.desc.dim_full)
+        nq = q.shape[0]
+        sl = np.ascontiguousarray(qual_slots, np.uint32).ravel()
+        if sl.shape != (nq,):
+            raise ValueError(f"qual_slots must have shape ({nq},), got {sl.shape}")
+        sl = sl if nq else np.zeros(1, np.uint32)
+        ids = np.empty((nq, k), np.uint32)
+        tids = np.empty((nq, k), np.uint64)
+        dist = np.empty((nq, k), np.float32)
+        rows = np.empty(max(nq, 1), np.uint32)
+        st = _lib.QualExactStats()
+        check(self._L.vs_search_batch_qual_exact(self.h, _p(q), nq, k, _p(sl), _p(ids), _p(tids), _p(dist), _p(rows), C.byref(st)))
+        return ids, tids, dist, rows[:nq], st.as_dict()
+
+    def search_batch_qual_exact_dev(self, d_queries, nq, k, d_qual_slots, d_out_ids, d_out_rows, d_out_tids=None, d_out_dist=None):
+        """the device-resident form: every pointer is device memory; synchronous on return -> stats"""
+        st = _lib.QualExactStats()
+        check(self._L.vs_search_batch_qual_exact_dev(self.h, d_queries, nq, k, d_qual_slots, d_out_ids, d_out_tids, d_out_dist, d_out_rows,
+                                                     C.byref(st)))
+        return st.as_dict()
+
     def autotune(self, d_queries, nq, search_list_size, rescore, k, d_qlabels=None, d_qlabel_off=None, reps=2, skip=()):
         """vs_index_autotune: times every applicable exact launch variant of the search kernel on this device-resident batch,
         disqualifies any whose rows / distance bits / counters differ from the default's, keeps the fastest -> report (list of dicts)"""
