@@ -1689,6 +1689,51 @@ int vs_search_batch_qual_exact_dev(vs_index* idx, const float* d_queries, uint32
                                    uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, uint32_t* d_out_rows,
                                    vs_qual_exact_stats* stats /* may be NULL */);
 
+/* ---- qualified flat scan: SBQ top-M over a qualifier's rows, then the exact top-k of those (vs_qual_flat.h) ----
+ * Between the post-filter, whose cost grows as 1 / density, and the exact call, which reads every qualifying row's full vector, sits
+ * the reference's own candidate-then-rescore rule with the graph walk left out: rank the qualifier's rows by the Hamming distance of
+ * their SBQ codes (a code row is 1/16 of a vector row at 2 bits per dimension), rescore the best `rescore` exactly.
+ *
+ * SEMANTICS.  Every scan q is handled on its own.  With s = qual_slots[q], C is the set vs_search_batch_qual_exact defines: the nodes
+ * i < n with bit i of qualifier s set (slot 0: every node), whose heap tid offset is not 0, and which the mask in force does not hide.
+ * S is the min(rescore, |C|) rows of C that are smallest by (Hamming distance between the prepared query's SBQ code and the row's
+ * code, node id) — the Hamming distance vs_scan_topk gives the pair, the query code the one vs_prepare_queries returns.  The call
+ * returns the min(k, |S|) rows of S that are smallest by (f32::total_cmp key of the full-precision distance, node id); the distance
+ * has the bits the rerank, vs_bruteforce_topk and vs_search_batch_qual_exact give that row.  out_ids / out_tids / out_dist are
+ * [nq][k] (each may be NULL); entries past the rows returned are VS_INVALID_NODE / 0 / NaN.  out_rows[q] = min(k, |S|).
+ * k in [1, 64]; rescore in [k, VS_QUAL_FLAT_MAX_RESCORE].  nq = 0 returns VS_OK.
+ * EQUIVALENCE.  With rescore >= |C| of a scan, S = C and the scan's rows are those of vs_search_batch_qual_exact, bit for bit.
+ * vs_search_batch_qual_flat takes HOST queries, slots and outputs; _dev takes DEVICE queries, slots and outputs and is synchronous on
+ * return.
+ * REFUSALS, each before anything is launched or written: NULL idx, qual_slots or out_rows; k or rescore out of range; a slot >
+ * VS_MAX_QUAL_SLOTS; a code row wider than 1023 words, whose Hamming distance does not fit 16 bits (VS_ERR_INVALID); an empty slot,
+ * a view handle, a batch of the handle in flight, no vector column on the device, plain storage, which has no codes (VS_ERR_STATE);
+ * a code row so wide that one scan's histogram of 64 x code words + 1 counters does not fit the LDS (VS_ERR_CAPACITY).
+ * HOW.  The row lists, the slot order and the tiles are the exact call's.  One workgroup per (tile, slice) gathers each listed code
+ * row once for the tile's scans, stores the Hamming distance as 16 bits per (scan, list place) and counts it in the scan's histogram;
+ * per scan a prefix sum over the histogram gives the threshold, and one ordered pass emits the places below it and the first places
+ * at it: selection by counting, so `rescore` is bound by no list on chip.  The device rerank gives the candidates' distances, a
+ * register list the k best.  The 16-bit distances of a batch are held for a chunk of tiles at a time.
+ * vs_qual_flat_stats: tile_queries (scans per tile), lists (distinct slots compacted), rows_listed (sum of the list lengths), tiles,
+ * slices (the largest slice count of a slot), chunks (chunks of tiles run), code_reads (code rows gathered: sum over tiles of the
+ * tile's list length), reranked (sum of |S|).
+ * Options, cost choices all — no row, distance bit or determined count depends on them: VS_QUAL_FLAT_TQ (scans per tile: 1, 2, 4, 8;
+ * default 8, less where the codes and histograms of the tile do not fit the LDS), VS_QUAL_FLAT_SLICES (slices per list; unset / 0:
+ * as many as fill the device), VS_QUAL_FLAT_WS_MB (the workspace of one chunk of tiles in MiB, default 1024; a chunk holds at least one
+ * tile, so 0 gives every tile a chunk of its own).
+ * Not built: an automatic switch between the three qualified paths (choose by vs_qual_info.n_set), label
+ * keys, per-scan visibility slots, and the broker, the shm server, vs_multi and the pools. */
+#define VS_QUAL_FLAT_MAX_RESCORE 4096
+typedef struct vs_qual_flat_stats {
+    uint64_t tile_queries, lists, rows_listed, tiles, slices, chunks, code_reads, reranked;
+} vs_qual_flat_stats;
+int vs_search_batch_qual_flat(vs_index* idx, const float* queries, uint32_t nq, uint32_t k, uint32_t rescore, const uint32_t* qual_slots,
+                              uint32_t* out_ids, uint64_t* out_tids, float* out_dist, /* [nq][k], may be NULL */
+                              uint32_t* out_rows /* [nq] */, vs_qual_flat_stats* stats /* may be NULL */);
+int vs_search_batch_qual_flat_dev(vs_index* idx, const float* d_queries, uint32_t nq, uint32_t k, uint32_t rescore,
+                                  const uint32_t* d_qual_slots, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist,
+                                  uint32_t* d_out_rows, vs_qual_flat_stats* stats /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

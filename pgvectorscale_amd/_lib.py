@@ -158,7 +158,15 @@ class QualExactStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class QualFlatStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("tile_queries", "lists", "rows_listed", "tiles", "slices", "chunks", "code_reads", "reranked")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 MAX_QUAL_SLOTS = 64
+QUAL_FLAT_MAX_RESCORE = 4096
 QUAL_MAX_POPS = 65536
 QUAL_COMPLETE, QUAL_ENDED, QUAL_CUT = 0, 1, 2
 QUAL_BUDGET = 3  # vs_scanpool_fetch_qual only: the pool's row budget was reached
@@ -377,6 +385,8 @@ SYMBOLS = {
     "vs_search_batch_dev_qual_finish": (_i, [_vp, C.POINTER(Stats), C.POINTER(QualBatchStats)]),
     "vs_search_batch_qual_exact": (_i, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualExactStats)]),
     "vs_search_batch_qual_exact_dev": (_i, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualExactStats)]),
+    "vs_search_batch_qual_flat": (_i, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualFlatStats)]),
+    "vs_search_batch_qual_flat_dev": (_i, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualFlatStats)]),
     "vs_meta_layout_default": (_i, [C.POINTER(MetaLayout)]),
     "vs_meta_page_decode": (_i, [_vp, _sz, C.POINTER(MetaLayout), C.POINTER(MetaPage), _vp, _vp, _vp, _u32]),
     "vs_pages_meta": (_i, [_vp, C.POINTER(MetaLayout), C.POINTER(MetaPage), C.POINTER(IndexDesc), _vp, _vp, _u32]),

@@ -1330,3 +1330,5 @@ extern "C" int vs_search_batch_dev_finish(vs_index* ix, vs_stats* stats) {
 #include "vs_qual.h"
 // vs_search_batch_qual_exact: the exact top-k over a qualifier's rows (kernels and host code; no graph is walked)
 #include "vs_qual_exact.h"
+// vs_search_batch_qual_flat: the SBQ top-M over a qualifier's rows, then the exact top-k of those (kernels and host code)
+#include "vs_qual_flat.h"

@@ -291,6 +291,19 @@ static int qx_build_lists(vs_index* ix, const std::vector<uint32_t>& slots, QxLi
     return VS_OK;
 }
 
+// the scans by slot, in their own order within a slot (a stable counting sort): perm[place] = scan, the scans of list i at the places
+// first[i] .. first[i + 1]
+static void qx_slot_order(const QxLists& ls, const uint32_t* slots, uint32_t cq, uint32_t* perm, std::vector<uint32_t>* first_out) {
+    std::vector<uint32_t>& first = *first_out;
+    first.assign(ls.slot.size() + 1, 0);
+    uint32_t li_of[VS_MAX_QUAL_SLOTS + 1] = {0};
+    for (size_t i = 0; i < ls.slot.size(); ++i) li_of[ls.slot[i]] = (uint32_t)i;
+    for (uint32_t q = 0; q < cq; ++q) first[li_of[slots[q]] + 1]++;
+    for (size_t i = 0; i < ls.slot.size(); ++i) first[i + 1] += first[i];
+    std::vector<uint32_t> at(first.begin(), first.end() - 1);
+    for (uint32_t q = 0; q < cq; ++q) perm[at[li_of[slots[q]]]++] = q;
+}
+
 // One chunk: cq scans whose raw queries, and whose outputs, are on the device; slots HOST.  Leaves its launches on the stream.
 static int qx_run_chunk(vs_index* ix, const QxLists& ls, const float* d_queries, const uint32_t* slots, uint32_t cq, uint32_t k, uint32_t tq,
                         uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, uint32_t* d_out_rows, vs_qual_exact_stats* st) {
@@ -299,18 +312,10 @@ static int qx_run_chunk(vs_index* ix, const QxLists& ls, const float* d_queries,
     VS_TRY(devbuf_reserve(c, w.q_full, (size_t)cq * ix->vec_stride * 4));
     VS_TRY(devbuf_reserve(c, w.qcodes, (size_t)cq * ix->code_stride * 8));
     VS_TRY(launch_prepare_queries(ix, d_queries, cq, (float*)w.q_full.p, (uint64_t*)w.qcodes.p));
-    // the scans by slot, in their own order within a slot
-    std::vector<uint32_t> tab((size_t)3 * cq), first(ls.slot.size() + 1, 0);
+    std::vector<uint32_t> tab((size_t)3 * cq), first;
     uint32_t* perm = tab.data();
     uint32_t *mbase = perm + cq, *mslices = mbase + cq;
-    uint32_t li_of[VS_MAX_QUAL_SLOTS + 1] = {0};
-    for (size_t i = 0; i < ls.slot.size(); ++i) li_of[ls.slot[i]] = (uint32_t)i;
-    for (uint32_t q = 0; q < cq; ++q) first[li_of[slots[q]] + 1]++;
-    for (size_t i = 0; i < ls.slot.size(); ++i) first[i + 1] += first[i];
-    {
-        std::vector<uint32_t> at(first.begin(), first.end() - 1);
-        for (uint32_t q = 0; q < cq; ++q) perm[at[li_of[slots[q]]]++] = q;
-    }
+    qx_slot_order(ls, slots, cq, perm, &first);
     // S: as many slices as fill the device given the tiles, every slice at least one pass; VS_QUAL_EXACT_SLICES forces it
     uint32_t n_tiles = 0;
     for (size_t i = 0; i < ls.slot.size(); ++i) n_tiles += (first[i + 1] - first[i] + tq - 1) / tq;

@@ -847,6 +847,32 @@ class DiskAnnIndex:
                                                      C.byref(st)))
         return st.as_dict()
 
+    def search_batch_qual_flat(self, queries, qual_slots, k=10, rescore=50):
+        """For each query: of the rows that pass the qualifier in qual_slots[q] (0: every node), are not deleted and are not hidden, the
+        `rescore` smallest by (Hamming distance of the SBQ codes, node id), and of those the k nearest by (exact distance, node id); no
+        graph is walked -> ids, tids, dist [nq, k] (past the rows returned: INVALID / 0 / NaN), rows [nq], stats (_lib.QualFlatStats as
+        a dict).  With rescore >= the rows that qualify: the rows of search_batch_qual_exact."""
+        q = np.ascontiguousarray(queries, np.float32).reshape(-1, self.desc.dim_full)
+        nq = q.shape[0]
+        sl = np.ascontiguousarray(qual_slots, np.uint32).ravel()
+        if sl.shape != (nq,):
+            raise ValueError(f"qual_slots must have shape ({nq},), got {sl.shape}")
+        sl = sl if nq else np.zeros(1, np.uint32)
+        ids = np.empty((nq, k), np.uint32)
+        tids = np.empty((nq, k), np.uint64)
+        dist = np.empty((nq, k), np.float32)
+        rows = np.empty(max(nq, 1), np.uint32)
+        st = _lib.QualFlatStats()
+        check(self._L.vs_search_batch_qual_flat(self.h, _p(q), nq, k, rescore, _p(sl), _p(ids), _p(tids), _p(dist), _p(rows), C.byref(st)))
+        return ids, tids, dist, rows[:nq], st.as_dict()
+
+    def search_batch_qual_flat_dev(self, d_queries, nq, k, rescore, d_qual_slots, d_out_ids, d_out_rows, d_out_tids=None, d_out_dist=None):
+        """the device-resident form: every pointer is device memory; synchronous on return -> stats"""
+        st = _lib.QualFlatStats()
+        check(self._L.vs_search_batch_qual_flat_dev(self.h, d_queries, nq, k, rescore, d_qual_slots, d_out_ids, d_out_tids, d_out_dist,
+                                                    d_out_rows, C.byref(st)))
+        return st.as_dict()
+
     def autotune(self, d_queries, nq, search_list_size, rescore, k, d_qlabels=None, d_qlabel_off=None, reps=2, skip=()):
         """vs_index_autotune: times every applicable exact launch variant of the search kernel on this device-resident batch,
         disqualifies any whose rows / distance bits / counters differ from the default's, keeps the fastest -> report (list of dicts)"""
