@@ -106,7 +106,7 @@ const char* vs_last_error(void);
 
 /* Which kernel the first attempt of a handle's last batch (its last chunk) ran, and with which planned capacities.  Read-only: it
  * changes no launch.  VS_ERR_INVALID for NULL arguments, VS_ERR_STATE before the first batch of the handle. */
-enum { VS_SEARCH_GENERAL = 0, VS_SEARCH_FAST_SBQ = 1, VS_SEARCH_FAST_PLAIN = 2 };
+enum { VS_SEARCH_GENERAL = 0, VS_SEARCH_FAST_SBQ = 1, VS_SEARCH_FAST_PLAIN = 2, VS_SEARCH_LAT_SBQ = 3 };
 typedef struct vs_search_info {
     uint32_t kernel;       /* what the first attempt of the last batch (chunk) ran */
     uint32_t resident;     /* scans in flight on the persistent grid (0: general kernel) */
@@ -142,6 +142,14 @@ int vs_index_last_search_info(const vs_index* idx, vs_search_info* out);
  * launches, where that state fits 96 KB of LDS; "0" (or VS_POOL_FAST "0") the general kernel.  Read when a pool is created, as
  * are VS_PF_HEAP_LDS / VS_PF_HEAP_CAP / VS_PF_DEDUP_SLOTS / VS_PF_VISITED, which override the pool's planned capacities too (a pooled
  * scan that outgrows one fails with VS_ERR_CAPACITY).  Rows, distance bits and the reference counters are the same under both.
+ * VS_LAT_SCANS: latency mode — "N" > 0: an SBQ batch (chunk) of at most N scans without label keys first runs k_search_lat, one scan
+ * per workgroup of several waves with the scan's state and a cache of speculatively scored neighbor lists on chip, the general kernel
+ * re-running the scans that outgrow it (vs_stats.fallback_scans); unset / "0" (default): off, every launch as without it.  Rows,
+ * distance bits and the reference counters are the same under both; vs_index_last_search_info reports VS_SEARCH_LAT_SBQ, the workgroups
+ * in `resident`, the waves per scan in reserved[0] and the cache entries in reserved[1].  Cost choices (no row, count or status depends
+ * on them): VS_LAT_WAVES (waves per scan, 2..8, default 4), VS_LAT_SPEC (targets scored per round, 1..7, default 7), VS_LAT_CACHE
+ * (cache entries, 1..64, default 8).  Its capacities, for tests and measurement (0 / unset = planned): VS_LAT_HEAP_LDS, VS_LAT_HEAP_CAP,
+ * VS_LAT_DEDUP_SLOTS (rounded up to a power of two), VS_LAT_VISITED.
  * VS_POOL_QUAL_CHUNK: the pops ONE window launch of vs_scanpool_fetch_qual may make per scan (default 4096, capped so that the launch
  * stays within 64 KB of LDS); a fetch that needs more launches again.  A cost choice: no row, count or state depends on it.
  * VS_QUAL_EXACT_SLICES: the slices vs_search_batch_qual_exact cuts every slot's row list into (unset / 0: as many as fill the device;

@@ -42,6 +42,7 @@ class Stats(C.Structure):
 
 
 VS_SEARCH_GENERAL, VS_SEARCH_FAST_SBQ, VS_SEARCH_FAST_PLAIN = 0, 1, 2
+VS_SEARCH_LAT_SBQ = 3  # k_search_lat: one SBQ scan per multi-wave workgroup (VS_LAT_SCANS)
 
 
 class SearchInfo(C.Structure):
@@ -49,7 +50,9 @@ class SearchInfo(C.Structure):
         ("reserved", C.c_uint32 * 2)]
 
     def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _ in self._fields_[:6]}
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_[:6]}
+        d["reserved"] = [int(v) for v in self.reserved]  # VS_SEARCH_LAT_SBQ: waves per scan, cache entries (else 0, 0)
+        return d
 
 
 class TuneEntry(C.Structure):

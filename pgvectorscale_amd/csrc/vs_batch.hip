@@ -757,6 +757,18 @@ static const size_t PLAIN_LDS_BUDGET = 40 * 1024;
 // (MI355X_MICROARCH.md "Indexed rows": 16 waves per CU at 4 rows in flight)
 static const size_t PLAIN_LDS_TARGET = 20 * 1024;
 
+// The planned capacities of a scan whose whole state lives on chip (k_search_plain, k_search_lat), from (n, num_neighbors, L, M) alone.
+// They clamp to the index: a scan inserts at most n ids, holds at most n heap entries and visits at most n nodes, so a small index is
+// planned for every possible scan and hands nothing over.
+static void plan_onchip_caps(uint32_t n, uint32_t R, uint32_t L, uint32_t M, uint32_t* slots, uint32_t* hcap, uint32_t* vcap) {
+    const uint64_t typ_visits = (uint64_t)L + L / 4 + M + 16;               // as initial_caps
+    const uint64_t typ_ins = typ_visits * std::min<uint32_t>(R, 32) + 64;   // up to 32 new ids per visit
+    *slots = std::max<uint32_t>(next_pow2_u32(std::min<uint64_t>(std::min<uint64_t>(typ_ins, n) * 4 / 3 + 1, 1u << 22)), 64);
+    const uint64_t pushes = (2ull * L + M + 32) * R;  // as initial_caps
+    *hcap = (uint32_t)std::max<uint64_t>(std::min<uint64_t>(std::min<uint64_t>(pushes, n), 1u << 22), 1);
+    *vcap = (uint32_t)std::max<uint64_t>(std::min<uint64_t>(3ull * L + M + 64, n), 1);
+}
+
 // Enqueues nothing and touches no buffer; its only device-facing call is the occupancy query.  *on = false: the general kernel
 // runs alone, as before.
 static int plan_plain_launch(vs_index* ix, const BatchPlan& bp, bool masked, PlainLaunch* out, bool* on) {
@@ -767,17 +779,10 @@ static int plan_plain_launch(vs_index* ix, const BatchPlan& bp, bool masked, Pla
     p.nq = bp.nq;
     p.L = L;
     p.M = M;
-    // Capacities clamp to the index: a scan inserts at most n ids, holds at most n heap entries and visits at most n nodes, so
-    // a small index is planned for every possible scan and hands nothing over.
-    const uint64_t typ_visits = (uint64_t)L + L / 4 + M + 16;               // as initial_caps
-    const uint64_t typ_ins = typ_visits * std::min<uint32_t>(R, 32) + 64;   // up to 32 new ids per visit
-    p.slots = std::max<uint32_t>(next_pow2_u32(std::min<uint64_t>(std::min<uint64_t>(typ_ins, n) * 4 / 3 + 1, 1u << 22)), 64);
+    plan_onchip_caps(n, R, L, M, &p.slots, &p.hcap, &p.vcap);
     if (const uint32_t v = env_u32("VS_PF_DEDUP_SLOTS", 0)) p.slots = std::max<uint32_t>(next_pow2_u32(std::min<uint32_t>(v, 1u << 22)), 64);
     p.ins_limit = n <= p.slots / 4 * 3 ? 0xFFFFFFFFu : p.slots / 4 * 3;  // load limit 75 %
     p.lds_table = p.slots <= PLAIN_LDS_TABLE_MAX ? 1u : 0u;
-    const uint64_t pushes = (2ull * L + M + 32) * R;  // as initial_caps
-    p.hcap = (uint32_t)std::max<uint64_t>(std::min<uint64_t>(std::min<uint64_t>(pushes, n), 1u << 22), 1);
-    p.vcap = (uint32_t)std::max<uint64_t>(std::min<uint64_t>(3ull * L + M + 64, n), 1);
     if (const uint32_t v = env_u32("VS_PF_VISITED", 0)) p.vcap = v;
     // the heap's LDS part: the largest of 1023 / 511 / 255 / 127 entries that keeps the scan within PLAIN_LDS_TARGET
     p.hl = 127;
@@ -832,6 +837,74 @@ static int run_plain_attempt(vs_index* ix, const BatchPlan& bp, PlainLaunch p) {
     return VS_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// the latency mode of a small SBQ chunk: k_search_lat (vs_search_lat.h), one scan per multi-wave workgroup.  Opt-in (VS_LAT_SCANS);
+// plan_lat_launch decides whether it runs and with which capacities, run_lat_attempt binds buffers and launches.  As for the plain
+// kernel nothing is remembered between batches, and the launch stays out of the SBQ tables' sizing feedback (ScanObs).
+// ---------------------------------------------------------------------------------------------------------------
+// Enqueues nothing and touches no buffer.  *on = false: the chunk's launches are exactly what they are without the option.
+static int plan_lat_launch(const vs_index* ix, const BatchPlan& bp, bool keyed, LatLaunch* out, bool* on) {
+    *on = false;
+    const uint32_t max_scans = env_u32("VS_LAT_SCANS", 0);
+    if (max_scans == 0 || bp.nq > max_scans || ix->d.storage_type == VS_STORAGE_PLAIN || keyed || ix->d.n == 0 || !ix->codes) return VS_OK;
+    const uint32_t n = ix->d.n, R = ix->d.num_neighbors, L = bp.L, M = bp.M;
+    LatLaunch p{};
+    p.nq = bp.nq;
+    p.L = L;
+    p.M = M;
+    p.waves = std::min<uint32_t>(std::max<uint32_t>(env_u32("VS_LAT_WAVES", 4), 2), 8);
+    p.spec = std::min<uint32_t>(std::max<uint32_t>(env_u32("VS_LAT_SPEC", 7), 1), 7);
+    p.cache = std::min<uint32_t>(std::max<uint32_t>(env_u32("VS_LAT_CACHE", 8), 1), 64);
+    plan_onchip_caps(n, R, L, M, &p.slots, &p.hcap, &p.vcap);  // (as the plain kernel's)
+    if (const uint32_t v = env_u32("VS_LAT_DEDUP_SLOTS", 0)) p.slots = std::max<uint32_t>(next_pow2_u32(std::min<uint32_t>(v, 1u << 22)), 64);
+    p.ins_limit = n <= p.slots / 4 * 3 ? 0xFFFFFFFFu : p.slots / 4 * 3;  // load limit 75 %
+    if (const uint32_t v = env_u32("VS_LAT_VISITED", 0)) p.vcap = v;
+    // the heap's LDS part: the largest of 4095 .. 127 entries that keeps the scan within the budget (one scan has the CU's LDS to itself)
+    p.hl = 127;
+    for (uint32_t hl : {4095u, 2047u, 1023u, 511u, 255u}) {
+        LatLaunch t = p;
+        t.hl = hl;
+        if (lat_lds_bytes(ix, t) <= LAT_LDS_BUDGET) {
+            p.hl = hl;
+            break;
+        }
+    }
+    if (const uint32_t v = env_u32("VS_LAT_HEAP_LDS", 0)) p.hl = v;
+    if (const uint32_t v = env_u32("VS_LAT_HEAP_CAP", 0)) p.hcap = v;
+    p.hl = std::min(p.hl, p.hcap);
+    if (lat_lds_bytes(ix, p) > LAT_LDS_BUDGET) return VS_OK;  // (a long search list: the throughput kernels take the chunk)
+    *out = p;
+    *on = true;
+    return VS_OK;
+}
+
+static int run_lat_attempt(vs_index* ix, const BatchPlan& bp, LatLaunch p) {
+    vs_ctx* c = ix->ctx;
+    SearchWorkspace& w = ix->ws;
+    ix->last_ins_limit = 0;  // (the sizing feedback of ScanObs is the fast kernel's tables': off for latency launches)
+    // the per-workgroup heap spill regions: never cleared, so they only have to exist
+    // (heap_g4b, not the array the fast kernel keeps in the index's slab: a latency launch moves nothing of a later fast launch)
+    VS_TRY(devbuf_reserve(c, w.heap_g4b, std::max<size_t>((size_t)p.nq * (p.hcap - p.hl) * 8, 16)));
+    VS_TRY(devbuf_reserve(c, w.pool_ctr, 64));
+    VS_HIP(hipMemsetAsync(w.pool_ctr.p, 0, 64, c->stream));
+    VS_TRY(devbuf_reserve(c, w.fb_flag, (size_t)p.nq * 4));
+    VS_HIP(hipMemsetAsync(w.fb_flag.p, 0, (size_t)p.nq * 4, c->stream));
+    p.vis = batch_vis(ix, bp);
+    p.qcodes = (const uint64_t*)w.qcodes.p;
+    p.heap_g = (uint64_t*)w.heap_g4b.p;
+    p.out_ids = (uint32_t*)w.stream_ids.p;
+    p.out_ham = (uint32_t*)w.stream_ham.p;
+    p.out_cnt = (uint32_t*)w.stream_cnt.p;
+    p.stats = (uint32_t*)w.stats.p;
+    p.status = (uint32_t*)w.status.p;
+    hipEvent_t ev = prof_begin(c);
+    VS_TRY(launch_search_lat(ix, p));
+    prof_end(c, PK_SEARCH, ev);
+    ix->last_info = vs_search_info{VS_SEARCH_LAT_SBQ, p.nq, (uint32_t)lat_lds_bytes(ix, p), p.hl, p.slots, p.vcap, {p.waves, p.cache}};
+    ix->last_info_valid = true;
+    return VS_OK;
+}
+
 // runs prepare -> search (-> rerank -> resort) for nq queries already on the device.  Outputs land in the workspace
 // (or the caller's device buffers).  Nothing here waits for the device: the scans that outgrew every pool are found and re-run by
 // finish_launch.
@@ -860,8 +933,12 @@ static int run_search_chunk(vs_index* ix, const BatchPlan& bp, const float* d_ra
     PlainLaunch pl;
     bool plain_first = false;
     VS_TRY(plan_plain_launch(ix, bp, batch_vis(ix, bp).bytes != nullptr, &pl, &plain_first));
-    const bool fast_done = caps.f_on || plain_first;  // a first attempt ran: the general kernel takes only what it handed over
-    if (caps.f_on) VS_TRY(run_fast_attempts(ix, bp, caps, d_qlabels, d_qlabel_off));
+    LatLaunch ll;
+    bool lat_first = false;
+    VS_TRY(plan_lat_launch(ix, bp, d_qlabel_off != nullptr, &ll, &lat_first));
+    const bool fast_done = lat_first || caps.f_on || plain_first;  // a first attempt ran: the general kernel takes only what it handed over
+    if (lat_first) VS_TRY(run_lat_attempt(ix, bp, ll));
+    else if (caps.f_on) VS_TRY(run_fast_attempts(ix, bp, caps, d_qlabels, d_qlabel_off));
     else if (plain_first) VS_TRY(run_plain_attempt(ix, bp, pl));
     else {
         SearchLaunch g = general_launch(ix, bp, caps, d_qlabels, d_qlabel_off);

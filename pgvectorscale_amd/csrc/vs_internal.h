@@ -647,6 +647,28 @@ size_t plain_resume_words(const PlainLaunch& s);  // u32 words of one saved scan
 int launch_search_plain(vs_index* idx, const PlainLaunch& s);
 int launch_search_plain_rs(vs_index* idx, const PlainLaunch& s);  // grid = s.nq pool slots; persist / scan_counter are not used
 int plain_resident_scans(vs_index* idx, const PlainLaunch& s, uint32_t* out);  // workgroups of k_search_plain the device holds at once
+// latency mode (vs_search_lat.h, k_search_lat): one SBQ scan per workgroup of `waves` waves — wave 0 owns the scan's state (all of it
+// in LDS but the heap positions >= hl), every wave fills the expansion cache of `cache` entries, up to `spec` targets a round
+struct LatLaunch {
+    uint32_t nq, L, M;
+    uint32_t hl;         // candidate-heap entries (8 bytes each) resident in LDS: heap positions [0, hl)
+    uint32_t hcap;       // total heap capacity; positions [hl, hcap) live in the workgroup's region of heap_g
+    uint32_t vcap;       // visited-list capacity (LDS)
+    uint32_t slots;      // slots of the dedup table (a power of two >= 64): ids and one occupancy bit per slot in LDS
+    uint32_t ins_limit;  // ids the table may hold (<= 3/4 of the slots); 0xFFFFFFFF: the index has fewer rows than that
+    uint32_t waves, cache, spec;
+    VisView vis;
+    const uint64_t* qcodes = nullptr;  // [nq][code_stride]
+    uint64_t* heap_g = nullptr;        // [nq][hcap - hl]
+    uint32_t* out_ids = nullptr;
+    uint32_t* out_ham = nullptr;
+    uint32_t* out_cnt = nullptr;
+    uint32_t* stats = nullptr;
+    uint32_t* status = nullptr;
+};
+static const size_t LAT_LDS_BUDGET = 128 * 1024;  // of a CU's 160 KB
+size_t lat_lds_bytes(const vs_index* idx, const LatLaunch& s);
+int launch_search_lat(vs_index* idx, const LatLaunch& s);  // grid = s.nq workgroups of s.waves waves
 enum { ST_VISITS = 0, ST_CAND = 1, ST_DQ = 2, ST_READS = 3, ST_NEXT = 4, ST_GSPILL = 5, ST_INVIS = 6, ST_INS = 7 /* ids the fast kernel inserted */, ST_N = 8 };
 enum { OVF_HEAP = 1, OVF_VISITED = 2, OVF_HASH = 4, OVF_POOL = 8,
        OVF_KEY = 16 };  // (fast kernel only) the scan key has more labels than its LDS slot holds: the general kernel runs the scan

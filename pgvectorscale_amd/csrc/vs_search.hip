@@ -1217,3 +1217,6 @@ int launch_search_plain_rs(vs_index* idx, const PlainLaunch& s) {
     return plain_dispatch(idx, s, nullptr, true);
 }
 int plain_resident_scans(vs_index* idx, const PlainLaunch& s, uint32_t* out) { return plain_dispatch(idx, s, out); }
+
+// k_search_lat: one SBQ scan per multi-wave workgroup for small batches (kernel and launch wrapper)
+#include "vs_search_lat.h"

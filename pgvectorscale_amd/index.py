@@ -227,8 +227,10 @@ class DiskAnnIndex:
         check(self._L.vs_index_get_desc(self.h, C.byref(self.desc)))
 
     def last_search_info(self):
-        """which kernel the first attempt of this handle's last batch ran (kernel: VS_SEARCH_GENERAL / _FAST_SBQ / _FAST_PLAIN), the scans
-        resident on its persistent grid, its LDS per scan and planned capacities (vs_index_last_search_info)"""
+        """which kernel the first attempt of this handle's last batch ran (kernel: VS_SEARCH_GENERAL / _FAST_SBQ / _FAST_PLAIN /
+        _LAT_SBQ), the scans resident on its persistent grid (_LAT_SBQ: the workgroups launched), its LDS per scan and planned capacities
+        (vs_index_last_search_info); `reserved`: the struct's two spare words as a list — [waves per scan, cache entries] under
+        _LAT_SBQ, [0, 0] otherwise"""
         info = _lib.SearchInfo()
         check(self._L.vs_index_last_search_info(self.h, C.byref(info)))
         return info.as_dict()
