@@ -154,7 +154,9 @@ int vs_index_last_search_info(const vs_index* idx, vs_search_info* out);
  * stays within 64 KB of LDS); a fetch that needs more launches again.  A cost choice: no row, count or state depends on it.
  * VS_QUAL_EXACT_SLICES: the slices vs_search_batch_qual_exact cuts every slot's row list into (unset / 0: as many as fill the device;
  * never more than the list has 32-row passes).  VS_QUAL_EXACT_TQ: the scans of one tile (1, 2, 4, 8, 16; default 8).  Cost choices
- * both: no row, distance bit or count depends on them. */
+ * both: no row, distance bit or count depends on them.
+ * VS_GROUP_FIRST_POPS: the pops of the first round of vs_search_batch_grouped (clamped to [k, max_pops]; unset / 0: the rule of
+ * vs_search_batch_qual, VS_QUAL_FIRST_POPS included).  A cost choice: no row, count or state depends on it. */
 int vs_set_option(const char* name, const char* value);
 int vs_get_option(const char* name, char* out, size_t cap);
 const char* vs_version(void);
@@ -1741,6 +1743,54 @@ int vs_search_batch_qual_flat(vs_index* idx, const float* queries, uint32_t nq, 
 int vs_search_batch_qual_flat_dev(vs_index* idx, const float* d_queries, uint32_t nq, uint32_t k, uint32_t rescore,
                                   const uint32_t* d_qual_slots, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist,
                                   uint32_t* d_out_rows, vs_qual_flat_stats* stats /* may be NULL */);
+
+/* ---- grouped scans: the first k rows of a scan with at most per_group rows per group (vs_group.h) ----
+ * A row of a chunked corpus is a chunk of a document: "the 10 nearest documents" (DISTINCT ON (doc_id)) and "the 10 nearest chunks, at
+ * most 3 per document" (row_number() OVER (PARTITION BY doc_id) <= g) ask for rows under a rule that depends on the rows kept before.
+ *
+ * SEMANTICS.  For scan q let r0, r1, ... be the rows of the qualified-scan section: the reference's successive amgettuple rows under the
+ * mask in force, the rows vs_search_batch returns for any k.  Let G be the index's GROUP COLUMN, one uint32 per node, and Q the
+ * qualifier scan q names (slot 0: every node passes).  Walking the rows in order, r_i is KEPT iff node(r_i) passes Q and
+ * G[node(r_i)] == VS_GROUP_NONE (ungrouped, never limited) or fewer than per_group rows kept before r_i carry the same group value.
+ * A row that fails Q does not count against its group.  The scan returns the first k kept rows in stream order, tid and distance bits
+ * as vs_search_batch gives them, and never looks past r_(max_pops - 1).  out_rows, out_pops, out_state (VS_QUAL_COMPLETE / _ENDED /
+ * _CUT) and vs_qual_batch_stats mean what they mean for vs_search_batch_qual.  A rejected row is left out AFTER its pop: it has sat in
+ * the rescore window and been reranked like any other.  Two identities hold bit for bit: per_group >= k gives the rows, pops and
+ * state of vs_search_batch_qual, and with every slot 0 as well the first k rows of vs_search_batch.
+ *
+ * THE GROUP COLUMN is device memory at the index's capacity.  vs_index_groups_put takes n HOST values, _put_dev n DEVICE values;
+ * vs_index_groups_patch overwrites rows [first_node, first_node + count) from HOST values (first_node + count <= n: how a shim gives
+ * appended rows their group); vs_index_groups_get reads the n values back; vs_index_groups_drop frees the column (VS_ERR_STATE
+ * without one, as _patch and _get).  LIFETIME: vs_index_reserve and growing inserts carry the column over, rows added later read
+ * VS_GROUP_NONE until they are patched; vs_index_compact renumbers the nodes and DROPS the column (one that
+ * VS_COMPACT_KEEP_EDGES_CHECK refuses leaves it untouched).  A view handle and a batch of the handle in flight are VS_ERR_STATE.
+ *
+ * THE BATCH.  The three calls are the qualified ones with per_group after k.  REFUSALS, each before anything is launched: per_group
+ * outside [1, k], max_pops outside [k, VS_QUAL_MAX_POPS] and k above VS_GROUP_MAX_K (VS_ERR_INVALID); no group column, a view handle, a batch of the handle in
+ * flight (VS_ERR_STATE); the slot checks of the qualified call, except that qual_slots may be NULL here: every slot is 0.
+ * The rounds are those of vs_search_batch_qual (first pops P1 by its rule, the option VS_GROUP_FIRST_POPS overrides it; unfinished scans
+ * re-run from the start at twice the pops): cost choices, on which no row, count or state depends.  The window is
+ * k_rerank_window_grouped, or k_resort_grouped (a wave per scan) for the windows it does not take, VS_RERANK_FUSED=0 and rescore 0.
+ * vs_search_batch_dev_grouped_finish finishes a vs_search_batch_dev_grouped (vs_search_batch_dev_qual_finish does too: the batch in
+ * flight is the same record).
+ * Not built: grouped scan pools, cursors, the broker, the shm server and vs_multi; the exact and the flat qualified calls under a
+ * group rule; per-scan visibility slots together with groups. */
+#define VS_GROUP_NONE 0xFFFFFFFFu
+#define VS_GROUP_MAX_K 8192 /* k of a grouped batch: the groups of a scan's kept rows stay on chip (a larger k is VS_ERR_INVALID) */
+int vs_index_groups_put(vs_index* idx, const uint32_t* values /* n host */);
+int vs_index_groups_put_dev(vs_index* idx, const uint32_t* d_values /* n device */);
+int vs_index_groups_patch(vs_index* idx, uint32_t first_node, uint32_t count, const uint32_t* values /* count host */);
+int vs_index_groups_get(vs_index* idx, uint32_t* values /* n host */);
+int vs_index_groups_drop(vs_index* idx);
+int vs_search_batch_grouped(vs_index* idx, const float* queries, const int16_t* qlabels, const uint32_t* qlabel_off, uint32_t nq,
+                            uint32_t search_list_size, uint32_t rescore, uint32_t k, uint32_t per_group, const uint32_t* qual_slots, uint32_t max_pops,
+                            uint32_t* out_ids, uint64_t* out_tids, float* out_dist, uint32_t* out_rows, uint32_t* out_pops,
+                            uint32_t* out_state, vs_stats* stats, vs_qual_batch_stats* qstats);
+int vs_search_batch_dev_grouped(vs_index* idx, const float* d_queries, const int16_t* d_qlabels, const uint32_t* d_qlabel_off, uint32_t nq,
+                                uint32_t search_list_size, uint32_t rescore, uint32_t k, uint32_t per_group, const uint32_t* d_qual_slots, uint32_t max_pops,
+                                uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, uint32_t* d_out_rows, uint32_t* d_out_pops,
+                                uint32_t* d_out_state);
+int vs_search_batch_dev_grouped_finish(vs_index* idx, vs_stats* stats, vs_qual_batch_stats* qstats);
 
 #ifdef __cplusplus
 }

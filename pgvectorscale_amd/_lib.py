@@ -172,6 +172,7 @@ MAX_QUAL_SLOTS = 64
 QUAL_FLAT_MAX_RESCORE = 4096
 QUAL_MAX_POPS = 65536
 QUAL_COMPLETE, QUAL_ENDED, QUAL_CUT = 0, 1, 2
+GROUP_NONE = 0xFFFFFFFF  # VS_GROUP_NONE: a node no group rule limits
 QUAL_BUDGET = 3  # vs_scanpool_fetch_qual only: the pool's row budget was reached
 
 
@@ -386,6 +387,15 @@ SYMBOLS = {
                                   C.POINTER(QualBatchStats)]),
     "vs_search_batch_dev_qual": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vs_search_batch_dev_qual_finish": (_i, [_vp, C.POINTER(Stats), C.POINTER(QualBatchStats)]),
+    "vs_index_groups_put": (_i, [_vp, _vp]),
+    "vs_index_groups_put_dev": (_i, [_vp, _vp]),
+    "vs_index_groups_patch": (_i, [_vp, _u32, _u32, _vp]),
+    "vs_index_groups_get": (_i, [_vp, _vp]),
+    "vs_index_groups_drop": (_i, [_vp]),
+    "vs_search_batch_grouped": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(Stats),
+                                     C.POINTER(QualBatchStats)]),
+    "vs_search_batch_dev_grouped": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vs_search_batch_dev_grouped_finish": (_i, [_vp, C.POINTER(Stats), C.POINTER(QualBatchStats)]),
     "vs_search_batch_qual_exact": (_i, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualExactStats)]),
     "vs_search_batch_qual_exact_dev": (_i, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualExactStats)]),
     "vs_search_batch_qual_flat": (_i, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualFlatStats)]),

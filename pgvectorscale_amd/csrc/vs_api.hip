@@ -509,6 +509,7 @@ extern "C" void vs_index_free(vs_index* ix) {
     for (DevBuf* b : bufs) devbuf_free(*b);
     if (!ix->is_view) vs_vis_base_free(ix);
     if (!ix->is_view) vs_qual_drop_all(ix);
+    if (!ix->is_view) vs_groups_drop(ix);
     if (w.red_host) (void)hipHostFree(w.red_host);
     w.red_host = nullptr;
     vs_slab_release(ix->slab);  // (after the stream synchronisation above; the last handle frees the allocation)
@@ -536,6 +537,8 @@ static int vs_index_view_impl(vs_index* src, vs_ctx* c, vs_index** out) {
     }
     v->visible_own = nullptr;
     v->qs = nullptr;  // (qualifiers are the owner's: a view names none)
+    v->groups = nullptr;  // (and so is the group column)
+    v->groups_rows = 0;
     v->ws = SearchWorkspace{};
     v->last_stats = vs_stats{};
     *out = v;
@@ -739,6 +742,7 @@ int vs_index_reserve_impl(vs_index* ix, uint32_t capacity, const char* what) {
     add(&ix->label_off, 4, 0, 1);
     add(&ix->visible_own, 1, 1);
     for (int sn = 1; sn < VS_MAX_SNAPSHOTS; ++sn) add(&ix->snap[sn], 1, 0);
+    add(&ix->groups, 4, 0xFF);  // (the group column: new rows read VS_GROUP_NONE, four bytes of 0xFF, until they are patched)
     if (ix->vb) add(&ix->vb->cls, 1, 0);  // (the class bytes of the visibility base: new rows read class 0, invisible to all)
     // the qualifiers (one bit per node; bits past d.n are 0 by construction, so the old words are kept whole): new rows do not qualify
     const size_t qual_words = ((size_t)capacity + 63) / 64;
@@ -777,6 +781,7 @@ int vs_index_reserve_impl(vs_index* ix, uint32_t capacity, const char* what) {
     }
     ix->capacity = capacity;
     if (ix->vb && ix->vb->cls) ix->vb->cls_rows = capacity;
+    if (ix->groups) ix->groups_rows = capacity;
     if (ix->qs && qual_words > ix->qs->words) {
         ix->qs->words = qual_words;
         if (ix->qs->tab) VS_HIP(hipMemcpy(ix->qs->tab, ix->qs->bits, sizeof ix->qs->bits, hipMemcpyHostToDevice));  // (the slots moved)

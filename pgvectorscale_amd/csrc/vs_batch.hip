@@ -259,7 +259,15 @@ static int run_post_search(vs_index* ix, const BatchPlan& bp, uint32_t* d_out_id
         // same with the serial heap replay forced for every scan; 0 = the k_rerank + k_resort pair, which also takes the windows
         // that do not fit the fused kernel's LDS budget (rerank_window_fits)
         const uint32_t fused = env_u32("VS_RERANK_FUSED", 1);
-        if (fused && bp.qual.pops && rerank_window_fits(ix, M, bp.rescore, bp.k)) {
+        if (fused && bp.qual.pops && bp.per_group && rerank_window_grouped_fits(ix, M, bp.rescore, bp.k)) {  // (a grouped batch: vs_group.h)
+            hipEvent_t ev = prof_begin(c);
+            VS_TRY(launch_rerank_window_grouped(ix, (const float*)w.q_full.p, (const uint32_t*)w.stream_ids.p, (const uint32_t*)w.stream_cnt.p, M,
+                                                bp.rescore, bp.k, nq, d_out_ids, d_out_tids, d_out_dist, fused == 2 ? 2u : 1u, perm, deal,
+                                                GroupLaunch{bp.qual, bp.groups, bp.per_group}));
+            prof_end(c, PK_RERANK, ev);
+            return VS_OK;
+        }
+        if (fused && bp.qual.pops && !bp.per_group && rerank_window_fits(ix, M, bp.rescore, bp.k)) {
             hipEvent_t ev = prof_begin(c);
             VS_TRY(launch_rerank_window_qual(ix, (const float*)w.q_full.p, (const uint32_t*)w.stream_ids.p, (const uint32_t*)w.stream_cnt.p, M,
                                              bp.rescore, bp.k, nq, d_out_ids, d_out_tids, d_out_dist, fused == 2 ? 2u : 1u, perm, deal, bp.qual));
@@ -279,6 +287,14 @@ static int run_post_search(vs_index* ix, const BatchPlan& bp, uint32_t* d_out_id
         VS_TRY(launch_rerank(ix, (const float*)w.q_full.p, (const uint32_t*)w.stream_ids.p, nullptr,
                              (const uint32_t*)w.stream_cnt.p, M, nq, (float*)w.rr_dist.p, 0, perm, deal));
         prof_end(c, PK_RERANK, ev);
+    }
+    if (bp.qual.pops && bp.per_group) {
+        hipEvent_t ev = prof_begin(c);
+        VS_TRY(launch_resort_grouped(ix, nq, M, bp.rescore, bp.k, (const uint32_t*)w.stream_ids.p, (const uint32_t*)w.stream_cnt.p,
+                                     bp.rescore ? (const float*)w.rr_dist.p : nullptr, (uint64_t*)w.resort_heap.p, d_out_ids, d_out_tids, d_out_dist,
+                                     GroupLaunch{bp.qual, bp.groups, bp.per_group}));
+        prof_end(c, PK_RESORT, ev);
+        return VS_OK;
     }
     if (bp.qual.pops) {
         hipEvent_t ev = prof_begin(c);
@@ -1321,7 +1337,7 @@ extern "C" int vs_stream_batch(vs_index* ix, const float* queries, const int16_t
 int vs_search_batch_dev_impl(vs_index* ix, const float* d_queries, const int16_t* d_qlabels,
                                    const uint32_t* d_qlabel_off, uint32_t nq, uint32_t L, uint32_t rescore, uint32_t k,
                                    uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, const uint32_t* d_scan_slots,
-                                   const QualLaunch* qual) {
+                                   const QualLaunch* qual, const uint32_t* d_groups, uint32_t per_group) {
     VS_REQUIRE(ix && (nq == 0 || (d_queries && d_out_ids)), "vs_search_batch_dev: bad args");
     uint32_t vis_mode = BV_INDEX_MASK;
     if (d_scan_slots && nq) {  // the slots come back once, so that a slot without an overlay is refused before anything is launched
@@ -1345,6 +1361,10 @@ int vs_search_batch_dev_impl(vs_index* ix, const float* d_queries, const int16_t
     VS_REQUIRE(chunk_queries(ix, caps, M, nq) == nq, "vs_search_batch_dev: batch of %u queries exceeds the workspace budget", nq);
     BatchPlan bp{nq, L, rescore, k, M, false, vis_mode, vis_mode == BV_SLOTS ? d_scan_slots : nullptr};
     if (qual) bp.qual = *qual;
+    if (qual && d_groups) {
+        bp.groups = d_groups;
+        bp.per_group = per_group;
+    }
     VS_TRY(run_search_chunk(ix, bp, d_queries, d_qlabels, d_qlabel_off, d_out_ids, d_out_tids, d_out_dist, caps));
     w.pending = true;
     w.pend = PendingBatch{bp, caps, d_qlabels, d_qlabel_off, d_out_ids, d_out_tids, d_out_dist};

@@ -2676,10 +2676,12 @@ static int compact_impl(vs_index* ix, uint64_t stage_bytes, uint32_t flags, uint
     VS_REQUIRE(stage_bytes >= widest, "%s: stage_bytes %llu holds no row of %zu bytes", what, (unsigned long long)stage_bytes, widest);
     VS_REQUIRE(ix->nbr_stride % 16 == 0, "%s: neighbor rows of %u entries", what, ix->nbr_stride);
     // Dropped by every compaction that goes ahead, but not by one VS_COMPACT_KEEP_EDGES_CHECK refuses ("every byte as it was"): the
-    // classes and the depends list name rows by their old numbers, and so do the qualifiers (a bit per OLD node number)
+    // classes and the depends list name rows by their old numbers, and so do the qualifiers (a bit per OLD node number) and the group
+    // column (a value per OLD node number)
     auto drop_numbered = [&]() {
         vs_vis_base_drop(ix);
         vs_qual_drop_all(ix);
+        vs_groups_drop(ix);
     };
     vs_compact_stats s{};
     s.n_before = s.n_after = n;

@@ -241,6 +241,13 @@ struct QualLaunch {
     uint32_t* out_pops = nullptr;
     uint32_t* out_state = nullptr;
 };
+// The same window under a GROUP rule (vs_search_batch_grouped, vs_group.h): a popped row that passes ql's qualifier is kept iff its group
+// groups[node] is VS_GROUP_NONE or fewer than per_group rows kept before it carry the same value.  groups: DEVICE, one u32 per node.
+struct GroupLaunch {
+    QualLaunch ql;
+    const uint32_t* groups = nullptr;
+    uint32_t per_group = 0;
+};
 // one launch (a chunk of the batch): nq scans of search list L that each leave a stream of M rows
 enum { BV_INDEX_MASK = 0, BV_NONE = 1, BV_SLOTS = 2 };
 struct BatchPlan {
@@ -251,6 +258,8 @@ struct BatchPlan {
     uint32_t vis_mode = 0;
     const uint32_t* d_slots = nullptr;
     QualLaunch qual;  // (pops > 0: the window keeps the rows that pass a qualifier; the d_out_* of the launch are the batch's)
+    const uint32_t* groups = nullptr;  // with qual.pops > 0 and per_group > 0: the window of a grouped batch (GroupLaunch)
+    uint32_t per_group = 0;
 };
 
 // ---- what a launch knows about heap visibility (vs_heap_vis.h) ----------------------------------------------------
@@ -312,6 +321,8 @@ struct PendingQual {
     uint32_t *d_out_ids = nullptr, *d_out_rows = nullptr, *d_out_pops = nullptr, *d_out_state = nullptr;
     uint64_t* d_out_tids = nullptr;
     float* d_out_dist = nullptr;
+    const uint32_t* d_groups = nullptr;  // vs_search_batch_grouped: the keep rule carries the group column and per_group (else null / 0)
+    uint32_t per_group = 0;
 };
 
 struct SearchWorkspace {
@@ -394,6 +405,8 @@ struct vs_index {
     uint8_t* visible_own = nullptr;    // the library's own copy (vs_index_set_visibility)
     uint8_t* snap[VS_MAX_SNAPSHOTS] = {nullptr};  // per-snapshot masks of shared launches (vs_index_snapshot_put); slot 0 unused
     QualSet* qs = nullptr;     // the qualifiers of an owner (vs_index_qual_*); a view holds none
+    uint32_t* groups = nullptr;  // the group column of an owner (vs_index_groups_*): one u32 per node at `capacity`, VS_GROUP_NONE past d.n
+    size_t groups_rows = 0;      // rows the column has room for
     VisBase* vb = nullptr;     // the visibility base and its overlays (vs_index_vis_base_eval); a view's is its source's (vs_index_vis_share)
     float* vecs = nullptr;
     float* vnorm = nullptr;  // per node: 0 => leave vector alone, else divisor sqrt(norm) (preprocess_cosine)
@@ -482,11 +495,13 @@ void stage_copy(void* dst, const void* src, size_t n);                         /
 int vs_search_batch_dev_impl(vs_index* ix, const float* d_queries, const int16_t* d_qlabels, const uint32_t* d_qlabel_off, uint32_t nq,
                              uint32_t L, uint32_t rescore, uint32_t k, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist,
                              const uint32_t* d_scan_slots = nullptr,   // vs_batch.hip; d_scan_slots: vs_search_batch_dev_vis
-                             const QualLaunch* qual = nullptr);        // qual: a round of vs_search_batch_qual (k kept rows of up to qual->pops)
+                             const QualLaunch* qual = nullptr,         // qual: a round of vs_search_batch_qual (k kept rows of up to qual->pops)
+                             const uint32_t* d_groups = nullptr, uint32_t per_group = 0);  // ... of vs_search_batch_grouped
 int vs_search_batch_dev_finish_impl(vs_index* ix, vs_stats* stats);  // vs_batch.hip
 void vs_vis_base_drop(vs_index* ix);  // vs_heap_vis.h: frees the base and every overlay of an owner (synchronises its stream first)
 void vs_vis_base_free(vs_index* ix);  // ... and the record itself (vs_index_free)
 void vs_qual_drop_all(vs_index* ix);  // vs_qual.h: frees every qualifier of an owner and the record (synchronises its stream first)
+void vs_groups_drop(vs_index* ix);    // vs_qual.h: frees the group column of an owner (synchronises its stream first)
 
 // ---- kernel launch wrappers (defined in the .hip files) -------------------------------------------------------
 struct SearchLaunch {
@@ -696,6 +711,14 @@ int launch_rerank_window_qual(vs_index* idx, const float* d_q_full, const uint32
                               uint32_t mode, const uint32_t* d_perm, bool deal, const QualLaunch& ql);
 int launch_resort_qual(vs_index* idx, uint32_t nq, uint32_t M, uint32_t rescore, uint32_t k, const uint32_t* d_stream_ids, const uint32_t* d_cnt,
                        const float* d_dist, uint64_t* d_heap_ws, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, const QualLaunch& ql);
+// the two window launches under a group rule (vs_group.h), and the fill of rows [first, first + count) of a group column with VS_GROUP_NONE
+bool rerank_window_grouped_fits(const vs_index* idx, uint32_t M, uint32_t rescore, uint32_t k);
+int launch_rerank_window_grouped(vs_index* idx, const float* d_q_full, const uint32_t* d_stream_ids, const uint32_t* d_cnt, uint32_t M,
+                                 uint32_t rescore, uint32_t k, uint32_t nq, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist,
+                                 uint32_t mode, const uint32_t* d_perm, bool deal, const GroupLaunch& gl);
+int launch_resort_grouped(vs_index* idx, uint32_t nq, uint32_t M, uint32_t rescore, uint32_t k, const uint32_t* d_stream_ids, const uint32_t* d_cnt,
+                          const float* d_dist, uint64_t* d_heap_ws, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, const GroupLaunch& gl);
+int launch_group_fill(vs_index* idx, uint32_t* d_groups, size_t first, size_t count);
 // VS_RERANK_ORDER: the order in which a batch's rerank workgroups take the scans.  d_perm (null = the scans' own order): place ->
 // scan number; deal: workgroup b takes place (b % 8) * ceil(nq / 8) + b / 8, a contiguous eighth of the order per XCD
 bool scan_order_fits(const vs_index* idx);  // the index has codes k_scan_regions can tile (code rows of up to 38 words)

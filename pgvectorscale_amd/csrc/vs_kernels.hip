@@ -674,7 +674,8 @@ __device__ __forceinline__ uint32_t qual_state(uint32_t kept, uint32_t k, uint32
 }
 
 // window_replay with the keep / stop rule: emit(sp) takes every row popped and returns true when the scan has what it wants.
-// Returns the number of rows popped (<= P).
+// Returns the number of rows popped (<= P).  window_pop (vs_group.h) is this body as one resumable pop: a change to the heap code
+// here is a change there (tests/test_gpu_zz_grouped.py runs both on the tie-heavy corpus).
 template <class Emit>
 __device__ __forceinline__ uint32_t window_replay_until(uint64_t* h, const float* sd, uint32_t n, uint32_t rescore, uint32_t P, Emit emit) {
     uint32_t popped = 0, len = 0, pos = 0;
@@ -1615,6 +1616,9 @@ int launch_rerank_window_qual(vs_index* idx, const float* d_q_full, const uint32
     VS_HIP(hipGetLastError());
     return VS_OK;
 }
+
+// the same two windows under a group rule (vs_search_batch_grouped), and the fill of a group column's tail: kernels and launches
+#include "vs_group.h"
 
 // The rerank order of a batch (k_scan_regions + the counting sort): d_perm[nq] = the scan numbers by (nearest of S seed rows, scan
 // number).  d_work: scan_order_work_bytes(nq, S) bytes.  S <= min(n, 4096) (a key and a Hamming distance share a 32-bit word).

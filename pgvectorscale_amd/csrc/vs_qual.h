@@ -337,8 +337,9 @@ static uint32_t qual_first_pops(uint32_t k, uint32_t max_pops, double density) {
 uint32_t vs_qual_first_pops(uint32_t k, uint32_t max_pops, double density) { return qual_first_pops(k, max_pops, density); }
 
 // (what needs no index comes first: a bad slot array or pop limit is named whatever the handle is)
-static int qual_check_gucs(const vs_index* ix, const char* what, const uint32_t* slots, uint32_t L, uint32_t rescore, uint32_t k, uint32_t max_pops) {
-    VS_REQUIRE(slots, "%s: qual_slots is NULL (the unqualified calls exist for that)", what);
+static int qual_check_gucs(const vs_index* ix, const char* what, const uint32_t* slots, uint32_t L, uint32_t rescore, uint32_t k, uint32_t max_pops,
+                           bool grouped = false) {
+    VS_REQUIRE(slots || grouped, "%s: qual_slots is NULL (the unqualified calls exist for that)", what);
     VS_REQUIRE(L >= 1 && L <= 10000, "%s: diskann.query_search_list_size %u outside [1,10000]", what, L);
     VS_REQUIRE(rescore <= 1000, "%s: diskann.query_rescore %u outside [0,1000]", what, rescore);
     VS_REQUIRE(k >= 1, "%s: k must be >= 1", what);
@@ -376,7 +377,7 @@ struct QualRoundLaunch {
 };
 static QualRoundLaunch qual_round_launch(const vs_index* ix, const PendingQual& pq, uint32_t P, uint32_t s0, const uint32_t* d_map) {
     QualRoundLaunch r{};
-    r.direct = pq.all_zero && P == pq.k && !d_map;
+    r.direct = pq.all_zero && P == pq.k && !d_map && !pq.d_groups;  // (a group rule always goes through its window)
     r.ids = pq.d_out_ids;
     r.tids = pq.d_out_tids;
     r.dist = pq.d_out_dist;
@@ -421,7 +422,7 @@ static int qual_run_rounds(vs_index* ix, const PendingQual& pq, vs_stats* st, vs
             const QualRoundLaunch r = qual_round_launch(ix, pq, P, s0, d_map);
             if (!in_flight)  // (else: round 1, launched by vs_search_batch_dev_qual with the same plan)
                 VS_TRY(vs_search_batch_dev_impl(ix, d_q + (size_t)s0 * dim, d_lab, d_off ? d_off + s0 : nullptr, cnt, pq.L, pq.rescore, k, r.ids, r.tids,
-                                                r.dist, nullptr, r.direct ? nullptr : &r.ql));
+                                                r.dist, nullptr, r.direct ? nullptr : &r.ql, pq.d_groups, pq.per_group));
             in_flight = false;
             vs_stats one{};
             VS_TRY(vs_search_batch_dev_finish_impl(ix, &one));
@@ -487,11 +488,39 @@ static int qual_run_rounds(vs_index* ix, const PendingQual& pq, vs_stats* st, vs
     return VS_OK;
 }
 
+// The keep rule a batch is handed on top of its qualifiers: none (a qualified batch), or the group rule of vs_search_batch_grouped
+// (the index's group column and per_group; group_check holds the refusals only the grouped calls have).
+struct GroupRule {
+    bool grouped = false;
+    uint32_t per_group = 0;
+};
+static int groups_fit(vs_index* ix, const char* what);
+static int group_check(vs_index* ix, const char* what, uint32_t k, uint32_t per_group) {
+    VS_REQUIRE(per_group >= 1 && per_group <= k, "%s: per_group %u outside [1, k = %u]", what, per_group, k);
+    VS_REQUIRE(k <= VS_GROUP_MAX_K, "%s: k %u above VS_GROUP_MAX_K = %d", what, k, VS_GROUP_MAX_K);
+    if (!ix->groups) {
+        vs_set_error("%s: the index has no group column (vs_index_groups_put)", what);
+        return VS_ERR_STATE;
+    }
+    if (ix->ws.pending) {
+        vs_set_error("%s: a batch of this handle is in flight (vs_search_batch_dev_finish first)", what);
+        return VS_ERR_STATE;
+    }
+    return groups_fit(ix, what);
+}
+// P1 of a grouped batch: the qualifier rule's value unchanged (the duplication rate of a stream is not known), VS_GROUP_FIRST_POPS over it
+static uint32_t group_first_pops(uint32_t k, uint32_t max_pops, double density) {
+    if (const uint32_t v = env_u32("VS_GROUP_FIRST_POPS", 0)) return std::min(std::max(v, k), max_pops);
+    return qual_first_pops(k, max_pops, density);
+}
+
 static int search_batch_dev_qual_impl(vs_index* ix, const float* d_queries, const int16_t* d_qlabels, const uint32_t* d_qlabel_off, uint32_t nq,
                                       uint32_t L, uint32_t rescore, uint32_t k, const uint32_t* d_slots, uint32_t max_pops, uint32_t* d_out_ids,
-                                      uint64_t* d_out_tids, float* d_out_dist, uint32_t* d_out_rows, uint32_t* d_out_pops, uint32_t* d_out_state) {
-    const char* what = "vs_search_batch_dev_qual";
-    VS_TRY(qual_check_gucs(ix, what, d_slots, L, rescore, k, max_pops));
+                                      uint64_t* d_out_tids, float* d_out_dist, uint32_t* d_out_rows, uint32_t* d_out_pops, uint32_t* d_out_state,
+                                      const GroupRule& gr = GroupRule{}) {
+    const char* what = gr.grouped ? "vs_search_batch_dev_grouped" : "vs_search_batch_dev_qual";
+    VS_TRY(qual_check_gucs(ix, what, d_slots, L, rescore, k, max_pops, gr.grouped));
+    if (gr.grouped) VS_TRY(group_check(ix, what, k, gr.per_group));
     VS_REQUIRE(nq == 0 || (d_queries && d_out_ids && d_out_rows && d_out_pops && d_out_state), "%s: null argument", what);
     if (ix->d.storage_type == VS_STORAGE_PLAIN) VS_REQUIRE(!d_qlabel_off, "Plain storage does not support label filters");
     SearchWorkspace& w = ix->ws;
@@ -499,11 +528,15 @@ static int search_batch_dev_qual_impl(vs_index* ix, const float* d_queries, cons
     w.qual_pending = false;
     if (nq == 0) return VS_OK;
     VS_HIP(hipSetDevice(ix->ctx->device));
-    std::vector<uint32_t> slots(nq);  // the slots come back once: an empty slot is refused before anything is launched
-    VS_TRY(vs_dev_download(ix->ctx, slots.data(), d_slots, (size_t)nq * 4));
+    std::vector<uint32_t> slots(nq, 0u);  // the slots come back once: an empty slot is refused before anything is launched
+    if (d_slots) VS_TRY(vs_dev_download(ix->ctx, slots.data(), d_slots, (size_t)nq * 4));
     PendingQual pq;
     double density = 1.0;
     VS_TRY(qual_check_slots(ix, what, slots.data(), nq, &pq.all_zero, &density));
+    if (gr.grouped) {
+        pq.d_groups = ix->groups;
+        pq.per_group = gr.per_group;
+    }
     pq.d_queries = d_queries;
     pq.d_qlabels = d_qlabels;
     pq.d_qlabel_off = d_qlabel_off;
@@ -513,7 +546,7 @@ static int search_batch_dev_qual_impl(vs_index* ix, const float* d_queries, cons
     pq.rescore = rescore;
     pq.k = k;
     pq.max_pops = max_pops;
-    pq.first_pops = qual_first_pops(k, max_pops, density);
+    pq.first_pops = gr.grouped ? group_first_pops(k, max_pops, density) : qual_first_pops(k, max_pops, density);
     pq.d_out_ids = d_out_ids;
     pq.d_out_tids = d_out_tids;
     pq.d_out_dist = d_out_dist;
@@ -524,7 +557,8 @@ static int search_batch_dev_qual_impl(vs_index* ix, const float* d_queries, cons
     const uint32_t P = pq.first_pops;
     if (qual_launch_scans(ix, L, rescore, P, nq) == nq) {
         const QualRoundLaunch r = qual_round_launch(ix, pq, P, 0, nullptr);
-        VS_TRY(vs_search_batch_dev_impl(ix, d_queries, d_qlabels, d_qlabel_off, nq, L, rescore, k, r.ids, r.tids, r.dist, nullptr, r.direct ? nullptr : &r.ql));
+        VS_TRY(vs_search_batch_dev_impl(ix, d_queries, d_qlabels, d_qlabel_off, nq, L, rescore, k, r.ids, r.tids, r.dist, nullptr, r.direct ? nullptr : &r.ql,
+                                        pq.d_groups, pq.per_group));
         pq.launched = true;
     }
     w.pending = true;
@@ -560,9 +594,10 @@ static int search_batch_dev_qual_finish_impl(vs_index* ix, vs_stats* stats, vs_q
 static int search_batch_qual_impl(vs_index* ix, const float* queries, const int16_t* qlabels, const uint32_t* qlabel_off, uint32_t nq, uint32_t L,
                                   uint32_t rescore, uint32_t k, const uint32_t* qual_slots, uint32_t max_pops, uint32_t* out_ids, uint64_t* out_tids,
                                   float* out_dist, uint32_t* out_rows, uint32_t* out_pops, uint32_t* out_state, vs_stats* stats,
-                                  vs_qual_batch_stats* qstats) {
-    const char* what = "vs_search_batch_qual";
-    VS_TRY(qual_check_gucs(ix, what, qual_slots, L, rescore, k, max_pops));
+                                  vs_qual_batch_stats* qstats, const GroupRule& gr = GroupRule{}) {
+    const char* what = gr.grouped ? "vs_search_batch_grouped" : "vs_search_batch_qual";
+    VS_TRY(qual_check_gucs(ix, what, qual_slots, L, rescore, k, max_pops, gr.grouped));
+    if (gr.grouped) VS_TRY(group_check(ix, what, k, gr.per_group));
     VS_REQUIRE(nq == 0 || (queries && out_ids && out_rows && out_pops && out_state), "%s: null argument", what);
     if (ix->d.storage_type == VS_STORAGE_PLAIN) VS_REQUIRE(!qlabel_off, "Plain storage does not support label filters");
     if (ix->ws.pending) {
@@ -571,12 +606,12 @@ static int search_batch_qual_impl(vs_index* ix, const float* queries, const int1
     }
     bool all_zero = true;
     double density = 1.0;
-    VS_TRY(qual_check_slots(ix, what, qual_slots, nq, &all_zero, &density));
+    if (qual_slots) VS_TRY(qual_check_slots(ix, what, qual_slots, nq, &all_zero, &density));
     if (stats) memset(stats, 0, sizeof(*stats));
     if (qstats) memset(qstats, 0, sizeof(*qstats));
     vs_stats st{};
     vs_qual_batch_stats qs{};
-    qs.first_pops = qual_first_pops(k, max_pops, density);
+    qs.first_pops = gr.grouped ? group_first_pops(k, max_pops, density) : qual_first_pops(k, max_pops, density);
     if (qstats) *qstats = qs;
     if (nq == 0) return VS_OK;
     vs_ctx* c = ix->ctx;
@@ -585,8 +620,10 @@ static int search_batch_qual_impl(vs_index* ix, const float* queries, const int1
     const int16_t* d_lab = nullptr;
     const uint32_t* d_off = nullptr;
     VS_TRY(upload_label_keys(ix, qlabels, qlabel_off, nq, &d_lab, &d_off));
-    VS_TRY(devbuf_reserve(c, w.qual_slots, (size_t)nq * 4));
-    VS_TRY(vs_dev_upload(c, w.qual_slots.p, qual_slots, (size_t)nq * 4));
+    if (qual_slots) {  // (NULL in a grouped batch: every slot is 0)
+        VS_TRY(devbuf_reserve(c, w.qual_slots, (size_t)nq * 4));
+        VS_TRY(vs_dev_upload(c, w.qual_slots.p, qual_slots, (size_t)nq * 4));
+    }
     // the chunks of a host batch, by the rule of vs_search_batch (VS_HOST_CHUNKS / VS_HOST_CHUNK_MIN); each runs its own rounds
     uint32_t chunk = nq;
     {
@@ -607,7 +644,11 @@ static int search_batch_qual_impl(vs_index* ix, const float* queries, const int1
         pq.d_queries = (const float*)w.raw_q.p;
         pq.d_qlabels = d_lab;
         pq.d_qlabel_off = d_off ? d_off + q0 : nullptr;
-        pq.d_slots = (const uint32_t*)w.qual_slots.p + q0;
+        pq.d_slots = qual_slots ? (const uint32_t*)w.qual_slots.p + q0 : nullptr;
+        if (gr.grouped) {
+            pq.d_groups = ix->groups;
+            pq.per_group = gr.per_group;
+        }
         pq.nq = cq;
         pq.L = L;
         pq.rescore = rescore;
@@ -654,4 +695,129 @@ extern "C" int vs_search_batch_dev_qual(vs_index* ix, const float* d_queries, co
 }
 extern "C" int vs_search_batch_dev_qual_finish(vs_index* ix, vs_stats* stats, vs_qual_batch_stats* qstats) {
     return vs_guard("vs_search_batch_dev_qual_finish", [&] { return search_batch_dev_qual_finish_impl(ix, stats, qstats); });
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// grouped scans: the group column of an index and the batch under a group rule (kernels: vs_group.h, in vs_kernels.hip)
+// ---------------------------------------------------------------------------------------------------------------
+void vs_groups_drop(vs_index* ix) {
+    if (!ix || !ix->groups) return;
+    (void)hipSetDevice(ix->ctx->device);
+    (void)hipStreamSynchronize(ix->ctx->stream);  // (no launch may still read it)
+    (void)hipFree(ix->groups);
+    ix->groups = nullptr;
+    ix->groups_rows = 0;
+}
+
+// room for every row of the index (an index whose arrays grew without vs_index_reserve: the column follows, the new rows ungrouped)
+static int groups_fit(vs_index* ix, const char* what) {
+    const size_t need = std::max<size_t>(std::max<size_t>(ix->d.n, ix->capacity), 1);
+    if (!ix->groups || need <= ix->groups_rows) return VS_OK;
+    vs_ctx* c = ix->ctx;
+    VS_HIP(hipSetDevice(c->device));
+    VS_HIP(hipStreamSynchronize(c->stream));
+    DevScope sc(c->stream);
+    uint32_t* fresh = nullptr;
+    VS_TRY(sc.alloc(&fresh, need * 4, what));
+    VS_HIP(hipMemcpyAsync(fresh, ix->groups, ix->groups_rows * 4, hipMemcpyDeviceToDevice, c->stream));
+    VS_TRY(launch_group_fill(ix, fresh, ix->groups_rows, need - ix->groups_rows));
+    VS_HIP(hipStreamSynchronize(c->stream));
+    (void)hipFree(ix->groups);
+    ix->groups = sc.release(fresh);
+    ix->groups_rows = need;
+    return VS_OK;
+}
+
+// the checks every vs_index_groups_* call shares; need_column: the call reads or patches an existing column
+static int groups_check(vs_index* ix, const char* what, bool need_column) {
+    VS_REQUIRE(ix, "%s: index is NULL", what);
+    VS_REQUIRE_OWNER(ix, what);
+    if (ix->ws.pending) {
+        vs_set_error("%s: a batch of this handle is in flight (vs_search_batch_dev_finish first)", what);
+        return VS_ERR_STATE;
+    }
+    if (need_column && !ix->groups) {
+        vs_set_error("%s: the index has no group column (vs_index_groups_put)", what);
+        return VS_ERR_STATE;
+    }
+    return groups_fit(ix, what);
+}
+
+// n values become rows [0, n) of a column allocated at the index's capacity; the rows past n read VS_GROUP_NONE (k_group_fill)
+static int groups_put_impl(vs_index* ix, const uint32_t* values, bool on_device, const char* what) {
+    VS_TRY(groups_check(ix, what, false));
+    VS_REQUIRE(values || ix->d.n == 0, "%s: values is NULL", what);
+    vs_ctx* c = ix->ctx;
+    VS_HIP(hipSetDevice(c->device));
+    const size_t n = ix->d.n, rows = std::max<size_t>(std::max<size_t>(n, ix->capacity), 1);
+    DevScope sc(c->stream);
+    uint32_t* fresh = nullptr;
+    VS_TRY(sc.alloc(&fresh, rows * 4, what));
+    if (n) {
+        if (on_device) VS_HIP(hipMemcpyAsync(fresh, values, n * 4, hipMemcpyDeviceToDevice, c->stream));
+        else VS_TRY(vs_dev_upload(c, fresh, values, n * 4));
+    }
+    VS_TRY(launch_group_fill(ix, fresh, n, rows - n));
+    VS_HIP(hipStreamSynchronize(c->stream));
+    vs_groups_drop(ix);
+    ix->groups = sc.release(fresh);
+    ix->groups_rows = rows;
+    return VS_OK;
+}
+
+extern "C" int vs_index_groups_put(vs_index* ix, const uint32_t* values) {
+    return vs_guard("vs_index_groups_put", [&] { return groups_put_impl(ix, values, false, "vs_index_groups_put"); });
+}
+extern "C" int vs_index_groups_put_dev(vs_index* ix, const uint32_t* d_values) {
+    return vs_guard("vs_index_groups_put_dev", [&] { return groups_put_impl(ix, d_values, true, "vs_index_groups_put_dev"); });
+}
+extern "C" int vs_index_groups_patch(vs_index* ix, uint32_t first_node, uint32_t count, const uint32_t* values) {
+    return vs_guard("vs_index_groups_patch", [&]() -> int {
+        const char* what = "vs_index_groups_patch";
+        VS_TRY(groups_check(ix, what, true));
+        VS_REQUIRE((uint64_t)first_node + count <= ix->d.n, "%s: rows [%u, %u + %u) reach past the index's %u nodes", what, first_node, first_node, count, ix->d.n);
+        VS_REQUIRE(values || count == 0, "%s: values is NULL", what);
+        if (count == 0) return VS_OK;
+        VS_HIP(hipSetDevice(ix->ctx->device));
+        VS_HIP(hipStreamSynchronize(ix->ctx->stream));
+        return vs_dev_upload(ix->ctx, ix->groups + first_node, values, (size_t)count * 4);
+    });
+}
+extern "C" int vs_index_groups_get(vs_index* ix, uint32_t* values) {
+    return vs_guard("vs_index_groups_get", [&]() -> int {
+        VS_TRY(groups_check(ix, "vs_index_groups_get", true));
+        VS_REQUIRE(values || ix->d.n == 0, "vs_index_groups_get: values is NULL");
+        if (ix->d.n == 0) return VS_OK;
+        VS_HIP(hipSetDevice(ix->ctx->device));
+        return vs_dev_download(ix->ctx, values, ix->groups, (size_t)ix->d.n * 4);
+    });
+}
+extern "C" int vs_index_groups_drop(vs_index* ix) {
+    return vs_guard("vs_index_groups_drop", [&]() -> int {
+        VS_TRY(groups_check(ix, "vs_index_groups_drop", true));
+        vs_groups_drop(ix);
+        return VS_OK;
+    });
+}
+
+extern "C" int vs_search_batch_grouped(vs_index* ix, const float* queries, const int16_t* qlabels, const uint32_t* qlabel_off, uint32_t nq, uint32_t L,
+                                       uint32_t rescore, uint32_t k, uint32_t per_group, const uint32_t* qual_slots, uint32_t max_pops, uint32_t* out_ids,
+                                       uint64_t* out_tids, float* out_dist, uint32_t* out_rows, uint32_t* out_pops, uint32_t* out_state, vs_stats* stats,
+                                       vs_qual_batch_stats* qstats) {
+    return vs_guard("vs_search_batch_grouped", [&] {
+        return search_batch_qual_impl(ix, queries, qlabels, qlabel_off, nq, L, rescore, k, qual_slots, max_pops, out_ids, out_tids, out_dist, out_rows,
+                                      out_pops, out_state, stats, qstats, GroupRule{true, per_group});
+    });
+}
+extern "C" int vs_search_batch_dev_grouped(vs_index* ix, const float* d_queries, const int16_t* d_qlabels, const uint32_t* d_qlabel_off, uint32_t nq,
+                                           uint32_t L, uint32_t rescore, uint32_t k, uint32_t per_group, const uint32_t* d_qual_slots, uint32_t max_pops,
+                                           uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, uint32_t* d_out_rows, uint32_t* d_out_pops,
+                                           uint32_t* d_out_state) {
+    return vs_guard("vs_search_batch_dev_grouped", [&] {
+        return search_batch_dev_qual_impl(ix, d_queries, d_qlabels, d_qlabel_off, nq, L, rescore, k, d_qual_slots, max_pops, d_out_ids, d_out_tids,
+                                          d_out_dist, d_out_rows, d_out_pops, d_out_state, GroupRule{true, per_group});
+    });
+}
+extern "C" int vs_search_batch_dev_grouped_finish(vs_index* ix, vs_stats* stats, vs_qual_batch_stats* qstats) {
+    return vs_guard("vs_search_batch_dev_grouped_finish", [&] { return search_batch_dev_qual_finish_impl(ix, stats, qstats); });
 }

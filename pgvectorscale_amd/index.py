@@ -824,6 +824,69 @@ class DiskAnnIndex:
         check(self._L.vs_search_batch_dev_qual_finish(self.h, C.byref(st), C.byref(qst)))
         return st.as_dict(), qst.as_dict()
 
+    # -- grouped scans: the first k rows with at most per_group rows per group (include/vsgpu.h, "grouped scans") ------
+    def groups_put(self, values):
+        """fills the group column: one uint32 per node (_lib.GROUP_NONE: ungrouped, never limited)"""
+        self._refresh()
+        a = np.ascontiguousarray(values, np.uint32).ravel()
+        if a.size != self.desc.n:
+            raise ValueError(f"a group column has one entry per node ({self.desc.n}), got {a.size}")
+        check(self._L.vs_index_groups_put(self.h, _p(a) if a.size else None))
+
+    def groups_put_dev(self, d_values):
+        """the same from n uint32 values in device memory"""
+        check(self._L.vs_index_groups_put_dev(self.h, d_values))
+
+    def groups_patch(self, first_node, values):
+        """overwrites the groups of nodes [first_node, first_node + len(values)): how appended rows get theirs"""
+        a = np.ascontiguousarray(values, np.uint32).ravel()
+        check(self._L.vs_index_groups_patch(self.h, first_node, a.size, _p(a) if a.size else None))
+
+    def groups_get(self):
+        self._refresh()
+        a = np.zeros(max(self.desc.n, 1), np.uint32)
+        check(self._L.vs_index_groups_get(self.h, _p(a)))
+        return a[:self.desc.n]
+
+    def groups_drop(self):
+        check(self._L.vs_index_groups_drop(self.h))
+
+    def search_batch_grouped(self, queries, k=10, per_group=1, qual_slots=None, max_pops=None,
+                             search_list_size=DEFAULT_QUERY_SEARCH_LIST_SIZE, rescore=DEFAULT_QUERY_RESCORE, qlabels=None):
+        """For each query: the first k rows of its amgettuple sequence that pass the qualifier in qual_slots[q] (None / 0: every node)
+        and whose group holds fewer than per_group of the rows kept before (GROUP_NONE: never limited), looking at no more than
+        max_pops rows (default: k) -> what search_batch_qual returns."""
+        q = np.ascontiguousarray(queries, np.float32).reshape(-1, self.desc.dim_full)
+        nq = q.shape[0]
+        max_pops = k if max_pops is None else max_pops
+        lv, lo = self._label_keys(qlabels, nq)
+        sl = None
+        if qual_slots is not None:
+            sl = np.ascontiguousarray(qual_slots, np.uint32).ravel()
+            if sl.shape != (nq,):
+                raise ValueError(f"qual_slots must have shape ({nq},), got {sl.shape}")
+            sl = sl if nq else np.zeros(1, np.uint32)
+        ids = np.empty((nq, k), np.uint32)
+        tids = np.empty((nq, k), np.uint64)
+        dist = np.empty((nq, k), np.float32)
+        rows, pops, state = (np.empty(max(nq, 1), np.uint32) for _ in range(3))
+        st, qst = Stats(), _lib.QualBatchStats()
+        check(self._L.vs_search_batch_grouped(self.h, _p(q), _p(lv), _p(lo), nq, search_list_size, rescore, k, per_group,
+                                              None if sl is None else _p(sl), max_pops, _p(ids), _p(tids), _p(dist), _p(rows), _p(pops),
+                                              _p(state), C.byref(st), C.byref(qst)))
+        return ids, tids, dist, rows[:nq], pops[:nq], state[:nq], st.as_dict(), qst.as_dict()
+
+    def search_batch_dev_grouped(self, d_queries, nq, search_list_size, rescore, k, per_group, d_qual_slots, max_pops, d_out_ids, d_out_rows,
+                                 d_out_pops, d_out_state, d_out_tids=None, d_out_dist=None, d_qlabels=None, d_qlabel_off=None):
+        """the device-resident form: every pointer is device memory and stays valid until search_batch_dev_grouped_finish()"""
+        check(self._L.vs_search_batch_dev_grouped(self.h, d_queries, d_qlabels, d_qlabel_off, nq, search_list_size, rescore, k, per_group,
+                                                  d_qual_slots, max_pops, d_out_ids, d_out_tids, d_out_dist, d_out_rows, d_out_pops, d_out_state))
+
+    def search_batch_dev_grouped_finish(self):
+        st, qst = Stats(), _lib.QualBatchStats()
+        check(self._L.vs_search_batch_dev_grouped_finish(self.h, C.byref(st), C.byref(qst)))
+        return st.as_dict(), qst.as_dict()
+
     def search_batch_qual_exact(self, queries, qual_slots, k=10):
         """For each query: the exact k nearest rows among those that pass the qualifier in qual_slots[q] (0: every node), are not
         deleted and are not hidden by the mask in force, ascending by (distance, node id); no graph is walked -> ids, tids, dist
