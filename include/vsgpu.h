@@ -1773,8 +1773,8 @@ int vs_search_batch_qual_flat_dev(vs_index* idx, const float* d_queries, uint32_
  * k_rerank_window_grouped, or k_resort_grouped (a wave per scan) for the windows it does not take, VS_RERANK_FUSED=0 and rescore 0.
  * vs_search_batch_dev_grouped_finish finishes a vs_search_batch_dev_grouped (vs_search_batch_dev_qual_finish does too: the batch in
  * flight is the same record).
- * Not built: grouped scan pools, cursors, the broker, the shm server and vs_multi; the exact and the flat qualified calls under a
- * group rule; per-scan visibility slots together with groups. */
+ * Not built: grouped scan pools, cursors, the broker, the shm server and vs_multi; per-scan visibility slots together with groups.
+ * (The exact and the flat qualified calls under a group rule: the next section.) */
 #define VS_GROUP_NONE 0xFFFFFFFFu
 #define VS_GROUP_MAX_K 8192 /* k of a grouped batch: the groups of a scan's kept rows stay on chip (a larger k is VS_ERR_INVALID) */
 int vs_index_groups_put(vs_index* idx, const uint32_t* values /* n host */);
@@ -1791,6 +1791,46 @@ int vs_search_batch_dev_grouped(vs_index* idx, const float* d_queries, const int
                                 uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, uint32_t* d_out_rows, uint32_t* d_out_pops,
                                 uint32_t* d_out_state);
 int vs_search_batch_dev_grouped_finish(vs_index* idx, vs_stats* stats, vs_qual_batch_stats* qstats);
+
+/* ---- exact and flat qualified top-k under a group rule (vs_qual_group.h) ----
+ * The grouped scan above is a post-filter: its cost grows as 1 / density of the qualifier.  A selective predicate together with a
+ * per-document cap (WHERE tenant_id = X ... row_number() OVER (PARTITION BY doc_id) <= g) is served by the exact and the flat
+ * qualified calls with the group rule applied INSIDE their selection, so k rows come back however many chunks a document has.
+ *
+ * SEMANTICS.  Every scan q is handled on its own.  C is the set vs_search_batch_qual_exact defines: the nodes i < n with bit i of
+ * qualifier qual_slots[q] set (slot 0: every node), whose heap tid offset is not 0, and which the mask in force does not hide.  G is
+ * the index's group column.  Order C ascending by (f32::total_cmp key of the full-precision distance, node id), the distance with the
+ * bits vs_search_batch_qual_exact gives the row.  A row r of C is CAPPED OUT iff G[r] != VS_GROUP_NONE and at least per_group rows of
+ * C with the same group value come before it in that order.
+ * vs_search_batch_qual_exact_grouped / _dev return the first min(k, rows of C not capped out) rows that are not capped out, in that
+ * order; ids, tids and distance bits are the exact call's, the tail is VS_INVALID_NODE / 0 / NaN, out_rows[q] is the count.
+ * vs_search_batch_qual_flat_grouped / _dev take S, the flat call's candidate set — the min(rescore, |C|) rows of C smallest by
+ * (Hamming distance of the SBQ codes, node id); NO group rule applies to this selection — and apply the same rule to S ordered by
+ * exact distance.  FEWER THAN k ROWS may therefore come back although C holds k groups: when the candidates fall into few groups (a
+ * document of many near chunks can fill S).  out_rows[q] says so; raise rescore, or use the exact grouped call.
+ * IDENTITIES, bit for bit: per_group >= k gives the rows of the ungrouped call; so does a column that is all VS_GROUP_NONE; the flat
+ * grouped call with rescore >= |C| gives the exact grouped call's rows.
+ * The prototypes are the ungrouped ones with per_group after k; the stats and the options (VS_QUAL_EXACT_*, VS_QUAL_FLAT_*) are the
+ * ungrouped calls' and mean the same, except that the exact grouped call's default tile is 4 scans (a cost choice).  REFUSALS, each before anything is launched or written: every refusal of the ungrouped call,
+ * unchanged; per_group outside [1, k] (VS_ERR_INVALID); no group column (VS_ERR_STATE).
+ * HOW.  "The first k rows under a per-group cap" is a mergeable summary as plain top-k is: a row enters a list of k
+ * only if it beats entry k - 1, and if its group already holds per_group entries it REPLACES the largest of them or is dropped.  So
+ * the exact call's register lists, their merge through LDS and the merge of the slice partials are kept; each entry carries its group
+ * in a second register, and the merges read the groups back from the column by node id.
+ * Not built: pools, the broker, the shm server and vs_multi; per-scan visibility slots; a group cap inside the Hamming selection of
+ * the flat call. */
+int vs_search_batch_qual_exact_grouped(vs_index* idx, const float* queries, uint32_t nq, uint32_t k, uint32_t per_group,
+                                       const uint32_t* qual_slots, uint32_t* out_ids, uint64_t* out_tids, float* out_dist,
+                                       uint32_t* out_rows, vs_qual_exact_stats* stats);
+int vs_search_batch_qual_exact_grouped_dev(vs_index* idx, const float* d_queries, uint32_t nq, uint32_t k, uint32_t per_group,
+                                           const uint32_t* d_qual_slots, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist,
+                                           uint32_t* d_out_rows, vs_qual_exact_stats* stats);
+int vs_search_batch_qual_flat_grouped(vs_index* idx, const float* queries, uint32_t nq, uint32_t k, uint32_t per_group, uint32_t rescore,
+                                      const uint32_t* qual_slots, uint32_t* out_ids, uint64_t* out_tids, float* out_dist,
+                                      uint32_t* out_rows, vs_qual_flat_stats* stats);
+int vs_search_batch_qual_flat_grouped_dev(vs_index* idx, const float* d_queries, uint32_t nq, uint32_t k, uint32_t per_group,
+                                          uint32_t rescore, const uint32_t* d_qual_slots, uint32_t* d_out_ids, uint64_t* d_out_tids,
+                                          float* d_out_dist, uint32_t* d_out_rows, vs_qual_flat_stats* stats);
 
 #ifdef __cplusplus
 }

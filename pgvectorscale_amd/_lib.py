@@ -400,6 +400,10 @@ SYMBOLS = {
     "vs_search_batch_qual_exact_dev": (_i, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualExactStats)]),
     "vs_search_batch_qual_flat": (_i, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualFlatStats)]),
     "vs_search_batch_qual_flat_dev": (_i, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualFlatStats)]),
+    "vs_search_batch_qual_exact_grouped": (_i, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualExactStats)]),
+    "vs_search_batch_qual_exact_grouped_dev": (_i, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualExactStats)]),
+    "vs_search_batch_qual_flat_grouped": (_i, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualFlatStats)]),
+    "vs_search_batch_qual_flat_grouped_dev": (_i, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualFlatStats)]),
     "vs_meta_layout_default": (_i, [C.POINTER(MetaLayout)]),
     "vs_meta_page_decode": (_i, [_vp, _sz, C.POINTER(MetaLayout), C.POINTER(MetaPage), _vp, _vp, _vp, _u32]),
     "vs_pages_meta": (_i, [_vp, C.POINTER(MetaLayout), C.POINTER(MetaPage), C.POINTER(IndexDesc), _vp, _vp, _u32]),

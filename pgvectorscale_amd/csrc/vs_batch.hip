@@ -1429,3 +1429,5 @@ extern "C" int vs_search_batch_dev_finish(vs_index* ix, vs_stats* stats) {
 #include "vs_qual_exact.h"
 // vs_search_batch_qual_flat: the SBQ top-M over a qualifier's rows, then the exact top-k of those (kernels and host code)
 #include "vs_qual_flat.h"
+// vs_search_batch_qual_exact_grouped / vs_search_batch_qual_flat_grouped: the two calls above under a group rule (kernels and entry points)
+#include "vs_qual_group.h"

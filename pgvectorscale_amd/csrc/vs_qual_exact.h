@@ -13,6 +13,7 @@
 #include "vs_device.h"
 
 #define VS_QX_TQ 8       // scans per tile (the default; VS_QUAL_EXACT_TQ picks another instantiation for measurement)
+#define VS_GX_TQ 4       // ... under a group rule: k_qual_exact_grouped<8> crosses 128 VGPRs and measured 1.8 x the time of <4>
 #define VS_QX_TQ_MAX 16
 enum { QX_PASS = 32, QX_LDS_BUDGET = 64 * 1024 - 256, QX_CHUNK_SCANS = 32768, QX_LIST_WORDS = 32, QX_LIST_BLOCKS = 4096 };
 
@@ -248,6 +249,20 @@ static void qx_launch(const vs_index* ix, uint32_t blocks, size_t lds, const uin
                        (const float*)ix->vnorm, ix->d.distance_type, (const float*)ix->ws.q_full.p, d_perm, d_list, d_tiles, k, d_part);
 }
 
+// The same grid and the same merge under a group rule (vs_qual_group.h, included after this file): k_qual_exact_grouped takes the
+// tiles, the lists and the partial lists of k_qual_exact, k_qual_exact_merge_grouped the tables of k_qual_exact_merge.
+struct QxScanLaunch {
+    uint32_t blocks;
+    size_t lds;
+    const uint32_t *perm, *list;
+    const QxTile* tiles;
+    uint32_t k;
+    uint64_t* part;
+};
+static void gx_launch_scan(const vs_index* ix, uint32_t tq, const QxScanLaunch& a, const GroupRule& gr);
+static void gx_launch_merge(const vs_index* ix, uint32_t cq, const uint64_t* d_part, const uint32_t* d_perm, uint32_t tq, uint32_t k, const GroupRule& gr,
+                            uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, uint32_t* d_out_rows);
+
 // the rows of every distinct slot named (ascending slot numbers): list_off[i] .. + list_m[i] of ws.qx_list
 struct QxLists {
     std::vector<uint32_t> slot, off, m;
@@ -305,8 +320,9 @@ static void qx_slot_order(const QxLists& ls, const uint32_t* slots, uint32_t cq,
 }
 
 // One chunk: cq scans whose raw queries, and whose outputs, are on the device; slots HOST.  Leaves its launches on the stream.
+// gr.grouped: the same tiles and tables, the two kernels of vs_qual_group.h in place of k_qual_exact / k_qual_exact_merge.
 static int qx_run_chunk(vs_index* ix, const QxLists& ls, const float* d_queries, const uint32_t* slots, uint32_t cq, uint32_t k, uint32_t tq,
-                        uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, uint32_t* d_out_rows, vs_qual_exact_stats* st) {
+                        uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, uint32_t* d_out_rows, vs_qual_exact_stats* st, const GroupRule& gr) {
     vs_ctx* c = ix->ctx;
     SearchWorkspace& w = ix->ws;
     VS_TRY(devbuf_reserve(c, w.q_full, (size_t)cq * ix->vec_stride * 4));
@@ -350,18 +366,24 @@ static int qx_run_chunk(vs_index* ix, const QxLists& ls, const float* d_queries,
     const size_t lds = (size_t)tq * std::max<size_t>((size_t)ix->vec_stride * 4, (size_t)4 * k * 8);
     const uint32_t blocks = (uint32_t)tiles.size();
     hipEvent_t ev = prof_begin(c);
-    switch (tq) {
-        case 16: qx_launch<16>(ix, blocks, lds, d_perm, (const uint32_t*)w.qx_list.p, d_tiles, k, (uint64_t*)w.qx_part.p); break;
-        case 8: qx_launch<8>(ix, blocks, lds, d_perm, (const uint32_t*)w.qx_list.p, d_tiles, k, (uint64_t*)w.qx_part.p); break;
-        case 4: qx_launch<4>(ix, blocks, lds, d_perm, (const uint32_t*)w.qx_list.p, d_tiles, k, (uint64_t*)w.qx_part.p); break;
-        case 2: qx_launch<2>(ix, blocks, lds, d_perm, (const uint32_t*)w.qx_list.p, d_tiles, k, (uint64_t*)w.qx_part.p); break;
-        default: qx_launch<1>(ix, blocks, lds, d_perm, (const uint32_t*)w.qx_list.p, d_tiles, k, (uint64_t*)w.qx_part.p); break;
+    if (gr.grouped) {
+        gx_launch_scan(ix, tq, QxScanLaunch{blocks, lds, d_perm, (const uint32_t*)w.qx_list.p, d_tiles, k, (uint64_t*)w.qx_part.p}, gr);
+    } else {
+        switch (tq) {
+            case 16: qx_launch<16>(ix, blocks, lds, d_perm, (const uint32_t*)w.qx_list.p, d_tiles, k, (uint64_t*)w.qx_part.p); break;
+            case 8: qx_launch<8>(ix, blocks, lds, d_perm, (const uint32_t*)w.qx_list.p, d_tiles, k, (uint64_t*)w.qx_part.p); break;
+            case 4: qx_launch<4>(ix, blocks, lds, d_perm, (const uint32_t*)w.qx_list.p, d_tiles, k, (uint64_t*)w.qx_part.p); break;
+            case 2: qx_launch<2>(ix, blocks, lds, d_perm, (const uint32_t*)w.qx_list.p, d_tiles, k, (uint64_t*)w.qx_part.p); break;
+            default: qx_launch<1>(ix, blocks, lds, d_perm, (const uint32_t*)w.qx_list.p, d_tiles, k, (uint64_t*)w.qx_part.p); break;
+        }
     }
     prof_end(c, PK_RERANK, ev);
     VS_HIP(hipGetLastError());
     ev = prof_begin(c);
-    hipLaunchKernelGGL(k_qual_exact_merge, dim3(cq), dim3(WAVE), 0, c->stream, (const uint64_t*)w.qx_part.p, d_perm + cq, d_perm + 2 * (size_t)cq, d_perm, tq, k,
-                       (const uint64_t*)ix->tids, d_out_ids, d_out_tids, d_out_dist, d_out_rows);
+    if (gr.grouped) gx_launch_merge(ix, cq, (const uint64_t*)w.qx_part.p, d_perm, tq, k, gr, d_out_ids, d_out_tids, d_out_dist, d_out_rows);
+    else
+        hipLaunchKernelGGL(k_qual_exact_merge, dim3(cq), dim3(WAVE), 0, c->stream, (const uint64_t*)w.qx_part.p, d_perm + cq, d_perm + 2 * (size_t)cq, d_perm, tq, k,
+                           (const uint64_t*)ix->tids, d_out_ids, d_out_tids, d_out_dist, d_out_rows);
     prof_end(c, PK_RESORT, ev);
     VS_HIP(hipGetLastError());
     return VS_OK;
@@ -369,7 +391,7 @@ static int qx_run_chunk(vs_index* ix, const QxLists& ls, const float* d_queries,
 
 static int search_batch_qual_exact_impl(vs_index* ix, const float* queries, uint32_t nq, uint32_t k, const uint32_t* qual_slots, uint32_t* out_ids,
                                         uint64_t* out_tids, float* out_dist, uint32_t* out_rows, vs_qual_exact_stats* stats, bool on_device,
-                                        const char* what) {
+                                        const char* what, const GroupRule& gr = GroupRule{}) {
     VS_REQUIRE(qual_slots, "%s: qual_slots is NULL", what);
     VS_REQUIRE(out_rows, "%s: out_rows is NULL", what);
     VS_REQUIRE(k >= 1 && k <= 64, "%s: k %u outside [1,64]", what, k);
@@ -384,6 +406,7 @@ static int search_batch_qual_exact_impl(vs_index* ix, const float* queries, uint
         vs_set_error("%s: needs the vector column on the device", what);
         return VS_ERR_STATE;
     }
+    if (gr.grouped) VS_TRY(group_check(ix, what, k, gr.per_group));
     vs_ctx* c = ix->ctx;
     VS_HIP(hipSetDevice(c->device));
     std::vector<uint32_t> slots(nq);
@@ -393,7 +416,7 @@ static int search_batch_qual_exact_impl(vs_index* ix, const float* queries, uint
     double density = 1.0;
     VS_TRY(qual_check_slots(ix, what, slots.data(), nq, &all_zero, &density));
     vs_qual_exact_stats st{};
-    const uint32_t tq = qx_tile_queries(ix, k, std::max<uint32_t>(env_u32("VS_QUAL_EXACT_TQ", VS_QX_TQ), 1));
+    const uint32_t tq = qx_tile_queries(ix, k, std::max<uint32_t>(env_u32("VS_QUAL_EXACT_TQ", gr.grouped ? VS_GX_TQ : VS_QX_TQ), 1));
     st.tile_queries = tq;
     if (stats) *stats = st;
     if (nq == 0) return VS_OK;
@@ -414,14 +437,14 @@ static int search_batch_qual_exact_impl(vs_index* ix, const float* queries, uint
         const uint32_t cq = std::min(chunk, nq - q0);
         if (on_device) {
             VS_TRY(qx_run_chunk(ix, ls, queries + (size_t)q0 * dim, slots.data() + q0, cq, k, tq, out_ids ? out_ids + (size_t)q0 * k : nullptr,
-                                out_tids ? out_tids + (size_t)q0 * k : nullptr, out_dist ? out_dist + (size_t)q0 * k : nullptr, out_rows + q0, &st));
+                                out_tids ? out_tids + (size_t)q0 * k : nullptr, out_dist ? out_dist + (size_t)q0 * k : nullptr, out_rows + q0, &st, gr));
             VS_HIP(hipStreamSynchronize(c->stream));  // (the next chunk's tables go into the buffers this one reads)
             continue;
         }
         char* ob = (char*)w.qual_out.p;
         VS_TRY(vs_dev_upload(c, w.raw_q.p, queries + (size_t)q0 * dim, (size_t)cq * dim * 4));
         VS_TRY(qx_run_chunk(ix, ls, (const float*)w.raw_q.p, slots.data() + q0, cq, k, tq, out_ids ? (uint32_t*)ob : nullptr,
-                            out_tids ? (uint64_t*)(ob + o_tids) : nullptr, out_dist ? (float*)(ob + o_dist) : nullptr, (uint32_t*)(ob + o_rows), &st));
+                            out_tids ? (uint64_t*)(ob + o_tids) : nullptr, out_dist ? (float*)(ob + o_dist) : nullptr, (uint32_t*)(ob + o_rows), &st, gr));
         if (out_ids) VS_TRY(vs_dev_download(c, out_ids + (size_t)q0 * k, ob, (size_t)cq * k * 4));
         if (out_tids) VS_TRY(vs_dev_download(c, out_tids + (size_t)q0 * k, ob + o_tids, (size_t)cq * k * 8));
         if (out_dist) VS_TRY(vs_dev_download(c, out_dist + (size_t)q0 * k, ob + o_dist, (size_t)cq * k * 4));

@@ -887,10 +887,8 @@ class DiskAnnIndex:
         check(self._L.vs_search_batch_dev_grouped_finish(self.h, C.byref(st), C.byref(qst)))
         return st.as_dict(), qst.as_dict()
 
-    def search_batch_qual_exact(self, queries, qual_slots, k=10):
-        """For each query: the exact k nearest rows among those that pass the qualifier in qual_slots[q] (0: every node), are not
-        deleted and are not hidden by the mask in force, ascending by (distance, node id); no graph is walked -> ids, tids, dist
-        [nq, k] (past the rows returned: INVALID / 0 / NaN), rows [nq], stats (_lib.QualExactStats as a dict)."""
+    def _qual_topk(self, fn, st, queries, qual_slots, k, *after_k):
+        """the host form of the exact / flat qualified calls: fn(h, queries, nq, k, *after_k, slots, ids, tids, dist, rows, stats)"""
         q = np.ascontiguousarray(queries, np.float32).reshape(-1, self.desc.dim_full)
         nq = q.shape[0]
         sl = np.ascontiguousarray(qual_slots, np.uint32).ravel()
@@ -901,9 +899,14 @@ class DiskAnnIndex:
         tids = np.empty((nq, k), np.uint64)
         dist = np.empty((nq, k), np.float32)
         rows = np.empty(max(nq, 1), np.uint32)
-        st = _lib.QualExactStats()
-        check(self._L.vs_search_batch_qual_exact(self.h, _p(q), nq, k, _p(sl), _p(ids), _p(tids), _p(dist), _p(rows), C.byref(st)))
+        check(fn(self.h, _p(q), nq, k, *after_k, _p(sl), _p(ids), _p(tids), _p(dist), _p(rows), C.byref(st)))
         return ids, tids, dist, rows[:nq], st.as_dict()
+
+    def search_batch_qual_exact(self, queries, qual_slots, k=10):
+        """For each query: the exact k nearest rows among those that pass the qualifier in qual_slots[q] (0: every node), are not
+        deleted and are not hidden by the mask in force, ascending by (distance, node id); no graph is walked -> ids, tids, dist
+        [nq, k] (past the rows returned: INVALID / 0 / NaN), rows [nq], stats (_lib.QualExactStats as a dict)."""
+        return self._qual_topk(self._L.vs_search_batch_qual_exact, _lib.QualExactStats(), queries, qual_slots, k)
 
     def search_batch_qual_exact_dev(self, d_queries, nq, k, d_qual_slots, d_out_ids, d_out_rows, d_out_tids=None, d_out_dist=None):
         """the device-resident form: every pointer is device memory; synchronous on return -> stats"""
@@ -917,25 +920,39 @@ class DiskAnnIndex:
         `rescore` smallest by (Hamming distance of the SBQ codes, node id), and of those the k nearest by (exact distance, node id); no
         graph is walked -> ids, tids, dist [nq, k] (past the rows returned: INVALID / 0 / NaN), rows [nq], stats (_lib.QualFlatStats as
         a dict).  With rescore >= the rows that qualify: the rows of search_batch_qual_exact."""
-        q = np.ascontiguousarray(queries, np.float32).reshape(-1, self.desc.dim_full)
-        nq = q.shape[0]
-        sl = np.ascontiguousarray(qual_slots, np.uint32).ravel()
-        if sl.shape != (nq,):
-            raise ValueError(f"qual_slots must have shape ({nq},), got {sl.shape}")
-        sl = sl if nq else np.zeros(1, np.uint32)
-        ids = np.empty((nq, k), np.uint32)
-        tids = np.empty((nq, k), np.uint64)
-        dist = np.empty((nq, k), np.float32)
-        rows = np.empty(max(nq, 1), np.uint32)
-        st = _lib.QualFlatStats()
-        check(self._L.vs_search_batch_qual_flat(self.h, _p(q), nq, k, rescore, _p(sl), _p(ids), _p(tids), _p(dist), _p(rows), C.byref(st)))
-        return ids, tids, dist, rows[:nq], st.as_dict()
+        return self._qual_topk(self._L.vs_search_batch_qual_flat, _lib.QualFlatStats(), queries, qual_slots, k, rescore)
 
     def search_batch_qual_flat_dev(self, d_queries, nq, k, rescore, d_qual_slots, d_out_ids, d_out_rows, d_out_tids=None, d_out_dist=None):
         """the device-resident form: every pointer is device memory; synchronous on return -> stats"""
         st = _lib.QualFlatStats()
         check(self._L.vs_search_batch_qual_flat_dev(self.h, d_queries, nq, k, rescore, d_qual_slots, d_out_ids, d_out_tids, d_out_dist,
                                                     d_out_rows, C.byref(st)))
+        return st.as_dict()
+
+    def search_batch_qual_exact_grouped(self, queries, qual_slots, k=10, per_group=1):
+        """search_batch_qual_exact under the group rule: of the qualifying rows in (distance, node id) order, the first k that are
+        not capped out — a row is capped out when per_group rows of its group come before it (GROUP_NONE: never) -> the same shapes."""
+        return self._qual_topk(self._L.vs_search_batch_qual_exact_grouped, _lib.QualExactStats(), queries, qual_slots, k, per_group)
+
+    def search_batch_qual_exact_grouped_dev(self, d_queries, nq, k, per_group, d_qual_slots, d_out_ids, d_out_rows, d_out_tids=None, d_out_dist=None):
+        """the device-resident form: every pointer is device memory; synchronous on return -> stats"""
+        st = _lib.QualExactStats()
+        check(self._L.vs_search_batch_qual_exact_grouped_dev(self.h, d_queries, nq, k, per_group, d_qual_slots, d_out_ids, d_out_tids, d_out_dist,
+                                                             d_out_rows, C.byref(st)))
+        return st.as_dict()
+
+    def search_batch_qual_flat_grouped(self, queries, qual_slots, k=10, per_group=1, rescore=50):
+        """search_batch_qual_flat under the group rule: the `rescore` candidates are chosen by Hamming distance WITHOUT the rule, the
+        rule is applied to them in (exact distance, node id) order -> the same shapes; fewer than k rows come back when the candidates
+        fall into few groups (rows says so).  With rescore >= the rows that qualify: the rows of search_batch_qual_exact_grouped."""
+        return self._qual_topk(self._L.vs_search_batch_qual_flat_grouped, _lib.QualFlatStats(), queries, qual_slots, k, per_group, rescore)
+
+    def search_batch_qual_flat_grouped_dev(self, d_queries, nq, k, per_group, rescore, d_qual_slots, d_out_ids, d_out_rows, d_out_tids=None,
+                                           d_out_dist=None):
+        """the device-resident form: every pointer is device memory; synchronous on return -> stats"""
+        st = _lib.QualFlatStats()
+        check(self._L.vs_search_batch_qual_flat_grouped_dev(self.h, d_queries, nq, k, per_group, rescore, d_qual_slots, d_out_ids, d_out_tids,
+                                                            d_out_dist, d_out_rows, C.byref(st)))
         return st.as_dict()
 
     def autotune(self, d_queries, nq, search_list_size, rescore, k, d_qlabels=None, d_qlabel_off=None, reps=2, skip=()):
