@@ -8,8 +8,9 @@ import pytest
 
 from test_emu_qual import EMU_DIR, ROOT, emu_lib  # noqa: F401  (the fixture that builds the interpreter library)
 
-# states 1, rule 3 x 16, identities 2, composition 1, ties 1, fallback + replay 4, plain 1, device entry 1, chunks 1, labels 1, insert 1, compact 1
-N_CASES = 63
+# states 1, rule 3 x 16, identities 2, composition 1, ties 1, fallback + replay 4, tombstones and a mask 4, plain 1, device entry 1, chunks 1,
+# labels 1, insert 1, compact 1
+N_CASES = 67
 RANDOMISED = "test_rule and forty or test_a_tie_heavy or test_the_fallback or test_a_qualifier"
 N_RANDOMISED = 16 + 1 + 4 + 1
 

@@ -143,6 +143,36 @@ def test_the_fallback_kernel_and_the_forced_replay(ix_a, how):
     assert how != "above_the_line" or got[7]["first_pops"] == mp  # (else round 1 would have fitted the fused kernel)
 
 
+@pytest.mark.parametrize("how", ["fused", "unfused", "forced_replay", "rescore_0"])
+def test_tombstones_and_a_mask_do_not_count_against_a_group(gpu_ctx, oracle, how):
+    """5 % of the rows deleted and 10 % hidden by a mask: such a row is no row of the scan, so it takes no place in its group.  With
+    rescore 0 the reference never fetches the heap, so the mask hides nothing there; a tombstone is no row of the scan even so."""
+    ti, g, q = QC.index_a(deleted_frac=0.05), layout("forty"), QC.index_a(deleted_frac=0.05).queries(NQ)
+    vis = (np.random.default_rng(41).random(ti.n) > 0.10).astype(np.uint8)
+    pg, k, mp, rs = 1, 10, 128, 0 if how == "rescore_0" else 10
+    opts = {"unfused": dict(VS_RERANK_FUSED="0"), "forced_replay": dict(VS_RERANK_FUSED="2")}.get(how, {})
+    with uploaded(gpu_ctx, ti) as ix:
+        # precondition, on the reference alone: with the filter off — no mask, the same graph without a tombstone — the rows differ,
+        # and rows the filter takes out were among them
+        unfiltered = QC.index_a()
+        assert (unfiltered.oracle.nbrs == ti.oracle.nbrs).all() and (unfiltered.tids != ti.tids).any()
+        off = expect(unfiltered.oracle, ti.tids, q, g, pg, k, mp, A_L, rs)
+        unmasked = expect(ti.oracle, ti.tids, q, g, pg, k, mp, A_L, rs)
+        ti.oracle.set_visibility(vis)
+        exp = expect(ti.oracle, ti.tids, q, g, pg, k, mp, A_L, rs)
+        dead, hidden = (ti.tids & np.uint64(0xFFFF)) == 0, vis == 0
+        took, kept = off[0][off[0] != INV], exp[0][exp[0] != INV]
+        assert (off[0] != exp[0]).any() and dead[took].any() and hidden[took].any() and not dead[kept].any()
+        if rs:
+            assert (unmasked[0] != exp[0]).any() and not hidden[kept].any()
+        else:
+            assert (unmasked[0] == exp[0]).all() and (unmasked[4] == exp[4]).all() and hidden[kept].any()
+        ix.set_visibility(vis)
+        ix.groups_put(g)
+        with options(**opts):
+            check(run(ix, q, k, pg, mp, A_L, rs), exp, mp)
+
+
 def test_a_plain_index(gpu_ctx, oracle):
     from test_gpu_zy_plain import PlainIndex
     pi = PlainIndex(n=1000, dim=96, R=24, distance=O.L2, seed=120, kind="gauss", dim_index=None)
