@@ -155,6 +155,9 @@ int vs_index_last_search_info(const vs_index* idx, vs_search_info* out);
  * VS_QUAL_EXACT_SLICES: the slices vs_search_batch_qual_exact cuts every slot's row list into (unset / 0: as many as fill the device;
  * never more than the list has 32-row passes).  VS_QUAL_EXACT_TQ: the scans of one tile (1, 2, 4, 8, 16; default 8).  Cost choices
  * both: no row, distance bit or count depends on them.
+ * VS_QUAL_WIDE_WS_MB: the workspace of one chunk of tiles of vs_search_batch_qual_exact_wide in MiB — 32-bit keys per (scan, list
+ * place) and the histograms (default 1024; a chunk holds at least one tile, so 0 gives every tile a chunk of its own).  A cost choice:
+ * no row depends on it.
  * VS_GROUP_FIRST_POPS: the pops of the first round of vs_search_batch_grouped (clamped to [k, max_pops]; unset / 0: the rule of
  * vs_search_batch_qual, VS_QUAL_FIRST_POPS included).  A cost choice: no row, count or state depends on it. */
 int vs_set_option(const char* name, const char* value);
@@ -1520,7 +1523,9 @@ typedef struct vs_datagen_params {
 } vs_datagen_params;
 /* fills d_out[row_begin .. row_begin+rows) (row stride = dim floats) with rows `first_row + i` of the stream */
 int vs_datagen_fill(vs_ctx* ctx, const vs_datagen_params* p, uint64_t first_row, uint64_t rows, float* d_out);
-/* exact brute-force f32 top-k on the device (ground truth for recall): d_queries [nq][dim_full] raw */
+/* exact brute-force f32 top-k on the device (ground truth for recall): d_queries [nq][dim_full] raw.  k in [1, 64]; for the ground
+ * truth at k up to VS_QUAL_WIDE_MAX_K (recall@100, recall@1000) call vs_search_batch_qual_exact_wide_dev with every slot 0: the same
+ * rows in the same order with the same distance bits (that call also leaves out the rows a visibility mask in force hides). */
 int vs_bruteforce_topk(vs_index* idx, const float* d_queries, uint32_t nq, uint32_t k, uint32_t* out_ids, float* out_dist);
 
 /* ---- qualified scans: the first k rows of a scan that pass a per-scan node bitmap (vs_qual.h) ----
@@ -1743,6 +1748,45 @@ int vs_search_batch_qual_flat(vs_index* idx, const float* queries, uint32_t nq, 
 int vs_search_batch_qual_flat_dev(vs_index* idx, const float* d_queries, uint32_t nq, uint32_t k, uint32_t rescore,
                                   const uint32_t* d_qual_slots, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist,
                                   uint32_t* d_out_rows, vs_qual_flat_stats* stats /* may be NULL */);
+
+/* ---- wide k: the exact and the flat qualified top-k for k up to 4096, selection by counting (vs_qual_wide.h) ----
+ * `LIMIT 100`, a page of 500, the 1 000 candidates a cross-encoder reranks, under a selective WHERE: vs_search_batch_qual_exact and
+ * vs_search_batch_qual_flat keep their rows as one entry per lane of a wave and stop at k = 64.  These calls are their twins for
+ * k in [1, VS_QUAL_WIDE_MAX_K]; the prototypes and the stats are those of the narrow calls, argument for argument.
+ *
+ * SEMANTICS.  Word for word those of vs_search_batch_qual_exact and vs_search_batch_qual_flat above: the set C and, for the flat call,
+ * S; the order (f32::total_cmp key of the distance, node id); the distance bits of the rerank; the VS_INVALID_NODE / 0 / NaN tail and
+ * out_rows; HOST pointers for the plain form, DEVICE pointers and a synchronous return for _dev; nq = 0 returns VS_OK.  Only the
+ * ranges differ: k in [1, VS_QUAL_WIDE_MAX_K], and for the flat call rescore in [k, VS_QUAL_FLAT_MAX_RESCORE].
+ * IDENTITIES, bit for bit.  For k <= 64 a wide call returns what its narrow call returns.  With rescore >= |C| of a scan the flat wide
+ * call returns the exact wide call's rows.  With every slot 0 the exact wide call is vs_bruteforce_topk's ground truth at k up to
+ * VS_QUAL_WIDE_MAX_K.
+ * REFUSALS.  Those of the narrow calls, each before anything is launched or written, with VS_QUAL_WIDE_MAX_K as the bound on k.
+ * HOW.  No list of k entries is kept while the rows are read.  The exact call runs the narrow call's row loop over the same lists,
+ * tiles and slices and stores the 32-bit key of every (scan, list place), counting its leading 10 bits in a histogram per scan; one
+ * workgroup per scan then finds the key of the k-th smallest entry by radix selection (10 + 11 + 11 bits, the later levels by
+ * re-reading the scan's keys), emits in one ordered pass the places below that key and the first places at it — the list ascends by
+ * node id, which is the tie rule — and sorts the <= 4096 survivors on chip.  A place's slot is a popcount of the emitted places before
+ * it and a histogram count is a sum: the result is reproducible.  The flat call keeps its Hamming selection and the device rerank and
+ * ends in the same on-chip sort over the `rescore` candidates.  vs_qual_exact_stats and vs_qual_flat_stats keep their meaning.
+ * Options, cost choices all — no row depends on them: VS_QUAL_EXACT_TQ / VS_QUAL_EXACT_SLICES and VS_QUAL_FLAT_TQ / VS_QUAL_FLAT_SLICES
+ * / VS_QUAL_FLAT_WS_MB as for the narrow calls (the exact wide tile is the largest of 8, 4, 2, 1 scans not above the option whose
+ * queries and histograms fit the LDS), VS_QUAL_WIDE_WS_MB (the keys and histograms of one chunk of tiles in MiB, default 1024; 4 bytes
+ * per (scan, list place): slot 0 of a 4 M row index is 16 MB per scan).
+ * Not built: the grouped forms at wide k, pools, the broker, the shm server, vs_multi, label keys and per-scan visibility slots. */
+#define VS_QUAL_WIDE_MAX_K 4096
+int vs_search_batch_qual_exact_wide(vs_index* idx, const float* queries, uint32_t nq, uint32_t k, const uint32_t* qual_slots,
+                                    uint32_t* out_ids, uint64_t* out_tids, float* out_dist, /* [nq][k], may be NULL */
+                                    uint32_t* out_rows /* [nq] */, vs_qual_exact_stats* stats /* may be NULL */);
+int vs_search_batch_qual_exact_wide_dev(vs_index* idx, const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_qual_slots,
+                                        uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, uint32_t* d_out_rows,
+                                        vs_qual_exact_stats* stats /* may be NULL */);
+int vs_search_batch_qual_flat_wide(vs_index* idx, const float* queries, uint32_t nq, uint32_t k, uint32_t rescore,
+                                   const uint32_t* qual_slots, uint32_t* out_ids, uint64_t* out_tids, float* out_dist, /* [nq][k], may be NULL */
+                                   uint32_t* out_rows /* [nq] */, vs_qual_flat_stats* stats /* may be NULL */);
+int vs_search_batch_qual_flat_wide_dev(vs_index* idx, const float* d_queries, uint32_t nq, uint32_t k, uint32_t rescore,
+                                       const uint32_t* d_qual_slots, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist,
+                                       uint32_t* d_out_rows, vs_qual_flat_stats* stats /* may be NULL */);
 
 /* ---- grouped scans: the first k rows of a scan with at most per_group rows per group (vs_group.h) ----
  * A row of a chunked corpus is a chunk of a document: "the 10 nearest documents" (DISTINCT ON (doc_id)) and "the 10 nearest chunks, at

@@ -400,6 +400,10 @@ SYMBOLS = {
     "vs_search_batch_qual_exact_dev": (_i, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualExactStats)]),
     "vs_search_batch_qual_flat": (_i, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualFlatStats)]),
     "vs_search_batch_qual_flat_dev": (_i, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualFlatStats)]),
+    "vs_search_batch_qual_exact_wide": (_i, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualExactStats)]),
+    "vs_search_batch_qual_exact_wide_dev": (_i, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualExactStats)]),
+    "vs_search_batch_qual_flat_wide": (_i, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualFlatStats)]),
+    "vs_search_batch_qual_flat_wide_dev": (_i, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualFlatStats)]),
     "vs_search_batch_qual_exact_grouped": (_i, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualExactStats)]),
     "vs_search_batch_qual_exact_grouped_dev": (_i, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualExactStats)]),
     "vs_search_batch_qual_flat_grouped": (_i, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(QualFlatStats)]),

@@ -505,7 +505,8 @@ extern "C" void vs_index_free(vs_index* ix) {
                       &w.stream_ham, &w.stream_cnt, &w.stats, &w.status, &w.rr_dist, &w.out_ids, &w.out_tids,
                       &w.out_dist, &w.resort_heap, &w.raw_q, &w.misc, &w.q_index, &w.red, &w.order_work, &w.order_perm, &w.order_labels, &w.vis_slots,
                       &w.qual_q, &w.qual_map, &w.qual_lab, &w.qual_laboff, &w.qual_slots, &w.qual_out,
-                      &w.qx_list, &w.qx_counts, &w.qx_tab, &w.qx_part, &w.qf_tab, &w.qf_ham, &w.qf_hist, &w.qf_cand};
+                      &w.qx_list, &w.qx_counts, &w.qx_tab, &w.qx_part, &w.qf_tab, &w.qf_ham, &w.qf_hist, &w.qf_cand,
+                      &w.qw_tab, &w.qw_keys, &w.qw_hist};
     for (DevBuf* b : bufs) devbuf_free(*b);
     if (!ix->is_view) vs_vis_base_free(ix);
     if (!ix->is_view) vs_qual_drop_all(ix);

@@ -1429,5 +1429,7 @@ extern "C" int vs_search_batch_dev_finish(vs_index* ix, vs_stats* stats) {
 #include "vs_qual_exact.h"
 // vs_search_batch_qual_flat: the SBQ top-M over a qualifier's rows, then the exact top-k of those (kernels and host code)
 #include "vs_qual_flat.h"
+// vs_search_batch_qual_exact_wide / vs_search_batch_qual_flat_wide: the two calls above for k up to 4096, selection by counting
+#include "vs_qual_wide.h"
 // vs_search_batch_qual_exact_grouped / vs_search_batch_qual_flat_grouped: the two calls above under a group rule (kernels and entry points)
 #include "vs_qual_group.h"

@@ -336,7 +336,8 @@ struct SearchWorkspace {
         qual_q, qual_map, qual_lab, qual_laboff,  // vs_search_batch_qual: the gathered queries, scan numbers and label keys of a later round
         qual_slots, qual_out,                     // ... the slots of a host batch, and its rows, counts and states before they go back
         qx_list, qx_counts, qx_tab, qx_part,      // vs_search_batch_qual_exact (vs_qual_exact.h): row lists, their counts, scan + tile tables, partial lists
-        qf_tab, qf_ham, qf_hist, qf_cand;         // vs_search_batch_qual_flat (vs_qual_flat.h): scan + tile tables, 16-bit distances, histograms, candidates + distances
+        qf_tab, qf_ham, qf_hist, qf_cand,         // vs_search_batch_qual_flat (vs_qual_flat.h): scan + tile tables, 16-bit distances, histograms, candidates + distances
+        qw_tab, qw_keys, qw_hist;                 // vs_search_batch_qual_exact_wide (vs_qual_wide.h): scan + tile tables, 32-bit keys, leading-digit histograms
     uint32_t order_nq = 0;         // scans of the last batch's rerank order in order_perm (0: it took the scans' own order)
     // what order_labels was built from: the seed rows s * lab_step for s < lab_S of the codes at epoch lab_epoch (vs_index::codes_epoch)
     uint32_t lab_rows = 0, lab_S = 0, lab_step = 0;

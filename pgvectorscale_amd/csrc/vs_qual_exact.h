@@ -389,12 +389,20 @@ static int qx_run_chunk(vs_index* ix, const QxLists& ls, const float* d_queries,
     return VS_OK;
 }
 
+// The same entry checks, lists and chunks of scans for k up to VS_QUAL_WIDE_MAX_K (vs_qual_wide.h, included after vs_qual_flat.h):
+// qw_run_chunk in place of qx_run_chunk, over a tile and a chunk of scans of its own choosing.
+static uint32_t qw_tile_queries(const vs_index* ix, uint32_t want);
+static uint32_t qw_chunk_scans(uint32_t nq, uint32_t k);
+static int qw_run_chunk(vs_index* ix, const QxLists& ls, const float* d_queries, const uint32_t* slots, uint32_t cq, uint32_t k, uint32_t tq,
+                        uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, uint32_t* d_out_rows, vs_qual_exact_stats* st);
+
 static int search_batch_qual_exact_impl(vs_index* ix, const float* queries, uint32_t nq, uint32_t k, const uint32_t* qual_slots, uint32_t* out_ids,
                                         uint64_t* out_tids, float* out_dist, uint32_t* out_rows, vs_qual_exact_stats* stats, bool on_device,
-                                        const char* what, const GroupRule& gr = GroupRule{}) {
+                                        const char* what, const GroupRule& gr = GroupRule{}, bool wide = false) {
     VS_REQUIRE(qual_slots, "%s: qual_slots is NULL", what);
     VS_REQUIRE(out_rows, "%s: out_rows is NULL", what);
-    VS_REQUIRE(k >= 1 && k <= 64, "%s: k %u outside [1,64]", what, k);
+    const uint32_t max_k = wide ? VS_QUAL_WIDE_MAX_K : 64;
+    VS_REQUIRE(k >= 1 && k <= max_k, "%s: k %u outside [1,%u]", what, k, max_k);
     VS_REQUIRE(ix, "%s: index is NULL", what);
     VS_REQUIRE(nq == 0 || queries, "%s: queries is NULL", what);
     VS_REQUIRE_OWNER(ix, what);
@@ -416,7 +424,8 @@ static int search_batch_qual_exact_impl(vs_index* ix, const float* queries, uint
     double density = 1.0;
     VS_TRY(qual_check_slots(ix, what, slots.data(), nq, &all_zero, &density));
     vs_qual_exact_stats st{};
-    const uint32_t tq = qx_tile_queries(ix, k, std::max<uint32_t>(env_u32("VS_QUAL_EXACT_TQ", gr.grouped ? VS_GX_TQ : VS_QX_TQ), 1));
+    const uint32_t tq_want = std::max<uint32_t>(env_u32("VS_QUAL_EXACT_TQ", gr.grouped ? VS_GX_TQ : VS_QX_TQ), 1);
+    const uint32_t tq = wide ? qw_tile_queries(ix, tq_want) : qx_tile_queries(ix, k, tq_want);
     st.tile_queries = tq;
     if (stats) *stats = st;
     if (nq == 0) return VS_OK;
@@ -425,8 +434,12 @@ static int search_batch_qual_exact_impl(vs_index* ix, const float* queries, uint
     st.lists = ls.slot.size();
     for (uint32_t m : ls.m) st.rows_listed += m;
     SearchWorkspace& w = ix->ws;
-    const uint32_t chunk = std::min<uint32_t>(nq, QX_CHUNK_SCANS);
+    const uint32_t chunk = wide ? qw_chunk_scans(nq, k) : std::min<uint32_t>(nq, QX_CHUNK_SCANS);
     const uint32_t dim = ix->d.dim_full;
+    auto run_chunk = [&](const float* d_q, const uint32_t* sl, uint32_t cq, uint32_t* o_ids, uint64_t* o_tid, float* o_dst, uint32_t* o_row) {
+        return wide ? qw_run_chunk(ix, ls, d_q, sl, cq, k, tq, o_ids, o_tid, o_dst, o_row, &st)
+                    : qx_run_chunk(ix, ls, d_q, sl, cq, k, tq, o_ids, o_tid, o_dst, o_row, &st, gr);
+    };
     // (host form) [chunk][k] ids | tids | distances, then [chunk] rows
     const size_t o_tids = (size_t)chunk * k * 4, o_dist = o_tids + (size_t)chunk * k * 8, o_rows = o_dist + (size_t)chunk * k * 4;
     if (!on_device) {
@@ -436,15 +449,15 @@ static int search_batch_qual_exact_impl(vs_index* ix, const float* queries, uint
     for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
         const uint32_t cq = std::min(chunk, nq - q0);
         if (on_device) {
-            VS_TRY(qx_run_chunk(ix, ls, queries + (size_t)q0 * dim, slots.data() + q0, cq, k, tq, out_ids ? out_ids + (size_t)q0 * k : nullptr,
-                                out_tids ? out_tids + (size_t)q0 * k : nullptr, out_dist ? out_dist + (size_t)q0 * k : nullptr, out_rows + q0, &st, gr));
+            VS_TRY(run_chunk(queries + (size_t)q0 * dim, slots.data() + q0, cq, out_ids ? out_ids + (size_t)q0 * k : nullptr,
+                             out_tids ? out_tids + (size_t)q0 * k : nullptr, out_dist ? out_dist + (size_t)q0 * k : nullptr, out_rows + q0));
             VS_HIP(hipStreamSynchronize(c->stream));  // (the next chunk's tables go into the buffers this one reads)
             continue;
         }
         char* ob = (char*)w.qual_out.p;
         VS_TRY(vs_dev_upload(c, w.raw_q.p, queries + (size_t)q0 * dim, (size_t)cq * dim * 4));
-        VS_TRY(qx_run_chunk(ix, ls, (const float*)w.raw_q.p, slots.data() + q0, cq, k, tq, out_ids ? (uint32_t*)ob : nullptr,
-                            out_tids ? (uint64_t*)(ob + o_tids) : nullptr, out_dist ? (float*)(ob + o_dist) : nullptr, (uint32_t*)(ob + o_rows), &st, gr));
+        VS_TRY(run_chunk((const float*)w.raw_q.p, slots.data() + q0, cq, out_ids ? (uint32_t*)ob : nullptr,
+                         out_tids ? (uint64_t*)(ob + o_tids) : nullptr, out_dist ? (float*)(ob + o_dist) : nullptr, (uint32_t*)(ob + o_rows)));
         if (out_ids) VS_TRY(vs_dev_download(c, out_ids + (size_t)q0 * k, ob, (size_t)cq * k * 4));
         if (out_tids) VS_TRY(vs_dev_download(c, out_tids + (size_t)q0 * k, ob + o_tids, (size_t)cq * k * 8));
         if (out_dist) VS_TRY(vs_dev_download(c, out_dist + (size_t)q0 * k, ob + o_dist, (size_t)cq * k * 4));

@@ -279,6 +279,9 @@ static void qf_launch_ham_any(const vs_index* ix, uint32_t tq, const QfHamArgs& 
 // k_qflat_final under a group rule (vs_qual_group.h, included after this file): the same candidates and distances
 static void gx_launch_final(const vs_index* ix, uint32_t cq, const uint32_t* d_cand, const uint32_t* d_cand_n, const float* d_dist, uint32_t rescore,
                             uint32_t k, const GroupRule& gr, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, uint32_t* d_out_rows);
+// ... and for k up to VS_QUAL_WIDE_MAX_K (vs_qual_wide.h, included after this file): k_qflat_final_wide sorts the candidates in LDS
+static void qw_launch_final(const vs_index* ix, uint32_t cq, const uint32_t* d_cand, const uint32_t* d_cand_n, const float* d_dist, uint32_t rescore,
+                            uint32_t k, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, uint32_t* d_out_rows);
 
 // a run of tiles whose distances and histograms fit the workspace budget together
 struct QfChunk {
@@ -287,10 +290,11 @@ struct QfChunk {
 };
 
 // One chunk of scans: cq scans whose raw queries, and whose outputs, are on the device; slots HOST.  Leaves its launches on the stream.
-// gr.grouped: k_qflat_final_grouped keeps the k best of the candidates under the rule; everything before it is the same.
+// gr.grouped: k_qflat_final_grouped keeps the k best of the candidates under the rule; wide: k_qflat_final_wide keeps the k <=
+// VS_QUAL_WIDE_MAX_K best; everything before it is the same.
 static int qf_run_chunk(vs_index* ix, const QxLists& ls, const float* d_queries, const uint32_t* slots, uint32_t cq, uint32_t k, uint32_t rescore,
                         uint32_t tq, uint32_t* d_out_ids, uint64_t* d_out_tids, float* d_out_dist, uint32_t* d_out_rows, vs_qual_flat_stats* st,
-                        const GroupRule& gr) {
+                        const GroupRule& gr, bool wide) {
     vs_ctx* c = ix->ctx;
     SearchWorkspace& w = ix->ws;
     const uint32_t bins = qf_bins(ix);
@@ -382,6 +386,7 @@ static int qf_run_chunk(vs_index* ix, const QxLists& ls, const float* d_queries,
     prof_end(c, PK_RERANK, ev);
     ev = prof_begin(c);
     if (gr.grouped) gx_launch_final(ix, cq, d_cand, d_cand_n, d_dist, rescore, k, gr, d_out_ids, d_out_tids, d_out_dist, d_out_rows);
+    else if (wide) qw_launch_final(ix, cq, d_cand, d_cand_n, d_dist, rescore, k, d_out_ids, d_out_tids, d_out_dist, d_out_rows);
     else
         hipLaunchKernelGGL(k_qflat_final, dim3(cq), dim3(WAVE), 0, c->stream, (const uint32_t*)d_cand, (const uint32_t*)d_cand_n, (const float*)d_dist, rescore, k,
                            (const uint64_t*)ix->tids, d_out_ids, d_out_tids, d_out_dist, d_out_rows);
@@ -392,10 +397,11 @@ static int qf_run_chunk(vs_index* ix, const QxLists& ls, const float* d_queries,
 
 static int search_batch_qual_flat_impl(vs_index* ix, const float* queries, uint32_t nq, uint32_t k, uint32_t rescore, const uint32_t* qual_slots,
                                        uint32_t* out_ids, uint64_t* out_tids, float* out_dist, uint32_t* out_rows, vs_qual_flat_stats* stats,
-                                       bool on_device, const char* what, const GroupRule& gr = GroupRule{}) {
+                                       bool on_device, const char* what, const GroupRule& gr = GroupRule{}, bool wide = false) {
     VS_REQUIRE(qual_slots, "%s: qual_slots is NULL", what);
     VS_REQUIRE(out_rows, "%s: out_rows is NULL", what);
-    VS_REQUIRE(k >= 1 && k <= 64, "%s: k %u outside [1,64]", what, k);
+    const uint32_t max_k = wide ? VS_QUAL_WIDE_MAX_K : 64;
+    VS_REQUIRE(k >= 1 && k <= max_k, "%s: k %u outside [1,%u]", what, k, max_k);
     VS_REQUIRE(rescore >= k && rescore <= VS_QUAL_FLAT_MAX_RESCORE, "%s: rescore %u outside [k = %u, %d]", what, rescore, k, VS_QUAL_FLAT_MAX_RESCORE);
     VS_REQUIRE(ix, "%s: index is NULL", what);
     VS_REQUIRE(nq == 0 || queries, "%s: queries is NULL", what);
@@ -448,14 +454,14 @@ static int search_batch_qual_flat_impl(vs_index* ix, const float* queries, uint3
         const uint32_t cq = std::min(chunk, nq - q0);
         if (on_device) {
             VS_TRY(qf_run_chunk(ix, ls, queries + (size_t)q0 * dim, slots.data() + q0, cq, k, rescore, tq, out_ids ? out_ids + (size_t)q0 * k : nullptr,
-                                out_tids ? out_tids + (size_t)q0 * k : nullptr, out_dist ? out_dist + (size_t)q0 * k : nullptr, out_rows + q0, &st, gr));
+                                out_tids ? out_tids + (size_t)q0 * k : nullptr, out_dist ? out_dist + (size_t)q0 * k : nullptr, out_rows + q0, &st, gr, wide));
             VS_HIP(hipStreamSynchronize(c->stream));  // (the next chunk's tables go into the buffers this one reads)
             continue;
         }
         char* ob = (char*)w.qual_out.p;
         VS_TRY(vs_dev_upload(c, w.raw_q.p, queries + (size_t)q0 * dim, (size_t)cq * dim * 4));
         VS_TRY(qf_run_chunk(ix, ls, (const float*)w.raw_q.p, slots.data() + q0, cq, k, rescore, tq, out_ids ? (uint32_t*)ob : nullptr,
-                            out_tids ? (uint64_t*)(ob + o_tids) : nullptr, out_dist ? (float*)(ob + o_dist) : nullptr, (uint32_t*)(ob + o_rows), &st, gr));
+                            out_tids ? (uint64_t*)(ob + o_tids) : nullptr, out_dist ? (float*)(ob + o_dist) : nullptr, (uint32_t*)(ob + o_rows), &st, gr, wide));
         if (out_ids) VS_TRY(vs_dev_download(c, out_ids + (size_t)q0 * k, ob, (size_t)cq * k * 4));
         if (out_tids) VS_TRY(vs_dev_download(c, out_tids + (size_t)q0 * k, ob + o_tids, (size_t)cq * k * 8));
         if (out_dist) VS_TRY(vs_dev_download(c, out_dist + (size_t)q0 * k, ob + o_dist, (size_t)cq * k * 4));

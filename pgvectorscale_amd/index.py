@@ -929,6 +929,30 @@ class DiskAnnIndex:
                                                     d_out_rows, C.byref(st)))
         return st.as_dict()
 
+    def search_batch_qual_exact_wide(self, queries, qual_slots, k=100):
+        """search_batch_qual_exact for k up to 4096 (VS_QUAL_WIDE_MAX_K): the same rows, order, distance bits, tail and shapes; for
+        k <= 64 what search_batch_qual_exact returns, bit for bit; with every slot 0 the brute-force ground truth at that k."""
+        return self._qual_topk(self._L.vs_search_batch_qual_exact_wide, _lib.QualExactStats(), queries, qual_slots, k)
+
+    def search_batch_qual_exact_wide_dev(self, d_queries, nq, k, d_qual_slots, d_out_ids, d_out_rows, d_out_tids=None, d_out_dist=None):
+        """the device-resident form: every pointer is device memory; synchronous on return -> stats"""
+        st = _lib.QualExactStats()
+        check(self._L.vs_search_batch_qual_exact_wide_dev(self.h, d_queries, nq, k, d_qual_slots, d_out_ids, d_out_tids, d_out_dist, d_out_rows,
+                                                          C.byref(st)))
+        return st.as_dict()
+
+    def search_batch_qual_flat_wide(self, queries, qual_slots, k=100, rescore=500):
+        """search_batch_qual_flat for k up to 4096 and rescore in [k, 4096]: the same candidates, rows, order, distance bits, tail
+        and shapes.  With rescore >= the rows that qualify: the rows of search_batch_qual_exact_wide."""
+        return self._qual_topk(self._L.vs_search_batch_qual_flat_wide, _lib.QualFlatStats(), queries, qual_slots, k, rescore)
+
+    def search_batch_qual_flat_wide_dev(self, d_queries, nq, k, rescore, d_qual_slots, d_out_ids, d_out_rows, d_out_tids=None, d_out_dist=None):
+        """the device-resident form: every pointer is device memory; synchronous on return -> stats"""
+        st = _lib.QualFlatStats()
+        check(self._L.vs_search_batch_qual_flat_wide_dev(self.h, d_queries, nq, k, rescore, d_qual_slots, d_out_ids, d_out_tids, d_out_dist,
+                                                         d_out_rows, C.byref(st)))
+        return st.as_dict()
+
     def search_batch_qual_exact_grouped(self, queries, qual_slots, k=10, per_group=1):
         """search_batch_qual_exact under the group rule: of the qualifying rows in (distance, node id) order, the first k that are
         not capped out — a row is capped out when per_group rows of its group come before it (GROUP_NONE: never) -> the same shapes."""
